@@ -10,7 +10,11 @@ checkpoints).  One "step" = one pass of the hot path over one batch: normalise +
 ln_post -> projection -> L2, i.e. exactly mq_encode_image_u8; for N > 1 the [256, 512] fp32 shards are then all-gathered over RCCL
 (the only collective on the path).  Work per GPU is fixed -> weak scaling.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+    python bench.py ... --dump-outputs DIR      (also writes the last timed step's embeddings as DIR/<name>.npy, float32)
+    python bench.py ... --full                  (also everything below: instrumented steps, CPU baselines, other workloads)
+
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the contract keys (`value`, `ms_per_step`, ...):
+the line's headline needs nothing else.  With --full it also carries
   roofline        — the dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs / HIP-event time of its launches
   cpu_baseline    — the CPU fp32 oracle (oracle/towers.py) run with the reference's 16-item batch loop (s2_inference.py:135-146) on a
                     bounded sample; `cores` = the torch thread count of the fastest run of a thread ladder, `host_hw_threads` / `cpu_quota` = what the box offers
@@ -85,10 +89,15 @@ def parse_args():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
                     help="GEMM operand type of the encoder blocks (fp8 = e4m3, BASELINE config 5; not the headline metric)")
     ap.add_argument("--merge-images", type=int, default=None, help="add_documents_stream: images per merged tower call (0 = no cross-request merging; default: marqo_amd.ingest.MERGE_IMAGES)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: roofline (instrumented steps + sustained-peak probe), "
+                         "CPU baselines, the bf16 twin, e2e_vectorise and the `also` workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; a fixed seeded row sample beyond 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the headline baseline sample")
-    ap.add_argument("--no-extras", action="store_true", help="skip e2e_vectorise and the `also` workloads (profiling runs)")
-    ap.add_argument("--no-also", action="store_true", help="keep e2e_vectorise but skip the `also` workloads (host-side A/B runs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip e2e_vectorise and the `also` workloads (profiling runs)")
+    ap.add_argument("--no-also", action="store_true", help="--full: keep e2e_vectorise but skip the `also` workloads (host-side A/B runs)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py spawns its own ranks (0 = pick a free one)")
     return ap.parse_args()
 
@@ -138,6 +147,8 @@ def run_stub(args, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert out.shape[0] == batch * world and sorted(set(out[:, 0].tolist())) == [float(r) for r in range(world)]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": out.numpy()})
     if rank == 0:
         print(json.dumps({"metric": "embeddings/sec", "value": round(batch * world * args.steps / elapsed, 1), "unit": "embeddings/s", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
@@ -380,6 +391,22 @@ def timed(run, steps, warmup, fence):
         out = run()
     fence()
     return time.perf_counter() - t0, out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """{name: array} of the last timed step -> dirname/<name>.npy in float32.  Beyond DUMP_MAX_BYTES in all, every array keeps the same share
+    of its rows, chosen by a fixed seed (sorted), so that two builds dump the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_MAX_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 _SUSTAINED = {}
@@ -699,6 +726,9 @@ def run_ingest(args, dev, rank, world, dist, lib, L):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert len(out) == 2 * docs
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"text_embeddings": np.stack([out[(i, "t")] for i in range(docs)]),
+                                         "image_embeddings": np.stack([out[(i, "i")] for i in range(docs)])})
     n_emb = 2 * docs
     value = n_emb * args.steps / elapsed
     gf = (varch.gflop_per_image + tarch.gflop_per_text(30)) / 2
@@ -711,13 +741,14 @@ def run_ingest(args, dev, rank, world, dist, lib, L):
                                   f"every rank returns the request's embeddings in order)",
                    "weights": "random-init (seed 0) ViT-B-32", "gflop_per_embedding": round(gf, 3)},
         "e2e_tflops": round(value * gf / 1e3, 1),
-        # the dominant kernel family over a few more requests (HIP events on the launch streams, as in the headline)
-        "roofline": gemm_roofline(lib, L, step, min(args.steps, 6), args.precision, "add_documents_mixed"),
-        "cpu_baseline": (mixed_request_cpu_baseline(varch, tarch, imgs, docs, args.cpu_seconds)
-                         if rank == 0 and world == 1 and not args.no_cpu_baseline else None),
         "note": "end-to-end through the Python boundary (host PIL -> uint8 pack -> H2D -> K10 -> towers -> gather -> D2H -> per-key rows); "
                 "the request (total work) is fixed, ranks split it: strong scaling",
     }
+    if args.full:
+        # the dominant kernel family over a few more requests (HIP events on the launch streams, as in the headline)
+        result["roofline"] = gemm_roofline(lib, L, step, min(args.steps, 6), args.precision, "add_documents_mixed")
+        result["cpu_baseline"] = (mixed_request_cpu_baseline(varch, tarch, imgs, docs, args.cpu_seconds)
+                                  if rank == 0 and world == 1 and not args.no_cpu_baseline else None)
     if rank == 0:
         print(json.dumps(result), flush=True)
 
@@ -790,22 +821,28 @@ def run_stream(args, dev, rank, world, dist, lib, L):
         memory["pinned_reserved_mb"] = round(hs.get("reserved_bytes.current", hs.get("reserved_bytes.peak", 0)) / 2**20, 1)
     except Exception:  # noqa: BLE001 - statistics of the pinned-memory allocator are not in every build
         pass
-    # roofline of the dominant kernel family over a few more GROUPS (HIP events on the launch streams, as in the headline)
-    # (groups one at a time, both modalities on the caller's thread: with a group in flight the two towers' kernels share the GPU and every
-    # family's HIP-event time would count the other tower's kernels too)
-    ing.collect()
-    ing.pipeline_depth, ing._bulk.two_threads = 0, False
+    if rank == 0 and args.dump_outputs:
+        last = sorted(rows)[-world:]    # the requests of the last timed step (one per rank)
+        dump_outputs(args.dump_outputs, {m: np.stack([rows[i][(i, d, k)] for i in last for d in range(docs)])
+                                         for m, k in (("text_embeddings", "t"), ("image_embeddings", "i"))})
+    roofline = None
+    if args.full:
+        # roofline of the dominant kernel family over a few more GROUPS (HIP events on the launch streams, as in the headline)
+        # (groups one at a time, both modalities on the caller's thread: with a group in flight the two towers' kernels share the GPU and every
+        # family's HIP-event time would count the other tower's kernels too)
+        ing.collect()
+        ing.pipeline_depth, ing._bulk.two_threads = 0, False
 
-    def group_step():
-        for _ in range(group):
-            step()
-        ing.drain()
-    prof_groups = max(2, min(args.steps // group, 6))
-    roofline = gemm_roofline(lib, L, group_step, prof_groups, args.precision, "add_documents_stream")
-    ing.collect()
-    ing.pipeline_depth, ing._bulk.two_threads = 1, True
+        def group_step():
+            for _ in range(group):
+                step()
+            ing.drain()
+        prof_groups = max(2, min(args.steps // group, 6))
+        roofline = gemm_roofline(lib, L, group_step, prof_groups, args.precision, "add_documents_stream")
+        ing.collect()
+        ing.pipeline_depth, ing._bulk.two_threads = 1, True
+        roofline["requests_per_profiled_step"] = group
     ing.close()
-    roofline["requests_per_profiled_step"] = group
     gf = (varch.gflop_per_image + tarch.gflop_per_text(30)) / 2
     result = {
         "metric": "embeddings/sec", "value": round(value, 1), "unit": "embeddings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -819,13 +856,15 @@ def run_stream(args, dev, rank, world, dist, lib, L):
                    "parallelism": f"dp{world}: replicated weights; request i belongs to rank i % {world}; no collective inside a request; ONE gather "
                                   f"(dist.gather, not all_gather) of the ranks' [n, 512] rows onto rank 0 at the end of the stream",
                    "weights": "random-init (seed 0) ViT-B-32", "gflop_per_embedding": round(gf, 3)},
-        "e2e_tflops": round(value * gf / 1e3, 1), "roofline": roofline,
+        "e2e_tflops": round(value * gf / 1e3, 1),
     }
-    busy = sum(f["ms_per_step"] for f in roofline.get("per_family", {}).values()) / group
-    result["gpu_busy_ms_per_step"] = round(busy, 4)               # sum of the kernel families' HIP-event time per request (groups run one at a time)
     result["memory"] = memory
-    result["gpu_idle_share"] = round(max(0.0, 1.0 - busy / (elapsed / args.steps * 1e3)), 4)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if roofline is not None:
+        result["roofline"] = roofline
+        busy = sum(f["ms_per_step"] for f in roofline.get("per_family", {}).values()) / group
+        result["gpu_busy_ms_per_step"] = round(busy, 4)               # sum of the kernel families' HIP-event time per request (groups run one at a time)
+        result["gpu_idle_share"] = round(max(0.0, 1.0 - busy / (elapsed / args.steps * 1e3)), 4)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the CPU path runs the SAME request (its images, its texts through the loaded model's tokeniser), so the error below compares like with like
         model, _ = s2.load_multimodal_model_and_get_preprocessors(name, s2.get_model_properties_from_registry(name), dev)
         ids = torch.from_numpy(np.asarray(model.tokenizer(pool[0][0])).astype(np.int64))
@@ -931,16 +970,17 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = batch * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": out.float().cpu().numpy()})
 
-    roofline = gemm_roofline(lib, L, w.run, min(args.steps, 10), args.precision, args.workload)
-    peak = roofline["peak"]
+    peak = FP8_DENSE_PEAK_TFLOPS if args.precision == "fp8" else BF16_DENSE_PEAK_TFLOPS
     e2e_tflops = value * w.gflop_per_emb / 1e3
     result = {
         "metric": "embeddings/sec", "value": round(value, 1), "unit": "embeddings/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
         "config": {"workload": wl["desc"], "global_batch": batch * world,
-                   "inputs": "resident in HBM when the timed region starts (tower-only); host-resident hand-over is reported under e2e_vectorise",
+                   "inputs": "resident in HBM when the timed region starts (tower-only); host-resident hand-over is reported under e2e_vectorise (--full)",
                    "gflop_per_embedding": round(w.gflop_per_emb, 3),
                    "parallelism": f"dp{world} (replicated weights, sharded items, RCCL all_gather of embeddings)",
                    "weights": ("trained-like statistics (engine/synthetic.py, seed 2) " if wl.get("weights") == "trained_like" else "random-init (seed 0) ") + wl["arch"],
@@ -951,10 +991,11 @@ def main():
                    "last_block_rows": "pooled" if os.environ.get("MQ_ROW_SELECT", "1") != "0" and kind != "bert" else "all",
                    **({"fp8_policy": w.fp8_policy} if w.fp8_policy else {})},
         "e2e_tflops": round(e2e_tflops, 1), "e2e_frac_of_peak": round(e2e_tflops / (peak * world), 4),
-        "roofline": roofline,
     }
+    if args.full:
+        result["roofline"] = gemm_roofline(lib, L, w.run, min(args.steps, 10), args.precision, args.workload)
 
-    solo = rank == 0 and world == 1
+    solo = rank == 0 and world == 1 and args.full     # what is measured beside the headline: --full only
     if kind == "chunked":
         result["config"]["crops_per_image"] = w.crops_per_image
         result["config"]["inputs"] = "source images resident in HBM when the timed region starts; the chunker (K11) and the tower are inside it"
@@ -981,7 +1022,7 @@ def main():
         for name in (() if args.no_also else ALSO_DEFAULT):
             try:
                 if WORKLOADS[name]["kind"] == "stream":      # BASELINE configs[3]: end-to-end by definition (host PIL + strings in, host rows out)
-                    sa = argparse.Namespace(**{**vars(args), "steps": 0, "warmup": 8, "batch": 0, "cpu_seconds": 8.0, "workload": name})   # steps 0 = the full 100 000 documents
+                    sa = argparse.Namespace(**{**vars(args), "steps": 0, "warmup": 8, "batch": 0, "cpu_seconds": 8.0, "workload": name, "dump_outputs": None})   # steps 0 = the full 100 000 documents
                     r = run_stream(sa, dev, 0, 1, None, lib, L)
                     also.append({"workload": r["config"]["workload"], "value": r["value"], "unit": r["unit"], "ms_per_step": r["ms_per_step"], "steps": r["steps"], "warmup": r["warmup"], "documents_in_stream": r["config"]["documents_in_stream"],
                                  "micro_batching": r["config"]["micro_batching"], "memory": r.get("memory"),

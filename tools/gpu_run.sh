@@ -26,12 +26,12 @@ for stage in "$@"; do
       else timeout 1700 python -m pytest tests -m gpu -q 2>&1 | tail -8 | tee $OUT/pytest_gpu.txt; fi ;;
     bench)
       wl=${arg:-vit_b32_image}
-      timeout 900 python bench.py --workload $wl > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err; tail -c 1500 $OUT/bench_$wl.json; tail -3 $OUT/bench_$wl.err ;;
+      timeout 900 python bench.py --full --workload $wl > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err; tail -c 1500 $OUT/bench_$wl.json; tail -3 $OUT/bench_$wl.err ;;
     ab)
       spec=${arg%%:*}; wl=${arg#*:}; [ "$wl" = "$arg" ] && wl=vit_b32_image
       var=${spec%%=*}; vals=${spec#*=}
       for rep in 1 2; do for v in ${vals//,/ }; do
-        env $var=$v timeout 300 python bench.py --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>$OUT/ab.err | line "$wl $var=$v" | tee -a $OUT/ab_$var.txt
+        env $var=$v timeout 300 python bench.py --full --workload $wl --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>$OUT/ab.err | line "$wl $var=$v" | tee -a $OUT/ab_$var.txt
       done; done ;;
     prof)
       cd /tmp
