@@ -580,6 +580,74 @@ int mq_encoder_forward_rows(const mq_encoder_cfg* cfg, const mq_block_weights* b
 /* rows of x: out[r,:] = x[r,:] / ||x[r,:]||_2   (in place allowed) */
 int mq_l2_normalize(const float* d_x, float* d_out, int64_t rows, int32_t D, void* stream);
 
+/* ---- ConvNeXt image towers (csrc/convnext.hip) ------------------------------------------------------------------------------------------------
+ * The open_clip convnext_* CLIP image towers (model_registry.py:274-339 in the reference; open_clip TimmModel over a timm ConvNeXt with timm_pool "",
+ * i.e. timm's own head: global average pool -> LayerNorm, then open_clip's projection head).  Activations are NHWC bf16 rows [pixels, C]: the 1x1
+ * convolutions (stem patches, downsample 2x2 patches, fc1 / fc2) are mq_gemm_bf16* calls, the LayerNorm of a block is folded into its fc1 GEMM
+ * (statistics from the depthwise kernel's slot partials), gamma (layer scale) into its fc2 GEMM.  Every pointer below is a device pointer. */
+#define MQ_CONVNEXT_HEAD_LINEAR 0   /* visual.head.proj: Linear(C3, out_dim) without bias */
+#define MQ_CONVNEXT_HEAD_MLP 1      /* visual.head.mlp: Linear(C3, 2 out_dim) + bias -> GELU -> Linear(2 out_dim, out_dim) [+ bias] */
+
+typedef struct mq_convnext_cfg {
+    int32_t image_size;   /* S: multiple of 32 (224 / 256 / 320) */
+    int32_t depths[4];    /* blocks per stage */
+    int32_t dims[4];      /* channels per stage, multiples of 64; <= 3072 (stages 0-2: <= 2048) */
+    float   ln_eps;       /* every LayerNorm of trunk and head */
+    int32_t head;         /* MQ_CONVNEXT_HEAD_* */
+    int32_t out_dim;      /* embedding width E */
+    float   mean[3];      /* preprocessing normalisation of the u8 entry point */
+    float   std[3];
+} mq_convnext_cfg;
+
+/* one block: x = x + gamma * fc2(GELU(fc1(LN(dwconv7x7(x))))) */
+typedef struct mq_convnext_block_weights {
+    const float* dw_w;    /* fp32 [49, C]: conv_dw.weight [C, 1, 7, 7] transposed to (ky * 7 + kx, c) */
+    const float* dw_b;    /* fp32 [C] */
+    const void*  fc1_w;   /* bf16 [4C, C] = bf16(norm.weight[k] * mlp.fc1.weight[n, k]) */
+    const float* fc1_b;   /* fp32 [4C] = fc1.bias + fc1.weight @ norm.bias */
+    const float* fc1_s;   /* fp32 [4C] = sum_k of the bf16 fc1_w row (the colsum of mq_gemm_bf16_ln) */
+    const void*  fc2_w;   /* bf16 [C, 4C] = bf16(gamma[n] * mlp.fc2.weight[n, k]) */
+    const float* fc2_b;   /* fp32 [C] = gamma * fc2.bias */
+} mq_convnext_block_weights;
+
+typedef struct mq_convnext_weights {
+    const void*  stem_w;                      /* bf16 [C0, 64]: stem.0.weight [C0, 3, 4, 4] flattened (c, ky, kx), zero-padded from 48 to 64 columns */
+    const float* stem_b;                      /* [C0] */
+    const float* stem_ln_g; const float* stem_ln_b;   /* stem.1 */
+    const float* ds_ln_g[4]; const float* ds_ln_b[4]; /* stages.i.downsample.0 (index 0 unused) */
+    const void*  ds_w[4];                     /* bf16 [C_i, 4 C_{i-1}]: stages.i.downsample.1.weight [C_i, C_{i-1}, 2, 2] permuted to (ky, kx, c) columns */
+    const float* ds_b[4];                     /* [C_i] */
+    const mq_convnext_block_weights* blocks;  /* host array, sum(depths) entries, stage by stage */
+    const float* head_ln_g; const float* head_ln_b;   /* head.norm */
+    const void*  proj_w;   /* linear: bf16 [E, C3]; mlp: bf16 [2E, C3] (head.mlp.fc1) */
+    const float* proj_b;   /* mlp: fp32 [2E]; linear: NULL */
+    const void*  proj2_w;  /* mlp: bf16 [E, 2E] (head.mlp.fc2); linear: NULL */
+    const float* proj2_b;  /* mlp: fp32 [E] or NULL */
+} mq_convnext_weights;
+
+/* workspace of one call of n images (0 for an unsupported cfg) */
+size_t mq_convnext_workspace_bytes(const mq_convnext_cfg* cfg, int64_t n_images);
+/* the whole tower in one call, with the contract of mq_encode_image_u8 / _f32: d_pixels uint8 [n, S, S, 3] (HWC RGB; ToTensor + Normalize with
+ * cfg->mean / std fused into the stem's patch gather) or fp32 [n, 3, S, S] (normalised); d_out fp32 [n, E], L2-normalised when normalize != 0. */
+int mq_encode_convnext_u8(const mq_convnext_cfg* cfg, const mq_convnext_weights* w, const uint8_t* d_pixels, int64_t n, float* d_out, int normalize,
+                          void* d_workspace, size_t workspace_bytes, void* stream);
+int mq_encode_convnext_f32(const mq_convnext_cfg* cfg, const mq_convnext_weights* w, const float* d_pixels, int64_t n, float* d_out, int normalize,
+                           void* d_workspace, size_t workspace_bytes, void* stream);
+/* building blocks (exported for parity tests):
+ *   mq_convnext_dwconv:     d_y bf16 [n, H, W, C] = depthwise 7x7 (zero padding 3) of d_x bf16 [n, H, W, C] + d_b, taps d_w fp32 [49, C]; d_partials fp32
+ *                           [C / 64][n H W][2] = (sum, sum of squares) of the stored bf16 values per pixel and 64-channel slot (mq_row_stats_finalize
+ *                           turns them into (mean, rstd)).  C % 64 == 0; d_y must not alias d_x.
+ *   mq_convnext_downsample: d_out bf16 [n (H/2) (W/2), 4 C], column (ky * 2 + kx) * C + c = LayerNorm(pixel (2 oy + ky, 2 ox + kx))[c] * g[c] + b[c],
+ *                           (mean, rstd) per input pixel from d_stats fp32 [n H W][2] (mq_row_stats).  H, W even, C % 8 == 0.
+ *   mq_convnext_pool_ln:    per image, LayerNorm over C of the mean of its HW rows of d_x bf16 [n, HW, C], in fp32; written as bf16 and / or fp32
+ *                           [n, C] (either output may be NULL).  C % 8 == 0, C <= 3072. */
+int mq_convnext_dwconv(const void* d_x, const float* d_w, const float* d_b, void* d_y, float* d_partials, int64_t n, int32_t H, int32_t W, int32_t C,
+                       void* stream);
+int mq_convnext_downsample(const void* d_x, const float* d_stats, const float* d_g, const float* d_b, void* d_out, int64_t n, int32_t H, int32_t W,
+                           int32_t C, void* stream);
+int mq_convnext_pool_ln(const void* d_x, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32, int64_t n, int32_t HW, int32_t C,
+                        float eps, void* stream);
+
 /* ---- text tokenisation on device (K14) ------------------------------------------------------------------- */
 /* The reference tokenises on the host with third-party code (open_clip SimpleTokenizer at
  * src/marqo/core/inference/embedding_models/open_clip_model.py:277, transformers BertTokenizer at

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext")  # build() refuses register spills in these
 ABI_VERSION = 14
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU = 1, 2, 3
@@ -110,6 +110,26 @@ class BertWeights(C.Structure):
 class BertCfg(C.Structure):
     _fields_ = [("enc", EncoderCfg), ("vocab", C.c_int32), ("max_pos", C.c_int32), ("pool", C.c_int32),
                 ("proj_hidden", C.c_int32), ("out_dim", C.c_int32)]
+
+
+class ConvNextCfg(C.Structure):
+    """mq_convnext_cfg: the open_clip convnext_* image towers (csrc/convnext.hip)"""
+    _fields_ = [("image_size", C.c_int32), ("depths", C.c_int32 * 4), ("dims", C.c_int32 * 4), ("ln_eps", C.c_float), ("head", C.c_int32),
+                ("out_dim", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+class ConvNextBlockWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dw_w", "dw_b", "fc1_w", "fc1_b", "fc1_s", "fc2_w", "fc2_b")]
+
+
+class ConvNextWeights(C.Structure):
+    _fields_ = [("stem_w", C.c_void_p), ("stem_b", C.c_void_p), ("stem_ln_g", C.c_void_p), ("stem_ln_b", C.c_void_p),
+                ("ds_ln_g", C.c_void_p * 4), ("ds_ln_b", C.c_void_p * 4), ("ds_w", C.c_void_p * 4), ("ds_b", C.c_void_p * 4),
+                ("blocks", C.POINTER(ConvNextBlockWeights)), ("head_ln_g", C.c_void_p), ("head_ln_b", C.c_void_p),
+                ("proj_w", C.c_void_p), ("proj_b", C.c_void_p), ("proj2_w", C.c_void_p), ("proj2_b", C.c_void_p)]
+
+
+MQ_CONVNEXT_HEAD_LINEAR, MQ_CONVNEXT_HEAD_MLP = 0, 1
 
 
 class WordPieceVocab(C.Structure):
@@ -225,6 +245,12 @@ _SIGNATURES = {
     "mq_queue_encode_images": (C.c_int, [_P, _P, C.c_int64, _P]),
     "mq_queue_get_stats": (C.c_int, [_P, C.POINTER(QueueStats)]),
     "mq_queue_destroy": (C.c_int, [_P]),
+    "mq_convnext_workspace_bytes": (C.c_size_t, [C.POINTER(ConvNextCfg), C.c_int64]),
+    "mq_encode_convnext_u8": (C.c_int, [C.POINTER(ConvNextCfg), C.POINTER(ConvNextWeights), _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    "mq_encode_convnext_f32": (C.c_int, [C.POINTER(ConvNextCfg), C.POINTER(ConvNextWeights), _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    "mq_convnext_dwconv": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_convnext_downsample": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_convnext_pool_ln": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
     "mq_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

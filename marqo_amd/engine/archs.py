@@ -8,7 +8,7 @@ src/marqo/s2_inference/model_registry.py:76-610,616-880).  Only towers whose att
 from __future__ import annotations
 
 from dataclasses import dataclass, replace
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 OPENAI_DATASET_MEAN = (0.48145466, 0.4578275, 0.40821073)  # clip_utils.py:32
 OPENAI_DATASET_STD = (0.26862954, 0.26130258, 0.27577711)  # clip_utils.py:33
@@ -76,6 +76,35 @@ class VitArch:
         else:
             head = 2 * W * self.out_dim
         return (patch + self.layers * layer + head) / 1e9
+
+
+@dataclass(frozen=True)
+class ConvNextArch:
+    """timm ConvNeXt trunk behind open_clip's TimmModel with timm_pool "" (timm's head: global average pool -> LayerNorm) and open_clip's
+    projection head (`visual.trunk.*`, `visual.head.*`): the open_clip convnext_* model configs (model_registry.py:274-339 in the reference)."""
+    image_size: int
+    depths: Tuple[int, int, int, int]
+    dims: Tuple[int, int, int, int]
+    ln_eps: float
+    head: str                  # "linear": visual.head.proj (no bias); "mlp": visual.head.mlp.fc1 (+ bias) -> GELU -> fc2
+    out_dim: int
+    preprocessor: Optional[str] = None   # (the OpenCLIP transform: bicubic shortest-side resize, centre crop, OpenAI statistics)
+    pool: str = "convnext"     # (read by the loaders: not "map", so the OpenCLIP preprocessing is selected)
+    quick_gelu: bool = False   # (kept so that resolve_open_clip can `replace` it; the trunk's GELU is always erf)
+
+    @property
+    def gflop_per_image(self) -> float:
+        """Algorithmic FLOPs: 2 MNK of every 1x1 convolution (stem, downsample, fc1, fc2, head) plus 2 * 49 per depthwise output."""
+        G = self.image_size // 4
+        f = 2 * G * G * self.dims[0] * 48
+        for i, (d, C) in enumerate(zip(self.depths, self.dims)):
+            if i > 0:
+                f += 2 * G * G * C * 4 * self.dims[i - 1]
+            f += d * (2 * G * G * C * 49 + 2 * 2 * G * G * C * 4 * C)
+            G //= 2
+        C3, E = self.dims[3], self.out_dim
+        f += 2 * C3 * E if self.head == "linear" else 2 * C3 * 2 * E + 2 * 2 * E * E
+        return f / 1e9
 
 
 @dataclass(frozen=True)
@@ -244,6 +273,15 @@ OPEN_CLIP_ARCHS = {
                    ClipTextArch(49408, 77, 768, 12, 12, 3072, 768, prefix="text.")),
     "EVA02-L-14-336": (VitArch(336, 14, 1024, 24, 16, 2730, 768, ln_eps=1e-6, ln_pre=False, eva=True),
                        ClipTextArch(49408, 77, 768, 12, 12, 3072, 768, prefix="text.")),
+    # ConvNeXt CLIPs (model_registry.py:274-339; open_clip model configs convnext_*: timm convnext_{base,large,xxlarge} trunks, timm_pool "",
+    # timm_proj linear / mlp).  The 1e-5 LayerNorm eps of xxlarge and the 16-layer text tower of large_d are from the timm / open_clip configs as
+    # published (neither library is vendored here): DESIGN.md §5
+    "convnext_base": (ConvNextArch(224, (3, 3, 27, 3), (128, 256, 512, 1024), 1e-6, "linear", 512), _TEXT_B),
+    "convnext_base_w": (ConvNextArch(256, (3, 3, 27, 3), (128, 256, 512, 1024), 1e-6, "linear", 640), _TEXT_B_PLUS),
+    "convnext_base_w_320": (ConvNextArch(320, (3, 3, 27, 3), (128, 256, 512, 1024), 1e-6, "linear", 640), _TEXT_B_PLUS),
+    "convnext_large_d": (ConvNextArch(256, (3, 3, 27, 3), (192, 384, 768, 1536), 1e-6, "mlp", 768), replace(_TEXT_L, layers=16)),
+    "convnext_large_d_320": (ConvNextArch(320, (3, 3, 27, 3), (192, 384, 768, 1536), 1e-6, "mlp", 768), replace(_TEXT_L, layers=16)),
+    "convnext_xxlarge": (ConvNextArch(256, (3, 4, 30, 3), (384, 768, 1536, 3072), 1e-5, "linear", 1024), _TEXT_H),
     "ViT-B-16-SigLIP": _siglip(224), "ViT-B-16-SigLIP-256": _siglip(256), "ViT-B-16-SigLIP-384": _siglip(384),
     "ViT-B-16-SigLIP-512": _siglip(512),
     "ViT-SO400M-14-SigLIP": _siglip(224, so400m=True), "ViT-SO400M-14-SigLIP-384": _siglip(384, so400m=True),
@@ -261,8 +299,8 @@ KNOWN_HF_HUB_ARCHS = {"hf-hub:Marqo/marqo-fashionCLIP": "ViT-B-16", "hf-hub:Marq
 OPENAI_CLIP_NAMES = {"ViT-B/32": "ViT-B-32", "ViT-B/16": "ViT-B-16", "ViT-L/14": "ViT-L-14", "ViT-L/14@336px": "ViT-L-14-336"}
 
 
-def resolve_open_clip(arch_name: str, pretrained: Optional[str] = None) -> Tuple[VitArch, ClipTextArch]:
-    """'ViT-B-32' / 'ViT-B-32-quickgelu' (+ pretrained tag) -> (vision, text) arch or KeyError."""
+def resolve_open_clip(arch_name: str, pretrained: Optional[str] = None) -> Tuple[Union[VitArch, ConvNextArch], ClipTextArch]:
+    """'ViT-B-32' / 'ViT-B-32-quickgelu' / 'convnext_base_w' (+ pretrained tag) -> (vision, text) arch or KeyError."""
     quick = False
     base = arch_name
     if base.endswith("-quickgelu"):

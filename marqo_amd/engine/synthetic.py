@@ -11,7 +11,7 @@ from typing import Dict
 
 import torch
 
-from marqo_amd.engine.archs import BertArch, ClipTextArch, VitArch
+from marqo_amd.engine.archs import BertArch, ClipTextArch, ConvNextArch, VitArch
 
 Tensor = torch.Tensor
 
@@ -39,11 +39,43 @@ def _resblocks(sd, prefix, layers, W, F, g):
         _lin(sd, p + "mlp.c_proj", W, F, g, std)
 
 
+def _convnext_visual(sd, arch: ConvNextArch, g) -> None:
+    """timm ConvNeXt trunk under visual.trunk.* + open_clip's projection head under visual.head.*.  The layer scales are trained-like,
+    U(0.05, 0.5): with timm's 1e-6 init every block would be the identity and a parity check would prove nothing."""
+    t, dims = "visual.trunk.", arch.dims
+    sd[t + "stem.0.weight"] = torch.randn(dims[0], 3, 4, 4, generator=g) / math.sqrt(48)
+    sd[t + "stem.0.bias"] = 0.02 * torch.randn(dims[0], generator=g)
+    _ln(sd, t + "stem.1", dims[0], g)
+    for i, (depth, C) in enumerate(zip(arch.depths, dims)):
+        p = f"{t}stages.{i}."
+        if i > 0:
+            _ln(sd, p + "downsample.0", dims[i - 1], g)
+            sd[p + "downsample.1.weight"] = torch.randn(C, dims[i - 1], 2, 2, generator=g) / math.sqrt(4 * dims[i - 1])
+            sd[p + "downsample.1.bias"] = 0.02 * torch.randn(C, generator=g)
+        for j in range(depth):
+            b = f"{p}blocks.{j}."
+            sd[b + "conv_dw.weight"] = torch.randn(C, 1, 7, 7, generator=g) / 7.0
+            sd[b + "conv_dw.bias"] = 0.02 * torch.randn(C, generator=g)
+            _ln(sd, b + "norm", C, g)
+            _lin(sd, b + "mlp.fc1", 4 * C, C, g, 1.0 / math.sqrt(C))
+            _lin(sd, b + "mlp.fc2", C, 4 * C, g, 1.0 / math.sqrt(4 * C))
+            sd[b + "gamma"] = 0.05 + 0.45 * torch.rand(C, generator=g)
+    _ln(sd, t + "head.norm", dims[3], g)
+    C3, E = dims[3], arch.out_dim
+    if arch.head == "linear":
+        sd["visual.head.proj.weight"] = torch.randn(E, C3, generator=g) / math.sqrt(C3)
+    else:
+        _lin(sd, "visual.head.mlp.fc1", 2 * E, C3, g, 1.0 / math.sqrt(C3))
+        sd["visual.head.mlp.fc2.weight"] = torch.randn(E, 2 * E, generator=g) / math.sqrt(2 * E)
+
+
 def random_open_clip_state_dict(vision: VitArch = None, text: ClipTextArch = None, seed: int = 0) -> Dict[str, Tensor]:
     """open_clip-named state dict for the given towers (either may be None)."""
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, Tensor] = {}
-    if vision is not None and vision.pool == "map":
+    if isinstance(vision, ConvNextArch):
+        _convnext_visual(sd, vision, g)
+    elif vision is not None and vision.pool == "map":
         # timm SigLIP ViT as open_clip's visual.trunk (no class token, conv bias, attention-pool head)
         W, P, F, t = vision.width, vision.patch_size, vision.mlp_dim, "visual.trunk."
         std = 0.6 / math.sqrt(W)

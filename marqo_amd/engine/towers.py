@@ -1612,3 +1612,136 @@ class MclipTextTower(BertTower):
         self.cfg.proj_hidden, self.cfg.out_dim = 0, out_dim
         if precision == "bf16":
             self.tune_residual_default()
+
+
+# ---- ConvNeXt image towers (csrc/convnext.hip) ------------------------------------------------------------------------------------------------
+# Load-time folds, as pure CPU-tensor functions (tests/test_convnext_host.py checks them against the unfolded fp32 computation).
+
+def convnext_dw_taps(conv_dw_w: Tensor) -> Tensor:
+    """conv_dw.weight [C, 1, 7, 7] -> fp32 [49, C] (tap-major: one tap's C channels are contiguous, as the kernel stages them)"""
+    C = conv_dw_w.shape[0]
+    return conv_dw_w.detach().to(torch.float32).reshape(C, 49).t().contiguous()
+
+
+def convnext_fold_ln_fc1(fc1_w: Tensor, fc1_b: Tensor, ln_g: Tensor, ln_b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """The block's LayerNorm folded into fc1 (mq_gemm_bf16_ln): LN(x) @ W^T + b = rstd * (x @ (g*W)^T - mean * colsum) + (b + W @ beta)
+    -> (bf16 g*W [4C, C], fp32 bias [4C], fp32 colsum of the ROUNDED folded weight [4C])"""
+    w32 = fc1_w.detach().to(torch.float32)
+    wf = (w32 * ln_g.detach().to(torch.float32).unsqueeze(0)).to(torch.bfloat16)
+    return wf, fc1_b.detach().to(torch.float32) + w32 @ ln_b.detach().to(torch.float32), wf.to(torch.float32).sum(dim=1)
+
+
+def convnext_fold_gamma_fc2(fc2_w: Tensor, fc2_b: Tensor, gamma: Tensor) -> Tuple[Tensor, Tensor]:
+    """gamma * (h @ W^T + b) = h @ (gamma[:, None] * W)^T + gamma * b  -> (fp32 weight [C, 4C], fp32 bias [C])"""
+    g = gamma.detach().to(torch.float32)
+    return fc2_w.detach().to(torch.float32) * g.unsqueeze(1), fc2_b.detach().to(torch.float32) * g
+
+
+def convnext_downsample_weight(w: Tensor) -> Tensor:
+    """downsample.1.weight [C_out, C_in, 2, 2] -> fp32 [C_out, 4 C_in] with columns in (ky, kx, c) order: the gather copies whole pixels"""
+    return w.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def convnext_downsample_gather(x_nhwc: Tensor) -> Tensor:
+    """the gather mq_convnext_downsample performs (without its LayerNorm), in torch: [n, H, W, C] -> [n (H/2) (W/2), 4 C], (ky, kx, c) columns"""
+    n, H, W, C = x_nhwc.shape
+    return x_nhwc.reshape(n, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(n * (H // 2) * (W // 2), 4 * C)
+
+
+# scratch one call may use: a larger batch is split into calls of at most this many bytes of workspace (stage 0 sizes it: ~6 MB per 256 px image of
+# convnext_base_w, ~18 MB of convnext_xxlarge)
+CONVNEXT_WORKSPACE_BYTES = _env_int("MARQO_AMD_CONVNEXT_WORKSPACE_MB", 4096) << 20
+
+
+class ConvNextTower(_TowerBase):
+    """open_clip ConvNeXt image tower (timm trunk under `visual.trunk.*`, projection head under `visual.head.*`), one mq_encode_convnext_* call
+    per chunk of images.  bf16 only; the small-call native queue does not take these towers."""
+
+    has_native_queue = False
+
+    def __init__(self, arch, sd: Dict[str, Tensor], device: str, mean: Sequence[float] = OPENAI_DATASET_MEAN,
+                 std: Sequence[float] = OPENAI_DATASET_STD, precision: str = "bf16", max_workspace_bytes: Optional[int] = None):
+        if precision != "bf16":
+            raise ValueError(f"ConvNeXt towers run in bf16 only (engine_precision {precision!r} is not supported for convnext_* models)")
+        super().__init__(device)
+        self.precision, self.arch, self._fp8 = precision, arch, None
+        h, t, dims = self._h, "visual.trunk.", arch.dims
+        f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+        C0 = dims[0]
+        stem_w = torch.zeros(C0, 64, dtype=torch.float32)
+        stem_w[:, :48] = f32(t + "stem.0.weight", (C0, 3, 4, 4)).reshape(C0, 48)
+        w = L.ConvNextWeights(stem_w=h.bf16(stem_w), stem_b=h.f32(f32(t + "stem.0.bias", (C0,))),
+                              stem_ln_g=h.f32(f32(t + "stem.1.weight", (C0,))), stem_ln_b=h.f32(f32(t + "stem.1.bias", (C0,))))
+        blocks = []
+        for i, (depth, Ch) in enumerate(zip(arch.depths, dims)):
+            p = f"{t}stages.{i}."
+            if i > 0:
+                Cp = dims[i - 1]
+                w.ds_ln_g[i] = h.f32(f32(p + "downsample.0.weight", (Cp,)))
+                w.ds_ln_b[i] = h.f32(f32(p + "downsample.0.bias", (Cp,)))
+                w.ds_w[i] = h.bf16(convnext_downsample_weight(f32(p + "downsample.1.weight", (Ch, Cp, 2, 2))))
+                w.ds_b[i] = h.f32(f32(p + "downsample.1.bias", (Ch,)))
+            for j in range(depth):
+                b = f"{p}blocks.{j}."
+                wf, bf, sf = convnext_fold_ln_fc1(f32(b + "mlp.fc1.weight", (4 * Ch, Ch)), f32(b + "mlp.fc1.bias", (4 * Ch,)),
+                                                  f32(b + "norm.weight", (Ch,)), f32(b + "norm.bias", (Ch,)))
+                w2, b2 = convnext_fold_gamma_fc2(f32(b + "mlp.fc2.weight", (Ch, 4 * Ch)), f32(b + "mlp.fc2.bias", (Ch,)), f32(b + "gamma", (Ch,)))
+                blocks.append(L.ConvNextBlockWeights(dw_w=h.f32(convnext_dw_taps(f32(b + "conv_dw.weight", (Ch, 1, 7, 7)))),
+                                                     dw_b=h.f32(f32(b + "conv_dw.bias", (Ch,))), fc1_w=h.bf16(wf), fc1_b=h.f32(bf),
+                                                     fc1_s=h.f32(sf), fc2_w=h.bf16(w2), fc2_b=h.f32(b2)))
+        self._blocks = (L.ConvNextBlockWeights * len(blocks))(*blocks)
+        w.blocks = C.cast(self._blocks, C.POINTER(L.ConvNextBlockWeights))
+        w.head_ln_g, w.head_ln_b = h.f32(f32(t + "head.norm.weight", (dims[3],))), h.f32(f32(t + "head.norm.bias", (dims[3],)))
+        E = arch.out_dim
+        if arch.head == "linear":
+            w.proj_w = h.bf16(f32("visual.head.proj.weight", (E, dims[3])))
+            head = L.MQ_CONVNEXT_HEAD_LINEAR
+        elif arch.head == "mlp":
+            w.proj_w = h.bf16(f32("visual.head.mlp.fc1.weight", (2 * E, dims[3])))
+            w.proj_b = h.f32(f32("visual.head.mlp.fc1.bias", (2 * E,)))
+            w.proj2_w = h.bf16(f32("visual.head.mlp.fc2.weight", (E, 2 * E)))
+            if "visual.head.mlp.fc2.bias" in sd:
+                w.proj2_b = h.f32(f32("visual.head.mlp.fc2.bias", (E,)))
+            head = L.MQ_CONVNEXT_HEAD_MLP
+        else:
+            raise ValueError(f"unknown ConvNeXt projection head {arch.head!r}")
+        self.w = w
+        self.cfg = L.ConvNextCfg(image_size=arch.image_size, depths=(C.c_int32 * 4)(*arch.depths), dims=(C.c_int32 * 4)(*dims),
+                                 ln_eps=arch.ln_eps, head=head, out_dim=E, mean=(C.c_float * 3)(*mean), std=(C.c_float * 3)(*std))
+        per_image = self.lib.mq_convnext_workspace_bytes(C.byref(self.cfg), 1)
+        if per_image == 0:
+            raise ValueError(f"ConvNeXt configuration not supported by the kernels: {arch}")
+        budget = CONVNEXT_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+        self.max_images_per_call = max(1, min(65535, budget // per_image))
+
+    def release_unused_folded(self) -> int:
+        return 0   # (the folded fc1 / fc2 copies are the only copies the blocks hold)
+
+    def queue_rows_images(self, tensors: Sequence[Tensor], normalize: bool = True) -> Optional[np.ndarray]:
+        return None   # small `.preprocess` calls take the regular path
+
+    def _run(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
+        n = pixels.shape[0]
+        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
+        fn = self.lib.mq_encode_convnext_u8 if kind == "u8" else self.lib.mq_encode_convnext_f32
+        with torch.cuda.device(self.device):
+            for i in range(0, n, self.max_images_per_call):
+                m = min(self.max_images_per_call, n - i)
+                ws = self._workspace(self.lib.mq_convnext_workspace_bytes(C.byref(self.cfg), m))
+                L.check(fn(C.byref(self.cfg), C.byref(self.w), pixels[i:i + m].data_ptr(), m, out[i:i + m].data_ptr(), 1 if normalize else 0,
+                           ws.data_ptr(), ws.numel(), self._stream()), "mq_encode_convnext")
+        return out
+
+    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
+        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
+        S = self.arch.image_size
+        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
+            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+        return self._run("u8", images_u8.to(self.device, non_blocking=True).contiguous(), normalize)
+
+    def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
+        """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
+        S = self.arch.image_size
+        if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
+            raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
+        return self._run("f32", pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous(), normalize)

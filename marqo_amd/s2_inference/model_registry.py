@@ -40,6 +40,13 @@ _OPEN_CLIP_TAGS = {
     "coca_ViT-L-14": ["laion2b_s13b_b90k", "mscoco_finetuned_laion2b_s13b_b90k"],
     # EVA02-CLIP (model_registry.py:441-460): timm Eva trunks behind open_clip's TimmModel
     "EVA02-B-16": ["merged2b_s8b_b131k"], "EVA02-L-14": ["merged2b_s4b_b131k"], "EVA02-L-14-336": ["merged2b_s6b_b61k"],
+    # ConvNeXt CLIPs (model_registry.py:274-339): timm ConvNeXt trunks behind open_clip's TimmModel + the CLIP text tower
+    "convnext_base": ["laion400m_s13b_b51k"],
+    "convnext_base_w": ["laion2b_s13b_b82k", "laion2b_s13b_b82k_augreg", "laion_aesthetic_s13b_b82k"],
+    "convnext_base_w_320": ["laion_aesthetic_s13b_b82k", "laion_aesthetic_s13b_b82k_augreg"],
+    "convnext_large_d": ["laion2b_s26b_b102k_augreg"],
+    "convnext_large_d_320": ["laion2b_s29b_b131k_ft", "laion2b_s29b_b131k_ft_soup"],
+    "convnext_xxlarge": ["laion2b_s34b_b82k_augreg", "laion2b_s34b_b82k_augreg_rewind", "laion2b_s34b_b82k_augreg_soup"],
     # SigLIP (model_registry.py:371-432)
     "ViT-B-16-SigLIP": ["webli"], "ViT-B-16-SigLIP-256": ["webli"], "ViT-B-16-SigLIP-384": ["webli"], "ViT-B-16-SigLIP-512": ["webli"],
     "ViT-L-16-SigLIP-256": ["webli"], "ViT-L-16-SigLIP-384": ["webli"], "ViT-SO400M-14-SigLIP-384": ["webli"],

@@ -46,6 +46,9 @@ _PREPROCESSOR_NORMS = {
     "CLIPA": ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225), "squash", "bilinear"),
 }
 _TIMM_SIGLIP = __import__("re").compile(r"^vit_(base|large|so400m)_patch1[46]_siglip_(\d+)$")
+# timm ConvNeXt trunks of the open_clip convnext_* configs: timm_model_name -> (depths, dims, LayerNorm eps)
+_TIMM_CONVNEXT = {"convnext_base": ((3, 3, 27, 3), (128, 256, 512, 1024), 1e-6), "convnext_large": ((3, 3, 27, 3), (192, 384, 768, 1536), 1e-6),
+                  "convnext_xxlarge": ((3, 4, 30, 3), (384, 768, 1536, 3072), 1e-5)}
 
 
 class OpenCLIPModelProperties:
@@ -199,6 +202,8 @@ class OPEN_CLIP(AbstractCLIPModel):
             with open(cfg_path) as f:
                 mc = json.load(f)["model_cfg"]
             v, t = mc["vision_cfg"], mc["text_cfg"]
+            if str(v.get("timm_model_name", "")) in _TIMM_CONVNEXT and "hf_model_name" not in t:
+                return self._convnext_from_config(arch_name, mc)
             m = _TIMM_SIGLIP.match(str(v.get("timm_model_name", "")))
             if m and "hf_model_name" not in t:
                 # SigLIP: timm trunk + TextTransformer(no_causal_mask, pool 'last', proj_bias) — marqo-fashionSigLIP, marqo-ecommerce-*
@@ -223,6 +228,20 @@ class OPEN_CLIP(AbstractCLIPModel):
             return archs.resolve_open_clip(arch_name, tag)
         except KeyError as e:
             raise InvalidModelPropertiesError(str(e)) from e
+
+    @staticmethod
+    def _convnext_from_config(arch_name: str, mc: dict):
+        """open_clip_config.json model_cfg of a ConvNeXt CLIP (timm trunk, timm_pool "", timm_proj linear / mlp) -> (ConvNextArch, ClipTextArch)"""
+        v, t = mc["vision_cfg"], mc["text_cfg"]
+        depths, dims, eps = _TIMM_CONVNEXT[str(v["timm_model_name"])]
+        proj = v.get("timm_proj", "linear")
+        if v.get("timm_pool", "") not in ("", None) or proj not in ("linear", "mlp"):
+            raise InvalidModelPropertiesError(f"{arch_name}: ConvNeXt towers are supported with timm_pool '' and timm_proj linear / mlp only")
+        vision = archs.ConvNextArch(int(v.get("image_size", 224)), depths, dims, eps, proj, int(mc["embed_dim"]))
+        W = int(t.get("width", 512))
+        text = archs.ClipTextArch(t.get("vocab_size", 49408), t.get("context_length", 77), W, t.get("layers", 12), t.get("heads", 8),
+                                  int(W * t.get("mlp_ratio", 4.0)), int(mc["embed_dim"]), bool(mc.get("quick_gelu", False)))
+        return vision, text
 
     def _load_necessary_components(self) -> None:
         if not str(self.device).startswith("cuda"):
@@ -264,7 +283,8 @@ class OPEN_CLIP(AbstractCLIPModel):
         self.preprocess_config = {"size": self.vision_arch.image_size, "mean": self._mean, "std": self._std,
                                   "interpolation": self._interpolation, "resize_mode": self._resize_mode}
         try:
-            self.vision = towers.VitTower(self.vision_arch, sd, self.device, mean=self._mean, std=self._std, precision=props.engine_precision)
+            tower = towers.ConvNextTower if isinstance(self.vision_arch, archs.ConvNextArch) else towers.VitTower
+            self.vision = tower(self.vision_arch, sd, self.device, mean=self._mean, std=self._std, precision=props.engine_precision)
             self.text = self._make_text_tower(sd, props.engine_precision)
         except ValueError as e:  # e.g. fp8 needs width / mlp_dim multiples of 128
             raise InvalidModelPropertiesError(str(e)) from e
@@ -633,7 +653,8 @@ class OPEN_CLIP(AbstractCLIPModel):
         from marqo_amd.engine import native_queue as NQ
         if not NQ.ENABLED or self.model is None or not isinstance(images, list) or not (1 <= len(images) <= NQ.IMAGE_REQUEST_MAX):
             return False
-        if getattr(self, "vision", None) is None or not hasattr(self.vision, "queue_rows_images"):
+        if getattr(self, "vision", None) is None or not hasattr(self.vision, "queue_rows_images") or \
+                not getattr(self.vision, "has_native_queue", True):
             return False
         return all(isinstance(t, torch.Tensor) and getattr(t, "_mq_block", None) is not None for t in images)
 
