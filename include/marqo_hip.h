@@ -580,6 +580,55 @@ int mq_encoder_forward_rows(const mq_encoder_cfg* cfg, const mq_block_weights* b
 /* rows of x: out[r,:] = x[r,:] / ||x[r,:]||_2   (in place allowed) */
 int mq_l2_normalize(const float* d_x, float* d_out, int64_t rows, int32_t D, void* stream);
 
+/* The front / back ends of the towers and their gated-MLP and rotary steps (csrc/embed.hip).  Every tower reaches them internally; they are
+ * exported for parity tests.  W % 4 == 0 and W <= 2048 wherever a row width W appears, unless stated otherwise.
+ *   mq_patchify:     d_out bf16 [n (S/P)^2, Kp], row (img, py, px), column c P^2 + ky P + kx = pixel (py P + ky, px P + kx) channel c of d_in, which
+ *                    is uint8 HWC [n, S, S, 3] (is_u8 != 0: (b / 255 - mean[c]) / std[c] in fp32) or normalised fp32 CHW [n, 3, S, S]; columns
+ *                    >= 3 P^2 are 0.  mean / std are HOST pointers to 3 floats (read at the call; ignored for fp32 input).  Kp % 8 == 0.
+ *   mq_vit_assemble: d_x [n T, W] = (class token d_cls at t = 0 | row b (T - 1) + t - 1 of d_patch_out) + d_pos[t], then LayerNorm(g, b) when g
+ *                    is not NULL; d_cls NULL: no class token, row b T + t of d_patch_out.  fp32 inputs; d_x fp32, or bf16 when x_bf16 != 0.
+ *   mq_embed_tokens: per sequence i of d_cu [nseq + 1], row r = tok[clamp(ids[r], 0, vocab - 1)] (+ pos[t]) (+ type0) (LayerNorm(g, b) when g is
+ *                    not NULL) -> d_x fp32 and / or d_xb bf16 [rows, W] (either may be NULL); t = r - d_cu[i], except the last row of a
+ *                    sequence takes pos[last_pos] when last_pos > 0 (CoCa's appended class embedding).
+ *   mq_pool:         d_out fp32 [nseq, W] = the mean over each sequence's rows (MQ_POOL_MEAN) or its first row (MQ_POOL_CLS) of d_x fp32, then
+ *                    x / max(||x||, 1e-12) when normalize != 0.
+ *   mq_map_pool:     one learned query per head: d_out bf16 [n, W], head h = softmax(q_h . k_t) . v_t over the T rows of each image in d_kv bf16
+ *                    [n T, 2 W] = (K | V); d_q fp32 [W] already scaled.  hd = W / heads a multiple of 8, <= 128; 1 <= T <= 4096.
+ *   mq_avg_tokens:   d_out fp32 [n, W] = mean of rows [first, T) of each image of d_x (fp32, or bf16 when x_bf16 != 0).
+ *   mq_move_rows:    gather (scatter == 0) d_dense[i] = d_sparse[d_idx[i]] or scatter (scatter != 0) d_sparse[d_idx[i]] = d_dense[i], rows of
+ *                    row_bytes bytes (a multiple of 16); rows of d_sparse not named in d_idx are not touched.
+ *   mq_last_rows / mq_cls_rows: d_rows int32 = d_cu[i + 1] - 1 per sequence / i T per image.
+ *   mq_rope:         rotary embedding (rotate_half form, angle float(t) * inv_freq[i] with t the row's position in its sequence) on the Q and K
+ *                    thirds of d_qkv bf16 [rows, 3 Wa], in place; V is not touched.  Sequences from d_cu, or fixed_len rows each when d_cu is
+ *                    NULL.  Head width Wa / heads a multiple of 16; d_inv_freq fp32 [head width / 2].
+ *   mq_rope_table:   rotary embedding from a table (the interleaved pairs of the EVA02 towers) on the Q and K thirds of d_qkv bf16 [rows, 3 Wa],
+ *                    in place; d_table fp32 [T - prefix][2][hs] = (cos | sin); the first `prefix` rows of every T-row sequence and V are not touched.
+ *                    rows % T == 0, hs = Wa / heads a multiple of 8.
+ *   mq_glu:          d_buf bf16 [rows, 2F] = (up | gate) -> d_buf[:, :F] = up * act(gate), in place (row stride 2F).  interleaved != 0: up and gate
+ *                    alternate 16 columns at a time (MQ_EPI_GLU's layout) and the product is written compactly to the first F columns;
+ *                    F % 8 == 0 (F % 16 == 0 and F <= 4096 interleaved).
+ *   mq_glu_ln:       d_buf bf16 [rows, 2F] -> d_buf[:, :F] = LayerNorm(product) g + b, statistics over the first Ft columns (the rest is the zero
+ *                    padding of a width Ft model).  mode 0: (up | gate) halves; 1: interleaved as mq_glu; 2: the product is already in the first F
+ *                    columns; 3: interleaved, the product only (no LayerNorm, g / b may be NULL).  F % 8 == 0, F <= 4096, Ft <= F, F % 16 == 0
+ *                    in modes 1 and 3. */
+int mq_patchify(const void* d_in, int32_t is_u8, void* d_out, int64_t n, int32_t S, int32_t P, int32_t Kp, const float* mean, const float* std,
+                void* stream);
+int mq_vit_assemble(const float* d_patch_out, const float* d_cls, const float* d_pos, const float* d_g, const float* d_b, void* d_x, int64_t n,
+                    int32_t T, int32_t W, float eps, int32_t x_bf16, void* stream);
+int mq_embed_tokens(const int32_t* d_ids, const int32_t* d_cu, int64_t nseq, const float* d_tok, const float* d_pos, const float* d_type0,
+                    const float* d_g, const float* d_b, float* d_x, void* d_xb, int32_t W, int32_t vocab, float eps, int32_t last_pos, void* stream);
+int mq_pool(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_out, int32_t W, int32_t pool, int32_t normalize, void* stream);
+int mq_map_pool(const void* d_kv, const float* d_q, void* d_out, int64_t n, int32_t T, int32_t W, int32_t heads, void* stream);
+int mq_avg_tokens(const void* d_x, int32_t x_bf16, float* d_out, int64_t n, int32_t T, int32_t first, int32_t W, void* stream);
+int mq_move_rows(void* d_sparse, const int32_t* d_idx, void* d_dense, int64_t n, int64_t row_bytes, int32_t scatter, void* stream);
+int mq_last_rows(const int32_t* d_cu, int32_t* d_rows, int64_t nseq, void* stream);
+int mq_cls_rows(int32_t* d_rows, int64_t n, int32_t T, void* stream);
+int mq_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t Wa, int32_t heads, const float* d_inv_freq, void* stream);
+int mq_rope_table(void* d_qkv, int64_t rows, int32_t T, int32_t prefix, int32_t Wa, int32_t heads, const float* d_table, void* stream);
+int mq_glu(void* d_buf, int64_t rows, int32_t F, int32_t act, int32_t interleaved, void* stream);
+int mq_glu_ln(void* d_buf, int64_t rows, int32_t F, int32_t Ft, int32_t act, const float* d_g, const float* d_b, float eps, int32_t mode,
+              void* stream);
+
 /* ---- ConvNeXt image towers (csrc/convnext.hip) ------------------------------------------------------------------------------------------------
  * The open_clip convnext_* CLIP image towers (model_registry.py:274-339 in the reference; open_clip TimmModel over a timm ConvNeXt with timm_pool "",
  * i.e. timm's own head: global average pool -> LayerNorm, then open_clip's projection head).  Activations are NHWC bf16 rows [pixels, C]: the 1x1

@@ -251,6 +251,20 @@ _SIGNATURES = {
     "mq_convnext_dwconv": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_convnext_downsample": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_convnext_pool_ln": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    # the towers' front / back ends, rotary and gated-MLP steps (csrc/embed.hip; building blocks for parity tests)
+    "mq_patchify": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mq_vit_assemble": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
+    "mq_embed_tokens": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
+    "mq_pool": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_map_pool": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_avg_tokens": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_move_rows": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P]),
+    "mq_last_rows": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "mq_cls_rows": (C.c_int, [_P, C.c_int64, C.c_int32, _P]),
+    "mq_rope": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mq_rope_table": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mq_glu": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_glu_ln": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, C.c_int32, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
     "mq_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -6,8 +6,6 @@
 //   * pooled head: mean over the pixels of an image, then LayerNorm over C (timm's head.norm), one workgroup per image, any C <= 3072.
 #include "common.h"
 
-int mq_patchify(const void* d_in, bool is_u8, void* d_out, int64_t n, int S, int P, int Kp, const float* mean, const float* std, hipStream_t s);
-
 static_assert(sizeof(mq_convnext_cfg) == 72, "mq_convnext_cfg layout");
 static_assert(sizeof(mq_convnext_block_weights) == 7 * 8 && sizeof(mq_convnext_weights) == 27 * 8, "mq_convnext weight layouts");
 

@@ -350,9 +350,10 @@ __global__ __launch_bounds__(256) void move_rows_kernel(uint4* __restrict__ spar
 
 }  // namespace
 
-// ---- internal host entry points (declared in towers.hip) ---------------------------------------------------
-int mq_patchify(const void* d_in, bool is_u8, void* d_out, int64_t n, int S, int P, int Kp,
-                const float* mean, const float* std, hipStream_t s) {
+// ---- host entry points (C ABI, include/marqo_hip.h) -----------------------------------------------------------
+extern "C" int mq_patchify(const void* d_in, int32_t is_u8, void* d_out, int64_t n, int32_t S, int32_t P, int32_t Kp, const float* mean,
+                           const float* std, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const int G = S / P;
     const int64_t total = n * G * G * (Kp >> 3);
     if (total <= 0) return MQ_OK;
@@ -373,14 +374,15 @@ int mq_patchify(const void* d_in, bool is_u8, void* d_out, int64_t n, int S, int
     return MQ_OK;
 }
 
-int mq_vit_assemble(const float* d_patch_out, const float* cls, const float* pos, const float* g, const float* b,
-                    float* d_x, int64_t n, int T, int W, float eps, hipStream_t s, int x_bf16) {
+extern "C" int mq_vit_assemble(const float* d_patch_out, const float* cls, const float* pos, const float* g, const float* b, void* d_x, int64_t n,
+                               int32_t T, int32_t W, float eps, int32_t x_bf16, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(W % 4 == 0 && W <= 64 * 4 * MAXC, "vit_assemble: W=%d unsupported", W);
     const int64_t rows = n * T;
     if (rows <= 0) return MQ_OK;
     MqProfScope prof(3, s);
     MQ_DISPATCH_CH(W, hipLaunchKernelGGL(vit_assemble_kernel<CH>, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s, d_patch_out,
-                                         cls, pos, g, b, d_x, rows, T, W, eps, x_bf16));
+                                         cls, pos, g, b, (float*)d_x, rows, T, W, eps, x_bf16));
     MQ_CHECK_LAUNCH("vit_assemble");
     return MQ_OK;
 }
@@ -404,7 +406,8 @@ __global__ __launch_bounds__(256) void avg_tokens_kernel(const void* __restrict_
     }
 }
 
-int mq_avg_tokens(const void* d_x, int x_bf16, float* d_out, int64_t n, int T, int first, int W, hipStream_t s) {
+extern "C" int mq_avg_tokens(const void* d_x, int32_t x_bf16, float* d_out, int64_t n, int32_t T, int32_t first, int32_t W, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(W % 4 == 0 && first >= 0 && first < T, "avg_tokens: bad shape W=%d T=%d first=%d", W, T, first);
     if (n <= 0) return MQ_OK;
     MqProfScope prof(4, s);
@@ -413,7 +416,8 @@ int mq_avg_tokens(const void* d_x, int x_bf16, float* d_out, int64_t n, int T, i
     return MQ_OK;
 }
 
-int mq_map_pool(const void* d_kv, const float* d_q, void* d_out, int64_t n, int T, int W, int heads, hipStream_t s) {
+extern "C" int mq_map_pool(const void* d_kv, const float* d_q, void* d_out, int64_t n, int32_t T, int32_t W, int32_t heads, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(heads >= 1 && W % heads == 0, "map_pool: W=%d heads=%d", W, heads);
     const int hd = W / heads;
     MQ_CHECK_ARG(hd % 8 == 0 && hd <= 128, "map_pool: head dim %d unsupported (multiple of 8, <= 128)", hd);
@@ -427,9 +431,10 @@ int mq_map_pool(const void* d_kv, const float* d_q, void* d_out, int64_t n, int 
     return MQ_OK;
 }
 
-int mq_embed_tokens(const int32_t* d_ids, const int32_t* d_cu, int64_t nseq, const float* tok, const float* pos,
-                    const float* type0, const float* g, const float* b, float* d_x, void* d_xb, int W, int vocab,
-                    float eps, hipStream_t s, int last_pos) {
+extern "C" int mq_embed_tokens(const int32_t* d_ids, const int32_t* d_cu, int64_t nseq, const float* tok, const float* pos, const float* type0,
+                               const float* g, const float* b, float* d_x, void* d_xb, int32_t W, int32_t vocab, float eps, int32_t last_pos,
+                               void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(W % 4 == 0 && W <= 64 * 4 * MAXC, "embed_tokens: W=%d unsupported", W);
     if (nseq <= 0) return MQ_OK;
     MqProfScope prof(3, s);
@@ -480,7 +485,9 @@ __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, con
     }
 }
 
-int mq_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int fixed_len, int Wa, int heads, const float* d_inv_freq, hipStream_t s) {
+extern "C" int mq_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t Wa, int32_t heads, const float* d_inv_freq,
+                       void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const int hs = Wa / heads;
     MQ_CHECK_ARG(hs * heads == Wa && hs % 16 == 0, "rope: head width %d must be a multiple of 16", hs);
     if (nseq <= 0) return MQ_OK;
@@ -514,7 +521,8 @@ __global__ __launch_bounds__(256) void glu_kernel(bf16_t* __restrict__ buf, int6
 }
 
 int mq_glu_il_rows(void* d_buf, int64_t rows, int F, int act, hipStream_t s);
-int mq_glu(void* d_buf, int64_t rows, int F, int act, hipStream_t s, int interleaved) {
+extern "C" int mq_glu(void* d_buf, int64_t rows, int32_t F, int32_t act, int32_t interleaved, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(F % 8 == 0 && (!interleaved || F % 16 == 0), "glu: F=%d must be a multiple of 8 (16 interleaved)", F);
     if (rows <= 0) return MQ_OK;
     MqProfScope prof(3, s);
@@ -612,7 +620,9 @@ __global__ __launch_bounds__(256) void glu_ln_kernel(bf16_t* __restrict__ buf, i
     }
 }
 
-int mq_glu_ln(void* d_buf, int64_t rows, int F, int Ft, int act, const float* g, const float* b, float eps, hipStream_t s, int mode = 0) {
+extern "C" int mq_glu_ln(void* d_buf, int64_t rows, int32_t F, int32_t Ft, int32_t act, const float* g, const float* b, float eps, int32_t mode,
+                         void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(F % 8 == 0 && F >= 8 && F <= 4096 && Ft >= 1 && Ft <= F && ((g && b) || mode == 3), "glu_ln: F=%d (a multiple of 8, <= 4096) / Ft=%d unsupported", F, Ft);
     MQ_CHECK_ARG(mode >= 0 && mode <= 3 && (mode == 0 || mode == 2 || F % 16 == 0), "glu_ln: mode %d / F=%d", mode, F);
     if (rows <= 0) return MQ_OK;
@@ -627,7 +637,7 @@ int mq_glu_ln(void* d_buf, int64_t rows, int F, int Ft, int act, const float* g,
     return MQ_OK;
 }
 // the un-normalised interleaved product (mq_glu's il form): one wave per row
-int mq_glu_il_rows(void* d_buf, int64_t rows, int F, int act, hipStream_t s) { return mq_glu_ln(d_buf, rows, F, F, act, nullptr, nullptr, 0.f, s, 3); }
+int mq_glu_il_rows(void* d_buf, int64_t rows, int F, int act, hipStream_t s) { return mq_glu_ln(d_buf, rows, F, F, act, nullptr, nullptr, 0.f, 3, s); }
 
 // ---- 2-D rotary position embedding of the EVA02 vision towers (timm RotaryEmbeddingCat + apply_rot_embed_cat) on the Q and K columns of the QKV
 // buffer, in place.  table: fp32 [T - prefix][2][hs] = (cos | sin) per rotated position, the same for every head; the first `prefix` rows of every
@@ -660,7 +670,8 @@ __global__ __launch_bounds__(256) void rope_table_kernel(bf16_t* __restrict__ qk
     }
 }
 
-int mq_rope_table(void* d_qkv, int64_t rows, int T, int prefix, int Wa, int heads, const float* d_table, hipStream_t s) {
+extern "C" int mq_rope_table(void* d_qkv, int64_t rows, int32_t T, int32_t prefix, int32_t Wa, int32_t heads, const float* d_table, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const int hs = Wa / heads;
     MQ_CHECK_ARG(hs * heads == Wa && hs % 8 == 0 && T >= 1 && prefix >= 0 && prefix <= T && rows % T == 0 && d_table,
                  "rope_table: head width %d must be a multiple of 8, rows (%ld) a multiple of the sequence length %d", hs, (long)rows, T);
@@ -673,8 +684,8 @@ int mq_rope_table(void* d_qkv, int64_t rows, int T, int prefix, int Wa, int head
     return MQ_OK;
 }
 
-int mq_pool(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_out, int W, int pool, int normalize,
-            hipStream_t s) {
+extern "C" int mq_pool(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_out, int32_t W, int32_t pool, int32_t normalize, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(W <= 2048, "pool: W=%d unsupported", W);
     if (nseq <= 0) return MQ_OK;
     MqProfScope prof(4, s);
@@ -683,7 +694,8 @@ int mq_pool(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_out, i
     return MQ_OK;
 }
 
-int mq_last_rows(const int32_t* d_cu, int32_t* d_rows, int64_t nseq, hipStream_t s) {
+extern "C" int mq_last_rows(const int32_t* d_cu, int32_t* d_rows, int64_t nseq, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     if (nseq <= 0) return MQ_OK;
     hipLaunchKernelGGL(last_rows_kernel, dim3((unsigned)cdiv64(nseq, 256)), dim3(256), 0, s, d_cu, d_rows, (int)nseq);
     MQ_CHECK_LAUNCH("last_rows");
@@ -691,7 +703,8 @@ int mq_last_rows(const int32_t* d_cu, int32_t* d_rows, int64_t nseq, hipStream_t
 }
 
 // row gather / scatter through an int32 row index (the pooled-rows-only last encoder block, towers.hip)
-int mq_move_rows(void* d_sparse, const int32_t* d_idx, void* d_dense, int64_t n, int64_t row_bytes, bool scatter, hipStream_t s) {
+extern "C" int mq_move_rows(void* d_sparse, const int32_t* d_idx, void* d_dense, int64_t n, int64_t row_bytes, int32_t scatter, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     MQ_CHECK_ARG(row_bytes % 16 == 0 && row_bytes / 16 < (1 << 30), "move_rows: row_bytes=%ld must be a multiple of 16", (long)row_bytes);
     if (n <= 0) return MQ_OK;
     MqProfScope prof(3, s);
@@ -704,7 +717,8 @@ int mq_move_rows(void* d_sparse, const int32_t* d_idx, void* d_dense, int64_t n,
     return MQ_OK;
 }
 
-int mq_cls_rows(int32_t* d_rows, int64_t n, int T, hipStream_t s) {
+extern "C" int mq_cls_rows(int32_t* d_rows, int64_t n, int32_t T, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     if (n <= 0) return MQ_OK;
     hipLaunchKernelGGL(cls_rows_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, d_rows, (int)n, T);
     MQ_CHECK_LAUNCH("cls_rows");

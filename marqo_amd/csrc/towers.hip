@@ -9,24 +9,6 @@
 
 // kernels in the sibling translation units
 int mq_cast_bf16(const float* d_x, void* d_out, int64_t n, hipStream_t s);
-int mq_patchify(const void* d_in, bool is_u8, void* d_out, int64_t n, int S, int P, int Kp,
-                const float* mean, const float* std, hipStream_t s);
-int mq_vit_assemble(const float* d_patch_out, const float* cls, const float* pos, const float* g, const float* b,
-                    float* d_x, int64_t n, int T, int W, float eps, hipStream_t s, int x_bf16 = 0);
-int mq_embed_tokens(const int32_t* d_ids, const int32_t* d_cu, int64_t nseq, const float* tok, const float* pos,
-                    const float* type0, const float* g, const float* b, float* d_x, void* d_xb, int W, int vocab,
-                    float eps, hipStream_t s, int last_pos = 0);
-int mq_pool(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_out, int W, int pool, int normalize,
-            hipStream_t s);
-int mq_last_rows(const int32_t* d_cu, int32_t* d_rows, int64_t nseq, hipStream_t s);
-int mq_cls_rows(int32_t* d_rows, int64_t n, int T, hipStream_t s);
-int mq_map_pool(const void* d_kv, const float* d_q, void* d_out, int64_t n, int T, int W, int heads, hipStream_t s);
-int mq_avg_tokens(const void* d_x, int x_bf16, float* d_out, int64_t n, int T, int first, int W, hipStream_t s);
-int mq_move_rows(void* d_sparse, const int32_t* d_idx, void* d_dense, int64_t n, int64_t row_bytes, bool scatter, hipStream_t s);
-int mq_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int fixed_len, int Wa, int heads, const float* d_inv_freq, hipStream_t s);
-int mq_glu(void* d_buf, int64_t rows, int F, int act, hipStream_t s, int interleaved = 0);
-int mq_glu_ln(void* d_buf, int64_t rows, int F, int Ft, int act, const float* g, const float* b, float eps, hipStream_t s, int mode = 0);
-int mq_rope_table(void* d_qkv, int64_t rows, int T, int prefix, int Wa, int heads, const float* d_table, hipStream_t s);
 extern "C" int mq_rowquant_fp8(const float* d_x, void* d_out_fp8, float* d_row_scale, int64_t rows, int32_t W, void* stream);
 
 // layouts the ctypes binding (marqo_amd/_lib.py) and tests/test_abi.py assume
@@ -454,8 +436,8 @@ int EncoderPass::block_eva(const mq_block_weights& b, int l) {
                    b.fc2_w, (size_t)W * F * 2, b.fc1_wf, b.fc1_bf, b.fc1_sf, row_stats, fold_mlp));
     if (cfg->mlp_glu) {
         const int mode = glu_epi ? 2 : il ? 1 : 0;
-        if (b.mlp_ln_g) MQ_TRY(mq_glu_ln(qf, rows, F, cfg->mlp_ln_dim ? cfg->mlp_ln_dim : F, cfg->act, b.mlp_ln_g, b.mlp_ln_b, cfg->ln_eps, s, mode));
-        else if (!glu_epi) MQ_TRY(mq_glu(qf, rows, F, cfg->act, s, il ? 1 : 0));
+        if (b.mlp_ln_g) MQ_TRY(mq_glu_ln(qf, rows, F, cfg->mlp_ln_dim ? cfg->mlp_ln_dim : F, cfg->act, b.mlp_ln_g, b.mlp_ln_b, cfg->ln_eps, mode, s));
+        else if (!glu_epi) MQ_TRY(mq_glu(qf, rows, F, cfg->act, il ? 1 : 0, s));
     }
     // fc2 (reads the F-wide product at the (up | gate) buffer's row stride) writes the x the NEXT block's QKV normalises
     if (fold_next) MQ_TRY(mq_gemm_bf16_rsf(qf, fc1_cols, b.fc2_w, F, b.fc2_b, d_x, d_x, W, rows, W, F, rflags, row_part, row_stats, cfg->ln_eps, band_ctr, pf(nbk->qkv_wf),
@@ -571,7 +553,7 @@ int EncoderPass::block_post_ln(const mq_block_weights& b, int l) {
     if (cfg->mlp_glu) {
         // gated MLP: fc1 = (up | gate) rows [2F, W] (bias optional), hidden = up * act(gate) in place, fc2 reads it with lda = 2F
         MQ_TRY(mq_gemm_bf16(h, W, b.fc1_w, W, b.fc1_b, nullptr, qf, 2 * F, rows, 2 * F, W, b.fc1_b ? MQ_EPI_BIAS : 0, s));
-        MQ_TRY(mq_glu(qf, rows, F, cfg->act, s));
+        MQ_TRY(mq_glu(qf, rows, F, cfg->act, 0, s));
         MQ_TRY(mq_gemm_bf16(qf, 2 * F, b.fc2_w, F, b.fc2_b, d_x, d_x, W, rows, W, F, res_flags, s));
     } else {
         MQ_TRY(mq_gemm_bf16(h, W, b.fc1_w, W, b.fc1_b, nullptr, qf, F, rows, F, W, MQ_EPI_BIAS | act_flag, s));
@@ -763,7 +745,7 @@ int encode_image_impl(const mq_vit_cfg* cfg, const mq_vit_weights* w, const void
     MQ_TRY(mq_patchify(d_pixels, is_u8, patches, n, cfg->image_size, cfg->patch_size, p.Kp, cfg->mean, cfg->std, s));
     MQ_TRY(mq_gemm_bf16(patches, p.Kp, w->patch_w, p.Kp, nullptr, nullptr, patch_out, W, n * p.np, W, p.Kp, MQ_EPI_OUT_F32, s));
     const int xb = stream_bf16(&cfg->enc) ? 1 : 0;   // residual stream in bf16 (same buffer, half of it used)
-    MQ_TRY(mq_vit_assemble(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, x, n, p.T, W, cfg->enc.ln_eps, s, xb));
+    MQ_TRY(mq_vit_assemble(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, x, n, p.T, W, cfg->enc.ln_eps, xb, s));
     if (map) {
         // K2-K5 x layers on every token, then the trunk's norm on every token and the attention-pool head:
         //   k | v = norm(x) @ kv_w^T + kv_b;  o = softmax(q k^T) v per head (one learned query);  y = o @ proj^T + b;
@@ -916,7 +898,7 @@ extern "C" int mq_encode_clip_text(const mq_clip_text_cfg* cfg, const mq_clip_te
 
     const int xb = stream_bf16(&cfg->enc) ? 1 : 0;   // residual stream in bf16: the embedding kernel writes its bf16 output into x
     MQ_TRY(mq_embed_tokens(d_ids, d_cu_seqlens, nseq, w->tok_emb, w->pos, nullptr, nullptr, nullptr, xb ? nullptr : x, xb ? (void*)x : nullptr, W,
-                           cfg->vocab, 0.f, s, cfg->cls_pos));
+                           cfg->vocab, 0.f, cfg->cls_pos, s));
     const int32_t* pool_rows = d_pool_rows;
     if (!pool_rows) { MQ_TRY(mq_last_rows(d_cu_seqlens, rows_idx, nseq, s)); pool_rows = rows_idx; }
     MQ_TRY(encoder_forward_impl(&cfg->enc, w->blocks, x, rows, d_cu_seqlens, nseq, 0, maxl, pool_rows, nseq, base + p.off_enc,
@@ -971,7 +953,7 @@ extern "C" int mq_encode_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, 
     const int W = cfg->enc.width;
 
     MQ_TRY(mq_embed_tokens(d_ids, d_cu_seqlens, nseq, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, x, nullptr, W,
-                           cfg->vocab, cfg->enc.ln_eps, s));
+                           cfg->vocab, cfg->enc.ln_eps, 0, s));
     // CLS pooling reads only the first row of every sequence (= d_cu_seqlens[0..nseq-1]); mean pooling reads them all
     const int32_t* sel = cfg->pool == MQ_POOL_CLS ? d_cu_seqlens : nullptr;
     MQ_TRY(encoder_forward_impl(&cfg->enc, w->blocks, x, rows, d_cu_seqlens, nseq, 0, maxl, sel, sel ? nseq : 0, base + p.off_enc,

@@ -86,3 +86,34 @@ def test_host_gather_checked_bounds_and_copies():
         assert np.array_equal(dst[o:o + a.nbytes], a)
     rc = lib.mq_host_gather_checked(srcs, nbytes.ctypes.data, offs.ctypes.data, 4, dst.ctypes.data, 5_001_900, 4)   # the last item would overrun
     assert rc != 0 and b"leaves" in lib.mq_last_error()
+
+
+def test_building_block_argument_errors_are_reported_without_a_gpu():
+    """csrc/embed.hip's entry points judge their shapes before any launch: each refusal returns -1 and names the problem"""
+    lib = L.load()
+    fake = 256   # a non-null operand address: never dereferenced, the argument check fails first
+
+    def refused(rc, msg):
+        assert rc == -1
+        assert msg in lib.mq_last_error(), lib.mq_last_error()
+
+    refused(lib.mq_rope(fake, None, 1, 4, 72, 1, fake, None), b"head width 72 must be a multiple of 16")
+    refused(lib.mq_rope(fake, None, 1, 4, 480, 12, fake, None), b"head width 40 must be a multiple of 16")
+    refused(lib.mq_glu_ln(fake, 4, 64, 65, L.MQ_ACT_SILU, fake, fake, 1e-6, 0, None), b"Ft=65 unsupported")
+    refused(lib.mq_glu_ln(fake, 4, 64, 64, L.MQ_ACT_SILU, fake, fake, 1e-6, 4, None), b"glu_ln: mode 4")
+    refused(lib.mq_glu_ln(fake, 4, 4104, 4104, L.MQ_ACT_SILU, fake, fake, 1e-6, 0, None), b"F=4104")
+    refused(lib.mq_glu_ln(fake, 4, 1032, 1032, L.MQ_ACT_SILU, fake, fake, 1e-6, 1, None), b"glu_ln: mode 1 / F=1032")
+    refused(lib.mq_glu_ln(fake, 4, 64, 64, L.MQ_ACT_SILU, None, None, 1e-6, 0, None), b"glu_ln: F=64")   # LayerNorm modes need g and b
+    refused(lib.mq_glu(fake, 4, 1032, L.MQ_ACT_SILU, 1, None), b"F=1032 must be a multiple of 8 (16 interleaved)")
+    refused(lib.mq_glu(fake, 4, 4608, L.MQ_ACT_SILU, 1, None), b"F=4608 > 4096")
+    refused(lib.mq_map_pool(fake, fake, fake, 1, 16, 136, 1, None), b"head dim 136 unsupported")
+    refused(lib.mq_map_pool(fake, fake, fake, 1, 4097, 768, 12, None), b"4097 tokens unsupported")
+    refused(lib.mq_map_pool(fake, fake, fake, 1, 16, 768, 7, None), b"map_pool: W=768 heads=7")
+    refused(lib.mq_pool(fake, fake, 1, fake, 2056, L.MQ_POOL_MEAN, 1, None), b"pool: W=2056 unsupported")
+    refused(lib.mq_move_rows(fake, fake, fake, 1, 24, 0, None), b"row_bytes=24 must be a multiple of 16")
+    refused(lib.mq_rope_table(fake, 10, 3, 1, 768, 12, fake, None), b"rows (10) a multiple of the sequence length 3")
+    refused(lib.mq_rope_table(fake, 9, 3, 1, 768, 12, None, None), b"rope_table:")   # no table
+    refused(lib.mq_vit_assemble(fake, fake, fake, None, None, fake, 1, 50, 2052, 1e-6, 0, None), b"vit_assemble: W=2052 unsupported")
+    refused(lib.mq_embed_tokens(fake, fake, 1, fake, None, None, None, None, fake, None, 770, 100, 1e-12, 0, None),
+            b"embed_tokens: W=770 unsupported")
+    refused(lib.mq_avg_tokens(fake, 0, fake, 1, 50, 50, 768, None), b"avg_tokens: bad shape W=768 T=50 first=50")
