@@ -29,7 +29,6 @@
 // Measured against the round 1-3 loop (bit-identical results, profiles/r04a_gemm_pl_check.txt, r04c_fold_pl_ab.txt): stand-alone -7 % at 8192^3,
 // -5.7 % ViT-L/14 fc1, +2 % at the ViT-B/32 shapes; inside the towers (cold weights, real launch sequence) +2.9 % ViT-B/32, +2.6 % ViT-L/14,
 // +1.9 % CLIP text embeddings/s.
-#include <stdlib.h>
 #include <map>
 #include <mutex>
 #include <string>
@@ -37,9 +36,8 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm_loop.h"
+#include "gemm_sched.h"
 
-extern mq_knob mq_gemm_fp8_force_mt;  // gemm_fp8.hip
-extern mq_knob mq_gemm_fp8_big;       // gemm_fp8.hip: 0 = plan, 1 = never the big tile, 3 = always
 extern mq_knob mq_tower_row_select;   // towers.hip
 extern mq_knob mq_tower_ln_fold;      // towers.hip
 extern mq_knob mq_tower_subln_fold;
@@ -56,8 +54,7 @@ int mq_gemm_small(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, co
                   int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, hipStream_t s);
 // gemm_wd.hip: the W-direct main loop on the same tile plan (-1: combination not instantiated, the caller launches its own kernel)
 int mq_gemm_wd_launch(int flags, int mt, int ns, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out,
-                      int64_t ldc, int M, int N, int K, int tiles_n, int num_tiles, int cgroup, int band_rows, int grid, int wide, unsigned a_bytes,
-                      unsigned w_bytes, const GemmLn& ln, hipStream_t s);
+                      int64_t ldc, int M, int N, int K, const GemmGeom& g, int wide, const GemmLn& ln, hipStream_t s);
 
 int mq_device_ok();   // runtime.hip
 
@@ -111,30 +108,8 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_n
                         : (FLAGS & MQ_EPI_OUT_F32) ? (MT <= 3 ? MT : (MT + 1) / 2) : (MT <= 5 ? MT : 3);
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // ---- XCD-aware, bijective (virtual) block -> tile map, L2-blocked order inside an XCD's share (as in rounds 1-3) --------------
-    const int q = num_tiles >> 3, r = num_tiles & 7;
-    const int tiles_m = (M + BM - 1) / BM;
-    auto tile_origin = [&](int vbid, int& m0, int& n0) {
-        const int xcd = vbid & 7, idx = vbid >> 3;
-        const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        int tm, tn;
-        if (cgroup > 0) {
-            const int band_tiles = band_rows * tiles_n;
-            const int band = tile / band_tiles, rb = tile - band * band_tiles;
-            const int rows_here = min(band_rows, tiles_m - band * band_rows);
-            const int full = rows_here * cgroup, ncg_full = tiles_n / cgroup;
-            int cg = rb / full, r2 = rb - cg * full, cw = cgroup;
-            if (cg >= ncg_full) { cg = ncg_full; r2 = rb - ncg_full * full; cw = tiles_n - ncg_full * cgroup; }
-            const int rr = r2 / cw;
-            tm = band * band_rows + rr;
-            tn = cg * cgroup + (r2 - rr * cw);
-        } else {
-            tm = tile / tiles_n;
-            tn = tile - tm * tiles_n;
-        }
-        m0 = tm * BM;
-        n0 = tn * BN;
-    };
+    // ---- the (virtual) block -> tile map (gemm_loop.h)
+    const GemmTileMap<BM, BN> tile_map(num_tiles, tiles_n, M, cgroup, band_rows);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -171,7 +146,7 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_n
     const bool has_main = !TAIL || (int)blockIdx.x < num_tiles;   // (TAIL: the grid is always the 256 workgroups; few full tiles may leave some without one)
     if (has_main) {
         int m0, n0;
-        tile_origin(d_vbid, m0, n0);
+        tile_map.origin(d_vbid, m0, n0);
         set_sources(m0, n0);
     } else {
         a_rec = 0; w_rec = 0;
@@ -198,7 +173,7 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_n
             d_vbid += gridDim.x;
             if (d_vbid < num_tiles) {
                 int m0, n0;
-                tile_origin(d_vbid, m0, n0);
+                tile_map.origin(d_vbid, m0, n0);
                 set_sources(m0, n0);
             } else {
                 a_rec = 0; w_rec = 0;
@@ -309,7 +284,7 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_n
 
     if (has_main) for (;;) {
         int cm0, cn0;
-        tile_origin(c_vbid, cm0, cn0);
+        tile_map.origin(c_vbid, cm0, cn0);
 #pragma unroll
         for (int h = 0; h < NH; ++h)
 #pragma unroll
@@ -466,50 +441,12 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_n
 __attribute__((used)) void* mq_gemm_probe() { return (void*)gemm_nt_kernel<MQ_GEMM_PROBE, MQ_GEMM_PROBE_MT, MQ_GEMM_PROBE_NH, MQ_GEMM_PROBE_WM, 2>; }
 }  // namespace
 #else
-constexpr int RESIDENT_SLOTS = 512;       // 256 CUs x 2 workgroups (NH = 1)
-constexpr int RESIDENT_SLOTS_WIDE = 256;  // 256 CUs x 1 workgroup (NH = 2: 120 KiB of LDS)
-
-// tuning knobs: initialised from the environment (MQ_GEMM_MT / _CGROUP / _NH), overridable through mq_tune()
-struct GemmTune {
-    // tail: the big tile's in-kernel tail (GemmSk).  OFF by default: its rows carry a differently associated k-sum, so an embedding's bits would
-    // depend on whether its tokens sit in the last partial row tile of a batch — the towers promise the same bits wherever an item stands
-    // (tests/test_towers_gpu.py permutation equivariance; the coalescer and the ingest merging lean on it) — for +1.6 % / +3.9 % on the ViT-L/14 rows
-    // (profiles/r05p).  mq_tune("gemm_tail", 1) / MQ_GEMM_TAIL=1 turns it on; without it a ragged last row tile is a tile like any other.
-    // wd: the W-direct main loop (gemm_wd.hip) on the narrow tiles: 0 = off, 2 / 3 = on with that many LDS stages of A
-    // rs_fin: the residual GEMMs of the bf16 stream finalise the row statistics inside their own launch (mq_gemm_bf16_rsf; 0 = a row_stats_finalize_kernel
-    // launch behind them, the round 4-5 form)
-    mq_knob mt, cgroup, nh, tail, wd, rs_fin;
-    static int env(const char* k, int d) { const char* v = getenv(k); return v ? atoi(v) : d; }
-    GemmTune() : mt(env("MQ_GEMM_MT", 0)), cgroup(env("MQ_GEMM_CGROUP", 8)), nh(env("MQ_GEMM_NH", 0)), tail(env("MQ_GEMM_TAIL", 0)), wd(env("MQ_GEMM_WD", 0)), rs_fin(env("MQ_GEMM_RS_FIN", 0)) {}
-};
-GemmTune g_tune;
 }  // namespace
-// mirrors of the knobs for gemm_fp8.hip
-mq_knob mq_gemm_knob_persist{1}, mq_gemm_knob_cgroup{(int)g_tune.cgroup}, mq_gemm_knob_wide{2};
+GemmTune g_tune;   // gemm_sched.h
 // operands are addressed through 32-bit buffer offsets: bytes below 4 GiB per launch and operand; a taller A goes in row chunks.
 // mq_tune("gemm_addr_limit_mb", v) lowers it so that the chunking can be tested at small sizes (0 = back to 4 GiB).
 std::atomic<uint64_t> mq_gemm_addr_limit{0xffffffffull};
 namespace {
-
-// pick the tile height: minimise rounds x (MT + fixed per-tile overhead in 16-row units).  The tile HEIGHT is a free parameter because rows
-// are guarded anyway; this removes most of the tile-quantisation loss at the towers' shapes (M = 12 800, N = 768: 600 128-row tiles = 2
-// rounds on 512 slots, 480 160-row tiles = 1 round).
-int choose_mt(int M, int N) {
-    constexpr int BN = 128;
-    const int tiles_n = (N + BN - 1) / BN;
-    const int cands[4] = {2, 4, 5, 6};
-    int best = 4;
-    double best_cost = 1e30;
-    for (int c = 0; c < 4; ++c) {
-        const int mt = cands[c];
-        const int bm = 32 * mt;
-        const int64_t tiles = (int64_t)((M + bm - 1) / bm) * tiles_n;
-        const int64_t rounds = (tiles + RESIDENT_SLOTS - 1) / RESIDENT_SLOTS;
-        const double cost = (double)rounds * (mt + 1.25);
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = mt; }
-    }
-    return best;
-}
 
 // ---- workspace of the big tile's in-kernel tail (GemmSk): partial-sum slots + flags, one block per HIP stream (launches on a stream are ordered, so
 // its slots are free again when the next launch starts; request threads own their streams).  Allocated on a stream's first big-tile launch with a
@@ -551,6 +488,14 @@ int sk_workspace(hipStream_t s, GemmSk& out) {
     return MQ_OK;
 }
 
+// GemmLn of the rows from r on.  The band counters advance by the row bands (row tiles x waves along M) of the launch that covered the earlier rows.
+GemmLn ln_rows_from(GemmLn ln, int64_t r, int64_t bands) {
+    if (ln.rowstats) ln.rowstats += r;
+    if (ln.partials) ln.partials += r;   // (slot-major: a row offset is a row offset)
+    if (ln.band_ctr) { ln.band_ctr += bands; ln.stats_out += r; }
+    return ln;
+}
+
 template <int FLAGS, int MT, int NH = 1, int ORD = 2, int WM = 2>
 int launch_gemm_mt(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out, int64_t ldc,
                    int M, int N, int K, hipStream_t s, const GemmLn& ln) {
@@ -565,53 +510,26 @@ int launch_gemm_mt(const void* A, int64_t lda, const void* W, int64_t ldw, const
     }
     // 16-byte bf16 epilogue stores need 16-B aligned rows
     const int wide = (!(FLAGS & MQ_EPI_OUT_F32) && ldc % 8 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-    const uint64_t lim = mq_gemm_addr_limit;   // rows x leading dimension x 2 B per launch
-    const uint64_t w_bytes = ((uint64_t)(N - 1) * (uint64_t)ldw + (uint64_t)K) * 2;
-    if (w_bytes > lim) {
-        mq_set_error("mq_gemm_bf16: weight matrix of %llu bytes exceeds the %llu bytes a launch can address", (unsigned long long)w_bytes, (unsigned long long)lim);
-        return MQ_ERR_INVALID;
-    }
-    // ... and a taller A goes in row chunks (rows are independent; whole tiles per chunk)
-    int64_t max_rows = (uint64_t)K * 2 > lim ? 0 : (int64_t)((lim - (uint64_t)K * 2) / ((uint64_t)lda * 2)) + 1;
-    max_rows = max_rows / BM * BM;
-    if (max_rows < BM) {
-        mq_set_error("mq_gemm_bf16: lda=%ld too large", (long)lda);
-        return MQ_ERR_INVALID;
-    }
-    const int tiles_n = (N + BN - 1) / BN;
-    for (int64_t r0 = 0; r0 < M; r0 += max_rows) {
-        const int m = (int)((M - r0) < max_rows ? (M - r0) : max_rows);
+    return gemm_row_chunks("mq_gemm_bf16", M, N, K, lda, ldw, 2, BM, BN, SLOTS, [&](int64_t r0, int m, GemmGeom g) {
         // big tile: a ragged last row of tiles is not a round of its own but the in-kernel tail (GemmSk), cut along K over the whole grid
         GemmSk sk{};
-        int tiles_m = (m + BM - 1) / BM;
         if constexpr (WM == 4) {
             const int nk = K / BK;
-            if (g_tune.tail && m % BM != 0 && m >= BM && tiles_n <= SLOTS && MT * NH == 8) {
-                if (int rc = sk_workspace(s, sk); rc != MQ_OK) return rc;
+            if (g_tune.tail && m % BM != 0 && m >= BM && g.tiles_n <= SLOTS && MT * NH == 8) {
+                MQ_TRY(sk_workspace(s, sk));
                 if (sk.partials) {                                 // (nullptr: refused — a second stream of this device uses the tail)
                     int S = 8;                                     // ranges per tail tile: a power of two <= 8 (the tile's 8 regions are shared out over them)
-                    while (S > 1 && (S * tiles_n > SLOTS || S > nk)) S >>= 1;
+                    while (S > 1 && (S * g.tiles_n > SLOTS || S > nk)) S >>= 1;
                     sk.tail_splits = S;
-                    tiles_m = m / BM;
+                    g.set_tiles_m(m / BM, SLOTS);
+                    g.grid = SLOTS;
                 }
             }
         }
-        const int num_tiles = tiles_m * tiles_n;
-        // L2 blocking only when there is something to block: more column tiles than one group and at least two row panels per XCD
-        const int knob_cgroup = g_tune.cgroup;
-        const int cgroup = (knob_cgroup > 0 && tiles_n > knob_cgroup && tiles_m >= 16) ? knob_cgroup : 0;
-        const int band_rows = (tiles_m + 7) / 8;
-        const int grid = sk.tail_splits > 0 ? SLOTS : (num_tiles > SLOTS ? SLOTS : num_tiles);
-        const uint64_t a_bytes = ((uint64_t)(m - 1) * (uint64_t)lda + (uint64_t)K) * 2;
-        const size_t out_row = (size_t)ldc * ((FLAGS & MQ_EPI_OUT_F32) ? 4 : 2);
-        const size_t res_row = (size_t)ldc * (((FLAGS & MQ_EPI_RESIDUAL) && !(FLAGS & MQ_EPI_OUT_F32)) ? 2 : 4);
-        GemmLn ln_chunk = ln;
-        if (ln_chunk.rowstats) ln_chunk.rowstats += r0;
-        if (ln_chunk.partials) ln_chunk.partials += r0;   // (slot-major: a row offset is a row offset)
+        const GemmRows v = gemm_rows_from<FLAGS, 2>(r0, A, lda, residual, out, ldc);
+        GemmLn ln_chunk = ln_rows_from(ln, r0, (r0 / BM) * WM);
         if (ln_chunk.band_ctr) {   // in-launch finalise: this launch's row bands (chunks are whole tiles), every wave of a band's column tiles arrives once
-            ln_chunk.band_ctr += (r0 / BM) * WM;
-            ln_chunk.stats_out += r0;
-            ln_chunk.band_target = tiles_n * 2;
+            ln_chunk.band_target = g.tiles_n * 2;
             if (sk.tail_splits > 0) {
                 mq_set_error("mq_gemm_bf16: the in-launch row-statistics finalise and the in-kernel tail exclude each other");
                 return MQ_ERR_INVALID;
@@ -619,18 +537,15 @@ int launch_gemm_mt(const void* A, int64_t lda, const void* W, int64_t ldw, const
         }
         if constexpr (NH == 1 && WM == 2) {
             if (const int wd = g_tune.wd; (wd == 2 || wd == 3 || wd == 6 || wd == 7) && !ln_chunk.band_ctr) {
-                const int rc = mq_gemm_wd_launch(FLAGS, MT, wd, (const bf16_t*)A + r0 * lda, lda, W, ldw, bias,
-                                                 residual ? (const float*)((const char*)residual + (size_t)r0 * res_row) : nullptr, (void*)((char*)out + (size_t)r0 * out_row),
-                                                 ldc, m, N, K, tiles_n, num_tiles, cgroup, band_rows, grid, wide, (unsigned)a_bytes, (unsigned)w_bytes, ln_chunk, s);
-                if (rc >= 0) { if (rc != MQ_OK) return rc; continue; }
+                const int rc = mq_gemm_wd_launch(FLAGS, MT, wd, v.A, lda, W, ldw, bias, v.residual, v.out, ldc, m, N, K, g, wide, ln_chunk, s);
+                if (rc >= 0) return rc;
             }
         }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * WM), LDS, s, (const bf16_t*)A + r0 * lda, lda, (const bf16_t*)W, ldw, bias,
-                           residual ? (const float*)((const char*)residual + (size_t)r0 * res_row) : nullptr, (void*)((char*)out + (size_t)r0 * out_row),
-                           ldc, m, N, K, tiles_n, num_tiles, cgroup, band_rows, wide, (unsigned)a_bytes, (unsigned)w_bytes, ln_chunk, sk);
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(128 * WM), LDS, s, (const bf16_t*)v.A, lda, (const bf16_t*)W, ldw, bias, v.residual, v.out, ldc, m, N, K,
+                           g.tiles_n, g.num_tiles, g.cgroup, g.band_rows, wide, g.a_bytes, g.w_bytes, ln_chunk, sk);
         MQ_CHECK_LAUNCH("mq_gemm_bf16");
-    }
-    return MQ_OK;
+        return MQ_OK;
+    });
 }
 
 // ---- the BIG tile: 256 x 256 x 64 as 8 waves (gemm_nt_kernel WM = 4, MT = 4, NH = 2), one workgroup per CU, two waves per SIMD --------------------
@@ -710,26 +625,29 @@ int launch_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const fl
     MQ_TRY(mq_device_ok());   // 256 CUs in 8 XCDs or nothing (runtime.hip)
     const int big_rows = plan_big_rows(M, N, K);
     if (big_rows >= M) return launch_gemm_mt<FLAGS, 4, 2, 2, 4>(A, lda, W, ldw, bias, residual, out, ldc, M, N, K, s, ln);
+    GemmLn ln_narrow = ln;
     if (big_rows > 0) {
         // leading rows on the big tile, the rest on the narrow one (rows are independent: row-offset views of every row-indexed operand)
-        if (int rc = launch_gemm_mt<FLAGS, 4, 2, 2, 4>(A, lda, W, ldw, bias, residual, out, ldc, big_rows, N, K, s, ln); rc != MQ_OK) return rc;
-        const size_t out_row = (size_t)ldc * ((FLAGS & MQ_EPI_OUT_F32) ? 4 : 2);
-        const size_t res_row = (size_t)ldc * (((FLAGS & MQ_EPI_RESIDUAL) && !(FLAGS & MQ_EPI_OUT_F32)) ? 2 : 4);
-        GemmLn ln2 = ln;
-        if (ln2.rowstats) ln2.rowstats += big_rows;
-        if (ln2.partials) ln2.partials += big_rows;
-        if (ln2.band_ctr) { ln2.band_ctr += (big_rows / 256) * 4; ln2.stats_out += big_rows; ln2.pf_na = ln2.pf_nb = 0; }   // (the first launch carried the prefetch)
-        A = (const bf16_t*)A + (int64_t)big_rows * lda;
-        if (residual) residual = (const float*)((const char*)residual + (size_t)big_rows * res_row);
-        out = (char*)out + (size_t)big_rows * out_row;
+        MQ_TRY((launch_gemm_mt<FLAGS, 4, 2, 2, 4>(A, lda, W, ldw, bias, residual, out, ldc, big_rows, N, K, s, ln)));
+        const GemmRows v = gemm_rows_from<FLAGS, 2>(big_rows, A, lda, residual, out, ldc);
+        A = v.A; residual = v.residual; out = v.out;
         M -= big_rows;
-        const int knob_mt2 = g_tune.mt;
-        const int mt2 = knob_mt2 ? knob_mt2 : choose_mt(M, N);
-        return launch_narrow<FLAGS>(mt2, A, lda, W, ldw, bias, residual, out, ldc, M, N, K, s, ln2);
+        ln_narrow = ln_rows_from(ln, big_rows, (big_rows / 256) * 4);
+        ln_narrow.pf_na = ln_narrow.pf_nb = 0;   // (the first launch carried the weight prefetch)
     }
     const int knob_mt = g_tune.mt;
     const int mt = knob_mt ? knob_mt : choose_mt(M, N);
-    return launch_narrow<FLAGS>(mt, A, lda, W, ldw, bias, residual, out, ldc, M, N, K, s, ln);
+    return launch_narrow<FLAGS>(mt, A, lda, W, ldw, bias, residual, out, ldc, M, N, K, s, ln_narrow);
+}
+
+// the shape and layout checks of the bf16 entry points (before any launch or device query); `who` names the entry point
+int check_shape(const char* who, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc) {
+    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK, "%s: bad shape M=%ld N=%ld K=%ld", who, (long)M, (long)N, (long)K);
+    MQ_CHECK_ARG(K % BK == 0, "%s: K=%ld must be a multiple of %d", who, (long)K, BK);
+    MQ_CHECK_ARG(N % 4 == 0, "%s: N=%ld must be a multiple of 4", who, (long)N);
+    MQ_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "%s: leading dims must keep 16-byte rows", who);
+    MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "%s: shape too large", who);
+    return MQ_OK;
 }
 
 }  // namespace
@@ -738,11 +656,7 @@ extern "C" int mq_gemm_bf16(const void* d_A, int64_t lda, const void* d_W, int64
                             const float* d_bias, const float* d_residual, void* d_out, int64_t ldc,
                             int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     MQ_CHECK_ARG(d_A && d_W && d_out, "mq_gemm_bf16: null operand");
-    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK, "mq_gemm_bf16: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-    MQ_CHECK_ARG(K % BK == 0, "mq_gemm_bf16: K=%ld must be a multiple of %d", (long)K, BK);
-    MQ_CHECK_ARG(N % 4 == 0, "mq_gemm_bf16: N=%ld must be a multiple of 4", (long)N);
-    MQ_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "mq_gemm_bf16: leading dims must keep 16-byte rows");
-    MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "mq_gemm_bf16: shape too large");
+    MQ_TRY(check_shape("mq_gemm_bf16", M, N, K, lda, ldw, ldc));
     MQ_CHECK_ARG(!(flags & MQ_EPI_BIAS) || d_bias, "mq_gemm_bf16: MQ_EPI_BIAS without bias");
     MQ_CHECK_ARG(!(flags & MQ_EPI_RESIDUAL) || d_residual, "mq_gemm_bf16: MQ_EPI_RESIDUAL without residual");
     MQ_CHECK_ARG(!(flags & MQ_EPI_GLU) || N % 32 == 0, "mq_gemm_bf16: MQ_EPI_GLU needs N %% 32 == 0 (16 up + 16 gate rows per group)");
@@ -781,10 +695,8 @@ extern "C" int mq_gemm_bf16(const void* d_A, int64_t lda, const void* d_W, int64
 extern "C" int mq_gemm_bf16_ln(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const float* d_colsum,
                                const float* d_rowstats, void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     MQ_CHECK_ARG(d_A && d_W && d_out && d_bias && d_colsum && d_rowstats, "mq_gemm_bf16_ln: null operand");
-    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK && K % BK == 0 && N % 4 == 0, "mq_gemm_bf16_ln: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+    MQ_TRY(check_shape("mq_gemm_bf16_ln", M, N, K, lda, ldw, ldc));
     MQ_CHECK_ARG(!(flags & MQ_EPI_GLU) || N % 32 == 0, "mq_gemm_bf16_ln: MQ_EPI_GLU needs N %% 32 == 0");
-    MQ_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "mq_gemm_bf16_ln: leading dims must keep 16-byte rows");
-    MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "mq_gemm_bf16_ln: shape too large");
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(0, s, 2.0 * (double)M * (double)N * (double)K);
     const int m = (int)M, n = (int)N, k = (int)K;
@@ -811,9 +723,7 @@ extern "C" int mq_gemm_bf16_rs(const void* d_A, int64_t lda, const void* d_W, in
                                int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, float* d_partials, void* stream) {
     MQ_CHECK_ARG(d_A && d_W && d_out && d_bias && d_residual && d_partials, "mq_gemm_bf16_rs: null operand");
     MQ_CHECK_ARG((flags | MQ_EPI_ROW_STATS) == (MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_ROW_STATS), "mq_gemm_bf16_rs: flags must be MQ_EPI_BIAS | MQ_EPI_RESIDUAL");
-    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK && K % BK == 0 && N % 4 == 0, "mq_gemm_bf16_rs: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-    MQ_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "mq_gemm_bf16_rs: leading dims must keep 16-byte rows");
-    MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "mq_gemm_bf16_rs: shape too large");
+    MQ_TRY(check_shape("mq_gemm_bf16_rs", M, N, K, lda, ldw, ldc));
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(0, s, 2.0 * (double)M * (double)N * (double)K);
     GemmLn ln{};
@@ -835,10 +745,8 @@ extern "C" int mq_gemm_bf16_lnrs(const void* d_A, int64_t lda, const void* d_W, 
     MQ_CHECK_ARG(d_A && d_W && d_out && d_bias && d_colsum && d_rowstats && d_partials, "mq_gemm_bf16_lnrs: null operand");
     MQ_CHECK_ARG(flags == (MQ_EPI_BIAS | MQ_EPI_RESIDUAL) || flags == (MQ_EPI_BIAS | MQ_EPI_GLU), "mq_gemm_bf16_lnrs: flags must be MQ_EPI_BIAS | MQ_EPI_RESIDUAL or MQ_EPI_BIAS | MQ_EPI_GLU");
     MQ_CHECK_ARG(!(flags & MQ_EPI_RESIDUAL) || d_residual, "mq_gemm_bf16_lnrs: MQ_EPI_RESIDUAL without residual");
-    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK && K % BK == 0 && N % 4 == 0, "mq_gemm_bf16_lnrs: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+    MQ_TRY(check_shape("mq_gemm_bf16_lnrs", M, N, K, lda, ldw, ldc));
     MQ_CHECK_ARG(!(flags & MQ_EPI_GLU) || N % 32 == 0, "mq_gemm_bf16_lnrs: MQ_EPI_GLU needs N %% 32 == 0");
-    MQ_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "mq_gemm_bf16_lnrs: leading dims must keep 16-byte rows");
-    MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "mq_gemm_bf16_lnrs: shape too large");
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(0, s, 2.0 * (double)M * (double)N * (double)K);
     GemmLn ln{};
@@ -866,9 +774,7 @@ extern "C" int mq_gemm_bf16_rsf(const void* d_A, int64_t lda, const void* d_W, i
                                 uint32_t* d_band_ctr, const void* d_pf_a, size_t pf_a_bytes, const void* d_pf_b, size_t pf_b_bytes, void* stream) {
     MQ_CHECK_ARG(d_A && d_W && d_out && d_bias && d_residual && d_partials && d_stats, "mq_gemm_bf16_rsf: null operand");
     MQ_CHECK_ARG((flags | MQ_EPI_ROW_STATS) == (MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_ROW_STATS), "mq_gemm_bf16_rsf: flags must be MQ_EPI_BIAS | MQ_EPI_RESIDUAL");
-    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK && K % BK == 0 && N % 4 == 0, "mq_gemm_bf16_rsf: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-    MQ_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "mq_gemm_bf16_rsf: leading dims must keep 16-byte rows");
-    MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "mq_gemm_bf16_rsf: shape too large");
+    MQ_TRY(check_shape("mq_gemm_bf16_rsf", M, N, K, lda, ldw, ldc));
     hipStream_t s = (hipStream_t)stream;
     const int nslots = (int)((N + 63) / 64);
     const bool in_launch = d_band_ctr && g_tune.rs_fin && !g_tune.tail;
@@ -907,9 +813,9 @@ extern "C" int mq_gemm_bf16_rsf(const void* d_A, int64_t lda, const void* d_W, i
 extern "C" int mq_tune(const char* key, int value) {
     MQ_CHECK_ARG(key, "mq_tune: null key");
     const std::string k(key);
-    if (k == "gemm_mt") { g_tune.mt = value; mq_gemm_fp8_force_mt = value; }
-    else if (k == "gemm_cgroup") { g_tune.cgroup = value; mq_gemm_knob_cgroup = value; }
-    else if (k == "gemm_nh") { g_tune.nh = value; mq_gemm_fp8_big = value == 4 ? 0 : value; }
+    if (k == "gemm_mt") g_tune.mt = value;   // (the bf16 and the fp8 tiles)
+    else if (k == "gemm_cgroup") g_tune.cgroup = value;
+    else if (k == "gemm_nh") { g_tune.nh = value; g_tune.fp8_big = value == 4 ? 0 : value; }
     else if (k == "gemm_tail") g_tune.tail = value;
     else if (k == "gemm_wd") g_tune.wd = value;
     else if (k == "rs_finalize") g_tune.rs_fin = value;

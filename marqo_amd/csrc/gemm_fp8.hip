@@ -8,7 +8,7 @@
 // at twice the bf16 rate (the non-scaled 16x16x32_fp8 runs at the bf16 rate), and fp8 operands halve the bytes moved
 // through the LDS-DMA path and the LDS, which is what bounds the bf16 kernel.
 //
-// Structure = gemm_bf16.hip (one design, round 4): (32*MT)x128 tile, 4 wave64s as 2x2, BK = 128 elements (= the same 128-B LDS rows), a 2-stage
+// Structure = gemm_bf16.hip (one design, round 4): (32*MT)x128 tile, 4 wave64s as 2x2, BK8 = 128 elements (= the same 128-B LDS rows), a 2-stage
 // LDS ring filled by buffer-descriptor LDS-DMA two stages ahead of the MFMAs (a cursor that walks over tile boundaries, so a tile's first stages
 // land during the previous tile's epilogue), fragment reads as inline-asm ds_read_b128 with hand-placed waits, ONE barrier per k-step placed
 // mid-step, persistent XCD-aware tile walk, operands fed swapped so a lane owns 4 consecutive n.  A lane's fragment is 32 consecutive k-bytes
@@ -22,50 +22,28 @@
 //   half B  2 MT MFMAs (mt, nt = 2 | 3), row group by row group; behind row group mt's last MFMA the read of the NEXT stage's A fragment mt
 //           into the same registers (an MFMA has read its operands long before a ds_read issued behind it returns), the next stage's W
 //           sub-tiles 0, 1, and the LDS-DMA pieces of the stage after next into the buffer this step has finished with
-#include <stdlib.h>
-#include <type_traits>
 #include "common.h"
+#include "gemm_loop.h"
+#include "gemm_sched.h"
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
-// scheduling knobs shared with gemm_bf16.hip (mq_tune "gemm_cgroup"; the widened epilogue stores are always on)
-extern mq_knob mq_gemm_knob_cgroup, mq_gemm_knob_wide;
 int mq_device_ok();   // runtime.hip
-extern std::atomic<uint64_t> mq_gemm_addr_limit;   // gemm_bf16.hip: bytes one launch may address per operand (4 GiB - 1; tests lower it)
-
-mq_knob mq_gemm_fp8_big{getenv("MQ_GEMM_FP8_NH") ? atoi(getenv("MQ_GEMM_FP8_NH")) : 0};   // mq_tune("gemm_nh", v) sets it too (gemm_bf16.hip)
 
 namespace {
 
-constexpr int BK = 128;                    // BK in fp8 elements == bytes
+constexpr int BK8 = 128;                   // the fp8 k-step, in elements == bytes
 constexpr int UNIT_SCALE = 0x7F7F7F7F;     // e8m0 127 = 2^0 in every byte
-constexpr int RESIDENT_SLOTS = 512;        // 256 CUs x 2 workgroups
-constexpr int RESIDENT_SLOTS_BIG = 256;    // the 8-wave 256 x 256 tile: one workgroup per CU
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff, unsigned lds_wave_base) {
-    // 16 B per lane; LDS destination = wave-uniform base (M0) + lane * 16; source = descriptor base + voff (per lane) + soff (scalar)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(uintptr_t)lds_wave_base, 16, voff, soff, 0, 0);
-}
 // a 32-byte fragment = two ds_read_b128 (logical chunks 2g, 2g + 1 of the lane's row) as inline asm: hipcc cannot tell a compiler-visible LDS
 // read from the LDS-DMA writes in flight and would put s_waitcnt vmcnt(0) in front of every one (gemm_bf16.hip)
 template <int OFF>
 __device__ __forceinline__ i32x8 lds_read32(unsigned addr0, unsigned addr1) {
-    i32x4_t lo, hi;
+    i32x4 lo, hi;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(lo) : "v"(addr0), "n"(OFF));
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(hi) : "v"(addr1), "n"(OFF));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-// ties the consumers of an asm-read fragment to the hand-placed s_waitcnt by data flow (gemm_bf16.hip, `landed`)
-template <class T>
-__device__ __forceinline__ void landed(T& v) { asm volatile("" : "+v"(v)); }
-
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
 // chunk swizzle: u = (row >> 1) & 7;  f = u for u in {0,1,6,7}, u ^ 2 for u in {2,3,4,5}
 __device__ __forceinline__ int fswz(int row) {
@@ -94,34 +72,12 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_f
     constexpr int BM = 16 * MT * WM, BN = 128 * NH;
     constexpr int NTW = 4 * NH;                 // 16-column W sub-tiles per wave (a wave spans half of BN)
     constexpr int HW = NTW / 2;                 // ... per half of the k-step
-    constexpr int A_TILE_BYTES = BM * BK, W_TILE_BYTES = BN * BK;
+    constexpr int A_TILE_BYTES = BM * BK8, W_TILE_BYTES = BN * BK8;
     constexpr int STAGE_BYTES = A_TILE_BYTES + W_TILE_BYTES;
     constexpr int NPW = 8 * NH / WM;            // W pieces (8 rows x 128 B) per wave per stage: BN / (2 WM) rows
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    const int q = num_tiles >> 3, r = num_tiles & 7;
-    const int tiles_m = (M + BM - 1) / BM;
-    auto tile_origin = [&](int vbid, int& m0, int& n0) {  // XCD-aware + L2-blocked map, see gemm_bf16.hip
-        const int xcd = vbid & 7, idx = vbid >> 3;
-        const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        int tm, tn;
-        if (cgroup > 0) {
-            const int band_tiles = band_rows * tiles_n;
-            const int band = tile / band_tiles, rb = tile - band * band_tiles;
-            const int rows_here = min(band_rows, tiles_m - band * band_rows);
-            const int full = rows_here * cgroup, ncg_full = tiles_n / cgroup;
-            int cg = rb / full, r2 = rb - cg * full, cw = cgroup;
-            if (cg >= ncg_full) { cg = ncg_full; r2 = rb - ncg_full * full; cw = tiles_n - ncg_full * cgroup; }
-            const int rr = r2 / cw;
-            tm = band * band_rows + rr;
-            tn = cg * cgroup + (r2 - rr * cw);
-        } else {
-            tm = tile / tiles_n;
-            tn = tile - tm * tiles_n;
-        }
-        m0 = tm * BM;
-        n0 = tn * BN;
-    };
+    const GemmTileMap<BM, BN> tile_map(num_tiles, tiles_n, M, cgroup, band_rows);   // gemm_loop.h
 
     constexpr int NL = MT + NPW;   // LDS-DMA pieces (8 rows x 128 B) per wave per stage
     constexpr int NB = HW * MT;    // MFMAs per wave per half
@@ -149,20 +105,20 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_f
             w_vo[i] = (unsigned)gn * (unsigned)ldw + (unsigned)(((lane & 7) ^ fswz(row)) * 16);
         }
     };
-    const int nk = K / BK;
+    const int nk = K / BK8;
     // DMA cursor: (tile d_vbid, k-step d_k) of the next stage to request, two stages ahead of the MFMAs; past the workgroup's last tile the
     // descriptors' sizes drop to 0 (the two trailing requests are out of range for every lane: no traffic, no second k-step variant)
     int d_vbid = blockIdx.x, d_k = 0;
     unsigned a_rec = a_bytes, w_rec = w_bytes;
     {
         int m0, n0;
-        tile_origin(d_vbid, m0, n0);
+        tile_map.origin(d_vbid, m0, n0);
         set_sources(m0, n0);
     }
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned dma_a0 = lds0 + (unsigned)wave * (8 * MT * 128), dma_w0 = lds0 + A_TILE_BYTES + (unsigned)wave * (8 * NPW * 128);   // scalars
     auto issue_piece = [&](int i, unsigned bufoff) {
-        const unsigned soff = (unsigned)d_k * BK;
+        const unsigned soff = (unsigned)d_k * BK8;
         if (i < MT) dma16(__builtin_amdgcn_make_buffer_rsrc((void*)A, 0, a_rec, 0x00020000), a_vo[i < MT ? i : 0], soff, dma_a0 + bufoff + (unsigned)i * 1024u);
         else dma16(__builtin_amdgcn_make_buffer_rsrc((void*)Wt, 0, w_rec, 0x00020000), w_vo[i >= MT ? i - MT : 0], soff, dma_w0 + bufoff + (unsigned)(i - MT) * 1024u);
     };
@@ -172,7 +128,7 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_f
             d_vbid += gridDim.x;
             if (d_vbid < num_tiles) {
                 int m0, n0;
-                tile_origin(d_vbid, m0, n0);
+                tile_map.origin(d_vbid, m0, n0);
                 set_sources(m0, n0);
             } else {
                 a_rec = 0; w_rec = 0;
@@ -283,7 +239,7 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_f
 
     for (;;) {
         int cm0, cn0;
-        tile_origin(c_vbid, cm0, cn0);
+        tile_map.origin(c_vbid, cm0, cn0);
 #pragma unroll
         for (int h = 0; h < NH; ++h)
 #pragma unroll
@@ -473,22 +429,6 @@ __global__ __launch_bounds__(128 * WM, (NH == 1 && WM == 2) ? 2 : 1) void gemm_f
 __attribute__((used)) void* mq_gemm_fp8_probe() { return (void*)gemm_fp8_kernel<MQ_GEMM_PROBE, MQ_GEMM_PROBE_MT, (MQ_GEMM_PROBE_ROWSCALE != 0), MQ_GEMM_PROBE_NH, MQ_GEMM_PROBE_WM>; }
 }  // namespace
 #else
-int choose_mt(int M, int N) {
-    constexpr int BN = 128;
-    const int tiles_n = (N + BN - 1) / BN;
-    const int cands[4] = {2, 4, 5, 6};
-    int best = 4;
-    double best_cost = 1e30;
-    for (int c = 0; c < 4; ++c) {
-        const int mt = cands[c];
-        const int64_t tiles = (int64_t)((M + 32 * mt - 1) / (32 * mt)) * tiles_n;
-        const int64_t rounds = (tiles + RESIDENT_SLOTS - 1) / RESIDENT_SLOTS;
-        const double cost = (double)rounds * (mt + 1.25);
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = mt; }
-    }
-    return best;
-}
-
 struct Fp8Args {
     const void* A; int64_t lda; const void* W; int64_t ldw; const float* a_scale; const float* w_scale; const float* bias;
     const float* residual; void* out; int64_t ldc; const float* out_scale; float* amax; int M, N, K;
@@ -497,65 +437,40 @@ struct Fp8Args {
 template <int FLAGS, int MT, bool ROWSCALE, int NH = 1, int WM = 2>
 int launch_fp8_mt(const Fp8Args& a, hipStream_t s) {
     constexpr int BM = 16 * MT * WM, BN = 128 * NH;
-    constexpr int LDS = 2 * (BM + BN) * BK;
-    constexpr int SLOTS = (NH == 1 && WM == 2) ? RESIDENT_SLOTS : RESIDENT_SLOTS_BIG;
+    constexpr int LDS = 2 * (BM + BN) * BK8;
+    constexpr int SLOTS = (NH == 1 && WM == 2) ? RESIDENT_SLOTS : RESIDENT_SLOTS_WIDE;
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = mq_ensure_dyn_lds((const void*)gemm_fp8_kernel<FLAGS, MT, ROWSCALE, NH, WM>, LDS, attr_done); e != hipSuccess) {
         mq_set_error("mq_gemm_fp8: hipFuncSetAttribute: %s", hipGetErrorString(e));
         return MQ_ERR_HIP;
     }
-    // the LDS-DMA addresses both operands through 32-bit buffer offsets: the weight must fit, a taller A goes in row chunks (rows are
-    // independent; whole tiles per chunk), exactly as launch_gemm_mt does in gemm_bf16.hip
-    const uint64_t lim = mq_gemm_addr_limit;
-    const uint64_t w_bytes = (uint64_t)(a.N - 1) * (uint64_t)a.ldw + (uint64_t)a.K;
-    if (w_bytes > lim) {
-        mq_set_error("mq_gemm_fp8: weight matrix of %llu bytes exceeds the %llu bytes a launch can address", (unsigned long long)w_bytes, (unsigned long long)lim);
-        return MQ_ERR_INVALID;
-    }
-    int64_t max_rows = (uint64_t)a.K > lim ? 0 : (int64_t)((lim - (uint64_t)a.K) / (uint64_t)a.lda) + 1;
-    max_rows = max_rows / BM * BM;
-    if (max_rows < BM) {
-        mq_set_error("mq_gemm_fp8: lda=%ld too large", (long)a.lda);
-        return MQ_ERR_INVALID;
-    }
-    const int tiles_n = (a.N + BN - 1) / BN;
     // 16-byte epilogue stores need 16-B aligned rows (bf16: ldc % 8; e4m3: ldc % 16)
     const int row_align = (FLAGS & MQ_EPI_OUT_FP8) ? 16 : 8;
-    const int wide = (mq_gemm_knob_wide && !(FLAGS & MQ_EPI_OUT_F32) && a.ldc % row_align == 0 && ((uintptr_t)a.out & 15) == 0) ? 1 : 0;
-    const size_t out_row = (size_t)a.ldc * ((FLAGS & MQ_EPI_OUT_F32) ? 4 : (FLAGS & MQ_EPI_OUT_FP8) ? 1 : 2);
-    const size_t res_row = (size_t)a.ldc * (((FLAGS & MQ_EPI_RESIDUAL) && !(FLAGS & MQ_EPI_OUT_F32)) ? 2 : 4);
-    for (int64_t r0 = 0; r0 < a.M; r0 += max_rows) {
-        const int m = (int)((a.M - r0) < max_rows ? (a.M - r0) : max_rows);
-        const int tiles_m = (m + BM - 1) / BM;
-        const int num_tiles = tiles_m * tiles_n;
-        const int knob_cgroup = mq_gemm_knob_cgroup;
-        const int cgroup = (knob_cgroup > 0 && tiles_n > knob_cgroup && tiles_m >= 16) ? knob_cgroup : 0;
-        const int band_rows = (tiles_m + 7) / 8;
-        const int grid = num_tiles > SLOTS ? SLOTS : num_tiles;
-        const uint64_t a_bytes = (uint64_t)(m - 1) * (uint64_t)a.lda + (uint64_t)a.K;
-        hipLaunchKernelGGL((gemm_fp8_kernel<FLAGS, MT, ROWSCALE, NH, WM>), dim3(grid), dim3(128 * WM), LDS, s, (const uint8_t*)a.A + r0 * a.lda, a.lda,
-                           (const uint8_t*)a.W, a.ldw, ROWSCALE ? a.a_scale + r0 : a.a_scale, a.w_scale, a.bias,
-                           a.residual ? (const float*)((const char*)a.residual + (size_t)r0 * res_row) : nullptr, (void*)((char*)a.out + (size_t)r0 * out_row),
-                           a.ldc, a.out_scale, a.amax, m, a.N, a.K, tiles_n, num_tiles, cgroup, band_rows, wide, (unsigned)a_bytes, (unsigned)w_bytes);
+    const int wide = (!(FLAGS & MQ_EPI_OUT_F32) && a.ldc % row_align == 0 && ((uintptr_t)a.out & 15) == 0) ? 1 : 0;
+    return gemm_row_chunks("mq_gemm_fp8", a.M, a.N, a.K, a.lda, a.ldw, 1, BM, BN, SLOTS, [&](int64_t r0, int m, const GemmGeom& g) {
+        const GemmRows v = gemm_rows_from<FLAGS, 1>(r0, a.A, a.lda, a.residual, a.out, a.ldc);
+        hipLaunchKernelGGL((gemm_fp8_kernel<FLAGS, MT, ROWSCALE, NH, WM>), dim3(g.grid), dim3(128 * WM), LDS, s, (const uint8_t*)v.A, a.lda, (const uint8_t*)a.W,
+                           a.ldw, ROWSCALE ? a.a_scale + r0 : a.a_scale, a.w_scale, a.bias, v.residual, v.out, a.ldc, a.out_scale, a.amax, m, a.N, a.K,
+                           g.tiles_n, g.num_tiles, g.cgroup, g.band_rows, wide, g.a_bytes, g.w_bytes);
         MQ_CHECK_LAUNCH("mq_gemm_fp8");
-    }
-    return MQ_OK;
+        return MQ_OK;
+    });
 }
 
 // The BIG tile (192 x 256 x 128, 8 waves; MT = 3: the 256-row form needs 274 registers, this one 232-242) takes a problem whose tiles fill the chip's
 // 256 workgroups for at least two rounds at >= 85 % fill, whose columns fill their last 256-wide tile and whose K is long (>= 2 048: the ViT-L/14 fc2
 // at >= 128 images, square GEMMs of the C ABI); everything else stays on the (32 MT) x 128 tiles.  mq_tune("gemm_nh", 1) forbids it, 3 forces it wherever N >= 256.
 bool plan_fp8_big(int M, int N, int K) {
-    const int nh = mq_gemm_fp8_big;
+    const int nh = g_tune.fp8_big;
     if (nh == 1 || N < 256) return false;
     if (nh == 3) return true;
     const int tiles_n = (N + 255) / 256;
     if ((double)N / (tiles_n * 256.0) < 0.9) return false;
     const int64_t tiles = (int64_t)((M + 191) / 192) * tiles_n;
-    const int64_t rounds = (tiles + RESIDENT_SLOTS_BIG - 1) / RESIDENT_SLOTS_BIG;
+    const int64_t rounds = (tiles + RESIDENT_SLOTS_WIDE - 1) / RESIDENT_SLOTS_WIDE;
     // measured (profiles/r06e_fp8_big_tile_ab.txt): -17 % at 8192^3 (2.13 -> 2.56 PF), -5 ... -9 % on the ViT-L/14 fc2 (K = 4 096) at 128 / 240 images; at
     // K = 1 024 the tile's un-overlapped prologue / epilogue (one workgroup per CU) costs more than its k-loop saves (+1 ... +20 %): long K only
-    return K >= 2048 && rounds >= 2 && (double)tiles / (double)(rounds * RESIDENT_SLOTS_BIG) >= 0.85;
+    return K >= 2048 && rounds >= 2 && (double)tiles / (double)(rounds * RESIDENT_SLOTS_WIDE) >= 0.85;
 }
 
 template <int FLAGS, bool ROWSCALE>
@@ -598,14 +513,12 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const bf16_t* __rest
 
 }  // namespace
 
-mq_knob mq_gemm_fp8_force_mt{0};  // set through mq_tune("gemm_mt", v) (shared knob, see gemm_bf16.hip)
-
 extern "C" int mq_gemm_fp8(const void* d_A8, int64_t lda, const void* d_W8, int64_t ldw, const float* d_a_scale, int a_scale_per_row,
                            const float* d_w_scale, const float* d_bias, const float* d_residual, void* d_out, int64_t ldc,
                            const float* d_out_scale, float* d_amax, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     MQ_CHECK_ARG(d_A8 && d_W8 && d_out && d_a_scale && d_w_scale, "mq_gemm_fp8: null operand");
-    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK, "mq_gemm_fp8: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-    MQ_CHECK_ARG(K % BK == 0, "mq_gemm_fp8: K=%ld must be a multiple of %d", (long)K, BK);
+    MQ_CHECK_ARG(M >= 1 && N >= 4 && K >= BK8, "mq_gemm_fp8: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+    MQ_CHECK_ARG(K % BK8 == 0, "mq_gemm_fp8: K=%ld must be a multiple of %d", (long)K, BK8);
     MQ_CHECK_ARG(N % 4 == 0, "mq_gemm_fp8: N=%ld must be a multiple of 4", (long)N);
     MQ_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0, "mq_gemm_fp8: leading dims must keep 16-byte rows");
     MQ_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "mq_gemm_fp8: shape too large");
@@ -616,7 +529,7 @@ extern "C" int mq_gemm_fp8(const void* d_A8, int64_t lda, const void* d_W8, int6
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(0, s, 2.0 * (double)M * (double)N * (double)K);
     const Fp8Args a{d_A8, lda, d_W8, ldw, d_a_scale, d_w_scale, d_bias, d_residual, d_out, ldc, d_out_scale, d_amax, (int)M, (int)N, (int)K};
-    const int fm = mq_gemm_fp8_force_mt;
+    const int fm = g_tune.mt;
 #define MQ_FP8_CASE(F)                                                                     \
     case (F):                                                                              \
         return a_scale_per_row ? launch_fp8<(F), true>(a, fm, s) : launch_fp8<(F), false>(a, fm, s)

@@ -1,4 +1,5 @@
-// Building blocks shared by the bf16 GEMM main loops (gemm_bf16.hip: both operands through the LDS ring; gemm_wd.hip: the W operand global -> VGPR).
+// Building blocks shared by the tiled GEMM main loops (gemm_bf16.hip: both operands through the LDS ring; gemm_wd.hip: the W operand global -> VGPR;
+// gemm_fp8.hip: the e4m3 loop, with a k-step of its own).
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -6,7 +7,39 @@
 
 namespace {
 
-constexpr int BK = 64;
+constexpr int BK = 64;   // the bf16 k-step (elements)
+
+// The persistent tiled GEMMs' (virtual) block -> tile map, XCD-aware and bijective: XCD k takes the k-th contiguous share of the tiles
+// (as xcd_banded_block), walked row-major — or, with cgroup > 0, L2-blocked: bands of band_rows tile rows, each walked cgroup tile columns at a time (the last
+// group narrower), so that an XCD's A panels and W column tiles fit its L2.  ONE map for gemm_nt_kernel, gemm_wd_kernel and gemm_fp8_kernel; built once at
+// the top of a kernel (the per-launch terms are then computed once, not at every tile).
+template <int BM, int BN>
+struct GemmTileMap {
+    int q, r, tiles_n, tiles_m, cgroup, band_rows;
+    __device__ __forceinline__ GemmTileMap(int num_tiles, int tiles_n_, int M, int cgroup_, int band_rows_)
+        : q(num_tiles >> 3), r(num_tiles & 7), tiles_n(tiles_n_), tiles_m((M + BM - 1) / BM), cgroup(cgroup_), band_rows(band_rows_) {}
+    __device__ __forceinline__ void origin(int vbid, int& m0, int& n0) const {
+        const int xcd = vbid & 7, idx = vbid >> 3;
+        const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        int tm, tn;
+        if (cgroup > 0) {
+            const int band_tiles = band_rows * tiles_n;
+            const int band = tile / band_tiles, rb = tile - band * band_tiles;
+            const int rows_here = min(band_rows, tiles_m - band * band_rows);
+            const int full = rows_here * cgroup, ncg_full = tiles_n / cgroup;
+            int cg = rb / full, r2 = rb - cg * full, cw = cgroup;
+            if (cg >= ncg_full) { cg = ncg_full; r2 = rb - ncg_full * full; cw = tiles_n - ncg_full * cgroup; }
+            const int rr = r2 / cw;
+            tm = band * band_rows + rr;
+            tn = cg * cgroup + (r2 - rr * cw);
+        } else {
+            tm = tile / tiles_n;
+            tn = tile - tm * tiles_n;
+        }
+        m0 = tm * BM;
+        n0 = tn * BN;
+    }
+};
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void_t;

@@ -17,10 +17,10 @@
 //                          buffer step s just finished with || A reads kk = 0 of stage s + 1 -> af0
 //   top of step s + 1    : vmcnt(NTW + NPA) -> W[p^1][0] landed; lgkmcnt(0)
 // Selected by mq_tune("gemm_wd", 2 | 3) / MQ_GEMM_WD (0 = off, the default until it wins): tools/gemm_bench.py --ab "base:gemm_wd=0;wd2:gemm_wd=2;wd3:gemm_wd=3".
-#include <stdlib.h>
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm_loop.h"
+#include "gemm_sched.h"
 
 namespace {
 
@@ -47,30 +47,8 @@ __global__ __launch_bounds__(256, 2) void gemm_wd_kernel(
     constexpr int ERG = !(FLAGS & MQ_EPI_RESIDUAL) ? MT : (FLAGS & MQ_EPI_OUT_F32) ? (MT <= 3 ? MT : (MT + 1) / 2) : (MT <= 4 ? MT : 3);
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // ---- XCD-aware, bijective (virtual) block -> tile map, L2-blocked order inside an XCD's share (the map of gemm_nt_kernel) ----------------------
-    const int q = num_tiles >> 3, r = num_tiles & 7;
-    const int tiles_m = (M + BM - 1) / BM;
-    auto tile_origin = [&](int vbid, int& m0, int& n0) {
-        const int xcd = vbid & 7, idx = vbid >> 3;
-        const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        int tm, tn;
-        if (cgroup > 0) {
-            const int band_tiles = band_rows * tiles_n;
-            const int band = tile / band_tiles, rb = tile - band * band_tiles;
-            const int rows_here = min(band_rows, tiles_m - band * band_rows);
-            const int full = rows_here * cgroup, ncg_full = tiles_n / cgroup;
-            int cg = rb / full, r2 = rb - cg * full, cw = cgroup;
-            if (cg >= ncg_full) { cg = ncg_full; r2 = rb - ncg_full * full; cw = tiles_n - ncg_full * cgroup; }
-            const int rr = r2 / cw;
-            tm = band * band_rows + rr;
-            tn = cg * cgroup + (r2 - rr * cw);
-        } else {
-            tm = tile / tiles_n;
-            tn = tile - tm * tiles_n;
-        }
-        m0 = tm * BM;
-        n0 = tn * BN;
-    };
+    // ---- the (virtual) block -> tile map (gemm_loop.h)
+    const GemmTileMap<BM, BN> tile_map(num_tiles, tiles_n, M, cgroup, band_rows);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -107,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wd_kernel(
     unsigned a_rec = a_bytes, w_rec = w_bytes;
     {
         int m0, n0;
-        tile_origin(d_vbid, m0, n0);
+        tile_map.origin(d_vbid, m0, n0);
         set_a_sources(m0);
         set_w_sources(n0);
     }
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wd_kernel(
             d_vbid += gridDim.x;
             if (d_vbid < num_tiles) {
                 int m0, n0;
-                tile_origin(d_vbid, m0, n0);
+                tile_map.origin(d_vbid, m0, n0);
                 set_a_sources(m0);
             } else a_rec = 0;
         }
@@ -134,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wd_kernel(
             w_vbid += gridDim.x;
             if (w_vbid < num_tiles) {
                 int m0, n0;
-                tile_origin(w_vbid, m0, n0);
+                tile_map.origin(w_vbid, m0, n0);
                 set_w_sources(n0);
             } else w_rec = 0;
         }
@@ -260,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wd_kernel(
 
     for (;;) {
         int cm0, cn0;
-        tile_origin(c_vbid, cm0, cn0);
+        tile_map.origin(c_vbid, cm0, cn0);
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -299,8 +277,7 @@ __attribute__((used)) void* mq_gemm_wd_probe() { return (void*)gemm_wd_kernel<MQ
 
 template <int FLAGS, int MT, int NS, bool PAIR>
 int launch_wd(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out, int64_t ldc,
-              int M, int N, int K, int tiles_n, int num_tiles, int cgroup, int band_rows, int grid, int wide, unsigned a_bytes, unsigned w_bytes,
-              const GemmLn& ln, hipStream_t s) {
+              int M, int N, int K, const GemmGeom& g, int wide, const GemmLn& ln, hipStream_t s) {
     constexpr int LDS = NS * 32 * MT * BK * 2;
     static std::atomic<uint64_t> attr_done{0};
     auto kern = gemm_wd_kernel<FLAGS, MT, NS, PAIR>;
@@ -308,18 +285,17 @@ int launch_wd(const void* A, int64_t lda, const void* W, int64_t ldw, const floa
         mq_set_error("mq_gemm_bf16 (W-direct): hipFuncSetAttribute: %s", hipGetErrorString(e));
         return MQ_ERR_HIP;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, s, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, residual, out, ldc, M, N, K, tiles_n,
-                       num_tiles, cgroup, band_rows, wide, a_bytes, w_bytes, ln);
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), LDS, s, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, residual, out, ldc, M, N, K, g.tiles_n,
+                       g.num_tiles, g.cgroup, g.band_rows, wide, g.a_bytes, g.w_bytes, ln);
     MQ_CHECK_LAUNCH("mq_gemm_bf16 (W-direct)");
     return MQ_OK;
 }
 
 template <int FLAGS>
 int dispatch_wd(int mt, int ns, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out, int64_t ldc,
-                int M, int N, int K, int tiles_n, int num_tiles, int cgroup, int band_rows, int grid, int wide, unsigned a_bytes, unsigned w_bytes,
-                const GemmLn& ln, hipStream_t s) {
+                int M, int N, int K, const GemmGeom& g, int wide, const GemmLn& ln, hipStream_t s) {
 #define MQ_WD(MTV, NSV) \
-    if (mt == MTV && ns == NSV) return launch_wd<FLAGS, MTV, NSV % 4, (NSV >= 4)>(A, lda, W, ldw, bias, residual, out, ldc, M, N, K, tiles_n, num_tiles, cgroup, band_rows, grid, wide, a_bytes, w_bytes, ln, s)
+    if (mt == MTV && ns == NSV) return launch_wd<FLAGS, MTV, NSV % 4, (NSV >= 4)>(A, lda, W, ldw, bias, residual, out, ldc, M, N, K, g, wide, ln, s)
     MQ_WD(4, 2); MQ_WD(4, 3); MQ_WD(5, 2); MQ_WD(5, 3); MQ_WD(4, 6); MQ_WD(4, 7); MQ_WD(5, 6); MQ_WD(5, 7);   // ns + 4: the PAIR form
 #undef MQ_WD
     return -1;
@@ -327,14 +303,13 @@ int dispatch_wd(int mt, int ns, const void* A, int64_t lda, const void* W, int64
 
 }  // namespace
 
-// One launch of the W-direct kernel with the tile plan gemm_bf16.hip's launch_gemm_mt made (same arguments as its own kernel).  Returns -1 when this
+// One launch of the W-direct kernel on the geometry gemm_bf16.hip's launch_gemm_mt made (same arguments as its own kernel).  Returns -1 when this
 // (flags, tile height, stages) combination is not instantiated or K / 64 is odd: the caller then launches the LDS-both kernel.
 int mq_gemm_wd_launch(int flags, int mt, int ns, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out,
-                      int64_t ldc, int M, int N, int K, int tiles_n, int num_tiles, int cgroup, int band_rows, int grid, int wide, unsigned a_bytes,
-                      unsigned w_bytes, const GemmLn& ln, hipStream_t s) {
+                      int64_t ldc, int M, int N, int K, const GemmGeom& g, int wide, const GemmLn& ln, hipStream_t s) {
     if ((K / BK) % 2 != 0 || K < 2 * BK) return -1;
 #define MQ_WD_CASE(F) \
-    case (F): return dispatch_wd<(F)>(mt, ns, A, lda, W, ldw, bias, residual, out, ldc, M, N, K, tiles_n, num_tiles, cgroup, band_rows, grid, wide, a_bytes, w_bytes, ln, s)
+    case (F): return dispatch_wd<(F)>(mt, ns, A, lda, W, ldw, bias, residual, out, ldc, M, N, K, g, wide, ln, s)
     switch (flags) {
         MQ_WD_CASE(0);
         MQ_WD_CASE(MQ_EPI_OUT_F32);

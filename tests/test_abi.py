@@ -58,6 +58,28 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert b"max_seqs" in lib.mq_last_error()
     assert lib.mq_queue_encode(None, None, None, 1, None) == -1 and b"null queue" in lib.mq_last_error()
     assert lib.mq_queue_get_stats(None, None) == -1 and lib.mq_queue_destroy(None) == 0
+    # the tiled GEMM entry points: every shape / layout refusal returns -1 before any launch or device query and names the entry point and the
+    # bad quantity (fake: a non-null operand address, never dereferenced)
+    fake = 256
+    gemms = {   # name -> (call(M, N, K, lda), K step, leading dimension of a bad layout)
+        "mq_gemm_bf16": (lambda M, N, K, ld: lib.mq_gemm_bf16(fake, ld, fake, K, fake, None, fake, N, M, N, K, 1, None), 64, 4),
+        "mq_gemm_bf16_ln": (lambda M, N, K, ld: lib.mq_gemm_bf16_ln(fake, ld, fake, K, fake, fake, fake, fake, N, M, N, K, 1, None), 64, 4),
+        "mq_gemm_bf16_rs": (lambda M, N, K, ld: lib.mq_gemm_bf16_rs(fake, ld, fake, K, fake, fake, fake, N, M, N, K, 9, fake, None), 64, 4),
+        "mq_gemm_bf16_lnrs": (lambda M, N, K, ld: lib.mq_gemm_bf16_lnrs(fake, ld, fake, K, fake, fake, fake, fake, fake, N, M, N, K, 9, fake, None),
+                              64, 4),
+        "mq_gemm_bf16_rsf": (lambda M, N, K, ld: lib.mq_gemm_bf16_rsf(fake, ld, fake, K, fake, fake, fake, N, M, N, K, 9, fake, fake, 1e-5, None,
+                                                                     None, 0, None, 0, None), 64, 4),
+        "mq_gemm_fp8": (lambda M, N, K, ld: lib.mq_gemm_fp8(fake, ld, fake, K, fake, 1, fake, fake, None, fake, N, None, None, M, N, K, 1, None), 128, 8),
+    }
+    for name, (call, bk, bad_ld) in gemms.items():
+        for args, what in (((0, 64, bk, bk), b"M=0"),                       # bad shape
+                           ((1, 64, bk + 32, bk + 32), b"K=%d" % (bk + 32)),  # K not a multiple of the k-step
+                           ((1, 66, bk, bk), b"N=66"),                      # N not a multiple of 4
+                           ((1, 64, bk, bad_ld), b"leading dims"),          # rows that are not 16-byte aligned
+                           ((1 << 30, 64, bk, bk), b"shape too large")):    # beyond the kernels' 32-bit row indices
+            assert call(*args) == -1, (name, args)
+            err = lib.mq_last_error()
+            assert err.startswith(name.encode() + b": ") and what in err, (name, args, err)
 
 
 def test_product_never_imports_the_oracle():
