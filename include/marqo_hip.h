@@ -482,6 +482,9 @@ int mq_ln_gemm_small_bf16(const void* d_x, int64_t ldx, int x_bf16, const float*
  * come INTERLEAVED 16 at a time — rows 32 j .. 32 j + 15 = up units 16 j .. 16 j + 15, rows 32 j + 16 .. 32 j + 31 = the same units' gate rows — so one lane
  * holds up AND gate of the same hidden units; out bf16 [M, F] at row stride ldc: out[m, u] = (up + b_up) * silu(gate + b_gate).  N % 32 == 0. */
 #define MQ_EPI_GLU 256
+/* MQ_EPI_RELU (mq_gemm_bf16 with MQ_EPI_BIAS [| MQ_EPI_RESIDUAL], bf16 out): max(0, .) as the last step, after the residual add (the ResNet
+ * towers' conv + BN + ReLU and conv3 + BN + identity + ReLU).  These combinations always run on the tiled GEMMs, whatever the row count. */
+#define MQ_EPI_RELU 512
 int mq_gemm_bf16_rs(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const void* d_residual, void* d_out, int64_t ldc,
                     int64_t M, int64_t N, int64_t K, int flags, float* d_partials, void* stream);
 int mq_row_stats_finalize(const float* d_partials, int32_t nslots, float* d_stats, int64_t rows, int32_t W, float eps, void* stream);
@@ -696,6 +699,67 @@ int mq_convnext_downsample(const void* d_x, const float* d_stats, const float* d
                            int32_t C, void* stream);
 int mq_convnext_pool_ln(const void* d_x, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32, int64_t n, int32_t HW, int32_t C,
                         float eps, void* stream);
+
+/* ---- ResNet image towers (csrc/resnet.hip) --------------------------------------------------------------------------------------------------
+ * OpenAI CLIP's / open_clip's ModifiedResNet (RN50, RN101, RN50x4, RN50x16, RN50x64; model_registry.py:16-140 in the reference).  Activations are
+ * NHWC bf16 rows [pixels, C]; every BatchNorm is folded into the convolution in front of it (weights and a bias).  Channel counts that are not a
+ * multiple of 64 (the stem output w and the planes of stages 1-2 when w = 80 / 96) are zero-padded to one: pad64(c) columns, whose weights and
+ * biases are 0, so that those columns stay 0 through the ReLUs.  The stem's inner width w / 2 is not padded.  Every pointer is a device pointer. */
+typedef struct mq_resnet_cfg {
+    int32_t image_size;   /* S: multiple of 32 */
+    int32_t layers[4];    /* Bottleneck blocks per stage */
+    int32_t width;        /* w: stem output width; stage i has planes w << i and 4 (w << i) output channels; w % 16 == 0 */
+    int32_t heads;        /* attention-pool heads = 32 w / 64 */
+    int32_t out_dim;      /* embedding width E (attnpool.c_proj) */
+    float   mean[3];      /* preprocessing normalisation of the u8 entry point */
+    float   std[3];
+} mq_resnet_cfg;
+
+/* one Bottleneck block; P = pad64(planes), I = the padded input width, O = 4 planes.  3x3 weights: bf16 [Cout, Kp], column (ky * 3 + kx) * Cin + c,
+ * Kp = 9 Cin rounded up to a multiple of 64, zero past 9 Cin. */
+typedef struct mq_resnet_block_weights {
+    const void* conv1_w; const float* conv1_b;   /* bf16 [P, I], fp32 [P]: conv1 * bn1 */
+    const void* conv2_w; const float* conv2_b;   /* bf16 [P, Kp(P)], fp32 [P]: conv2 (3x3) * bn2 */
+    const void* conv3_w; const float* conv3_b;   /* bf16 [O, P], fp32 [O]: conv3 * bn3 */
+    const void* ds_w;    const float* ds_b;      /* bf16 [O, I], fp32 [O]: downsample.0 * downsample.1; NULL when the block has none */
+} mq_resnet_block_weights;
+
+typedef struct mq_resnet_weights {
+    const void*  stem_w[3];   /* conv1 (3x3 / 2, Cin 3): bf16 [w/2, 64], column (ky * 3 + kx) * 3 + c, zero past 27; conv2: [w/2, Kp(w/2)]; conv3: [pad64(w), Kp(w/2)] */
+    const float* stem_b[3];   /* the folded bn1..bn3 biases: [w/2], [w/2], [pad64(w)] */
+    const mq_resnet_block_weights* blocks;   /* host array, sum(layers) entries, stage by stage */
+    const float* pos;         /* fp32 [T, C]: attnpool.positional_embedding, T = (S/32)^2 + 1, C = 32 w */
+    const void*  q_w; const float* q_b;      /* bf16 [C, C], fp32 [C]: q_proj scaled by 1/8 (= 64^-0.5) */
+    const void*  kv_w; const float* kv_b;    /* bf16 [2C, C], fp32 [2C]: k_proj rows, then v_proj rows */
+    const void*  c_w; const float* c_b;      /* bf16 [E, C], fp32 [E]: c_proj */
+} mq_resnet_weights;
+
+/* workspace of one call of n images (0 for an unsupported cfg) */
+size_t mq_resnet_workspace_bytes(const mq_resnet_cfg* cfg, int64_t n_images);
+/* the whole tower in one call, with the contract of mq_encode_convnext_u8 / _f32: d_pixels uint8 [n, S, S, 3] (HWC RGB, normalised with cfg->mean /
+ * std in the stem gather) or fp32 [n, 3, S, S] (normalised); d_out fp32 [n, E], L2-normalised when normalize != 0. */
+int mq_encode_resnet_u8(const mq_resnet_cfg* cfg, const mq_resnet_weights* w, const uint8_t* d_pixels, int64_t n, float* d_out, int normalize,
+                        void* d_workspace, size_t workspace_bytes, void* stream);
+int mq_encode_resnet_f32(const mq_resnet_cfg* cfg, const mq_resnet_weights* w, const float* d_pixels, int64_t n, float* d_out, int normalize,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
+/* building blocks (exported for parity tests):
+ *   mq_resnet_conv3x3:         d_y bf16 [n H W, ldy] columns 0..Cout-1 = [ReLU](3x3 convolution, stride 1, zero padding 1, of d_x bf16 [n, H, W, Cin] with d_w
+ *                              (layout above) + d_b fp32 [Cout]); columns Cout..ldy-1 untouched.  Cin % 8 == 0, Cout % 4 == 0, both <= 4096; relu 0 / 1;
+ *                              n H W < 2^30; d_y must not alias d_x.  An implicit GEMM with 64-bit activation addresses: no 2^31-byte limit on d_x / d_y.
+ *   mq_resnet_stem_gather:     d_out bf16 [n (S/2)^2, 64], column (ky * 3 + kx) * 3 + c = the normalised pixel (2 oy + ky - 1, 2 ox + kx - 1) of channel
+ *                              c (0 outside the image and past column 26); is_u8: d_pixels uint8 [n, S, S, 3] with mean / std (host arrays), else fp32
+ *                              [n, 3, S, S] (mean / std ignored).  S even.
+ *   mq_resnet_avgpool2:        d_out bf16 [n (H/2) (W/2), C] = mean of each 2x2 window of d_x bf16 [n, H, W, C].  H, W even, C % 8 == 0.
+ *   mq_resnet_attnpool_tokens: d_tokens bf16 [n, HW + 1, C]: row 0 = mean of the HW rows of d_x bf16 [n, HW, C] + d_pos[0], row 1 + p = row p + d_pos[1 + p]
+ *                              (d_pos fp32 [HW + 1, C]).  C % 8 == 0, HW + 1 <= 256.
+ *   mq_resnet_attnpool_attend: d_out bf16 [n, C], heads of 64: softmax(q . k^T) v per image and head, with d_q bf16 [n, C] (already scaled) and d_kv bf16
+ *                              [n, T, 2C] (k columns, then v columns).  C % 64 == 0, T <= 256. */
+int mq_resnet_conv3x3(const void* d_x, const void* d_w, const float* d_b, void* d_y, int64_t ldy, int64_t n, int32_t H, int32_t W, int32_t Cin,
+                      int32_t Cout, int32_t relu, void* stream);
+int mq_resnet_stem_gather(const void* d_pixels, int32_t is_u8, void* d_out, int64_t n, int32_t S, const float* mean, const float* std, void* stream);
+int mq_resnet_avgpool2(const void* d_x, void* d_out, int64_t n, int32_t H, int32_t W, int32_t C, void* stream);
+int mq_resnet_attnpool_tokens(const void* d_x, const float* d_pos, void* d_tokens, int64_t n, int32_t HW, int32_t C, void* stream);
+int mq_resnet_attnpool_attend(const void* d_q, const void* d_kv, void* d_out, int64_t n, int32_t T, int32_t C, void* stream);
 
 /* ---- text tokenisation on device (K14) ------------------------------------------------------------------- */
 /* The reference tokenises on the host with third-party code (open_clip SimpleTokenizer at

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet")  # build() refuses register spills in these
 ABI_VERSION = 14
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU = 1, 2, 3
@@ -130,6 +130,22 @@ class ConvNextWeights(C.Structure):
 
 
 MQ_CONVNEXT_HEAD_LINEAR, MQ_CONVNEXT_HEAD_MLP = 0, 1
+MQ_EPI_RELU = 512
+
+
+class ResNetCfg(C.Structure):
+    """mq_resnet_cfg: the OpenAI / open_clip ResNet image towers (csrc/resnet.hip)"""
+    _fields_ = [("image_size", C.c_int32), ("layers", C.c_int32 * 4), ("width", C.c_int32), ("heads", C.c_int32), ("out_dim", C.c_int32),
+                ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+class ResNetBlockWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "ds_w", "ds_b")]
+
+
+class ResNetWeights(C.Structure):
+    _fields_ = [("stem_w", C.c_void_p * 3), ("stem_b", C.c_void_p * 3), ("blocks", C.POINTER(ResNetBlockWeights)), ("pos", C.c_void_p),
+                ("q_w", C.c_void_p), ("q_b", C.c_void_p), ("kv_w", C.c_void_p), ("kv_b", C.c_void_p), ("c_w", C.c_void_p), ("c_b", C.c_void_p)]
 
 
 class WordPieceVocab(C.Structure):
@@ -251,6 +267,14 @@ _SIGNATURES = {
     "mq_convnext_dwconv": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_convnext_downsample": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_convnext_pool_ln": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_resnet_workspace_bytes": (C.c_size_t, [C.POINTER(ResNetCfg), C.c_int64]),
+    "mq_encode_resnet_u8": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(ResNetWeights), _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    "mq_encode_resnet_f32": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(ResNetWeights), _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    "mq_resnet_conv3x3": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_resnet_stem_gather": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "mq_resnet_avgpool2": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_resnet_attnpool_tokens": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "mq_resnet_attnpool_attend": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     # the towers' front / back ends, rotary and gated-MLP steps (csrc/embed.hip; building blocks for parity tests)
     "mq_patchify": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "mq_vit_assemble": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),

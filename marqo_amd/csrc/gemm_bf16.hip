@@ -665,6 +665,15 @@ extern "C" int mq_gemm_bf16(const void* d_A, int64_t lda, const void* d_W, int64
         MqProfScope prof(0, s, 2.0 * (double)M * (double)N * (double)K);
         return launch_gemm<MQ_EPI_BIAS | MQ_EPI_GLU>(d_A, lda, d_W, ldw, d_bias, d_residual ? (const float*)d_residual : nullptr, d_out, ldc, (int)M, (int)N, (int)K, s);
     }
+    if (flags & MQ_EPI_RELU) {   // (nor a ReLU one: the tiled family for any row count)
+        MqProfScope prof(0, s, 2.0 * (double)M * (double)N * (double)K);
+        if (flags == (MQ_EPI_BIAS | MQ_EPI_RELU))
+            return launch_gemm<MQ_EPI_BIAS | MQ_EPI_RELU>(d_A, lda, d_W, ldw, d_bias, nullptr, d_out, ldc, (int)M, (int)N, (int)K, s);
+        if (flags == (MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_RELU))   // bf16 residual in, bf16 out; ReLU after the residual add
+            return launch_gemm<MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_RELU>(d_A, lda, d_W, ldw, d_bias, d_residual, d_out, ldc, (int)M, (int)N, (int)K, s);
+        mq_set_error("mq_gemm_bf16: unsupported epilogue flag combination 0x%x", flags);
+        return MQ_ERR_INVALID;
+    }
     // a handful of rows (single queries, pooled rows of a small batch): the column-sliced skinny kernel spreads the weight stream over the
     // whole chip instead of N/128 workgroups (gemm_small.hip)
     if (mq_gemm_small_ok(M, N, K, false) || mq_gemm_small_grouped_ok(M, N, K)) return mq_gemm_small(d_A, lda, d_W, ldw, d_bias, d_residual, d_out, ldc, M, N, K, flags, s);

@@ -183,6 +183,10 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[MT][4], const float* 
             for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
         }
         if (FLAGS & MQ_EPI_RESIDUAL) v += res_v[(FLAGS & MQ_EPI_RESIDUAL) ? (mt % RG) : 0][nt];
+        if constexpr ((FLAGS & MQ_EPI_RELU) != 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        }
         return v;
     };
 #pragma unroll

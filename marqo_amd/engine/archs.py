@@ -108,6 +108,49 @@ class ConvNextArch:
 
 
 @dataclass(frozen=True)
+class ResNetArch:
+    """OpenAI CLIP's ModifiedResNet image tower (open_clip's is the same module and state dict): a 3-conv stem, four stages of Bottleneck
+    blocks (planes w, 2w, 4w, 8w; expansion 4; anti-aliased strides by average pooling) and an AttentionPool2d head with one query
+    (model_registry.py:16-140 in the reference)."""
+    image_size: int
+    layers: Tuple[int, int, int, int]
+    width: int                 # w: the stem's output width
+    out_dim: int
+    preprocessor: Optional[str] = None   # (the OpenCLIP transform, as for the ViTs)
+    pool: str = "resnet"
+    quick_gelu: bool = False   # (kept so that the resolver can `replace` it; the image tower itself has no GELU)
+
+    @property
+    def heads(self) -> int:
+        return 32 * self.width // 64
+
+    @property
+    def tokens(self) -> int:
+        return (self.image_size // 32) ** 2 + 1
+
+    @property
+    def gflop_per_image(self) -> float:
+        """2 MAC-FLOPs of every convolution, of the k / v projections of all tokens and of q / c_proj on token 0 (BN, ReLU, pooling and the
+        attention scores not counted)."""
+        S, w = self.image_size, self.width
+        G = S // 2
+        f = 2 * G * G * 9 * (3 * (w // 2) + (w // 2) * (w // 2) + (w // 2) * w)
+        G //= 2
+        inp = w
+        for i, depth in enumerate(self.layers):
+            P = w << i
+            for j in range(depth):
+                Go = G // 2 if (i > 0 and j == 0) else G
+                f += 2 * G * G * inp * P + 2 * G * G * 9 * P * P + 2 * Go * Go * P * 4 * P
+                if (i > 0 and j == 0) or inp != 4 * P:
+                    f += 2 * Go * Go * inp * 4 * P
+                G, inp = Go, 4 * P
+        C, T = 32 * w, self.tokens
+        f += 2 * T * 2 * C * C + 2 * C * C + 2 * C * self.out_dim
+        return f / 1e9
+
+
+@dataclass(frozen=True)
 class ClipTextArch:
     vocab: int
     ctx: int
@@ -294,6 +337,32 @@ UNSUPPORTED_HINT = ("this open_clip architecture is not runnable by the marqo_am
 # hf-hub repos the reference registry names (model_registry.py:483-494) -> the open_clip architecture their open_clip_config.json
 # describes (used when that file is not on disk, e.g. with synthetic weights)
 KNOWN_HF_HUB_ARCHS = {"hf-hub:Marqo/marqo-fashionCLIP": "ViT-B-16", "hf-hub:Marqo/marqo-fashionSigLIP": "ViT-B-16-SigLIP"}
+
+# ResNet CLIPs (model_registry.py:16-140; open_clip model configs RN50 ... RN50x64): resolved by resolve_resnet_clip only
+_TEXT_RN = {512: ClipTextArch(49408, 77, 512, 12, 8, 2048, 1024), 640: ClipTextArch(49408, 77, 640, 12, 10, 2560, 640),
+            768: ClipTextArch(49408, 77, 768, 12, 12, 3072, 768), 1024: ClipTextArch(49408, 77, 1024, 12, 16, 4096, 1024)}
+RESNET_CLIP_ARCHS = {
+    "RN50": (ResNetArch(224, (3, 4, 6, 3), 64, 1024), _TEXT_RN[512]),
+    "RN101": (ResNetArch(224, (3, 4, 23, 3), 64, 512), replace(_TEXT_RN[512], out_dim=512)),
+    "RN50x4": (ResNetArch(288, (4, 6, 10, 6), 80, 640), _TEXT_RN[640]),
+    "RN50x16": (ResNetArch(384, (6, 8, 18, 8), 96, 768), _TEXT_RN[768]),
+    "RN50x64": (ResNetArch(448, (3, 15, 36, 10), 128, 1024), _TEXT_RN[1024]),
+}
+# OpenAI `clip` ResNet names -> open_clip architecture (OpenAI checkpoints: QuickGELU text tower)
+OPENAI_RESNET_NAMES = {"RN50": "RN50", "RN101": "RN101", "RN50x4": "RN50x4", "RN50x16": "RN50x16", "RN50x64": "RN50x64"}
+
+
+def resolve_resnet_clip(arch_name: str, pretrained: Optional[str] = None) -> Tuple[ResNetArch, ClipTextArch]:
+    """'RN50' / 'RN50-quickgelu' (+ pretrained tag) -> (vision, text) arch or KeyError.  QuickGELU as resolve_open_clip applies it: on for
+    -quickgelu names and for the openai tag."""
+    base, quick = arch_name, pretrained == "openai"
+    if base.endswith("-quickgelu"):
+        base, quick = base[: -len("-quickgelu")], True
+    if base not in RESNET_CLIP_ARCHS:
+        raise KeyError(f"{arch_name}: not a ResNet CLIP architecture")
+    v, t = RESNET_CLIP_ARCHS[base]
+    return replace(v, quick_gelu=quick), replace(t, quick_gelu=quick)
+
 
 # OpenAI `clip` names (clip_utils.py:295-492) -> open_clip architecture (always QuickGELU)
 OPENAI_CLIP_NAMES = {"ViT-B/32": "ViT-B-32", "ViT-B/16": "ViT-B-16", "ViT-L/14": "ViT-L-14", "ViT-L/14@336px": "ViT-L-14-336"}

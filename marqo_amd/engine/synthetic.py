@@ -11,7 +11,7 @@ from typing import Dict
 
 import torch
 
-from marqo_amd.engine.archs import BertArch, ClipTextArch, ConvNextArch, VitArch
+from marqo_amd.engine.archs import BertArch, ClipTextArch, ConvNextArch, ResNetArch, VitArch
 
 Tensor = torch.Tensor
 
@@ -69,12 +69,53 @@ def _convnext_visual(sd, arch: ConvNextArch, g) -> None:
         sd["visual.head.mlp.fc2.weight"] = torch.randn(E, 2 * E, generator=g) / math.sqrt(2 * E)
 
 
+def _bn(sd, name, C, g, scale=(0.5, 1.0)):
+    """eval-mode BatchNorm with trained-like statistics: a running mean / variance that the conv output does not match exactly, and weights of
+    `scale` (lo, hi) — the last BN of a residual branch gets small ones, as trained ResNets have them, so that 100+ blocks stay bounded"""
+    lo, hi = scale
+    sd[name + ".weight"] = lo + (hi - lo) * torch.rand(C, generator=g)
+    sd[name + ".bias"] = 0.05 * torch.randn(C, generator=g)
+    sd[name + ".running_mean"] = 0.1 * torch.randn(C, generator=g)
+    sd[name + ".running_var"] = 0.5 + torch.rand(C, generator=g)
+    sd[name + ".num_batches_tracked"] = torch.tensor(0)
+
+
+def _conv(sd, name, O, I, k, g):
+    sd[name + ".weight"] = torch.randn(O, I, k, k, generator=g) * math.sqrt(2.0 / (I * k * k))
+
+
+def _resnet_visual(sd, arch: ResNetArch, g) -> None:
+    """ModifiedResNet under visual.* (OpenAI CLIP / open_clip names): He-initialised convolutions, trained-like BatchNorm statistics"""
+    v, w = "visual.", arch.width
+    _conv(sd, v + "conv1", w // 2, 3, 3, g); _bn(sd, v + "bn1", w // 2, g)
+    _conv(sd, v + "conv2", w // 2, w // 2, 3, g); _bn(sd, v + "bn2", w // 2, g)
+    _conv(sd, v + "conv3", w, w // 2, 3, g); _bn(sd, v + "bn3", w, g)
+    inp = w
+    for i, depth in enumerate(arch.layers):
+        P = w << i
+        for j in range(depth):
+            p = f"{v}layer{i + 1}.{j}."
+            _conv(sd, p + "conv1", P, inp, 1, g); _bn(sd, p + "bn1", P, g)
+            _conv(sd, p + "conv2", P, P, 3, g); _bn(sd, p + "bn2", P, g)
+            _conv(sd, p + "conv3", 4 * P, P, 1, g); _bn(sd, p + "bn3", 4 * P, g, (0.05, 0.25))
+            if (i > 0 and j == 0) or inp != 4 * P:
+                _conv(sd, p + "downsample.0", 4 * P, inp, 1, g); _bn(sd, p + "downsample.1", 4 * P, g)
+            inp = 4 * P
+    C, E, ap = 32 * w, arch.out_dim, v + "attnpool."
+    sd[ap + "positional_embedding"] = torch.randn(arch.tokens, C, generator=g) / math.sqrt(C)
+    for name in ("q_proj", "k_proj", "v_proj"):
+        _lin(sd, ap + name, C, C, g, 1.0 / math.sqrt(C))
+    _lin(sd, ap + "c_proj", E, C, g, 1.0 / math.sqrt(C))
+
+
 def random_open_clip_state_dict(vision: VitArch = None, text: ClipTextArch = None, seed: int = 0) -> Dict[str, Tensor]:
     """open_clip-named state dict for the given towers (either may be None)."""
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, Tensor] = {}
     if isinstance(vision, ConvNextArch):
         _convnext_visual(sd, vision, g)
+    elif isinstance(vision, ResNetArch):
+        _resnet_visual(sd, vision, g)
     elif vision is not None and vision.pool == "map":
         # timm SigLIP ViT as open_clip's visual.trunk (no class token, conv bias, attention-pool head)
         W, P, F, t = vision.width, vision.patch_size, vision.mlp_dim, "visual.trunk."

@@ -1745,3 +1745,165 @@ class ConvNextTower(_TowerBase):
         if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
             raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
         return self._run("f32", pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous(), normalize)
+
+
+# ---- ResNet CLIP image towers (csrc/resnet.hip) -------------------------------------------------------------------------------------------------
+RESNET_BN_EPS = 1e-5
+
+
+def resnet_pad64(c: int) -> int:
+    """channel count as the tower stores it: zero-padded to a multiple of 64 (the tiled GEMMs' k-step)"""
+    return (c + 63) // 64 * 64
+
+
+def resnet_fold_bn(conv_w: Tensor, bn_w: Tensor, bn_b: Tensor, bn_mean: Tensor, bn_var: Tensor, eps: float = RESNET_BN_EPS) -> Tuple[Tensor, Tensor]:
+    """conv (no bias) followed by eval-mode BatchNorm -> one conv with a bias: w' = w * g / sqrt(var + eps) per output channel, b' = beta - mean * that"""
+    s = bn_w.double() / torch.sqrt(bn_var.double() + eps)
+    w = (conv_w.double() * s.view(-1, *([1] * (conv_w.dim() - 1)))).float()
+    return w, (bn_b.double() - bn_mean.double() * s).float()
+
+
+def resnet_conv3x3_weight(w: Tensor, cin: int, cout: int) -> Tensor:
+    """[O, I, 3, 3] -> fp32 [cout, Kp]: column (ky * 3 + kx) * cin + c (mq_resnet_conv3x3), zero-padded to cin input / cout output channels and to
+    Kp = 9 cin rounded up to a multiple of 64"""
+    O, I = w.shape[:2]
+    full = torch.zeros(cout, 3, 3, cin, dtype=torch.float32)
+    full[:O, :, :, :I] = w.permute(0, 2, 3, 1).float()
+    Kp = (9 * cin + 63) // 64 * 64
+    out = torch.zeros(cout, Kp, dtype=torch.float32)
+    out[:, :9 * cin] = full.reshape(cout, 9 * cin)
+    return out
+
+
+def resnet_conv1x1_weight(w: Tensor, cin: int, cout: int) -> Tensor:
+    """[O, I, 1, 1] -> fp32 [cout, cin], zero-padded"""
+    O, I = w.shape[:2]
+    out = torch.zeros(cout, cin, dtype=torch.float32)
+    out[:O, :I] = w.reshape(O, I).float()
+    return out
+
+
+def resnet_stem_weight(w: Tensor) -> Tensor:
+    """visual.conv1 [O, 3, 3, 3] -> fp32 [O, 64]: column (ky * 3 + kx) * 3 + c (mq_resnet_stem_gather's patch rows), zero past 27"""
+    out = torch.zeros(w.shape[0], 64, dtype=torch.float32)
+    out[:, :27] = w.permute(0, 2, 3, 1).reshape(w.shape[0], 27).float()
+    return out
+
+
+def resnet_pad_vec(v: Tensor, n: int) -> Tensor:
+    out = torch.zeros(n, dtype=torch.float32)
+    out[:v.numel()] = v.float()
+    return out
+
+
+def resnet_attnpool_weights(sd: Dict[str, Tensor], arch) -> Dict[str, Tensor]:
+    """visual.attnpool.* -> the fp32 operands of the tower's attention pool (mq_resnet_weights): positions [T, C]; q_proj with the 64^-0.5 softmax
+    scale folded into weight and bias (a power of two: the folded weight rounds to bf16 exactly as the unscaled one); k_proj and v_proj stacked into
+    one [2C, C] projection; c_proj"""
+    Cw, T, E, ap = 32 * arch.width, arch.tokens, arch.out_dim, "visual.attnpool."
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    scale = 64 ** -0.5
+    return {"pos": f32(ap + "positional_embedding", (T, Cw)),
+            "q_w": f32(ap + "q_proj.weight", (Cw, Cw)) * scale, "q_b": f32(ap + "q_proj.bias", (Cw,)) * scale,
+            "kv_w": torch.cat([f32(ap + "k_proj.weight", (Cw, Cw)), f32(ap + "v_proj.weight", (Cw, Cw))]),
+            "kv_b": torch.cat([f32(ap + "k_proj.bias", (Cw,)), f32(ap + "v_proj.bias", (Cw,))]),
+            "c_w": f32(ap + "c_proj.weight", (E, Cw)), "c_b": f32(ap + "c_proj.bias", (E,))}
+
+
+RESNET_WORKSPACE_BYTES = _env_int("MARQO_AMD_RESNET_WORKSPACE_MB", 4096) << 20
+
+
+class ResNetTower(_TowerBase):
+    """OpenAI CLIP / open_clip ModifiedResNet image tower (`visual.*`), one mq_encode_resnet_* call per chunk of images.  Every BatchNorm is
+    folded into the convolution in front of it at load; bf16 only; the small-call native queue does not take these towers."""
+
+    has_native_queue = False
+
+    def __init__(self, arch, sd: Dict[str, Tensor], device: str, mean: Sequence[float] = OPENAI_DATASET_MEAN,
+                 std: Sequence[float] = OPENAI_DATASET_STD, precision: str = "bf16", max_workspace_bytes: Optional[int] = None):
+        if precision != "bf16":
+            raise ValueError(f"ResNet towers run in bf16 only (engine_precision {precision!r} is not supported for RN* models)")
+        super().__init__(device)
+        self.precision, self.arch, self._fp8 = precision, arch, None
+        h, v, w0 = self._h, "visual.", arch.width
+        f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+
+        def conv_bn(conv, bn, O, I, k):
+            return resnet_fold_bn(f32(conv + ".weight", (O, I, k, k)), f32(bn + ".weight", (O,)), f32(bn + ".bias", (O,)),
+                                  f32(bn + ".running_mean", (O,)), f32(bn + ".running_var", (O,)))
+
+        c1, wp = w0 // 2, resnet_pad64(w0)
+        w = L.ResNetWeights()
+        a, b = conv_bn(v + "conv1", v + "bn1", c1, 3, 3)
+        w.stem_w[0], w.stem_b[0] = h.bf16(resnet_stem_weight(a)), h.f32(b)
+        a, b = conv_bn(v + "conv2", v + "bn2", c1, c1, 3)
+        w.stem_w[1], w.stem_b[1] = h.bf16(resnet_conv3x3_weight(a, c1, c1)), h.f32(b)
+        a, b = conv_bn(v + "conv3", v + "bn3", w0, c1, 3)
+        w.stem_w[2], w.stem_b[2] = h.bf16(resnet_conv3x3_weight(a, c1, wp)), h.f32(resnet_pad_vec(b, wp))
+        blocks, inp = [], w0
+        for i, depth in enumerate(arch.layers):
+            P = w0 << i
+            Pp, O = resnet_pad64(P), 4 * P
+            for j in range(depth):
+                p = f"{v}layer{i + 1}.{j}."
+                ip = resnet_pad64(inp)
+                bw = L.ResNetBlockWeights()
+                a, b = conv_bn(p + "conv1", p + "bn1", P, inp, 1)
+                bw.conv1_w, bw.conv1_b = h.bf16(resnet_conv1x1_weight(a, ip, Pp)), h.f32(resnet_pad_vec(b, Pp))
+                a, b = conv_bn(p + "conv2", p + "bn2", P, P, 3)
+                bw.conv2_w, bw.conv2_b = h.bf16(resnet_conv3x3_weight(a, Pp, Pp)), h.f32(resnet_pad_vec(b, Pp))
+                a, b = conv_bn(p + "conv3", p + "bn3", O, P, 1)
+                bw.conv3_w, bw.conv3_b = h.bf16(resnet_conv1x1_weight(a, Pp, O)), h.f32(b)
+                if (i > 0 and j == 0) or inp != O:
+                    a, b = conv_bn(p + "downsample.0", p + "downsample.1", O, inp, 1)
+                    bw.ds_w, bw.ds_b = h.bf16(resnet_conv1x1_weight(a, ip, O)), h.f32(b)
+                blocks.append(bw)
+                inp = O
+        self._blocks = (L.ResNetBlockWeights * len(blocks))(*blocks)
+        w.blocks = C.cast(self._blocks, C.POINTER(L.ResNetBlockWeights))
+        Cw, T, E = 32 * w0, arch.tokens, arch.out_dim
+        apw = resnet_attnpool_weights(sd, arch)
+        w.pos = h.f32(apw["pos"])
+        w.q_w, w.q_b = h.bf16(apw["q_w"]), h.f32(apw["q_b"])
+        w.kv_w, w.kv_b = h.bf16(apw["kv_w"]), h.f32(apw["kv_b"])
+        w.c_w, w.c_b = h.bf16(apw["c_w"]), h.f32(apw["c_b"])
+        self.w = w
+        self.cfg = L.ResNetCfg(image_size=arch.image_size, layers=(C.c_int32 * 4)(*arch.layers), width=w0, heads=arch.heads, out_dim=E,
+                               mean=(C.c_float * 3)(*mean), std=(C.c_float * 3)(*std))
+        per_image = self.lib.mq_resnet_workspace_bytes(C.byref(self.cfg), 1)
+        if per_image == 0:
+            raise ValueError(f"ResNet configuration not supported by the kernels: {arch}")
+        budget = RESNET_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+        self.max_images_per_call = max(1, min(65535, budget // per_image))
+
+    def release_unused_folded(self) -> int:
+        return 0   # (the folded convolutions are the only copies the blocks hold)
+
+    def queue_rows_images(self, tensors: Sequence[Tensor], normalize: bool = True) -> Optional[np.ndarray]:
+        return None   # small `.preprocess` calls take the regular path
+
+    def _run(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
+        n = pixels.shape[0]
+        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
+        fn = self.lib.mq_encode_resnet_u8 if kind == "u8" else self.lib.mq_encode_resnet_f32
+        with torch.cuda.device(self.device):
+            for i in range(0, n, self.max_images_per_call):
+                m = min(self.max_images_per_call, n - i)
+                ws = self._workspace(self.lib.mq_resnet_workspace_bytes(C.byref(self.cfg), m))
+                L.check(fn(C.byref(self.cfg), C.byref(self.w), pixels[i:i + m].data_ptr(), m, out[i:i + m].data_ptr(), 1 if normalize else 0,
+                           ws.data_ptr(), ws.numel(), self._stream()), "mq_encode_resnet")
+        return out
+
+    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
+        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
+        S = self.arch.image_size
+        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
+            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+        return self._run("u8", images_u8.to(self.device, non_blocking=True).contiguous(), normalize)
+
+    def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
+        """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
+        S = self.arch.image_size
+        if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
+            raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
+        return self._run("f32", pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous(), normalize)

@@ -98,8 +98,21 @@ _HF_BERT = {
 }
 
 
+# ResNet CLIPs (model_registry.py:16-140): OpenAI's ModifiedResNet image towers, resolved by archs.resolve_resnet_clip
+_RESNET_TAGS = {
+    "RN50": ["openai", "yfcc15m", "cc12m"], "RN50-quickgelu": ["openai", "yfcc15m", "cc12m"],
+    "RN101": ["openai", "yfcc15m"], "RN101-quickgelu": ["openai", "yfcc15m"],
+    "RN50x4": ["openai"], "RN50x16": ["openai"], "RN50x64": ["openai"],
+}
+
+
 def _get_open_clip_properties() -> Dict:
     out = {}
+    for arch_name, tags in _RESNET_TAGS.items():
+        vision, _ = archs.resolve_resnet_clip(arch_name)
+        for tag in tags:
+            name = f"open_clip/{arch_name}/{tag}"
+            out[name] = {"name": name, "dimensions": vision.out_dim, "note": "open_clip models", "type": "open_clip", "pretrained": tag}
     for arch_name, tags in _OPEN_CLIP_TAGS.items():
         vision, _ = archs.resolve_open_clip(arch_name)
         for tag in tags:
@@ -118,6 +131,9 @@ _FP16_CLIP_NAMES = ("ViT-B/32", "ViT-B/16", "ViT-L/14")   # the reference regist
 def _get_clip_properties() -> Dict:
     """OpenAI-CLIP names (model_registry.py:16-73) and their fp16 variants (:2069-2092): same towers, QuickGELU."""
     out = {}
+    for openai_name, arch_name in archs.OPENAI_RESNET_NAMES.items():
+        vision, _ = archs.resolve_resnet_clip(arch_name, "openai")
+        out[openai_name] = {"name": openai_name, "dimensions": vision.out_dim, "notes": f"CLIP resnet{openai_name[2:].lower()}", "type": "clip"}
     for openai_name, arch_name in archs.OPENAI_CLIP_NAMES.items():
         vision, _ = archs.resolve_open_clip(arch_name, "openai")
         out[openai_name] = {"name": openai_name, "dimensions": vision.out_dim, "notes": "CLIP resnet", "type": "clip"}

@@ -225,6 +225,8 @@ class OPEN_CLIP(AbstractCLIPModel):
                                       bool(mc.get("quick_gelu", False)))
             return vision, text
         try:
+            if arch_name.split("-quickgelu")[0] in archs.RESNET_CLIP_ARCHS:
+                return archs.resolve_resnet_clip(arch_name, tag)
             return archs.resolve_open_clip(arch_name, tag)
         except KeyError as e:
             raise InvalidModelPropertiesError(str(e)) from e
@@ -283,7 +285,8 @@ class OPEN_CLIP(AbstractCLIPModel):
         self.preprocess_config = {"size": self.vision_arch.image_size, "mean": self._mean, "std": self._std,
                                   "interpolation": self._interpolation, "resize_mode": self._resize_mode}
         try:
-            tower = towers.ConvNextTower if isinstance(self.vision_arch, archs.ConvNextArch) else towers.VitTower
+            tower = (towers.ConvNextTower if isinstance(self.vision_arch, archs.ConvNextArch) else
+                     towers.ResNetTower if isinstance(self.vision_arch, archs.ResNetArch) else towers.VitTower)
             self.vision = tower(self.vision_arch, sd, self.device, mean=self._mean, std=self._std, precision=props.engine_precision)
             self.text = self._make_text_tower(sd, props.engine_precision)
         except ValueError as e:  # e.g. fp8 needs width / mlp_dim multiples of 128
@@ -724,10 +727,11 @@ class CLIP(OPEN_CLIP):
         props = dict(model_properties or {})
         name = props.get("name", model_type)
         base = name[len("fp16/"):] if name.startswith("fp16/") else name
-        if base in archs.OPENAI_CLIP_NAMES and not (props.get("localpath") or props.get("url")):
-            props["name"] = f"open_clip/{archs.OPENAI_CLIP_NAMES[base]}/openai"
-        elif base in archs.OPENAI_CLIP_NAMES:
-            props["name"] = archs.OPENAI_CLIP_NAMES[base] + "-quickgelu"
+        openai_names = archs.OPENAI_RESNET_NAMES if base in archs.OPENAI_RESNET_NAMES else archs.OPENAI_CLIP_NAMES
+        if base in openai_names and not (props.get("localpath") or props.get("url")):
+            props["name"] = f"open_clip/{openai_names[base]}/openai"
+        elif base in openai_names:
+            props["name"] = openai_names[base] + "-quickgelu"
         props.setdefault("dimensions", embedding_dim)
         props.setdefault("type", "clip")
         super().__init__(device=device, model_properties=props, model_auth=model_auth)
@@ -883,6 +887,8 @@ class CLIP_ONNX(OPEN_CLIP):
                 raise InvalidModelPropertiesError(f"{model_name}: {archs.UNSUPPORTED_HINT}")
             name = f"open_clip/{archs.OPENAI_CLIP_NAMES[self.clip_model]}/openai"
         else:
+            if self.clip_model.split("/")[0].split("-quickgelu")[0] in archs.RESNET_CLIP_ARCHS:   # (the ResNet towers serve their own names only)
+                raise InvalidModelPropertiesError(f"{model_name}: {archs.UNSUPPORTED_HINT}")
             name = "open_clip/" + self.clip_model
         props = {"name": name, "dimensions": (model_properties or {}).get("dimensions", embedding_dim), "type": "open_clip"}
         for k in ("enginePrecision", "fp8Budget"):
