@@ -54,6 +54,7 @@ extern "C" {
 #define MQ_ACT_GELU 1      /* erf GELU (open_clip nn.GELU, HF "gelu") */
 #define MQ_ACT_QUICKGELU 2 /* x * sigmoid(1.702 x) (OpenAI / *-quickgelu weights) */
 #define MQ_ACT_SILU 3      /* x * sigmoid(x): the gate of the SwiGLU MLP (EVA02 towers; gated MLPs only) */
+#define MQ_ACT_RELU 4      /* max(0, x) (the M2M100 / NLLB encoder behind the NLLB-CLIP text towers): plain pre-LN bf16 encoders only — no fp8, no gated MLP */
 
 #define MQ_MASK_NONE 0   /* ViT: full attention inside a sequence */
 #define MQ_MASK_CAUSAL 1 /* CLIP text tower */
@@ -483,7 +484,9 @@ int mq_ln_gemm_small_bf16(const void* d_x, int64_t ldx, int x_bf16, const float*
  * holds up AND gate of the same hidden units; out bf16 [M, F] at row stride ldc: out[m, u] = (up + b_up) * silu(gate + b_gate).  N % 32 == 0. */
 #define MQ_EPI_GLU 256
 /* MQ_EPI_RELU (mq_gemm_bf16 with MQ_EPI_BIAS [| MQ_EPI_RESIDUAL], bf16 out): max(0, .) as the last step, after the residual add (the ResNet
- * towers' conv + BN + ReLU and conv3 + BN + identity + ReLU).  These combinations always run on the tiled GEMMs, whatever the row count. */
+ * towers' conv + BN + ReLU and conv3 + BN + identity + ReLU).  These combinations always run on the tiled GEMMs, whatever the row count.
+ * MQ_EPI_BIAS | MQ_EPI_RELU is also an epilogue of mq_gemm_bf16_ln (LayerNorm folded in) and of the skinny kernels (mq_gemm_small_bf16,
+ * mq_ln_gemm_small_bf16): the fc1 of an MQ_ACT_RELU encoder block, whatever its row count. */
 #define MQ_EPI_RELU 512
 int mq_gemm_bf16_rs(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const void* d_residual, void* d_out, int64_t ldc,
                     int64_t M, int64_t N, int64_t K, int flags, float* d_partials, void* stream);
@@ -830,6 +833,15 @@ size_t mq_tokenize_sentencepiece_workspace_bytes(int64_t n, int64_t total_bytes,
 int mq_tokenize_sentencepiece(const mq_sentencepiece_vocab* v, const uint8_t* d_text, const int64_t* d_offsets, int64_t n,
                               int64_t total_bytes, int32_t max_length, int32_t* d_ids, int64_t ld, int32_t* d_lens,
                               int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* SentencePiece BPE (the NLLB vocabulary of the NLLB-CLIP text towers): the same vocabulary struct and normalisation stage as the unigram entry,
+ * then SentencePiece's BPE encode per whitespace word (one thread per word): start from the characters, repeatedly merge the adjacent pair whose
+ * concatenation is a piece with the highest score (leftmost on ties) until none is; a symbol that is no piece is <unk> (consecutive ones joined into one).  The caller guarantees
+ * that no piece carries U+2581 behind its first character (merges then never cross a word).  unk_score is unused.  Rows as above.
+ * Workspace: mq_tokenize_workspace_bytes(n, total_bytes, max_length). */
+int mq_tokenize_sentencepiece_bpe(const mq_sentencepiece_vocab* v, const uint8_t* d_text, const int64_t* d_offsets, int64_t n,
+                                  int64_t total_bytes, int32_t max_length, int32_t* d_ids, int64_t ld, int32_t* d_lens,
+                                  int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* padded id rows -> the packed layout of the text towers: d_packed[cu[s] + j] = d_padded[s * ld + j], j < cu[s+1] - cu[s] */
 int mq_pack_ids(const int32_t* d_padded, int64_t ld, const int32_t* d_cu_seqlens, int64_t nseq, int32_t* d_packed,

@@ -31,7 +31,7 @@ MQ_OK = 0
 NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet")  # build() refuses register spills in these
 ABI_VERSION = 14
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
-MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU = 1, 2, 3
+MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
 MQ_MASK_NONE, MQ_MASK_CAUSAL, MQ_MASK_CAUSAL_CLS = 0, 1, 2
 MQ_POOL_MEAN, MQ_POOL_CLS = 0, 1
 MQ_VIT_POOL_CLS, MQ_VIT_POOL_MAP, MQ_VIT_POOL_AVG, MQ_VIT_POOL_QUERY = 0, 1, 2, 3
@@ -254,6 +254,8 @@ _SIGNATURES = {
     "mq_tokenize_sentencepiece_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
     "mq_tokenize_sentencepiece": (C.c_int, [C.POINTER(SentencePieceVocab), _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P,
                                             C.c_size_t, _P]),
+    "mq_tokenize_sentencepiece_bpe": (C.c_int, [C.POINTER(SentencePieceVocab), _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P,
+                                                C.c_size_t, _P]),
     "mq_pack_ids": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
     "mq_weighted_combine": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     "mq_queue_create": (C.c_int, [C.POINTER(QueueCfg), _P, _P, C.POINTER(_P)]),

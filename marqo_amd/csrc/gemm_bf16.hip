@@ -700,7 +700,7 @@ extern "C" int mq_gemm_bf16(const void* d_A, int64_t lda, const void* d_W, int64
 
 // GEMM over the UN-normalised bf16 rows with the LayerNorm folded in (gemm_epilogue.h): out = act( LN(A) @ W0^T + b0 ) where d_W = bf16(gamma * W0)
 // (the LayerNorm's scale folded into the weight's columns), d_bias = b0 + W0 @ beta, d_colsum[n] = sum_k d_W[n, k] (of the ROUNDED folded weight),
-// d_rowstats = (mean, rstd) per row of A (mq_row_stats) and K = the normalised width.  flags: MQ_EPI_BIAS [| MQ_EPI_GELU | MQ_EPI_QUICKGELU]; bf16 out.
+// d_rowstats = (mean, rstd) per row of A (mq_row_stats) and K = the normalised width.  flags: MQ_EPI_BIAS [| MQ_EPI_GELU | MQ_EPI_QUICKGELU | MQ_EPI_RELU]; bf16 out.
 extern "C" int mq_gemm_bf16_ln(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const float* d_colsum,
                                const float* d_rowstats, void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     MQ_CHECK_ARG(d_A && d_W && d_out && d_bias && d_colsum && d_rowstats, "mq_gemm_bf16_ln: null operand");
@@ -718,6 +718,7 @@ extern "C" int mq_gemm_bf16_ln(const void* d_A, int64_t lda, const void* d_W, in
         MQ_GEMM_LN_CASE(MQ_EPI_BIAS | MQ_EPI_LN_APPLY);
         MQ_GEMM_LN_CASE(MQ_EPI_BIAS | MQ_EPI_GELU | MQ_EPI_LN_APPLY);
         MQ_GEMM_LN_CASE(MQ_EPI_BIAS | MQ_EPI_QUICKGELU | MQ_EPI_LN_APPLY);
+        MQ_GEMM_LN_CASE(MQ_EPI_BIAS | MQ_EPI_RELU | MQ_EPI_LN_APPLY);   // fc1 of an MQ_ACT_RELU block (the NLLB text tower)
         MQ_GEMM_LN_CASE(MQ_EPI_BIAS | MQ_EPI_GLU | MQ_EPI_LN_APPLY);
         default:
             mq_set_error("mq_gemm_bf16_ln: unsupported epilogue flag combination 0x%x", flags);

@@ -189,6 +189,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_small_kernel(const void* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
         }
+        if constexpr ((FLAGS & MQ_EPI_RELU) != 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        }
         const int64_t o = (int64_t)m * ldc + n;
         if (FLAGS & MQ_EPI_RESIDUAL) {
             if (RES_BF16) {
@@ -300,6 +304,7 @@ int mq_gemm_small(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, co
         MQ_SM_CASE(MQ_EPI_BIAS);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_GELU);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_QUICKGELU);
+        MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_RELU);   // fc1 of an MQ_ACT_RELU block (the NLLB text tower)
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_RESIDUAL);
         default:
@@ -327,6 +332,7 @@ int mq_ln_gemm_small(const void* d_x, int64_t ldx, int x_bf16, const float* ln_g
         MQ_SM_CASE(MQ_EPI_BIAS);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_GELU);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_QUICKGELU);
+        MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_RELU);   // fc1 of an MQ_ACT_RELU block (the NLLB text tower)
         default:
             mq_set_error("mq_ln_gemm_small: unsupported epilogue flag combination 0x%x", flags);
             return MQ_ERR_INVALID;

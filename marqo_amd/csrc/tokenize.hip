@@ -2,7 +2,7 @@
 // The algorithms are the host+device functions of tokenize_algo.h, in three launches per call: A splits every text into
 // word / pre-token spans (one thread per text, no table access), B runs the vocabulary work — greedy WordPiece matching / BPE
 // merging, dependent hash-table lookups in L2 — one thread per WORD (a 1024-text batch is ~60 k threads instead of the 1 k
-// of a thread-per-text form, which measured 3 ms per batch), C concatenates per text.  Latency-bound byte and integer work:
+// of a thread-per-text form, which measured 3 ms per batch), C concatenates per text.  SentencePiece BPE (NLLB) takes the same three phases.  Latency-bound byte and integer work:
 // per-thread scratch (the current word / its BPE symbols) lives in LDS, lane-strided so that lane t touches bank
 // (i*64 + t) and the waves never conflict.  Deliberately not reshaped into anything matrix-like.
 #include "common.h"
@@ -141,6 +141,47 @@ __global__ __launch_bounds__(TOK_THREADS) void sp_kernel(mq_sp_table T, mq_sp_fr
     status[t] = st;
 }
 
+// ---- SentencePiece BPE: the three phases of the WordPiece path (split per text, merges per word, gather per text) -------------------------
+__global__ __launch_bounds__(TOK_THREADS) void spb_split_kernel(mq_sp_table T, const uint8_t* __restrict__ text, const int64_t* __restrict__ offsets, int n, int cap,
+                                                                uint64_t* __restrict__ spans, uint8_t* __restrict__ norm, int32_t* __restrict__ totals,
+                                                                int32_t* __restrict__ status) {
+    const int t = blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (t >= n) return;
+    const int64_t b0 = offsets[t], b1 = offsets[t + 1];
+    int st;
+    totals[t] = mq_spb_split(T, text + b0, (int)(b1 - b0), cap, spans + (int64_t)t * cap, norm + norm_base(b0, t), &st);
+    status[t] = st;
+}
+
+__global__ __launch_bounds__(TOK_THREADS) void spb_word_kernel(mq_sp_table T, const uint8_t* __restrict__ norm, const int64_t* __restrict__ offsets, int cap,
+                                                               int blocks_per_text, const uint64_t* __restrict__ spans, const int32_t* __restrict__ totals,
+                                                               int16_t* __restrict__ counts, int32_t* __restrict__ pieces, int32_t* __restrict__ status) {
+    __shared__ uint8_t word[MQ_SPB_MAX_WORD * TOK_THREADS];
+    __shared__ uint8_t slen[MQ_SPB_MAX_WORD * TOK_THREADS];
+    __shared__ float pair[MQ_SPB_MAX_WORD * TOK_THREADS];
+    const int t = blockIdx.x / blocks_per_text;
+    const int j = (blockIdx.x - t * blocks_per_text) * TOK_THREADS + threadIdx.x;
+    const int nw = min(totals[t], cap);
+    if (j >= nw) return;
+    const int64_t nb = norm_base(offsets[t], t);
+    const uint64_t span = spans[(int64_t)t * cap + j];
+    const int c = mq_spb_word(T, norm + nb, span, pieces + nb + mq_span_start(span), word + threadIdx.x, slen + threadIdx.x, pair + threadIdx.x, TOK_THREADS);
+    if (c < 0) status[t] = MQ_TOK_NEEDS_HOST;   // (benign race: every writer stores the same value)
+    counts[(int64_t)t * cap + j] = (int16_t)(c < 0 ? 0 : c);
+}
+
+__global__ __launch_bounds__(TOK_THREADS) void spb_gather_kernel(mq_sp_table T, mq_sp_frame F, const int64_t* __restrict__ offsets, int n, int cap, int max_length,
+                                                                 const uint64_t* __restrict__ spans, const int32_t* __restrict__ totals,
+                                                                 const int16_t* __restrict__ counts, const int32_t* __restrict__ pieces,
+                                                                 int32_t* __restrict__ ids, int64_t ld, int32_t* __restrict__ lens, const int32_t* __restrict__ status) {
+    const int t = blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (t >= n) return;
+    const int ok = status[t] == MQ_TOK_OK;
+    const int len = mq_spb_gather(T, F, spans + (int64_t)t * cap, counts + (int64_t)t * cap, pieces + norm_base(offsets[t], t), ok ? min(totals[t], cap) : 0,
+                                  max_length, ids + (int64_t)t * ld, (int)ld);
+    lens[t] = ok ? len : 0;
+}
+
 // packed[cu[s] + j] = padded[s, j] for j < cu[s+1] - cu[s]
 __global__ __launch_bounds__(256) void pack_ids_kernel(const int32_t* __restrict__ padded, int64_t ld, const int32_t* __restrict__ cu,
                                                        int32_t* __restrict__ packed) {
@@ -247,6 +288,37 @@ extern "C" int mq_tokenize_sentencepiece(const mq_sentencepiece_vocab* v, const 
     hipLaunchKernelGGL(sp_kernel, dim3((unsigned)cdiv64(n, TOK_THREADS)), dim3(TOK_THREADS), 0, s, T, F, d_text, d_offsets, (int)n, max_length, w.norm,
                        w.best, w.bstart, w.bid, w.pieces, d_ids, ld, d_lens, d_status);
     MQ_CHECK_LAUNCH("mq_tokenize_sentencepiece");
+    return MQ_OK;
+}
+
+extern "C" int mq_tokenize_sentencepiece_bpe(const mq_sentencepiece_vocab* v, const uint8_t* d_text, const int64_t* d_offsets, int64_t n,
+                                             int64_t total_bytes, int32_t max_length, int32_t* d_ids, int64_t ld, int32_t* d_lens,
+                                             int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
+    MQ_CHECK_ARG(v && v->d_slots && v->d_pool && v->d_score && v->d_nmap && v->d_npool && v->d_ccc && pow2(v->n_slots),
+                 "mq_tokenize_sentencepiece_bpe: bad vocabulary tables");
+    MQ_CHECK_ARG(max_length >= 2 && ld >= max_length && v->max_piece_bytes >= 1, "mq_tokenize_sentencepiece_bpe: need 2 <= max_length (%d) <= ld (%ld)",
+                 max_length, (long)ld);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_text && d_offsets && d_ids && d_lens && d_status && d_workspace, "mq_tokenize_sentencepiece_bpe: null pointer");
+    MQ_CHECK_ARG(n < (1LL << 24) && total_bytes >= 0 && total_bytes < (1LL << 28), "mq_tokenize_sentencepiece_bpe: too many texts / bytes");
+    const int cap = max_length;   // words kept per text: every word yields at least one id
+    const TokWs w = tok_ws(d_workspace, n, total_bytes, cap, 4);
+    if (workspace_bytes < w.bytes) { mq_set_error("mq_tokenize_sentencepiece_bpe: workspace %zu < required %zu", workspace_bytes, w.bytes); return MQ_ERR_WORKSPACE; }
+    mq_sp_table T;
+    T.slots = (const mq_sp_entry*)v->d_slots; T.pool = v->d_pool; T.score = v->d_score; T.nmap = v->d_nmap; T.npool = v->d_npool; T.ccc = v->d_ccc;
+    T.mask = v->n_slots - 1; T.unk_id = v->unk_id; T.unk_score = v->unk_score; T.add_dummy_prefix = v->add_dummy_prefix;
+    T.remove_extra_ws = v->remove_extra_ws; T.max_piece_bytes = v->max_piece_bytes;
+    const mq_sp_frame F{v->prefix_id, v->suffix_id, v->pad_id, v->id_offset, v->unk_out};
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(3, s);
+    const unsigned per_text = (unsigned)cdiv64(n, TOK_THREADS);
+    const int bpt = (cap + TOK_THREADS - 1) / TOK_THREADS;
+    hipLaunchKernelGGL(spb_split_kernel, dim3(per_text), dim3(TOK_THREADS), 0, s, T, d_text, d_offsets, (int)n, cap, w.spans, w.norm, w.totals, d_status);
+    hipLaunchKernelGGL(spb_word_kernel, dim3((unsigned)(n * bpt)), dim3(TOK_THREADS), 0, s, T, w.norm, d_offsets, cap, bpt, w.spans, w.totals, w.counts,
+                       (int32_t*)w.pieces, d_status);
+    hipLaunchKernelGGL(spb_gather_kernel, dim3(per_text), dim3(TOK_THREADS), 0, s, T, F, d_offsets, (int)n, cap, max_length, w.spans, w.totals, w.counts,
+                       (const int32_t*)w.pieces, d_ids, ld, d_lens, d_status);
+    MQ_CHECK_LAUNCH("mq_tokenize_sentencepiece_bpe");
     return MQ_OK;
 }
 

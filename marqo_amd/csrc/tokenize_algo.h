@@ -634,3 +634,122 @@ MQ_TOK_FN int mq_sp_gather(const mq_sp_table& T, const mq_sp_frame& F, const int
     for (int j = cnt; j < ld; ++j) row[j] = F.pad_id;
     return cnt;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// SentencePiece BPE (the NLLB-200 vocabulary behind the NLLB-CLIP text towers).  Reference behaviour being reproduced (third-party,
+// un-vendored): sentencepiece's normaliser — the same stage as above, mq_sp_normalize over the same tables — followed by the BPE model's
+// Encode: the symbols start as the characters of the normalised text; the adjacent pair whose concatenation is a piece with the
+// HIGHEST score is merged, the LEFTMOST such pair on equal scores, until no adjacent pair spells a piece; a symbol that is no piece
+// becomes <unk>, and the processor joins consecutive <unk> into one, as it does behind the unigram model (mq_spb_gather: also across words).
+// The table builder (engine/gpu_tokenizers.py) admits a vocabulary only when no piece carries U+2581 behind its first character: a merge
+// then never joins symbols across a U+2581, so every stretch [U+2581] characters... ("word") is encoded on its own, one thread per word:
+//   A  mq_spb_split   (per text)  normalise, then one span per word
+//   B  mq_spb_word    (per word)  the merges; piece ids at the word's own (normalised) byte positions
+//   C  mq_spb_gather  (per text)  concatenate, truncate, frame (mq_sp_frame), pad
+// Pieces are looked up whole in the unigram path's hash table (mq_sp_find verifies the bytes; its prefix-only entries, id -2, are misses here).
+// ---------------------------------------------------------------------------------------------------------------
+#define MQ_SPB_MAX_WORD 128  // scratch bytes per thread for the current word; a longer word sends its text to the host
+#define MQ_SPB_NONE (-3.0e38f)  // pair score of two neighbours that spell no piece (piece scores are finite)
+
+// A: -> number of words (at most `cap` spans written: every word yields >= 1 id); *status as mq_sp_normalize
+MQ_TOK_FN int mq_spb_split(const mq_sp_table& T, const uint8_t* text, int nbytes, int cap, uint64_t* spans, uint8_t* norm, int* status) {
+    const int n = mq_sp_normalize(T, text, nbytes, norm, status);
+    if (*status != MQ_TOK_OK) return 0;
+    int cnt = 0, start = 0;
+    for (int i = 0; i <= n;) {
+        const int boundary = i == n || (i + 2 < n && norm[i] == 0xe2 && norm[i + 1] == 0x96 && norm[i + 2] == 0x81);
+        if (boundary && i > start) {
+            if (cnt < cap) spans[cnt] = mq_span(start, i - start, 0);
+            ++cnt;
+            start = i;
+        }
+        i += i < n ? mq_utf8_len(norm[i]) : 1;
+    }
+    return cnt;
+}
+
+// score of the piece spelt by w[s .. s + len) (scratch with element stride ws), *id its id; found = 0 when it is no piece
+MQ_TOK_FN int mq_spb_piece(const mq_sp_table& T, const uint8_t* w, int ws, int s, int len, int32_t* id) {
+    if (len > 255 || len > T.max_piece_bytes) return 0;
+    uint64_t h = MQ_FNV_OFFSET;
+    for (int k = 0; k < len; ++k) h = mq_wp_step(h, w[(s + k) * ws]);
+    uint32_t slot = (uint32_t)(h ^ (h >> 32)) & T.mask;
+    for (;;) {
+        const mq_sp_entry e = T.slots[slot];
+        if (e.id == -1) return 0;
+        if (e.hash == h && (int)(e.off_len & 0xffu) == len) {
+            const uint8_t* p = T.pool + (e.off_len >> 8);
+            int same = 1;
+            for (int k = 0; k < len; ++k)
+                if (p[k] != w[(s + k) * ws]) { same = 0; break; }
+            if (same) { *id = e.id; return e.id >= 0; }
+        }
+        slot = (slot + 1) & T.mask;
+    }
+}
+
+// B: BPE of one word (span from A, bytes in `norm`) -> out[0 .. count) (room for one id per byte of the word), SentencePiece numbering; returns
+// count, or -1 when the word does not fit the scratch.  Scratch per thread, element stride ws: word [MQ_SPB_MAX_WORD] bytes, slen
+// [MQ_SPB_MAX_WORD] (byte length of the symbol that starts at a byte, 0 inside a symbol), pair [MQ_SPB_MAX_WORD] (score of the piece spelt by the
+// symbol starting there and its right neighbour, MQ_SPB_NONE when that is no piece)
+MQ_TOK_FN int mq_spb_word(const mq_sp_table& T, const uint8_t* norm, uint64_t span, int32_t* out, uint8_t* word, uint8_t* slen, float* pair, int ws) {
+    const int start = mq_span_start(span), L = mq_span_bytes(span);
+    if (L > MQ_SPB_MAX_WORD) return -1;
+    for (int j = 0; j < L; ++j) { word[j * ws] = norm[start + j]; slen[j * ws] = 0; }
+    for (int j = 0; j < L;) {
+        int cl = mq_utf8_len(word[j * ws]);
+        if (j + cl > L) cl = L - j;
+        slen[j * ws] = (uint8_t)cl;
+        j += cl;
+    }
+    // pair scores of every adjacent pair
+    auto refresh = [&](int s) {
+        const int a = slen[s * ws], r = s + a;
+        pair[s * ws] = MQ_SPB_NONE;
+        if (r >= L) return;
+        int32_t id;
+        if (mq_spb_piece(T, word, ws, s, a + slen[r * ws], &id)) pair[s * ws] = T.score[id];
+    };
+    for (int s = 0; s < L; s += slen[s * ws]) refresh(s);
+    for (;;) {
+        int best = -1, best_prev = -1, prev = -1;
+        float best_score = MQ_SPB_NONE;
+        for (int s = 0; s < L; s += slen[s * ws]) {
+            if (pair[s * ws] > best_score) { best = s; best_prev = prev; best_score = pair[s * ws]; }   // strictly greater: the leftmost of equals
+            prev = s;
+        }
+        if (best < 0) break;
+        const int r = best + slen[best * ws];
+        slen[best * ws] = (uint8_t)(slen[best * ws] + slen[r * ws]);
+        slen[r * ws] = 0;
+        refresh(best);
+        if (best_prev >= 0) refresh(best_prev);
+    }
+    int cnt = 0;
+    for (int s = 0; s < L; s += slen[s * ws]) {
+        int32_t id;
+        out[cnt++] = mq_spb_piece(T, word, ws, s, slen[s * ws], &id) ? id : T.unk_id;
+    }
+    return cnt;
+}
+
+// C: row = [prefix_id] ids + id_offset ... suffix_id pad...; returns the row length.  piece_cnt[j] / pieces at piece_buf[start_j ...] are B's output.
+MQ_TOK_FN int mq_spb_gather(const mq_sp_table& T, const mq_sp_frame& F, const uint64_t* spans, const int16_t* piece_cnt, const int32_t* piece_buf, int nwords,
+                            int max_length, int32_t* row, int ld) {
+    const int specials = (F.prefix_id >= 0 ? 1 : 0) + 1;
+    const int keep = max_length - specials > 0 ? max_length - specials : 0;
+    int cnt = 0, taken = 0, prev_unk = 0;
+    if (F.prefix_id >= 0) row[cnt++] = F.prefix_id;
+    for (int j = 0; j < nwords && taken < keep; ++j) {
+        const int32_t* src = piece_buf + mq_span_start(spans[j]);
+        const int k = piece_cnt[j];
+        for (int e = 0; e < k && taken < keep; ++e) {
+            const int unk = src[e] == T.unk_id;
+            if (!(unk && prev_unk)) { row[cnt++] = unk ? F.unk_out : src[e] + F.id_offset; ++taken; }   // consecutive <unk> are one piece
+            prev_unk = unk;
+        }
+    }
+    row[cnt++] = F.suffix_id;
+    for (int j = cnt; j < ld; ++j) row[j] = F.pad_id;
+    return cnt;
+}

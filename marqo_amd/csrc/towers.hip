@@ -72,6 +72,10 @@ static inline const void* pf(const void* w) { return t_ln_prefetch ? w : nullptr
 int mq_layernorm_fp8_pf(const void* d_x, int x_bf16, const float* d_g, const float* d_b, void* d_out_fp8, float* d_row_scale, float* d_out_f32,
                         int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 bool mq_gemm_small_grouped_ok(int64_t M, int64_t N, int64_t K);
+int mq_gemm_small(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const void* d_residual, void* d_out, int64_t ldc, int64_t M,
+                  int64_t N, int64_t K, int flags, hipStream_t s);
+// the epilogue flag of a plain (un-gated) MLP's activation
+static inline int act_epi(int act) { return act == MQ_ACT_QUICKGELU ? MQ_EPI_QUICKGELU : act == MQ_ACT_RELU ? MQ_EPI_RELU : MQ_EPI_GELU; }
 extern "C" int mq_gemm_bf16_ln(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const float* d_colsum,
                                const float* d_rowstats, void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 extern "C" int mq_gemm_bf16_rs(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const void* d_residual, void* d_out,
@@ -102,6 +106,10 @@ static int ln_gemm(const void* d_x, int xb, const float* g, const float* b, floa
         return mq_gemm_bf16_ln(d_x, K, wf, K, bf, sf, row_stats, out, N, rows, N, K, flags, s);
     }
     MQ_TRY(mq_layernorm_pf(d_x, xb, nullptr, g, b, h, nullptr, rows, K, eps, pf(W), (size_t)N * K * 2, pf(next_w), next_bytes, s));
+    // (mq_gemm_bf16 keeps its MQ_EPI_RELU calls — the ResNet towers' — on the tiled family for any row count; an encoder block's few rows take the
+    // skinny kernel like their GELU twins)
+    if ((flags & MQ_EPI_RELU) && (mq_gemm_small_ok(rows, N, K, false) || mq_gemm_small_grouped_ok(rows, N, K)))
+        return mq_gemm_small(h, K, W, K, bias, nullptr, out, N, rows, N, K, flags, s);
     return mq_gemm_bf16(h, K, W, K, bias, nullptr, out, N, rows, N, K, flags, s);
 }
 // ln_gemm's folded form for fixed-length image sequences that fill the chip: one workgroup per image (panel_gemm.hip; same output bits).  false = not taken
@@ -168,7 +176,11 @@ int check_encoder_cfg(const mq_encoder_cfg* c) {
                  "encoder attention width must be heads * {64, 96, 112, 128} (attention width %d, heads %d)", wa, c->heads);
     MQ_CHECK_ARG(c->mlp_dim >= 64 && c->mlp_dim % 64 == 0, "encoder mlp_dim %d must be a multiple of 64", c->mlp_dim);
     MQ_CHECK_ARG(c->layers >= 0, "encoder layers < 0");
-    MQ_CHECK_ARG(c->act == MQ_ACT_GELU || c->act == MQ_ACT_QUICKGELU || (c->act == MQ_ACT_SILU && c->mlp_glu), "encoder act %d unsupported (MQ_ACT_SILU: gated MLPs only)", c->act);
+    MQ_CHECK_ARG(c->act == MQ_ACT_GELU || c->act == MQ_ACT_QUICKGELU || (c->act == MQ_ACT_SILU && c->mlp_glu) || c->act == MQ_ACT_RELU,
+                 "encoder act %d unsupported (MQ_ACT_SILU: gated MLPs only)", c->act);
+    if (c->act == MQ_ACT_RELU)
+        MQ_CHECK_ARG(c->precision == MQ_PREC_BF16 && !c->post_ln && !c->mlp_glu && !c->d_rope_inv_freq && !c->d_rope_table,
+                     "MQ_ACT_RELU: plain pre-LN encoders on bf16 operands only (no fp8, no gated MLP, no rotary positions)");
     MQ_CHECK_ARG(c->mlp_glu >= 0 && c->mlp_glu <= 2 && (c->mlp_glu != 2 || (!c->post_ln && c->act == MQ_ACT_SILU && c->mlp_dim % 16 == 0)),
                  "mlp_glu = 2 (fc1 rows interleaved for MQ_EPI_GLU): pre-LN blocks with MQ_ACT_SILU and mlp_dim %% 16 == 0");
     MQ_CHECK_ARG(c->precision == MQ_PREC_BF16 || c->precision == MQ_PREC_FP8, "encoder precision %d unsupported", c->precision);
@@ -253,7 +265,7 @@ int last_block_selected(const mq_encoder_cfg* cfg, const mq_block_weights& b, in
                         const int32_t* d_sel, int64_t nsel, void* h, void* a, void* qf, float* row_scale, float* row_stats, bool stats_ready, float* x_sel,
                         bool f8, hipStream_t s) {
     const int W = cfg->width, F = cfg->mlp_dim, Wa = attn_width(cfg);
-    const int act_flag = cfg->act == MQ_ACT_QUICKGELU ? MQ_EPI_QUICKGELU : MQ_EPI_GELU;
+    const int act_flag = act_epi(cfg->act);
     const int res_flags = MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32;
     if (f8) {
         const float* s_attn = cfg->d_fp8_act_scale + 2 * l;
@@ -489,7 +501,7 @@ int EncoderPass::block_pre_ln(const mq_block_weights& b, int l) {
     // (the LAST block of a call that reads only pooled rows never folds its MLP: the pooled rows take the small-call kernels — LayerNorm
     // kernel + un-folded weights — and dead-row elimination stays bit-identical to this all-rows form, tests/test_towers_gpu.py)
     panel = false;
-    if (!last_pooled)
+    if (!last_pooled && !(act_flag & MQ_EPI_RELU))   // (the panel kernel has GELU / QuickGELU epilogues only)
         MQ_TRY(ln_gemm_panel(panel, d_x, xb, cfg->ln_eps, qf, rows, nseq, fixed_len, d_cu_seqlens, F, W, MQ_EPI_BIAS | act_flag, s, b.fc2_w, (size_t)W * F * 2, b.fc1_wf, b.fc1_bf,
                              b.fc1_sf, row_stats, fold_mlp));
     if (!panel)
@@ -616,7 +628,7 @@ int encoder_forward_impl(const mq_encoder_cfg* cfg, const mq_block_weights* bloc
     else if (cfg->post_ln) MQ_TRY(mq_cast_bf16(d_x, h, rows * W, s));
 
     EncoderPass p{cfg, blocks, d_x, rows, d_cu_seqlens, nseq, fixed_len, max_len, d_sel, nsel, s, W, F, Wa, h, a, qf, row_scale, row_stats, row_part, xn, band_ctr,
-                  /*x_has_partials*/ false, cfg->act == MQ_ACT_QUICKGELU ? MQ_EPI_QUICKGELU : MQ_EPI_GELU, MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32, first8};
+                  /*x_has_partials*/ false, act_epi(cfg->act), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32, first8};
     for (int l = 0; l < cfg->layers; ++l) {
         const mq_block_weights& b = blocks[l];
         const bool f8 = l >= first8;

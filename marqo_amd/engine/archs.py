@@ -262,6 +262,52 @@ class HfClipTextArch:
         return self.bert.gflop_per_text(tokens or self.ctx) + 2 * (self.bert.width + self.out_dim) * self.proj_hidden / 1e9
 
 
+@dataclass(frozen=True)
+class NllbTextArch:
+    """The NLLB-CLIP text tower (hf-hub:visheratin/nllb-clip-*-siglip, model_registry.py:510-533 in the reference): open_clip's HFTextEncoder
+    over the ENCODER of facebook/nllb-200-distilled-600M (12 layers, FFN 4096) / -1.3B (24 layers, FFN 8192) — a transformers M2M100 encoder:
+    pre-LN blocks with a key-padding mask and a ReLU MLP, token embeddings scaled by sqrt(width), sinusoidal positions (first token at
+    position padding_idx + 1 = 2), a final LayerNorm — then `cls_pooler` (position 0: the language-code token) and a `linear` projection without
+    bias.  Checkpoint keys `text.transformer.{embed_tokens, layers.N.*, layer_norm}` + `text.proj.weight`.  Rows are
+    [lang code] pieces + 1 ... </s> = 2, padded with <pad> = 1 to ctx; only the un-padded rows run."""
+    vocab: int = 256206
+    ctx: int = 77
+    width: int = 1024
+    layers: int = 12
+    heads: int = 16
+    mlp_dim: int = 4096
+    out_dim: int = 768
+    pad_id: int = 1
+    ln_eps: float = 1e-5
+    pos_offset: int = 2        # M2M100SinusoidalPositionalEmbedding: `offset` = 2 rows in front of the table, first token at padding_idx + 1
+    src_lang: str = "eng_Latn"  # what open_clip's HFTokenizer gets from NllbTokenizer without a `src_lang`
+    hf_model_name: str = "facebook/nllb-200-distilled-600M"
+
+    def position_table(self):
+        """fp32 [ctx, width]: row i = the sinusoidal embedding of position pos_offset + i, transformers' M2M100SinusoidalPositionalEmbedding.get_embedding
+        (the torch ops in their order): half = width // 2 frequencies exp(-k * ln(10000) / (half - 1)), [sin | cos] halves.  A non-persistent buffer
+        there, so no checkpoint carries it."""
+        import math
+        import torch
+        half = self.width // 2
+        emb = math.log(10000) / (half - 1)
+        emb = torch.exp(torch.arange(half, dtype=torch.int64).float() * -emb)
+        emb = torch.arange(self.pos_offset + self.ctx, dtype=torch.int64).float().unsqueeze(1) * emb.unsqueeze(0)
+        emb = torch.cat([torch.sin(emb), torch.cos(emb)], dim=1).view(self.pos_offset + self.ctx, -1)
+        if self.width % 2 == 1:
+            emb = torch.cat([emb, torch.zeros(self.pos_offset + self.ctx, 1)], dim=1)
+        return emb[self.pos_offset:].contiguous()
+
+    def gflop_per_text(self, tokens: Optional[int] = None) -> float:
+        T, W, F = tokens or self.ctx, self.width, self.mlp_dim
+        layer = 2 * T * W * (3 * W) + 2 * T * W * W + 2 * 2 * T * W * F + 4 * T * T * W
+        return (self.layers * layer + 2 * W * self.out_dim) / 1e9
+
+
+_NLLB_BASE = NllbTextArch(layers=12, mlp_dim=4096, out_dim=768, hf_model_name="facebook/nllb-200-distilled-600M")
+_NLLB_LARGE = NllbTextArch(layers=24, mlp_dim=8192, out_dim=1152, hf_model_name="facebook/nllb-200-distilled-1.3B")
+NLLB_TEXT_ARCHS = {a.hf_model_name: a for a in (_NLLB_BASE, _NLLB_LARGE)}
+
 _TEXT_B = ClipTextArch(vocab=49408, ctx=77, width=512, layers=12, heads=8, mlp_dim=2048, out_dim=512)
 _TEXT_L = ClipTextArch(vocab=49408, ctx=77, width=768, layers=12, heads=12, mlp_dim=3072, out_dim=768)
 _TEXT_B_PLUS = ClipTextArch(vocab=49408, ctx=77, width=640, layers=12, heads=10, mlp_dim=2560, out_dim=640)
@@ -329,14 +375,23 @@ OPEN_CLIP_ARCHS = {
     "ViT-B-16-SigLIP-512": _siglip(512),
     "ViT-SO400M-14-SigLIP": _siglip(224, so400m=True), "ViT-SO400M-14-SigLIP-384": _siglip(384, so400m=True),
     "ViT-L-16-SigLIP-256": _siglip(256, large=True), "ViT-L-16-SigLIP-384": _siglip(384, large=True),
+    # NLLB-CLIP (model_registry.py:510-533; open_clip model configs nllb-clip-base-siglip / nllb-clip-large-siglip: the SigLIP image towers
+    # vit_base_patch16_siglip_384 / vit_so400m_patch14_siglip_384 + the NLLB-200 encoder as HF text tower)
+    "nllb-clip-base-siglip": (_siglip(384)[0], _NLLB_BASE),
+    "nllb-clip-large-siglip": (_siglip(384, so400m=True)[0], _NLLB_LARGE),
 }
-# architectures the registry names but which are not ViT / CLIP-text / BERT-family towers (ResNet, ConvNeXt, NLLB text towers ...)
+# architectures the registry names but which the engine does not run (the message of the refusal)
 UNSUPPORTED_HINT = ("this open_clip architecture is not runnable by the marqo_amd engine yet "
                     "(supported: " + ", ".join(sorted(OPEN_CLIP_ARCHS)) + " and their -quickgelu variants)")
 
 # hf-hub repos the reference registry names (model_registry.py:483-494) -> the open_clip architecture their open_clip_config.json
 # describes (used when that file is not on disk, e.g. with synthetic weights)
-KNOWN_HF_HUB_ARCHS = {"hf-hub:Marqo/marqo-fashionCLIP": "ViT-B-16", "hf-hub:Marqo/marqo-fashionSigLIP": "ViT-B-16-SigLIP"}
+KNOWN_HF_HUB_ARCHS = {"hf-hub:Marqo/marqo-fashionCLIP": "ViT-B-16", "hf-hub:Marqo/marqo-fashionSigLIP": "ViT-B-16-SigLIP",
+                      # (that the two `mrl` repos carry the model_cfg of the two `clip` ones is taken from the reference registry's dimensions:
+                      # an open_clip_config.json on disk always wins — DESIGN.md §3, "NLLB-CLIP")
+                      "hf-hub:visheratin/nllb-clip-base-siglip": "nllb-clip-base-siglip", "hf-hub:visheratin/nllb-siglip-mrl-base": "nllb-clip-base-siglip",
+                      "hf-hub:visheratin/nllb-clip-large-siglip": "nllb-clip-large-siglip",
+                      "hf-hub:visheratin/nllb-siglip-mrl-large": "nllb-clip-large-siglip"}
 
 # ResNet CLIPs (model_registry.py:16-140; open_clip model configs RN50 ... RN50x64): resolved by resolve_resnet_clip only
 _TEXT_RN = {512: ClipTextArch(49408, 77, 512, 12, 8, 2048, 1024), 640: ClipTextArch(49408, 77, 640, 12, 10, 2560, 640),
@@ -387,6 +442,8 @@ def resolve_open_clip(arch_name: str, pretrained: Optional[str] = None) -> Tuple
               "xlmr-large": BertArch(vocab=250002, max_pos=512, width=1024, layers=24, heads=16, mlp_dim=4096, ln_eps=1e-5, pos_offset=2,
                                      type_vocab=1)}[size]
         t = HfClipTextArch(bert=xl, out_dim=int(out_dim))
+    if isinstance(t, NllbTextArch):   # (its activation is the encoder's own ReLU)
+        return replace(v, quick_gelu=quick), t
     return replace(v, quick_gelu=quick), replace(t, quick_gelu=quick)
 
 

@@ -458,8 +458,9 @@ def _insert_open_addressing(home: np.ndarray, n_slots: int) -> np.ndarray:
     return place
 
 
-def build_sentencepiece_table(sp) -> Dict[str, object]:
-    """SentencePieceProcessor (unigram) -> the device tables of csrc/tokenize_algo.h::mq_sp_table:
+def build_sentencepiece_table(sp, bpe: bool = False) -> Dict[str, object]:
+    """SentencePieceProcessor (unigram; bpe = True: a model of type BPE, for mq_tokenize_sentencepiece_bpe) -> the device tables of
+    csrc/tokenize_algo.h::mq_sp_table:
       * hash table over every NORMAL piece AND every proper prefix (at character boundaries) of one, keyed by FNV-1a-64 of the bytes;
       * scores[id];
       * per-code-point normalisation map, read off the model's OWN normaliser: X(c) = Normalize('a' + c + 'b') minus the frame, checked in
@@ -468,8 +469,10 @@ def build_sentencepiece_table(sp) -> Dict[str, object]:
     import unicodedata
     from sentencepiece import sentencepiece_model_pb2 as pb
     m = pb.ModelProto.FromString(sp.serialized_model_proto())
-    if m.trainer_spec.model_type != 1:
-        raise ValueError("device SentencePiece supports unigram models only")
+    if m.trainer_spec.model_type != (2 if bpe else 1):
+        raise ValueError("device SentencePiece: the model is not of the type asked for (unigram = 1, BPE = 2)")
+    if bpe and any(p.type in (4, 5) for p in m.pieces):
+        raise ValueError("device SentencePiece-BPE does not support user-defined / unused pieces")
     if m.trainer_spec.byte_fallback or any(p.type in (4, 6) for p in m.pieces):
         raise ValueError("device SentencePiece does not support byte-fallback / user-defined symbols")
     if m.trainer_spec.treat_whitespace_as_suffix or not m.normalizer_spec.escape_whitespaces:
@@ -478,6 +481,10 @@ def build_sentencepiece_table(sp) -> Dict[str, object]:
     normal = [(i, p.piece.encode("utf-8"), float(p.score)) for i, p in enumerate(m.pieces) if p.type == 1]
     if not normal or max(len(b) for _, b, _ in normal) > 255:
         raise ValueError("vocabulary without pieces / with a piece longer than 255 bytes")
+    if bpe and any("\u2581".encode("utf-8") in b[1:] for _, b, _ in normal):
+        # the device merges word by word, which equals SentencePiece's merge over the whole text only when no merge can cross a U+2581
+        # (true for models trained with the default split_by_whitespace)
+        raise ValueError("device SentencePiece-BPE needs a vocabulary without U+2581 behind a piece's first character")
     scores = np.zeros(len(m.pieces), dtype=np.float32)
     for i, _, sc in normal:
         scores[i] = sc
@@ -580,7 +587,8 @@ def build_sentencepiece_table(sp) -> Dict[str, object]:
 
 
 class DeviceSentencePieceTokenizer(_DeviceTokenizerBase):
-    """SentencePiece unigram on the GPU.  `host` is the host tokeniser of record: an XlmRobertaTokenizer (rows <s> ids + 1 ... </s>, <pad>
+    """SentencePiece on the GPU: unigram, or — host an NllbTokenizer — BPE (rows language code, ids + 1 ... </s>, <pad> padding; merges one thread per
+    whitespace word, mq_tokenize_sentencepiece_bpe; besides the flagged texts, a text with a word longer than the per-thread scratch goes to the host).  `host` is the host tokeniser of record: an XlmRobertaTokenizer (rows <s> ids + 1 ... </s>, <pad>
     padding, <unk> = 3) or a SiglipTokenizer backed by `spiece.model` (canonicalize on the host — three string operations — then rows
     ids ... </s> padded with </s> to the context length).  Texts the kernel flags (composing marks, conjoining jamo, reordering mark
     sequences, code points beyond U+2FFFF) are tokenised by `host` and patched in."""
@@ -588,22 +596,39 @@ class DeviceSentencePieceTokenizer(_DeviceTokenizerBase):
     def __init__(self, host, device: str):
         super().__init__(device)
         self.host = host
-        from marqo_amd.engine.tokenizers import SiglipTokenizer, XlmRobertaTokenizer
-        if isinstance(host, XlmRobertaTokenizer):
+        from marqo_amd.engine.tokenizers import NllbTokenizer, SiglipTokenizer, XlmRobertaTokenizer
+        if isinstance(host, NllbTokenizer):
+            unk = int(host.sp.unk_id())
+            sp, frame = host.sp, dict(prefix_id=host.lang_id, suffix_id=host.sep_id, pad_id=host.pad_id, id_offset=host.FAIRSEQ_OFFSET,
+                                      unk_out=unk + host.FAIRSEQ_OFFSET if unk else host.unk_id)
+            self.kind = "nllb"
+        elif isinstance(host, XlmRobertaTokenizer):
             sp, frame = host.sp, dict(prefix_id=host.cls_id, suffix_id=host.sep_id, pad_id=host.pad_id, id_offset=host.FAIRSEQ_OFFSET, unk_out=host.unk_id)
             self.kind = "xlmr"
         elif isinstance(host, SiglipTokenizer) and host._sp is not None:
             sp, frame = host._sp, dict(prefix_id=-1, suffix_id=host.eos_id, pad_id=host.pad_id, id_offset=0, unk_out=int(host._sp.unk_id()))
             self.kind = "siglip"
         else:
-            raise ValueError("DeviceSentencePieceTokenizer needs an XlmRobertaTokenizer or a sentencepiece-backed SiglipTokenizer")
-        t = build_sentencepiece_table(sp)
+            raise ValueError("DeviceSentencePieceTokenizer needs an XlmRobertaTokenizer, an NllbTokenizer or a sentencepiece-backed SiglipTokenizer")
+        t = build_sentencepiece_table(sp, bpe=self.kind == "nllb")
         self.pad_id = frame["pad_id"]
         self.vocab = L.SentencePieceVocab(
             d_slots=self._up(t["slots"]).data_ptr(), d_pool=self._up(t["pool"]).data_ptr(), d_score=self._up(t["scores"]).data_ptr(),
             d_nmap=self._up(t["nmap"]).data_ptr(), d_npool=self._up(t["npool"]).data_ptr(), d_ccc=self._up(t["ccc"]).data_ptr(),
             n_slots=t["n_slots"], unk_id=t["unk_id"], unk_score=t["unk_score"], add_dummy_prefix=t["add_dummy_prefix"],
             remove_extra_ws=t["remove_extra_ws"], max_piece_bytes=t["max_piece_bytes"], **frame)
+
+    def _launch(self, d_blob, d_off, m: int, total: int, max_length: int, d_ids, d_meta) -> None:
+        """the tokenisation kernels over m staged texts: rows into d_ids [m, max_length], (lengths, status) into d_meta [2, m]"""
+        bpe = self.kind == "nllb"
+        need = int(self.lib.mq_tokenize_workspace_bytes(m, total, max_length) if bpe else
+                   self.lib.mq_tokenize_sentencepiece_workspace_bytes(m, total, max_length))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
+        fn, name = (self.lib.mq_tokenize_sentencepiece_bpe, "mq_tokenize_sentencepiece_bpe") if bpe else \
+                   (self.lib.mq_tokenize_sentencepiece, "mq_tokenize_sentencepiece")
+        L.check(fn(C.byref(self.vocab), d_blob.data_ptr(), d_off.data_ptr(), m, total, max_length, d_ids.data_ptr(), max_length, d_meta[0].data_ptr(),
+                   d_meta[1].data_ptr(), self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), name)
 
     def encode_device(self, texts: Sequence[str], max_length: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (ids int32 [n, max_length] on device, padded with the pad id; lengths int64 [n] on host, specials included)"""
@@ -625,13 +650,7 @@ class DeviceSentencePieceTokenizer(_DeviceTokenizerBase):
                 d_blob, d_off, total = self._stage(sel)
                 d_ids = ids if m == n else torch.empty(m, max_length, dtype=torch.int32, device=self.device)
                 d_meta = torch.empty(2, m, dtype=torch.int32, device=self.device)
-                need = int(self.lib.mq_tokenize_sentencepiece_workspace_bytes(m, total, max_length))
-                if self._ws is None or self._ws.numel() < need:
-                    self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
-                L.check(self.lib.mq_tokenize_sentencepiece(C.byref(self.vocab), d_blob.data_ptr(), d_off.data_ptr(), m, total, max_length,
-                                                           d_ids.data_ptr(), max_length, d_meta[0].data_ptr(), d_meta[1].data_ptr(),
-                                                           self._ws.data_ptr(), self._ws.numel(),
-                                                           torch.cuda.current_stream(self.device).cuda_stream), "mq_tokenize_sentencepiece")
+                self._launch(d_blob, d_off, m, total, max_length, d_ids, d_meta)
                 meta = d_meta.cpu().numpy()
             if meta[1].any():
                 dev_set.difference_update(on_dev[j] for j in np.nonzero(meta[1])[0].tolist())
@@ -642,7 +661,7 @@ class DeviceSentencePieceTokenizer(_DeviceTokenizerBase):
         if rest:
             block = np.full((len(rest), max_length), self.pad_id, dtype=np.int32)
             for j, i in enumerate(rest):
-                if self.kind == "xlmr":
+                if self.kind in ("xlmr", "nllb"):
                     e = self.host.encode(texts[i], max_length)
                 else:  # (already canonicalised above)
                     e = (list(self.host._sp.encode(texts[i]))[: max_length - 1]) + [self.host.eos_id]

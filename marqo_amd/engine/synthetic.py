@@ -11,7 +11,7 @@ from typing import Dict
 
 import torch
 
-from marqo_amd.engine.archs import BertArch, ClipTextArch, ConvNextArch, ResNetArch, VitArch
+from marqo_amd.engine.archs import BertArch, ClipTextArch, ConvNextArch, NllbTextArch, ResNetArch, VitArch
 
 Tensor = torch.Tensor
 
@@ -187,7 +187,10 @@ def random_open_clip_state_dict(vision: VitArch = None, text: ClipTextArch = Non
         else:
             _ln(sd, "visual.ln_post", W, g)
             sd["visual.proj"] = torch.randn(W, vision.out_dim, generator=g) / math.sqrt(W)
-    if text is not None and hasattr(text, "bert"):
+    if isinstance(text, NllbTextArch):
+        sd.update(random_nllb_text_state_dict(text, seed=seed + 1))
+        sd["logit_scale"], sd["logit_bias"] = torch.tensor(math.log(10.0)), torch.tensor(-10.0)
+    elif text is not None and hasattr(text, "bert"):
         # open_clip HFTextEncoder (CustomTextCLIP): HF-named encoder under text.transformer.*, projection MLP under text.proj.{0,2}
         for k, v in random_bert_state_dict(text.bert, seed=seed + 1).items():
             sd["text.transformer." + k] = v
@@ -210,6 +213,26 @@ def random_open_clip_state_dict(vision: VitArch = None, text: ClipTextArch = Non
         else:
             sd[px + "text_projection"] = torch.randn(W, text.out_dim, generator=g) / math.sqrt(W)
         sd["logit_scale"] = torch.tensor(math.log(1 / 0.07))
+    return sd
+
+
+def random_nllb_text_state_dict(arch: NllbTextArch, seed: int = 0) -> Dict[str, Tensor]:
+    """open_clip HFTextEncoder over a transformers M2M100Encoder (the NLLB-CLIP text tower): `text.transformer.*` + `text.proj.weight`.  The token
+    table is small (M2M100 multiplies it by sqrt(width) = 32) so that the sinusoidal positions, of unit scale, stay visible in the sum."""
+    g = torch.Generator().manual_seed(seed)
+    W, F, t = arch.width, arch.mlp_dim, "text.transformer."
+    std = 0.6 / math.sqrt(W)
+    sd: Dict[str, Tensor] = {t + "embed_tokens.weight": (1.0 / math.sqrt(W)) * torch.randn(arch.vocab, W, generator=g)}
+    for i in range(arch.layers):
+        p = f"{t}layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            _lin(sd, p + "self_attn." + n, W, W, g, std)
+        _ln(sd, p + "self_attn_layer_norm", W, g)
+        _lin(sd, p + "fc1", F, W, g, std)
+        _lin(sd, p + "fc2", W, F, g, 0.6 / math.sqrt(F))
+        _ln(sd, p + "final_layer_norm", W, g)
+    _ln(sd, t + "layer_norm", W, g)
+    sd["text.proj.weight"] = torch.randn(arch.out_dim, W, generator=g) / math.sqrt(W)
     return sd
 
 

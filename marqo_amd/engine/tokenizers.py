@@ -434,6 +434,61 @@ class XlmRobertaTokenizer:
 
 
 # ---------------------------------------------------------------------------------------------------
+# NLLB SentencePiece-BPE (the NLLB-CLIP text towers)
+# ---------------------------------------------------------------------------------------------------
+class NllbTokenizer:
+    """transformers' NllbTokenizer (non-legacy behaviour, no `src_lang` given: eng_Latn) over the checkpoint's `sentencepiece.bpe.model` — a
+    SentencePiece model of type BPE, encoded by the `sentencepiece` wheel — as open_clip's HFTokenizer calls it: rows
+    [language code] pieces... </s>, truncated to max_length with the language code and </s> kept, padded with <pad>.  fairseq id layout as for
+    XLM-RoBERTa: <s> 0, <pad> 1, </s> 2, <unk> 3, every SentencePiece id shifted by one (SentencePiece id 0 maps to <unk> = 3).  The language code's
+    id is read from the checkpoint's tokenizer files (`tokenizer.json` added tokens, else `added_tokens.json`) by its string."""
+    FAIRSEQ_OFFSET = 1
+
+    def __init__(self, path: str, src_lang: str = "eng_Latn"):
+        import json
+        import sentencepiece as spm
+        d = path if os.path.isdir(path) else os.path.dirname(path)
+        model_file = path if os.path.isfile(path) and path.endswith(".model") else os.path.join(d, "sentencepiece.bpe.model")
+        self.sp = spm.SentencePieceProcessor(model_file=model_file)
+        self.cls_id, self.pad_id, self.sep_id, self.unk_id = 0, 1, 2, 3
+        self.src_lang = src_lang
+        self.lang_id: Optional[int] = None
+        tj, aj = os.path.join(d, "tokenizer.json"), os.path.join(d, "added_tokens.json")
+        if os.path.isfile(tj):
+            with open(tj, encoding="utf-8") as f:
+                for tok in json.load(f).get("added_tokens", []):
+                    if tok.get("content") == src_lang:
+                        self.lang_id = int(tok["id"])
+        if self.lang_id is None and os.path.isfile(aj):
+            with open(aj, encoding="utf-8") as f:
+                self.lang_id = json.load(f).get(src_lang)
+        if self.lang_id is None:
+            raise FileNotFoundError(f"the id of the language code {src_lang!r} was not found in tokenizer.json / added_tokens.json under {d}")
+        self.vocab_size = max(len(self.sp) + self.FAIRSEQ_OFFSET, self.lang_id + 1)
+
+    def piece_ids(self, text: str) -> List[int]:
+        return [i + self.FAIRSEQ_OFFSET if i else self.unk_id for i in self.sp.encode(text)]
+
+    def encode(self, text: str, max_length: Optional[int] = None) -> List[int]:
+        ids = self.piece_ids(text)
+        if max_length is not None and len(ids) > max_length - 2:
+            ids = ids[:max(max_length - 2, 0)]
+        return [self.lang_id] + ids + [self.sep_id]
+
+    def __call__(self, texts: Union[str, Sequence[str]], max_length: Optional[int] = None) -> Dict[str, np.ndarray]:
+        if isinstance(texts, str):
+            texts = [texts]
+        enc = [self.encode(t, max_length) for t in texts]
+        S = max((len(e) for e in enc), default=0)
+        ids = np.full((len(enc), S), self.pad_id, dtype=np.int64)
+        mask = np.zeros((len(enc), S), dtype=np.int64)
+        for i, e in enumerate(enc):
+            ids[i, :len(e)] = e
+            mask[i, :len(e)] = 1
+        return {"input_ids": ids, "attention_mask": mask}
+
+
+# ---------------------------------------------------------------------------------------------------
 # stand-in for random-init models (no vocabulary exists for them)
 # ---------------------------------------------------------------------------------------------------
 def canonicalize_text(text: str) -> str:

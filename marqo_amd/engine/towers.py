@@ -13,6 +13,7 @@ once, so nothing is ever re-uploaded):
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -1078,13 +1079,14 @@ class _TextTowerBase(_TowerBase):
     _queues: Optional[Dict[bool, tuple]] = None
     _queues_off = False
     _active = 0                       # request-thread calls of the small-call path in flight on this tower
+    pool_first = False                # CLIP-form towers whose pooled row is each sequence's FIRST (NLLB: the language-code token), not its last
     _active_lock = threading.Lock()   # (class-wide: two increments)
 
     def _queue(self, normalize: bool, clip: bool) -> Optional["NQ.TextQueue"]:
         """this tower's queue for `normalize` (created at first use, re-created when the tower's policy fields have changed since: its scratch is
         sized from them), or None — switched off, or it could not be created (logged once; the direct path stays)"""
-        if not NQ.ENABLED or self._queues_off or (self._fp8 is not None and not self._fp8.calibrated):
-            return None
+        if not NQ.ENABLED or self._queues_off or self.pool_first or (self._fp8 is not None and not self._fp8.calibrated):
+            return None                   # (the native queue pools a CLIP-form tower's LAST rows)
         sig = bytes(self.cfg)
         ent = (self._queues or {}).get(bool(normalize))
         if ent is not None and ent[0] == sig:
@@ -1185,7 +1187,7 @@ class _TextTowerBase(_TowerBase):
                 keep, d_pool = [], None
                 if clip:
                     ws = torch.empty(self.lib.mq_clip_text_workspace_bytes(C.byref(self.cfg), n_tok, 1) + 256, dtype=torch.uint8, device=self.device)
-                    d_pool = torch.tensor([n_tok - 1], dtype=torch.int32).to(self.device)   # the pooled row (last = EOT) is known at capture
+                    d_pool = torch.tensor([0 if self.pool_first else n_tok - 1], dtype=torch.int32).to(self.device)   # the pooled row (last = EOT; NLLB: first) is known at capture
                     keep.append(d_pool)
                 else:
                     ws = torch.empty(self.lib.mq_bert_workspace_bytes(C.byref(self.cfg), n_tok, 1) + 256, dtype=torch.uint8, device=self.device)
@@ -1222,7 +1224,7 @@ class _TextTowerBase(_TowerBase):
                 d_packed = torch.empty(rows, dtype=torch.int32, device=self.device)
                 L.check(self.lib.mq_pack_ids(d_ids[a:b].data_ptr(), S, d_cu.data_ptr(), nseq, d_packed.data_ptr(), self._stream()), "mq_pack_ids")
                 need = (self.lib.mq_clip_text_workspace_bytes if clip else self.lib.mq_bert_workspace_bytes)(C.byref(self.cfg), rows, nseq)
-                self._call_text(clip, d_packed, d_cu, cu, nseq, None, out[a:b], normalize, self._workspace(need))
+                self._call_text(clip, d_packed, d_cu, cu, nseq, d_cu if self.pool_first else None, out[a:b], normalize, self._workspace(need))   # (cu[s] = first row of s)
         return out
 
 
@@ -1378,6 +1380,116 @@ class ClipTextTower(_TextTowerBase):
         if self.arch.cls_embed:   # the class id is appended on the host (a [n, S] id matrix: KBs)
             ids_h = _host_i64(d_ids)
             return self.encode_ids(torch.from_numpy(np.where(np.arange(ids_h.shape[1])[None] < _host_i64(lengths)[:, None], ids_h, 0)), normalize=normalize)
+        return self._encode_device(d_ids, lengths, self.arch.ctx, normalize, clip=True)
+
+
+def nllb_clip_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """The load-time transforms of the NLLB-CLIP text tower: open_clip HFTextEncoder / transformers M2M100Encoder tensors (`text.transformer.*`,
+    `text.proj.weight`) -> the CLIP text tower's own names (fp32), so that everything but the ReLU runs on what exists:
+      * token_embedding  = embed_tokens * sqrt(width)   (M2M100's embed_scale; row pad_id is never gathered: only un-padded rows run)
+      * positional_embedding [ctx, width] = the sinusoidal table from position pos_offset on (arch.position_table(): a non-persistent buffer)
+      * resblocks.N: q_proj | k_proj | v_proj packed into attn.in_proj_{weight, bias}; self_attn_layer_norm -> ln_1, final_layer_norm -> ln_2,
+        fc1 / fc2 -> mlp.c_fc / mlp.c_proj; the encoder's layer_norm -> ln_final; text_projection [width, out_dim] = proj.weight^T (no bias)."""
+    W, F = arch.width, arch.mlp_dim
+    t = "text.transformer."
+    f32 = lambda key, shape: _need(sd, key, shape).detach().to(torch.float32)
+    out = {"token_embedding.weight": f32(t + "embed_tokens.weight", (arch.vocab, W)) * math.sqrt(W),
+           "positional_embedding": arch.position_table(),
+           "ln_final.weight": f32(t + "layer_norm.weight", (W,)), "ln_final.bias": f32(t + "layer_norm.bias", (W,)),
+           "text_projection": f32("text.proj.weight", (arch.out_dim, W)).t().contiguous()}
+    for i in range(arch.layers):
+        p, o = f"{t}layers.{i}.", f"transformer.resblocks.{i}."
+        out[o + "attn.in_proj_weight"] = torch.cat([f32(p + f"self_attn.{n}_proj.weight", (W, W)) for n in "qkv"], dim=0)
+        out[o + "attn.in_proj_bias"] = torch.cat([f32(p + f"self_attn.{n}_proj.bias", (W,)) for n in "qkv"], dim=0)
+        for src, dst, shape in (("self_attn.out_proj", "attn.out_proj", (W, W)), ("fc1", "mlp.c_fc", (F, W)), ("fc2", "mlp.c_proj", (W, F))):
+            out[o + dst + ".weight"] = f32(p + src + ".weight", shape)
+            out[o + dst + ".bias"] = f32(p + src + ".bias", shape[:1])
+        for src, dst in (("self_attn_layer_norm", "ln_1"), ("final_layer_norm", "ln_2")):
+            out[o + dst + ".weight"], out[o + dst + ".bias"] = f32(p + src + ".weight", (W,)), f32(p + src + ".bias", (W,))
+    return out
+
+
+class NllbTextTower(_TextTowerBase):
+    """NLLB-CLIP text tower (open_clip HFTextEncoder over the NLLB-200 / M2M100 encoder, `cls_pooler`, `linear` projection): the pre-LN bf16
+    encoder with MQ_ACT_RELU behind mq_encode_clip_text — scaled token table, sinusoidal positions as the position table, no mask over the packed
+    (un-padded) rows, pooled row = each sequence's first.  bf16 operands only."""
+    pool_first = True
+
+    def __init__(self, arch, sd: Dict[str, Tensor], device: str, precision: str = "bf16"):
+        super().__init__(device)
+        if precision != "bf16":
+            raise ValueError(f"the NLLB text tower runs on bf16 operands only (its ReLU blocks have no e4m3 kernels), got precision {precision!r}")
+        if arch.width != arch.heads * 64:
+            raise ValueError("the NLLB text tower runs 64-wide attention heads")
+        self.precision = precision
+        self.arch = arch
+        self.pools_one_row = True
+        W = arch.width
+        h = self._h
+        csd = nllb_clip_state_dict(arch, sd)
+        self._blocks = _clip_blocks(h, csd, "transformer.", arch.layers, W, arch.mlp_dim, arch.heads)
+        self.w = L.ClipTextWeights(tok_emb=h.f32(csd["token_embedding.weight"]), pos=h.f32(csd["positional_embedding"]), blocks=self._blocks,
+                                   ln_final_g=h.f32(csd["ln_final.weight"]), ln_final_b=h.f32(csd["ln_final.bias"]),
+                                   proj_w=h.bf16(csd["text_projection"].t()), proj_b=None)
+        enc = _encoder_cfg(W, arch.layers, arch.heads, arch.mlp_dim, False, False, L.MQ_MASK_NONE, arch.ln_eps)
+        enc.act = L.MQ_ACT_RELU
+        self.cfg = L.ClipTextCfg(enc=enc, vocab=arch.vocab, ctx=arch.ctx, out_dim=arch.out_dim, cls_pos=0)
+        self.cfg.enc.residual_stream = 2
+        self.tune_residual_default()
+
+    def tune_residual_default(self) -> str:
+        ids = self.calibration_ids()
+        return self.tune_residual_stream(lambda: self.encode_ids(ids))
+
+    def calibration_ids(self, n: int = 32, seed: int = 0) -> Tensor:
+        """fixed, seeded calibration rows of the residual-stream policy: int64 [n, ctx] = language-code id, random ids, </s>, <pad> padding, with
+        lengths spread over 3 .. ctx"""
+        a = self.arch
+        g = torch.Generator().manual_seed(2000 + seed)
+        ids = torch.full((n, a.ctx), a.pad_id, dtype=torch.int64)
+        for i in range(n):
+            L_ = 3 + (i * (a.ctx - 3)) // max(n - 1, 1)
+            ids[i, :L_] = torch.randint(4, a.vocab, (L_,), generator=g)
+            ids[i, 0], ids[i, L_ - 1] = a.vocab - 1, 2
+        return ids
+
+    def _lengths(self, ids_h: np.ndarray) -> np.ndarray:
+        """right-padded rows -> token counts (attention_mask = ids != pad_id, as open_clip's HFTextEncoder builds it)"""
+        keep = ids_h != self.arch.pad_id
+        lengths = keep.sum(axis=1)
+        if lengths.size and (int(lengths.min()) < 1 or bool((keep != (np.arange(ids_h.shape[1])[None, :] < lengths[:, None])).any())):
+            raise ValueError("the NLLB text tower takes right-padded rows of at least one token (no pad id inside a text)")
+        return lengths.astype(np.int64)
+
+    def encode_ids(self, ids: Tensor, normalize: bool = True) -> Tensor:
+        """ids: int [n, <= ctx] rows `lang pieces... </s>` right-padded with pad_id, host or device.  Only the un-padded rows run (the key-padding mask
+        of the reference keeps padded keys out of every real row, and the pooled row is a real one)."""
+        if ids.ndim != 2 or ids.shape[1] > self.arch.ctx:
+            raise ValueError(f"expected ids [n, <= {self.arch.ctx}], got {tuple(ids.shape)}")
+        ids_h = _host_i64(ids)
+        n = ids_h.shape[0]
+        lengths = self._lengths(ids_h)
+        if n == 1 and self._graphs_ok():
+            one = self._encode_one(torch.from_numpy(ids_h[0, :int(lengths[0])]), normalize, clip=True)
+            if one is not None:
+                return one
+        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
+            for a, b in self._chunks(lengths):
+                packed, cu = _pack(ids_h[a:b], lengths[a:b])
+                d_ids, d_cu = self._to_device(packed), self._to_device(cu)
+                rows, nseq = packed.numel(), b - a
+                need = self.lib.mq_clip_text_workspace_bytes(C.byref(self.cfg), rows, nseq)
+                self._call_text(True, d_ids, d_cu, cu, nseq, d_cu, out[a:b], normalize, self._workspace(need))   # pooled rows = cu[s]: each sequence's first
+        return out
+
+    encode_padded = encode_ids   # (the loaders' name for "rows padded to ctx", as on HfClipTextTower)
+
+    def queue_rows_ids(self, ids_h: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
+        return None   # (the native queue pools last rows: this tower keeps the regular path and its captured single-query graphs)
+
+    def encode_device(self, d_ids: Tensor, lengths: Tensor, normalize: bool = True) -> Tensor:
+        """ids already on the device (engine/gpu_tokenizers.py): int32 [n, S] right-padded rows, lengths int64 [n] on the host"""
         return self._encode_device(d_ids, lengths, self.arch.ctx, normalize, clip=True)
 
 

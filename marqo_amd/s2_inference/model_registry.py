@@ -120,7 +120,9 @@ def _get_open_clip_properties() -> Dict:
             out[name] = {"name": name, "dimensions": vision.out_dim, "note": f"open_clip {arch_name} ({tag})",
                          "type": "open_clip", "pretrained": tag}
     for hub_name, arch_name in archs.KNOWN_HF_HUB_ARCHS.items():  # Marqo's fashion models (model_registry.py:483-494)
-        vision, _ = archs.resolve_open_clip(arch_name)
+        vision, text = archs.resolve_open_clip(arch_name)
+        if isinstance(text, archs.NllbTextArch):   # NLLB-CLIP: reached through model_properties with the hf-hub name, no short registry key
+            continue
         out[hub_name[len("hf-hub:"):]] = {"name": hub_name, "dimensions": vision.out_dim, "note": f"{hub_name} ({arch_name})", "type": "open_clip"}
     return out
 

@@ -25,7 +25,7 @@ from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint, synthetic
 from marqo_amd.engine.gpu_tokenizers import prefers_host
 from marqo_amd.engine.towers import request_stream
-from marqo_amd.engine.tokenizers import (ClipBpeTokenizer, RobertaBpeTokenizer, SiglipTokenizer, SyntheticTokenizer, WordPieceTokenizer,
+from marqo_amd.engine.tokenizers import (ClipBpeTokenizer, NllbTokenizer, RobertaBpeTokenizer, SiglipTokenizer, SyntheticTokenizer, WordPieceTokenizer,
                                           XlmRobertaTokenizer, _clean_text)
 from marqo_amd.s2_inference.abstract_models import AbstractCLIPModel
 from marqo_amd.s2_inference.errors import InvalidModelPropertiesError, ModelLoadError
@@ -205,6 +205,17 @@ class OPEN_CLIP(AbstractCLIPModel):
             if str(v.get("timm_model_name", "")) in _TIMM_CONVNEXT and "hf_model_name" not in t:
                 return self._convnext_from_config(arch_name, mc)
             m = _TIMM_SIGLIP.match(str(v.get("timm_model_name", "")))
+            if m and t.get("hf_model_name") in archs.NLLB_TEXT_ARCHS:
+                # NLLB-CLIP: the SigLIP image trunk + open_clip's HFTextEncoder over the NLLB-200 encoder (cls_pooler, linear projection)
+                if v.get("timm_pool", "map") != "map" or v.get("timm_proj", "none") not in ("none", None, ""):
+                    raise InvalidModelPropertiesError(f"{arch_name}: timm towers are supported with pool 'map' and no projection only")
+                if t.get("hf_pooler_type", "cls_pooler") != "cls_pooler" or t.get("hf_proj_type", t.get("proj_type", "linear")) != "linear":
+                    raise InvalidModelPropertiesError(f"{arch_name}: the NLLB text tower is supported with hf_pooler_type 'cls_pooler' and hf_proj_type 'linear' only")
+                vision, _ = archs._siglip(int(v.get("image_size", m.group(2))), large=m.group(1) == "large", so400m=m.group(1) == "so400m")
+                if mc["embed_dim"] != vision.width:
+                    raise InvalidModelPropertiesError(f"{arch_name}: unexpected embed_dim {mc['embed_dim']} for a {vision.width}-wide SigLIP trunk without projection")
+                from dataclasses import replace
+                return vision, replace(archs.NLLB_TEXT_ARCHS[t["hf_model_name"]], out_dim=int(mc["embed_dim"]), ctx=int(t.get("context_length", 77)))
             if m and "hf_model_name" not in t:
                 # SigLIP: timm trunk + TextTransformer(no_causal_mask, pool 'last', proj_bias) — marqo-fashionSigLIP, marqo-ecommerce-*
                 if v.get("timm_pool", "map") != "map" or v.get("timm_proj", "none") not in ("none", None, ""):
@@ -230,6 +241,23 @@ class OPEN_CLIP(AbstractCLIPModel):
             return archs.resolve_open_clip(arch_name, tag)
         except KeyError as e:
             raise InvalidModelPropertiesError(str(e)) from e
+
+    @staticmethod
+    def _preprocess_cfg_on_disk(ckpt_dir: Optional[str]):
+        """`preprocess_cfg` of the open_clip_config.json next to the checkpoint -> (mean, std, resize_mode, interpolation), fields it does not name from
+        open_clip's defaults (OpenAI statistics, bicubic, shortest-side resize + centre crop); None without the file (the caller's own choice holds)"""
+        path = os.path.join(ckpt_dir or "", "open_clip_config.json")
+        if not os.path.isfile(path):
+            return None
+        with open(path) as f:
+            pc = json.load(f).get("preprocess_cfg") or {}
+        three = lambda v: tuple(float(x) for x in v) if isinstance(v, (list, tuple)) else (float(v),) * 3
+        mean, std = three(pc.get("mean", archs.OPENAI_DATASET_MEAN)), three(pc.get("std", archs.OPENAI_DATASET_STD))
+        interpolation, resize_mode = str(pc.get("interpolation", "bicubic")), str(pc.get("resize_mode", "shortest"))
+        if len(mean) != 3 or len(std) != 3 or resize_mode not in ("squash", "shortest") or interpolation not in ("bicubic", "bilinear") or \
+                (resize_mode == "shortest" and interpolation != "bicubic"):
+            raise InvalidModelPropertiesError(f"{path}: unsupported preprocess_cfg {pc} (resize_mode squash with bicubic / bilinear, or shortest with bicubic)")
+        return mean, std, resize_mode, interpolation
 
     @staticmethod
     def _convnext_from_config(arch_name: str, mc: dict):
@@ -262,6 +290,8 @@ class OPEN_CLIP(AbstractCLIPModel):
         ckpt = checkpoint.find_open_clip_checkpoint(props.name, props.localpath)
         ckpt_dir = os.path.dirname(ckpt) if ckpt and os.path.isfile(ckpt) else ckpt
         self.vision_arch, self.text_arch = self._resolve_archs(arch_name, tag, ckpt_dir)
+        if isinstance(self.text_arch, archs.NllbTextArch) and props.engine_precision == "fp8":
+            raise InvalidModelPropertiesError(f"{arch_name}: the NLLB text tower runs on bf16 operands only ('enginePrecision': 'fp8' is not supported)")
         if props.size is not None and props.size != self.vision_arch.image_size:
             raise InvalidModelPropertiesError(f"'size'={props.size} does not match the architecture's image size {self.vision_arch.image_size}")
         if self.vision_arch.out_dim != props.dimensions:
@@ -275,11 +305,19 @@ class OPEN_CLIP(AbstractCLIPModel):
         else:
             raise ModelLoadError(f"no checkpoint for {props.name} under {checkpoint.model_dir()} (and no 'localpath'). There is no "
                                  f"network download in the marqo_amd engine; set MARQO_AMD_SYNTHETIC_WEIGHTS=1 for random-init weights.")
+        if isinstance(self.text_arch, archs.NllbTextArch) and "text.transformer.embed_tokens.weight" in sd:
+            from dataclasses import replace    # (the checkpoint's own vocabulary size: 256206 for NLLB-200)
+            self.text_arch = replace(self.text_arch, vocab=int(sd["text.transformer.embed_tokens.weight"].shape[0]))
         # preprocessing: a custom checkpoint follows 'image_preprocessor' (open_clip_model.py:87-104); registry and hf-hub names
         # get open_clip's own transform for that model (create_model_and_transforms, :183-205) — the SigLIP pipeline for SigLIP towers
         custom = props.localpath is not None
         kind = props.image_preprocessor if custom else (self.vision_arch.preprocessor or ("SigLIP" if self.vision_arch.pool == "map" else "OpenCLIP"))
         mean, std, self._resize_mode, self._interpolation = _PREPROCESSOR_NORMS[kind]
+        if isinstance(self.text_arch, archs.NllbTextArch) and not custom:
+            # NLLB-CLIP: the file on disk decides — open_clip builds the transform from the repo's preprocess_cfg, its own defaults for what is missing
+            file_cfg = self._preprocess_cfg_on_disk(ckpt_dir)
+            if file_cfg is not None:
+                mean, std, self._resize_mode, self._interpolation = file_cfg
         self._mean = tuple(props.mean) if props.mean is not None else mean
         self._std = tuple(props.std) if props.std is not None else std
         self.preprocess_config = {"size": self.vision_arch.image_size, "mean": self._mean, "std": self._std,
@@ -316,7 +354,7 @@ class OPEN_CLIP(AbstractCLIPModel):
         elif isinstance(self.tokenizer, WordPieceTokenizer) and os.environ.get("MARQO_AMD_HOST_TOKENIZER", "0") != "1":
             from marqo_amd.engine.gpu_tokenizers import DeviceWordPieceTokenizer
             self._device_tokenizer = DeviceWordPieceTokenizer(self.tokenizer, self.device)
-        elif isinstance(self.tokenizer, HfClipTokenizer) and isinstance(self.tokenizer.hf, XlmRobertaTokenizer) and \
+        elif isinstance(self.tokenizer, HfClipTokenizer) and isinstance(self.tokenizer.hf, (XlmRobertaTokenizer, NllbTokenizer)) and \
                 os.environ.get("MARQO_AMD_HOST_TOKENIZER", "0") != "1":
             from marqo_amd.engine.gpu_tokenizers import DeviceSentencePieceTokenizer
             try:
@@ -336,6 +374,8 @@ class OPEN_CLIP(AbstractCLIPModel):
         from marqo_amd.engine import towers
         if isinstance(self.text_arch, archs.HfClipTextArch):   # open_clip HFTextEncoder: XLM-RoBERTa encoder + mean pooler + projection MLP
             return towers.HfClipTextTower(self.text_arch, sd, self.device, precision=precision)
+        if isinstance(self.text_arch, archs.NllbTextArch):     # open_clip HFTextEncoder: NLLB-200 encoder + cls pooler + linear projection
+            return towers.NllbTextTower(self.text_arch, sd, self.device, precision=precision)
         return towers.ClipTextTower(self.text_arch, sd, self.device, precision=precision)
 
     def _load_tokenizer(self, ckpt_dir: Optional[str]):
@@ -363,6 +403,19 @@ class OPEN_CLIP(AbstractCLIPModel):
                     out[out == wp.sep_id] = 0
                 return out
             return hf_tok
+        if isinstance(self.text_arch, archs.NllbTextArch):
+            # open_clip HFTokenizer over the checkpoint's NllbTokenizer: sentencepiece.bpe.model (+ tokenizer.json for the language code's id) next to
+            # the checkpoint, in the repo's directory under the model dir, or in the NLLB-200 repo on disk
+            repo = props.name[len(HF_HUB_PREFIX):] if props.name.startswith(HF_HUB_PREFIX) else props.name
+            hf = self.text_arch.hf_model_name
+            for d in filter(None, (ckpt_dir, os.path.join(checkpoint.model_dir(), "hf-hub", *repo.split("/")), checkpoint.find_hf_dir(hf),
+                                   os.path.join(checkpoint.model_dir(), "hf", *hf.split("/")))):
+                if os.path.isfile(os.path.join(d, "sentencepiece.bpe.model")):
+                    return HfClipTokenizer(NllbTokenizer(d, src_lang=self.text_arch.src_lang), self.text_arch.ctx)
+            if self.weights_source and str(self.weights_source).startswith("synthetic"):
+                return HfClipTokenizer(SyntheticTokenizer("xlmr", self.text_arch.vocab), self.text_arch.ctx)
+            raise ModelLoadError(f"the NLLB tokenizer (sentencepiece.bpe.model + tokenizer.json) was not found next to the checkpoint or under "
+                                 f"{os.path.join(checkpoint.model_dir(), 'hf-hub', *repo.split('/'))}")
         if isinstance(self.text_arch, archs.HfClipTextArch):
             # open_clip HFTokenizer(hf_tokenizer_name = xlm-roberta-base / -large): the SentencePiece model next to the checkpoint, or the HF
             # repo of that name on disk
@@ -666,7 +719,8 @@ class OPEN_CLIP(AbstractCLIPModel):
         the merging of concurrent calls to it instead of the Python coalescer.  Host-tokenised small calls only — ids from the device tokeniser
         stay in HBM and take the direct path."""
         from marqo_amd.engine import native_queue as NQ
-        if not NQ.ENABLED or self.model is None or getattr(self, "text", None) is None or not hasattr(self.text, "_small_call"):
+        if not NQ.ENABLED or self.model is None or getattr(self, "text", None) is None or not hasattr(self.text, "_small_call") or \
+                getattr(self.text, "pool_first", False):   # (the NLLB tower pools first rows: not a native-queue tower)
             return False
         texts = [texts] if isinstance(texts, str) else texts
         if not (1 <= len(texts) <= NQ.MAX_SEQS) or not all(isinstance(t, str) for t in texts):
@@ -685,7 +739,7 @@ class OPEN_CLIP(AbstractCLIPModel):
             if rows is not None:
                 return rows
         with request_stream(self.device, device_output=return_device):
-            if isinstance(self.text_arch, archs.HfClipTextArch):
+            if isinstance(self.text_arch, (archs.HfClipTextArch, archs.NllbTextArch)):
                 texts = [_clean_text(t) for t in ([sentence] if isinstance(sentence, str) else list(sentence))]
                 if getattr(self, "_device_tokenizer", None) is not None and not prefers_host(texts):
                     d_ids, lens = self._device_tokenizer.encode_device(texts, self.text_arch.ctx)
