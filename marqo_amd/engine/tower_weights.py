@@ -1,0 +1,394 @@
+"""Checkpoint tensors -> the tensors the kernels read: every load-time transform of the towers (engine/towers.py) that needs no device.
+
+Head and MLP padding, LayerNorm / BatchNorm / layer-scale folding, key renaming and the per-block hand-over to a `_Holder` (which may sit on
+the CPU: tests/test_tower_weights_host.py runs the block loaders there).  The order in which tensors reach the holder is the allocation
+order of a tower's weights on the device."""
+from __future__ import annotations
+
+import math
+import os
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from marqo_amd import _lib as L
+
+Tensor = torch.Tensor
+
+
+class _Holder:
+    """Keeps device tensors alive and hands out raw pointers."""
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.tensors: List[Tensor] = []
+
+    def f32(self, t: Tensor) -> int:
+        d = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.tensors.append(d)
+        return d.data_ptr()
+
+    def bf16(self, t: Tensor) -> int:
+        d = t.detach().to(dtype=torch.float32).to(device=self.device).to(torch.bfloat16).contiguous()
+        self.tensors.append(d)
+        return d.data_ptr()
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors)
+
+    def drop(self, ptr: int) -> int:
+        """forget the tensor that starts at `ptr` (its HBM goes back to the allocator once nothing else holds it) -> bytes released"""
+        for i, t in enumerate(self.tensors):
+            if t.data_ptr() == ptr:
+                del self.tensors[i]
+                return t.numel() * t.element_size()
+        return 0
+
+
+def _need(sd: Dict[str, Tensor], key: str, shape: Optional[Tuple[int, ...]] = None) -> Tensor:
+    if key not in sd:
+        raise KeyError(f"checkpoint is missing tensor '{key}'")
+    t = sd[key]
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"checkpoint tensor '{key}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def _head_dim(width: int, heads: int) -> int:
+    """model head dim; the attention kernel runs 64- / 96- / 112- / 128-wide heads, anything else is zero-padded at load (_pad_heads)"""
+    if heads < 1 or width % heads:
+        raise ValueError(f"width {width} is not divisible by heads {heads}")
+    d = width // heads
+    if d > 128:
+        raise ValueError(f"attention head dim must be <= 128 for the gfx950 attention kernel (width={width}, heads={heads}: {d})")
+    return d
+
+
+KERNEL_HEAD_DIMS = (64, 96, 112, 128)  # head strides csrc/attention.hip is instantiated for
+
+
+def _kernel_head_dim(d: int, heads: int = 2) -> int:
+    """head width the kernel runs for a model head dim d: the smallest instantiated stride >= d whose attention width heads * hp
+    keeps the GEMM's K a multiple of 64: 32 / 16 -> 64 (e5-small, MiniLM), 80 / 88 -> 96 (ViT-H / g), 104 -> 112 (ViT-bigG)"""
+    for hp in KERNEL_HEAD_DIMS:
+        if hp >= d and (heads * hp) % 64 == 0:
+            return hp
+    return 128
+
+
+def _pad_heads(qkv_w: Tensor, qkv_b: Tensor, out_w: Tensor, heads: int, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """[3W, W] / [3W] / [W, W] with d-wide heads -> [3*heads*hp, W] / [3*heads*hp] / [W, heads*hp] (hp = _kernel_head_dim): each
+    head's Q / K / V rows and out-projection columns are zero-padded to hp (zero key / query dims add nothing to q.k, zero value
+    dims meet zero out-proj columns), and Q is scaled by sqrt(hp / d) so that the kernel's 1/sqrt(hp) softmax scale equals the
+    model's 1/sqrt(d)."""
+    W = out_w.shape[0]
+    hp = _kernel_head_dim(d, heads)
+    q, k, v = qkv_w.float().view(3, heads, d, W).unbind(0)
+    qb, kb, vb = qkv_b.float().view(3, heads, d).unbind(0)
+    sc = (float(hp) / d) ** 0.5
+    pad_w = lambda t: torch.nn.functional.pad(t, (0, 0, 0, hp - d)).reshape(heads * hp, W)
+    pad_b = lambda t: torch.nn.functional.pad(t, (0, hp - d)).reshape(heads * hp)
+    qkv_w2 = torch.cat([pad_w(q * sc), pad_w(k), pad_w(v)], 0)
+    qkv_b2 = torch.cat([pad_b(qb * sc), pad_b(kb), pad_b(vb)], 0)
+    out_w2 = torch.nn.functional.pad(out_w.float().view(W, heads, d), (0, hp - d)).reshape(W, heads * hp)
+    return qkv_w2, qkv_b2, out_w2
+
+
+def _ceil64(v: int) -> int:
+    return (v + 63) // 64 * 64
+
+
+def _pad_mlp(fc1_w: Tensor, fc1_b: Tensor, fc2_w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """MLP hidden sizes that are not a multiple of 64 (ViT-SO400M: 4304) are zero-padded: the extra hidden units are act(0 + 0) = 0
+    for GELU / QuickGELU and meet zero fc2 columns — exact."""
+    F = fc1_w.shape[0]
+    Fp = _ceil64(F)
+    if Fp == F:
+        return fc1_w, fc1_b, fc2_w
+    pad = torch.nn.functional.pad
+    return pad(fc1_w.detach().float(), (0, 0, 0, Fp - F)), pad(fc1_b.detach().float(), (0, Fp - F)), pad(fc2_w.detach().float(), (0, Fp - F))
+
+
+# LayerNorm folding of the pre-LN CLIP blocks (csrc/gemm_epilogue.h, MQ_EPI_LN_APPLY): the loaders prepare gamma-folded copies of the QKV / fc1
+# weights (+ folded bias and column sums); on the bf16 residual stream the tiled GEMMs then read the stream itself and no LayerNorm kernel runs in
+# front of them.  The un-folded weights stay for the small-call kernels (fused-LayerNorm skinny GEMMs) and the fp32-stream towers.
+# MARQO_AMD_LN_FOLD=0: do not build the folded tensors (the towers then always launch their LayerNorms).
+LN_FOLD = os.environ.get("MARQO_AMD_LN_FOLD", "1") != "0"
+
+
+# per-block tensor names: open_clip ResidualAttentionBlock / timm Block (the SigLIP trunks)
+_OPEN_CLIP_KEYS = dict(block="resblocks.{}.", ln1="ln_1", qkv_w="attn.in_proj_weight", qkv_b="attn.in_proj_bias", out="attn.out_proj",
+                       ln2="ln_2", fc1="mlp.c_fc", fc2="mlp.c_proj")
+_TIMM_KEYS = dict(block="blocks.{}.", ln1="norm1", qkv_w="attn.qkv.weight", qkv_b="attn.qkv.bias", out="attn.proj",
+                  ln2="norm2", fc1="mlp.fc1", fc2="mlp.fc2")
+
+
+def fold_layernorm(w: Tensor, b: Tensor, gamma: Tensor, beta: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """A LayerNorm folded into the linear layer behind it (csrc/gemm_epilogue.h, MQ_EPI_LN_APPLY; mq_gemm_bf16_ln):
+    LN(x) @ W^T + b = rstd * (x @ (g*W)^T - mean * colsum(g*W)) + (b + W @ beta)  -> (bf16 g*W [N, K], fp32 bias [N], fp32 colsum [N]).
+    colsum is taken over the bf16-ROUNDED folded weight (what the MFMA multiplies), the bias in fp32 from the fp32 W.  Callers pass the tensors
+    the block really runs (head- / MLP-padded where it pads)."""
+    w32 = w.detach().to(torch.float32)
+    wf = (w32 * gamma.detach().to(torch.float32).unsqueeze(0)).to(torch.bfloat16)
+    return wf, b.detach().to(torch.float32) + w32 @ beta.detach().to(torch.float32), wf.to(torch.float32).sum(dim=1)
+
+
+def _hand_over_fold(h: _Holder, b, name: str, w: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor) -> None:
+    """block fields <name>_wf / _sf / _bf = fold_layernorm(...), handed to the holder in that order"""
+    wf, bf, sf = fold_layernorm(w, bias, gamma, beta)
+    setattr(b, name + "_wf", h.bf16(wf))
+    setattr(b, name + "_sf", h.f32(sf))
+    setattr(b, name + "_bf", h.f32(bf))
+
+
+def _clip_blocks(h: _Holder, sd, prefix: str, layers: int, W: int, F: int, heads: int, keys=_OPEN_CLIP_KEYS):
+    d = _head_dim(W, heads)
+    padded = d != _kernel_head_dim(d, heads)  # ViT-H / g / bigG: 80 / 88 / 104-wide heads run as 96 / 96 / 112
+    arr = (L.BlockWeights * layers)()
+    k = keys
+    for i in range(layers):
+        p = prefix + k["block"].format(i)
+        b = arr[i]
+        b.ln1_g = h.f32(_need(sd, p + k["ln1"] + ".weight", (W,)))
+        b.ln1_b = h.f32(_need(sd, p + k["ln1"] + ".bias", (W,)))
+        qkv_w, qkv_b = _need(sd, p + k["qkv_w"], (3 * W, W)), _need(sd, p + k["qkv_b"], (3 * W,))
+        out_w = _need(sd, p + k["out"] + ".weight", (W, W))
+        if padded:
+            qkv_w, qkv_b, out_w = _pad_heads(qkv_w.detach(), qkv_b.detach(), out_w.detach(), heads, d)
+        b.qkv_w, b.qkv_b, b.out_w = h.bf16(qkv_w), h.f32(qkv_b), h.bf16(out_w)
+        b.out_b = h.f32(_need(sd, p + k["out"] + ".bias", (W,)))
+        b.ln2_g = h.f32(_need(sd, p + k["ln2"] + ".weight", (W,)))
+        b.ln2_b = h.f32(_need(sd, p + k["ln2"] + ".bias", (W,)))
+        fc1_w, fc1_b, fc2_w = _pad_mlp(_need(sd, p + k["fc1"] + ".weight", (F, W)), _need(sd, p + k["fc1"] + ".bias", (F,)),
+                                       _need(sd, p + k["fc2"] + ".weight", (W, F)))
+        b.fc1_w, b.fc1_b, b.fc2_w = h.bf16(fc1_w), h.f32(fc1_b), h.bf16(fc2_w)
+        b.fc2_b = h.f32(_need(sd, p + k["fc2"] + ".bias", (W,)))
+        if LN_FOLD:   # ln_1 into the QKV GEMM, ln_2 into fc1
+            for name, w_t, b_t, lg in (("qkv", qkv_w, qkv_b, k["ln1"]), ("fc1", fc1_w, fc1_b, k["ln2"])):
+                _hand_over_fold(h, b, name, w_t, b_t, sd[p + lg + ".weight"], sd[p + lg + ".bias"])
+    return arr
+
+
+# EVA02 blocks: up * silu(gate) in the (up | gate) GEMM's epilogue (MQ_EPI_GLU; 0 = the round-5 form: the GEMM writes (up | gate), glu_ln_kernel multiplies)
+EVA_GLU_EPILOGUE = os.environ.get("MARQO_AMD_EVA_GLU_EPILOGUE", "1") != "0"
+
+
+def _eva_blocks(h: _Holder, sd, prefix: str, layers: int, W: int, F: int, heads: int):
+    """timm EvaBlock tensors (eva.py; `blocks.{i}.`): norm1, attn.{q_proj, k_proj (no bias), v_proj} or the fused attn.qkv + q_bias / v_bias,
+    attn.norm (the LayerNorm in front of attn.proj; absent without `scale_attn_inner`), attn.proj, norm2, mlp.{fc1_g, fc1_x, norm, fc2}
+    (timm SwiGLU: fc2(norm(silu(fc1_g(x)) * fc1_x(x)))).  fc1 is stored as (up, gate) = (fc1_x, fc1_g) rows interleaved 16 by 16, the hidden width F zero-padded
+    to a multiple of 64: silu(0) * 0 = 0 meets zero LayerNorm weights and zero fc2 columns — exact; the statistics run over F (mlp_ln_dim)."""
+    if _head_dim(W, heads) != _kernel_head_dim(_head_dim(W, heads), heads):
+        raise ValueError("EVA02 towers with heads that are not 64 / 96 / 112 / 128 wide are not runnable (rotary positions on padded heads)")
+    Fp = _ceil64(F)
+    pad = torch.nn.functional.pad
+    arr = (L.BlockWeights * layers)()
+    for i in range(layers):
+        p = prefix + f"blocks.{i}."
+        f32 = lambda k, shape: _need(sd, p + k, shape).detach().to(torch.float32)
+        b = arr[i]
+        b.ln1_g, b.ln1_b = h.f32(f32("norm1.weight", (W,))), h.f32(f32("norm1.bias", (W,)))
+        if p + "attn.qkv.weight" in sd:
+            qkv_w = f32("attn.qkv.weight", (3 * W, W))
+            qb = f32("attn.q_bias", (W,)) if p + "attn.q_bias" in sd else torch.zeros(W)
+            vb = f32("attn.v_bias", (W,)) if p + "attn.v_bias" in sd else torch.zeros(W)
+        else:
+            qkv_w = torch.cat([f32("attn.q_proj.weight", (W, W)), f32("attn.k_proj.weight", (W, W)), f32("attn.v_proj.weight", (W, W))], dim=0)
+            qb = f32("attn.q_proj.bias", (W,)) if p + "attn.q_proj.bias" in sd else torch.zeros(W)
+            vb = f32("attn.v_proj.bias", (W,)) if p + "attn.v_proj.bias" in sd else torch.zeros(W)
+        qkv_b = torch.cat([qb, torch.zeros(W), vb])                                        # (keys carry no bias)
+        b.qkv_w, b.qkv_b = h.bf16(qkv_w), h.f32(qkv_b)
+        if p + "attn.norm.weight" in sd:
+            b.attn_ln_g, b.attn_ln_b = h.f32(f32("attn.norm.weight", (W,))), h.f32(f32("attn.norm.bias", (W,)))
+        b.out_w, b.out_b = h.bf16(f32("attn.proj.weight", (W, W))), h.f32(f32("attn.proj.bias", (W,)))
+        b.ln2_g, b.ln2_b = h.f32(f32("norm2.weight", (W,))), h.f32(f32("norm2.bias", (W,)))
+        up_w, up_b = f32("mlp.fc1_x.weight", (F, W)), f32("mlp.fc1_x.bias", (F,))
+        gate_w, gate_b = f32("mlp.fc1_g.weight", (F, W)), f32("mlp.fc1_g.bias", (F,))
+        # (up, gate) rows interleaved 16 by 16 (mq_encoder_cfg.mlp_glu = 2): a lane of the GEMM's epilogue then holds up AND gate of the same hidden
+        # units and forms up * silu(gate) itself (MQ_EPI_GLU) — the (up | gate) tensor is never written
+        il = (lambda u, g_: torch.stack([u.reshape(Fp // 16, 16, *u.shape[1:]), g_.reshape(Fp // 16, 16, *g_.shape[1:])], dim=1).reshape(2 * Fp, *u.shape[1:])) \
+            if EVA_GLU_EPILOGUE else (lambda u, g_: torch.cat([u, g_], dim=0))
+        fc1_w = il(pad(up_w, (0, 0, 0, Fp - F)), pad(gate_w, (0, 0, 0, Fp - F)))
+        fc1_b = il(pad(up_b, (0, Fp - F)), pad(gate_b, (0, Fp - F)))
+        b.fc1_w, b.fc1_b = h.bf16(fc1_w), h.f32(fc1_b)
+        if p + "mlp.norm.weight" in sd:
+            b.mlp_ln_g, b.mlp_ln_b = h.f32(pad(f32("mlp.norm.weight", (F,)), (0, Fp - F))), h.f32(pad(f32("mlp.norm.bias", (F,)), (0, Fp - F)))
+        b.fc2_w, b.fc2_b = h.bf16(pad(f32("mlp.fc2.weight", (W, F)), (0, Fp - F))), h.f32(f32("mlp.fc2.bias", (W,)))
+        if LN_FOLD:   # norm1 into the QKV GEMM, norm2 into the (up | gate) GEMM (as _clip_blocks)
+            for name, w32, b32, lg in (("qkv", qkv_w, qkv_b, "norm1"), ("fc1", fc1_w, fc1_b, "norm2")):
+                _hand_over_fold(h, b, name, w32, b32, f32(lg + ".weight", (W,)), f32(lg + ".bias", (W,)))
+            # ... and the sub-LayerNorms into the GEMMs behind them (ABI 12, csrc/towers.hip block_eva): attn.norm into attn.proj, mlp.norm into mlp.fc2 (over
+            # the padded hidden width: zero LayerNorm weights meet zero fc2 columns).  Their rows' statistics come from the attention kernel / the gated epilogue.
+            subs = []
+            if p + "attn.norm.weight" in sd:
+                subs.append(("out", f32("attn.proj.weight", (W, W)), f32("attn.proj.bias", (W,)), f32("attn.norm.weight", (W,)), f32("attn.norm.bias", (W,))))
+            if p + "mlp.norm.weight" in sd and EVA_GLU_EPILOGUE:
+                subs.append(("fc2", pad(f32("mlp.fc2.weight", (W, F)), (0, Fp - F)), f32("mlp.fc2.bias", (W,)), pad(f32("mlp.norm.weight", (F,)), (0, Fp - F)),
+                             pad(f32("mlp.norm.bias", (F,)), (0, Fp - F))))
+            for sub in subs:
+                _hand_over_fold(h, b, *sub)
+    return arr
+
+
+def _bert_blocks(h: _Holder, sd, prefix: str, layers: int, W: int, F: int, heads: int, new_model: bool = False, mpnet: bool = False):
+    """post-LN HF encoder layers (`encoder.layer.{i}.`): BertModel / XLM-RoBERTa naming, MPNetModel naming (`mpnet`) or Alibaba-NLP NewModel naming
+    (`new_model`: fused qkv_proj, (up | gate) MLP).  No LayerNorm is folded: post-LN blocks normalise behind their GEMMs."""
+    hd = _head_dim(W, heads)
+    arr = (L.BlockWeights * layers)()
+    # checkpoint key names of the attention sub-block: (q, k, v, out-projection, LayerNorm)
+    ak = ("attention.attn.q", "attention.attn.k", "attention.attn.v", "attention.attn.o", "attention.LayerNorm") if mpnet else \
+         ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense", "attention.output.LayerNorm")
+    for i in range(layers):
+        p = prefix + f"encoder.layer.{i}."
+        b = arr[i]
+        if new_model:
+            qkv_w = _need(sd, p + "attention.qkv_proj.weight", (3 * W, W)).detach().float()
+            qkv_b = _need(sd, p + "attention.qkv_proj.bias", (3 * W,)).detach().float()
+            b.qkv_w, b.qkv_b = h.bf16(qkv_w), h.f32(qkv_b)
+            b.out_w = h.bf16(_need(sd, p + "attention.o_proj.weight", (W, W)))
+            b.out_b = h.f32(_need(sd, p + "attention.o_proj.bias", (W,)))
+            b.ln1_g, b.ln1_b = h.f32(_need(sd, p + "attn_ln.weight", (W,))), h.f32(_need(sd, p + "attn_ln.bias", (W,)))
+            b.fc1_w = h.bf16(_need(sd, p + "mlp.up_gate_proj.weight", (2 * F, W)))      # rows [0, F) = up, [F, 2F) = gate
+            b.fc1_b = h.f32(sd[p + "mlp.up_gate_proj.bias"]) if p + "mlp.up_gate_proj.bias" in sd else None
+            b.fc2_w = h.bf16(_need(sd, p + "mlp.down_proj.weight", (W, F)))
+            b.fc2_b = h.f32(_need(sd, p + "mlp.down_proj.bias", (W,)))
+            b.ln2_g, b.ln2_b = h.f32(_need(sd, p + "mlp_ln.weight", (W,))), h.f32(_need(sd, p + "mlp_ln.bias", (W,)))
+            continue
+        qkv_w = torch.cat([_need(sd, p + f"{n}.weight", (W, W)).detach().float() for n in ak[:3]], 0)
+        qkv_b = torch.cat([_need(sd, p + f"{n}.bias", (W,)).detach().float() for n in ak[:3]], 0)
+        out_w = _need(sd, p + ak[3] + ".weight", (W, W)).detach().float()
+        if hd != _kernel_head_dim(hd, heads):  # e5-small / bge-small / MiniLM: 12 heads of 32
+            qkv_w, qkv_b, out_w = _pad_heads(qkv_w, qkv_b, out_w, heads, hd)
+        b.qkv_w, b.qkv_b = h.bf16(qkv_w), h.f32(qkv_b)
+        b.out_w = h.bf16(out_w)
+        b.out_b = h.f32(_need(sd, p + ak[3] + ".bias", (W,)))
+        b.ln1_g = h.f32(_need(sd, p + ak[4] + ".weight", (W,)))
+        b.ln1_b = h.f32(_need(sd, p + ak[4] + ".bias", (W,)))
+        b.fc1_w = h.bf16(_need(sd, p + "intermediate.dense.weight", (F, W)))
+        b.fc1_b = h.f32(_need(sd, p + "intermediate.dense.bias", (F,)))
+        b.fc2_w = h.bf16(_need(sd, p + "output.dense.weight", (W, F)))
+        b.fc2_b = h.f32(_need(sd, p + "output.dense.bias", (W,)))
+        b.ln2_g = h.f32(_need(sd, p + "output.LayerNorm.weight", (W,)))
+        b.ln2_b = h.f32(_need(sd, p + "output.LayerNorm.bias", (W,)))
+    return arr
+
+
+def nllb_clip_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """The load-time transforms of the NLLB-CLIP text tower: open_clip HFTextEncoder / transformers M2M100Encoder tensors (`text.transformer.*`,
+    `text.proj.weight`) -> the CLIP text tower's own names (fp32), so that everything but the ReLU runs on what exists:
+      * token_embedding  = embed_tokens * sqrt(width)   (M2M100's embed_scale; row pad_id is never gathered: only un-padded rows run)
+      * positional_embedding [ctx, width] = the sinusoidal table from position pos_offset on (arch.position_table(): a non-persistent buffer)
+      * resblocks.N: q_proj | k_proj | v_proj packed into attn.in_proj_{weight, bias}; self_attn_layer_norm -> ln_1, final_layer_norm -> ln_2,
+        fc1 / fc2 -> mlp.c_fc / mlp.c_proj; the encoder's layer_norm -> ln_final; text_projection [width, out_dim] = proj.weight^T (no bias)."""
+    W, F = arch.width, arch.mlp_dim
+    t = "text.transformer."
+    f32 = lambda key, shape: _need(sd, key, shape).detach().to(torch.float32)
+    out = {"token_embedding.weight": f32(t + "embed_tokens.weight", (arch.vocab, W)) * math.sqrt(W),
+           "positional_embedding": arch.position_table(),
+           "ln_final.weight": f32(t + "layer_norm.weight", (W,)), "ln_final.bias": f32(t + "layer_norm.bias", (W,)),
+           "text_projection": f32("text.proj.weight", (arch.out_dim, W)).t().contiguous()}
+    for i in range(arch.layers):
+        p, o = f"{t}layers.{i}.", f"transformer.resblocks.{i}."
+        out[o + "attn.in_proj_weight"] = torch.cat([f32(p + f"self_attn.{n}_proj.weight", (W, W)) for n in "qkv"], dim=0)
+        out[o + "attn.in_proj_bias"] = torch.cat([f32(p + f"self_attn.{n}_proj.bias", (W,)) for n in "qkv"], dim=0)
+        for src, dst, shape in (("self_attn.out_proj", "attn.out_proj", (W, W)), ("fc1", "mlp.c_fc", (F, W)), ("fc2", "mlp.c_proj", (W, F))):
+            out[o + dst + ".weight"] = f32(p + src + ".weight", shape)
+            out[o + dst + ".bias"] = f32(p + src + ".bias", shape[:1])
+        for src, dst in (("self_attn_layer_norm", "ln_1"), ("final_layer_norm", "ln_2")):
+            out[o + dst + ".weight"], out[o + dst + ".bias"] = f32(p + src + ".weight", (W,)), f32(p + src + ".bias", (W,))
+    return out
+
+
+# ---- ConvNeXt image towers (csrc/convnext.hip) ------------------------------------------------------------------------------------------------
+# Load-time folds, as pure CPU-tensor functions (tests/test_convnext_host.py checks them against the unfolded fp32 computation).
+
+def convnext_dw_taps(conv_dw_w: Tensor) -> Tensor:
+    """conv_dw.weight [C, 1, 7, 7] -> fp32 [49, C] (tap-major: one tap's C channels are contiguous, as the kernel stages them)"""
+    C = conv_dw_w.shape[0]
+    return conv_dw_w.detach().to(torch.float32).reshape(C, 49).t().contiguous()
+
+
+def convnext_fold_ln_fc1(fc1_w: Tensor, fc1_b: Tensor, ln_g: Tensor, ln_b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """The block's LayerNorm folded into fc1 (mq_gemm_bf16_ln): LN(x) @ W^T + b = rstd * (x @ (g*W)^T - mean * colsum) + (b + W @ beta)
+    -> (bf16 g*W [4C, C], fp32 bias [4C], fp32 colsum of the ROUNDED folded weight [4C])"""
+    return fold_layernorm(fc1_w, fc1_b, ln_g, ln_b)
+
+
+def convnext_fold_gamma_fc2(fc2_w: Tensor, fc2_b: Tensor, gamma: Tensor) -> Tuple[Tensor, Tensor]:
+    """gamma * (h @ W^T + b) = h @ (gamma[:, None] * W)^T + gamma * b  -> (fp32 weight [C, 4C], fp32 bias [C])"""
+    g = gamma.detach().to(torch.float32)
+    return fc2_w.detach().to(torch.float32) * g.unsqueeze(1), fc2_b.detach().to(torch.float32) * g
+
+
+def convnext_downsample_weight(w: Tensor) -> Tensor:
+    """downsample.1.weight [C_out, C_in, 2, 2] -> fp32 [C_out, 4 C_in] with columns in (ky, kx, c) order: the gather copies whole pixels"""
+    return w.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def convnext_downsample_gather(x_nhwc: Tensor) -> Tensor:
+    """the gather mq_convnext_downsample performs (without its LayerNorm), in torch: [n, H, W, C] -> [n (H/2) (W/2), 4 C], (ky, kx, c) columns"""
+    n, H, W, C = x_nhwc.shape
+    return x_nhwc.reshape(n, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(n * (H // 2) * (W // 2), 4 * C)
+
+
+# ---- ResNet CLIP image towers (csrc/resnet.hip) -------------------------------------------------------------------------------------------------
+RESNET_BN_EPS = 1e-5
+
+
+def resnet_pad64(c: int) -> int:
+    """channel count as the tower stores it: zero-padded to a multiple of 64 (the tiled GEMMs' k-step)"""
+    return (c + 63) // 64 * 64
+
+
+def resnet_fold_bn(conv_w: Tensor, bn_w: Tensor, bn_b: Tensor, bn_mean: Tensor, bn_var: Tensor, eps: float = RESNET_BN_EPS) -> Tuple[Tensor, Tensor]:
+    """conv (no bias) followed by eval-mode BatchNorm -> one conv with a bias: w' = w * g / sqrt(var + eps) per output channel, b' = beta - mean * that"""
+    s = bn_w.double() / torch.sqrt(bn_var.double() + eps)
+    w = (conv_w.double() * s.view(-1, *([1] * (conv_w.dim() - 1)))).float()
+    return w, (bn_b.double() - bn_mean.double() * s).float()
+
+
+def resnet_conv3x3_weight(w: Tensor, cin: int, cout: int) -> Tensor:
+    """[O, I, 3, 3] -> fp32 [cout, Kp]: column (ky * 3 + kx) * cin + c (mq_resnet_conv3x3), zero-padded to cin input / cout output channels and to
+    Kp = 9 cin rounded up to a multiple of 64"""
+    O, I = w.shape[:2]
+    full = torch.zeros(cout, 3, 3, cin, dtype=torch.float32)
+    full[:O, :, :, :I] = w.permute(0, 2, 3, 1).float()
+    Kp = (9 * cin + 63) // 64 * 64
+    out = torch.zeros(cout, Kp, dtype=torch.float32)
+    out[:, :9 * cin] = full.reshape(cout, 9 * cin)
+    return out
+
+
+def resnet_conv1x1_weight(w: Tensor, cin: int, cout: int) -> Tensor:
+    """[O, I, 1, 1] -> fp32 [cout, cin], zero-padded"""
+    O, I = w.shape[:2]
+    out = torch.zeros(cout, cin, dtype=torch.float32)
+    out[:O, :I] = w.reshape(O, I).float()
+    return out
+
+
+def resnet_stem_weight(w: Tensor) -> Tensor:
+    """visual.conv1 [O, 3, 3, 3] -> fp32 [O, 64]: column (ky * 3 + kx) * 3 + c (mq_resnet_stem_gather's patch rows), zero past 27"""
+    out = torch.zeros(w.shape[0], 64, dtype=torch.float32)
+    out[:, :27] = w.permute(0, 2, 3, 1).reshape(w.shape[0], 27).float()
+    return out
+
+
+def resnet_pad_vec(v: Tensor, n: int) -> Tensor:
+    out = torch.zeros(n, dtype=torch.float32)
+    out[:v.numel()] = v.float()
+    return out
+
+
+def resnet_attnpool_weights(sd: Dict[str, Tensor], arch) -> Dict[str, Tensor]:
+    """visual.attnpool.* -> the fp32 operands of the tower's attention pool (mq_resnet_weights): positions [T, C]; q_proj with the 64^-0.5 softmax
+    scale folded into weight and bias (a power of two: the folded weight rounds to bf16 exactly as the unscaled one); k_proj and v_proj stacked into
+    one [2C, C] projection; c_proj"""
+    Cw, T, E, ap = 32 * arch.width, arch.tokens, arch.out_dim, "visual.attnpool."
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    scale = 64 ** -0.5
+    return {"pos": f32(ap + "positional_embedding", (T, Cw)),
+            "q_w": f32(ap + "q_proj.weight", (Cw, Cw)) * scale, "q_b": f32(ap + "q_proj.bias", (Cw,)) * scale,
+            "kv_w": torch.cat([f32(ap + "k_proj.weight", (Cw, Cw)), f32(ap + "v_proj.weight", (Cw, Cw))]),
+            "kv_b": torch.cat([f32(ap + "k_proj.bias", (Cw,)), f32(ap + "v_proj.bias", (Cw,))]),
+            "c_w": f32(ap + "c_proj.weight", (E, Cw)), "c_b": f32(ap + "c_proj.bias", (E,))}

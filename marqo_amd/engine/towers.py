@@ -9,14 +9,17 @@ once, so nothing is ever re-uploaded):
   * biases, LayerNorm affine, class/positional/token embeddings   fp32
   * patch-embed conv weight  bf16 [W, Kp], K = (c, ky, kx) flattened, zero-padded to a multiple of 64
   * projections      bf16 [D, W] (transposed once at load so they are plain NT GEMM operands)
+
+The checkpoint-to-tensor transforms themselves (padding, folding, key renaming, the per-block loaders) live in engine/tower_weights.py
+and are imported here under their names, so `towers.<name>` keeps resolving for all of them.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
+import logging
 import os
 import threading
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -24,8 +27,14 @@ import torch
 from marqo_amd import _lib as L
 from marqo_amd.engine import native_queue as NQ
 from marqo_amd.engine.archs import BertArch, ClipTextArch, VitArch, OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
+from marqo_amd.engine.tower_weights import (  # noqa: F401  (re-exported: tests, tools and the loaders reach them as towers.<name>)
+    EVA_GLU_EPILOGUE, KERNEL_HEAD_DIMS, LN_FOLD, RESNET_BN_EPS, _OPEN_CLIP_KEYS, _TIMM_KEYS, _Holder, _bert_blocks, _ceil64, _clip_blocks,
+    _eva_blocks, _head_dim, _kernel_head_dim, _need, _pad_heads, _pad_mlp, convnext_downsample_gather, convnext_downsample_weight,
+    convnext_dw_taps, convnext_fold_gamma_fc2, convnext_fold_ln_fc1, fold_layernorm, nllb_clip_state_dict, resnet_attnpool_weights,
+    resnet_conv1x1_weight, resnet_conv3x3_weight, resnet_fold_bn, resnet_pad64, resnet_pad_vec, resnet_stem_weight)
 
 Tensor = torch.Tensor
+_log = logging.getLogger(__name__)
 
 # upper bound of token rows pushed through one C-ABI call (bounds the scratch workspace; with
 # 288 GB of HBM this is deliberately large so GEMMs see M in the 10^5 range)
@@ -62,99 +71,6 @@ def _require_gpu(device: str) -> torch.device:
             raise L.MarqoHipUnavailableError(lib.mq_last_error().decode())
         _checked_devices.add(d.index)
     return d
-
-
-class _Holder:
-    """Keeps device tensors alive and hands out raw pointers."""
-
-    def __init__(self, device: torch.device):
-        self.device = device
-        self.tensors: List[Tensor] = []
-
-    def f32(self, t: Tensor) -> int:
-        d = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        self.tensors.append(d)
-        return d.data_ptr()
-
-    def bf16(self, t: Tensor) -> int:
-        d = t.detach().to(dtype=torch.float32).to(device=self.device).to(torch.bfloat16).contiguous()
-        self.tensors.append(d)
-        return d.data_ptr()
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.tensors)
-
-    def drop(self, ptr: int) -> int:
-        """forget the tensor that starts at `ptr` (its HBM goes back to the allocator once nothing else holds it) -> bytes released"""
-        for i, t in enumerate(self.tensors):
-            if t.data_ptr() == ptr:
-                del self.tensors[i]
-                return t.numel() * t.element_size()
-        return 0
-
-
-def _need(sd: Dict[str, Tensor], key: str, shape: Optional[Tuple[int, ...]] = None) -> Tensor:
-    if key not in sd:
-        raise KeyError(f"checkpoint is missing tensor '{key}'")
-    t = sd[key]
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"checkpoint tensor '{key}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t
-
-
-def _head_dim(width: int, heads: int) -> int:
-    """model head dim; the attention kernel runs 64- / 96- / 112- / 128-wide heads, anything else is zero-padded at load (_pad_heads)"""
-    if heads < 1 or width % heads:
-        raise ValueError(f"width {width} is not divisible by heads {heads}")
-    d = width // heads
-    if d > 128:
-        raise ValueError(f"attention head dim must be <= 128 for the gfx950 attention kernel (width={width}, heads={heads}: {d})")
-    return d
-
-
-KERNEL_HEAD_DIMS = (64, 96, 112, 128)  # head strides csrc/attention.hip is instantiated for
-
-
-def _kernel_head_dim(d: int, heads: int = 2) -> int:
-    """head width the kernel runs for a model head dim d: the smallest instantiated stride >= d whose attention width heads * hp
-    keeps the GEMM's K a multiple of 64: 32 / 16 -> 64 (e5-small, MiniLM), 80 / 88 -> 96 (ViT-H / g), 104 -> 112 (ViT-bigG)"""
-    for hp in KERNEL_HEAD_DIMS:
-        if hp >= d and (heads * hp) % 64 == 0:
-            return hp
-    return 128
-
-
-def _pad_heads(qkv_w: Tensor, qkv_b: Tensor, out_w: Tensor, heads: int, d: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """[3W, W] / [3W] / [W, W] with d-wide heads -> [3*heads*hp, W] / [3*heads*hp] / [W, heads*hp] (hp = _kernel_head_dim): each
-    head's Q / K / V rows and out-projection columns are zero-padded to hp (zero key / query dims add nothing to q.k, zero value
-    dims meet zero out-proj columns), and Q is scaled by sqrt(hp / d) so that the kernel's 1/sqrt(hp) softmax scale equals the
-    model's 1/sqrt(d)."""
-    W = out_w.shape[0]
-    hp = _kernel_head_dim(d, heads)
-    q, k, v = qkv_w.float().view(3, heads, d, W).unbind(0)
-    qb, kb, vb = qkv_b.float().view(3, heads, d).unbind(0)
-    sc = (float(hp) / d) ** 0.5
-    pad_w = lambda t: torch.nn.functional.pad(t, (0, 0, 0, hp - d)).reshape(heads * hp, W)
-    pad_b = lambda t: torch.nn.functional.pad(t, (0, hp - d)).reshape(heads * hp)
-    qkv_w2 = torch.cat([pad_w(q * sc), pad_w(k), pad_w(v)], 0)
-    qkv_b2 = torch.cat([pad_b(qb * sc), pad_b(kb), pad_b(vb)], 0)
-    out_w2 = torch.nn.functional.pad(out_w.float().view(W, heads, d), (0, hp - d)).reshape(W, heads * hp)
-    return qkv_w2, qkv_b2, out_w2
-
-
-def _ceil64(v: int) -> int:
-    return (v + 63) // 64 * 64
-
-
-def _pad_mlp(fc1_w: Tensor, fc1_b: Tensor, fc2_w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-    """MLP hidden sizes that are not a multiple of 64 (ViT-SO400M: 4304) are zero-padded: the extra hidden units are act(0 + 0) = 0
-    for GELU / QuickGELU and meet zero fc2 columns — exact."""
-    F = fc1_w.shape[0]
-    Fp = _ceil64(F)
-    if Fp == F:
-        return fc1_w, fc1_b, fc2_w
-    pad = torch.nn.functional.pad
-    return pad(fc1_w.detach().float(), (0, 0, 0, Fp - F)), pad(fc1_b.detach().float(), (0, Fp - F)), pad(fc2_w.detach().float(), (0, Fp - F))
 
 
 def _encoder_cfg(width, layers, heads, mlp_dim, quick_gelu, post_ln, mask, eps) -> L.EncoderCfg:
@@ -199,123 +115,6 @@ class _Fp8State:
         seen = self.amax > 0
         self.scale[seen] = (self.amax[seen] * (margin / 448.0))
         self.amax.zero_()
-
-
-# LayerNorm folding of the pre-LN CLIP blocks (csrc/gemm_epilogue.h, MQ_EPI_LN_APPLY): the loaders prepare gamma-folded copies of the QKV / fc1
-# weights (+ folded bias and column sums); on the bf16 residual stream the tiled GEMMs then read the stream itself and no LayerNorm kernel runs in
-# front of them.  The un-folded weights stay for the small-call kernels (fused-LayerNorm skinny GEMMs) and the fp32-stream towers.
-# MARQO_AMD_LN_FOLD=0: do not build the folded tensors (the towers then always launch their LayerNorms).
-LN_FOLD = os.environ.get("MARQO_AMD_LN_FOLD", "1") != "0"
-
-
-# per-block tensor names: open_clip ResidualAttentionBlock / timm Block (the SigLIP trunks)
-_OPEN_CLIP_KEYS = dict(block="resblocks.{}.", ln1="ln_1", qkv_w="attn.in_proj_weight", qkv_b="attn.in_proj_bias", out="attn.out_proj",
-                       ln2="ln_2", fc1="mlp.c_fc", fc2="mlp.c_proj")
-_TIMM_KEYS = dict(block="blocks.{}.", ln1="norm1", qkv_w="attn.qkv.weight", qkv_b="attn.qkv.bias", out="attn.proj",
-                  ln2="norm2", fc1="mlp.fc1", fc2="mlp.fc2")
-
-
-def _clip_blocks(h: _Holder, sd, prefix: str, layers: int, W: int, F: int, heads: int, keys=_OPEN_CLIP_KEYS):
-    d = _head_dim(W, heads)
-    padded = d != _kernel_head_dim(d, heads)  # ViT-H / g / bigG: 80 / 88 / 104-wide heads run as 96 / 96 / 112
-    arr = (L.BlockWeights * layers)()
-    k = keys
-    for i in range(layers):
-        p = prefix + k["block"].format(i)
-        b = arr[i]
-        b.ln1_g = h.f32(_need(sd, p + k["ln1"] + ".weight", (W,)))
-        b.ln1_b = h.f32(_need(sd, p + k["ln1"] + ".bias", (W,)))
-        qkv_w, qkv_b = _need(sd, p + k["qkv_w"], (3 * W, W)), _need(sd, p + k["qkv_b"], (3 * W,))
-        out_w = _need(sd, p + k["out"] + ".weight", (W, W))
-        if padded:
-            qkv_w, qkv_b, out_w = _pad_heads(qkv_w.detach(), qkv_b.detach(), out_w.detach(), heads, d)
-        b.qkv_w, b.qkv_b, b.out_w = h.bf16(qkv_w), h.f32(qkv_b), h.bf16(out_w)
-        b.out_b = h.f32(_need(sd, p + k["out"] + ".bias", (W,)))
-        b.ln2_g = h.f32(_need(sd, p + k["ln2"] + ".weight", (W,)))
-        b.ln2_b = h.f32(_need(sd, p + k["ln2"] + ".bias", (W,)))
-        fc1_w, fc1_b, fc2_w = _pad_mlp(_need(sd, p + k["fc1"] + ".weight", (F, W)), _need(sd, p + k["fc1"] + ".bias", (F,)),
-                                       _need(sd, p + k["fc2"] + ".weight", (W, F)))
-        b.fc1_w, b.fc1_b, b.fc2_w = h.bf16(fc1_w), h.f32(fc1_b), h.bf16(fc2_w)
-        b.fc2_b = h.f32(_need(sd, p + k["fc2"] + ".bias", (W,)))
-        if LN_FOLD:
-            # LayerNorm folding (csrc/gemm_epilogue.h): LN(x) @ W^T = rstd * (x @ (g*W)^T - mean * colsum(g*W)) + (b + W @ beta).
-            # colsum is taken over the bf16-ROUNDED folded weight (what the MFMA multiplies), the bias in fp32 from the fp32 W; the (possibly
-            # head- / MLP-padded) tensors the block really runs are the ones folded.
-            for name, w_t, b_t, lg in (("qkv", qkv_w, qkv_b, k["ln1"]), ("fc1", fc1_w, fc1_b, k["ln2"])):
-                w32 = w_t.detach().to(torch.float32)
-                gam, bet = sd[p + lg + ".weight"].detach().to(torch.float32), sd[p + lg + ".bias"].detach().to(torch.float32)
-                wf = (w32 * gam.unsqueeze(0)).to(torch.bfloat16)
-                setattr(b, name + "_wf", h.bf16(wf))
-                setattr(b, name + "_sf", h.f32(wf.to(torch.float32).sum(dim=1)))
-                setattr(b, name + "_bf", h.f32(b_t.detach().to(torch.float32) + w32 @ bet))
-    return arr
-
-
-# EVA02 blocks: up * silu(gate) in the (up | gate) GEMM's epilogue (MQ_EPI_GLU; 0 = the round-5 form: the GEMM writes (up | gate), glu_ln_kernel multiplies)
-EVA_GLU_EPILOGUE = os.environ.get("MARQO_AMD_EVA_GLU_EPILOGUE", "1") != "0"
-
-
-def _eva_blocks(h: _Holder, sd, prefix: str, layers: int, W: int, F: int, heads: int):
-    """timm EvaBlock tensors (eva.py; `blocks.{i}.`): norm1, attn.{q_proj, k_proj (no bias), v_proj} or the fused attn.qkv + q_bias / v_bias,
-    attn.norm (the LayerNorm in front of attn.proj; absent without `scale_attn_inner`), attn.proj, norm2, mlp.{fc1_g, fc1_x, norm, fc2}
-    (timm SwiGLU: fc2(norm(silu(fc1_g(x)) * fc1_x(x)))).  fc1 is stored as (up, gate) = (fc1_x, fc1_g) rows interleaved 16 by 16, the hidden width F zero-padded
-    to a multiple of 64: silu(0) * 0 = 0 meets zero LayerNorm weights and zero fc2 columns — exact; the statistics run over F (mlp_ln_dim)."""
-    if _head_dim(W, heads) != _kernel_head_dim(_head_dim(W, heads), heads):
-        raise ValueError("EVA02 towers with heads that are not 64 / 96 / 112 / 128 wide are not runnable (rotary positions on padded heads)")
-    Fp = _ceil64(F)
-    pad = torch.nn.functional.pad
-    arr = (L.BlockWeights * layers)()
-    for i in range(layers):
-        p = prefix + f"blocks.{i}."
-        f32 = lambda k, shape: _need(sd, p + k, shape).detach().to(torch.float32)
-        b = arr[i]
-        b.ln1_g, b.ln1_b = h.f32(f32("norm1.weight", (W,))), h.f32(f32("norm1.bias", (W,)))
-        if p + "attn.qkv.weight" in sd:
-            qkv_w = f32("attn.qkv.weight", (3 * W, W))
-            qb = f32("attn.q_bias", (W,)) if p + "attn.q_bias" in sd else torch.zeros(W)
-            vb = f32("attn.v_bias", (W,)) if p + "attn.v_bias" in sd else torch.zeros(W)
-        else:
-            qkv_w = torch.cat([f32("attn.q_proj.weight", (W, W)), f32("attn.k_proj.weight", (W, W)), f32("attn.v_proj.weight", (W, W))], dim=0)
-            qb = f32("attn.q_proj.bias", (W,)) if p + "attn.q_proj.bias" in sd else torch.zeros(W)
-            vb = f32("attn.v_proj.bias", (W,)) if p + "attn.v_proj.bias" in sd else torch.zeros(W)
-        qkv_b = torch.cat([qb, torch.zeros(W), vb])                                        # (keys carry no bias)
-        b.qkv_w, b.qkv_b = h.bf16(qkv_w), h.f32(qkv_b)
-        if p + "attn.norm.weight" in sd:
-            b.attn_ln_g, b.attn_ln_b = h.f32(f32("attn.norm.weight", (W,))), h.f32(f32("attn.norm.bias", (W,)))
-        b.out_w, b.out_b = h.bf16(f32("attn.proj.weight", (W, W))), h.f32(f32("attn.proj.bias", (W,)))
-        b.ln2_g, b.ln2_b = h.f32(f32("norm2.weight", (W,))), h.f32(f32("norm2.bias", (W,)))
-        up_w, up_b = f32("mlp.fc1_x.weight", (F, W)), f32("mlp.fc1_x.bias", (F,))
-        gate_w, gate_b = f32("mlp.fc1_g.weight", (F, W)), f32("mlp.fc1_g.bias", (F,))
-        # (up, gate) rows interleaved 16 by 16 (mq_encoder_cfg.mlp_glu = 2): a lane of the GEMM's epilogue then holds up AND gate of the same hidden
-        # units and forms up * silu(gate) itself (MQ_EPI_GLU) — the (up | gate) tensor is never written
-        il = (lambda u, g_: torch.stack([u.reshape(Fp // 16, 16, *u.shape[1:]), g_.reshape(Fp // 16, 16, *g_.shape[1:])], dim=1).reshape(2 * Fp, *u.shape[1:])) \
-            if EVA_GLU_EPILOGUE else (lambda u, g_: torch.cat([u, g_], dim=0))
-        fc1_w = il(pad(up_w, (0, 0, 0, Fp - F)), pad(gate_w, (0, 0, 0, Fp - F)))
-        fc1_b = il(pad(up_b, (0, Fp - F)), pad(gate_b, (0, Fp - F)))
-        b.fc1_w, b.fc1_b = h.bf16(fc1_w), h.f32(fc1_b)
-        if p + "mlp.norm.weight" in sd:
-            b.mlp_ln_g, b.mlp_ln_b = h.f32(pad(f32("mlp.norm.weight", (F,)), (0, Fp - F))), h.f32(pad(f32("mlp.norm.bias", (F,)), (0, Fp - F)))
-        b.fc2_w, b.fc2_b = h.bf16(pad(f32("mlp.fc2.weight", (W, F)), (0, Fp - F))), h.f32(f32("mlp.fc2.bias", (W,)))
-        if LN_FOLD:   # norm1 into the QKV GEMM, norm2 into the (up | gate) GEMM (as _clip_blocks)
-            for name, w32, b32, lg in (("qkv", qkv_w, qkv_b, "norm1"), ("fc1", fc1_w, fc1_b, "norm2")):
-                wf = (w32 * f32(lg + ".weight", (W,)).unsqueeze(0)).to(torch.bfloat16)
-                setattr(b, name + "_wf", h.bf16(wf))
-                setattr(b, name + "_sf", h.f32(wf.to(torch.float32).sum(dim=1)))
-                setattr(b, name + "_bf", h.f32(b32 + w32 @ f32(lg + ".bias", (W,))))
-            # ... and the sub-LayerNorms into the GEMMs behind them (ABI 12, csrc/towers.hip block_eva): attn.norm into attn.proj, mlp.norm into mlp.fc2 (over
-            # the padded hidden width: zero LayerNorm weights meet zero fc2 columns).  Their rows' statistics come from the attention kernel / the gated epilogue.
-            subs = []
-            if p + "attn.norm.weight" in sd:
-                subs.append(("out", f32("attn.proj.weight", (W, W)), f32("attn.proj.bias", (W,)), f32("attn.norm.weight", (W,)), f32("attn.norm.bias", (W,))))
-            if p + "mlp.norm.weight" in sd and EVA_GLU_EPILOGUE:
-                subs.append(("fc2", pad(f32("mlp.fc2.weight", (W, F)), (0, Fp - F)), f32("mlp.fc2.bias", (W,)), pad(f32("mlp.norm.weight", (F,)), (0, Fp - F)),
-                             pad(f32("mlp.norm.bias", (F,)), (0, Fp - F))))
-            for name, w32, b32, gam, bet in subs:
-                wf = (w32 * gam.unsqueeze(0)).to(torch.bfloat16)
-                setattr(b, name + "_wf", h.bf16(wf))
-                setattr(b, name + "_sf", h.f32(wf.to(torch.float32).sum(dim=1)))
-                setattr(b, name + "_bf", h.f32(b32 + w32 @ bet))
-    return arr
 
 
 # Single-request calls (the search path: one query text / one image per vectorise()) are ~75-150 dependent launches of 5-10 us.
@@ -455,6 +254,23 @@ class _large_call:
         return False
 
 
+def _max_cos_error(out: Tensor, ref: Tensor) -> float:
+    """max over the rows of 1 - cos(out, ref): the error measure of both load-time policies (fp64 [n, D] in)"""
+    cos = (out * ref).sum(-1) / (out.norm(dim=-1) * ref.norm(dim=-1))
+    return float((1 - cos).max())
+
+
+def _residual_mode() -> str:
+    """MARQO_AMD_RESIDUAL_STREAM = auto (default) | fp32 | bf16"""
+    return os.environ.get("MARQO_AMD_RESIDUAL_STREAM", "auto").lower()
+
+
+def _check_precision(precision: str, allowed: Tuple[str, ...] = ("bf16", "fp8"), what: Optional[str] = None) -> None:
+    """`what`: the refusal's message where a tower has its own wording"""
+    if precision not in allowed:
+        raise ValueError(what or f"precision must be 'bf16' or 'fp8', got {precision!r}")
+
+
 class _TowerBase:
     _fp8: Optional[_Fp8State] = None
 
@@ -498,7 +314,7 @@ class _TowerBase:
         """`run()` pushes the tower's fixed calibration batch through it and returns the [n, D] embeddings -> 'bf16' | 'fp32'"""
         enc = self.cfg.enc
         getattr(self, "_graphs", {}).clear()   # captured single-item graphs bake in the stream's layout and launch sequence: a re-tune must not replay stale ones
-        mode = os.environ.get("MARQO_AMD_RESIDUAL_STREAM", "auto").lower()
+        mode = _residual_mode()
         if self.precision != "bf16" or mode == "fp32":
             enc.residual_stream, self.residual_stream = 2, "fp32"
             return self.residual_stream
@@ -510,14 +326,11 @@ class _TowerBase:
         ref = run().double()
         enc.residual_stream = 1
         out = run().double()
-        cos = (out * ref).sum(-1) / (out.norm(dim=-1) * ref.norm(dim=-1))
-        e = float((1 - cos).max())
+        e = _max_cos_error(out, ref)
         self.residual_stream_error = e
         ok = e <= budget and bool(torch.isfinite(out).all())
         enc.residual_stream, self.residual_stream = (1, "bf16") if ok else (2, "fp32")
-        import logging
-        logging.getLogger(__name__).info("residual stream: %s (bf16 vs fp32 stream on the calibration batch: 1 - cos %.2e, budget %.1e)",
-                                         self.residual_stream, e, budget)
+        _log.info("residual stream: %s (bf16 vs fp32 stream on the calibration batch: 1 - cos %.2e, budget %.1e)", self.residual_stream, e, budget)
         return self.residual_stream
 
     # ---- fp8 policy --------------------------------------------------------------------------------------------------------
@@ -557,22 +370,15 @@ class _TowerBase:
         ref = run().double()
         enc.precision = L.MQ_PREC_FP8
 
-        def err_split(first: int, extra: int) -> float:
+        def err_split(first: int, extra: int = 0) -> float:
             enc.fp8_first_layer, enc.fp8_mlp_extra = first, extra
-            out = run().double()
-            cos = (out * ref).sum(-1) / (out.norm(dim=-1) * ref.norm(dim=-1))
-            return float((1 - cos).max())
+            return _max_cos_error(run().double(), ref)
 
-        def err(first: int) -> float:
-            enc.fp8_first_layer, enc.fp8_mlp_extra = first, 0
-            out = run().double()
-            cos = (out * ref).sum(-1) / (out.norm(dim=-1) * ref.norm(dim=-1))
-            return float((1 - cos).max())
         # The stream itself (pre-LN towers): bf16 rows halve the residual traffic of EVERY block, e4m3 or not.  Its rounding spends part of the
         # same budget (all errors below are measured against the fp32-stream bf16 run), so it is taken only when it costs at most
         # FP8_STREAM_SHARE of the budget with every block still on bf16 operands.
         enc.residual_stream, self.residual_stream, self.residual_stream_error = 2, "fp32", None
-        mode = os.environ.get("MARQO_AMD_RESIDUAL_STREAM", "auto").lower()
+        mode = _residual_mode()
         if not enc.post_ln and mode != "fp32":
             enc.residual_stream = 1
             e_stream = err_split(layers, 0)
@@ -580,7 +386,7 @@ class _TowerBase:
                 self.residual_stream, self.residual_stream_error = "bf16", e_stream
             else:
                 enc.residual_stream = 2
-        e0 = err(0)
+        e0 = err_split(0)
         self.fp8_all_blocks_error = e0
         if e0 <= budget:
             first, e = 0, e0
@@ -588,7 +394,7 @@ class _TowerBase:
             lo, hi, e = 0, layers, 0.0          # err(lo) > budget, err(hi) <= budget (hi == layers: every block bf16)
             while hi - lo > 1:
                 mid = (lo + hi) // 2
-                em = err(mid)
+                em = err_split(mid)
                 if em <= budget:
                     hi, e = mid, em
                 else:
@@ -627,10 +433,8 @@ class _TowerBase:
         enc.fp8_first_layer, enc.fp8_mlp_extra = first, extra
         self.fp8_first_layer, self.fp8_mlp_extra, self.fp8_calibration_error = first, extra, e
         self._fp8.calibrated = True
-        import logging
-        logging.getLogger(__name__).info("fp8 policy: blocks [%d, %d) on e4m3 + the MLP halves of blocks [%d, %d), %s residual stream, 1 - cos vs bf16 on "
-                                         "the calibration batch %.2e (all blocks: %.2e, budget %.1e)", first, layers, first - extra, first,
-                                         self.residual_stream, e, e0, budget)
+        _log.info("fp8 policy: blocks [%d, %d) on e4m3 + the MLP halves of blocks [%d, %d), %s residual stream, 1 - cos vs bf16 on the calibration "
+                  "batch %.2e (all blocks: %.2e, budget %.1e)", first, layers, first - extra, first, self.residual_stream, e, e0, budget)
         return first
 
     def release_unused_folded(self) -> int:
@@ -661,11 +465,22 @@ class _TowerBase:
                         setattr(b, name + suffix, None)
         if freed:
             getattr(self, "_graphs", {}).clear()     # captured launch sequences may have baked the folded form in
-            for _, q in (getattr(self, "_queues", None) or {}).values():    # ... and so may the native queues' (engine/native_queue.py)
+            for _, q in (self._queues or {}).values():    # ... and so may the native queues' (engine/native_queue.py)
                 q.close()
-            if getattr(self, "_queues", None):
+            if self._queues:
                 self._queues = {}
         return freed
+
+    # ---- load-time policies on the tower's own calibration batch ---------------------------------------------------------------
+    def _calibration_run(self):
+        """-> `run()`: pushes this tower's fixed, seeded calibration batch through it and returns the [n, D] embeddings"""
+        raise NotImplementedError(f"{type(self).__name__} has no calibration batch")
+
+    def tune_residual_default(self) -> str:
+        return self.tune_residual_stream(self._calibration_run())
+
+    def tune_fp8_default(self, budget: Optional[float] = None) -> int:
+        return self.tune_fp8(self._calibration_run(), budget=budget)
 
     # towers whose output is ONE row per item (class token / EOT): the last block's out-proj and MLP run on those rows only (towers.hip,
     # last_block_selected — in bf16, whatever the policy says), so of that block only the QKV GEMM (3 of its 12 W^2) can be e4m3 work at all
@@ -699,12 +514,53 @@ class _TowerBase:
         self._ops = L.load_torch_ops() if L.boundary() == "torch_ops" else None
         self._blobs = None
 
+    # ---- native request queues (engine/native_queue.py, csrc/queue.hip): the request threads' small calls share tower calls ----------------------
+    _queues: Optional[Dict[bool, tuple]] = None    # normalize -> (signature of cfg at creation, queue)
+    _queues_off = False
+
+    def _cached_queue(self, normalize: bool, make, what: str, *how):
+        """this tower's queue for `normalize`: `make(device index, normalize, *how)` at first use, again when the tower's policy fields have changed
+        since (a queue's scratch is sized from them); None once it could not be created (logged once; the direct path stays)"""
+        sig = bytes(self.cfg)
+        ent = (self._queues or {}).get(bool(normalize))
+        if ent is not None and ent[0] == sig:
+            return ent[1]
+        with self._lock:
+            if self._queues is None:
+                self._queues = {}
+            ent = self._queues.get(bool(normalize))
+            if ent is not None and ent[0] == sig:
+                return ent[1]
+            if ent is not None:
+                ent[1].close()
+            try:
+                q = make(self.device.index if self.device.index is not None else torch.cuda.current_device(), normalize, *how)
+            except (L.MarqoHipUnavailableError, L.MarqoHipError) as e:
+                self._queues_off = True
+                _log.warning("native request queue unavailable (%s); small %s calls keep the direct path", e, what)
+                return None
+            self._queues[bool(normalize)] = (sig, q)
+            return q
+
     def _forget_queue(self, q) -> None:
         """a native queue that was closed under a caller (engine/native_queue.gone): the next small call creates a fresh one"""
         with self._lock:
-            for k, ent in list((getattr(self, "_queues", None) or {}).items()):
+            for k, ent in list((self._queues or {}).items()):
                 if ent[1] is q:
                     del self._queues[k]
+
+    def _through_queue(self, q, encode, *args):
+        """encode(*args) on queue `q` -> its rows; None when the queue is gone (it is forgotten: the caller takes the direct path)"""
+        try:
+            return encode(*args)
+        except L.MarqoHipError as e:
+            if NQ.gone(e):
+                self._forget_queue(q)
+                return None
+            raise
+
+    def queue_stats(self) -> Dict[bool, Dict[str, int]]:
+        return {k: ent[1].stats() for k, ent in (self._queues or {}).items()}
 
     def _desc(self):
         """(cfg, weights) descriptors as the CPU byte tensors the custom ops take — zero-copy aliases of the ctypes structs"""
@@ -755,8 +611,7 @@ class _TowerBase:
                 g = self._graphs[key] = make()
             except RuntimeError as e:
                 self._graphs_off = True
-                import logging
-                logging.getLogger(__name__).warning("hipGraph capture failed (%s); this tower keeps launching eagerly", e)
+                _log.warning("hipGraph capture failed (%s); this tower keeps launching eagerly", e)
                 return None
         return g
 
@@ -782,7 +637,40 @@ class _TowerBase:
         return self._h.nbytes()
 
 
-class VitTower(_TowerBase):
+class _ImageTowerBase(_TowerBase):
+    """The image towers' front end: input checks, then calls of at most `max_images_per_call` images.  A tower supplies
+    `_image_workspace_bytes(m)` (scratch of one call of m images) and `_launch_images(kind, pixels, m, out, normalize, ws)` (that call)."""
+
+    def _run_chunks(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
+        """(inside the device context)"""
+        n = pixels.shape[0]
+        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
+        for i in range(0, n, self.max_images_per_call):
+            m = min(self.max_images_per_call, n - i)
+            ws = self._workspace(self._image_workspace_bytes(m))
+            self._launch_images(kind, pixels[i:i + m], m, out[i:i + m], normalize, ws)
+        return out
+
+    def _run(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
+        with torch.cuda.device(self.device):
+            return self._run_chunks(kind, pixels, normalize)
+
+    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
+        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
+        S = self.arch.image_size
+        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
+            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+        return self._run("u8", images_u8.to(self.device, non_blocking=True).contiguous(), normalize)
+
+    def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
+        """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
+        S = self.arch.image_size
+        if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
+            raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
+        return self._run("f32", pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous(), normalize)
+
+
+class VitTower(_ImageTowerBase):
     """CLIP ViT image tower (open_clip `visual.*` checkpoint tensors); arch.pool == "map": the timm SigLIP ViT behind open_clip's
     TimmModel (`visual.trunk.*`)."""
 
@@ -790,8 +678,7 @@ class VitTower(_TowerBase):
                  mean: Sequence[float] = OPENAI_DATASET_MEAN, std: Sequence[float] = OPENAI_DATASET_STD,
                  precision: str = "bf16"):
         super().__init__(device)
-        if precision not in ("bf16", "fp8"):
-            raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
+        _check_precision(precision)
         self.precision = precision
         self.arch = arch
         W, P = arch.width, arch.patch_size
@@ -907,9 +794,15 @@ class VitTower(_TowerBase):
         if precision == "bf16":
             self.tune_residual_default()
 
-    def tune_residual_default(self) -> str:
+    def _calibration_run(self):
         u8 = self.calibration_images()
-        return self.tune_residual_stream(lambda: self.encode_u8(u8))
+        return lambda: self.encode_u8(u8)
+
+    def _image_workspace_bytes(self, m: int) -> int:
+        return self.lib.mq_vit_workspace_bytes(C.byref(self.cfg), m)
+
+    def _launch_images(self, kind: str, pixels: Tensor, m: int, out: Tensor, normalize: bool, ws: Tensor) -> None:
+        self._call_image(kind, pixels, m, out, normalize, ws)
 
     def _run(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
         n = pixels.shape[0]
@@ -918,51 +811,23 @@ class VitTower(_TowerBase):
                 def make():
                     inp = torch.empty_like(pixels)
                     o = torch.empty(1, self.arch.out_dim, dtype=torch.float32, device=self.device)
-                    ws = torch.empty(self.lib.mq_vit_workspace_bytes(C.byref(self.cfg), 1) + 256, dtype=torch.uint8, device=self.device)
+                    ws = torch.empty(self._image_workspace_bytes(1) + 256, dtype=torch.uint8, device=self.device)
                     inp.copy_(pixels)
                     return _GraphedCall(self.device, inp, o, (ws,), lambda: self._call_image(kind, inp, 1, o, normalize, ws))
                 g = self._capture((pixels.dtype, bool(normalize)), make)
                 if g is not None:
                     return g(pixels)
-        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device), _large_call(self.device, n * self.arch.tokens):
-            for i in range(0, n, self.max_images_per_call):
-                m = min(self.max_images_per_call, n - i)
-                need = self.lib.mq_vit_workspace_bytes(C.byref(self.cfg), m)
-                ws = self._workspace(need)
-                self._call_image(kind, pixels[i:i + m], m, out[i:i + m], normalize, ws)
-        return out
-
-    # ---- native request queue (engine/native_queue.py, csrc/queue.hip): the request threads' small calls on preprocessed images share tower calls ----
-    _queues: Optional[Dict[bool, tuple]] = None
-    _queues_off = False
+            return self._run_chunks(kind, pixels, normalize)
 
     def _queue(self, normalize: bool) -> Optional["NQ.ImageQueue"]:
         """this tower's image queue for `normalize` (created at first use, re-created when the tower's policy fields have changed), or None"""
         if not NQ.ENABLED or NQ.IMAGE_REQUEST_MAX <= 0 or self._queues_off or (self._fp8 is not None and not self._fp8.calibrated):
             return None
-        sig = bytes(self.cfg)
-        ent = (self._queues or {}).get(bool(normalize))
-        if ent is not None and ent[0] == sig:
-            return ent[1]
-        with self._lock:
-            if self._queues is None:
-                self._queues = {}
-            ent = self._queues.get(bool(normalize))
-            if ent is not None and ent[0] == sig:
-                return ent[1]
-            if ent is not None:
-                ent[1].close()
-            try:
-                idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-                q = NQ.ImageQueue(self.lib, self.cfg, self.w, idx, self.arch.out_dim, bool(normalize))
-            except (L.MarqoHipUnavailableError, L.MarqoHipError) as e:
-                self._queues_off = True
-                import logging
-                logging.getLogger(__name__).warning("native request queue unavailable (%s); small image calls keep the direct path", e)
-                return None
-            self._queues[bool(normalize)] = (sig, q)
-            return q
+        return self._cached_queue(normalize, self._make_queue, "image")
+
+    def _make_queue(self, idx: int, normalize: bool) -> "NQ.ImageQueue":
+        return NQ.ImageQueue(self.lib, self.cfg, self.w, idx, self.arch.out_dim, bool(normalize))
 
     def queue_rows_images(self, tensors: Sequence[Tensor], normalize: bool = True) -> Optional[np.ndarray]:
         """the loaders' lean small-call path for preprocessed images: fp32 [3, S, S] device tensors (complete: the caller has seen their stream idle) ->
@@ -979,16 +844,7 @@ class VitTower(_TowerBase):
             if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != (3, S, S) or not t.is_contiguous():
                 return None
             ptrs.append(t.data_ptr())
-        try:
-            return q.encode_ptrs(ptrs)
-        except L.MarqoHipError as e:
-            if NQ.gone(e):
-                self._forget_queue(q)
-                return None
-            raise
-
-    def queue_stats(self) -> Dict[bool, Dict[str, int]]:
-        return {k: ent[1].stats() for k, ent in (self._queues or {}).items()}
+        return self._through_queue(q, q.encode_ptrs, ptrs)
 
     def calibration_images(self, n: int = 16, seed: int = 0) -> Tensor:
         """the fixed, seeded calibration batch of the fp8 policy: half uniform pixel noise, half smooth low-frequency fields plus
@@ -1001,26 +857,6 @@ class VitTower(_TowerBase):
         smooth = torch.nn.functional.interpolate(coarse, size=(S, S), mode="bilinear", align_corners=False)
         smooth = (smooth * 255 + 12 * torch.randn(smooth.shape, generator=g)).clamp(0, 255).permute(0, 2, 3, 1).to(torch.uint8)
         return torch.cat([noise, smooth], dim=0).contiguous().to(self.device)
-
-    def tune_fp8_default(self, budget: Optional[float] = None) -> int:
-        u8 = self.calibration_images()
-        return self.tune_fp8(lambda: self.encode_u8(u8), budget=budget)
-
-    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
-        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
-        S = self.arch.image_size
-        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
-            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-        images_u8 = images_u8.to(self.device, non_blocking=True).contiguous()
-        return self._run("u8", images_u8, normalize)
-
-    def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
-        """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
-        S = self.arch.image_size
-        if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
-            raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
-        pixels = pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        return self._run("f32", pixels, normalize)
 
 
 def _host_i64(t) -> np.ndarray:
@@ -1075,42 +911,31 @@ class _TextTowerBase(_TowerBase):
         """small host -> device copy through pinned memory (a pageable copy would synchronise the stream)"""
         return t.pin_memory().to(self.device, non_blocking=True)
 
-    # ---- native request queue (engine/native_queue.py, csrc/queue.hip): concurrent small calls of the request threads share tower calls ----------
-    _queues: Optional[Dict[bool, tuple]] = None
-    _queues_off = False
+    # ---- native request queue (_TowerBase._cached_queue): concurrent small calls of the request threads share tower calls ----------
     _active = 0                       # request-thread calls of the small-call path in flight on this tower
-    pool_first = False                # CLIP-form towers whose pooled row is each sequence's FIRST (NLLB: the language-code token), not its last
     _active_lock = threading.Lock()   # (class-wide: two increments)
+    pool_first = False                # CLIP-form towers whose pooled row is each sequence's FIRST (NLLB: the language-code token), not its last
+
+    def _small_call_enters(self) -> bool:
+        """count a request thread's small call in (its `finally` calls _small_call_leaves) -> True: no other one is in flight on this tower"""
+        with _TextTowerBase._active_lock:
+            self._active += 1
+            return self._active == 1
+
+    def _small_call_leaves(self) -> None:
+        with _TextTowerBase._active_lock:
+            self._active -= 1
 
     def _queue(self, normalize: bool, clip: bool) -> Optional["NQ.TextQueue"]:
-        """this tower's queue for `normalize` (created at first use, re-created when the tower's policy fields have changed since: its scratch is
-        sized from them), or None — switched off, or it could not be created (logged once; the direct path stays)"""
+        """this tower's queue for `normalize`, or None — switched off, or it could not be created"""
         if not NQ.ENABLED or self._queues_off or self.pool_first or (self._fp8 is not None and not self._fp8.calibrated):
             return None                   # (the native queue pools a CLIP-form tower's LAST rows)
-        sig = bytes(self.cfg)
-        ent = (self._queues or {}).get(bool(normalize))
-        if ent is not None and ent[0] == sig:
-            return ent[1]
-        with self._lock:
-            if self._queues is None:
-                self._queues = {}
-            ent = self._queues.get(bool(normalize))
-            if ent is not None and ent[0] == sig:
-                return ent[1]
-            if ent is not None:
-                ent[1].close()
-            try:
-                idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-                max_len = (self.arch.ctx + (1 if getattr(self.arch, "cls_embed", False) else 0)) if clip else self.arch.max_pos
-                q = NQ.TextQueue(self.lib, L.QUEUE_CLIP_TEXT if clip else L.QUEUE_BERT, self.cfg, self.w, idx,
-                                 self.arch.out_dim if clip else self.out_width, max_len, bool(normalize))
-            except (L.MarqoHipUnavailableError, L.MarqoHipError) as e:
-                self._queues_off = True
-                import logging
-                logging.getLogger(__name__).warning("native request queue unavailable (%s); small text calls keep the direct path", e)
-                return None
-            self._queues[bool(normalize)] = (sig, q)
-            return q
+        return self._cached_queue(normalize, self._make_queue, "text", clip)
+
+    def _make_queue(self, idx: int, normalize: bool, clip: bool) -> "NQ.TextQueue":
+        max_len = (self.arch.ctx + (1 if getattr(self.arch, "cls_embed", False) else 0)) if clip else self.arch.max_pos
+        return NQ.TextQueue(self.lib, L.QUEUE_CLIP_TEXT if clip else L.QUEUE_BERT, self.cfg, self.w, idx,
+                            self.arch.out_dim if clip else self.out_width, max_len, bool(normalize))
 
     def _small_call(self, ids_h: np.ndarray, lengths: np.ndarray, normalize: bool, clip: bool) -> Optional[Tensor]:
         """the request threads' small calls (loaders inside `request_stream`, host rows wanted): a LONE single-sequence call replays the captured
@@ -1119,9 +944,7 @@ class _TextTowerBase(_TowerBase):
         n = int(lengths.size)
         if not getattr(_request_tls, "host_output", False) or n < 1 or n > NQ.MAX_SEQS:
             return None
-        with _TextTowerBase._active_lock:
-            self._active += 1
-            alone = self._active == 1
+        alone = self._small_call_enters()
         try:
             if n == 1 and alone and self._graphs_ok():
                 one = self._encode_one(torch.from_numpy(ids_h[0, :int(lengths[0])]), normalize, clip)
@@ -1131,16 +954,10 @@ class _TextTowerBase(_TowerBase):
             if q is None or not q.takes(n, int(lengths.sum())):
                 return None
             packed, _ = _pack(ids_h, lengths)
-            try:
-                return torch.from_numpy(q.encode(packed.numpy(), lengths))
-            except L.MarqoHipError as e:
-                if NQ.gone(e):
-                    self._forget_queue(q)
-                    return None
-                raise
+            rows = self._through_queue(q, q.encode, packed.numpy(), lengths)
+            return None if rows is None else torch.from_numpy(rows)
         finally:
-            with _TextTowerBase._active_lock:
-                self._active -= 1
+            self._small_call_leaves()
 
     def queue_rows(self, ids_h: np.ndarray, lengths: np.ndarray, normalize: bool, clip: bool) -> Optional[np.ndarray]:
         """the loaders' LEAN small-call path — host ids in, host rows out, no stream context, no torch call, a handful of NumPy calls (with 16
@@ -1150,9 +967,7 @@ class _TextTowerBase(_TowerBase):
         n = int(lengths.size)
         if n < 1 or n > NQ.MAX_SEQS:
             return None
-        with _TextTowerBase._active_lock:
-            self._active += 1
-            alone = self._active == 1
+        alone = self._small_call_enters()
         try:
             if n == 1 and alone and not NQ.GRAPHS and self._graphs_ok():
                 return None                       # (MARQO_AMD_NATIVE_QUEUE_GRAPHS=0: the lone query replays the tower's own captured graph, through torch)
@@ -1160,19 +975,9 @@ class _TextTowerBase(_TowerBase):
             if q is None or not q.takes(n, int(lengths.sum())):
                 return None
             packed = ids_h[0, :int(lengths[0])] if n == 1 else ids_h[np.arange(ids_h.shape[1])[None, :] < lengths[:, None]]
-            try:
-                return q.encode_raw(np.ascontiguousarray(packed, dtype=np.int32), np.ascontiguousarray(lengths, dtype=np.int32), n)
-            except L.MarqoHipError as e:
-                if NQ.gone(e):
-                    self._forget_queue(q)
-                    return None
-                raise
+            return self._through_queue(q, q.encode_raw, np.ascontiguousarray(packed, dtype=np.int32), np.ascontiguousarray(lengths, dtype=np.int32), n)
         finally:
-            with _TextTowerBase._active_lock:
-                self._active -= 1
-
-    def queue_stats(self) -> Dict[bool, Dict[str, int]]:
-        return {k: ent[1].stats() for k, ent in (self._queues or {}).items()}
+            self._small_call_leaves()
 
     def _encode_one(self, src_ids: Tensor, normalize: bool, clip: bool) -> Optional[Tensor]:
         """ONE sequence (1-D ids of its real length, host or device) through the captured launch sequence of that token count
@@ -1212,19 +1017,33 @@ class _TextTowerBase(_TowerBase):
             one = self._encode_one(d_ids[0, :int(lengths[0])], normalize, clip)
             if one is not None:
                 return one
-        out_dim = self.arch.out_dim if clip else self.out_width
-        out = torch.empty(n, out_dim, dtype=torch.float32, device=self.device)
+
+        def stage(a: int, b: int):
+            cu_np = np.zeros(b - a + 1, dtype=np.int32)
+            np.cumsum(lengths[a:b], out=cu_np[1:])
+            cu = torch.from_numpy(cu_np)
+            d_cu = self._to_device(cu)
+            d_packed = torch.empty(int(cu_np[-1]), dtype=torch.int32, device=self.device)
+            L.check(self.lib.mq_pack_ids(d_ids[a:b].data_ptr(), S, d_cu.data_ptr(), b - a, d_packed.data_ptr(), self._stream()), "mq_pack_ids")
+            return d_packed, d_cu, cu, (d_cu if self.pool_first else None)   # (cu[s] = first row of s)
+        return self._encode_chunks(lengths, normalize, clip, stage)
+
+    def _stage_host(self, ids_h: np.ndarray, lengths: np.ndarray, a: int, b: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """sequences [a, b) of right-padded host ids: packed on the host, then ids and cu_seqlens through pinned memory -> (d_packed, d_cu, cu)"""
+        packed, cu = _pack(ids_h[a:b], lengths[a:b])
+        return self._to_device(packed), self._to_device(cu), cu
+
+    def _encode_chunks(self, lengths: np.ndarray, normalize: bool, clip: bool, stage) -> Tensor:
+        """The towers' call loop: one mq_encode_clip_text / mq_encode_bert call per `_chunks` range of sequences.  `stage(a, b)` brings that range's
+        ids to the device -> (d_packed int32 [rows], d_cu int32 [b - a + 1], cu (the same on the host), d_pool: the pooled row of each sequence
+        or None = its last)."""
+        out = torch.empty(int(lengths.size), self.arch.out_dim if clip else self.out_width, dtype=torch.float32, device=self.device)
+        ws_bytes = self.lib.mq_clip_text_workspace_bytes if clip else self.lib.mq_bert_workspace_bytes
         with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
             for a, b in self._chunks(lengths):
-                cu_np = np.zeros(b - a + 1, dtype=np.int32)
-                np.cumsum(lengths[a:b], out=cu_np[1:])
-                cu = torch.from_numpy(cu_np)
-                rows, nseq = int(cu_np[-1]), b - a
-                d_cu = self._to_device(cu)
-                d_packed = torch.empty(rows, dtype=torch.int32, device=self.device)
-                L.check(self.lib.mq_pack_ids(d_ids[a:b].data_ptr(), S, d_cu.data_ptr(), nseq, d_packed.data_ptr(), self._stream()), "mq_pack_ids")
-                need = (self.lib.mq_clip_text_workspace_bytes if clip else self.lib.mq_bert_workspace_bytes)(C.byref(self.cfg), rows, nseq)
-                self._call_text(clip, d_packed, d_cu, cu, nseq, d_cu if self.pool_first else None, out[a:b], normalize, self._workspace(need))   # (cu[s] = first row of s)
+                d_packed, d_cu, cu, d_pool = stage(a, b)
+                rows, nseq = d_packed.numel(), b - a
+                self._call_text(clip, d_packed, d_cu, cu, nseq, d_pool, out[a:b], normalize, self._workspace(ws_bytes(C.byref(self.cfg), rows, nseq)))
         return out
 
 
@@ -1233,8 +1052,7 @@ class ClipTextTower(_TextTowerBase):
 
     def __init__(self, arch: ClipTextArch, sd: Dict[str, Tensor], device: str, precision: str = "bf16"):
         super().__init__(device)
-        if precision not in ("bf16", "fp8"):
-            raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
+        _check_precision(precision)
         self.precision = precision
         self.arch = arch
         self.pools_one_row = True   # EOT (causal) / last (SigLIP) position
@@ -1296,9 +1114,9 @@ class ClipTextTower(_TextTowerBase):
         out[r[is_full], full + 1] = self.arch.vocab + 1
         return out
 
-    def tune_residual_default(self) -> str:
+    def _calibration_run(self):
         ids = self.calibration_ids()
-        return self.tune_residual_stream(lambda: self.encode_ids(ids))
+        return lambda: self.encode_ids(ids)
 
     def calibration_ids(self, n: int = 32, seed: int = 0) -> Tensor:
         """fixed, seeded calibration texts of the fp8 policy: int64 [n, ctx] rows SOT, L random ids, EOT, zero padding with L spread
@@ -1319,10 +1137,6 @@ class ClipTextTower(_TextTowerBase):
             ids[i, 1:1 + L_] = torch.randint(1, a.vocab - 2, (L_,), generator=g)
             ids[i, 1 + L_] = a.vocab - 1
         return ids
-
-    def tune_fp8_default(self, budget: Optional[float] = None) -> int:
-        ids = self.calibration_ids()
-        return self.tune_fp8(lambda: self.encode_ids(ids), budget=budget)
 
     def encode_ids(self, ids: Tensor, normalize: bool = True, pack: bool = True) -> Tensor:
         """ids: int [n, ctx] zero-padded CLIP token ids (SOT ... EOT 0 0 ...), host or device.
@@ -1351,19 +1165,13 @@ class ClipTextTower(_TextTowerBase):
             one = self._encode_one(torch.from_numpy(ids_h[0, :int(lengths[0])]), normalize, clip=True)
             if one is not None:
                 return one
-        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
-            for a, b in self._chunks(lengths):
-                packed, cu = _pack(ids_h[a:b], lengths[a:b])
-                pool_rows = None if pack else torch.from_numpy((cu.numpy()[:-1].astype(np.int64) + eot[a:b]).astype(np.int32))
-                d_ids = self._to_device(packed)
-                d_cu = self._to_device(cu)
-                d_pool = self._to_device(pool_rows) if pool_rows is not None else None
-                rows, nseq = packed.numel(), b - a
-                need = self.lib.mq_clip_text_workspace_bytes(C.byref(self.cfg), rows, nseq)
-                self._call_text(True, d_ids, d_cu, cu, nseq, d_pool, out[a:b], normalize, self._workspace(need))
-        return out
 
+        def stage(a: int, b: int):
+            d_packed, d_cu, cu = self._stage_host(ids_h, lengths, a, b)
+            if pack:
+                return d_packed, d_cu, cu, None
+            return d_packed, d_cu, cu, self._to_device(torch.from_numpy((cu.numpy()[:-1].astype(np.int64) + eot[a:b]).astype(np.int32)))   # the EOT rows
+        return self._encode_chunks(lengths, normalize, True, stage)
 
     def queue_rows_ids(self, ids_h: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
         """`queue_rows` for the tokeniser's [n, <= ctx] id matrix (SOT ... EOT 0 ...): each sequence up to its EOT, as encode_ids(pack=True) runs it.
@@ -1383,32 +1191,6 @@ class ClipTextTower(_TextTowerBase):
         return self._encode_device(d_ids, lengths, self.arch.ctx, normalize, clip=True)
 
 
-def nllb_clip_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
-    """The load-time transforms of the NLLB-CLIP text tower: open_clip HFTextEncoder / transformers M2M100Encoder tensors (`text.transformer.*`,
-    `text.proj.weight`) -> the CLIP text tower's own names (fp32), so that everything but the ReLU runs on what exists:
-      * token_embedding  = embed_tokens * sqrt(width)   (M2M100's embed_scale; row pad_id is never gathered: only un-padded rows run)
-      * positional_embedding [ctx, width] = the sinusoidal table from position pos_offset on (arch.position_table(): a non-persistent buffer)
-      * resblocks.N: q_proj | k_proj | v_proj packed into attn.in_proj_{weight, bias}; self_attn_layer_norm -> ln_1, final_layer_norm -> ln_2,
-        fc1 / fc2 -> mlp.c_fc / mlp.c_proj; the encoder's layer_norm -> ln_final; text_projection [width, out_dim] = proj.weight^T (no bias)."""
-    W, F = arch.width, arch.mlp_dim
-    t = "text.transformer."
-    f32 = lambda key, shape: _need(sd, key, shape).detach().to(torch.float32)
-    out = {"token_embedding.weight": f32(t + "embed_tokens.weight", (arch.vocab, W)) * math.sqrt(W),
-           "positional_embedding": arch.position_table(),
-           "ln_final.weight": f32(t + "layer_norm.weight", (W,)), "ln_final.bias": f32(t + "layer_norm.bias", (W,)),
-           "text_projection": f32("text.proj.weight", (arch.out_dim, W)).t().contiguous()}
-    for i in range(arch.layers):
-        p, o = f"{t}layers.{i}.", f"transformer.resblocks.{i}."
-        out[o + "attn.in_proj_weight"] = torch.cat([f32(p + f"self_attn.{n}_proj.weight", (W, W)) for n in "qkv"], dim=0)
-        out[o + "attn.in_proj_bias"] = torch.cat([f32(p + f"self_attn.{n}_proj.bias", (W,)) for n in "qkv"], dim=0)
-        for src, dst, shape in (("self_attn.out_proj", "attn.out_proj", (W, W)), ("fc1", "mlp.c_fc", (F, W)), ("fc2", "mlp.c_proj", (W, F))):
-            out[o + dst + ".weight"] = f32(p + src + ".weight", shape)
-            out[o + dst + ".bias"] = f32(p + src + ".bias", shape[:1])
-        for src, dst in (("self_attn_layer_norm", "ln_1"), ("final_layer_norm", "ln_2")):
-            out[o + dst + ".weight"], out[o + dst + ".bias"] = f32(p + src + ".weight", (W,)), f32(p + src + ".bias", (W,))
-    return out
-
-
 class NllbTextTower(_TextTowerBase):
     """NLLB-CLIP text tower (open_clip HFTextEncoder over the NLLB-200 / M2M100 encoder, `cls_pooler`, `linear` projection): the pre-LN bf16
     encoder with MQ_ACT_RELU behind mq_encode_clip_text — scaled token table, sinusoidal positions as the position table, no mask over the packed
@@ -1417,8 +1199,7 @@ class NllbTextTower(_TextTowerBase):
 
     def __init__(self, arch, sd: Dict[str, Tensor], device: str, precision: str = "bf16"):
         super().__init__(device)
-        if precision != "bf16":
-            raise ValueError(f"the NLLB text tower runs on bf16 operands only (its ReLU blocks have no e4m3 kernels), got precision {precision!r}")
+        _check_precision(precision, ("bf16",), f"the NLLB text tower runs on bf16 operands only (its ReLU blocks have no e4m3 kernels), got precision {precision!r}")
         if arch.width != arch.heads * 64:
             raise ValueError("the NLLB text tower runs 64-wide attention heads")
         self.precision = precision
@@ -1437,9 +1218,9 @@ class NllbTextTower(_TextTowerBase):
         self.cfg.enc.residual_stream = 2
         self.tune_residual_default()
 
-    def tune_residual_default(self) -> str:
+    def _calibration_run(self):
         ids = self.calibration_ids()
-        return self.tune_residual_stream(lambda: self.encode_ids(ids))
+        return lambda: self.encode_ids(ids)
 
     def calibration_ids(self, n: int = 32, seed: int = 0) -> Tensor:
         """fixed, seeded calibration rows of the residual-stream policy: int64 [n, ctx] = language-code id, random ids, </s>, <pad> padding, with
@@ -1473,15 +1254,11 @@ class NllbTextTower(_TextTowerBase):
             one = self._encode_one(torch.from_numpy(ids_h[0, :int(lengths[0])]), normalize, clip=True)
             if one is not None:
                 return one
-        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
-            for a, b in self._chunks(lengths):
-                packed, cu = _pack(ids_h[a:b], lengths[a:b])
-                d_ids, d_cu = self._to_device(packed), self._to_device(cu)
-                rows, nseq = packed.numel(), b - a
-                need = self.lib.mq_clip_text_workspace_bytes(C.byref(self.cfg), rows, nseq)
-                self._call_text(True, d_ids, d_cu, cu, nseq, d_cu, out[a:b], normalize, self._workspace(need))   # pooled rows = cu[s]: each sequence's first
-        return out
+
+        def stage(a: int, b: int):
+            d_packed, d_cu, cu = self._stage_host(ids_h, lengths, a, b)
+            return d_packed, d_cu, cu, d_cu   # pooled rows = cu[s]: each sequence's first
+        return self._encode_chunks(lengths, normalize, True, stage)
 
     encode_padded = encode_ids   # (the loaders' name for "rows padded to ctx", as on HfClipTextTower)
 
@@ -1500,8 +1277,7 @@ class BertTower(_TextTowerBase):
 
     def __init__(self, arch: BertArch, sd: Dict[str, Tensor], device: str, pooling: str = "mean", precision: str = "bf16"):
         super().__init__(device)
-        if precision not in ("bf16", "fp8"):
-            raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
+        _check_precision(precision)
         self.precision = precision
         self.arch = arch
         if pooling not in ("mean", "cls"):
@@ -1513,48 +1289,13 @@ class BertTower(_TextTowerBase):
         W, F = arch.width, arch.mlp_dim
         hd = _head_dim(W, arch.heads)
         h = self._h
-        arr = (L.BlockWeights * arch.layers)()
         new_model = arch.glu or arch.rope_theta is not None   # Alibaba-NLP NewModel naming (stella_en_400M_v5, gte-*-en-v1.5)
         if new_model and (precision != "bf16" or hd != _kernel_head_dim(hd, arch.heads)):
             raise ValueError("NewModel (rotary / gated-MLP) encoders run on the bf16 path with 64-wide heads")
         mpnet = arch.rel_buckets > 0   # MPNetModel naming: attention.attn.{q,k,v,o}, attention.LayerNorm, + one relative-position bias table
         if mpnet and (precision != "bf16" or hd != 64):
             raise ValueError("MPNet encoders (relative-position attention bias) run on the bf16 path with 64-wide heads")
-        # checkpoint key names of the attention sub-block: (q, k, v, out-projection, LayerNorm)
-        ak = ("attention.attn.q", "attention.attn.k", "attention.attn.v", "attention.attn.o", "attention.LayerNorm") if mpnet else \
-             ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense", "attention.output.LayerNorm")
-        for i in range(arch.layers):
-            p = f"encoder.layer.{i}."
-            b = arr[i]
-            if new_model:
-                qkv_w = _need(sd, p + "attention.qkv_proj.weight", (3 * W, W)).detach().float()
-                qkv_b = _need(sd, p + "attention.qkv_proj.bias", (3 * W,)).detach().float()
-                b.qkv_w, b.qkv_b = h.bf16(qkv_w), h.f32(qkv_b)
-                b.out_w = h.bf16(_need(sd, p + "attention.o_proj.weight", (W, W)))
-                b.out_b = h.f32(_need(sd, p + "attention.o_proj.bias", (W,)))
-                b.ln1_g, b.ln1_b = h.f32(_need(sd, p + "attn_ln.weight", (W,))), h.f32(_need(sd, p + "attn_ln.bias", (W,)))
-                b.fc1_w = h.bf16(_need(sd, p + "mlp.up_gate_proj.weight", (2 * F, W)))      # rows [0, F) = up, [F, 2F) = gate
-                b.fc1_b = h.f32(sd[p + "mlp.up_gate_proj.bias"]) if p + "mlp.up_gate_proj.bias" in sd else None
-                b.fc2_w = h.bf16(_need(sd, p + "mlp.down_proj.weight", (W, F)))
-                b.fc2_b = h.f32(_need(sd, p + "mlp.down_proj.bias", (W,)))
-                b.ln2_g, b.ln2_b = h.f32(_need(sd, p + "mlp_ln.weight", (W,))), h.f32(_need(sd, p + "mlp_ln.bias", (W,)))
-                continue
-            qkv_w = torch.cat([_need(sd, p + f"{n}.weight", (W, W)).detach().float() for n in ak[:3]], 0)
-            qkv_b = torch.cat([_need(sd, p + f"{n}.bias", (W,)).detach().float() for n in ak[:3]], 0)
-            out_w = _need(sd, p + ak[3] + ".weight", (W, W)).detach().float()
-            if hd != _kernel_head_dim(hd, arch.heads):  # e5-small / bge-small / MiniLM: 12 heads of 32
-                qkv_w, qkv_b, out_w = _pad_heads(qkv_w, qkv_b, out_w, arch.heads, hd)
-            b.qkv_w, b.qkv_b = h.bf16(qkv_w), h.f32(qkv_b)
-            b.out_w = h.bf16(out_w)
-            b.out_b = h.f32(_need(sd, p + ak[3] + ".bias", (W,)))
-            b.ln1_g = h.f32(_need(sd, p + ak[4] + ".weight", (W,)))
-            b.ln1_b = h.f32(_need(sd, p + ak[4] + ".bias", (W,)))
-            b.fc1_w = h.bf16(_need(sd, p + "intermediate.dense.weight", (F, W)))
-            b.fc1_b = h.f32(_need(sd, p + "intermediate.dense.bias", (F,)))
-            b.fc2_w = h.bf16(_need(sd, p + "output.dense.weight", (W, F)))
-            b.fc2_b = h.f32(_need(sd, p + "output.dense.bias", (W,)))
-            b.ln2_g = h.f32(_need(sd, p + "output.LayerNorm.weight", (W,)))
-            b.ln2_b = h.f32(_need(sd, p + "output.LayerNorm.bias", (W,)))
+        arr = _bert_blocks(h, sd, "", arch.layers, W, F, arch.heads, new_model=new_model, mpnet=mpnet)
         self._blocks = arr
         self.w = L.BertWeights(
             word_emb=h.f32(_need(sd, "embeddings.word_embeddings.weight", (arch.vocab, W))),
@@ -1590,8 +1331,11 @@ class BertTower(_TextTowerBase):
         if self.arch.glu or self.arch.rope_theta is not None:
             self.cfg.enc.residual_stream, self.residual_stream = 2, "fp32"
             return self.residual_stream
+        return super().tune_residual_default()
+
+    def _calibration_run(self):
         ids, mask = self.calibration_batch()
-        return self.tune_residual_stream(lambda: self.encode_ids(ids, mask))
+        return lambda: self.encode_ids(ids, mask)
 
     @property
     def out_width(self) -> int:
@@ -1612,10 +1356,6 @@ class BertTower(_TextTowerBase):
             ids[i, 0], ids[i, L_ - 1] = (101, 102) if a.vocab > 102 and a.pos_offset == 0 else (0, 2)
             mask[i, :L_] = 1
         return ids, mask
-
-    def tune_fp8_default(self, budget: Optional[float] = None) -> int:
-        ids, mask = self.calibration_batch()
-        return self.tune_fp8(lambda: self.encode_ids(ids, mask), budget=budget)
 
     def encode_ids(self, ids: Tensor, attention_mask: Tensor, normalize: bool = True) -> Tensor:
         """ids / attention_mask: int [n, S] as produced by the HF tokenizer call of the reference
@@ -1640,16 +1380,7 @@ class BertTower(_TextTowerBase):
             one = self._encode_one(torch.from_numpy(ids_h[0, :int(lengths[0])]), normalize, clip=False)
             if one is not None:
                 return one
-        out = torch.empty(n, self.out_width, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
-            for a, b in self._chunks(lengths):
-                packed, cu = _pack(ids_h[a:b], lengths[a:b])
-                d_ids = self._to_device(packed)
-                d_cu = self._to_device(cu)
-                rows, nseq = packed.numel(), b - a
-                need = self.lib.mq_bert_workspace_bytes(C.byref(self.cfg), rows, nseq)
-                self._call_text(False, d_ids, d_cu, cu, nseq, None, out[a:b], normalize, self._workspace(need))
-        return out
+        return self._encode_chunks(lengths, normalize, False, lambda a, b: (*self._stage_host(ids_h, lengths, a, b), None))
 
     def queue_rows_ids(self, ids_h: np.ndarray, mask_h: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
         """`queue_rows` for the tokeniser's right-padded [n, S] ids + attention mask (the engine's own tokenisers: the mask is a prefix of ones by
@@ -1726,57 +1457,47 @@ class MclipTextTower(BertTower):
             self.tune_residual_default()
 
 
+class _ConvTowerBase(_ImageTowerBase):
+    """What the convolutional image towers share: bf16 only, one mq_encode_<name>_{u8, f32} call per chunk of images, the chunk sized from a
+    workspace budget; the small-call native queue does not take these towers (small `.preprocess` calls take the regular path)."""
+
+    has_native_queue = False
+
+    def _bind_kernels(self, workspace_bytes, encode_u8, encode_f32, family: str, budget: int) -> None:
+        """the tower's three entry points of the built library, and the images one call may take inside `budget` bytes of scratch"""
+        self._workspace_bytes, self._encode = workspace_bytes, {"u8": encode_u8, "f32": encode_f32}
+        self._encode_name = f"mq_encode_{family.lower()}"
+        per_image = self._image_workspace_bytes(1)
+        if per_image == 0:
+            raise ValueError(f"{family} configuration not supported by the kernels: {self.arch}")
+        self.max_images_per_call = max(1, min(65535, int(budget) // per_image))
+
+    def _image_workspace_bytes(self, m: int) -> int:
+        return self._workspace_bytes(C.byref(self.cfg), m)
+
+    def _launch_images(self, kind: str, pixels: Tensor, m: int, out: Tensor, normalize: bool, ws: Tensor) -> None:
+        L.check(self._encode[kind](C.byref(self.cfg), C.byref(self.w), pixels.data_ptr(), m, out.data_ptr(), 1 if normalize else 0,
+                                   ws.data_ptr(), ws.numel(), self._stream()), self._encode_name)
+
+    def queue_rows_images(self, tensors: Sequence[Tensor], normalize: bool = True) -> Optional[np.ndarray]:
+        return None
+
+
 # ---- ConvNeXt image towers (csrc/convnext.hip) ------------------------------------------------------------------------------------------------
-# Load-time folds, as pure CPU-tensor functions (tests/test_convnext_host.py checks them against the unfolded fp32 computation).
-
-def convnext_dw_taps(conv_dw_w: Tensor) -> Tensor:
-    """conv_dw.weight [C, 1, 7, 7] -> fp32 [49, C] (tap-major: one tap's C channels are contiguous, as the kernel stages them)"""
-    C = conv_dw_w.shape[0]
-    return conv_dw_w.detach().to(torch.float32).reshape(C, 49).t().contiguous()
-
-
-def convnext_fold_ln_fc1(fc1_w: Tensor, fc1_b: Tensor, ln_g: Tensor, ln_b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-    """The block's LayerNorm folded into fc1 (mq_gemm_bf16_ln): LN(x) @ W^T + b = rstd * (x @ (g*W)^T - mean * colsum) + (b + W @ beta)
-    -> (bf16 g*W [4C, C], fp32 bias [4C], fp32 colsum of the ROUNDED folded weight [4C])"""
-    w32 = fc1_w.detach().to(torch.float32)
-    wf = (w32 * ln_g.detach().to(torch.float32).unsqueeze(0)).to(torch.bfloat16)
-    return wf, fc1_b.detach().to(torch.float32) + w32 @ ln_b.detach().to(torch.float32), wf.to(torch.float32).sum(dim=1)
-
-
-def convnext_fold_gamma_fc2(fc2_w: Tensor, fc2_b: Tensor, gamma: Tensor) -> Tuple[Tensor, Tensor]:
-    """gamma * (h @ W^T + b) = h @ (gamma[:, None] * W)^T + gamma * b  -> (fp32 weight [C, 4C], fp32 bias [C])"""
-    g = gamma.detach().to(torch.float32)
-    return fc2_w.detach().to(torch.float32) * g.unsqueeze(1), fc2_b.detach().to(torch.float32) * g
-
-
-def convnext_downsample_weight(w: Tensor) -> Tensor:
-    """downsample.1.weight [C_out, C_in, 2, 2] -> fp32 [C_out, 4 C_in] with columns in (ky, kx, c) order: the gather copies whole pixels"""
-    return w.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
-
-
-def convnext_downsample_gather(x_nhwc: Tensor) -> Tensor:
-    """the gather mq_convnext_downsample performs (without its LayerNorm), in torch: [n, H, W, C] -> [n (H/2) (W/2), 4 C], (ky, kx, c) columns"""
-    n, H, W, C = x_nhwc.shape
-    return x_nhwc.reshape(n, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(n * (H // 2) * (W // 2), 4 * C)
-
-
 # scratch one call may use: a larger batch is split into calls of at most this many bytes of workspace (stage 0 sizes it: ~6 MB per 256 px image of
 # convnext_base_w, ~18 MB of convnext_xxlarge)
 CONVNEXT_WORKSPACE_BYTES = _env_int("MARQO_AMD_CONVNEXT_WORKSPACE_MB", 4096) << 20
 
 
-class ConvNextTower(_TowerBase):
+class ConvNextTower(_ConvTowerBase):
     """open_clip ConvNeXt image tower (timm trunk under `visual.trunk.*`, projection head under `visual.head.*`), one mq_encode_convnext_* call
-    per chunk of images.  bf16 only; the small-call native queue does not take these towers."""
-
-    has_native_queue = False
+    per chunk of images."""
 
     def __init__(self, arch, sd: Dict[str, Tensor], device: str, mean: Sequence[float] = OPENAI_DATASET_MEAN,
                  std: Sequence[float] = OPENAI_DATASET_STD, precision: str = "bf16", max_workspace_bytes: Optional[int] = None):
-        if precision != "bf16":
-            raise ValueError(f"ConvNeXt towers run in bf16 only (engine_precision {precision!r} is not supported for convnext_* models)")
+        _check_precision(precision, ("bf16",), f"ConvNeXt towers run in bf16 only (engine_precision {precision!r} is not supported for convnext_* models)")
         super().__init__(device)
-        self.precision, self.arch, self._fp8 = precision, arch, None
+        self.precision, self.arch = precision, arch
         h, t, dims = self._h, "visual.trunk.", arch.dims
         f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
         C0 = dims[0]
@@ -1820,123 +1541,23 @@ class ConvNextTower(_TowerBase):
         self.w = w
         self.cfg = L.ConvNextCfg(image_size=arch.image_size, depths=(C.c_int32 * 4)(*arch.depths), dims=(C.c_int32 * 4)(*dims),
                                  ln_eps=arch.ln_eps, head=head, out_dim=E, mean=(C.c_float * 3)(*mean), std=(C.c_float * 3)(*std))
-        per_image = self.lib.mq_convnext_workspace_bytes(C.byref(self.cfg), 1)
-        if per_image == 0:
-            raise ValueError(f"ConvNeXt configuration not supported by the kernels: {arch}")
-        budget = CONVNEXT_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
-        self.max_images_per_call = max(1, min(65535, budget // per_image))
-
-    def release_unused_folded(self) -> int:
-        return 0   # (the folded fc1 / fc2 copies are the only copies the blocks hold)
-
-    def queue_rows_images(self, tensors: Sequence[Tensor], normalize: bool = True) -> Optional[np.ndarray]:
-        return None   # small `.preprocess` calls take the regular path
-
-    def _run(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
-        n = pixels.shape[0]
-        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
-        fn = self.lib.mq_encode_convnext_u8 if kind == "u8" else self.lib.mq_encode_convnext_f32
-        with torch.cuda.device(self.device):
-            for i in range(0, n, self.max_images_per_call):
-                m = min(self.max_images_per_call, n - i)
-                ws = self._workspace(self.lib.mq_convnext_workspace_bytes(C.byref(self.cfg), m))
-                L.check(fn(C.byref(self.cfg), C.byref(self.w), pixels[i:i + m].data_ptr(), m, out[i:i + m].data_ptr(), 1 if normalize else 0,
-                           ws.data_ptr(), ws.numel(), self._stream()), "mq_encode_convnext")
-        return out
-
-    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
-        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
-        S = self.arch.image_size
-        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
-            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-        return self._run("u8", images_u8.to(self.device, non_blocking=True).contiguous(), normalize)
-
-    def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
-        """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
-        S = self.arch.image_size
-        if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
-            raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
-        return self._run("f32", pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous(), normalize)
+        self._bind_kernels(self.lib.mq_convnext_workspace_bytes, self.lib.mq_encode_convnext_u8, self.lib.mq_encode_convnext_f32, "ConvNeXt",
+                           CONVNEXT_WORKSPACE_BYTES if max_workspace_bytes is None else max_workspace_bytes)
 
 
 # ---- ResNet CLIP image towers (csrc/resnet.hip) -------------------------------------------------------------------------------------------------
-RESNET_BN_EPS = 1e-5
-
-
-def resnet_pad64(c: int) -> int:
-    """channel count as the tower stores it: zero-padded to a multiple of 64 (the tiled GEMMs' k-step)"""
-    return (c + 63) // 64 * 64
-
-
-def resnet_fold_bn(conv_w: Tensor, bn_w: Tensor, bn_b: Tensor, bn_mean: Tensor, bn_var: Tensor, eps: float = RESNET_BN_EPS) -> Tuple[Tensor, Tensor]:
-    """conv (no bias) followed by eval-mode BatchNorm -> one conv with a bias: w' = w * g / sqrt(var + eps) per output channel, b' = beta - mean * that"""
-    s = bn_w.double() / torch.sqrt(bn_var.double() + eps)
-    w = (conv_w.double() * s.view(-1, *([1] * (conv_w.dim() - 1)))).float()
-    return w, (bn_b.double() - bn_mean.double() * s).float()
-
-
-def resnet_conv3x3_weight(w: Tensor, cin: int, cout: int) -> Tensor:
-    """[O, I, 3, 3] -> fp32 [cout, Kp]: column (ky * 3 + kx) * cin + c (mq_resnet_conv3x3), zero-padded to cin input / cout output channels and to
-    Kp = 9 cin rounded up to a multiple of 64"""
-    O, I = w.shape[:2]
-    full = torch.zeros(cout, 3, 3, cin, dtype=torch.float32)
-    full[:O, :, :, :I] = w.permute(0, 2, 3, 1).float()
-    Kp = (9 * cin + 63) // 64 * 64
-    out = torch.zeros(cout, Kp, dtype=torch.float32)
-    out[:, :9 * cin] = full.reshape(cout, 9 * cin)
-    return out
-
-
-def resnet_conv1x1_weight(w: Tensor, cin: int, cout: int) -> Tensor:
-    """[O, I, 1, 1] -> fp32 [cout, cin], zero-padded"""
-    O, I = w.shape[:2]
-    out = torch.zeros(cout, cin, dtype=torch.float32)
-    out[:O, :I] = w.reshape(O, I).float()
-    return out
-
-
-def resnet_stem_weight(w: Tensor) -> Tensor:
-    """visual.conv1 [O, 3, 3, 3] -> fp32 [O, 64]: column (ky * 3 + kx) * 3 + c (mq_resnet_stem_gather's patch rows), zero past 27"""
-    out = torch.zeros(w.shape[0], 64, dtype=torch.float32)
-    out[:, :27] = w.permute(0, 2, 3, 1).reshape(w.shape[0], 27).float()
-    return out
-
-
-def resnet_pad_vec(v: Tensor, n: int) -> Tensor:
-    out = torch.zeros(n, dtype=torch.float32)
-    out[:v.numel()] = v.float()
-    return out
-
-
-def resnet_attnpool_weights(sd: Dict[str, Tensor], arch) -> Dict[str, Tensor]:
-    """visual.attnpool.* -> the fp32 operands of the tower's attention pool (mq_resnet_weights): positions [T, C]; q_proj with the 64^-0.5 softmax
-    scale folded into weight and bias (a power of two: the folded weight rounds to bf16 exactly as the unscaled one); k_proj and v_proj stacked into
-    one [2C, C] projection; c_proj"""
-    Cw, T, E, ap = 32 * arch.width, arch.tokens, arch.out_dim, "visual.attnpool."
-    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
-    scale = 64 ** -0.5
-    return {"pos": f32(ap + "positional_embedding", (T, Cw)),
-            "q_w": f32(ap + "q_proj.weight", (Cw, Cw)) * scale, "q_b": f32(ap + "q_proj.bias", (Cw,)) * scale,
-            "kv_w": torch.cat([f32(ap + "k_proj.weight", (Cw, Cw)), f32(ap + "v_proj.weight", (Cw, Cw))]),
-            "kv_b": torch.cat([f32(ap + "k_proj.bias", (Cw,)), f32(ap + "v_proj.bias", (Cw,))]),
-            "c_w": f32(ap + "c_proj.weight", (E, Cw)), "c_b": f32(ap + "c_proj.bias", (E,))}
-
-
 RESNET_WORKSPACE_BYTES = _env_int("MARQO_AMD_RESNET_WORKSPACE_MB", 4096) << 20
 
 
-class ResNetTower(_TowerBase):
+class ResNetTower(_ConvTowerBase):
     """OpenAI CLIP / open_clip ModifiedResNet image tower (`visual.*`), one mq_encode_resnet_* call per chunk of images.  Every BatchNorm is
-    folded into the convolution in front of it at load; bf16 only; the small-call native queue does not take these towers."""
-
-    has_native_queue = False
+    folded into the convolution in front of it at load."""
 
     def __init__(self, arch, sd: Dict[str, Tensor], device: str, mean: Sequence[float] = OPENAI_DATASET_MEAN,
                  std: Sequence[float] = OPENAI_DATASET_STD, precision: str = "bf16", max_workspace_bytes: Optional[int] = None):
-        if precision != "bf16":
-            raise ValueError(f"ResNet towers run in bf16 only (engine_precision {precision!r} is not supported for RN* models)")
+        _check_precision(precision, ("bf16",), f"ResNet towers run in bf16 only (engine_precision {precision!r} is not supported for RN* models)")
         super().__init__(device)
-        self.precision, self.arch, self._fp8 = precision, arch, None
+        self.precision, self.arch = precision, arch
         h, v, w0 = self._h, "visual.", arch.width
         f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
 
@@ -1982,40 +1603,5 @@ class ResNetTower(_TowerBase):
         self.w = w
         self.cfg = L.ResNetCfg(image_size=arch.image_size, layers=(C.c_int32 * 4)(*arch.layers), width=w0, heads=arch.heads, out_dim=E,
                                mean=(C.c_float * 3)(*mean), std=(C.c_float * 3)(*std))
-        per_image = self.lib.mq_resnet_workspace_bytes(C.byref(self.cfg), 1)
-        if per_image == 0:
-            raise ValueError(f"ResNet configuration not supported by the kernels: {arch}")
-        budget = RESNET_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
-        self.max_images_per_call = max(1, min(65535, budget // per_image))
-
-    def release_unused_folded(self) -> int:
-        return 0   # (the folded convolutions are the only copies the blocks hold)
-
-    def queue_rows_images(self, tensors: Sequence[Tensor], normalize: bool = True) -> Optional[np.ndarray]:
-        return None   # small `.preprocess` calls take the regular path
-
-    def _run(self, kind: str, pixels: Tensor, normalize: bool) -> Tensor:
-        n = pixels.shape[0]
-        out = torch.empty(n, self.arch.out_dim, dtype=torch.float32, device=self.device)
-        fn = self.lib.mq_encode_resnet_u8 if kind == "u8" else self.lib.mq_encode_resnet_f32
-        with torch.cuda.device(self.device):
-            for i in range(0, n, self.max_images_per_call):
-                m = min(self.max_images_per_call, n - i)
-                ws = self._workspace(self.lib.mq_resnet_workspace_bytes(C.byref(self.cfg), m))
-                L.check(fn(C.byref(self.cfg), C.byref(self.w), pixels[i:i + m].data_ptr(), m, out[i:i + m].data_ptr(), 1 if normalize else 0,
-                           ws.data_ptr(), ws.numel(), self._stream()), "mq_encode_resnet")
-        return out
-
-    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
-        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
-        S = self.arch.image_size
-        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
-            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-        return self._run("u8", images_u8.to(self.device, non_blocking=True).contiguous(), normalize)
-
-    def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
-        """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
-        S = self.arch.image_size
-        if pixels.ndim != 4 or tuple(pixels.shape[1:]) != (3, S, S):
-            raise ValueError(f"expected float [n, 3, {S}, {S}], got {tuple(pixels.shape)}")
-        return self._run("f32", pixels.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous(), normalize)
+        self._bind_kernels(self.lib.mq_resnet_workspace_bytes, self.lib.mq_encode_resnet_u8, self.lib.mq_encode_resnet_f32, "ResNet",
+                           RESNET_WORKSPACE_BYTES if max_workspace_bytes is None else max_workspace_bytes)

@@ -32,7 +32,7 @@ def _ln_gemm(lib, xb, wf, bf, colsum, out, flags, eps):
 
 
 def _folded(W, b, gam, bet):
-    """what the loader precomputes (engine/towers.py::_clip_blocks)"""
+    """what the loader precomputes (engine/tower_weights.py::_clip_blocks)"""
     wf = (W * gam.unsqueeze(0)).to(torch.bfloat16)
     return wf, (b + W @ bet).contiguous(), wf.float().sum(1).contiguous()
 

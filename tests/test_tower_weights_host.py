@@ -1,0 +1,154 @@
+"""engine/tower_weights.py on the CPU: the one LayerNorm fold, and the block loaders over `synthetic` state dicts on a CPU _Holder — every folded tensor
+a block holds must be the fold of the tensors that block really runs (head- / MLP-padded where the loader pads).  No GPU is needed."""
+import ctypes
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from marqo_amd.engine import archs, synthetic, tower_weights as TW, towers
+
+CPU = torch.device("cpu")
+
+
+def _plain_fold(w32, b32, gamma, beta):
+    wf = (w32 * gamma.unsqueeze(0)).to(torch.bfloat16)
+    sf = wf.to(torch.float32).sum(dim=1)       # over the ROUNDED weight
+    bf = b32 + w32 @ beta
+    return wf, bf, sf
+
+
+def test_fold_layernorm_is_the_three_line_restatement_exactly():
+    g = torch.Generator().manual_seed(0)
+    for n, k in ((384, 128), (200, 160), (64, 64)):
+        w, b, gam, bet = torch.randn(n, k, generator=g), torch.randn(n, generator=g), torch.randn(k, generator=g), torch.randn(k, generator=g)
+        got, want = TW.fold_layernorm(w, b, gam, bet), _plain_fold(w, b, gam, bet)
+        assert [t.dtype for t in got] == [torch.bfloat16, torch.float32, torch.float32]
+        for a, e in zip(got, want):
+            assert a.dtype == e.dtype and torch.equal(a, e)
+        # the column sum is NOT the sum of the unrounded product
+        assert not torch.equal(got[2], (w * gam.unsqueeze(0)).sum(dim=1))
+    assert towers.fold_layernorm is TW.fold_layernorm and towers.convnext_fold_ln_fc1 is TW.convnext_fold_ln_fc1
+    for a, e in zip(TW.convnext_fold_ln_fc1(w, b, gam, bet), TW.fold_layernorm(w, b, gam, bet)):
+        assert torch.equal(a, e)
+
+
+def test_fold_layernorm_matches_the_unfolded_linear_of_a_layernorm():
+    """the bf16-exact setting and the tolerances of tests/test_convnext_host.py::test_fold_ln_into_fc1_matches_unfolded"""
+    g = torch.Generator().manual_seed(0)
+    C, R, eps = 256, 64, 1e-6
+    W = torch.randn(4 * C, C, generator=g).to(torch.bfloat16).float() / 16
+    b = torch.randn(4 * C, generator=g)
+    ln_g = 2.0 ** torch.randint(-2, 3, (C,), generator=g).float()
+    ln_b = torch.randn(C, generator=g)
+    x = 1.5 + torch.randn(R, C, generator=g)
+    ref = F.linear(F.layer_norm(x, (C,), ln_g, ln_b, eps), W, b)
+    wf, bf, sf = TW.fold_layernorm(W, b, ln_g, ln_b)
+    assert wf.dtype == torch.bfloat16
+    mean = x.mean(1, keepdim=True)
+    rstd = torch.rsqrt(x.var(1, unbiased=False, keepdim=True) + eps)
+    out = rstd * (x @ wf.float().t() - mean * sf) + bf
+    torch.testing.assert_close(out, ref, rtol=1e-5, atol=1e-4)
+
+
+def _fields(h, block):
+    """field name -> the holder tensor a block's pointer field points at"""
+    by_ptr = {t.data_ptr(): t for t in h.tensors}
+    return {f: by_ptr[getattr(block, f)] for f, ty in block._fields_ if ty is ctypes.c_void_p and getattr(block, f)}
+
+
+def _assert_fold(fields, name, w32, b32, gamma, beta):
+    wf, bf, sf = TW.fold_layernorm(w32, b32, gamma, beta)
+    assert torch.equal(fields[name + "_wf"], wf) and fields[name + "_wf"].dtype == torch.bfloat16
+    assert torch.equal(fields[name + "_bf"], bf) and torch.equal(fields[name + "_sf"], sf)
+    assert fields[name + "_wf"].shape == fields[name + "_w"].shape       # the fold of what the block runs, not of the checkpoint tensor
+
+
+@pytest.mark.parametrize("case", ["open_clip", "timm", "padded_heads", "padded_mlp"])
+def test_clip_blocks_fold_the_tensors_the_block_runs(case):
+    assert TW.LN_FOLD
+    W, heads, mlp, pool = {"open_clip": (128, 2, 256, "cls"), "timm": (128, 2, 256, "map"), "padded_heads": (160, 2, 640, "cls"),
+                           "padded_mlp": (128, 2, 200, "cls")}[case]
+    arch = archs.VitArch(32, 16, W, 2, heads, mlp, W if pool == "map" else 64, pool=pool)
+    sd = synthetic.random_open_clip_state_dict(vision=arch, seed=3)
+    keys, prefix = (TW._TIMM_KEYS, "visual.trunk.") if pool == "map" else (TW._OPEN_CLIP_KEYS, "visual.transformer.")
+    h = TW._Holder(CPU)
+    arr = TW._clip_blocks(h, sd, prefix, 2, W, mlp, heads, keys=keys)
+    assert len(h.tensors) == 2 * 18
+    d = W // heads
+    for i in range(2):
+        p = prefix + keys["block"].format(i)
+        f = _fields(h, arr[i])
+        qkv_w, qkv_b, out_w = sd[p + keys["qkv_w"]], sd[p + keys["qkv_b"]], sd[p + keys["out"] + ".weight"]
+        if case == "padded_heads":                      # 80-wide heads run as 96
+            qkv_w, qkv_b, out_w = TW._pad_heads(qkv_w, qkv_b, out_w, heads, d)
+            assert qkv_w.shape == (3 * heads * 96, W)
+        fc1_w, fc1_b, fc2_w = TW._pad_mlp(sd[p + keys["fc1"] + ".weight"], sd[p + keys["fc1"] + ".bias"], sd[p + keys["fc2"] + ".weight"])
+        assert fc1_w.shape[0] == (256 if case == "padded_mlp" else mlp)
+        assert torch.equal(f["qkv_w"], qkv_w.to(torch.bfloat16)) and torch.equal(f["qkv_b"], qkv_b.float())
+        assert torch.equal(f["out_w"], out_w.to(torch.bfloat16))
+        assert torch.equal(f["fc1_w"], fc1_w.to(torch.bfloat16)) and torch.equal(f["fc2_w"], fc2_w.to(torch.bfloat16))
+        _assert_fold(f, "qkv", qkv_w.float(), qkv_b.float(), sd[p + keys["ln1"] + ".weight"], sd[p + keys["ln1"] + ".bias"])
+        _assert_fold(f, "fc1", fc1_w.float(), fc1_b.float(), sd[p + keys["ln2"] + ".weight"], sd[p + keys["ln2"] + ".bias"])
+
+
+@pytest.mark.parametrize("sub_ln", [True, False])
+def test_eva_blocks_fold_the_tensors_the_block_runs(sub_ln):
+    assert TW.LN_FOLD and TW.EVA_GLU_EPILOGUE
+    W, heads, Fd, Fp = 128, 2, 344, 384
+    arch = archs.VitArch(32, 16, W, 2, heads, Fd, 64, eva=True, ln_eps=1e-6)
+    sd = synthetic.random_open_clip_state_dict(vision=arch, seed=4)
+    if not sub_ln:
+        sd = {k: v for k, v in sd.items() if ".attn.norm." not in k and ".mlp.norm." not in k}
+    h = TW._Holder(CPU)
+    arr = TW._eva_blocks(h, sd, "visual.trunk.", 2, W, Fd, heads)
+    assert len(h.tensors) == 2 * (28 if sub_ln else 18)
+    pad = F.pad
+    for i in range(2):
+        p = f"visual.trunk.blocks.{i}."
+        f = _fields(h, arr[i])
+        # the tensors the block runs, read back from the holder where they are fp32, rebuilt from the checkpoint where the holder keeps bf16
+        qkv_w = torch.cat([sd[p + "attn.q_proj.weight"], sd[p + "attn.k_proj.weight"], sd[p + "attn.v_proj.weight"]], dim=0)
+        assert torch.equal(f["qkv_w"], qkv_w.to(torch.bfloat16))
+        assert torch.equal(f["qkv_b"], torch.cat([sd[p + "attn.q_proj.bias"], torch.zeros(W), sd[p + "attn.v_proj.bias"]]))   # (keys carry no bias)
+        _assert_fold(f, "qkv", qkv_w, f["qkv_b"], sd[p + "norm1.weight"], sd[p + "norm1.bias"])
+        il = lambda u, g_: torch.stack([u.reshape(Fp // 16, 16, *u.shape[1:]), g_.reshape(Fp // 16, 16, *g_.shape[1:])], dim=1).reshape(2 * Fp, *u.shape[1:])
+        fc1_w = il(pad(sd[p + "mlp.fc1_x.weight"], (0, 0, 0, Fp - Fd)), pad(sd[p + "mlp.fc1_g.weight"], (0, 0, 0, Fp - Fd)))
+        assert torch.equal(f["fc1_w"], fc1_w.to(torch.bfloat16)) and f["fc1_b"].shape == (2 * Fp,)
+        _assert_fold(f, "fc1", fc1_w, f["fc1_b"], sd[p + "norm2.weight"], sd[p + "norm2.bias"])
+        if sub_ln:
+            _assert_fold(f, "out", sd[p + "attn.proj.weight"], sd[p + "attn.proj.bias"], sd[p + "attn.norm.weight"], sd[p + "attn.norm.bias"])
+            fc2_w = pad(sd[p + "mlp.fc2.weight"], (0, Fp - Fd))
+            assert torch.equal(f["fc2_w"], fc2_w.to(torch.bfloat16)) and torch.equal(f["mlp_ln_g"], pad(sd[p + "mlp.norm.weight"], (0, Fp - Fd)))
+            _assert_fold(f, "fc2", fc2_w, sd[p + "mlp.fc2.bias"], f["mlp_ln_g"], f["mlp_ln_b"])
+        else:
+            assert not {"out_wf", "fc2_wf", "attn_ln_g", "mlp_ln_g"} & set(f)
+
+
+def test_bert_blocks_hand_over_padded_heads_and_fold_nothing():
+    arch = archs.BertArch(vocab=300, max_pos=64, width=384, layers=2, heads=12, mlp_dim=1536)     # e5-small: 12 heads of 32, run as 64
+    sd = synthetic.random_bert_state_dict(arch, seed=5)
+    h = TW._Holder(CPU)
+    arr = TW._bert_blocks(h, sd, "", arch.layers, arch.width, arch.mlp_dim, arch.heads)
+    assert len(h.tensors) == 2 * 12
+    W = arch.width
+    for i in range(2):
+        p = f"encoder.layer.{i}.attention."
+        f = _fields(h, arr[i])
+        assert not [k for k in f if k.endswith(("_wf", "_sf", "_bf"))]                             # post-LN: no LayerNorm in front of a GEMM
+        qkv_w = torch.cat([sd[p + f"self.{n}.weight"] for n in ("query", "key", "value")], 0)
+        qkv_b = torch.cat([sd[p + f"self.{n}.bias"] for n in ("query", "key", "value")], 0)
+        qkv_w2, qkv_b2, out_w2 = TW._pad_heads(qkv_w, qkv_b, sd[p + "output.dense.weight"], arch.heads, 32)
+        assert qkv_w2.shape == (3 * 12 * 64, W) and out_w2.shape == (W, 12 * 64)
+        assert torch.equal(f["qkv_w"], qkv_w2.to(torch.bfloat16)) and torch.equal(f["qkv_b"], qkv_b2) and torch.equal(f["out_w"], out_w2.to(torch.bfloat16))
+        assert f["fc1_w"].shape == (arch.mlp_dim, W) and torch.equal(f["ln1_g"], sd[p + "output.LayerNorm.weight"])
+
+
+def test_towers_module_keeps_resolving_the_moved_names():
+    for name in ("_need", "_head_dim", "KERNEL_HEAD_DIMS", "_kernel_head_dim", "_pad_heads", "_ceil64", "_pad_mlp", "_Holder", "LN_FOLD", "EVA_GLU_EPILOGUE",
+                 "_OPEN_CLIP_KEYS", "_TIMM_KEYS", "_clip_blocks", "_eva_blocks", "_bert_blocks", "nllb_clip_state_dict", "convnext_dw_taps",
+                 "convnext_fold_ln_fc1", "convnext_fold_gamma_fc2", "convnext_downsample_weight", "convnext_downsample_gather", "RESNET_BN_EPS",
+                 "resnet_pad64", "resnet_fold_bn", "resnet_conv3x3_weight", "resnet_conv1x1_weight", "resnet_stem_weight", "resnet_pad_vec",
+                 "resnet_attnpool_weights"):
+        assert getattr(towers, name) is getattr(TW, name), name
+    assert towers._encoder_cfg.__module__ == towers.__name__ and towers._Fp8State.__module__ == towers.__name__

@@ -358,7 +358,7 @@ def test_golden_mpnet_small():
 
 def test_golden_bert_32_wide_heads():
     """12-heads-of-32 checkpoints (e5-small, bge-small, MiniLM) run on the 64-wide attention kernel through zero-padded heads
-    (engine/towers.py::_pad_heads); bf16 and fp8, mean and CLS pooling, against the transformers golden"""
+    (engine/tower_weights.py::_pad_heads); bf16 and fp8, mean and CLS pooling, against the transformers golden"""
     T, A = _towers()
     sd, z = G.load("bert_small_h32")
     V, P, W, L_, H, F = [int(v) for v in z["cfg"]]
@@ -378,7 +378,7 @@ def test_golden_bert_32_wide_heads():
 @pytest.mark.parametrize("name,layers", [("ViT-H-14", 3), ("ViT-g-14", 2), ("ViT-bigG-14", 2), ("ViT-H-14-378", 2)])
 def test_vit_wide_heads_vs_oracle(name, layers):
     """ViT-H / g / bigG (model_registry.py:237-256): 16 heads of 80 / 88 / 104 run as zero-padded 96 / 96 / 112-wide heads
-    (engine/towers.py::_pad_heads, attention_kernel<HD=128, HS>: 257 tokens = the full 160 KiB of LDS).  Real widths / MLP dims /
+    (engine/tower_weights.py::_pad_heads, attention_kernel<HD=128, HS>: 257 tokens = the full 160 KiB of LDS).  Real widths / MLP dims /
     token counts, depth cut to keep the fp32 CPU oracle in seconds; the text towers of these models are plain 64-wide."""
     from dataclasses import replace
     T, A = _towers()
