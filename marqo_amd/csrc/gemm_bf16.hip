@@ -50,6 +50,8 @@ bool mq_gemm_small_ok(int64_t M, int64_t N, int64_t K, bool ln);
 bool mq_gemm_small_grouped_ok(int64_t M, int64_t N, int64_t K);
 extern mq_knob mq_gemm_small_group_rows;
 extern mq_knob mq_ln_prefetch;        // rowops.hip
+extern mq_knob mq_ln_rows_per_wave;
+extern mq_knob mq_ln_bf16_wide;
 int mq_gemm_small(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const void* d_residual, void* d_out,
                   int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, hipStream_t s);
 // gemm_wd.hip: the W-direct main loop on the same tile plan (-1: combination not instantiated, the caller launches its own kernel)
@@ -819,7 +821,8 @@ extern "C" int mq_gemm_bf16_rsf(const void* d_A, int64_t lda, const void* d_W, i
 // "subln_fold" (0 = the EVA02 sub-LayerNorms run as LayerNorm passes instead of inside the out-projection / fc2 GEMMs),
 // "attn_proj" (fewest fixed-length sequences from which a ViT-B/32-shaped block runs attention + out-projection + residual + statistics as ONE launch,
 // attn_proj.hip; 0 = never), "panel_gemm" (fewest fixed-length sequences from which the folded QKV / fc1 GEMMs of a 768-wide tower run one workgroup per
-// sequence, panel_gemm.hip; 0 = never).
+// sequence, panel_gemm.hip; 0 = never), "ln_rows" (rowops.hip: 1 = one row per wave in the generic LayerNorm at any row count, 2 = two from 8192 rows),
+// "ln_bf16_wide" (0 = bf16 rows take the generic LayerNorm, 1 = the 16-byte form above small_m rows, 4 = that form with four rows per wave from 16384 rows).
 extern "C" int mq_tune(const char* key, int value) {
     MQ_CHECK_ARG(key, "mq_tune: null key");
     const std::string k(key);
@@ -840,6 +843,8 @@ extern "C" int mq_tune(const char* key, int value) {
     else if (k == "small_m") mq_gemm_small_max_rows = value;
     else if (k == "small_m_grouped") mq_gemm_small_group_rows = value;
     else if (k == "ln_prefetch") mq_ln_prefetch = value;
+    else if (k == "ln_rows") mq_ln_rows_per_wave = value;
+    else if (k == "ln_bf16_wide") mq_ln_bf16_wide = value;
     else if (k == "gemm_addr_limit_mb") mq_gemm_addr_limit = value > 0 ? ((uint64_t)value << 20) - 1 : 0xffffffffull;
     else { mq_set_error("mq_tune: unknown key %s", key); return MQ_ERR_INVALID; }
     return MQ_OK;

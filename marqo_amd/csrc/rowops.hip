@@ -4,13 +4,13 @@
 #include <stdlib.h>
 #include "common.h"
 
-int mq_ln_rows_per_wave = getenv("MQ_LN_ROWS") ? atoi(getenv("MQ_LN_ROWS")) : 2;  // mq_tune("ln_rows", 1 | 2)
-extern int mq_gemm_small_max_rows;   // gemm_small.hip
+mq_knob mq_ln_rows_per_wave{getenv("MQ_LN_ROWS") ? atoi(getenv("MQ_LN_ROWS")) : 2};  // mq_tune("ln_rows", 1 | 2) / MQ_LN_ROWS
+extern mq_knob mq_gemm_small_max_rows;   // gemm_small.hip
 int mq_layernorm_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32,
                     int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 int mq_layernorm_fp8_pf(const void* d_x, int x_bf16, const float* d_g, const float* d_b, void* d_out_fp8, float* d_row_scale, float* d_out_f32,
                         int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
-int mq_ln_bf16_wide = getenv("MQ_LN_BF16_WIDE") ? atoi(getenv("MQ_LN_BF16_WIDE")) : 1;   // mq_tune("ln_bf16_wide", 0 | 1): 16-byte bf16-input LayerNorm
+mq_knob mq_ln_bf16_wide{getenv("MQ_LN_BF16_WIDE") ? atoi(getenv("MQ_LN_BF16_WIDE")) : 1};   // mq_tune("ln_bf16_wide", 0 | 1 | 4) / MQ_LN_BF16_WIDE: 16-byte bf16-input LayerNorm (4: four rows per wave from 16384 rows)
 
 namespace {
 

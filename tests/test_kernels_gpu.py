@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import attention_ref as AR
+from tests import rowops_ref as RR
 
 pytestmark = pytest.mark.gpu
 
@@ -109,12 +110,16 @@ def test_layernorm(lib, rows, W):
     torch.cuda.synchronize()
     assert torch.allclose(of, ref, rtol=1e-5, atol=1e-5)
     assert torch.allclose(ob.float(), ref, rtol=1e-2, atol=1e-2)
+    # ... and within 1.25 x the rounding budget of the float64 reference (tests/rowops_ref.py): the bf16 output is rounded to nearest, not merely close
+    y64, B = RR.reference_ln(x, gam, bet, 1e-5)
+    assert RR.ratio(of, y64, B) <= 1.25 and RR.ratio(ob, y64, B + RR.half_ulp_bf16(y64)) <= 1.25
     # gathered rows
     idx = torch.tensor([rows - 1, 0, rows // 2], device="cuda", dtype=torch.int32)
     og = torch.empty(3, W, device="cuda")
     L.check(lib.mq_layernorm(x.data_ptr(), idx.data_ptr(), gam.data_ptr(), bet.data_ptr(), 0, og.data_ptr(), 3, W, 1e-5, _stream()))
     torch.cuda.synchronize()
     assert torch.allclose(og, ref[idx.long()], rtol=1e-5, atol=1e-5)
+    assert RR.ratio(og, y64[idx.long()], B[idx.long()]) <= 1.25
 
 
 def _ref_attention(qkv, lens, heads, causal, hd=64):
