@@ -764,6 +764,27 @@ int mq_resnet_avgpool2(const void* d_x, void* d_out, int64_t n, int32_t H, int32
 int mq_resnet_attnpool_tokens(const void* d_x, const float* d_pos, void* d_tokens, int64_t n, int32_t HW, int32_t C, void* stream);
 int mq_resnet_attnpool_attend(const void* d_q, const void* d_kv, void* d_out, int64_t n, int32_t T, int32_t C, void* stream);
 
+/* ---- attention-based image patching (csrc/patch_attn.hip) ---------------------------------------------------------------------------------
+ * The 'dino-v1' / 'dino-v2' patch methods of the reference (s2_inference/processing/image.py:102-108, DINO_utils.py): where the class token of a
+ * DINO ViT looks in the last block, and boxes around the bright regions of those maps.  Both are building blocks of engine/dino.py.
+ *   mq_attention_cls_probs: d_qkv bf16 [nseq T, 3W] in mq_attention's layout, 64-wide heads (W == heads * 64), every sequence T rows long with the
+ *                           class token in row 0.  d_probs fp32 [nseq, heads, T - 1] = softmax(q_0 . k_j / 8) over ALL T keys j, entries j = 1 .. T - 1
+ *                           written (the class key counts in the denominator and is left out of the output).  fp32 arithmetic on exact bf16 products;
+ *                           V is never read.  2 <= T <= 8192.
+ *   mq_attn_boxes:          d_probs fp32 [n, heads, G G], one row-major G x G map per (image, head), G <= 32.  mode 0: one map per image, the mean over
+ *                           the heads of |p|; mode 1: one map per head, negatives zeroed (maps = 1 in mode 0, heads in mode 1).  Per map: x / max(x) * 255 in float32,
+ *                           truncated to uint8; Otsu's threshold over the 256-bin histogram as OpenCV's getThreshVal_Otsu computes it (double precision,
+ *                           classes lighter than FLT_EPSILON skipped, first strict maximum); foreground = value > threshold; 8-connected foreground
+ *                           components, of which those are reported that touch the 4-connected background joined to the frame (cv2.findContours with
+ *                           RETR_EXTERNAL: a blob inside another blob's hole is not).  d_boxes int32 [n, maps, max_boxes, 4] = (x, y, x + w, y + h) in
+ *                           grid cells, in the raster order of each component's first cell; d_counts int32 [n, maps] = components found (only the first
+ *                           max_boxes are written; ceil(G / 2)^2 always suffice).  max_boxes >= 1.  A map whose maximum is 0 (all zero, or in mode 1 nothing
+ *                           positive) has no defined rescale in the reference (0 / 0 cast to uint8); here every cell becomes level 0, the
+ *                           threshold is 0 and the map reports no box (count 0). */
+int mq_attention_cls_probs(const void* d_qkv, float* d_probs, int64_t nseq, int32_t T, int32_t W, int32_t heads, void* stream);
+int mq_attn_boxes(const float* d_probs, int64_t n, int32_t heads, int32_t G, int32_t mode, int32_t* d_boxes, int32_t* d_counts, int32_t max_boxes,
+                  void* stream);
+
 /* ---- text tokenisation on device (K14) ------------------------------------------------------------------- */
 /* The reference tokenises on the host with third-party code (open_clip SimpleTokenizer at
  * src/marqo/core/inference/embedding_models/open_clip_model.py:277, transformers BertTokenizer at

@@ -419,6 +419,23 @@ def resolve_resnet_clip(arch_name: str, pretrained: Optional[str] = None) -> Tup
     return replace(v, quick_gelu=quick), replace(t, quick_gelu=quick)
 
 
+# facebookresearch/dino ViTs behind the 'dino-v1' / 'dino-v2' image patch methods (processing/DINO_utils.py:15-63, vision_transformer.py:248-259):
+# (width, layers, heads, mlp_dim) at patch 16 or 8 and 224 px; class token, learned positions, conv bias, no ln_pre, erf-GELU, LayerNorm eps 1e-6
+DINO_ARCHS = {"vit_small": (384, 12, 6, 1536), "vit_base": (768, 12, 12, 3072)}
+DINO_MEAN, DINO_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # DINO_utils.py:76-77
+
+
+def dino_arch(name: str = "vit_small", patch_size: int = 16, image_size: int = 224) -> VitArch:
+    """'vit_small' | 'vit_base' at patch 16 | 8 -> the VitArch engine/dino.py runs (out_dim is the width: the tower has no projection)"""
+    if name not in DINO_ARCHS:
+        raise KeyError(f"{name} not found in {tuple(DINO_ARCHS)}")
+    if patch_size not in (8, 16):
+        raise KeyError(f"{patch_size} not found in (8, 16)")
+    W, layers, heads, mlp = DINO_ARCHS[name]
+    return VitArch(image_size=image_size, patch_size=patch_size, width=W, layers=layers, heads=heads, mlp_dim=mlp, out_dim=W, ln_eps=1e-6,
+                   ln_pre=False)
+
+
 # OpenAI `clip` names (clip_utils.py:295-492) -> open_clip architecture (always QuickGELU)
 OPENAI_CLIP_NAMES = {"ViT-B/32": "ViT-B-32", "ViT-B/16": "ViT-B-16", "ViT-L/14": "ViT-L-14", "ViT-L/14@336px": "ViT-L-14-336"}
 

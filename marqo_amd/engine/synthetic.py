@@ -216,6 +216,28 @@ def random_open_clip_state_dict(vision: VitArch = None, text: ClipTextArch = Non
     return sd
 
 
+def random_dino_state_dict(arch: VitArch, seed: int = 0) -> Dict[str, Tensor]:
+    """facebookresearch/dino VisionTransformer-named state dict (engine/dino.py; the 'dino-v1' / 'dino-v2' patch methods)"""
+    g = torch.Generator().manual_seed(seed)
+    W, P, F = arch.width, arch.patch_size, arch.mlp_dim
+    std = 0.6 / math.sqrt(W)
+    sd: Dict[str, Tensor] = {}
+    sd["cls_token"] = 0.5 * torch.randn(1, 1, W, generator=g)
+    sd["pos_embed"] = 0.3 * torch.randn(1, arch.tokens, W, generator=g)
+    sd["patch_embed.proj.weight"] = torch.randn(W, 3, P, P, generator=g) / math.sqrt(3 * P * P)
+    sd["patch_embed.proj.bias"] = 0.05 * torch.randn(W, generator=g)
+    for i in range(arch.layers):
+        p = f"blocks.{i}."
+        _ln(sd, p + "norm1", W, g)
+        _lin(sd, p + "attn.qkv", 3 * W, W, g, std)
+        _lin(sd, p + "attn.proj", W, W, g, std)
+        _ln(sd, p + "norm2", W, g)
+        _lin(sd, p + "mlp.fc1", F, W, g, std)
+        _lin(sd, p + "mlp.fc2", W, F, g, std / 2)
+    _ln(sd, "norm", W, g)
+    return sd
+
+
 def random_nllb_text_state_dict(arch: NllbTextArch, seed: int = 0) -> Dict[str, Tensor]:
     """open_clip HFTextEncoder over a transformers M2M100Encoder (the NLLB-CLIP text tower): `text.transformer.*` + `text.proj.weight`.  The token
     table is small (M2M100 multiplies it by sqrt(width) = 32) so that the sinusoidal positions, of unit scale, stay visible in the sum."""
