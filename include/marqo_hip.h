@@ -241,7 +241,7 @@ typedef struct mq_clip_text_cfg {
 typedef struct mq_bert_weights {
     const float* word_emb;   /* fp32 [V, W] */
     const float* pos_emb;    /* fp32 [P, W] */
-    const float* type_emb;   /* fp32 [2, W] (row 0 is used: token_type_ids are all zero) */
+    const float* type_emb;   /* fp32 [2, W] (mq_encode_bert uses row 0: token_type_ids are all zero; mq_score_pairs_bert looks the row up per token) */
     const float* emb_ln_g; const float* emb_ln_b;
     const mq_block_weights* blocks;
     /* optional projection head on the pooled row (NULL: none) — open_clip's HFTextEncoder with proj "mlp" (the text tower of
@@ -979,6 +979,52 @@ int mq_profile_collect(double* ms_per_family /* [MQ_PROF_FAMILIES] */,
  * about target_ms on `stream`; waits for it.  *tflops = the dense bf16 rate this chip sustains at the clock it holds under full MFMA
  * load, *shader_mhz = that clock (s_memtime ticks / wall time).  d_scratch: >= 32 KiB of device memory.  No reference counterpart. */
 int mq_probe_mfma_peak(double target_ms, void* d_scratch, int64_t scratch_bytes, double* tflops, double* shader_mhz, void* stream);
+
+/* ---- text reranking: cross-encoder scoring on the BERT tower (csrc/rerank.hip) --------------------------------------------------------------
+ * s2_inference/reranking/rerank.py rerank_search_results -> cross_encoders.py ReRankerText -> sentence-transformers CrossEncoder.predict in the
+ * reference: a BertForSequenceClassification (encoder, pooler = tanh(Linear) on the [CLS] row, one-logit classifier) over (query, chunk) pairs.
+ * Additions to ABI 14: nothing above changes.  Every pointer is a device pointer unless its name starts with h_.
+ *
+ *   mq_pair_plan:   per pair i of ONE query of la = Lq pieces and document i of lb = clamp(d_doc_len[i] - 2, 0, ld - 2) pieces, the lengths kept
+ *                   by the `tokenizers` library's LongestFirst truncation (the fast tokenizers' truncation="longest_first"; NOT the slow
+ *                   tokenizers' one-token-at-a-time loop) to B = max_length - 3 pieces: both when la + lb <= B; else with s = min, l = max
+ *                   (a tie counts the SECOND text as the longer): l' = s when s > B, else max(s, B - s); when s + l' > B: s = B / 2,
+ *                   l' = B - s; the longer text keeps l'.  d_keep_a / d_keep_b int32 [n]; d_total int32 [n] = a + b + 3.  max_length >= 4.
+ *   mq_pack_pairs:  d_ids / d_type_ids int32 [rows]: sequence i at [d_cu[i], d_cu[i + 1]) = [CLS] q[:a] [SEP] (type 0) d_i[:b] [SEP] (type 1);
+ *                   d_query int32 [Lq] holds the query's pieces only, d_docs int32 [n, ld] rows [CLS] pieces [SEP] pad (mq_tokenize_wordpiece's
+ *                   layout: the pieces start at column 1).  d_cu int32 [n + 1] is the exclusive scan of d_total (the caller's: it needs the
+ *                   host copy for the tower anyway).  Both texts keep their prefix.  Nothing at or beyond row `rows` is written.
+ *   mq_embed_tokens_typed: mq_embed_tokens with a type id per row: + d_type_emb[clamp(d_type_ids[r], 0, type_vocab - 1)] where mq_embed_tokens
+ *                   adds row 0 — same order of the additions (token, position, type), so all-zero type ids give mq_embed_tokens' bits.
+ *   mq_score_head:  d_h fp32 [n, W] (the final [CLS] rows) -> y = tanh(pooler_w bf16(h) + pooler_b) (mq_gemm_bf16: bf16 operands, fp32
+ *                   accumulation; tanhf in fp32), z = cls_w . y + cls_b -> d_logits fp32 [n]; d_scores (NULL ok) = 1 / (1 + exp(-z)).
+ *                   W % 64 == 0, W <= 2048.  Scratch: mq_score_head_workspace_bytes(n, W).
+ *   mq_score_pairs_bert: typed embedding -> the encoder with mq_encode_bert's MQ_POOL_CLS row selection -> the [CLS] rows (d_cls_rows fp32
+ *                   [nseq, W], NULL ok: bit-identical to mq_encode_bert(pool = CLS, normalize = 0) when the type rows agree) -> mq_score_head.
+ *                   bf16 encoders only (MQ_PREC_FP8 is refused).  Scratch: mq_score_pairs_workspace_bytes(cfg, rows, nseq). */
+typedef struct mq_score_head_weights {
+    const void*  pooler_w;   /* bf16 [W, W]: bert.pooler.dense.weight */
+    const float* pooler_b;   /* fp32 [W] */
+    const float* cls_w;      /* fp32 [W]: classifier.weight (num_labels = 1) */
+    float        cls_b;      /* classifier.bias */
+    int32_t      type_vocab; /* rows of mq_bert_weights.type_emb (config.json type_vocab_size) */
+} mq_score_head_weights;
+
+int mq_pair_plan(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t* d_keep_a, int32_t* d_keep_b,
+                 int32_t* d_total, void* stream);
+int mq_pack_pairs(const int32_t* d_query, int32_t Lq, const int32_t* d_docs, int32_t ld, const int32_t* d_keep_a, const int32_t* d_keep_b,
+                  const int32_t* d_cu, int64_t n, int32_t cls_id, int32_t sep_id, int32_t* d_ids, int32_t* d_type_ids, int64_t rows,
+                  void* stream);
+int mq_embed_tokens_typed(const int32_t* d_ids, const int32_t* d_type_ids, const int32_t* d_cu, int64_t nseq, const float* d_tok,
+                          const float* d_pos, const float* d_type_emb, int32_t type_vocab, const float* d_g, const float* d_b, float* d_x,
+                          void* d_xb, int32_t W, int32_t vocab, float eps, int32_t last_pos, void* stream);
+size_t mq_score_head_workspace_bytes(int64_t n, int32_t W);
+int mq_score_head(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
+                  void* d_workspace, size_t workspace_bytes, void* stream);
+size_t mq_score_pairs_workspace_bytes(const mq_bert_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_score_pairs_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                        const int32_t* d_type_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits,
+                        float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

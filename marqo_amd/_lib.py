@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank")  # build() refuses register spills in these
 ABI_VERSION = 14
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -178,6 +178,12 @@ class QueueStats(C.Structure):
 
 QUEUE_CLIP_TEXT, QUEUE_BERT, QUEUE_IMAGE_F32 = 0, 1, 2
 
+
+class ScoreHeadWeights(C.Structure):
+    """mq_score_head_weights: pooler + one-logit classifier of a cross-encoder (csrc/rerank.hip)"""
+    _fields_ = [("pooler_w", C.c_void_p), ("pooler_b", C.c_void_p), ("cls_w", C.c_void_p), ("cls_b", C.c_float), ("type_vocab", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -294,6 +300,15 @@ _SIGNATURES = {
     "mq_rope_table": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mq_glu": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_glu_ln": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, C.c_int32, _P]),
+    # text reranking: cross-encoder scoring on the BERT tower (csrc/rerank.hip; engine/rerank.py)
+    "mq_pair_plan": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mq_pack_pairs": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "mq_embed_tokens_typed": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
+    "mq_score_head_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "mq_score_head": (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(ScoreHeadWeights), _P, _P, _P, C.c_size_t, _P]),
+    "mq_score_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(BertCfg), C.c_int64, C.c_int64]),
+    "mq_score_pairs_bert": (C.c_int, [C.POINTER(BertCfg), C.POINTER(BertWeights), C.POINTER(ScoreHeadWeights), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
+                                      _P, C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
     "mq_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

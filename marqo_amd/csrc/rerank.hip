@@ -1,0 +1,284 @@
+// Text reranking: a cross-encoder (BertForSequenceClassification, one logit) on the BERT tower.
+//   * pair_plan / pack_pairs: [CLS] q [SEP] d [SEP] for ONE query against n documents with the `tokenizers` library's LongestFirst
+//     truncation, from the ids mq_tokenize_wordpiece left on the device.
+//   * embed_tokens_typed: embed.hip's embed_tokens with a token-type id per row.
+//   * score_head: pooler (tanh(Linear), through mq_gemm_bf16) + the one-logit classifier (+ sigmoid).
+//   * mq_score_pairs_bert: typed embedding -> encoder (the [CLS] row selection of mq_encode_bert) -> head.
+// All of it is bandwidth-trivial next to the encoder: coalesced, bounds-guarded, untuned.
+#include "common.h"
+
+int mq_cast_bf16(const float* d_x, void* d_out, int64_t n, hipStream_t s);   // rowops.hip
+
+static_assert(sizeof(mq_score_head_weights) == 32, "mq_score_head_weights layout");   // (marqo_amd/_lib.py ScoreHeadWeights)
+
+namespace {
+constexpr int MAXC = 8;          // W <= 2048
+constexpr size_t WS_ALIGN = 256;
+
+// ---- LongestFirst truncation of a pair to B pieces ----------------------------------------------------------------------------------
+// tokenizers' truncate_encodings: n1 = the shorter (the FIRST text on a tie), n2 = n1 when n1 > B else max(n1, B - n1); when that
+// still exceeds B: n1 = B / 2, n2 = B - n1; the texts take them back in their own order.
+__host__ __device__ inline void pair_keep(int la, int lb, int B, int* a, int* b) {
+    if (la + lb <= B) { *a = la; *b = lb; return; }
+    const bool swap = la > lb;
+    int s = swap ? lb : la;
+    int l = s > B ? s : (s > B - s ? s : B - s);
+    if (s + l > B) { s = B / 2; l = B - s; }
+    *a = swap ? l : s;
+    *b = swap ? s : l;
+}
+
+__global__ __launch_bounds__(256) void pair_plan_kernel(int la, const int32_t* __restrict__ doc_len, int n, int ld, int B,
+                                                        int32_t* __restrict__ keep_a, int32_t* __restrict__ keep_b, int32_t* __restrict__ total) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int lb = doc_len[i] - 2;                      // [CLS] pieces [SEP]
+    lb = lb < 0 ? 0 : (lb > ld - 2 ? ld - 2 : lb);
+    int a, b;
+    pair_keep(la, lb, B, &a, &b);
+    keep_a[i] = a;
+    keep_b[i] = b;
+    total[i] = a + b + 3;
+}
+
+// grid = n blocks; the block's threads walk the sequence's rows.  Reads stay inside q [Lq] and row i of docs [n, ld], writes inside
+// [cu[i], min(cu[i + 1], rows)), whatever the plan arrays hold.
+__global__ __launch_bounds__(256) void pack_pairs_kernel(const int32_t* __restrict__ q, int Lq, const int32_t* __restrict__ docs, int ld,
+                                                         const int32_t* __restrict__ keep_a, const int32_t* __restrict__ keep_b,
+                                                         const int32_t* __restrict__ cu, int cls_id, int sep_id, int32_t* __restrict__ ids,
+                                                         int32_t* __restrict__ types, int64_t rows) {
+    const int i = blockIdx.x;
+    int a = keep_a[i], b = keep_b[i];
+    a = a < 0 ? 0 : (a > Lq ? Lq : a);
+    b = b < 0 ? 0 : (b > ld - 2 ? ld - 2 : b);
+    const int64_t row0 = cu[i];
+    int len = cu[i + 1] - cu[i];
+    if (len > a + b + 3) len = a + b + 3;
+    if (row0 < 0) return;
+    const int32_t* d = docs + (int64_t)i * ld + 1;
+    for (int t = threadIdx.x; t < len && row0 + t < rows; t += 256) {
+        int id, ty = 0;
+        if (t == 0) id = cls_id;
+        else if (t <= a) id = q[t - 1];
+        else if (t == a + 1) id = sep_id;
+        else if (t < a + 2 + b) { id = d[t - a - 2]; ty = 1; }
+        else { id = sep_id; ty = 1; }
+        ids[row0 + t] = id;
+        types[row0 + t] = ty;
+    }
+}
+
+// ---- token + position + type[type id] embedding (+ LayerNorm): embed.hip's embed_tokens_kernel with the type row looked up per token -----
+// (the same statements in the same order, so that all-zero type ids reproduce its bits)
+template <bool LN, int CH>
+__global__ __launch_bounds__(256, (CH <= 2 ? 8 : 4)) void embed_tokens_typed_kernel(
+    const int32_t* __restrict__ ids, const int32_t* __restrict__ tids, const int32_t* __restrict__ cu, const float* __restrict__ tok,
+    const float* __restrict__ pos, const float* __restrict__ type_emb, int type_vocab, const float* __restrict__ gam,
+    const float* __restrict__ bet, float* __restrict__ x, bf16_t* __restrict__ xb, int W, int vocab, float eps, int last_pos) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row0 = cu[blockIdx.x], len = cu[blockIdx.x + 1] - row0;
+    const int nch = W >> 2;
+    for (int t = wave; t < len; t += 4) {
+        const int64_t row = row0 + t;
+        int id = ids[row];
+        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        int ty = tids[row];
+        ty = ty < 0 ? 0 : (ty >= type_vocab ? type_vocab - 1 : ty);
+        const float* tr = tok + (int64_t)id * W;
+        const float* pr = pos ? pos + (int64_t)((last_pos > 0 && t == len - 1) ? last_pos : t) * W : nullptr;
+        const float* yr = type_emb + (int64_t)ty * W;
+        f32x4 v[CH];
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int c = lane + i * 64;
+            v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (c < nch) {
+                v[i] = *(const f32x4*)(tr + c * 4);
+                if (pr) v[i] += *(const f32x4*)(pr + c * 4);
+                v[i] += *(const f32x4*)(yr + c * 4);
+            }
+        }
+        if (LN) ln_normalize_row<CH>(v, lane, nch, W, eps);
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int c = lane + i * 64;
+            if (c < nch) {
+                f32x4 y = v[i];
+                if (LN) {
+                    const f32x4 gg = *(const f32x4*)(gam + c * 4);
+                    const f32x4 bb = *(const f32x4*)(bet + c * 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[e] = v[i][e] * gg[e] + bb[e];
+                }
+                if (x) *(f32x4*)(x + row * W + c * 4) = y;
+                if (xb) {
+                    uint2 p;
+                    p.x = pack_bf16x2(y[0], y[1]);
+                    p.y = pack_bf16x2(y[2], y[3]);
+                    *(uint2*)(xb + row * W + c * 4) = p;
+                }
+            }
+        }
+    }
+}
+
+// ---- classifier on the pooler's pre-activation: one wave64 per pair --------------------------------------------------------------------
+// z = sum_j cls_w[j] tanhf(p[j]) + cls_b: lane c takes columns c, c + 64, ... (fma chain), the xor butterfly adds the lanes
+__global__ __launch_bounds__(256) void score_tail_kernel(const float* __restrict__ p, const float* __restrict__ cls_w, float cls_b, int64_t n,
+                                                         int W, float* __restrict__ logits, float* __restrict__ scores) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const float* pr = p + r * W;
+    float acc = 0.f;
+    for (int j = lane; j < W; j += 64) acc = fmaf(cls_w[j], tanhf(pr[j]), acc);
+    const float z = wave_sum(acc) + cls_b;
+    if (lane == 0) {
+        logits[r] = z;
+        if (scores) scores[r] = 1.0f / (1.0f + expf(-z));
+    }
+}
+
+struct HeadPlan { size_t off_hb, off_p, total; };
+HeadPlan head_plan(int64_t n, int W) {
+    HeadPlan h;
+    h.off_hb = 0;                                                       // bf16 [n, W]: the rows as the GEMM's operand
+    h.off_p = align_up((size_t)n * W * 2, WS_ALIGN);                    // fp32 [n, W]: pooler_w h + pooler_b
+    h.total = h.off_p + align_up((size_t)n * W * 4, WS_ALIGN);
+    return h;
+}
+
+struct PairsPlan { size_t off_enc, enc_bytes, off_cls, off_head, total; };
+// [ mq_bert_workspace_bytes: x fp32 [rows, W] | encoder scratch ] [ CLS rows fp32 [nseq, W] ] [ head scratch ]
+PairsPlan pairs_plan(const mq_bert_cfg* cfg, int64_t rows, int64_t nseq) {
+    PairsPlan p;
+    const size_t bert = align_up(mq_bert_workspace_bytes(cfg, rows, nseq), WS_ALIGN);
+    p.off_enc = align_up((size_t)rows * cfg->enc.width * 4, WS_ALIGN);
+    p.enc_bytes = bert - p.off_enc;
+    p.off_cls = bert;
+    p.off_head = p.off_cls + align_up((size_t)nseq * cfg->enc.width * 4, WS_ALIGN);
+    p.total = p.off_head + head_plan(nseq, cfg->enc.width).total;
+    return p;
+}
+}  // namespace
+
+extern "C" int mq_pair_plan(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t* d_keep_a,
+                            int32_t* d_keep_b, int32_t* d_total, void* stream) {
+    MQ_CHECK_ARG(max_length >= 4, "mq_pair_plan: max_length=%d must be >= 4 ([CLS] a [SEP] b [SEP] with at least one piece)", max_length);
+    MQ_CHECK_ARG(Lq >= 0 && ld >= 2 && n < (1ll << 31), "mq_pair_plan: bad shape Lq=%d ld=%d n=%lld", Lq, ld, (long long)n);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_doc_len && d_keep_a && d_keep_b && d_total, "mq_pair_plan: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(3, s);
+    hipLaunchKernelGGL(pair_plan_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, Lq, d_doc_len, (int)n, ld, max_length - 3, d_keep_a,
+                       d_keep_b, d_total);
+    MQ_CHECK_LAUNCH("mq_pair_plan");
+    return MQ_OK;
+}
+
+extern "C" int mq_pack_pairs(const int32_t* d_query, int32_t Lq, const int32_t* d_docs, int32_t ld, const int32_t* d_keep_a,
+                             const int32_t* d_keep_b, const int32_t* d_cu, int64_t n, int32_t cls_id, int32_t sep_id, int32_t* d_ids,
+                             int32_t* d_type_ids, int64_t rows, void* stream) {
+    MQ_CHECK_ARG(Lq >= 0 && ld >= 2 && n < (1ll << 31) && rows >= 0, "mq_pack_pairs: bad shape Lq=%d ld=%d n=%lld rows=%lld", Lq, ld,
+                 (long long)n, (long long)rows);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG((d_query || Lq == 0) && d_docs && d_keep_a && d_keep_b && d_cu && d_ids && d_type_ids, "mq_pack_pairs: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(3, s);
+    hipLaunchKernelGGL(pack_pairs_kernel, dim3((unsigned)n), dim3(256), 0, s, d_query, Lq, d_docs, ld, d_keep_a, d_keep_b, d_cu, cls_id, sep_id,
+                       d_ids, d_type_ids, rows);
+    MQ_CHECK_LAUNCH("mq_pack_pairs");
+    return MQ_OK;
+}
+
+extern "C" int mq_embed_tokens_typed(const int32_t* d_ids, const int32_t* d_type_ids, const int32_t* d_cu, int64_t nseq, const float* tok,
+                                     const float* pos, const float* type_emb, int32_t type_vocab, const float* g, const float* b, float* d_x,
+                                     void* d_xb, int32_t W, int32_t vocab, float eps, int32_t last_pos, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    MQ_CHECK_ARG(W >= 4 && W % 4 == 0 && W <= 64 * 4 * MAXC, "embed_tokens_typed: W=%d unsupported", W);
+    MQ_CHECK_ARG(type_vocab >= 1 && vocab >= 1, "embed_tokens_typed: type_vocab=%d vocab=%d", type_vocab, vocab);
+    if (nseq <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_ids && d_type_ids && d_cu && tok && type_emb && (!g || b) && (d_x || d_xb), "embed_tokens_typed: null pointer");
+    MqProfScope prof(3, s);
+    if (g)
+        MQ_DISPATCH_CH(W, hipLaunchKernelGGL((embed_tokens_typed_kernel<true, CH>), dim3((unsigned)nseq), dim3(256), 0, s, d_ids, d_type_ids,
+                                             d_cu, tok, pos, type_emb, type_vocab, g, b, d_x, (bf16_t*)d_xb, W, vocab, eps, last_pos));
+    else
+        MQ_DISPATCH_CH(W, hipLaunchKernelGGL((embed_tokens_typed_kernel<false, CH>), dim3((unsigned)nseq), dim3(256), 0, s, d_ids, d_type_ids,
+                                             d_cu, tok, pos, type_emb, type_vocab, g, b, d_x, (bf16_t*)d_xb, W, vocab, eps, last_pos));
+    MQ_CHECK_LAUNCH("embed_tokens_typed");
+    return MQ_OK;
+}
+
+extern "C" size_t mq_score_head_workspace_bytes(int64_t n, int32_t W) {
+    if (n <= 0 || W <= 0) return 0;
+    return head_plan(n, W).total;
+}
+
+extern "C" int mq_score_head(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
+                             void* d_workspace, size_t workspace_bytes, void* stream) {
+    MQ_CHECK_ARG(head, "mq_score_head: null head");
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "mq_score_head: W=%d must be a multiple of 64, at most %d", W, 64 * 4 * MAXC);
+    MQ_CHECK_ARG(head->pooler_w && head->pooler_b && head->cls_w, "mq_score_head: null weight pointer");
+    MQ_CHECK_ARG(n < (1ll << 31), "mq_score_head: n=%lld too large", (long long)n);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_h && d_logits && d_workspace, "mq_score_head: null input / output / workspace");
+    const HeadPlan hp = head_plan(n, W);
+    if (workspace_bytes < hp.total) { mq_set_error("mq_score_head: workspace %zu < required %zu", workspace_bytes, hp.total); return MQ_ERR_WORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_workspace;
+    void* hb = base + hp.off_hb;
+    float* p = (float*)(base + hp.off_p);
+    MQ_TRY(mq_cast_bf16(d_h, hb, n * W, s));
+    MQ_TRY(mq_gemm_bf16(hb, W, head->pooler_w, W, head->pooler_b, nullptr, p, W, n, W, W, MQ_EPI_BIAS | MQ_EPI_OUT_F32, s));
+    MqProfScope prof(4, s);
+    hipLaunchKernelGGL(score_tail_kernel, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, s, p, head->cls_w, head->cls_b, n, W, d_logits, d_scores);
+    MQ_CHECK_LAUNCH("mq_score_head");
+    return MQ_OK;
+}
+
+extern "C" size_t mq_score_pairs_workspace_bytes(const mq_bert_cfg* cfg, int64_t rows, int64_t nseq) {
+    if (!cfg || rows <= 0 || nseq <= 0) return 0;
+    return pairs_plan(cfg, rows, nseq).total;
+}
+
+extern "C" int mq_score_pairs_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                                   const int32_t* d_type_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq,
+                                   float* d_logits, float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes,
+                                   void* stream) {
+    MQ_CHECK_ARG(cfg && w && head && d_logits, "mq_score_pairs_bert: null pointer");
+    MQ_CHECK_ARG(cfg->enc.precision == MQ_PREC_BF16, "mq_score_pairs_bert: bf16 encoders only (precision %d)", cfg->enc.precision);
+    MQ_CHECK_ARG(cfg->enc.post_ln == 1 && cfg->enc.mask == MQ_MASK_NONE, "mq_score_pairs_bert: BERT is post-LN with full attention");
+    MQ_CHECK_ARG(!cfg->enc.d_rope_inv_freq && !cfg->enc.mlp_glu && !cfg->enc.d_rel_bias, "mq_score_pairs_bert: plain BERT encoders only");
+    MQ_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b, "mq_score_pairs_bert: null weight pointer");
+    MQ_CHECK_ARG(head->type_vocab >= 1, "mq_score_pairs_bert: type_vocab=%d", head->type_vocab);
+    const int W = cfg->enc.width;
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "mq_score_pairs_bert: W=%d must be a multiple of 64, at most %d", W, 64 * 4 * MAXC);
+    MQ_CHECK_ARG(nseq < (1ll << 31), "mq_score_pairs_bert: nseq=%lld too large", (long long)nseq);
+    if (nseq <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_ids && d_type_ids && d_cu_seqlens && h_cu_seqlens && d_workspace, "mq_score_pairs_bert: null input / workspace");
+    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "mq_score_pairs_bert: cu_seqlens[0] must be 0");
+    int maxl = 0;
+    for (int64_t i = 0; i < nseq; ++i) {
+        const int l = h_cu_seqlens[i + 1] - h_cu_seqlens[i];
+        MQ_CHECK_ARG(l >= 1 && l <= cfg->max_pos, "mq_score_pairs_bert: sequence lengths must be in [1, max_pos=%d]", cfg->max_pos);
+        if (l > maxl) maxl = l;
+    }
+    const int64_t rows = h_cu_seqlens[nseq];
+    const PairsPlan p = pairs_plan(cfg, rows, nseq);
+    const size_t enc_need = mq_encoder_workspace_bytes(&cfg->enc, rows, nseq);
+    if (workspace_bytes < p.total) { mq_set_error("mq_score_pairs_bert: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    if (p.enc_bytes < enc_need) { mq_set_error("mq_score_pairs_bert: encoder scratch %zu < required %zu", p.enc_bytes, enc_need); return MQ_ERR_WORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_workspace;
+    float* x = (float*)base;
+    float* cls = (float*)(base + p.off_cls);
+
+    MQ_TRY(mq_embed_tokens_typed(d_ids, d_type_ids, d_cu_seqlens, nseq, w->word_emb, w->pos_emb, w->type_emb, head->type_vocab, w->emb_ln_g,
+                                 w->emb_ln_b, x, nullptr, W, cfg->vocab, cfg->enc.ln_eps, 0, s));
+    // the final [CLS] row of sequence i is row d_cu_seqlens[i]: the last block may run on those rows only, as for MQ_POOL_CLS
+    MQ_TRY(mq_encoder_forward_rows(&cfg->enc, w->blocks, x, rows, d_cu_seqlens, nseq, 0, maxl, d_cu_seqlens, nseq, base + p.off_enc, p.enc_bytes, s));
+    MQ_TRY(mq_pool(x, d_cu_seqlens, nseq, cls, W, MQ_POOL_CLS, 0, s));
+    if (d_cls_rows) MQ_CHECK_HIP(hipMemcpyAsync(d_cls_rows, cls, (size_t)nseq * W * 4, hipMemcpyDeviceToDevice, s));
+    return mq_score_head(cls, nseq, W, head, d_logits, d_scores, base + p.off_head, workspace_bytes - p.off_head, s);
+}

@@ -1,0 +1,178 @@
+"""Cross-encoder scoring for text reranking: (query, passage) pairs through the BERT tower and a one-logit head (csrc/rerank.hip).
+
+The reference scores pairs with sentence-transformers' `CrossEncoder` (s2_inference/reranking/model_utils.py load_sbert_cross_encoder_model),
+i.e. a Hugging Face `BertForSequenceClassification` with num_labels = 1 behind the fast tokenizer's pair call
+(`truncation="longest_first"`).  Here the texts are tokenised once on the GPU (engine/gpu_tokenizers.py), paired, truncated and packed
+there (mq_pair_plan / mq_pack_pairs), and every batch is ONE mq_score_pairs_bert call.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import json
+import os
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from marqo_amd import _lib as L
+from marqo_amd.engine import archs, checkpoint
+from marqo_amd.engine.tokenizers import WordPieceTokenizer
+from marqo_amd.engine.towers import BertTower, _large_call, _need, request_stream
+
+Tensor = torch.Tensor
+
+
+def pair_lengths(la, lb, max_length: int):
+    """Pieces (a, b) that the `tokenizers` library's LongestFirst truncation keeps of a pair with la and lb pieces when the sequence
+    [CLS] a [SEP] b [SEP] may hold max_length tokens (ints or integer arrays; both texts keep their prefix).  B = max_length - 3:
+    nothing is cut when la + lb <= B.  Otherwise, with s the shorter and l the longer text (on a tie the SECOND text counts as the
+    longer), l' = s when s > B, else max(s, B - s); when s + l' is still above B, s = B // 2 and l' = B - s; the longer text keeps l'.
+    This is NOT the slow tokenizers' loop that removes one token at a time from the longer text."""
+    if max_length < 4:
+        raise ValueError(f"max_length={max_length} must be at least 4")
+    scalar = np.ndim(la) == 0 and np.ndim(lb) == 0
+    la, lb = np.broadcast_arrays(np.asarray(la, dtype=np.int64), np.asarray(lb, dtype=np.int64))
+    B = max_length - 3
+    swap = la > lb
+    s = np.where(swap, lb, la)
+    l = np.where(s > B, s, np.maximum(s, B - s))
+    both = s + l > B
+    s = np.where(both, B // 2, s)
+    l = np.where(both, B - B // 2, l)
+    fits = la + lb <= B
+    a = np.where(fits, la, np.where(swap, l, s))
+    b = np.where(fits, lb, np.where(swap, s, l))
+    return (int(a), int(b)) if scalar else (a, b)
+
+
+def _tokenizer_settings(directory: str) -> Tuple[bool, int]:
+    """(do_lower_case, model_max_length) of a checkpoint's tokenizer_config.json (BERT's defaults when absent)"""
+    lower, max_len = True, 512
+    p = os.path.join(directory, "tokenizer_config.json")
+    if os.path.isfile(p):
+        try:
+            with open(p) as f:
+                j = json.load(f)
+            lower = bool(j.get("do_lower_case", True))
+            m = j.get("model_max_length", 512)
+            if isinstance(m, (int, float)) and 4 <= m < 1 << 20:    # (transformers writes 1e30 for "no limit")
+                max_len = int(m)
+        except (OSError, ValueError):
+            pass
+    return lower, max_len
+
+
+class CrossEncoderTower(BertTower):
+    """`BertForSequenceClassification` (num_labels = 1): `bert.*` = the encoder (prepared exactly as for the embedding towers:
+    engine/tower_weights.py), `bert.pooler.dense.*` and `classifier.*` = the head.  score() returns the raw logits and their sigmoid."""
+
+    def __init__(self, arch: archs.BertArch, sd: Dict[str, Tensor], device: str, tokenizer: WordPieceTokenizer, model_max_length: int = 512):
+        if arch.glu or arch.rope_theta is not None or arch.rel_buckets or arch.pos_offset:
+            raise ValueError("cross-encoders run on plain BERT encoders (model_type 'bert')")
+        W = arch.width
+        if W % 64 != 0 or W > 2048:
+            raise ValueError(f"the scoring head needs a hidden size that is a multiple of 64, at most 2048 (got {W})")
+        pooler_w = _need(sd, "bert.pooler.dense.weight", (W, W))
+        pooler_b = _need(sd, "bert.pooler.dense.bias", (W,))
+        cls_w = _need(sd, "classifier.weight", (1, W))
+        cls_b = _need(sd, "classifier.bias", (1,))
+        enc = {k[len("bert."):]: v for k, v in sd.items() if k.startswith("bert.")}
+        super().__init__(arch, enc, device, pooling="cls", precision="bf16")
+        h = self._h
+        self.head = L.ScoreHeadWeights(pooler_w=h.bf16(pooler_w), pooler_b=h.f32(pooler_b), cls_w=h.f32(cls_w.reshape(W)),
+                                       cls_b=float(cls_b.detach().float().reshape(-1)[0]), type_vocab=int(arch.type_vocab))
+        if _need(sd, "bert.embeddings.token_type_embeddings.weight").shape != (arch.type_vocab, W):
+            raise ValueError(f"token_type_embeddings must be [{arch.type_vocab}, {W}]")
+        self.tokenizer = tokenizer
+        self.model_max_length = int(min(model_max_length, arch.max_pos))
+        from marqo_amd.engine.gpu_tokenizers import DeviceWordPieceTokenizer
+        self.device_tokenizer = DeviceWordPieceTokenizer(tokenizer, str(self.device))
+        self.tune_residual_default()      # the same load-time policy as the embedding towers, on the encoder's [CLS] rows
+        self.release_unused_folded()
+
+    @classmethod
+    def from_dir(cls, directory: str, device: str) -> "CrossEncoderTower":
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, vocab.txt, tokenizer_config.json"""
+        cfg, sd = checkpoint.load_hf_dir(directory)
+        mtype = cfg.get("model_type", "bert")
+        if mtype != "bert":
+            raise ValueError(f"{directory}: model_type={mtype!r} is not served as a cross-encoder (only 'bert')")
+        labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
+        if int(labels) != 1:
+            raise ValueError(f"{directory}: num_labels={labels} is not served as a cross-encoder (only one-logit heads)")
+        try:
+            arch = archs.bert_arch_from_hf_config(cfg)
+        except KeyError as e:
+            raise ValueError(f"{directory}: {e}") from e
+        arch = dataclasses.replace(arch, type_vocab=int(cfg.get("type_vocab_size", 2)))
+        lower, max_len = _tokenizer_settings(directory)
+        return cls(arch, sd, device, WordPieceTokenizer(directory, do_lower_case=lower), model_max_length=max_len)
+
+    # ---- scoring -------------------------------------------------------------------------------------------------------------------
+    def _tokenize(self, texts: Sequence[str], cap: int) -> Tuple[Tensor, np.ndarray]:
+        d_ids, lens = self.device_tokenizer.encode_device(list(texts), cap)
+        return d_ids.contiguous(), lens.numpy().astype(np.int64)
+
+    def score(self, query: str, docs: Sequence[str], max_length: int = 512) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (logits, sigmoid(logits)) fp32 [len(docs)] on the host, in the order of `docs`.  Texts are stripped as CrossEncoder strips
+        them; the pair is cut to min(max_length, the tokenizer's model_max_length) tokens by `pair_lengths`."""
+        if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
+            raise TypeError("a cross-encoder scores (str, str) pairs")
+        n = len(docs)
+        if n == 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        cap = int(min(max_length, self.model_max_length))
+        if cap < 4:
+            raise ValueError(f"max_length={max_length} must be at least 4")
+        query, docs = query.strip(), [d.strip() for d in docs]
+        lib, dev, tok = self.lib, self.device, self.tokenizer
+        with request_stream(dev), torch.cuda.device(dev):
+            # the query once (its full length: which text is the longer decides who loses a piece), the documents once.  A document cut
+            # to cap - 2 pieces is still longer than B = cap - 3, and still at least as long as any query of <= cap - 2 pieces; for a
+            # longer query the documents are read up to the query's length, which keeps every comparison of pair_lengths exact.
+            d_q, qlen = self._tokenize([query], max(len(query) + 2, 4))
+            la = int(qlen[0]) - 2
+            ld = cap if la <= cap - 2 else la + 2
+            d_docs, dlen = self._tokenize(docs, ld)
+            a, b = pair_lengths(la, dlen - 2, cap)
+            total = (a + b + 3).astype(np.int64)
+            order = np.argsort(-total, kind="stable")          # longest first: a batch holds sequences of similar length
+            inv = np.empty(n, dtype=np.int64)
+            inv[order] = np.arange(n)
+            sorted_total = total[order]
+            d_order = self._to_device(torch.from_numpy(order))
+            d_docs = d_docs.index_select(0, d_order)            # (row gather: memory movement, as torch is used throughout the engine)
+            d_dlen = self._to_device(torch.from_numpy(dlen[order].astype(np.int32)))
+            d_query = d_q[0, 1:1 + max(la, 0)].contiguous()
+            logits = torch.empty(n, dtype=torch.float32, device=dev)
+            scores = torch.empty(n, dtype=torch.float32, device=dev)
+            stream = self._stream()
+            with _large_call(dev, int(sorted_total.sum())):
+                for s0, s1 in self._chunks(sorted_total):
+                    m = s1 - s0
+                    cu_np = np.zeros(m + 1, dtype=np.int32)
+                    np.cumsum(sorted_total[s0:s1], out=cu_np[1:])
+                    rows = int(cu_np[-1])
+                    cu = torch.from_numpy(cu_np)
+                    d_cu = self._to_device(cu)
+                    plan = torch.empty(3, m, dtype=torch.int32, device=dev)
+                    d_ids = torch.empty(2, rows, dtype=torch.int32, device=dev)
+                    L.check(lib.mq_pair_plan(la, d_dlen[s0:s1].data_ptr(), m, ld, cap, plan[0].data_ptr(), plan[1].data_ptr(),
+                                             plan[2].data_ptr(), stream), "mq_pair_plan")
+                    L.check(lib.mq_pack_pairs(d_query.data_ptr() if la > 0 else None, la, d_docs[s0:s1].data_ptr(), ld, plan[0].data_ptr(),
+                                              plan[1].data_ptr(), d_cu.data_ptr(), m, tok.cls_id, tok.sep_id, d_ids[0].data_ptr(),
+                                              d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
+                    ws = self._workspace(lib.mq_score_pairs_workspace_bytes(C.byref(self.cfg), rows, m))
+                    self.score_packed(d_ids[0], d_ids[1], d_cu, cu, logits[s0:s1], scores[s0:s1], None, ws)
+            out = torch.stack((logits, scores)).cpu().numpy()
+        return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
+
+    def score_packed(self, d_ids: Tensor, d_type_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Optional[Tensor],
+                     cls_rows: Optional[Tensor], ws: Tensor) -> None:
+        """one mq_score_pairs_bert call on this thread's current stream: packed ids / type ids int32 [rows], cu_seqlens on the device and the
+        host, logits / scores fp32 [nseq] (scores may be None), cls_rows fp32 [nseq, W] or None"""
+        L.check(self.lib.mq_score_pairs_bert(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_type_ids.data_ptr(),
+                                             d_cu.data_ptr(), cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores),
+                                             L.ptr(cls_rows), ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_bert")

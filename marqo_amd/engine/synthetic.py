@@ -297,6 +297,28 @@ def random_bert_state_dict(arch: BertArch, seed: int = 0) -> Dict[str, Tensor]:
     return sd
 
 
+def cross_encoder_state_dict(W: int, layers: int, heads: int, mlp: int, vocab: int, seed: int = 0, max_pos: int = 512,
+                             pooler_std: float = 1.0, classifier_std: float = 8.0, attention_gain: float = 4.0) -> Dict[str, Tensor]:
+    """HuggingFace BertForSequenceClassification-named state dict with one label: `bert.*` = random_bert_state_dict, plus the pooler
+    and the classifier.  The pooler's pre-activation has a standard deviation of about pooler_std (its input, a LayerNorm output, has
+    unit scale), so tanh is neither linear nor saturated; the classifier's weights are classifier_std / sqrt(W), which spreads the
+    logits — a head whose logits all agree would hide an error of the tower.  The query / key weights are attention_gain times
+    random_bert_state_dict's: its near-uniform attention averages the passage away and leaves every pair of one query almost the same
+    [CLS] row (logits of 24 unrelated pairs then spread by 0.3; with the peaky attention and these scales by 1.4 or more, checked on
+    the CPU against transformers in tests/test_rerank_host.py)."""
+    arch = BertArch(vocab=vocab, max_pos=max_pos, width=W, layers=layers, heads=heads, mlp_dim=mlp)
+    sd = {"bert." + k: v for k, v in random_bert_state_dict(arch, seed=seed).items()}
+    for k in sd:
+        if k.endswith(("attention.self.query.weight", "attention.self.key.weight")):
+            sd[k] = sd[k] * attention_gain
+    g = torch.Generator().manual_seed(seed + 7919)
+    sd["bert.pooler.dense.weight"] = pooler_std / math.sqrt(W) * torch.randn(W, W, generator=g)
+    sd["bert.pooler.dense.bias"] = 0.1 * torch.randn(W, generator=g)
+    sd["classifier.weight"] = classifier_std / math.sqrt(W) * torch.randn(1, W, generator=g)
+    sd["classifier.bias"] = 0.3 * torch.randn(1, generator=g)
+    return sd
+
+
 # ---- trained-like statistics (bench.py's fp8 row) -------------------------------------------------------------------------------------------
 # N(0, s) weights never show a quantiser what a trained checkpoint does, and the load-time fp8 policy (towers.tune_fp8) decides on measured
 # error: on random-init weights it moves 7 of ViT-L/14's 24 blocks to e4m3, on trained-like ones 13 + 8 MLP halves — the bench row on random

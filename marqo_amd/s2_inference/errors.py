@@ -67,6 +67,8 @@ BatchInferenceSizeNotMatchError = _s2("BatchInferenceSizeNotMatchError")
 ImageDownloadError = _s2("ImageDownloadError")
 MediaDownloadError = _s2("MediaDownloadError")
 UnsupportedModalityError = _s2("UnsupportedModalityError")
+RerankerError = _s2("RerankerError")
+RerankerNameError = _s2("RerankerNameError")
 
 
 # ---- API-level exceptions raised from inside the path (marqo.api.exceptions in the reference) ----

@@ -1,0 +1,234 @@
+"""`ReRankerText`: scores every (query, chunk of a field) pair of a search result with a cross-encoder and keeps the best chunks per hit.
+
+The reference (s2_inference/reranking/cross_encoders.py:224-338, model_utils.py:242-273) does this on pandas frames around a
+sentence-transformers `CrossEncoder`; here the bookkeeping is plain Python (the product does not import pandas) with the same observable
+behaviour, and the scores come from engine/rerank.py CrossEncoderTower (csrc/rerank.hip) with sigmoid as the activation, which is what the
+reference always constructs its CrossEncoder with.
+"""
+from __future__ import annotations
+
+import datetime
+import logging
+import math
+import os
+import threading
+import uuid
+from collections import defaultdict
+from typing import Any, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from marqo_amd.s2_inference.enums import AvailableModelsKey
+from marqo_amd.s2_inference.errors import RerankerError
+from marqo_amd.s2_inference.processing import text as text_processor
+from marqo_amd.s2_inference.reranking.configs import get_default_text_processing_parameters
+from marqo_amd.s2_inference.reranking.enums import Columns, ResultsFields
+
+logger = logging.getLogger(__name__)
+
+_load_lock = threading.Lock()
+
+
+# ---- models --------------------------------------------------------------------------------------------------------------------------
+class DummyModel:
+    """'_testing': uniform random scores, as the reference's DummyModel"""
+
+    def predict(self, inputs: Sequence) -> np.ndarray:
+        return np.random.rand(len(inputs))
+
+
+class EngineCrossEncoder:
+    """predict() of sentence-transformers' CrossEncoder on the engine: [[query, passage], ...] -> sigmoid(logit) fp32 [n]"""
+
+    def __init__(self, directory: str, device: str, max_length: int = 512):
+        from marqo_amd.engine.rerank import CrossEncoderTower
+        self.tower = CrossEncoderTower.from_dir(directory, device)
+        # (model_utils.py:266-270: a max_length above the tokenizer's model_max_length is lowered to it)
+        self.max_length = min(int(max_length), self.tower.model_max_length)
+        self.weights_source = directory
+
+    def predict(self, inputs: Sequence[Sequence[str]]) -> np.ndarray:
+        scores = np.zeros(len(inputs), dtype=np.float32)
+        by_query: Dict[str, List[int]] = {}
+        for i, pair in enumerate(inputs):
+            if len(pair) != 2 or not isinstance(pair[0], str) or not isinstance(pair[1], str):
+                raise TypeError(f"expected [query, text] pairs of strings, found {pair!r}")
+            by_query.setdefault(pair[0], []).append(i)
+        for query, idx in by_query.items():       # (one query per search: one pass)
+            scores[idx] = self.tower.score(query, [inputs[i][1] for i in idx], self.max_length)[1]
+        return scores
+
+
+def _checkpoint_candidates(name: str) -> List[str]:
+    from marqo_amd.engine import checkpoint
+    return [name, os.path.join(checkpoint.model_dir(), "hf", *name.split("/")), os.path.join(checkpoint.model_dir(), *name.split("/")),
+            *checkpoint._hub_cache_dirs(name)]
+
+
+def load_cross_encoder_model(model_name: str, device: str, max_length: int = 512) -> Dict[str, Any]:
+    """the reference's load_sbert_cross_encoder_model: the model lives in the model cache under _create_model_cache_key(model_name, device),
+    so LRU ejection and get_loaded_models cover it.  The checkpoint is looked up where HuggingFaceModel looks `name` up; never downloaded."""
+    from marqo_amd.engine import checkpoint
+    from marqo_amd.s2_inference.s2_inference import _create_model_cache_key, get_available_models
+    key = _create_model_cache_key(model_name, device)
+    models = get_available_models()
+    entry = models.get(key)
+    if entry is None:
+        with _load_lock:
+            entry = models.get(key)
+            if entry is None:
+                logger.info(f"loading {model_name} on device {device} and adding to cache...")
+                if model_name == "_testing":
+                    model = DummyModel()
+                elif model_name.startswith("onnx/"):
+                    raise RerankerError(f"{model_name}: the 'onnx/' prefix (optimum / onnxruntime cross-encoders) is not served by the marqo_amd "
+                                        f"engine; name the Hugging Face checkpoint itself")
+                else:
+                    directory = checkpoint.find_hf_dir(model_name)
+                    if directory is None:
+                        raise RerankerError(f"no local checkpoint for the reranker {model_name}: looked for config.json + model.safetensors | "
+                                            f"pytorch_model.bin under {_checkpoint_candidates(model_name)} (the marqo_amd engine never downloads)")
+                    try:
+                        model = EngineCrossEncoder(directory, device, max_length)
+                    except (ValueError, KeyError, FileNotFoundError) as e:
+                        raise RerankerError(f"cannot load the reranker {model_name} from {directory}: {e}") from e
+                entry = models[key] = {AvailableModelsKey.model: model, AvailableModelsKey.most_recently_used_time: datetime.datetime.now()}
+    else:
+        entry[AvailableModelsKey.most_recently_used_time] = datetime.datetime.now()
+    return {"model": entry[AvailableModelsKey.model]}
+
+
+# ---- result bookkeeping -------------------------------------------------------------------------------------------------------------------
+def _is_missing(v: Any) -> bool:
+    """a field a hit does not hold, or holds as None / NaN (what a frame built from the hits would show as NA)"""
+    return v is None or (isinstance(v, float) and math.isnan(v))
+
+
+class FormattedResults:
+    """the hits as rows for the model: every hit gets its `_rerank_id` (`_id`, or a fresh uuid); with `searchable_fields` given as a list
+    only the hits that hold all of them are kept; `searchable_fields` ends up as the hits' own field names (those not starting with '_')
+    in order of first appearance"""
+
+    def __init__(self, results: Dict, searchable_fields: Optional[List[str]] = None):
+        self.results = results
+        for hit in results[ResultsFields.hits]:
+            hit[ResultsFields.reranked_id] = hit[ResultsFields.id] if ResultsFields.id in hit else str(uuid.uuid4())
+        if searchable_fields is not None and isinstance(searchable_fields, list):
+            results[ResultsFields.hits] = [h for h in results[ResultsFields.hits] if all(s in h for s in searchable_fields)]
+        self.columns: List[str] = list(dict.fromkeys(k for hit in results[ResultsFields.hits] for k in hit))
+        self.searchable_fields = [c for c in self.columns if not c.startswith("_")]
+
+    def format_for_model(self, searchable_fields: List[str], query: Optional[str] = None) -> List[Dict[str, Any]]:
+        """one row per (field, hit) whose content is there, field by field"""
+        rows = []
+        for field in searchable_fields:
+            if field not in self.columns:
+                raise KeyError(f"field {field!r} is in none of the hits")
+            for hit in self.results[ResultsFields.hits]:
+                content = hit.get(field)
+                if _is_missing(content):
+                    continue
+                rows.append({Columns.query: query, Columns.field_content: content, ResultsFields.reranked_id: hit[ResultsFields.reranked_id],
+                             Columns.original_field_name: field, ResultsFields.original_score: hit.get(ResultsFields.original_score, 1.0)})
+        return rows
+
+
+class ReRanker:
+    def __init__(self):
+        self.results = None
+        self.formatted_results = None
+        self.inputs: List[Dict[str, Any]] = []
+        self.num_highlights = 1
+
+    def load_model(self):
+        pass
+
+    def format_results(self, results: Dict, query: Optional[str] = None, searchable_fields: Optional[List[str]] = None):
+        self.results = results
+        self.formatted_results = FormattedResults(results, searchable_fields=searchable_fields)
+
+    @staticmethod
+    def _prepare_inputs(rows: List[Dict[str, Any]]) -> List[List[str]]:
+        return [[r[Columns.query], r[Columns.field_content]] for r in rows]
+
+    def get_reranked_results(self, score_column: str = ResultsFields.reranker_score, highlight_content_column: str = Columns.field_content):
+        """per hit the `num_highlights` best rows -> `_reranked_score` (a number, or a list of them from 2 highlights on) and
+        `_reranked_highlights` ([{field: chunk}, ...]); then the hits in descending order of that score"""
+        groups: Dict[Any, List[Dict[str, Any]]] = defaultdict(list)
+        for row in self.inputs:
+            groups[row[ResultsFields.reranked_id]].append(row)
+        top = {rid: sorted(rows, key=lambda r: r[score_column], reverse=True)[:self.num_highlights] for rid, rows in groups.items()}
+        for hit in self.results[ResultsFields.hits]:
+            rid = hit[ResultsFields.reranked_id]
+            if rid not in top:
+                raise KeyError(f"hit {rid!r} has nothing to score in the searchable fields")
+            best = top[rid]
+            if self.num_highlights == 1:
+                hit[ResultsFields.reranker_score] = best[0][score_column]
+                hit[ResultsFields.highlights_reranked] = [{best[0][Columns.original_field_name]: best[0][highlight_content_column]}]
+            else:
+                if len(best) < 2:   # (the reference fails here too: it asks a single score for its `.values`)
+                    raise ValueError(f"hit {rid!r} has one scored chunk, {self.num_highlights} highlights were asked for")
+                hit[ResultsFields.reranker_score] = [r[score_column] for r in best]
+                hit[ResultsFields.highlights_reranked] = [{r[Columns.original_field_name]: r[highlight_content_column]} for r in best]
+        self.results[ResultsFields.hits] = sorted(self.results[ResultsFields.hits], key=lambda h: h[ResultsFields.reranker_score], reverse=True)
+
+
+class ReRankerText(ReRanker):
+    """reranking with a Hugging Face cross-encoder (BertForSequenceClassification with one logit)"""
+
+    def __init__(self, model_name: str, device: str, max_length: int = 512, num_highlights: int = 1,
+                 split_params: Optional[Dict] = get_default_text_processing_parameters()):
+        super().__init__()
+        self.model_name = model_name
+        self.device = device
+        self.max_length = max_length
+        self.num_highlights = num_highlights
+        self.split_params = split_params
+        self.model = None
+        self.split_length = self.split_overlap = self.split_method = None
+        if isinstance(split_params, (dict, defaultdict)):
+            self.split_length, self.split_overlap, self.split_method = (split_params[k] for k in ("split_length", "split_overlap", "split_method"))
+
+    def load_model(self) -> None:
+        self.model = load_cross_encoder_model(model_name=self.model_name, device=self.device, max_length=self.max_length)["model"]
+
+    def explode_nested_content_field(self, rows: List[Dict[str, Any]]) -> List[Dict[str, Any]]:
+        """one row per chunk of a row's content (chunked as indexing chunks text), the unchunked text kept beside it"""
+        out = []
+        for row in rows:
+            chunks = text_processor.split_text(row[Columns.field_content], split_length=self.split_length, split_overlap=self.split_overlap,
+                                               split_by=self.split_method)
+            for chunk in chunks if len(chunks) else [None]:
+                out.append({**row, Columns.field_content: chunk, Columns.field_content_original: row[Columns.field_content]})
+        return out
+
+    def rerank(self, query: str, results: Dict, searchable_attributes: Optional[List[str]] = None) -> None:
+        self.results = results
+        self.searchable_attributes = searchable_attributes
+        if not isinstance(results, (dict, defaultdict)):
+            raise TypeError(f"expected a dict or defaultdict, received {type(results)}")
+        if len(results[ResultsFields.hits]) == 0:
+            logger.warning("empty results for re-ranking. returning doing nothing...")
+            return
+        if self.model is None:
+            self.load_model()
+        self.format_results(results)
+        if self.searchable_attributes is None:
+            self.searchable_attributes = self.formatted_results.searchable_fields
+        self.inputs = self.formatted_results.format_for_model(self.searchable_attributes, query=query)
+        if self.split_params is not None:
+            n = len(self.inputs)
+            self.inputs = self.explode_nested_content_field(self.inputs)
+            logger.info(f"chunking field content, went from length {n} to {len(self.inputs)}")
+        self.model_inputs = self._prepare_inputs(self.inputs)
+        self.scores = [float(s) for s in np.asarray(self.model.predict(self.model_inputs)).reshape(-1)]
+        if len(self.scores) != len(self.inputs):
+            raise RuntimeError(f"the model returned {len(self.scores)} scores for {len(self.inputs)} pairs")
+        for row, s in zip(self.inputs, self.scores):
+            row[ResultsFields.reranker_score] = s
+            orig = row[ResultsFields.original_score]
+            if isinstance(orig, (int, float)):    # kept for a hybrid ranking, as in the reference; nothing reads them yet
+                row[ResultsFields.hybrid_score_multiply] = max(orig, 1e-3) * max(s, 1e-3)
+                row[ResultsFields.hybrid_score_add] = orig + s
+        self.get_reranked_results()
