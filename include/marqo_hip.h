@@ -1026,6 +1026,37 @@ int mq_score_pairs_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const 
                         const int32_t* d_type_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits,
                         float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- image reranking: the OWL-ViT detection heads (csrc/owl_head.hip; engine/owl.py) ----------------------------------------------------------
+ * s2_inference/reranking/rerank.py rerank_search_results -> cross_encoders.py ReRankerOwl -> transformers' OwlViTForObjectDetection in the
+ * reference.  The image encoder is the CLIP ViT of the towers (all T rows of every image kept); these entry points are what follows it, as
+ * modeling_owlvit.py computes it (image_text_embedder, OwlViTClassPredictionHead, OwlViTBoxPredictionHead, box_predictor); the W x W linears in
+ * between are mq_gemm_bf16 calls.  Additions to ABI 14: nothing above changes.  P = T - 1 patches per image, P <= 8191; no scratch is needed.
+ *
+ *   mq_owl_merge_ln:   d_x fp32 [n T, W], class token in row 0 of every image.  c = LayerNorm(x_0; post_g, post_b), p_j = LayerNorm(x_j; post_g,
+ *                      post_b), feats[img P + j - 1] = LayerNorm(p_j * c; ln_g, ln_b) for j = 1 .. T - 1, written as bf16 (d_feats_bf16) and / or
+ *                      fp32 (d_feats_f32) [n P, W]; one eps for the three.  W % 4 == 0, W <= 2048, T >= 2.
+ *   mq_owl_class_head: d_embeds fp32 [n P, Dq] = class_head.dense0(feats); d_queries fp32 [Q, Dq] shared by every image (per_image == 0) or
+ *                      [n, Q, Dq] (per_image != 0) = the model's query_embeds; d_query_mask int32 of the same leading shape (NULL: all valid).
+ *                      Per row: z_q = (e / (|e| + 1e-6)) . (t_q / (|t_q| + 1e-6)); shift = feats . shift_w + shift_b; scale = ELU(feats . scale_w +
+ *                      scale_b) + 1; logit_q = (z_q + shift) scale, -FLT_MAX where the mask is 0.  d_logits fp32 [n P] = max_q, d_labels int32 =
+ *                      the first q that attains it, d_scores = 1 / (1 + exp(-max)).  1 <= Q <= 8.
+ *   mq_owl_box_head:   d_hidden bf16 [n P, W] = gelu(box_head.dense1(gelu(box_head.dense0(feats)))), the GELU epilogue's output; d_w2 fp32 [4, W], d_b2 fp32 [4] = dense2;
+ *                      d_box_bias fp32 [P, 4] = compute_box_bias of the grid.  (cx, cy, w, h) = sigmoid(hidden w2^T + b2 + box_bias[patch]) ->
+ *                      d_boxes fp32 [n P, 4] = (cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2) x (target_w, target_h, target_w, target_h);
+ *                      d_boxes 16-byte aligned.
+ *   mq_owl_topk:       per image the k highest of d_scores fp32 [n, P] in descending order, ties to the lower patch, NaN last: d_top_scores fp32
+ *                      [n, k], d_top_boxes fp32 [n, k, 4] (rows of d_boxes [n, P, 4]; both 16-byte aligned), d_top_patch int32 [n, k].
+ *                      1 <= k <= P (callers clamp k = min(num_highlights, P)).  One workgroup per image. */
+int mq_owl_merge_ln(const float* d_x, const float* d_post_g, const float* d_post_b, const float* d_ln_g, const float* d_ln_b, void* d_feats_bf16,
+                    float* d_feats_f32, int64_t n, int32_t T, int32_t W, float eps, void* stream);
+int mq_owl_class_head(const float* d_embeds, const float* d_feats, const float* d_queries, const int32_t* d_query_mask, int32_t per_image,
+                      const float* d_shift_w, float shift_b, const float* d_scale_w, float scale_b, float* d_scores, float* d_logits,
+                      int32_t* d_labels, int64_t n, int32_t P, int32_t W, int32_t Dq, int32_t Q, void* stream);
+int mq_owl_box_head(const void* d_hidden, const float* d_w2, const float* d_b2, const float* d_box_bias, float* d_boxes, int64_t n, int32_t P,
+                    int32_t W, float target_w, float target_h, void* stream);
+int mq_owl_topk(const float* d_scores, const float* d_boxes, int64_t n, int32_t P, int32_t k, float* d_top_scores, float* d_top_boxes,
+                int32_t* d_top_patch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head")  # build() refuses register spills in these
 ABI_VERSION = 14
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -309,6 +309,12 @@ _SIGNATURES = {
     "mq_score_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(BertCfg), C.c_int64, C.c_int64]),
     "mq_score_pairs_bert": (C.c_int, [C.POINTER(BertCfg), C.POINTER(BertWeights), C.POINTER(ScoreHeadWeights), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
                                       _P, C.c_size_t, _P]),
+    # image reranking: the OWL-ViT detection heads and top-k boxes (csrc/owl_head.hip; engine/owl.py)
+    "mq_owl_merge_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_owl_class_head": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_float, _P, C.c_float, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, _P]),
+    "mq_owl_box_head": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
+    "mq_owl_topk": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
     "mq_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

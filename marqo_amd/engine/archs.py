@@ -540,3 +540,81 @@ def bert_arch_from_hf_config(cfg: dict) -> BertArch:
                     layers=cfg["num_hidden_layers"], heads=cfg["num_attention_heads"],
                     mlp_dim=cfg["intermediate_size"], ln_eps=cfg.get("layer_norm_eps", 1e-12 if mtype == "bert" else 1e-5),
                     pos_offset=off)
+
+
+# ---- OWL-ViT (the image reranker: s2_inference/reranking/cross_encoders.py ReRankerOwl -> engine/owl.py) ---------------------------------------
+@dataclass(frozen=True)
+class OwlArch:
+    """transformers' OwlViTConfig as the engine runs it: a CLIP ViT with pre_layernorm whose every token is kept, a 16-position CLIP text tower,
+    and the detection heads.  The class head's dense0 maps the vision width to the TEXT width, and its rows are multiplied with projected text
+    embeddings, so the query dimension is both the text width and the projection dimension."""
+    image_size: int
+    patch_size: int
+    width: int
+    layers: int
+    heads: int
+    mlp_dim: int
+    text_width: int
+    text_layers: int
+    text_heads: int
+    text_mlp_dim: int
+    query_dim: int
+    vocab: int = 49408
+    ctx: int = 16
+    quick_gelu: bool = True
+    text_quick_gelu: bool = True
+    ln_eps: float = 1e-5
+    text_ln_eps: float = 1e-5
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    @property
+    def tokens(self) -> int:
+        return self.grid ** 2 + 1
+
+    def vision(self) -> VitArch:
+        return VitArch(image_size=self.image_size, patch_size=self.patch_size, width=self.width, layers=self.layers, heads=self.heads,
+                       mlp_dim=self.mlp_dim, out_dim=self.width, quick_gelu=self.quick_gelu, ln_eps=self.ln_eps)
+
+    def text(self) -> ClipTextArch:
+        return ClipTextArch(vocab=self.vocab, ctx=self.ctx, width=self.text_width, layers=self.text_layers, heads=self.text_heads,
+                            mlp_dim=self.text_mlp_dim, out_dim=self.query_dim, quick_gelu=self.text_quick_gelu, ln_eps=self.text_ln_eps)
+
+
+def _owl(patch: int, image: int, large: bool = False) -> OwlArch:
+    if large:
+        return OwlArch(image, patch, 1024, 24, 16, 4096, 768, 12, 12, 3072, 768)
+    return OwlArch(image, patch, 768, 12, 12, 3072, 512, 12, 8, 2048, 512)
+
+
+# the three published checkpoints (the names ReRankerOwl maps its model names to)
+OWL_ARCHS = {"google/owlvit-base-patch32": _owl(32, 768), "google/owlvit-base-patch16": _owl(16, 768),
+             "google/owlvit-large-patch14": _owl(14, 840, large=True)}
+
+
+def owl_arch_from_hf_config(cfg: dict, base: Optional[OwlArch] = None) -> OwlArch:
+    """A local OWL-ViT `config.json` -> OwlArch.  Keys that the file leaves out take `base`'s values (the table entry of the checkpoint's
+    name) or OwlViTConfig's defaults (= google/owlvit-base-patch32)."""
+    if cfg.get("model_type") != "owlvit":
+        raise KeyError(f"model_type={cfg.get('model_type')!r} is not 'owlvit'")
+    b = base or OWL_ARCHS["google/owlvit-base-patch32"]
+    v, t = cfg.get("vision_config") or {}, cfg.get("text_config") or {}
+    acts = {"quick_gelu": True, "gelu": False}
+    for side, c in (("vision", v), ("text", t)):
+        if c.get("hidden_act", "quick_gelu") not in acts:
+            raise KeyError(f"{side}_config.hidden_act={c.get('hidden_act')!r} unsupported (quick_gelu | gelu)")
+    text_width = int(t.get("hidden_size", b.text_width))
+    query_dim = int(cfg.get("projection_dim", b.query_dim))
+    if query_dim != text_width:
+        raise KeyError(f"projection_dim={query_dim} must equal text_config.hidden_size={text_width}: the class head multiplies rows of that width "
+                       f"with the projected text embeddings")
+    return OwlArch(image_size=int(v.get("image_size", b.image_size)), patch_size=int(v.get("patch_size", b.patch_size)),
+                   width=int(v.get("hidden_size", b.width)), layers=int(v.get("num_hidden_layers", b.layers)),
+                   heads=int(v.get("num_attention_heads", b.heads)), mlp_dim=int(v.get("intermediate_size", b.mlp_dim)),
+                   text_width=text_width, text_layers=int(t.get("num_hidden_layers", b.text_layers)),
+                   text_heads=int(t.get("num_attention_heads", b.text_heads)), text_mlp_dim=int(t.get("intermediate_size", b.text_mlp_dim)),
+                   query_dim=query_dim, vocab=int(t.get("vocab_size", b.vocab)), ctx=int(t.get("max_position_embeddings", b.ctx)),
+                   quick_gelu=acts[v.get("hidden_act", "quick_gelu")], text_quick_gelu=acts[t.get("hidden_act", "quick_gelu")],
+                   ln_eps=float(v.get("layer_norm_eps", b.ln_eps)), text_ln_eps=float(t.get("layer_norm_eps", b.text_ln_eps)))

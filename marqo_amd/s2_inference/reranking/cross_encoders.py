@@ -1,25 +1,29 @@
 """`ReRankerText`: scores every (query, chunk of a field) pair of a search result with a cross-encoder and keeps the best chunks per hit.
+`ReRankerOwl`: scores every hit's image against the query with OWL-ViT and keeps the best boxes per hit.
 
 The reference (s2_inference/reranking/cross_encoders.py:224-338, model_utils.py:242-273) does this on pandas frames around a
 sentence-transformers `CrossEncoder`; here the bookkeeping is plain Python (the product does not import pandas) with the same observable
 behaviour, and the scores come from engine/rerank.py CrossEncoderTower (csrc/rerank.hip) with sigmoid as the activation, which is what the
-reference always constructs its CrossEncoder with.
+reference always constructs its CrossEncoder with.  The image reranker (cross_encoders.py:341-461, model_utils.py:305-430) runs transformers'
+OwlViTForObjectDetection one image at a time there; here all images of a search go through engine/owl.py OwlTower (csrc/owl_head.hip) at once.
 """
 from __future__ import annotations
 
 import datetime
+import functools
 import logging
 import math
 import os
 import threading
 import uuid
 from collections import defaultdict
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from marqo_amd.s2_inference.enums import AvailableModelsKey
-from marqo_amd.s2_inference.errors import RerankerError
+from marqo_amd.s2_inference.errors import RerankerError, RerankerNameError
+from marqo_amd.s2_inference.processing import image as image_processor
 from marqo_amd.s2_inference.processing import text as text_processor
 from marqo_amd.s2_inference.reranking.configs import get_default_text_processing_parameters
 from marqo_amd.s2_inference.reranking.enums import Columns, ResultsFields
@@ -232,3 +236,120 @@ class ReRankerText(ReRanker):
                 row[ResultsFields.hybrid_score_multiply] = max(orig, 1e-3) * max(s, 1e-3)
                 row[ResultsFields.hybrid_score_add] = orig + s
         self.get_reranked_results()
+
+
+# ---- image reranking: OWL-ViT -------------------------------------------------------------------------------------------------------------------
+OWL_MODEL_MAP = {
+    "google/owlvit-base-patch32": "google/owlvit-base-patch32",
+    "google/owlvit-base-patch16": "google/owlvit-base-patch16",
+    "google/owlvit-large-patch14": "google/owlvit-large-patch14",
+    "owl/ViT-B/32": "google/owlvit-base-patch32",
+    "owl/ViT-B/16": "google/owlvit-base-patch16",
+    "owl/ViT-L/14": "google/owlvit-large-patch14",
+}
+
+
+def load_owl_vit(model_name: str, device: str) -> Dict[str, Any]:
+    """the reference's load_owl_vit for a mapped `google/owlvit-*` name: the tower lives in the model cache under
+    _create_model_cache_key(model_name, device); its checkpoint is looked up where HuggingFaceModel looks a name up, never downloaded"""
+    from marqo_amd.engine import checkpoint
+    from marqo_amd.s2_inference.s2_inference import _create_model_cache_key, get_available_models
+    key = _create_model_cache_key(model_name, device)
+    models = get_available_models()
+    entry = models.get(key)
+    if entry is None:
+        with _load_lock:
+            entry = models.get(key)
+            if entry is None:
+                logger.info(f"loading {model_name} on device {device} and adding to cache...")
+                directory = checkpoint.find_hf_dir(model_name)
+                if directory is None:
+                    raise RerankerError(f"{model_name}: the OWL-ViT image reranker is not served without a local checkpoint: looked for config.json + "
+                                        f"model.safetensors | pytorch_model.bin under {_checkpoint_candidates(model_name)} (the marqo_amd engine "
+                                        f"never downloads)")
+                from marqo_amd.engine.owl import OwlTower
+                try:
+                    model = OwlTower.from_dir(directory, device, name=model_name)
+                except (ValueError, KeyError, FileNotFoundError) as e:
+                    raise RerankerError(f"cannot load the image reranker {model_name} from {directory}: {e}") from e
+                entry = models[key] = {AvailableModelsKey.model: model, AvailableModelsKey.most_recently_used_time: datetime.datetime.now()}
+    else:
+        entry[AvailableModelsKey.most_recently_used_time] = datetime.datetime.now()
+    return {"model": entry[AvailableModelsKey.model]}
+
+
+@functools.lru_cache
+def _load_image(filename: str, size: Optional[Tuple[int, int]] = None):
+    """(the working image, its original size); cached by (pointer, size) as in the reference"""
+    from marqo_amd.s2_inference.image_input import load_image_from_path
+    im = load_image_from_path(filename, {})
+    original_size = im.size
+    if size is not None:
+        im = im.resize(size).convert("RGB")
+    return im, original_size
+
+
+class ReRankerOwl(ReRanker):
+    """reranking of image fields with OWL-ViT: a hit's score is the score of its image's best box for the query, its highlight that box in
+    the pixels of the original image"""
+
+    def __init__(self, model_name: str, device: str, image_size: Tuple[int, int]):
+        super().__init__()
+        self.model_name = model_name
+        self.device = device
+        self.image_size = image_size
+        self.model = None
+        self.image_attributes = None
+        self.num_highlights = None
+        self._model_map = dict(OWL_MODEL_MAP)
+        if self.model_name not in self._model_map:
+            raise RerankerNameError(f"could not find model_name={self.model_name} in mappings {list(self._model_map.keys())}")
+
+    def load_model(self) -> None:
+        self._remapped_name = self._model_map[self.model_name]
+        logger.info(f"loading model={self._remapped_name} from input name={self.model_name} to device {self.device}")
+        self.model = load_owl_vit(self._remapped_name, device=self.device)["model"]
+
+    @staticmethod
+    def load_images(content: Sequence[str], size: Tuple[int, int]):
+        """-> (working images, original sizes), through the loader every image model uses"""
+        if not len(content):
+            return (), ()
+        images, original_size = zip(*[_load_image(f, size=size) for f in content])
+        return images, original_size
+
+    def rerank(self, query: str, results: Dict, image_attributes: List, num_highlights: int = 1) -> None:
+        self.results = results
+        self.image_attributes = image_attributes
+        self.num_highlights = num_highlights
+        if not isinstance(results, (dict, defaultdict)):
+            raise TypeError(f"expected a dict or defaultdict, received {type(results)}")
+        if len(results[ResultsFields.hits]) == 0:
+            logger.warning("empty results for re-ranking. returning doing nothing...")
+            return
+        if self.model is None:
+            self.load_model()
+        self.format_results(results, searchable_fields=image_attributes)
+        self.inputs = self.formatted_results.format_for_model(self.image_attributes, query=query)
+        self.model_inputs = self._prepare_inputs(self.inputs)
+        image_names = [pair[1] for pair in self.model_inputs]
+        self.images, self.original_sizes = self.load_images(image_names, self.image_size)
+        # every image of the search in one detect(): scores [n, k], boxes [n, k, 4] in the working image's pixels, best first
+        pixels = np.stack([np.asarray(im, dtype=np.uint8) for im in self.images]) if len(self.images) else np.zeros((0, *self.image_size[::-1], 3), np.uint8)
+        try:
+            scores, boxes, _ = self.model.detect(query, pixels, k=num_highlights, target_size=self.image_size)
+        except ValueError as e:        # (a query beyond the model's 16 positions)
+            raise RerankerError(str(e)) from e
+        boxes_scores = []
+        for i, (content, orig_size) in enumerate(zip(image_names, self.original_sizes)):
+            for j in range(scores.shape[1]):
+                box = [float(v) for v in boxes[i, j]]
+                boxes_scores.append({Columns.bbox: box, ResultsFields.reranker_score: float(scores[i, j]), Columns.field_content: content,
+                                     Columns.bbox_original: list(image_processor.rescale_box(box, self.image_size, orig_size))})
+        # merged back by the image pointer, as the reference's frame merge does: a box row meets every hit row with its image, so two hits that
+        # share an image each see that image's rows once per hit
+        by_content: Dict[Any, List[Dict[str, Any]]] = defaultdict(list)
+        for row in self.inputs:
+            by_content[row[Columns.field_content]].append(row)
+        self.inputs = [{**row, **bs} for bs in boxes_scores for row in by_content[bs[Columns.field_content]]]
+        self.get_reranked_results(highlight_content_column=Columns.bbox_original)
