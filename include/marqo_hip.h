@@ -1057,6 +1057,28 @@ int mq_owl_box_head(const void* d_hidden, const float* d_w2, const float* d_b2, 
 int mq_owl_topk(const float* d_scores, const float* d_boxes, int64_t n, int32_t P, int32_t k, float* d_top_scores, float* d_top_boxes,
                 int32_t* d_top_patch, void* stream);
 
+/* ---- LanguageBind video tower: the temporal sub-block and the clip-layout front end (csrc/temporal.hip; engine/languagebind.py) ---------------
+ * s2_inference/languagebind/video/modeling_video.py:209-231 in the reference: in front of every CLIP block, a per-frame temporal embedding is
+ * added into the residual stream, a temporal LayerNorm follows, a second attention attends ACROSS the T frames at each spatial token, and a residual
+ * add closes the sub-block.  The activation keeps the frame-major order of the spatial blocks throughout: row r = (b T + t) N + n (clip b, frame t,
+ * token n); the reference's `(b t) n d <-> (b n) t d` transposes are never materialised.  The QKV / out-projection GEMMs are mq_gemm_bf16 calls.
+ * Additions to ABI 14: nothing above changes.  No scratch is needed.
+ *
+ *   mq_temporal_embed_ln:  d_x fp32 [B T N, W], in place: x[r, :] += d_temb[t, :] (d_temb fp32 [T, W]; one fp32 add per element; skipped when
+ *                          T == 1, as the reference skips it), then d_out_bf16 [B T N, W] = LayerNorm(x[r]; g, b) of the updated row.  One pass over
+ *                          the row.  W % 4 == 0, W <= 2048.
+ *   mq_temporal_attention: d_qkv bf16 [B T N, 3W] in mq_attention's column layout (q | k | v, head h owns columns 64 h .. 64 h + 63 of each third),
+ *                          d_out bf16 [B T N, W] in the same row order.  For every (b, n, head): out = softmax(q k^T / 8) v, unmasked, over the T
+ *                          rows {(b T + t) N + n}.  Scores, softmax and the P V sums are fp32 (the probabilities are not rounded); every q / k / v
+ *                          element is read once.  W == 64 heads and 1 <= T <= 16, anything else is MQ_ERR_INVALID and launches nothing.  Both
+ *                          pointers 16-byte aligned.
+ *   mq_patchify_clip:      d_in fp32 [B, 3, T, S, S] (the `pixel_values` layout `b c t h w`) -> d_out bf16 [B T (S/P)^2, Kp]: the rows mq_patchify
+ *                          (is_u8 == 0) writes for the B T frames in (b t) order, bit for bit.  Kp % 8 == 0, Kp >= 3 P^2. */
+int mq_temporal_embed_ln(float* d_x, const float* d_temb, const float* d_g, const float* d_b, void* d_out_bf16, int64_t B, int32_t T, int32_t N,
+                         int32_t W, float eps, void* stream);
+int mq_temporal_attention(const void* d_qkv, void* d_out, int64_t B, int32_t T, int32_t N, int32_t W, int32_t heads, void* stream);
+int mq_patchify_clip(const float* d_in, void* d_out, int64_t B, int32_t T, int32_t S, int32_t P, int32_t Kp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -618,3 +618,65 @@ def owl_arch_from_hf_config(cfg: dict, base: Optional[OwlArch] = None) -> OwlArc
                    query_dim=query_dim, vocab=int(t.get("vocab_size", b.vocab)), ctx=int(t.get("max_position_embeddings", b.ctx)),
                    quick_gelu=acts[v.get("hidden_act", "quick_gelu")], text_quick_gelu=acts[t.get("hidden_act", "quick_gelu")],
                    ln_eps=float(v.get("layer_norm_eps", b.ln_eps)), text_ln_eps=float(t.get("layer_norm_eps", b.text_ln_eps)))
+
+
+# ---- LanguageBind (the multimodal loader: s2_inference/multimodal_model_load.py -> engine/languagebind.py) --------------------------------------
+@dataclass(frozen=True)
+class LanguageBindArch:
+    """One LanguageBind part (the reference's languagebind/{video,image}/configuration_*.py) as the engine runs it: a CLIP ViT with
+    `pre_layrnorm` whose class rows are pooled, with `add_time_attn` a temporal sub-block in front of every layer and the mean over the
+    `num_frames` class rows of a clip, and a 77-position CLIP text tower.  Both project to `projection_dim`."""
+    image_size: int
+    patch_size: int
+    width: int
+    layers: int
+    heads: int
+    mlp_dim: int
+    num_frames: int
+    add_time_attn: bool
+    text_width: int
+    text_layers: int
+    text_heads: int
+    text_mlp_dim: int
+    out_dim: int
+    vocab: int = 49408
+    ctx: int = 77
+    quick_gelu: bool = False
+    text_quick_gelu: bool = False
+    ln_eps: float = 1e-5
+    text_ln_eps: float = 1e-5
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    @property
+    def tokens(self) -> int:
+        return self.grid ** 2 + 1
+
+    def vision(self) -> VitArch:
+        return VitArch(image_size=self.image_size, patch_size=self.patch_size, width=self.width, layers=self.layers, heads=self.heads,
+                       mlp_dim=self.mlp_dim, out_dim=self.out_dim, quick_gelu=self.quick_gelu, ln_eps=self.ln_eps)
+
+    def text(self) -> ClipTextArch:
+        return ClipTextArch(vocab=self.vocab, ctx=self.ctx, width=self.text_width, layers=self.text_layers, heads=self.text_heads,
+                            mlp_dim=self.text_mlp_dim, out_dim=self.out_dim, quick_gelu=self.text_quick_gelu, ln_eps=self.text_ln_eps)
+
+
+def languagebind_arch_from_hf_config(cfg: dict) -> LanguageBindArch:
+    """A local LanguageBind `config.json` -> LanguageBindArch.  Keys the file leaves out take the defaults of the reference's configuration
+    classes (CLIP ViT-B/32-like sides, 512-wide projection, quick_gelu, one frame, no temporal attention)."""
+    v, t = cfg.get("vision_config") or {}, cfg.get("text_config") or {}
+    acts = {"quick_gelu": True, "gelu": False}
+    for side, c in (("vision", v), ("text", t)):
+        if c.get("hidden_act", "quick_gelu") not in acts:
+            raise KeyError(f"{side}_config.hidden_act={c.get('hidden_act')!r} unsupported (quick_gelu | gelu)")
+    return LanguageBindArch(image_size=int(v.get("image_size", 224)), patch_size=int(v.get("patch_size", 32)), width=int(v.get("hidden_size", 768)),
+                            layers=int(v.get("num_hidden_layers", 12)), heads=int(v.get("num_attention_heads", 12)),
+                            mlp_dim=int(v.get("intermediate_size", 3072)), num_frames=int(v.get("num_frames", 1)),
+                            add_time_attn=bool(v.get("add_time_attn", False)), text_width=int(t.get("hidden_size", 512)),
+                            text_layers=int(t.get("num_hidden_layers", 12)), text_heads=int(t.get("num_attention_heads", 8)),
+                            text_mlp_dim=int(t.get("intermediate_size", 2048)), out_dim=int(cfg.get("projection_dim", 512)),
+                            vocab=int(t.get("vocab_size", 49408)), ctx=int(t.get("max_position_embeddings", 77)),
+                            quick_gelu=acts[v.get("hidden_act", "quick_gelu")], text_quick_gelu=acts[t.get("hidden_act", "quick_gelu")],
+                            ln_eps=float(v.get("layer_norm_eps", 1e-5)), text_ln_eps=float(t.get("layer_norm_eps", 1e-5)))

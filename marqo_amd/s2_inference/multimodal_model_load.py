@@ -1,0 +1,186 @@
+"""The `languagebind` loader: the engine's `MultimodalModel` and `LanguageBindEncoder` (reference: s2_inference/multimodal_model_load.py:42-115,
+204-311; the model itself: s2_inference/languagebind/__init__.py:33-64).  Written from the behaviour, not from the text, of those classes.
+
+What is served: the two names whose parts are video, image and text — `LanguageBind/Video_V1.5_FT` and `LanguageBind/Video_V1.5_FT_Image` — on
+the HIP towers of engine/languagebind.py, modalities VIDEO, IMAGE and TEXT.  What is not:
+  * the audio tower (spectrogram front end, non-square grid): the four names with an audio part are refused at load with
+    InvalidModelPropertiesError naming that part;
+  * decoding media: no video / audio decoder is a dependency of this engine, and the reference's video processor applies a RANDOM horizontal
+    flip.  VIDEO content is what the reference's caller hands over after ITS preprocessing: `pixel_values` [b, 3, T, S, S];
+  * fp8 ('enginePrecision': 'fp8' is refused like the ConvNeXt towers: bf16 only);
+  * downloads: `localpath` in model_properties names a directory with one sub-directory per part (LanguageBind_Video_V1.5_FT,
+    LanguageBind_Image), each a Hugging Face checkpoint directory (config.json, model.safetensors | pytorch_model.bin, vocab.json, merges.txt).
+
+The names are reached through `model_properties` (the reference's registry dict for the name, plus `localpath`), as the NLLB-CLIP names are: the
+registry's 204 names and 12 loader keys are pinned by tests.  `s2_inference._load_model`, `validate_model_properties` and `get_encoder`
+special-case `type == "languagebind"` where the reference does (s2_inference.py:173,382,539).
+
+One difference from the reference: for a list of `pixel_values` dicts EVERY item is encoded (the reference reads `content[0]` only,
+multimodal_model_load.py:285-287); for a one-item list the result is the same.
+"""
+from __future__ import annotations
+
+import threading
+from typing import Any, Dict, List, Optional
+
+import numpy as np
+import torch
+
+from marqo_amd.s2_inference.enums import Modality
+from marqo_amd.s2_inference.errors import InvalidModelPropertiesError, ModelLoadError
+
+SERVED_MODALITIES = (Modality.VIDEO, Modality.IMAGE, Modality.TEXT)
+
+
+class MultimodalModelProperties:
+    """multimodal_model_load.py:42-49 (a pydantic model there): name, loader, supported_modalities, dimensions, video_chunk_length and
+    audio_chunk_length are required; `type` defaults to "multimodal"; other keys (localpath, model_size, ...) are ignored here"""
+    REQUIRED = ("name", "loader", "supported_modalities", "dimensions", "video_chunk_length", "audio_chunk_length")
+
+    def __init__(self, **p: Any):
+        missing = [k for k in self.REQUIRED if k not in p]
+        if missing:
+            raise InvalidModelPropertiesError(f"model_properties of a multimodal model has missing key(s) {missing}; required: {list(self.REQUIRED)}")
+        if not isinstance(p["name"], str) or not isinstance(p["loader"], str):
+            raise InvalidModelPropertiesError("model_properties 'name' and 'loader' of a multimodal model must be strings")
+        try:
+            self.supported_modalities: List[Modality] = [Modality(m) for m in p["supported_modalities"]]
+        except (ValueError, TypeError) as e:
+            raise InvalidModelPropertiesError(f"model_properties 'supported_modalities' must be a list of {[m.value for m in Modality]}: {e}") from e
+        for k in ("dimensions", "video_chunk_length", "audio_chunk_length"):
+            if isinstance(p[k], bool) or not isinstance(p[k], int):
+                raise InvalidModelPropertiesError(f"model_properties '{k}' of a multimodal model must be an integer, received {p[k]!r}")
+        self.name, self.loader, self.dimensions = p["name"], p["loader"], p["dimensions"]
+        self.type = p.get("type", "multimodal")
+        self.video_chunk_length, self.audio_chunk_length = p["video_chunk_length"], p["audio_chunk_length"]
+
+
+class MultimodalModel:
+    """multimodal_model_load.py:52-115.  `model` is the engine's LanguageBindModel (the towers), `encoder` the LanguageBindEncoder in front of it."""
+
+    def __init__(self, model_name: str, model_properties: Dict[str, Any], device: str):
+        self.model_name = model_name
+        self.model_properties = dict(model_properties)
+        self.properties = MultimodalModelProperties(**model_properties)
+        self.device = device
+        self.model = None
+        self.encoder = None
+        self.clip_type: Optional[Dict[str, str]] = None
+
+    def _load_multimodal_model(self):
+        if self.properties.loader == "languagebind":
+            return self._load_languagebind_model()
+        raise ValueError(f"Unsupported loader: {self.properties.loader}")
+
+    def _load_languagebind_model(self):
+        from marqo_amd.engine import languagebind as LB
+        if self.model_name not in LB.MODEL_PARTS:
+            raise ValueError(f"Unsupported LanguageBind model: {self.model_name}")
+        parts = LB.MODEL_PARTS[self.model_name]
+        if "audio" in parts:
+            raise InvalidModelPropertiesError(f"{self.model_name}: its audio part {parts['audio']} is not supported by this engine (no audio tower); "
+                                              f"the names served are {[n for n, p in LB.MODEL_PARTS.items() if 'audio' not in p]}")
+        precision = str(self.model_properties.get("enginePrecision", "bf16")).lower()
+        if precision != "bf16":
+            raise InvalidModelPropertiesError(f"{self.model_name}: LanguageBind towers run on bf16 operands only ('enginePrecision': {precision!r} is not supported)")
+        self.clip_type = dict(parts)
+        try:
+            return LB.LanguageBindModel(self.model_name, self.model_properties.get("localpath"), self.device)
+        except FileNotFoundError as e:
+            raise ModelLoadError(f"Unable to load {self.model_name}: {e}") from e
+
+    def load(self) -> None:
+        self.model = self._load_multimodal_model()
+        self.encoder = LanguageBindEncoder(self)
+
+    def preprocessor(self, modality):
+        if self.encoder is None:
+            raise ValueError("Model has not been loaded yet. Call _load_model() first.")
+        return self.encoder.preprocessor(modality)
+
+    def encode(self, content, modality, **kwargs):
+        if self.encoder is None:
+            raise ValueError("Model has not been loaded yet. Call _load_model() first.")
+        return self.encoder.encode(content, modality, **kwargs)
+
+
+def video_pixel_values(content, modality: Modality = Modality.VIDEO) -> List[torch.Tensor]:
+    """What VIDEO content may be -> the list of `pixel_values` tensors to encode, each [b, 3, T, S, S], in order:
+    a list of dicts with a `pixel_values` tensor (what the reference's caller hands over, multimodal_model_load.py:285-287; every item, not only
+    the first), one such dict, or such a tensor itself.  Anything else — URLs included: nothing here decodes media — raises ValueError with the
+    reference's message (:291)."""
+    bad = lambda: ValueError(f"Unsupported {modality.value} content type: {type(content)}, content: {content}")
+    if isinstance(content, torch.Tensor):
+        items = [content]
+    elif isinstance(content, dict):
+        items = [content]
+    elif isinstance(content, (list, tuple)) and len(content) > 0:
+        items = list(content)
+    else:
+        raise bad()
+    out = []
+    for it in items:
+        if isinstance(it, dict) and isinstance(it.get("pixel_values"), torch.Tensor):
+            it = it["pixel_values"]
+        if not isinstance(it, torch.Tensor) or it.ndim != 5:
+            raise bad()
+        out.append(it)
+    return out
+
+
+class LanguageBindEncoder:
+    """multimodal_model_load.py:204-311 on the engine's towers.  encode(content, modality, normalize) -> np.ndarray fp32 [n, D]:
+    with normalize every row is unit; without, a video or image row is the unit vector times exp(logit_scale) of its part and a text row is the
+    unit vector (languagebind/__init__.py:59-63)."""
+
+    def __init__(self, model: MultimodalModel):
+        self.model = model
+        self._local = threading.local()
+
+    def preprocessor(self, modality):
+        """The reference returns its video / audio / image processor objects here; media decoding is out of this engine's scope: None"""
+        return None
+
+    def _image_pre(self):
+        p = getattr(self._local, "pre", None)
+        if p is None:
+            from marqo_amd.engine.preprocess import ImagePreprocessor
+            lb = self.model.model
+            p = self._local.pre = ImagePreprocessor(str(lb.image.device), lb.image.arch.image_size)
+        return p
+
+    def _encode_images(self, content, normalize: bool, image_download_headers: Optional[dict]) -> torch.Tensor:
+        """what the image loaders accept (PIL image, path or URL, uint8 ndarray, preprocessed tensor; one or a list): Resize(S, bicubic) +
+        CenterCrop(S) + the OpenAI mean / std of the reference's LanguageBindImageProcessor, on the GPU"""
+        from marqo_amd.s2_inference.image_input import format_and_load_CLIP_image, pil_to_pixels
+        lb = self.model.model
+        if lb.image is None:
+            raise ValueError(f"{self.model.model_name} has no image part")
+        if isinstance(content, torch.Tensor) and content.ndim == 4:
+            return lb.encode_image_f32(content, normalize)
+        items = list(content) if isinstance(content, (list, tuple)) else [content]
+        loaded = [i if isinstance(i, np.ndarray) and i.dtype == np.uint8 and i.ndim == 3 and i.shape[2] == 3
+                  else format_and_load_CLIP_image(i, image_download_headers or {}) for i in items]
+        if all(isinstance(i, torch.Tensor) for i in loaded):
+            return lb.encode_image_f32(torch.stack([t.to(lb.image.device) for t in loaded]), normalize)
+        if any(isinstance(i, torch.Tensor) for i in loaded):
+            raise ValueError("a list of images is either all preprocessed tensors or none")
+        with torch.cuda.device(lb.image.device):
+            u8 = self._image_pre().resize_crop_u8([i if isinstance(i, np.ndarray) else pil_to_pixels(i) for i in loaded])
+        return lb.encode_image_u8(u8, normalize)
+
+    def encode(self, content, modality, normalize=True, image_download_headers: Optional[dict] = None, **kwargs):
+        lb = self.model.model
+        if lb is None:
+            raise ValueError("Model has not been loaded yet. Call _load_model() first.")
+        modality = Modality(modality) if not isinstance(modality, Modality) else modality
+        if modality == Modality.TEXT:
+            texts = [content] if isinstance(content, str) else list(content)
+            out = lb.encode_text(texts, bool(normalize))
+        elif modality == Modality.IMAGE:
+            out = self._encode_images(content, bool(normalize), image_download_headers)
+        elif modality == Modality.VIDEO:
+            out = torch.cat([lb.encode_video(px, bool(normalize)) for px in video_pixel_values(content, modality)], dim=0)
+        else:
+            raise ValueError(f"Unsupported {modality.value} content type: {type(content)}, content: {content}")
+        return out.cpu().numpy()

@@ -34,6 +34,7 @@ from marqo_amd.s2_inference.errors import (ConfigurationError, InternalError, In
                                            ModelCacheManagementError, ModelDownloadError, ModelLoadError,
                                            ModelNotInCacheError, UnknownModelError, VectoriseError)
 from marqo_amd.s2_inference import coalesce as _coalesce
+from marqo_amd.s2_inference import multimodal_model_load as _multimodal   # (reached through its own namespace: no names of it are re-exported here)
 from marqo_amd.s2_inference.inference_cache import MarqoInferenceCache
 from marqo_amd.s2_inference.model_registry import load_model_properties
 
@@ -71,6 +72,11 @@ class DefaultEncoder:
 
 
 def get_encoder(model):
+    """s2_inference.py:171-177"""
+    if isinstance(model, _multimodal.MultimodalModel):
+        if model.properties.loader == "languagebind":
+            return model.encoder if model.encoder is not None else _multimodal.LanguageBindEncoder(model)
+        raise NotImplementedError(f"Model {model.model_name} is not supported")
     return DefaultEncoder(model)
 
 
@@ -122,7 +128,8 @@ def infer_modality(content, media_download_headers: Optional[dict] = None, timeo
     """multimodal_model_load.py:148-203, the function the reference's search and add_documents paths import FROM this module
     (tensor_search.py:74, add_docs.py:24-25).  A string that is not a URL is text; a URL is classified by its extension (image / video /
     audio lists of the reference), else by the first 10 KB of what it serves; bytes by their signature; anything else is text.  Video and
-    audio are only NAMED here (the callers answer them with UnsupportedModalityError for every model family this engine runs)."""
+    Video is served by the LanguageBind names (s2_inference/multimodal_model_load.py: preprocessed `pixel_values`, nothing here decodes media);
+    the callers answer it with UnsupportedModalityError for every other model family, and audio for all of them."""
     if isinstance(content, str):
         if not validate_url(content):
             return Modality.TEXT
@@ -457,6 +464,8 @@ def validate_model_properties(model_name: str, model_properties: dict) -> dict:
         elif model_type in (ModelType.Test, ModelType.Random, ModelType.MultilingualClip, ModelType.FP16_CLIP,
                             ModelType.SBERT_ONNX, ModelType.CLIP_ONNX):
             pass
+        elif model_type in (ModelType.LanguageBind,):
+            _multimodal.MultimodalModelProperties(**model_properties)
         else:
             raise InvalidModelPropertiesError(
                 "Invalid model type. Please check the model type in model_properties. Supported model types are "
@@ -542,6 +551,10 @@ def _load_model(model_name: str, model_properties: dict, device: str, calling_fu
         raise RuntimeError(f"The function `{_load_model.__name__}` should only be called by "
                            f"`unit_test` or `_update_available_models` for threading safeness.")
     model_type = model_properties.get("type")
+    if model_type in (ModelType.LanguageBind,):
+        model = _multimodal.MultimodalModel(model_name, model_properties, device)
+        model.load()
+        return model
     loader = _get_model_loader(model_properties.get("name", None), model_properties)
     if model_type in (ModelType.OpenCLIP, ModelType.HF_MODEL, ModelType.HF_STELLA):
         model = loader(device=device, model_properties=model_properties, model_auth=model_auth)
