@@ -20,65 +20,42 @@ import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine.archs import DINO_MEAN, DINO_STD, VitArch, dino_arch
-from marqo_amd.engine.towers import MAX_ROWS_PER_CALL, _ImageTowerBase, _check_precision, _clip_blocks, _encoder_cfg, _need, _TIMM_KEYS
+from marqo_amd.engine.towers import _need, _TIMM_KEYS
+from marqo_amd.engine.vit_tokens import VitTokenTower
 
 Tensor = torch.Tensor
 MODE_MEAN, MODE_PER_HEAD = 0, 1     # mq_attn_boxes: 'abs' (dino-v1) / 'pos' (dino-v2) of the reference's _process_attention
 
 
-class DinoTower(_ImageTowerBase):
+class DinoTower(VitTokenTower):
     """facebookresearch/dino state dict (`cls_token`, `pos_embed`, `patch_embed.proj.*`, `blocks.N.*`, `norm`) -> class-token attention maps and
     their boxes.  `DinoTower(arch, sd, device)` or `DinoTower(arch, None, device, synthetic=seed)`; bf16 operands only."""
 
     def __init__(self, arch: VitArch, sd: Optional[Dict[str, Tensor]], device: str, precision: str = "bf16", synthetic: Optional[int] = None):
-        super().__init__(device)
-        _check_precision(precision, ("bf16",), "DinoTower runs on bf16 operands only")
+        super().__init__(device, arch, precision, arch.layers - 1)
         if sd is None:
             if synthetic is None:
                 raise ValueError("DinoTower needs a state dict or a synthetic= seed")
             from marqo_amd.engine.synthetic import random_dino_state_dict
             sd = random_dino_state_dict(arch, seed=int(synthetic))
-        self.precision, self.arch = precision, arch
-        W, P, S = arch.width, arch.patch_size, arch.image_size
-        if arch.heads * 64 != W:
-            raise ValueError(f"DinoTower runs 64-wide heads (width {W}, heads {arch.heads})")
-        if arch.layers < 1 or S % P or S // P > 32:
-            raise ValueError(f"DinoTower: image {S} / patch {P} must give a whole grid of at most 32 x 32 patches, and the model at least one block")
-        self.grid = S // P
-        K = 3 * P * P
-        self.Kp = (K + 63) // 64 * 64
-        h = self._h
-        patch_w = torch.zeros(W, self.Kp, dtype=torch.float32)
-        patch_w[:, :K] = _need(sd, "patch_embed.proj.weight", (W, 3, P, P)).detach().to(torch.float32).reshape(W, K)
+        W = arch.width
+        if self.grid > 32:
+            raise ValueError(f"DinoTower: image {arch.image_size} / patch {arch.patch_size} must give a grid of at most 32 x 32 patches")
         pos = _need(sd, "pos_embed", (1, arch.tokens, W)).detach().to(torch.float32)[0].clone()
         pos[1:] += _need(sd, "patch_embed.proj.bias", (W,)).detach().to(torch.float32)
-        self._patch_w, self._pos = h.bf16(patch_w), h.f32(pos)
-        self._cls = h.f32(_need(sd, "cls_token", (1, 1, W)).detach().to(torch.float32).reshape(W))
         _need(sd, "norm.weight", (W,))     # (part of the checkpoint's contract; the attention maps are read in front of it)
-        self._blocks = _clip_blocks(h, sd, "", arch.layers, W, arch.mlp_dim, arch.heads, keys=_TIMM_KEYS)
-        self.enc = _encoder_cfg(W, arch.layers - 1, arch.heads, arch.mlp_dim, False, False, L.MQ_MASK_NONE, arch.ln_eps)
-        self.enc.residual_stream = 2
+        self._load_vit(sd, "patch_embed.proj.weight", _need(sd, "cls_token", (1, 1, W)).reshape(W), pos, None, sd, "", _TIMM_KEYS)
         self.mean, self.std = (C.c_float * 3)(*DINO_MEAN), (C.c_float * 3)(*DINO_STD)
-        self.max_images_per_call = max(1, MAX_ROWS_PER_CALL // arch.tokens)
         self.max_boxes = ((self.grid + 1) // 2) ** 2       # isolated cells on every other row and column: no map has more components
 
     # ---- one call of m images: uint8 [m, S, S, 3] on the device -> fp32 [m, heads, T - 1] -------------------------------------------------------
     def _probs_call(self, u8: Tensor, out: Tensor) -> None:
         lib, a, s = self.lib, self.arch, self._stream()
-        m, W, T, G = u8.shape[0], a.width, a.tokens, self.grid
+        m, W, T = u8.shape[0], a.width, a.tokens
         rows, dev = m * T, self.device
-        patches = torch.empty(m * G * G, self.Kp, dtype=torch.bfloat16, device=dev)
-        patch_out = torch.empty(m * G * G, W, dtype=torch.float32, device=dev)
-        x = torch.empty(rows, W, dtype=torch.float32, device=dev)
-        L.check(lib.mq_patchify(u8.data_ptr(), 1, patches.data_ptr(), m, a.image_size, a.patch_size, self.Kp, C.addressof(self.mean), C.addressof(self.std), s),
-                "mq_patchify")
-        L.check(lib.mq_gemm_bf16(patches.data_ptr(), self.Kp, self._patch_w, self.Kp, None, None, patch_out.data_ptr(), W, m * G * G, W, self.Kp,
-                                 L.MQ_EPI_OUT_F32, s), "mq_gemm_bf16")
-        L.check(lib.mq_vit_assemble(patch_out.data_ptr(), self._cls, self._pos, None, None, x.data_ptr(), m, T, W, a.ln_eps, 0, s), "mq_vit_assemble")
+        x = self._tokens(self._patchify(u8), m)
         if self.enc.layers > 0:
-            ws = self._workspace(lib.mq_encoder_workspace_bytes(C.byref(self.enc), rows, m))
-            L.check(lib.mq_encoder_forward(C.byref(self.enc), self._blocks, x.data_ptr(), rows, None, m, T, T, ws.data_ptr(), ws.numel(), s),
-                    "mq_encoder_forward")
+            self._encoder(x, m, self._encoder_workspace(m))
         # The last block's norm1 and QKV run as mq_layernorm + mq_gemm_bf16, not as the encoder's LN-folded QKV GEMM: that fold takes its row statistics
         # from the bf16 residual stream, and this tower keeps the stream in fp32 (the maps are thresholded between two uint8 levels).  The buffers
         # below are allocated per call: one call per indexed image, off the throughput path.  (_clip_blocks prepares the folded qkv / fc1 tensors for
@@ -91,20 +68,14 @@ class DinoTower(_ImageTowerBase):
                 "mq_gemm_bf16")
         L.check(lib.mq_attention_cls_probs(qkv.data_ptr(), out.data_ptr(), m, T, W, a.heads, s), "mq_attention_cls_probs")
 
-    def _check_images(self, images_u8: Tensor) -> Tensor:
-        S = self.arch.image_size
-        if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
-            raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-        return images_u8.to(self.device, non_blocking=True).contiguous()
-
     def probs(self, images_u8: Tensor) -> Tensor:
         """uint8 [n, S, S, 3] (HWC RGB) -> fp32 [n, heads, G * G] on the device: the class token's attention over the patch keys in the last block"""
-        u8 = self._check_images(images_u8)
+        u8 = self._check_u8(images_u8)
         n, a = u8.shape[0], self.arch
         with torch.cuda.device(self.device):
             out = torch.empty(n, a.heads, a.tokens - 1, dtype=torch.float32, device=self.device)
-            for i in range(0, n, self.max_images_per_call):
-                self._probs_call(u8[i:i + self.max_images_per_call], out[i:i + self.max_images_per_call])
+            for i in range(0, n, self.max_items_per_call):
+                self._probs_call(u8[i:i + self.max_items_per_call], out[i:i + self.max_items_per_call])
         return out
 
     def boxes_from_probs(self, probs: Tensor, mode: int) -> Tuple[Tensor, Tensor]:

@@ -22,7 +22,6 @@ text tower is `towers.ClipTextTower` on 77 positions, packed up to the EOT as ev
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Dict, Optional
 
@@ -32,10 +31,10 @@ import torch
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
 from marqo_amd.engine.archs import LanguageBindArch
-from marqo_amd.engine.owl import clip_state_dict, load_tokenizer
+from marqo_amd.engine.hf_clip import clip_state_dict, clip_text_state_dict, load_tokenizer
 from marqo_amd.engine.tokenizers import ClipBpeTokenizer
-from marqo_amd.engine.towers import (MAX_ROWS_PER_CALL, ClipTextTower, VitTower, _ImageTowerBase, _check_precision, _clip_blocks, _encoder_cfg,
-                                     _need, request_stream)
+from marqo_amd.engine.towers import ClipTextTower, VitTower, _check_precision, _need, request_stream
+from marqo_amd.engine.vit_tokens import VitTokenTower
 
 Tensor = torch.Tensor
 MAX_FRAMES = 16        # mq_temporal_attention
@@ -67,17 +66,6 @@ def vision_state_dict(sd: Dict[str, Tensor], arch: LanguageBindArch) -> Dict[str
     return out
 
 
-def text_state_dict(sd: Dict[str, Tensor], arch: LanguageBindArch) -> Dict[str, Tensor]:
-    """`text_model.*` + `text_projection.weight` -> the open_clip names ClipTextTower loads"""
-    t = "text_model."
-    out = clip_state_dict(sd, t, arch.text_layers)
-    out["token_embedding.weight"] = _need(sd, t + "embeddings.token_embedding.weight", (arch.vocab, arch.text_width))
-    out["positional_embedding"] = _need(sd, t + "embeddings.position_embedding.weight", (arch.ctx, arch.text_width))
-    out["ln_final.weight"], out["ln_final.bias"] = _need(sd, t + "final_layer_norm.weight"), _need(sd, t + "final_layer_norm.bias")
-    out["text_projection"] = _need(sd, "text_projection.weight", (arch.out_dim, arch.text_width)).detach().to(torch.float32).t().contiguous()
-    return out
-
-
 def temporal_weights(sd: Dict[str, Tensor], arch: LanguageBindArch, layer: int) -> Dict[str, Tensor]:
     """the temporal sub-block of one layer as fp32 host tensors: qkv_w [3W, W] (q | k | v packed), qkv_b [3W], out_w [W, W], out_b [W],
     ln_g / ln_b [W], temb [T, W] (the checkpoint's [1, T, W])"""
@@ -90,45 +78,25 @@ def temporal_weights(sd: Dict[str, Tensor], arch: LanguageBindArch, layer: int) 
             "temb": f32("temporal_embedding", (1, T, W))[0].contiguous()}
 
 
-class LanguageBindVideoTower(_ImageTowerBase):
+class LanguageBindVideoTower(VitTokenTower):
     """`LanguageBindVideo` vision side (`vision_model.*`, `visual_projection.weight`) -> one embedding per clip.  bf16 operands only."""
 
     def __init__(self, arch: LanguageBindArch, sd: Dict[str, Tensor], device: str, precision: str = "bf16"):
-        super().__init__(device)
-        _check_precision(precision, ("bf16",), f"the LanguageBind video tower runs on bf16 operands only, got precision {precision!r}")
-        self.precision, self.arch = precision, arch
-        W, P, S, T = arch.width, arch.patch_size, arch.image_size, arch.num_frames
+        # one block per mq_encoder_forward call: the temporal sub-block sits between the blocks
+        super().__init__(device, arch, precision, 1, frames=arch.num_frames)
+        W, T = arch.width, arch.num_frames
         if not arch.add_time_attn:
             raise ValueError("LanguageBindVideoTower is the tower with temporal attention (vision_config.add_time_attn); a part without it is a CLIP ViT")
-        if arch.heads * 64 != W or W > 2048:
-            raise ValueError(f"LanguageBindVideoTower runs 64-wide attention heads and widths up to 2048 (width {W} with {arch.heads} heads)")
-        if not 1 <= T <= MAX_FRAMES:
-            raise ValueError(f"LanguageBindVideoTower takes 1 to {MAX_FRAMES} frames per clip, the checkpoint has num_frames = {T}")
-        if arch.layers < 1 or S % P or arch.tokens > 8192 or arch.out_dim % 4 or arch.out_dim > 2048:
-            raise ValueError(f"LanguageBindVideoTower: image {S} / patch {P} must give a whole grid of at most 8191 patches, the model at least one "
-                             f"block and a projection dimension that is a multiple of 4, at most 2048 (got {arch.out_dim})")
-        K = 3 * P * P
-        self.Kp = (K + 63) // 64 * 64
+        if not 1 <= T <= MAX_FRAMES or arch.out_dim % 4 or arch.out_dim > 2048:
+            raise ValueError(f"LanguageBindVideoTower takes 1 to {MAX_FRAMES} frames per clip and a projection dimension that is a multiple of 4, at most "
+                             f"2048 (the checkpoint has num_frames = {T}, projection_dim = {arch.out_dim})")
         h = self._h
-        f32 = lambda k, shape=None: _need(sd, k, shape).detach().to(torch.float32)
-        v = "vision_model."
-        patch_w = torch.zeros(W, self.Kp, dtype=torch.float32)
-        patch_w[:, :K] = f32(v + "embeddings.patch_embedding.weight", (W, 3, P, P)).reshape(W, K)
-        self._patch_w = h.bf16(patch_w)
-        self._cls = h.f32(f32(v + "embeddings.class_embedding", (W,)))
-        self._pos = h.f32(f32(v + "embeddings.position_embedding.weight", (arch.tokens, W)))
-        self._pre = (h.f32(f32(v + "pre_layrnorm.weight", (W,))), h.f32(f32(v + "pre_layrnorm.bias", (W,))))
-        self._post = (h.f32(f32(v + "post_layernorm.weight", (W,))), h.f32(f32(v + "post_layernorm.bias", (W,))))
-        self._proj = h.bf16(f32("visual_projection.weight", (arch.out_dim, W)))
-        self._blocks = _clip_blocks(h, clip_state_dict(sd, v, arch.layers), "transformer.", arch.layers, W, arch.mlp_dim, arch.heads)
+        self._load_hf_vit(sd, "vision_model.", "pre_layrnorm")
+        self._proj = h.bf16(_need(sd, "visual_projection.weight", (arch.out_dim, W)))
         self._temporal = []
         for i in range(arch.layers):
             t = temporal_weights(sd, arch, i)
             self._temporal.append({k: (h.bf16(t[k]) if k in ("qkv_w", "out_w") else h.f32(t[k])) for k in t})
-        # one block per mq_encoder_forward call: the temporal sub-block sits between the blocks
-        self.enc = _encoder_cfg(W, 1, arch.heads, arch.mlp_dim, arch.quick_gelu, False, L.MQ_MASK_NONE, arch.ln_eps)
-        self.enc.residual_stream = 2
-        self.max_clips_per_call = max(1, MAX_ROWS_PER_CALL // (T * arch.tokens))
 
     def _forward(self, px: Tensor, out: Tensor, normalize: bool) -> None:
         """px fp32 [b, 3, T, S, S] on the device (contiguous) -> out fp32 [b, D]"""
@@ -137,16 +105,13 @@ class LanguageBindVideoTower(_ImageTowerBase):
         frames, rows, G2 = b * T, b * T * N, a.grid ** 2
         bf16 = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
         f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        patches, patch_out, x = bf16(frames * G2, self.Kp), f32(frames * G2, W), f32(rows, W)
+        patches = bf16(frames * G2, self.Kp)
         L.check(lib.mq_patchify_clip(px.data_ptr(), patches.data_ptr(), b, T, a.image_size, a.patch_size, self.Kp, s), "mq_patchify_clip")
-        L.check(lib.mq_gemm_bf16(patches.data_ptr(), self.Kp, self._patch_w, self.Kp, None, None, patch_out.data_ptr(), W, frames * G2, W, self.Kp,
-                                 L.MQ_EPI_OUT_F32, s), "mq_gemm_bf16")
-        L.check(lib.mq_vit_assemble(patch_out.data_ptr(), self._cls, self._pos, self._pre[0], self._pre[1], x.data_ptr(), frames, N, W, a.ln_eps, 0, s),
-                "mq_vit_assemble")
-        del patches, patch_out
+        x = self._tokens(patches, frames)
+        del patches
         # the per-layer path's scratch, once per call
         xn, qkv, att = bf16(rows, W), bf16(rows, 3 * W), bf16(rows, W)
-        ws = self._workspace(lib.mq_encoder_workspace_bytes(C.byref(self.enc), rows, frames))
+        ws = self._encoder_workspace(frames)
         res = L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL | L.MQ_EPI_OUT_F32
         for i in range(a.layers):
             t = self._temporal[i]
@@ -156,8 +121,7 @@ class LanguageBindVideoTower(_ImageTowerBase):
                     "mq_gemm_bf16")
             L.check(lib.mq_temporal_attention(qkv.data_ptr(), att.data_ptr(), b, T, N, W, a.heads, s), "mq_temporal_attention")
             L.check(lib.mq_gemm_bf16(att.data_ptr(), W, t["out_w"], W, t["out_b"], x.data_ptr(), x.data_ptr(), W, rows, W, W, res, s), "mq_gemm_bf16")
-            L.check(lib.mq_encoder_forward(C.byref(self.enc), C.byref(self._blocks[i]), x.data_ptr(), rows, None, frames, N, N, ws.data_ptr(),
-                                           ws.numel(), s), "mq_encoder_forward")
+            self._encoder(x, frames, ws, first=i)
         cls_rows = torch.empty(frames, dtype=torch.int32, device=dev)
         cls_ln, proj = bf16(frames, W), f32(frames, D)
         pooled = out if not normalize else f32(b, D)
@@ -181,8 +145,8 @@ class LanguageBindVideoTower(_ImageTowerBase):
             px = pixel_values.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
             n = px.shape[0]
             out = torch.empty(n, a.out_dim, dtype=torch.float32, device=self.device)
-            for i in range(0, n, self.max_clips_per_call):
-                j = min(n, i + self.max_clips_per_call)
+            for i in range(0, n, self.max_items_per_call):
+                j = min(n, i + self.max_items_per_call)
                 self._forward(px[i:j], out[i:j], bool(normalize))
         return out
 
@@ -229,7 +193,7 @@ class LanguageBindModel:
         self.tokenizer: ClipBpeTokenizer = load_tokenizer(last_dir, last_arch.ctx)
         if self.tokenizer.eot_id >= last_arch.vocab:
             raise ValueError(f"the tokenizer's EOT id {self.tokenizer.eot_id} is outside the model's vocabulary of {last_arch.vocab}")
-        self.text = ClipTextTower(last_arch.text(), text_state_dict(last_sd, last_arch), device, precision="bf16")
+        self.text = ClipTextTower(last_arch.text(), clip_text_state_dict(last_sd, "text_model.", "text_projection.weight", last_arch.text()), device)
         self.text.release_unused_folded()
 
     # ---- text ----------------------------------------------------------------------------------------------------------------------------------

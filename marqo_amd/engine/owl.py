@@ -19,8 +19,6 @@ not one pooled row, and this is one call per search, not the throughput path.
 from __future__ import annotations
 
 import ctypes as C
-import json
-import os
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -29,12 +27,13 @@ import torch
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
 from marqo_amd.engine.archs import OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, OwlArch
+from marqo_amd.engine.hf_clip import clip_text_state_dict, load_tokenizer
 from marqo_amd.engine.tokenizers import ClipBpeTokenizer
-from marqo_amd.engine.towers import MAX_ROWS_PER_CALL, ClipTextTower, _ImageTowerBase, _check_precision, _clip_blocks, _encoder_cfg, _need, request_stream
+from marqo_amd.engine.towers import ClipTextTower, _need, request_stream
+from marqo_amd.engine.vit_tokens import VitTokenTower
 
 Tensor = torch.Tensor
 MAX_QUERIES = 8        # mq_owl_class_head
-HF_SOT, HF_EOT = "<|startoftext|>", "<|endoftext|>"
 
 
 def box_bias(grid: int) -> Tensor:
@@ -52,79 +51,24 @@ def box_bias(grid: int) -> Tensor:
     return torch.cat([coord, torch.log(size + 1e-4) - torch.log1p(-size + 1e-4)], dim=-1).contiguous()
 
 
-def clip_state_dict(sd: Dict[str, Tensor], prefix: str, layers: int) -> Dict[str, Tensor]:
-    """transformers' CLIP-style encoder layers under `prefix` (encoder.layers.N.{self_attn.{q,k,v,out}_proj, layer_norm1, mlp.fc1, mlp.fc2,
-    layer_norm2}) -> open_clip's `transformer.resblocks.N.*` names, q | k | v packed, as _clip_blocks loads them"""
-    out = {}
-    for i in range(layers):
-        p, o = f"{prefix}encoder.layers.{i}.", f"transformer.resblocks.{i}."
-        for kind in ("weight", "bias"):
-            out[o + "attn.in_proj_" + kind] = torch.cat([_need(sd, p + f"self_attn.{n}_proj.{kind}").detach().to(torch.float32) for n in "qkv"], dim=0)
-            for src, dst in (("self_attn.out_proj", "attn.out_proj"), ("layer_norm1", "ln_1"), ("layer_norm2", "ln_2"), ("mlp.fc1", "mlp.c_fc"),
-                             ("mlp.fc2", "mlp.c_proj")):
-                out[o + dst + "." + kind] = _need(sd, p + src + "." + kind)
-    return out
-
-
-def load_tokenizer(directory: str, ctx: int) -> ClipBpeTokenizer:
-    """vocab.json + merges.txt of a Hugging Face CLIP tokenizer -> the engine's CLIP BPE tokenizer, after checking that the ids the merges imply
-    (byte units, byte units + </w>, merges in order, SOT, EOT) are the ids vocab.json assigns"""
-    merges_path, vocab_path = os.path.join(directory, "merges.txt"), os.path.join(directory, "vocab.json")
-    for p in (merges_path, vocab_path):
-        if not os.path.isfile(p):
-            raise FileNotFoundError(f"{p} not found: the OWL-ViT query tokenizer needs vocab.json and merges.txt")
-    with open(merges_path, encoding="utf-8") as f:
-        lines = f.read().split("\n")
-    merges = [tuple(ln.split()) for ln in lines if ln.strip() and not ln.startswith("#version")]
-    if any(len(m) != 2 for m in merges):
-        raise ValueError(f"{merges_path}: every line must hold two symbols")
-    tok = ClipBpeTokenizer(merges, context_length=ctx)
-    with open(vocab_path, encoding="utf-8") as f:
-        vocab = json.load(f)
-    names = {tok.SOT: HF_SOT, tok.EOT: HF_EOT}
-    bad = [(t, i, vocab.get(names.get(t, t))) for t, i in tok.encoder.items() if vocab.get(names.get(t, t)) != i]
-    if bad or len(vocab) != len(tok.encoder):
-        raise ValueError(f"{vocab_path} does not number the tokens as its merges.txt implies ({len(vocab)} entries against {len(tok.encoder)}; "
-                         f"first disagreements (token, implied id, vocab.json id): {bad[:3]})")
-    return tok
-
-
-class OwlTower(_ImageTowerBase):
+class OwlTower(VitTokenTower):
     """`OwlViTForObjectDetection` state dict (`owlvit.vision_model.*`, `owlvit.text_model.*`, `owlvit.text_projection`, `class_head.*`,
     `box_head.*`, `layer_norm.*`) -> per-patch scores and boxes, and the k best per image.  bf16 operands only."""
 
     def __init__(self, arch: OwlArch, sd: Dict[str, Tensor], device: str, tokenizer: ClipBpeTokenizer, precision: str = "bf16"):
-        super().__init__(device)
-        _check_precision(precision, ("bf16",), "OwlTower runs on bf16 operands only")
-        self.precision, self.arch, self.tokenizer = precision, arch, tokenizer
-        W, P, S, Dq = arch.width, arch.patch_size, arch.image_size, arch.query_dim
-        if arch.heads * 64 != W or arch.text_heads * 64 != arch.text_width:
-            raise ValueError(f"OwlTower runs 64-wide attention heads (vision width {W} with {arch.heads} heads, text width {arch.text_width} with "
-                             f"{arch.text_heads} heads)")
-        if arch.layers < 1 or S % P or arch.tokens > 8192:
-            raise ValueError(f"OwlTower: image {S} / patch {P} must give a whole grid of at most 8191 patches, and the model at least one block")
-        if W > 2048 or Dq > 2048 or Dq % 4 or Dq != arch.text_width:
-            raise ValueError(f"OwlTower: widths up to 2048, a query dimension that is a multiple of 4 and equals the text width (W {W}, query {Dq}, "
-                             f"text {arch.text_width})")
+        super().__init__(device, arch, precision, arch.layers)
+        self.tokenizer = tokenizer
+        W, Dq = arch.width, arch.query_dim
+        if arch.text_heads * 64 != arch.text_width or Dq > 2048 or Dq % 4 or Dq != arch.text_width:
+            raise ValueError(f"OwlTower runs 64-wide attention heads and a query dimension up to 2048 that is a multiple of 4 and equals the text "
+                             f"width (text width {arch.text_width} with {arch.text_heads} heads, query {Dq})")
         if tokenizer.eot_id >= arch.vocab:
             raise ValueError(f"the tokenizer's EOT id {tokenizer.eot_id} is outside the model's vocabulary of {arch.vocab}")
-        self.grid, self.patches = arch.grid, arch.grid ** 2
-        K = 3 * P * P
-        self.Kp = (K + 63) // 64 * 64
+        self.patches = self.grid ** 2
         h = self._h
         f32 = lambda k, shape=None: _need(sd, k, shape).detach().to(torch.float32)
-        v = "owlvit.vision_model."
-        patch_w = torch.zeros(W, self.Kp, dtype=torch.float32)
-        patch_w[:, :K] = f32(v + "embeddings.patch_embedding.weight", (W, 3, P, P)).reshape(W, K)
-        self._patch_w = h.bf16(patch_w)
-        self._cls = h.f32(f32(v + "embeddings.class_embedding", (W,)))
-        self._pos = h.f32(f32(v + "embeddings.position_embedding.weight", (arch.tokens, W)))
-        self._pre = (h.f32(f32(v + "pre_layernorm.weight", (W,))), h.f32(f32(v + "pre_layernorm.bias", (W,))))
-        self._post = (h.f32(f32(v + "post_layernorm.weight", (W,))), h.f32(f32(v + "post_layernorm.bias", (W,))))
+        self._load_hf_vit(sd, "owlvit.vision_model.", "pre_layernorm")
         self._merge = (h.f32(f32("layer_norm.weight", (W,))), h.f32(f32("layer_norm.bias", (W,))))
-        self._blocks = _clip_blocks(h, clip_state_dict(sd, v, arch.layers), "transformer.", arch.layers, W, arch.mlp_dim, arch.heads)
-        self.enc = _encoder_cfg(W, arch.layers, arch.heads, arch.mlp_dim, arch.quick_gelu, False, L.MQ_MASK_NONE, arch.ln_eps)
-        self.enc.residual_stream = 2
         # heads
         self._cls0 = (h.bf16(f32("class_head.dense0.weight", (Dq, W))), h.f32(f32("class_head.dense0.bias", (Dq,))))
         self._shift_w, self._shift_b = h.f32(f32("class_head.logit_shift.weight", (1, W)).reshape(W)), float(f32("class_head.logit_shift.bias", (1,))[0])
@@ -134,15 +78,8 @@ class OwlTower(_ImageTowerBase):
         self._box2 = (h.f32(f32("box_head.dense2.weight", (4, W))), h.f32(f32("box_head.dense2.bias", (4,))))
         self._box_bias = h.f32(box_bias(self.grid))
         self.mean, self.std = (C.c_float * 3)(*OPENAI_DATASET_MEAN), (C.c_float * 3)(*OPENAI_DATASET_STD)
-        self.max_images_per_call = max(1, MAX_ROWS_PER_CALL // arch.tokens)
         # the query side: the CLIP text tower on 16 positions
-        t = "owlvit.text_model."
-        tsd = clip_state_dict(sd, t, arch.text_layers)
-        tsd["token_embedding.weight"] = _need(sd, t + "embeddings.token_embedding.weight", (arch.vocab, arch.text_width))
-        tsd["positional_embedding"] = _need(sd, t + "embeddings.position_embedding.weight", (arch.ctx, arch.text_width))
-        tsd["ln_final.weight"], tsd["ln_final.bias"] = _need(sd, t + "final_layer_norm.weight"), _need(sd, t + "final_layer_norm.bias")
-        tsd["text_projection"] = f32("owlvit.text_projection.weight", (Dq, arch.text_width)).t().contiguous()
-        self.text = ClipTextTower(arch.text(), tsd, str(self.device), precision="bf16")
+        self.text = ClipTextTower(arch.text(), clip_text_state_dict(sd, "owlvit.text_model.", "owlvit.text_projection.weight", arch.text()), str(self.device))
         self.text.release_unused_folded()
 
     @classmethod
@@ -197,20 +134,8 @@ class OwlTower(_ImageTowerBase):
         """uint8 [m, S, S, 3] on the device -> feats (bf16, fp32) [m P, W]: encoder, post_layernorm, class-token merge, layer_norm"""
         lib, a, s, dev = self.lib, self.arch, self._stream(), self.device
         m, W, T, P = u8.shape[0], a.width, a.tokens, self.patches
-        rows = m * T
-        patches = torch.empty(m * P, self.Kp, dtype=torch.bfloat16, device=dev)
-        patch_out = torch.empty(m * P, W, dtype=torch.float32, device=dev)
-        x = torch.empty(rows, W, dtype=torch.float32, device=dev)
-        L.check(lib.mq_patchify(u8.data_ptr(), 1, patches.data_ptr(), m, a.image_size, a.patch_size, self.Kp, C.addressof(self.mean),
-                                C.addressof(self.std), s), "mq_patchify")
-        L.check(lib.mq_gemm_bf16(patches.data_ptr(), self.Kp, self._patch_w, self.Kp, None, None, patch_out.data_ptr(), W, m * P, W, self.Kp,
-                                 L.MQ_EPI_OUT_F32, s), "mq_gemm_bf16")
-        L.check(lib.mq_vit_assemble(patch_out.data_ptr(), self._cls, self._pos, self._pre[0], self._pre[1], x.data_ptr(), m, T, W, a.ln_eps, 0, s),
-                "mq_vit_assemble")
-        del patches, patch_out
-        ws = self._workspace(lib.mq_encoder_workspace_bytes(C.byref(self.enc), rows, m))
-        L.check(lib.mq_encoder_forward(C.byref(self.enc), self._blocks, x.data_ptr(), rows, None, m, T, T, ws.data_ptr(), ws.numel(), s),
-                "mq_encoder_forward")
+        x = self._tokens(self._patchify(u8), m)
+        self._encoder(x, m, self._encoder_workspace(m))
         fb = torch.empty(m * P, W, dtype=torch.bfloat16, device=dev)
         ff = torch.empty(m * P, W, dtype=torch.float32, device=dev)
         L.check(lib.mq_owl_merge_ln(x.data_ptr(), self._post[0], self._post[1], self._merge[0], self._merge[1], fb.data_ptr(), ff.data_ptr(), m, T, W,
@@ -268,8 +193,8 @@ class OwlTower(_ImageTowerBase):
             logit = torch.empty(n, P, dtype=torch.float32, device=dev)
             label = torch.empty(n, P, dtype=torch.int32, device=dev)
             boxes = torch.empty(n, P, 4, dtype=torch.float32, device=dev)
-            for i in range(0, n, self.max_images_per_call):
-                j = min(n, i + self.max_images_per_call)
+            for i in range(0, n, self.max_items_per_call):
+                j = min(n, i + self.max_items_per_call)
                 fb, ff = self.features(self.resize(u8[i:j]))
                 self.heads(fb, ff, emb, mask, j - i, target_size, score[i:j], logit[i:j], label[i:j], boxes[i:j])
         return score, logit, label, boxes

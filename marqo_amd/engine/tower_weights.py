@@ -98,6 +98,13 @@ def _ceil64(v: int) -> int:
     return (v + 63) // 64 * 64
 
 
+def patch_embed_weight(sd: Dict[str, Tensor], key: str, W: int, P: int) -> Tensor:
+    """the patch-embedding conv weight sd[key] [W, 3, P, P] -> fp32 [W, Kp]: the GEMM's operand, K = 3 P P columns in (c, ky, kx) order,
+    zero-padded to Kp = the next multiple of 64 (the tiled GEMMs' k-step; callers read Kp from the result's shape)"""
+    K = 3 * P * P
+    return torch.nn.functional.pad(_need(sd, key, (W, 3, P, P)).detach().to(torch.float32).reshape(W, K), (0, _ceil64(K) - K))
+
+
 def _pad_mlp(fc1_w: Tensor, fc1_b: Tensor, fc2_w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """MLP hidden sizes that are not a multiple of 64 (ViT-SO400M: 4304) are zero-padded: the extra hidden units are act(0 + 0) = 0
     for GELU / QuickGELU and meet zero fc2 columns — exact."""
@@ -335,9 +342,7 @@ def convnext_downsample_gather(x_nhwc: Tensor) -> Tensor:
 RESNET_BN_EPS = 1e-5
 
 
-def resnet_pad64(c: int) -> int:
-    """channel count as the tower stores it: zero-padded to a multiple of 64 (the tiled GEMMs' k-step)"""
-    return (c + 63) // 64 * 64
+resnet_pad64 = _ceil64     # channel count as the tower stores it: zero-padded to a multiple of 64 (the tiled GEMMs' k-step)
 
 
 def resnet_fold_bn(conv_w: Tensor, bn_w: Tensor, bn_b: Tensor, bn_mean: Tensor, bn_var: Tensor, eps: float = RESNET_BN_EPS) -> Tuple[Tensor, Tensor]:
@@ -353,7 +358,7 @@ def resnet_conv3x3_weight(w: Tensor, cin: int, cout: int) -> Tensor:
     O, I = w.shape[:2]
     full = torch.zeros(cout, 3, 3, cin, dtype=torch.float32)
     full[:O, :, :, :I] = w.permute(0, 2, 3, 1).float()
-    Kp = (9 * cin + 63) // 64 * 64
+    Kp = _ceil64(9 * cin)
     out = torch.zeros(cout, Kp, dtype=torch.float32)
     out[:, :9 * cin] = full.reshape(cout, 9 * cin)
     return out

@@ -30,7 +30,7 @@ from marqo_amd.engine.archs import BertArch, ClipTextArch, VitArch, OPENAI_DATAS
 from marqo_amd.engine.tower_weights import (  # noqa: F401  (re-exported: tests, tools and the loaders reach them as towers.<name>)
     EVA_GLU_EPILOGUE, KERNEL_HEAD_DIMS, LN_FOLD, RESNET_BN_EPS, _OPEN_CLIP_KEYS, _TIMM_KEYS, _Holder, _bert_blocks, _ceil64, _clip_blocks,
     _eva_blocks, _head_dim, _kernel_head_dim, _need, _pad_heads, _pad_mlp, convnext_downsample_gather, convnext_downsample_weight,
-    convnext_dw_taps, convnext_fold_gamma_fc2, convnext_fold_ln_fc1, fold_layernorm, nllb_clip_state_dict, resnet_attnpool_weights,
+    convnext_dw_taps, convnext_fold_gamma_fc2, convnext_fold_ln_fc1, fold_layernorm, nllb_clip_state_dict, patch_embed_weight, resnet_attnpool_weights,
     resnet_conv1x1_weight, resnet_conv3x3_weight, resnet_fold_bn, resnet_pad64, resnet_pad_vec, resnet_stem_weight)
 
 Tensor = torch.Tensor
@@ -655,12 +655,15 @@ class _ImageTowerBase(_TowerBase):
         with torch.cuda.device(self.device):
             return self._run_chunks(kind, pixels, normalize)
 
-    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
-        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
+    def _check_u8(self, images_u8: Tensor) -> Tensor:
         S = self.arch.image_size
         if images_u8.dtype != torch.uint8 or images_u8.ndim != 4 or tuple(images_u8.shape[1:]) != (S, S, 3):
             raise ValueError(f"expected uint8 [n, {S}, {S}, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-        return self._run("u8", images_u8.to(self.device, non_blocking=True).contiguous(), normalize)
+        return images_u8.to(self.device, non_blocking=True).contiguous()
+
+    def encode_u8(self, images_u8: Tensor, normalize: bool = True) -> Tensor:
+        """uint8 [n, S, S, 3] (HWC RGB, on this device) -> fp32 [n, D] on device (async on the current stream)."""
+        return self._run("u8", self._check_u8(images_u8), normalize)
 
     def encode_f32(self, pixels: Tensor, normalize: bool = True) -> Tensor:
         """preprocessed fp32 [n, 3, S, S] -> fp32 [n, D] on device."""
@@ -686,10 +689,8 @@ class VitTower(_ImageTowerBase):
             raise ValueError("image_size must be at least one patch")
         # (an image size that is not a multiple of the patch — ViT-SO400M-14-SigLIP-384: 384 = 27 * 14 + 6 — follows the strided conv:
         # floor(S / P) patches per side, the trailing pixels are not read)
-        K = 3 * P * P
-        Kp = (K + 63) // 64 * 64
         h = self._h
-        patch_w = torch.zeros(W, Kp, dtype=torch.float32)
+        patch_w = patch_embed_weight(sd, "visual.trunk.patch_embed.proj.weight" if arch.pool == "map" or arch.eva else "visual.conv1.weight", W, P)
         if arch.pool == "map":
             # timm SigLIP ViT as open_clip's `visual.trunk` (no class token, no ln_pre, conv bias, attention-pool head, no proj)
             t = "visual.trunk."
@@ -697,7 +698,6 @@ class VitTower(_ImageTowerBase):
             hd = _head_dim(W, arch.heads)
             if arch.out_dim != W:
                 raise ValueError(f"SigLIP towers have no visual projection: out_dim {arch.out_dim} must equal the width {W}")
-            patch_w[:, :K] = _need(sd, t + "patch_embed.proj.weight", (W, 3, P, P)).detach().to(torch.float32).reshape(W, K)
             pos = _need(sd, t + "pos_embed", (1, arch.tokens, W)).detach().to(torch.float32)[0] + \
                 _need(sd, t + "patch_embed.proj.bias", (W,)).detach().to(torch.float32)  # the conv bias rides on the position table
             self._blocks = _clip_blocks(h, sd, t, arch.layers, W, F, arch.heads, keys=_TIMM_KEYS)
@@ -720,7 +720,6 @@ class VitTower(_ImageTowerBase):
             D, Hp = arch.out_dim, arch.pool_heads
             if D % Hp or (D // Hp) % 8 or D // Hp > 128 or D % 64 or D > W:
                 raise ValueError(f"attentional pooler of width {D} with {Hp} heads is not runnable (head dim a multiple of 8, <= 128; width a multiple of 64, <= {W})")
-            patch_w[:, :K] = _need(sd, "visual.conv1.weight", (W, 3, P, P)).detach().to(torch.float32).reshape(W, K)
             self._blocks = _clip_blocks(h, sd, "visual.transformer.", arch.layers, W, arch.mlp_dim, arch.heads)
             a = "visual.attn_pool."
             f32 = lambda k, shape: _need(sd, a + k, shape).detach().to(torch.float32)
@@ -751,7 +750,6 @@ class VitTower(_ImageTowerBase):
                 raise ValueError("EVA02 towers run on the bf16 path with the class-token head")
             t = "visual.trunk."
             f32 = lambda k, shape: _need(sd, t + k, shape).detach().to(torch.float32)
-            patch_w[:, :K] = f32("patch_embed.proj.weight", (W, 3, P, P)).reshape(W, K)
             pos = f32("pos_embed", (1, arch.tokens, W))[0].clone()
             pos[1:] += f32("patch_embed.proj.bias", (W,))
             self._blocks = _eva_blocks(h, sd, t, arch.layers, W, arch.mlp_dim, arch.heads)
@@ -761,7 +759,6 @@ class VitTower(_ImageTowerBase):
                                   proj_w=h.bf16(f32("head.weight", (arch.out_dim, W))), map=None, proj_b=h.f32(f32("head.bias", (arch.out_dim,))))
             pool, map_mlp = L.MQ_VIT_POOL_CLS, 0
         else:
-            patch_w[:, :K] = _need(sd, "visual.conv1.weight", (W, 3, P, P)).detach().to(torch.float32).reshape(W, K)
             self._blocks = _clip_blocks(h, sd, "visual.transformer.", arch.layers, W, arch.mlp_dim, arch.heads)
             if arch.pool == "avg" and arch.ln_pre:
                 raise ValueError("pool 'avg' is built for the no_ln_pre / final_ln_after_pool form (CLIPA)")

@@ -214,7 +214,7 @@ def _props(name, root):
 
 def test_vectorise_end_to_end(tmp_path, monkeypatch):
     from PIL import Image
-    from marqo_amd.engine.owl import load_tokenizer
+    from marqo_amd.engine.hf_clip import load_tokenizer
     from marqo_amd.s2_inference import s2_inference as S
     from marqo_amd.s2_inference.enums import Modality
     monkeypatch.setenv("MARQO_MAX_CUDA_MODEL_MEMORY", "64")

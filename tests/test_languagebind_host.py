@@ -6,7 +6,7 @@ import copy
 import pytest
 import torch
 
-from marqo_amd.engine import archs
+from marqo_amd.engine import archs, hf_clip
 from marqo_amd.engine import languagebind as LB
 from marqo_amd.s2_inference import multimodal_model_load as MM
 from marqo_amd.s2_inference import s2_inference as S
@@ -134,7 +134,7 @@ def test_key_to_weight_mapping():
     assert torch.equal(v["visual.transformer.resblocks.0.attn.in_proj_weight"][W:2 * W], sd["vision_model.encoder.layers.0.self_attn.k_proj.weight"])
     assert torch.equal(v["visual.transformer.resblocks.0.mlp.c_fc.weight"], sd["vision_model.encoder.layers.0.mlp.fc1.weight"])
     assert v["visual.positional_embedding"].shape == (a.tokens, W)
-    x = LB.text_state_dict(sd, a)
+    x = hf_clip.clip_text_state_dict(sd, "text_model.", "text_projection.weight", a.text())
     assert x["text_projection"].shape == (a.text_width, D) and x["positional_embedding"].shape == (77, a.text_width)
     assert torch.equal(x["ln_final.bias"], sd["text_model.final_layer_norm.bias"])
     bad = dict(sd)

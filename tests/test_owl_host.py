@@ -16,7 +16,8 @@ import owl_ref as O  # noqa: E402
 import test_owl_gpu as G  # noqa: E402  (the measured tolerances and the seeds of the tower tests)
 from marqo_amd import _lib as L  # noqa: E402
 from marqo_amd.engine import archs  # noqa: E402
-from marqo_amd.engine.owl import OwlTower, box_bias, load_tokenizer  # noqa: E402
+from marqo_amd.engine.hf_clip import load_tokenizer  # noqa: E402
+from marqo_amd.engine.owl import OwlTower, box_bias  # noqa: E402
 from marqo_amd.s2_inference.errors import RerankerError, RerankerNameError  # noqa: E402
 from marqo_amd.s2_inference.reranking import cross_encoders, rerank  # noqa: E402
 from oracle import ref_shim  # noqa: E402

@@ -51,6 +51,19 @@ def test_fold_layernorm_matches_the_unfolded_linear_of_a_layernorm():
     torch.testing.assert_close(out, ref, rtol=1e-5, atol=1e-4)
 
 
+@pytest.mark.parametrize("W,P,K,Kp", [(128, 16, 768, 768), (128, 14, 588, 640), (64, 32, 3072, 3072)])    # no padding, padding, a larger patch
+def test_patch_embed_weight_pads_the_reshaped_conv_weight_with_zeros(W, P, K, Kp):
+    conv = torch.randn(W, 3, P, P, generator=torch.Generator().manual_seed(W + P))
+    got = TW.patch_embed_weight({"conv": conv}, "conv", W, P)
+    assert 3 * P * P == K and got.shape == (W, Kp) and Kp % 64 == 0 and got.dtype == torch.float32 and got.is_contiguous()
+    assert torch.equal(got[:, :K], conv.reshape(W, K)) and not got[:, K:].any()
+    for bad in (conv[:, :, :, :-1], conv[:-1], conv.reshape(W, K)):
+        with pytest.raises(ValueError, match=r"checkpoint tensor 'conv' has shape .*, expected \(%d, 3, %d, %d\)" % (W, P, P)):
+            TW.patch_embed_weight({"conv": bad}, "conv", W, P)
+    with pytest.raises(KeyError, match="checkpoint is missing tensor 'conv'"):
+        TW.patch_embed_weight({}, "conv", W, P)
+
+
 def _fields(h, block):
     """field name -> the holder tensor a block's pointer field points at"""
     by_ptr = {t.data_ptr(): t for t in h.tensors}
@@ -149,6 +162,6 @@ def test_towers_module_keeps_resolving_the_moved_names():
                  "_OPEN_CLIP_KEYS", "_TIMM_KEYS", "_clip_blocks", "_eva_blocks", "_bert_blocks", "nllb_clip_state_dict", "convnext_dw_taps",
                  "convnext_fold_ln_fc1", "convnext_fold_gamma_fc2", "convnext_downsample_weight", "convnext_downsample_gather", "RESNET_BN_EPS",
                  "resnet_pad64", "resnet_fold_bn", "resnet_conv3x3_weight", "resnet_conv1x1_weight", "resnet_stem_weight", "resnet_pad_vec",
-                 "resnet_attnpool_weights"):
+                 "resnet_attnpool_weights", "patch_embed_weight"):
         assert getattr(towers, name) is getattr(TW, name), name
     assert towers._encoder_cfg.__module__ == towers.__name__ and towers._Fp8State.__module__ == towers.__name__
