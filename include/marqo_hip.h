@@ -959,7 +959,9 @@ int mq_queue_destroy(mq_queue* q);
  * (row limits of the skinny GEMM kernels), "ln_prefetch", "xcd_band", "attn_waves" (0 = auto, 4 / 8 wave64s per attention workgroup),
  * "attn_proj" (ABI 13: fewest fixed-length sequences from which a ViT-B/32-shaped block runs mq_attention_proj instead of attention + out-projection +
  * finalise, 0 = never; default 128, MQ_ATTN_PROJ), "panel_gemm" (ABI 13: fewest fixed-length sequences from which the folded QKV / fc1 GEMMs of a 768-wide
- * tower run as mq_panel_gemm_ln; default 0 = never, MQ_PANEL_GEMM).
+ * tower run as mq_panel_gemm_ln; default 0 = never, MQ_PANEL_GEMM), "pool_strided" (0 = the ViT class-token rows of the pooled last block and the head
+ * go through an index vector, two gathers and a scatter instead of being read and updated where they lie; default 1, MQ_POOL_STRIDED), "assemble_stats"
+ * (0 = a row-statistics pass over x behind the ViT token assembly instead of the (mean, rstd) the assembly leaves itself; default 1, MQ_ASSEMBLE_STATS).
  * Initial values come from the environment (MQ_GEMM_MT, MQ_GEMM_CGROUP, MQ_GEMM_NH, MQ_GEMM_TAIL, MQ_GEMM_WD, MQ_GEMM_RS_FIN, MQ_ROW_SELECT,
  * MQ_LN_FOLD, ...). */
 int mq_tune(const char* key, int value);

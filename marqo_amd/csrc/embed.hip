@@ -122,10 +122,15 @@ __global__ __launch_bounds__(256) void patchify_u8x8_kernel(const uint8_t* __res
 // row (b, t): t == 0 ? cls : patch_out[b*np + t-1];  + pos[t];  LayerNorm(ln_pre) -> x fp32
 // cls == nullptr: no class token (T = np; timm / SigLIP ViTs), gam == nullptr: no ln_pre (their patch bias is folded into pos)
 constexpr int MAXC = 8;
-template <int CH>
+// ST (bf16 stream with ln_pre only, W % 8 == 0): the wave also leaves (mean, rstd) of the bf16 row it stores in stats[row] — what the first block's folded
+// LayerNorm reads (gemm_epilogue.h, MQ_EPI_LN_APPLY), so no statistics pass over x follows.  The packed row goes through LDS into the lane layout of
+// row_stats_bf16_kernel (rowops.hip: 8 elements per lane and chunk) and takes that kernel's arithmetic in its order: the same bits.
+template <int CH, bool ST = false>
 __global__ __launch_bounds__(256, (CH <= 4 ? 8 : 4)) void vit_assemble_kernel(
     const float* __restrict__ patch_out, const float* __restrict__ cls, const float* __restrict__ pos,
-    const float* __restrict__ gam, const float* __restrict__ bet, float* __restrict__ x, int64_t rows, int T, int W, float eps, int x_bf16) {
+    const float* __restrict__ gam, const float* __restrict__ bet, float* __restrict__ x, int64_t rows, int T, int W, float eps, int x_bf16,
+    float2* __restrict__ stats = nullptr, const unsigned* __restrict__ pfa = nullptr, unsigned na = 0u, const unsigned* __restrict__ pfb = nullptr, unsigned nb = 0u) {
+    __shared__ __attribute__((aligned(16))) uint2 srow[ST ? 4 : 1][ST ? CH * 64 : 1];
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -135,6 +140,7 @@ __global__ __launch_bounds__(256, (CH <= 4 ? 8 : 4)) void vit_assemble_kernel(
             q.x = pack_bf16x2(y[0], y[1]);
             q.y = pack_bf16x2(y[2], y[3]);
             *(uint2*)((bf16_t*)x + row * W + c * 4) = q;
+            if constexpr (ST) srow[threadIdx.x >> 6][c] = q;
         } else {
             *(f32x4*)(x + row * W + c * 4) = y;
         }
@@ -170,6 +176,50 @@ __global__ __launch_bounds__(256, (CH <= 4 ? 8 : 4)) void vit_assemble_kernel(
             for (int e = 0; e < 4; ++e) y[e] = v[i][e] * gg[e] + bb[e];
             put(c, y);
         }
+    }
+    if constexpr (ST) {
+        // the weight prefetch the statistics launch carried (rowops.hip, LnExtra): thread t of the grid touches one dword of 128-byte line t of the first
+        // block's QKV / out-projection weights (values unused), behind the row's own loads and stores
+        unsigned pq = 0u;
+        const unsigned t = blockIdx.x * 256u + threadIdx.x;
+        if (t < na) pq = pfa[(size_t)t * 32];
+        else if (t - na < nb) pq = pfb[(size_t)(t - na) * 32];
+        // (a wave reads back only what its own lanes wrote: LDS serves a wave's requests in order — the fence keeps the compiler from moving the reads up)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        constexpr int CH8 = (CH + 1) / 2;
+        const int nch8 = W >> 3;
+        float u[CH8][8];
+#pragma unroll
+        for (int i = 0; i < CH8; ++i) {
+            const int c = lane + i * 64;
+            uint4 q = make_uint4(0u, 0u, 0u, 0u);
+            if (c < nch8) q = *(const uint4*)&srow[threadIdx.x >> 6][2 * c];
+            const unsigned w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { u[i][2 * e] = __uint_as_float(w4[e] << 16); u[i][2 * e + 1] = __uint_as_float(w4[e] & 0xffff0000u); }
+        }
+        float s1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH8; ++i)
+            if (lane + i * 64 < nch8) s1 += ((u[i][0] + u[i][1]) + (u[i][2] + u[i][3])) + ((u[i][4] + u[i][5]) + (u[i][6] + u[i][7]));
+        float mean = s1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mean += __shfl_xor(mean, o, 64);
+        mean = mean / (float)W;
+        float s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH8; ++i)
+            if (lane + i * 64 < nch8) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float d = u[i][e] - mean; s2 += d * d; }
+            }
+        float rstd = s2;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) rstd += __shfl_xor(rstd, o, 64);
+        if (lane == 0) stats[row] = make_float2(mean, rsqrtf(rstd / (float)W + eps));
+        asm volatile("" ::"v"(pq));
     }
 }
 
@@ -384,6 +434,26 @@ extern "C" int mq_vit_assemble(const float* d_patch_out, const float* cls, const
     MQ_DISPATCH_CH(W, hipLaunchKernelGGL(vit_assemble_kernel<CH>, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s, d_patch_out,
                                          cls, pos, g, b, (float*)d_x, rows, T, W, eps, x_bf16));
     MQ_CHECK_LAUNCH("vit_assemble");
+    return MQ_OK;
+}
+
+// mq_vit_assemble on the bf16 stream with ln_pre, leaving (mean, rstd) of every stored row in d_stats (fp32 [n * T][2]; the row statistics a folded
+// LayerNorm reads: mq_row_stats would compute the same bits from d_x).  W % 8 == 0.
+bool mq_vit_assemble_stats_ok(int32_t W) { return W % 8 == 0 && W >= 8 && W <= 64 * 4 * MAXC; }
+extern mq_knob mq_ln_prefetch;   // rowops.hip
+int mq_vit_assemble_stats(const float* d_patch_out, const float* cls, const float* pos, const float* g, const float* b, void* d_x, float* d_stats, int64_t n,
+                          int32_t T, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s) {
+    MQ_CHECK_ARG(mq_vit_assemble_stats_ok(W) && g && b && d_stats, "vit_assemble_stats: W=%d unsupported / null pointer", W);
+    const int64_t rows = n * T;
+    if (rows <= 0) return MQ_OK;
+    MqProfScope prof(3, s);
+    // pf_a / pf_b (optional): weight ranges to pull into the Infinity Cache, under the rules of the LayerNorm kernels' prefetch (ln_extra, rowops.hip)
+    const bool pf = mq_ln_prefetch && rows >= 1024;
+    auto lines = [pf](const void* p, size_t bytes) { return (pf && p && ((uintptr_t)p & 3) == 0 && bytes < ((size_t)1 << 30)) ? (unsigned)(bytes / 128) : 0u; };
+    const unsigned na = lines(pf_a, bytes_a), nb = lines(pf_b, bytes_b);
+    MQ_DISPATCH_CH(W, hipLaunchKernelGGL((vit_assemble_kernel<CH, true>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s, d_patch_out,
+                                         cls, pos, g, b, (float*)d_x, rows, T, W, eps, 1, (float2*)d_stats, (const unsigned*)pf_a, na, (const unsigned*)pf_b, nb));
+    MQ_CHECK_LAUNCH("vit_assemble_stats");
     return MQ_OK;
 }
 

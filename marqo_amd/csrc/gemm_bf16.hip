@@ -45,6 +45,7 @@ extern mq_knob mq_tower_attn_proj;
 extern mq_knob mq_tower_panel_gemm;
 extern mq_knob mq_attention_waves;    // attention.hip
 extern mq_knob mq_tower_residual_bf16;  // towers.hip
+extern mq_knob mq_tower_pool_strided, mq_tower_assemble_stats;
 extern mq_knob mq_gemm_small_max_rows;  // gemm_small.hip
 bool mq_gemm_small_ok(int64_t M, int64_t N, int64_t K, bool ln);
 bool mq_gemm_small_grouped_ok(int64_t M, int64_t N, int64_t K);
@@ -822,7 +823,9 @@ extern "C" int mq_gemm_bf16_rsf(const void* d_A, int64_t lda, const void* d_W, i
 // "attn_proj" (fewest fixed-length sequences from which a ViT-B/32-shaped block runs attention + out-projection + residual + statistics as ONE launch,
 // attn_proj.hip; 0 = never), "panel_gemm" (fewest fixed-length sequences from which the folded QKV / fc1 GEMMs of a 768-wide tower run one workgroup per
 // sequence, panel_gemm.hip; 0 = never), "ln_rows" (rowops.hip: 1 = one row per wave in the generic LayerNorm at any row count, 2 = two from 8192 rows),
-// "ln_bf16_wide" (0 = bf16 rows take the generic LayerNorm, 1 = the 16-byte form above small_m rows, 4 = that form with four rows per wave from 16384 rows).
+// "ln_bf16_wide" (0 = bf16 rows take the generic LayerNorm, 1 = the 16-byte form above small_m rows, 4 = that form with four rows per wave from 16384 rows),
+// "pool_strided" (0 = the ViT class-token rows go through an index vector, two gathers and a scatter instead of being used where they lie),
+// "assemble_stats" (0 = a row_stats pass over x behind the ViT token assembly instead of the statistics the assembly leaves itself).
 extern "C" int mq_tune(const char* key, int value) {
     MQ_CHECK_ARG(key, "mq_tune: null key");
     const std::string k(key);
@@ -840,6 +843,8 @@ extern "C" int mq_tune(const char* key, int value) {
     else if (k == "xcd_band") mq_xcd_band = value;
     else if (k == "attn_waves") mq_attention_waves = value;
     else if (k == "residual_bf16") mq_tower_residual_bf16 = value;
+    else if (k == "pool_strided") mq_tower_pool_strided = value;
+    else if (k == "assemble_stats") mq_tower_assemble_stats = value;
     else if (k == "small_m") mq_gemm_small_max_rows = value;
     else if (k == "small_m_grouped") mq_gemm_small_group_rows = value;
     else if (k == "ln_prefetch") mq_ln_prefetch = value;

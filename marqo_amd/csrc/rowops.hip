@@ -8,6 +8,8 @@ mq_knob mq_ln_rows_per_wave{getenv("MQ_LN_ROWS") ? atoi(getenv("MQ_LN_ROWS")) : 
 extern mq_knob mq_gemm_small_max_rows;   // gemm_small.hip
 int mq_layernorm_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32,
                     int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
+int mq_layernorm_rows_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, int64_t row_mul, const float* d_g, const float* d_b, void* d_out_bf16,
+                         float* d_out_f32, int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 int mq_layernorm_fp8_pf(const void* d_x, int x_bf16, const float* d_g, const float* d_b, void* d_out_fp8, float* d_row_scale, float* d_out_f32,
                         int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 mq_knob mq_ln_bf16_wide{getenv("MQ_LN_BF16_WIDE") ? atoi(getenv("MQ_LN_BF16_WIDE")) : 1};   // mq_tune("ln_bf16_wide", 0 | 1 | 4) / MQ_LN_BF16_WIDE: 16-byte bf16-input LayerNorm (4: four rows per wave from 16384 rows)
@@ -35,6 +37,7 @@ struct LnExtra {
     const unsigned* pfa;
     const unsigned* pfb;
     unsigned step;            // dwords between touches: 32 = one per 128-byte L2 line, 16 = one per 64-byte fabric request
+    unsigned row_mul;         // LayerNorm kernels without a row_idx: input row r is row r * row_mul (1 = dense; pooled rows at a fixed pitch, towers.hip)
 };
 constexpr int LN_PF = 2;   // lines per thread (one dword of a line brings the line: one VGPR per touched line)
 
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(256, (CH * R <= 2 ? 8 : CH * R <= 4 ? 5 : CH * R <=
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int64_t row = row0 + r < rows ? row0 + r : rows - 1;  // a ragged last wave re-reads the last row (never stored)
-        const int64_t src = row_idx ? (int64_t)row_idx[row] : row;
+        const int64_t src = row_idx ? (int64_t)row_idx[row] : row * ex.row_mul;
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
             const int c = lane + i * 64;
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(256) void layernorm_bf16in_kernel(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int64_t row = row0 + r < rows ? row0 + r : rows - 1;
-        const int64_t src = row_idx ? (int64_t)row_idx[row] : row;
+        const int64_t src = row_idx ? (int64_t)row_idx[row] : row * ex.row_mul;
 #pragma unroll
         for (int i = 0; i < CH8; ++i) {
             const int c = lane + i * 64;
@@ -399,7 +402,7 @@ extern "C" int mq_layernorm(const float* d_x, const int32_t* d_row_idx, const fl
 mq_knob mq_ln_prefetch{getenv("MQ_LN_PREFETCH") ? atoi(getenv("MQ_LN_PREFETCH")) : 1};
 
 static LnExtra ln_extra(int band, int64_t rows, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b) {
-    LnExtra ex{band, 0u, 0u, nullptr, nullptr, 32u};
+    LnExtra ex{band, 0u, 0u, nullptr, nullptr, 32u, 1u};
     if (mq_ln_prefetch && rows >= 1024) {   // (a small call is latency-bound: nothing to hide the extra loads behind)
         const size_t gran = mq_ln_prefetch == 2 ? 64 : mq_ln_prefetch == 3 ? 32 : 128;      // bytes per touch (knob values 2 / 3: A/B of the granularity)
         ex.step = (unsigned)(gran / 4);
@@ -420,12 +423,20 @@ extern "C" int mq_layernorm_ex(const void* d_x, int x_bf16, const int32_t* d_row
 // discard, one dword per 128-byte line, as far as its thread count reaches (LN_PF lines per thread); either may be NULL
 int mq_layernorm_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32,
                     int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s) {
+    return mq_layernorm_rows_pf(d_x, x_bf16, d_row_idx, 1, d_g, d_b, d_out_bf16, d_out_f32, rows, W, eps, pf_a, bytes_a, pf_b, bytes_b, s);
+}
+
+// ... with input row r read at row r * row_mul of d_x when there is no d_row_idx (pooled rows at a fixed pitch; the output rows are dense)
+int mq_layernorm_rows_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, int64_t row_mul, const float* d_g, const float* d_b, void* d_out_bf16,
+                         float* d_out_f32, int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s) {
     MQ_CHECK_ARG(d_x && d_g && d_b && (d_out_bf16 || d_out_f32), "mq_layernorm: null pointer");
+    MQ_CHECK_ARG(row_mul >= 1 && row_mul < ((int64_t)1 << 31) && (d_row_idx == nullptr || row_mul == 1), "mq_layernorm: bad row multiplier");
     MQ_CHECK_ARG(W >= 4 && W % 4 == 0 && W <= 64 * 4 * LN_MAX_CHUNKS, "mq_layernorm: W=%d unsupported (multiple of 4, <= 2048)", W);
     if (rows <= 0) return MQ_OK;
     MqProfScope prof(1, s);
     // banding: dense batches only (a gather has no row locality to keep)
-    const LnExtra band = ln_extra((mq_xcd_band && !d_row_idx && rows >= 4096) ? 1 : 0, rows, pf_a, bytes_a, pf_b, bytes_b);
+    LnExtra band = ln_extra((mq_xcd_band && !d_row_idx && row_mul == 1 && rows >= 4096) ? 1 : 0, rows, pf_a, bytes_a, pf_b, bytes_b);
+    band.row_mul = (unsigned)row_mul;
     // two rows per wave once there are enough rows to fill the chip that way (and the row fits: CH * 2 float4 per lane)
     // The LayerNorm form follows the GEMM family of the call: at most mq_gemm_small_max_rows rows (the search path: skinny GEMMs, whose fused
     // LayerNorm prologue sums a row in the generic kernel's lane order) keep the generic kernel, so a query has the same bits alone and inside

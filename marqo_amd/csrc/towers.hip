@@ -49,6 +49,15 @@ static bool panel_fill_ok(int64_t nseq) {
 // add (measured 1 - cos 5e-5 .. 1.2e-4 against the fp32 oracle at full depth, well inside the 1e-3 tolerance; the reference's own GPU path
 // keeps its activations in fp16 under autocast, open_clip_model.py:255-260).  Post-LN (BERT) and fp8 towers keep the fp32 stream.
 mq_knob mq_tower_residual_bf16{getenv("MQ_RESIDUAL_BF16") ? atoi(getenv("MQ_RESIDUAL_BF16")) : 0};
+// pooled rows at a fixed pitch (the class token of every image: row i * T) are read and written WHERE THEY LIE: the skinny GEMMs of the pooled last block
+// and the head take a row pitch of T * W (gemm_small.hip reads A and the residual with ordinary loads), the LayerNorms a row multiplier — no index
+// vector (cls_rows_kernel), no gathers into a dense copy, no scatter back.  Same kernels on the same values: bit-identical.
+// mq_tune("pool_strided", 0) / MQ_POOL_STRIDED=0: the index vector and the three move_rows launches
+mq_knob mq_tower_pool_strided{getenv("MQ_POOL_STRIDED") ? atoi(getenv("MQ_POOL_STRIDED")) : 1};
+// the ViT front end leaves the first block's (mean, rstd) behind: vit_assemble_kernel holds whole token rows, so it also writes the statistics of the bf16
+// rows it stores (embed.hip, arithmetic and lane order of row_stats_bf16_kernel) and the first QKV GEMM needs no statistics pass.
+// mq_tune("assemble_stats", 0) / MQ_ASSEMBLE_STATS=0: the row_stats_bf16_kernel launch
+mq_knob mq_tower_assemble_stats{getenv("MQ_ASSEMBLE_STATS") ? atoi(getenv("MQ_ASSEMBLE_STATS")) : 1};
 extern "C" int mq_layernorm_ex(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16,
                                float* d_out_f32, int64_t rows, int32_t W, float eps, void* stream);
 // search path (rows <= 80): LayerNorm fused into the skinny GEMM's prologue (gemm_small.hip)
@@ -60,6 +69,9 @@ int mq_ln_gemm_small(const void* d_x, int64_t ldx, int x_bf16, const float* ln_g
 // (the LayerNorm kernel also pulls W and `next_w` — the weights of the GEMM after this one — into the Infinity Cache: rowops.hip, LnExtra)
 int mq_layernorm_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32,
                     int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
+// ... with input row r read at row r * row_mul of d_x (no index vector; output rows dense)
+int mq_layernorm_rows_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, int64_t row_mul, const float* d_g, const float* d_b, void* d_out_bf16,
+                         float* d_out_f32, int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 // The prefetch pays only when the weights do not survive in the 256 MB Infinity Cache from one step to the next: the blocks' bf16 weights
 // (x layers) at least half of it.  Measured (profiles/r03r_ln_prefetch_ab.txt): ViT-B/32 image (170 MB) GEMMs -4 %, step +2 %; ViT-L/14 (604 MB)
 // +3 %; CLIP text B/32 (38 MB) and BERT-base (85 MB, ~480 MB of activations per layer) neutral to -1 % -> off there.  Decided per encoder call.
@@ -90,6 +102,9 @@ int mq_row_stats_finalize_pf(const float* d_partials, int32_t nslots, float* d_s
 bool mq_row_stats_ok(int32_t W);
 int mq_row_stats_pf(const void* d_x_bf16, float* d_stats, int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b,
                     size_t bytes_b, hipStream_t s);
+bool mq_vit_assemble_stats_ok(int32_t W);   // embed.hip
+int mq_vit_assemble_stats(const float* d_patch_out, const float* cls, const float* pos, const float* g, const float* b, void* d_x, float* d_stats, int64_t n,
+                          int32_t T, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 // folded LayerNorm + GEMM: the bf16 stream is the A operand (no LayerNorm launch, no normalised copy)
 static bool fold_ok(int xb, const void* wf, const float* bf, const float* sf, int64_t rows, int N, int K) {
     return mq_tower_ln_fold && xb && wf && bf && sf && mq_row_stats_ok(K) && !mq_gemm_small_ok(rows, N, K, false) && !mq_gemm_small_grouped_ok(rows, N, K);
@@ -134,6 +149,14 @@ static bool stream_bf16(const mq_encoder_cfg* c) {
 // out-projection, a gated (SwiGLU) MLP with a LayerNorm behind the gate.  Every row runs every block; residual stream and LayerNorm folding as in the
 // plain pre-LN blocks (LN1 into the QKV GEMM, LN2 into the (up | gate) GEMM; the two sub-LayerNorms are kernels).
 static bool eva_form(const mq_encoder_cfg* c) { return !c->post_ln && (c->mlp_glu || c->d_rope_table); }
+// pooled rows at pitch `sel_stride` (row i * sel_stride, i < nsel) can be used in place, without an index vector: plain pre-LN bf16-operand encoders whose
+// pooled last block runs on the skinny kernels (a tiled GEMM wants its A panel dense: larger calls keep the gathers)
+static bool sel_strided_ok(const mq_encoder_cfg* c, int64_t nsel, int64_t sel_stride) {
+    const int W = c->width, F = c->mlp_dim, Wa = c->attn_width ? c->attn_width : c->width;
+    auto small = [](int64_t M, int64_t N, int64_t K) { return mq_gemm_small_ok(M, N, K, false) || mq_gemm_small_grouped_ok(M, N, K); };
+    return mq_tower_pool_strided && sel_stride > 0 && nsel > 0 && !c->post_ln && c->precision == MQ_PREC_BF16 && !eva_form(c) && (sel_stride * Wa) % 8 == 0 &&
+           small(nsel, W, Wa) && small(nsel, F, W) && small(nsel, W, F);
+}
 
 // post-LN encoders (BERT family) on the bf16 stream: the normalised bf16 rows `h` ARE the residual — the out-projection / fc2 epilogues add
 // into them in place (bf16 read-modify-write), the LayerNorm normalises them in place, and the fp32 copy of x disappears from the block
@@ -262,8 +285,8 @@ namespace {
 // behind the fc1 output (all of h / a / qkv are dead by the time they are overwritten).
 int last_block_selected(const mq_encoder_cfg* cfg, const mq_block_weights& b, int l, float* d_x, int64_t rows,
                         const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
-                        const int32_t* d_sel, int64_t nsel, void* h, void* a, void* qf, float* row_scale, float* row_stats, bool stats_ready, float* x_sel,
-                        bool f8, hipStream_t s) {
+                        const int32_t* d_sel, int64_t sel_stride, int64_t nsel, void* h, void* a, void* qf, float* row_scale, float* row_stats, bool stats_ready,
+                        float* x_sel, bool f8, hipStream_t s) {
     const int W = cfg->width, F = cfg->mlp_dim, Wa = attn_width(cfg);
     const int act_flag = act_epi(cfg->act);
     const int res_flags = MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32;
@@ -289,6 +312,20 @@ int last_block_selected(const mq_encoder_cfg* cfg, const mq_block_weights& b, in
         const int64_t xrow = (int64_t)W * (xb ? 2 : 4);
         MQ_TRY(ln_gemm(d_x, xb, b.ln1_g, b.ln1_b, cfg->ln_eps, h, b.qkv_w, b.qkv_b, qf, rows, 3 * Wa, W, MQ_EPI_BIAS, s, nullptr, 0, b.qkv_wf, b.qkv_bf, b.qkv_sf, row_stats, stats_ready));
         MQ_TRY(attn_bf16(cfg, qf, a, d_cu_seqlens, nseq, fixed_len, max_len, Wa, s));
+        if (sel_stride > 0) {
+            // pooled rows at a fixed pitch (sel_strided_ok): the skinny GEMMs read the rows of `a` and update the rows of x where they lie
+            const int64_t lda = sel_stride * Wa, ldx = sel_stride * W;
+            MQ_TRY(mq_gemm_bf16(a, lda, b.out_w, Wa, b.out_b, d_x, d_x, ldx, nsel, W, Wa, rflags, s));
+            if (mq_gemm_small_ok(nsel, F, W, true))
+                MQ_TRY(mq_ln_gemm_small(d_x, ldx, xb, b.ln2_g, b.ln2_b, cfg->ln_eps, b.fc1_w, W, b.fc1_b, qf, F, nsel, F, W, MQ_EPI_BIAS | act_flag, nullptr, nullptr, s));
+            else {
+                MQ_TRY(mq_layernorm_rows_pf(d_x, xb, nullptr, sel_stride, b.ln2_g, b.ln2_b, h, nullptr, nsel, W, cfg->ln_eps, pf(b.fc1_w), (size_t)F * W * 2, nullptr, 0, s));
+                if (act_flag & MQ_EPI_RELU) MQ_TRY(mq_gemm_small(h, W, b.fc1_w, W, b.fc1_b, nullptr, qf, F, nsel, F, W, MQ_EPI_BIAS | act_flag, s));
+                else MQ_TRY(mq_gemm_bf16(h, W, b.fc1_w, W, b.fc1_b, nullptr, qf, F, nsel, F, W, MQ_EPI_BIAS | act_flag, s));
+            }
+            MQ_TRY(mq_gemm_bf16(qf, F, b.fc2_w, F, b.fc2_b, d_x, d_x, ldx, nsel, W, F, rflags, s));
+            return MQ_OK;
+        }
         MQ_TRY(mq_move_rows(a, d_sel, h, nsel, (int64_t)Wa * 2, false, s));
         MQ_TRY(mq_move_rows(d_x, d_sel, x_sel, nsel, xrow, false, s));
         MQ_TRY(mq_gemm_bf16(h, Wa, b.out_w, Wa, b.out_b, x_sel, x_sel, W, nsel, W, Wa, rflags, s));
@@ -346,6 +383,8 @@ struct EncoderPass {
     uint32_t* band_ctr;              // arrival counters of the residual GEMMs' in-launch statistics finalise (mq_gemm_bf16_rsf), zeroed once per pass
     bool x_has_partials;             // row_stats holds (mean, rstd) of the current d_x (the residual GEMM that wrote it left them behind)
     int act_flag, res_flags, first8;
+    const float* stats0;             // (mean, rstd) of the rows of d_x as the caller hands them in (the ViT front end leaves them), or nullptr
+    bool has_sel;                    // the caller reads only `nsel` pooled rows afterwards (d_sel, or rows at a fixed pitch)
 
     int block_fp8(const mq_block_weights& b, int l);            // e4m3 GEMM operands, post-LN or pre-LN
     int block_eva(const mq_block_weights& b, int l);            // pre-LN with rotary table / sub-LayerNorms / gated MLP (EVA02)
@@ -464,14 +503,17 @@ int EncoderPass::block_pre_ln(const mq_block_weights& b, int l) {
     const int xb = stream_bf16(cfg) ? 1 : 0;
     const int rflags = xb ? (MQ_EPI_BIAS | MQ_EPI_RESIDUAL) : res_flags;
     bool panel = false;
+    // (block 0: the caller may hand the statistics of its rows in — they live outside this pass's scratch)
+    float* stats1 = l == 0 && stats0 ? const_cast<float*>(stats0) : row_stats;
+    const bool ready1 = x_has_partials || (l == 0 && stats0);
     MQ_TRY(ln_gemm_panel(panel, d_x, xb, cfg->ln_eps, qf, rows, nseq, fixed_len, d_cu_seqlens, 3 * Wa, W, MQ_EPI_BIAS, s, b.out_w, (size_t)W * Wa * 2, b.qkv_wf, b.qkv_bf,
-                         b.qkv_sf, row_stats, x_has_partials));
+                         b.qkv_sf, stats1, ready1));
     if (!panel)
         MQ_TRY(ln_gemm(d_x, xb, b.ln1_g, b.ln1_b, cfg->ln_eps, h, b.qkv_w, b.qkv_b, qf, rows, 3 * Wa, W, MQ_EPI_BIAS, s, b.out_w, (size_t)W * Wa * 2,
-                       b.qkv_wf, b.qkv_bf, b.qkv_sf, row_stats, x_has_partials));
+                       b.qkv_wf, b.qkv_bf, b.qkv_sf, stats1, ready1));
     x_has_partials = false;
     // the residual GEMMs leave the rows' partial sums behind whenever the GEMM after them folds its LayerNorm (tiled family, bf16 stream)
-    const bool last_pooled = d_sel && nsel > 0 && l == cfg->layers - 1;
+    const bool last_pooled = has_sel && l == cfg->layers - 1;
     const bool mlp_fp8 = cfg->precision == MQ_PREC_FP8 && l >= first8 - cfg->fp8_mlp_extra;
     const bool fold_mlp = mq_tower_ln_fold >= 2 && !last_pooled && !mlp_fp8 && fold_ok(xb, b.fc1_wf, b.fc1_bf, b.fc1_sf, rows, F, W) &&
                           !mq_gemm_small_ok(rows, W, Wa, false) && !mq_gemm_small_grouped_ok(rows, W, Wa);
@@ -579,8 +621,12 @@ int EncoderPass::block_post_ln(const mq_block_weights& b, int l) {
 
 int encoder_forward_impl(const mq_encoder_cfg* cfg, const mq_block_weights* blocks, float* d_x, int64_t rows,
                          const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
-                         const int32_t* d_sel, int64_t nsel, void* d_workspace, size_t workspace_bytes, hipStream_t s) {
+                         const int32_t* d_sel, int64_t nsel, void* d_workspace, size_t workspace_bytes, hipStream_t s, int64_t sel_stride = 0,
+                         const float* stats0 = nullptr) {
+    // sel_stride > 0 (the caller has asked sel_strided_ok): the pooled rows are i * sel_stride, i < nsel, and d_sel is not read
     MQ_TRY(check_encoder_cfg(cfg));
+    MQ_CHECK_ARG(sel_stride == 0 || (sel_strided_ok(cfg, nsel, sel_stride) && (nsel - 1) * sel_stride < rows), "mq_encoder_forward: bad pooled-row pitch");
+    const bool has_sel = (d_sel || sel_stride > 0) && nsel > 0;
     MQ_CHECK_ARG(d_x && (blocks || cfg->layers == 0), "mq_encoder_forward: null pointer");
     if (rows <= 0 || cfg->layers == 0) return MQ_OK;
     if (workspace_bytes < encoder_ws(cfg, rows)) {
@@ -608,7 +654,7 @@ int encoder_forward_impl(const mq_encoder_cfg* cfg, const mq_block_weights* bloc
     // activation maxima must see every row); x_sel must fit behind the fc1 output inside `qf`
     const size_t xsel_off = align_up((size_t)(nsel > 0 ? nsel : 0) * F * 2, WS_ALIGN);
     // (not on the search path either: a call of a few rows is bound by its launch count, and the selection costs 4 launches more)
-    const bool select_last = d_sel && nsel > 0 && nsel * 2 <= rows && mq_tower_row_select && !cfg->mlp_glu && !cfg->d_rope_inv_freq && !cfg->d_rope_table &&
+    const bool select_last = has_sel && nsel * 2 <= rows && mq_tower_row_select && !cfg->mlp_glu && !cfg->d_rope_inv_freq && !cfg->d_rope_table &&
                              !mq_gemm_small_ok(rows, W, W, false) &&
                              !(cfg->precision == MQ_PREC_FP8 && (cfg->d_fp8_act_amax || cfg->post_ln)) &&
                              xsel_off + (size_t)nsel * W * 4 <= (size_t)rows * big * 2;
@@ -628,7 +674,7 @@ int encoder_forward_impl(const mq_encoder_cfg* cfg, const mq_block_weights* bloc
     else if (cfg->post_ln) MQ_TRY(mq_cast_bf16(d_x, h, rows * W, s));
 
     EncoderPass p{cfg, blocks, d_x, rows, d_cu_seqlens, nseq, fixed_len, max_len, d_sel, nsel, s, W, F, Wa, h, a, qf, row_scale, row_stats, row_part, xn, band_ctr,
-                  /*x_has_partials*/ false, act_epi(cfg->act), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32, first8};
+                  /*x_has_partials*/ false, act_epi(cfg->act), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32, first8, stats0, has_sel};
     for (int l = 0; l < cfg->layers; ++l) {
         const mq_block_weights& b = blocks[l];
         const bool f8 = l >= first8;
@@ -639,8 +685,8 @@ int encoder_forward_impl(const mq_encoder_cfg* cfg, const mq_block_weights* bloc
         // post-LN: the previous (bf16) block left its output as a bf16 operand; the first e4m3 block wants e4m3 rows + row scales
         if (cfg->post_ln && f8 && l == first8 && l > 0) MQ_TRY(mq_rowquant_fp8(d_x, h, row_scale, rows, W, s));
         if (select_last && l == cfg->layers - 1) {
-            MQ_TRY(last_block_selected(cfg, b, l, d_x, rows, d_cu_seqlens, nseq, fixed_len, max_len, d_sel, nsel, h, a, qf, row_scale, row_stats, p.x_has_partials,
-                                       (float*)((char*)qf + xsel_off), f8, s));
+            MQ_TRY(last_block_selected(cfg, b, l, d_x, rows, d_cu_seqlens, nseq, fixed_len, max_len, d_sel, sel_stride, nsel, h, a, qf, row_scale, row_stats,
+                                       p.x_has_partials, (float*)((char*)qf + xsel_off), f8, s));
             break;
         }
         if (f8) MQ_TRY(p.block_fp8(b, l));
@@ -674,7 +720,7 @@ extern "C" int mq_encoder_forward_rows(const mq_encoder_cfg* cfg, const mq_block
 namespace {
 struct VitPlan {
     int T, np, Kp; int64_t rows;
-    size_t off_x, off_rows, off_cls, off_enc, off_patches, off_patch_out, total;
+    size_t off_x, off_rows, off_cls, off_stats0, off_enc, off_patches, off_patch_out, total;
     size_t off_map_y, off_map_z, off_map_h, off_tok, off_kv;  // MQ_VIT_POOL_MAP (off_tok / off_kv inside the encoder's region)
 };
 VitPlan vit_plan(const mq_vit_cfg* c, int64_t n) {
@@ -687,6 +733,7 @@ VitPlan vit_plan(const mq_vit_cfg* c, int64_t n) {
     p.off_x = cv.take((size_t)p.rows * W * 4);
     p.off_rows = cv.take((size_t)n * 4);
     p.off_cls = cv.take((size_t)n * W * 2);       // CLIP: ln_post(class token) bf16; MAP: pooled attention output bf16
+    p.off_stats0 = cv.take((size_t)p.rows * 8);   // (mean, rstd) of the assembled rows (the encoder's own statistics buffer overlaps the patch buffers)
     p.off_map_y = p.off_map_z = p.off_map_h = p.off_tok = p.off_kv = 0;
     if (map) {
         p.off_map_y = cv.take((size_t)n * W * 4);                 // fp32 [n, W] head stream
@@ -757,7 +804,22 @@ int encode_image_impl(const mq_vit_cfg* cfg, const mq_vit_weights* w, const void
     MQ_TRY(mq_patchify(d_pixels, is_u8, patches, n, cfg->image_size, cfg->patch_size, p.Kp, cfg->mean, cfg->std, s));
     MQ_TRY(mq_gemm_bf16(patches, p.Kp, w->patch_w, p.Kp, nullptr, nullptr, patch_out, W, n * p.np, W, p.Kp, MQ_EPI_OUT_F32, s));
     const int xb = stream_bf16(&cfg->enc) ? 1 : 0;   // residual stream in bf16 (same buffer, half of it used)
-    MQ_TRY(mq_vit_assemble(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, x, n, p.T, W, cfg->enc.ln_eps, xb, s));
+    // class-token towers on the bf16 stream whose first block folds its LayerNorm into the QKV GEMM: the assembly, which holds whole rows, also
+    // leaves that block's (mean, rstd) — the statistics pass over x (row_stats_bf16_kernel) is not launched
+    const float* stats0 = nullptr;
+    if (mq_tower_assemble_stats && xb && w->ln_pre_g && cfg->pool == MQ_VIT_POOL_CLS && cfg->enc.precision == MQ_PREC_BF16 && !cfg->enc.post_ln &&
+        !eva_form(&cfg->enc) && cfg->enc.layers >= 2 && mq_tower_ln_fold && mq_tower_panel_gemm == 0 && mq_vit_assemble_stats_ok(W) && w->blocks &&
+        fold_ok(xb, w->blocks[0].qkv_wf, w->blocks[0].qkv_bf, w->blocks[0].qkv_sf, p.rows, 3 * attn_width(&cfg->enc), W) &&
+        !mq_gemm_small_ok(p.rows, 3 * attn_width(&cfg->enc), W, true))
+        stats0 = (const float*)(base + p.off_stats0);
+    if (stats0) {
+        // (with the weight prefetch the statistics pass would have carried: ln_gemm)
+        const int Wa = attn_width(&cfg->enc);
+        const bool wpf = weights_outlive_cache(&cfg->enc, Wa);
+        MQ_TRY(mq_vit_assemble_stats(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, x, const_cast<float*>(stats0), n, p.T, W, cfg->enc.ln_eps,
+                                     wpf ? w->blocks[0].qkv_wf : nullptr, (size_t)3 * Wa * W * 2, wpf ? w->blocks[0].out_w : nullptr, (size_t)W * Wa * 2, s));
+    }
+    else MQ_TRY(mq_vit_assemble(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, x, n, p.T, W, cfg->enc.ln_eps, xb, s));
     if (map) {
         // K2-K5 x layers on every token, then the trunk's norm on every token and the attention-pool head:
         //   k | v = norm(x) @ kv_w^T + kv_b;  o = softmax(q k^T) v per head (one learned query);  y = o @ proj^T + b;
@@ -823,15 +885,19 @@ int encode_image_impl(const mq_vit_cfg* cfg, const mq_vit_weights* w, const void
         return MQ_OK;
     }
     // K2-K5 x layers (only the class-token rows are read afterwards -> the last block's row-wise half runs on them alone)
-    MQ_TRY(mq_cls_rows(rows_idx, n, p.T, s));
+    // (the class tokens lie at a fixed pitch of T rows: read and updated in place where the pooled block runs on the skinny kernels — sel_strided_ok —
+    // else through an index vector and gathers)
+    const int64_t pitch = sel_strided_ok(&cfg->enc, n, p.T) ? p.T : 0;
+    if (!pitch) MQ_TRY(mq_cls_rows(rows_idx, n, p.T, s));
+    else rows_idx = nullptr;
     MQ_TRY(encoder_forward_impl(&cfg->enc, w->blocks, x, p.rows, nullptr, n, p.T, p.T, rows_idx, n, base + p.off_enc,
-                                ws_bytes - p.off_enc, s));
+                                ws_bytes - p.off_enc, s, pitch, stats0));
     // K6: ln_post(class token) @ proj, L2
     if (mq_gemm_small_ok(n, cfg->out_dim, W, true))   // search path: ln_post rides in the head GEMM's prologue
-        MQ_TRY(mq_ln_gemm_small(x, W, xb, w->ln_post_g, w->ln_post_b, cfg->enc.ln_eps, w->proj_w, W, w->proj_b, d_out, cfg->out_dim, n, cfg->out_dim,
+        MQ_TRY(mq_ln_gemm_small(x, pitch ? pitch * W : W, xb, w->ln_post_g, w->ln_post_b, cfg->enc.ln_eps, w->proj_w, W, w->proj_b, d_out, cfg->out_dim, n, cfg->out_dim,
                                 W, MQ_EPI_OUT_F32 | (w->proj_b ? MQ_EPI_BIAS : 0), nullptr, rows_idx, s));
     else {
-        MQ_TRY(mq_layernorm_ex(x, xb, rows_idx, w->ln_post_g, w->ln_post_b, cls_ln, nullptr, n, W, cfg->enc.ln_eps, s));
+        MQ_TRY(mq_layernorm_rows_pf(x, xb, rows_idx, pitch ? pitch : 1, w->ln_post_g, w->ln_post_b, cls_ln, nullptr, n, W, cfg->enc.ln_eps, nullptr, 0, nullptr, 0, s));
         MQ_TRY(mq_gemm_bf16(cls_ln, W, w->proj_w, W, w->proj_b, nullptr, d_out, cfg->out_dim, n, cfg->out_dim, W, MQ_EPI_OUT_F32 | (w->proj_b ? MQ_EPI_BIAS : 0), s));
     }
     if (normalize) MQ_TRY(mq_l2_normalize(d_out, d_out, n, cfg->out_dim, s));

@@ -542,6 +542,16 @@ class _TowerBase:
             self._queues[bool(normalize)] = (sig, q)
             return q
 
+    def tune(self, key: str, value: int) -> None:
+        """mq_tune(key, value) for A/B runs and parity tests, and forget what this tower has recorded under the previous setting: a captured
+        graph replays the launch sequence it was captured with, and a native queue keeps its own captured graphs — both are re-created at the next use"""
+        L.check(self.lib.mq_tune(key.encode(), int(value)), "mq_tune")
+        with self._lock:
+            getattr(self, "_graphs", {}).clear()
+            for ent in (self._queues or {}).values():
+                ent[1].close()
+            self._queues = None
+
     def _forget_queue(self, q) -> None:
         """a native queue that was closed under a caller (engine/native_queue.gone): the next small call creates a fresh one"""
         with self._lock:
