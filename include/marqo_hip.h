@@ -992,10 +992,18 @@ int mq_probe_mfma_peak(double target_ms, void* d_scratch, int64_t scratch_bytes,
  *                   tokenizers' one-token-at-a-time loop) to B = max_length - 3 pieces: both when la + lb <= B; else with s = min, l = max
  *                   (a tie counts the SECOND text as the longer): l' = s when s > B, else max(s, B - s); when s + l' > B: s = B / 2,
  *                   l' = B - s; the longer text keeps l'.  d_keep_a / d_keep_b int32 [n]; d_total int32 [n] = a + b + 3.  max_length >= 4.
+ *   mq_pair_plan_n: the same rule for a pair sequence with `specials` special tokens (0 .. 8): B = max_length - specials, d_total = a + b +
+ *                   specials, max_length >= specials + 1.  mq_pair_plan is mq_pair_plan_n with specials = 3; XLM-RoBERTa's
+ *                   <s> a </s> </s> b </s> has 4.
  *   mq_pack_pairs:  d_ids / d_type_ids int32 [rows]: sequence i at [d_cu[i], d_cu[i + 1]) = [CLS] q[:a] [SEP] (type 0) d_i[:b] [SEP] (type 1);
  *                   d_query int32 [Lq] holds the query's pieces only, d_docs int32 [n, ld] rows [CLS] pieces [SEP] pad (mq_tokenize_wordpiece's
  *                   layout: the pieces start at column 1).  d_cu int32 [n + 1] is the exclusive scan of d_total (the caller's: it needs the
  *                   host copy for the tower anyway).  Both texts keep their prefix.  Nothing at or beyond row `rows` is written.
+ *   mq_pack_pairs_xlmr: d_ids int32 [rows]: sequence i at [d_cu[i], d_cu[i + 1]) = cls_id q[:a] sep_id sep_id d_i[:b] sep_id (XLM-RoBERTa's
+ *                   <s> a </s> </s> b </s>; no type ids: the family has one type row).  d_query int32 [Lq] holds the query's pieces only, d_docs
+ *                   int32 [n, ld] rows <s> pieces </s> <pad> (mq_tokenize_sentencepiece's layout: the pieces start at column 1); d_keep_a /
+ *                   d_keep_b / d_cu from mq_pair_plan_n with specials = 4.  Both texts keep their prefix.  Nothing at or beyond row `rows` is
+ *                   written.
  *   mq_embed_tokens_typed: mq_embed_tokens with a type id per row: + d_type_emb[clamp(d_type_ids[r], 0, type_vocab - 1)] where mq_embed_tokens
  *                   adds row 0 — same order of the additions (token, position, type), so all-zero type ids give mq_embed_tokens' bits.
  *   mq_score_head:  d_h fp32 [n, W] (the final [CLS] rows) -> y = tanh(pooler_w bf16(h) + pooler_b) (mq_gemm_bf16: bf16 operands, fp32
@@ -1003,20 +1011,31 @@ int mq_probe_mfma_peak(double target_ms, void* d_scratch, int64_t scratch_bytes,
  *                   W % 64 == 0, W <= 2048.  Scratch: mq_score_head_workspace_bytes(n, W).
  *   mq_score_pairs_bert: typed embedding -> the encoder with mq_encode_bert's MQ_POOL_CLS row selection -> the [CLS] rows (d_cls_rows fp32
  *                   [nseq, W], NULL ok: bit-identical to mq_encode_bert(pool = CLS, normalize = 0) when the type rows agree) -> mq_score_head.
- *                   bf16 encoders only (MQ_PREC_FP8 is refused).  Scratch: mq_score_pairs_workspace_bytes(cfg, rows, nseq). */
+ *                   bf16 encoders only (MQ_PREC_FP8 is refused).  Scratch: mq_score_pairs_workspace_bytes(cfg, rows, nseq).
+ *   mq_score_pairs_xlmr: mq_score_pairs_bert for an encoder with ONE type row and a position offset (XLMRobertaForSequenceClassification): no
+ *                   type ids; the embedding is mq_encode_bert's own (mq_embed_tokens: token + position + type row 0), so token t of a sequence
+ *                   takes row t of mq_bert_weights.pos_emb.  As for mq_encode_bert, the host hands that table over from row padding_idx + 1
+ *                   on: the position ids of a packed pair run offset, offset + 1, ... over the whole pair, which is transformers'
+ *                   create_position_ids_from_input_ids on an unpadded row.  The head is RoBERTa's classification head under the names of
+ *                   mq_score_head_weights: pooler_w / pooler_b = classifier.dense, cls_w / cls_b = classifier.out_proj.  d_cls_rows are
+ *                   bit-identical to mq_encode_bert(pool = CLS, normalize = 0).  Same refusals and scratch as mq_score_pairs_bert. */
 typedef struct mq_score_head_weights {
-    const void*  pooler_w;   /* bf16 [W, W]: bert.pooler.dense.weight */
+    const void*  pooler_w;   /* bf16 [W, W]: bert.pooler.dense.weight (RoBERTa heads: classifier.dense.weight) */
     const float* pooler_b;   /* fp32 [W] */
-    const float* cls_w;      /* fp32 [W]: classifier.weight (num_labels = 1) */
-    float        cls_b;      /* classifier.bias */
+    const float* cls_w;      /* fp32 [W]: classifier.weight (num_labels = 1; RoBERTa heads: classifier.out_proj.weight) */
+    float        cls_b;      /* classifier.bias (classifier.out_proj.bias) */
     int32_t      type_vocab; /* rows of mq_bert_weights.type_emb (config.json type_vocab_size) */
 } mq_score_head_weights;
 
 int mq_pair_plan(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t* d_keep_a, int32_t* d_keep_b,
                  int32_t* d_total, void* stream);
+int mq_pair_plan_n(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t specials, int32_t* d_keep_a,
+                   int32_t* d_keep_b, int32_t* d_total, void* stream);
 int mq_pack_pairs(const int32_t* d_query, int32_t Lq, const int32_t* d_docs, int32_t ld, const int32_t* d_keep_a, const int32_t* d_keep_b,
                   const int32_t* d_cu, int64_t n, int32_t cls_id, int32_t sep_id, int32_t* d_ids, int32_t* d_type_ids, int64_t rows,
                   void* stream);
+int mq_pack_pairs_xlmr(const int32_t* d_query, int32_t Lq, const int32_t* d_docs, int32_t ld, const int32_t* d_keep_a, const int32_t* d_keep_b,
+                       const int32_t* d_cu, int64_t n, int32_t cls_id, int32_t sep_id, int32_t* d_ids, int64_t rows, void* stream);
 int mq_embed_tokens_typed(const int32_t* d_ids, const int32_t* d_type_ids, const int32_t* d_cu, int64_t nseq, const float* d_tok,
                           const float* d_pos, const float* d_type_emb, int32_t type_vocab, const float* d_g, const float* d_b, float* d_x,
                           void* d_xb, int32_t W, int32_t vocab, float eps, int32_t last_pos, void* stream);
@@ -1027,6 +1046,9 @@ size_t mq_score_pairs_workspace_bytes(const mq_bert_cfg* cfg, int64_t rows, int6
 int mq_score_pairs_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
                         const int32_t* d_type_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits,
                         float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream);
+int mq_score_pairs_xlmr(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                        const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits, float* d_scores,
+                        float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- image reranking: the OWL-ViT detection heads (csrc/owl_head.hip; engine/owl.py) ----------------------------------------------------------
  * s2_inference/reranking/rerank.py rerank_search_results -> cross_encoders.py ReRankerOwl -> transformers' OwlViTForObjectDetection in the

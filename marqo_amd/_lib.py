@@ -302,6 +302,8 @@ _SIGNATURES = {
     "mq_glu_ln": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, C.c_int32, _P]),
     # text reranking: cross-encoder scoring on the BERT tower (csrc/rerank.hip; engine/rerank.py)
     "mq_pair_plan": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mq_pair_plan_n": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mq_pack_pairs_xlmr": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "mq_pack_pairs": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "mq_embed_tokens_typed": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "mq_score_head_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
@@ -309,6 +311,8 @@ _SIGNATURES = {
     "mq_score_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(BertCfg), C.c_int64, C.c_int64]),
     "mq_score_pairs_bert": (C.c_int, [C.POINTER(BertCfg), C.POINTER(BertWeights), C.POINTER(ScoreHeadWeights), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
                                       _P, C.c_size_t, _P]),
+    "mq_score_pairs_xlmr": (C.c_int, [C.POINTER(BertCfg), C.POINTER(BertWeights), C.POINTER(ScoreHeadWeights), _P, _P, _P, C.c_int64, _P, _P, _P, _P,
+                                      C.c_size_t, _P]),
     # image reranking: the OWL-ViT detection heads and top-k boxes (csrc/owl_head.hip; engine/owl.py)
     "mq_owl_merge_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
     "mq_owl_class_head": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_float, _P, C.c_float, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,

@@ -1,9 +1,11 @@
-// Text reranking: a cross-encoder (BertForSequenceClassification, one logit) on the BERT tower.
+// Text reranking: a cross-encoder (BertForSequenceClassification / XLMRobertaForSequenceClassification, one logit) on the BERT tower.
 //   * pair_plan / pack_pairs: [CLS] q [SEP] d [SEP] for ONE query against n documents with the `tokenizers` library's LongestFirst
-//     truncation, from the ids mq_tokenize_wordpiece left on the device.
+//     truncation, from the ids mq_tokenize_wordpiece left on the device.  pack_pairs_xlmr: <s> q </s> </s> d </s> (four specials, no
+//     type ids) from the rows mq_tokenize_sentencepiece left there.
 //   * embed_tokens_typed: embed.hip's embed_tokens with a token-type id per row.
 //   * score_head: pooler (tanh(Linear), through mq_gemm_bf16) + the one-logit classifier (+ sigmoid).
 //   * mq_score_pairs_bert: typed embedding -> encoder (the [CLS] row selection of mq_encode_bert) -> head.
+//   * mq_score_pairs_xlmr: the same with mq_encode_bert's own embedding (one type row; the position table starts at the offset row).
 // All of it is bandwidth-trivial next to the encoder: coalesced, bounds-guarded, untuned.
 #include "common.h"
 
@@ -28,17 +30,17 @@ __host__ __device__ inline void pair_keep(int la, int lb, int B, int* a, int* b)
     *b = swap ? s : l;
 }
 
-__global__ __launch_bounds__(256) void pair_plan_kernel(int la, const int32_t* __restrict__ doc_len, int n, int ld, int B,
+__global__ __launch_bounds__(256) void pair_plan_kernel(int la, const int32_t* __restrict__ doc_len, int n, int ld, int B, int specials,
                                                         int32_t* __restrict__ keep_a, int32_t* __restrict__ keep_b, int32_t* __restrict__ total) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int lb = doc_len[i] - 2;                      // [CLS] pieces [SEP]
+    int lb = doc_len[i] - 2;                      // [CLS] pieces [SEP] / <s> pieces </s>
     lb = lb < 0 ? 0 : (lb > ld - 2 ? ld - 2 : lb);
     int a, b;
     pair_keep(la, lb, B, &a, &b);
     keep_a[i] = a;
     keep_b[i] = b;
-    total[i] = a + b + 3;
+    total[i] = a + b + specials;
 }
 
 // grid = n blocks; the block's threads walk the sequence's rows.  Reads stay inside q [Lq] and row i of docs [n, ld], writes inside
@@ -65,6 +67,32 @@ __global__ __launch_bounds__(256) void pack_pairs_kernel(const int32_t* __restri
         else { id = sep_id; ty = 1; }
         ids[row0 + t] = id;
         types[row0 + t] = ty;
+    }
+}
+
+// <s> q[:a] </s> </s> d[:b] </s>: the same walk with four specials and no type ids; the same clamps keep reads inside q [Lq] and the pieces
+// of row i of docs [n, ld] (columns 1 .. ld - 2), writes inside [cu[i], min(cu[i + 1], rows)).
+__global__ __launch_bounds__(256) void pack_pairs_xlmr_kernel(const int32_t* __restrict__ q, int Lq, const int32_t* __restrict__ docs, int ld,
+                                                              const int32_t* __restrict__ keep_a, const int32_t* __restrict__ keep_b,
+                                                              const int32_t* __restrict__ cu, int cls_id, int sep_id, int32_t* __restrict__ ids,
+                                                              int64_t rows) {
+    const int i = blockIdx.x;
+    int a = keep_a[i], b = keep_b[i];
+    a = a < 0 ? 0 : (a > Lq ? Lq : a);
+    b = b < 0 ? 0 : (b > ld - 2 ? ld - 2 : b);
+    const int64_t row0 = cu[i];
+    int len = cu[i + 1] - cu[i];
+    if (len > a + b + 4) len = a + b + 4;
+    if (row0 < 0) return;
+    const int32_t* d = docs + (int64_t)i * ld + 1;
+    for (int t = threadIdx.x; t < len && row0 + t < rows; t += 256) {
+        int id;
+        if (t == 0) id = cls_id;
+        else if (t <= a) id = q[t - 1];
+        else if (t <= a + 2) id = sep_id;
+        else if (t < a + 3 + b) id = d[t - a - 3];
+        else id = sep_id;
+        ids[row0 + t] = id;
     }
 }
 
@@ -162,18 +190,26 @@ PairsPlan pairs_plan(const mq_bert_cfg* cfg, int64_t rows, int64_t nseq) {
 }
 }  // namespace
 
-extern "C" int mq_pair_plan(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t* d_keep_a,
-                            int32_t* d_keep_b, int32_t* d_total, void* stream) {
-    MQ_CHECK_ARG(max_length >= 4, "mq_pair_plan: max_length=%d must be >= 4 ([CLS] a [SEP] b [SEP] with at least one piece)", max_length);
+extern "C" int mq_pair_plan_n(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t specials,
+                              int32_t* d_keep_a, int32_t* d_keep_b, int32_t* d_total, void* stream) {
+    MQ_CHECK_ARG(specials >= 0 && specials <= 8, "mq_pair_plan: specials=%d must be in [0, 8]", specials);
+    MQ_CHECK_ARG(max_length >= specials + 1, "mq_pair_plan: max_length=%d must be >= %d (%d special tokens and at least one piece)", max_length,
+                 specials + 1, specials);
     MQ_CHECK_ARG(Lq >= 0 && ld >= 2 && n < (1ll << 31), "mq_pair_plan: bad shape Lq=%d ld=%d n=%lld", Lq, ld, (long long)n);
     if (n <= 0) return MQ_OK;
     MQ_CHECK_ARG(d_doc_len && d_keep_a && d_keep_b && d_total, "mq_pair_plan: null pointer");
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(3, s);
-    hipLaunchKernelGGL(pair_plan_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, Lq, d_doc_len, (int)n, ld, max_length - 3, d_keep_a,
-                       d_keep_b, d_total);
+    hipLaunchKernelGGL(pair_plan_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, Lq, d_doc_len, (int)n, ld, max_length - specials, specials,
+                       d_keep_a, d_keep_b, d_total);
     MQ_CHECK_LAUNCH("mq_pair_plan");
     return MQ_OK;
+}
+
+// [CLS] a [SEP] b [SEP]: three specials
+extern "C" int mq_pair_plan(int32_t Lq, const int32_t* d_doc_len, int64_t n, int32_t ld, int32_t max_length, int32_t* d_keep_a,
+                            int32_t* d_keep_b, int32_t* d_total, void* stream) {
+    return mq_pair_plan_n(Lq, d_doc_len, n, ld, max_length, 3, d_keep_a, d_keep_b, d_total, stream);
 }
 
 extern "C" int mq_pack_pairs(const int32_t* d_query, int32_t Lq, const int32_t* d_docs, int32_t ld, const int32_t* d_keep_a,
@@ -188,6 +224,21 @@ extern "C" int mq_pack_pairs(const int32_t* d_query, int32_t Lq, const int32_t* 
     hipLaunchKernelGGL(pack_pairs_kernel, dim3((unsigned)n), dim3(256), 0, s, d_query, Lq, d_docs, ld, d_keep_a, d_keep_b, d_cu, cls_id, sep_id,
                        d_ids, d_type_ids, rows);
     MQ_CHECK_LAUNCH("mq_pack_pairs");
+    return MQ_OK;
+}
+
+extern "C" int mq_pack_pairs_xlmr(const int32_t* d_query, int32_t Lq, const int32_t* d_docs, int32_t ld, const int32_t* d_keep_a,
+                                  const int32_t* d_keep_b, const int32_t* d_cu, int64_t n, int32_t cls_id, int32_t sep_id, int32_t* d_ids,
+                                  int64_t rows, void* stream) {
+    MQ_CHECK_ARG(Lq >= 0 && ld >= 2 && n < (1ll << 31) && rows >= 0, "mq_pack_pairs_xlmr: bad shape Lq=%d ld=%d n=%lld rows=%lld", Lq, ld,
+                 (long long)n, (long long)rows);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG((d_query || Lq == 0) && d_docs && d_keep_a && d_keep_b && d_cu && d_ids, "mq_pack_pairs_xlmr: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(3, s);
+    hipLaunchKernelGGL(pack_pairs_xlmr_kernel, dim3((unsigned)n), dim3(256), 0, s, d_query, Lq, d_docs, ld, d_keep_a, d_keep_b, d_cu, cls_id,
+                       sep_id, d_ids, rows);
+    MQ_CHECK_LAUNCH("mq_pack_pairs_xlmr");
     return MQ_OK;
 }
 
@@ -242,43 +293,66 @@ extern "C" size_t mq_score_pairs_workspace_bytes(const mq_bert_cfg* cfg, int64_t
     return pairs_plan(cfg, rows, nseq).total;
 }
 
-extern "C" int mq_score_pairs_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
-                                   const int32_t* d_type_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq,
-                                   float* d_logits, float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes,
-                                   void* stream) {
-    MQ_CHECK_ARG(cfg && w && head && d_logits, "mq_score_pairs_bert: null pointer");
-    MQ_CHECK_ARG(cfg->enc.precision == MQ_PREC_BF16, "mq_score_pairs_bert: bf16 encoders only (precision %d)", cfg->enc.precision);
-    MQ_CHECK_ARG(cfg->enc.post_ln == 1 && cfg->enc.mask == MQ_MASK_NONE, "mq_score_pairs_bert: BERT is post-LN with full attention");
-    MQ_CHECK_ARG(!cfg->enc.d_rope_inv_freq && !cfg->enc.mlp_glu && !cfg->enc.d_rel_bias, "mq_score_pairs_bert: plain BERT encoders only");
-    MQ_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b, "mq_score_pairs_bert: null weight pointer");
-    MQ_CHECK_ARG(head->type_vocab >= 1, "mq_score_pairs_bert: type_vocab=%d", head->type_vocab);
+namespace {
+// typed = false: every token adds type row 0, through mq_embed_tokens as mq_encode_bert embeds (XLM-R: one type row).  The position of
+// token t of a sequence is row t of w->pos_emb: for a checkpoint whose position ids start at padding_idx + 1 the host hands over the table
+// from that row on (as for mq_encode_bert), so a packed pair runs offset, offset + 1, ... over the whole pair.
+int score_pairs(const char* what, const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                const int32_t* d_type_ids, bool typed, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits,
+                float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream) {
+    MQ_CHECK_ARG(cfg && w && head && d_logits, "%s: null pointer", what);
+    MQ_CHECK_ARG(cfg->enc.precision == MQ_PREC_BF16, "%s: bf16 encoders only (precision %d)", what, cfg->enc.precision);
+    MQ_CHECK_ARG(cfg->enc.post_ln == 1 && cfg->enc.mask == MQ_MASK_NONE, "%s: BERT is post-LN with full attention", what);
+    MQ_CHECK_ARG(!cfg->enc.d_rope_inv_freq && !cfg->enc.mlp_glu && !cfg->enc.d_rel_bias, "%s: plain BERT encoders only", what);
+    MQ_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b, "%s: null weight pointer", what);
+    MQ_CHECK_ARG(head->type_vocab >= 1, "%s: type_vocab=%d", what, head->type_vocab);
     const int W = cfg->enc.width;
-    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "mq_score_pairs_bert: W=%d must be a multiple of 64, at most %d", W, 64 * 4 * MAXC);
-    MQ_CHECK_ARG(nseq < (1ll << 31), "mq_score_pairs_bert: nseq=%lld too large", (long long)nseq);
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "%s: W=%d must be a multiple of 64, at most %d", what, W, 64 * 4 * MAXC);
+    MQ_CHECK_ARG(nseq < (1ll << 31), "%s: nseq=%lld too large", what, (long long)nseq);
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_ids && d_type_ids && d_cu_seqlens && h_cu_seqlens && d_workspace, "mq_score_pairs_bert: null input / workspace");
-    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "mq_score_pairs_bert: cu_seqlens[0] must be 0");
+    MQ_CHECK_ARG(d_ids && (d_type_ids || !typed) && d_cu_seqlens && h_cu_seqlens && d_workspace, "%s: null input / workspace", what);
+    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "%s: cu_seqlens[0] must be 0", what);
     int maxl = 0;
     for (int64_t i = 0; i < nseq; ++i) {
         const int l = h_cu_seqlens[i + 1] - h_cu_seqlens[i];
-        MQ_CHECK_ARG(l >= 1 && l <= cfg->max_pos, "mq_score_pairs_bert: sequence lengths must be in [1, max_pos=%d]", cfg->max_pos);
+        MQ_CHECK_ARG(l >= 1 && l <= cfg->max_pos, "%s: sequence lengths must be in [1, max_pos=%d]", what, cfg->max_pos);
         if (l > maxl) maxl = l;
     }
     const int64_t rows = h_cu_seqlens[nseq];
     const PairsPlan p = pairs_plan(cfg, rows, nseq);
     const size_t enc_need = mq_encoder_workspace_bytes(&cfg->enc, rows, nseq);
-    if (workspace_bytes < p.total) { mq_set_error("mq_score_pairs_bert: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
-    if (p.enc_bytes < enc_need) { mq_set_error("mq_score_pairs_bert: encoder scratch %zu < required %zu", p.enc_bytes, enc_need); return MQ_ERR_WORKSPACE; }
+    if (workspace_bytes < p.total) { mq_set_error("%s: workspace %zu < required %zu", what, workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    if (p.enc_bytes < enc_need) { mq_set_error("%s: encoder scratch %zu < required %zu", what, p.enc_bytes, enc_need); return MQ_ERR_WORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)base;
     float* cls = (float*)(base + p.off_cls);
 
-    MQ_TRY(mq_embed_tokens_typed(d_ids, d_type_ids, d_cu_seqlens, nseq, w->word_emb, w->pos_emb, w->type_emb, head->type_vocab, w->emb_ln_g,
-                                 w->emb_ln_b, x, nullptr, W, cfg->vocab, cfg->enc.ln_eps, 0, s));
+    if (typed)
+        MQ_TRY(mq_embed_tokens_typed(d_ids, d_type_ids, d_cu_seqlens, nseq, w->word_emb, w->pos_emb, w->type_emb, head->type_vocab, w->emb_ln_g,
+                                     w->emb_ln_b, x, nullptr, W, cfg->vocab, cfg->enc.ln_eps, 0, s));
+    else
+        MQ_TRY(mq_embed_tokens(d_ids, d_cu_seqlens, nseq, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, x, nullptr, W, cfg->vocab,
+                               cfg->enc.ln_eps, 0, s));
     // the final [CLS] row of sequence i is row d_cu_seqlens[i]: the last block may run on those rows only, as for MQ_POOL_CLS
     MQ_TRY(mq_encoder_forward_rows(&cfg->enc, w->blocks, x, rows, d_cu_seqlens, nseq, 0, maxl, d_cu_seqlens, nseq, base + p.off_enc, p.enc_bytes, s));
     MQ_TRY(mq_pool(x, d_cu_seqlens, nseq, cls, W, MQ_POOL_CLS, 0, s));
     if (d_cls_rows) MQ_CHECK_HIP(hipMemcpyAsync(d_cls_rows, cls, (size_t)nseq * W * 4, hipMemcpyDeviceToDevice, s));
     return mq_score_head(cls, nseq, W, head, d_logits, d_scores, base + p.off_head, workspace_bytes - p.off_head, s);
+}
+}  // namespace
+
+extern "C" int mq_score_pairs_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                                   const int32_t* d_type_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq,
+                                   float* d_logits, float* d_scores, float* d_cls_rows, void* d_workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return score_pairs("mq_score_pairs_bert", cfg, w, head, d_ids, d_type_ids, true, d_cu_seqlens, h_cu_seqlens, nseq, d_logits, d_scores,
+                       d_cls_rows, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_score_pairs_xlmr(const mq_bert_cfg* cfg, const mq_bert_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                                   const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits, float* d_scores,
+                                   float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream) {
+    return score_pairs("mq_score_pairs_xlmr", cfg, w, head, d_ids, nullptr, false, d_cu_seqlens, h_cu_seqlens, nseq, d_logits, d_scores,
+                       d_cls_rows, d_workspace, workspace_bytes, stream);
 }

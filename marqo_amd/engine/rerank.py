@@ -1,9 +1,11 @@
 """Cross-encoder scoring for text reranking: (query, passage) pairs through the BERT tower and a one-logit head (csrc/rerank.hip).
 
 The reference scores pairs with sentence-transformers' `CrossEncoder` (s2_inference/reranking/model_utils.py load_sbert_cross_encoder_model),
-i.e. a Hugging Face `BertForSequenceClassification` with num_labels = 1 behind the fast tokenizer's pair call
-(`truncation="longest_first"`).  Here the texts are tokenised once on the GPU (engine/gpu_tokenizers.py), paired, truncated and packed
-there (mq_pair_plan / mq_pack_pairs), and every batch is ONE mq_score_pairs_bert call.
+i.e. a Hugging Face `*ForSequenceClassification` with num_labels = 1 behind the fast tokenizer's pair call (`truncation="longest_first"`).
+Two families are served (`_Family`): BERT (WordPiece, [CLS] a [SEP] b [SEP], two type rows, pooler + classifier) and XLM-RoBERTa /
+SentencePiece RoBERTa (<s> a </s> </s> b </s>, one type row, position ids from padding_idx + 1, classifier.dense + classifier.out_proj).
+The texts are tokenised once on the GPU (engine/gpu_tokenizers.py), paired, truncated and packed there (mq_pair_plan_n / mq_pack_pairs |
+mq_pack_pairs_xlmr), and every batch is ONE mq_score_pairs_bert | mq_score_pairs_xlmr call.
 """
 from __future__ import annotations
 
@@ -18,23 +20,40 @@ import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
-from marqo_amd.engine.tokenizers import WordPieceTokenizer
+from marqo_amd.engine.tokenizers import WordPieceTokenizer, XlmRobertaTokenizer
 from marqo_amd.engine.towers import BertTower, _large_call, _need, request_stream
 
 Tensor = torch.Tensor
 
 
-def pair_lengths(la, lb, max_length: int):
+@dataclasses.dataclass(frozen=True)
+class _Family:
+    """what differs between the cross-encoder families: everything else of CrossEncoderTower is shared"""
+    name: str
+    prefix: str           # of the encoder's weights
+    dense: str            # head: tanh(Linear) on the final first row ...
+    out: str              # ... and the one-logit Linear on it
+    specials: int         # special tokens of a packed pair
+    typed: bool           # the pack kernel writes token-type ids and the scoring call looks the type row up per token
+
+
+BERT = _Family("bert", "bert.", "bert.pooler.dense", "classifier", specials=3, typed=True)
+# RobertaClassificationHead: classifier.dense -> tanh -> classifier.out_proj on the final <s> row; the encoder has no pooler
+XLMR = _Family("xlm-roberta", "roberta.", "classifier.dense", "classifier.out_proj", specials=4, typed=False)
+
+
+def pair_lengths(la, lb, max_length: int, specials: int = 3):
     """Pieces (a, b) that the `tokenizers` library's LongestFirst truncation keeps of a pair with la and lb pieces when the sequence
-    [CLS] a [SEP] b [SEP] may hold max_length tokens (ints or integer arrays; both texts keep their prefix).  B = max_length - 3:
+    [CLS] a [SEP] b [SEP] (`specials` = 3; <s> a </s> </s> b </s>: 4) may hold max_length tokens (ints or integer arrays; both texts keep
+    their prefix).  B = max_length - specials:
     nothing is cut when la + lb <= B.  Otherwise, with s the shorter and l the longer text (on a tie the SECOND text counts as the
     longer), l' = s when s > B, else max(s, B - s); when s + l' is still above B, s = B // 2 and l' = B - s; the longer text keeps l'.
     This is NOT the slow tokenizers' loop that removes one token at a time from the longer text."""
-    if max_length < 4:
-        raise ValueError(f"max_length={max_length} must be at least 4")
+    if max_length < specials + 1:
+        raise ValueError(f"max_length={max_length} must be at least {specials + 1}")
     scalar = np.ndim(la) == 0 and np.ndim(lb) == 0
     la, lb = np.broadcast_arrays(np.asarray(la, dtype=np.int64), np.asarray(lb, dtype=np.int64))
-    B = max_length - 3
+    B = max_length - specials
     swap = la > lb
     s = np.where(swap, lb, la)
     l = np.where(s > B, s, np.maximum(s, B - s))
@@ -48,7 +67,8 @@ def pair_lengths(la, lb, max_length: int):
 
 
 def _tokenizer_settings(directory: str) -> Tuple[bool, int]:
-    """(do_lower_case, model_max_length) of a checkpoint's tokenizer_config.json (BERT's defaults when absent)"""
+    """(do_lower_case, model_max_length) of a checkpoint's tokenizer_config.json (BERT's defaults when absent; XLM-R's model_max_length
+    defaults to 512 as well)"""
     lower, max_len = True, 512
     p = os.path.join(directory, "tokenizer_config.json")
     if os.path.isfile(p):
@@ -64,41 +84,64 @@ def _tokenizer_settings(directory: str) -> Tuple[bool, int]:
     return lower, max_len
 
 
-class CrossEncoderTower(BertTower):
-    """`BertForSequenceClassification` (num_labels = 1): `bert.*` = the encoder (prepared exactly as for the embedding towers:
-    engine/tower_weights.py), `bert.pooler.dense.*` and `classifier.*` = the head.  score() returns the raw logits and their sigmoid."""
+def head_tensors(sd: Dict[str, Tensor], family: _Family, W: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dense weight [W, W], dense bias [W], out weight [1, W], out bias [1]) of a checkpoint's scoring head under the family's names"""
+    return (_need(sd, family.dense + ".weight", (W, W)), _need(sd, family.dense + ".bias", (W,)),
+            _need(sd, family.out + ".weight", (1, W)), _need(sd, family.out + ".bias", (1,)))
 
-    def __init__(self, arch: archs.BertArch, sd: Dict[str, Tensor], device: str, tokenizer: WordPieceTokenizer, model_max_length: int = 512):
-        if arch.glu or arch.rope_theta is not None or arch.rel_buckets or arch.pos_offset:
-            raise ValueError("cross-encoders run on plain BERT encoders (model_type 'bert')")
+
+class CrossEncoderTower(BertTower):
+    """`BertForSequenceClassification` / `XLMRobertaForSequenceClassification` (num_labels = 1): `bert.*` | `roberta.*` = the encoder (prepared
+    exactly as for the embedding towers: engine/tower_weights.py; XLM-R's position table is handed over from row padding_idx + 1 on),
+    `bert.pooler.dense.*` + `classifier.*` | `classifier.dense.*` + `classifier.out_proj.*` = the head (a `roberta.pooler.*` is not read: the
+    model is built with add_pooling_layer=False).  score() returns the raw logits and their sigmoid."""
+
+    def __init__(self, arch: archs.BertArch, sd: Dict[str, Tensor], device: str, tokenizer, model_max_length: int = 512,
+                 family: _Family = BERT):
+        if arch.glu or arch.rope_theta is not None or arch.rel_buckets:
+            raise ValueError("cross-encoders run on plain BERT encoders (model_type 'bert', 'xlm-roberta' or 'roberta')")
+        if bool(arch.pos_offset) != (family is XLMR):
+            raise ValueError(f"a {family.name} cross-encoder cannot have position ids that start at {arch.pos_offset}")
+        if arch.type_vocab < 1:
+            raise ValueError(f"type_vocab_size={arch.type_vocab}: a cross-encoder's embedding needs a token-type row")
         W = arch.width
         if W % 64 != 0 or W > 2048:
             raise ValueError(f"the scoring head needs a hidden size that is a multiple of 64, at most 2048 (got {W})")
-        pooler_w = _need(sd, "bert.pooler.dense.weight", (W, W))
-        pooler_b = _need(sd, "bert.pooler.dense.bias", (W,))
-        cls_w = _need(sd, "classifier.weight", (1, W))
-        cls_b = _need(sd, "classifier.bias", (1,))
-        enc = {k[len("bert."):]: v for k, v in sd.items() if k.startswith("bert.")}
+        pooler_w, pooler_b, cls_w, cls_b = head_tensors(sd, family, W)
+        enc = {k[len(family.prefix):]: v for k, v in sd.items() if k.startswith(family.prefix)}
         super().__init__(arch, enc, device, pooling="cls", precision="bf16")
         h = self._h
+        self.family = family
         self.head = L.ScoreHeadWeights(pooler_w=h.bf16(pooler_w), pooler_b=h.f32(pooler_b), cls_w=h.f32(cls_w.reshape(W)),
                                        cls_b=float(cls_b.detach().float().reshape(-1)[0]), type_vocab=int(arch.type_vocab))
-        if _need(sd, "bert.embeddings.token_type_embeddings.weight").shape != (arch.type_vocab, W):
+        if _need(sd, family.prefix + "embeddings.token_type_embeddings.weight").shape != (arch.type_vocab, W):
             raise ValueError(f"token_type_embeddings must be [{arch.type_vocab}, {W}]")
         self.tokenizer = tokenizer
-        self.model_max_length = int(min(model_max_length, arch.max_pos))
-        from marqo_amd.engine.gpu_tokenizers import DeviceWordPieceTokenizer
-        self.device_tokenizer = DeviceWordPieceTokenizer(tokenizer, str(self.device))
+        self.model_max_length = int(min(model_max_length, arch.max_pos))     # (max_pos counts the usable positions: archs.BertArch)
+        from marqo_amd.engine.gpu_tokenizers import DeviceSentencePieceTokenizer, DeviceWordPieceTokenizer
+        device_cls = DeviceWordPieceTokenizer if family is BERT else DeviceSentencePieceTokenizer
+        self.device_tokenizer = device_cls(tokenizer, str(self.device))
         self.tune_residual_default()      # the same load-time policy as the embedding towers, on the encoder's [CLS] rows
         self.release_unused_folded()
 
     @classmethod
     def from_dir(cls, directory: str, device: str) -> "CrossEncoderTower":
-        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, vocab.txt, tokenizer_config.json"""
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, vocab.txt | sentencepiece.bpe.model,
+        tokenizer_config.json"""
         cfg, sd = checkpoint.load_hf_dir(directory)
         mtype = cfg.get("model_type", "bert")
-        if mtype != "bert":
-            raise ValueError(f"{directory}: model_type={mtype!r} is not served as a cross-encoder (only 'bert')")
+        if mtype == "bert":
+            family = BERT
+        elif mtype in ("xlm-roberta", "roberta"):
+            family = XLMR
+            if not os.path.isfile(os.path.join(directory, "sentencepiece.bpe.model")):
+                if mtype == "roberta" or os.path.isfile(os.path.join(directory, "merges.txt")):
+                    raise ValueError(f"{directory}: model_type={mtype!r} with a byte-level BPE tokeniser (vocab.json + merges.txt) is not served as "
+                                     f"a cross-encoder: RoBERTa checkpoints are served only with a SentencePiece model (sentencepiece.bpe.model)")
+                raise ValueError(f"{directory}: model_type={mtype!r} needs the checkpoint's sentencepiece.bpe.model, which is not there")
+        else:
+            raise ValueError(f"{directory}: model_type={mtype!r} is not served as a cross-encoder (only 'bert', 'xlm-roberta', and 'roberta' "
+                             f"with a SentencePiece model)")
         labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
         if int(labels) != 1:
             raise ValueError(f"{directory}: num_labels={labels} is not served as a cross-encoder (only one-logit heads)")
@@ -106,38 +149,53 @@ class CrossEncoderTower(BertTower):
             arch = archs.bert_arch_from_hf_config(cfg)
         except KeyError as e:
             raise ValueError(f"{directory}: {e}") from e
-        arch = dataclasses.replace(arch, type_vocab=int(cfg.get("type_vocab_size", 2)))
+        arch = dataclasses.replace(arch, type_vocab=int(cfg.get("type_vocab_size", 2 if family is BERT else 1)))
         lower, max_len = _tokenizer_settings(directory)
-        return cls(arch, sd, device, WordPieceTokenizer(directory, do_lower_case=lower), model_max_length=max_len)
+        tokenizer = WordPieceTokenizer(directory, do_lower_case=lower) if family is BERT else XlmRobertaTokenizer(directory)
+        return cls(arch, sd, device, tokenizer, model_max_length=max_len, family=family)
 
     # ---- scoring -------------------------------------------------------------------------------------------------------------------
     def _tokenize(self, texts: Sequence[str], cap: int) -> Tuple[Tensor, np.ndarray]:
         d_ids, lens = self.device_tokenizer.encode_device(list(texts), cap)
         return d_ids.contiguous(), lens.numpy().astype(np.int64)
 
+    def _tokenize_query(self, query: str) -> Tuple[Tensor, np.ndarray]:
+        """the query's row at its full length.  A WordPiece text has at most one piece per character.  SentencePiece adds the dummy prefix
+        and normalises by NFKC, which can expand a character: a row that fills 4 pieces per character is tokenised again on the host."""
+        if self.family is BERT:
+            return self._tokenize([query], max(len(query) + 2, 4))
+        cap = 4 * len(query) + 4
+        d_q, qlen = self._tokenize([query], cap)
+        if int(qlen[0]) >= cap:
+            row = np.asarray(self.tokenizer.encode(query), dtype=np.int32)
+            return self._to_device(torch.from_numpy(row[None, :])), np.asarray([row.size], dtype=np.int64)
+        return d_q, qlen
+
     def score(self, query: str, docs: Sequence[str], max_length: int = 512) -> Tuple[np.ndarray, np.ndarray]:
         """-> (logits, sigmoid(logits)) fp32 [len(docs)] on the host, in the order of `docs`.  Texts are stripped as CrossEncoder strips
-        them; the pair is cut to min(max_length, the tokenizer's model_max_length) tokens by `pair_lengths`."""
+        them; the pair is cut to min(max_length, the tokenizer's model_max_length) tokens by `pair_lengths`.  An empty text contributes no
+        piece, as in the fast tokenizer's pair call: the pair keeps all of its special tokens."""
         if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
             raise TypeError("a cross-encoder scores (str, str) pairs")
         n = len(docs)
         if n == 0:
             return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        fam = self.family
         cap = int(min(max_length, self.model_max_length))
-        if cap < 4:
-            raise ValueError(f"max_length={max_length} must be at least 4")
+        if cap < fam.specials + 1:
+            raise ValueError(f"max_length={max_length} must be at least {fam.specials + 1}")
         query, docs = query.strip(), [d.strip() for d in docs]
         lib, dev, tok = self.lib, self.device, self.tokenizer
         with request_stream(dev), torch.cuda.device(dev):
             # the query once (its full length: which text is the longer decides who loses a piece), the documents once.  A document cut
-            # to cap - 2 pieces is still longer than B = cap - 3, and still at least as long as any query of <= cap - 2 pieces; for a
-            # longer query the documents are read up to the query's length, which keeps every comparison of pair_lengths exact.
-            d_q, qlen = self._tokenize([query], max(len(query) + 2, 4))
+            # to cap - 2 pieces is still longer than B = cap - specials, and still at least as long as any query of <= cap - 2 pieces; for
+            # a longer query the documents are read up to the query's length, which keeps every comparison of pair_lengths exact.
+            d_q, qlen = self._tokenize_query(query)
             la = int(qlen[0]) - 2
             ld = cap if la <= cap - 2 else la + 2
             d_docs, dlen = self._tokenize(docs, ld)
-            a, b = pair_lengths(la, dlen - 2, cap)
-            total = (a + b + 3).astype(np.int64)
+            a, b = pair_lengths(la, dlen - 2, cap, fam.specials)
+            total = (a + b + fam.specials).astype(np.int64)
             order = np.argsort(-total, kind="stable")          # longest first: a batch holds sequences of similar length
             inv = np.empty(n, dtype=np.int64)
             inv[order] = np.arange(n)
@@ -158,21 +216,32 @@ class CrossEncoderTower(BertTower):
                     cu = torch.from_numpy(cu_np)
                     d_cu = self._to_device(cu)
                     plan = torch.empty(3, m, dtype=torch.int32, device=dev)
-                    d_ids = torch.empty(2, rows, dtype=torch.int32, device=dev)
-                    L.check(lib.mq_pair_plan(la, d_dlen[s0:s1].data_ptr(), m, ld, cap, plan[0].data_ptr(), plan[1].data_ptr(),
-                                             plan[2].data_ptr(), stream), "mq_pair_plan")
-                    L.check(lib.mq_pack_pairs(d_query.data_ptr() if la > 0 else None, la, d_docs[s0:s1].data_ptr(), ld, plan[0].data_ptr(),
-                                              plan[1].data_ptr(), d_cu.data_ptr(), m, tok.cls_id, tok.sep_id, d_ids[0].data_ptr(),
-                                              d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
+                    d_ids = torch.empty(2 if fam.typed else 1, rows, dtype=torch.int32, device=dev)
+                    L.check(lib.mq_pair_plan_n(la, d_dlen[s0:s1].data_ptr(), m, ld, cap, fam.specials, plan[0].data_ptr(), plan[1].data_ptr(),
+                                               plan[2].data_ptr(), stream), "mq_pair_plan_n")
+                    pack = (d_query.data_ptr() if la > 0 else None, la, d_docs[s0:s1].data_ptr(), ld, plan[0].data_ptr(), plan[1].data_ptr(),
+                            d_cu.data_ptr(), m, tok.cls_id, tok.sep_id, d_ids[0].data_ptr())
+                    if fam.typed:
+                        L.check(lib.mq_pack_pairs(*pack, d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
+                    else:
+                        L.check(lib.mq_pack_pairs_xlmr(*pack, rows, stream), "mq_pack_pairs_xlmr")
                     ws = self._workspace(lib.mq_score_pairs_workspace_bytes(C.byref(self.cfg), rows, m))
-                    self.score_packed(d_ids[0], d_ids[1], d_cu, cu, logits[s0:s1], scores[s0:s1], None, ws)
+                    self.score_packed(d_ids[0], d_ids[1] if fam.typed else None, d_cu, cu, logits[s0:s1], scores[s0:s1], None, ws)
             out = torch.stack((logits, scores)).cpu().numpy()
         return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
 
-    def score_packed(self, d_ids: Tensor, d_type_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Optional[Tensor],
+    def score_packed(self, d_ids: Tensor, d_type_ids: Optional[Tensor], d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Optional[Tensor],
                      cls_rows: Optional[Tensor], ws: Tensor) -> None:
-        """one mq_score_pairs_bert call on this thread's current stream: packed ids / type ids int32 [rows], cu_seqlens on the device and the
-        host, logits / scores fp32 [nseq] (scores may be None), cls_rows fp32 [nseq, W] or None"""
+        """one mq_score_pairs_bert | mq_score_pairs_xlmr call on this thread's current stream: packed ids / type ids int32 [rows] (type ids:
+        BERT only, None for XLM-R), cu_seqlens on the device and the host, logits / scores fp32 [nseq] (scores may be None), cls_rows fp32
+        [nseq, W] or None"""
+        if (d_type_ids is not None) != self.family.typed:
+            raise ValueError(f"a {self.family.name} cross-encoder takes {'token-type ids' if self.family.typed else 'no token-type ids'}")
+        if not self.family.typed:
+            L.check(self.lib.mq_score_pairs_xlmr(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_cu.data_ptr(),
+                                                 cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores), L.ptr(cls_rows),
+                                                 ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_xlmr")
+            return
         L.check(self.lib.mq_score_pairs_bert(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_type_ids.data_ptr(),
                                              d_cu.data_ptr(), cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores),
                                              L.ptr(cls_rows), ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_bert")

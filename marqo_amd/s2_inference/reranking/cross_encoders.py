@@ -179,7 +179,7 @@ class ReRanker:
 
 
 class ReRankerText(ReRanker):
-    """reranking with a Hugging Face cross-encoder (BertForSequenceClassification with one logit)"""
+    """reranking with a Hugging Face cross-encoder (BertForSequenceClassification / XLMRobertaForSequenceClassification with one logit)"""
 
     def __init__(self, model_name: str, device: str, max_length: int = 512, num_highlights: int = 1,
                  split_params: Optional[Dict] = get_default_text_processing_parameters()):
