@@ -1103,6 +1103,35 @@ int mq_temporal_embed_ln(float* d_x, const float* d_temb, const float* d_g, cons
 int mq_temporal_attention(const void* d_qkv, void* d_out, int64_t B, int32_t T, int32_t N, int32_t W, int32_t heads, void* stream);
 int mq_patchify_clip(const float* d_in, void* d_out, int64_t B, int32_t T, int32_t S, int32_t P, int32_t Kp, void* stream);
 
+/* ---- LanguageBind audio part: Kaldi fbank, the three-crop picture, im2col rows of a non-square picture (csrc/audio.hip; engine/audio.py,
+ * engine/languagebind.py) -----------------------------------------------------------------------------------------------------------------------
+ * s2_inference/languagebind/audio/processing_audio.py in the reference: torchaudio.compliance.kaldi.fbank (sample_frequency 16000, frame_length 25,
+ * frame_shift 10, window_type "hanning", dither 0, use_energy False, htk_compat True, everything else at torchaudio's default), three crops of the
+ * log-mel rows stacked into a [3, num_mel_bins, target_length] picture, (x - audio_mean) / (2 audio_std); modeling_audio.py:767-811: a CLIP ViT
+ * over image_size = [num_mel_bins, target_length].  Additions to ABI 14: nothing above changes.  Every entry point judges its arguments before any
+ * launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_fbank:         d_wave fp32 [n_mean] -> d_mel fp32 [m, bins], m = 1 + (n - 400) / 160 (integer division; the samples behind the last whole
+ *                     frame are dropped).  The mean of all n_mean samples is subtracted first (the reference's `audio_data -= audio_data.mean()`
+ *                     over the whole tensor), and frames are cut from the first n of them: for a [channels, n] waveform n_mean = channels n and
+ *                     channel 0 is framed, as Kaldi does; for a 1-D one n_mean = n.  Per frame: subtract the frame's mean; x[i] -= 0.97 x[i - 1]
+ *                     with x[-1] := x[0]; times the symmetric Hann window 0.5 - 0.5 cos(2 pi i / 399); zero-padded to 512; power spectrum of bins
+ *                     0..255 (the Nyquist bin carries no weight); `bins` triangular filters, linear in mel(f) = 1127 ln(1 + f / 700) from 20 Hz to
+ *                     8 kHz; log(max(e, FLT_EPSILON)).  fp32 in and out, fp64 between (the FFT and the filter sums included).  d_ws:
+ *                     MQ_FBANK_WS_BYTES of device scratch, 8-byte aligned (the partial sums of the mean).  Served: sample_rate == 16000,
+ *                     1 <= bins <= 128, n >= 400; anything else is refused.
+ *   mq_mel_fusion:    d_mel fp32 [m, bins] -> d_px fp32 [3, bins, L]: px[c, f, t] = (mel[(start_c + t) mod m, f] - mean) / (2 std), the division
+ *                     IEEE.  start 0, 0, 0 on m <= L rows is the reference's mel.repeat(...)[:L]; three starts with start + L <= m are its three
+ *                     crops.  0 <= start_c < m, std > 0, 1 <= bins <= 128.
+ *   mq_patchify_rect: d_in fp32 [n, 3, H, Wd] -> d_out bf16 [n (H/P)(Wd/P), Kp], rows in (img, py, px) order, columns as mq_patchify writes them
+ *                     (c P^2 + ky P + kx, zero from 3 P^2 on); for H == Wd bit for bit what mq_patchify (is_u8 == 0) writes.  H % P == 0,
+ *                     Wd % P == 0, Kp % 8 == 0, Kp >= 3 P^2, d_out 16-byte aligned. */
+#define MQ_FBANK_WS_BYTES 2048
+int mq_fbank(const float* d_wave, int64_t n, int64_t n_mean, int32_t sample_rate, int32_t bins, float* d_mel, void* d_ws, void* stream);
+int mq_mel_fusion(const float* d_mel, int64_t m, int32_t bins, int64_t start0, int64_t start1, int64_t start2, float mean, float std, float* d_px,
+                  int32_t L, void* stream);
+int mq_patchify_rect(const float* d_in, void* d_out, int64_t n, int32_t H, int32_t Wd, int32_t P, int32_t Kp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

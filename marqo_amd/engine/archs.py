@@ -625,7 +625,9 @@ def owl_arch_from_hf_config(cfg: dict, base: Optional[OwlArch] = None) -> OwlArc
 class LanguageBindArch:
     """One LanguageBind part (the reference's languagebind/{video,image}/configuration_*.py) as the engine runs it: a CLIP ViT with
     `pre_layrnorm` whose class rows are pooled, with `add_time_attn` a temporal sub-block in front of every layer and the mean over the
-    `num_frames` class rows of a clip, and a 77-position CLIP text tower.  Both project to `projection_dim`."""
+    `num_frames` class rows of a clip, and a 77-position CLIP text tower.  Both project to `projection_dim`.  An AUDIO part
+    (languagebind/audio/configuration_audio.py) has `num_mel_bins` and `target_length` set: its picture is num_mel_bins x target_length
+    (modeling_audio.py:769-771), `image_size` is then not what the tower runs on."""
     image_size: int
     patch_size: int
     width: int
@@ -645,14 +647,36 @@ class LanguageBindArch:
     text_quick_gelu: bool = False
     ln_eps: float = 1e-5
     text_ln_eps: float = 1e-5
+    num_mel_bins: int = 0
+    target_length: int = 0
+    audio_sample_rate: int = 16000
+    audio_mean: float = 0.5
+    audio_std: float = 0.5
+
+    @property
+    def is_audio(self) -> bool:
+        return self.num_mel_bins != 0 and self.target_length != 0
+
+    @property
+    def image_hw(self) -> tuple:
+        """(height, width) of the picture the vision side runs on"""
+        return (self.num_mel_bins, self.target_length) if self.is_audio else (self.image_size, self.image_size)
 
     @property
     def grid(self) -> int:
         return self.image_size // self.patch_size
 
     @property
+    def grid_h(self) -> int:
+        return self.image_hw[0] // self.patch_size
+
+    @property
+    def grid_w(self) -> int:
+        return self.image_hw[1] // self.patch_size
+
+    @property
     def tokens(self) -> int:
-        return self.grid ** 2 + 1
+        return self.grid_h * self.grid_w + 1
 
     def vision(self) -> VitArch:
         return VitArch(image_size=self.image_size, patch_size=self.patch_size, width=self.width, layers=self.layers, heads=self.heads,
@@ -665,7 +689,8 @@ class LanguageBindArch:
 
 def languagebind_arch_from_hf_config(cfg: dict) -> LanguageBindArch:
     """A local LanguageBind `config.json` -> LanguageBindArch.  Keys the file leaves out take the defaults of the reference's configuration
-    classes (CLIP ViT-B/32-like sides, 512-wide projection, quick_gelu, one frame, no temporal attention)."""
+    classes (CLIP ViT-B/32-like sides, 512-wide projection, quick_gelu, one frame, no temporal attention; for the audio keys
+    num_mel_bins 0, target_length 0 — both written as 0.0 there —, audio_sample_rate 16000, audio_mean 0.5, audio_std 0.5)."""
     v, t = cfg.get("vision_config") or {}, cfg.get("text_config") or {}
     acts = {"quick_gelu": True, "gelu": False}
     for side, c in (("vision", v), ("text", t)):
@@ -679,4 +704,7 @@ def languagebind_arch_from_hf_config(cfg: dict) -> LanguageBindArch:
                             text_mlp_dim=int(t.get("intermediate_size", 2048)), out_dim=int(cfg.get("projection_dim", 512)),
                             vocab=int(t.get("vocab_size", 49408)), ctx=int(t.get("max_position_embeddings", 77)),
                             quick_gelu=acts[v.get("hidden_act", "quick_gelu")], text_quick_gelu=acts[t.get("hidden_act", "quick_gelu")],
-                            ln_eps=float(v.get("layer_norm_eps", 1e-5)), text_ln_eps=float(t.get("layer_norm_eps", 1e-5)))
+                            ln_eps=float(v.get("layer_norm_eps", 1e-5)), text_ln_eps=float(t.get("layer_norm_eps", 1e-5)),
+                            num_mel_bins=int(v.get("num_mel_bins", 0)), target_length=int(v.get("target_length", 0)),
+                            audio_sample_rate=int(v.get("audio_sample_rate", 16000)), audio_mean=float(v.get("audio_mean", 0.5)),
+                            audio_std=float(v.get("audio_std", 0.5)))

@@ -1,4 +1,4 @@
-"""LanguageBind video / image / text embeddings: the model family behind the reference's `languagebind` loader (s2_inference/languagebind/,
+"""LanguageBind video / audio / image / text embeddings: the model family behind the reference's `languagebind` loader (s2_inference/languagebind/,
 s2_inference/multimodal_model_load.py).
 
 LanguageBind_Video_V1.5_FT is a CLIP ViT-L/14 over the T = 8 frames of a clip with a temporal sub-block in front of every layer
@@ -16,6 +16,16 @@ r = (b T + t) N + n from the first layer to the last, and the temporal attention
 
 Everything of a call runs on one stream; the scratch of the per-layer path is allocated once per call, in front of the first layer.  The residual
 stream is fp32 (the temporal embedding is added into it with one fp32 add, as the reference keeps the sum in its stream).  bf16 operands only.
+
+The audio part (`LanguageBind_Audio_FT`, languagebind/audio/modeling_audio.py:767-811) is the same CLIP ViT over ONE picture that is not
+square: image_size = [num_mel_bins, target_length], 112 x 1036 at patch 14 for the released checkpoint, an 8 x 74 grid of 593 tokens, one frame,
+no temporal attention.  Its positions are already in the checkpoint at that length (the reference resizes them at construction, before the
+weights load), so nothing is interpolated here:
+
+    mq_patchify_rect (fp32 [b, 3, bins, L] -> im2col rows in (py, px) order) -> mq_gemm_bf16 -> mq_vit_assemble -> mq_encoder_forward (all blocks)
+    -> mq_cls_rows -> mq_layernorm (post_layernorm) -> mq_gemm_bf16 (visual_projection) -> mq_l2_normalize
+
+The picture comes from engine/audio.py (Kaldi fbank and the three-crop fusion on the GPU) or from the caller's own preprocessing.
 
 The image part (`LanguageBind_Image`, no temporal attention) is a plain CLIP ViT under Hugging Face names and runs on `towers.VitTower`; the
 text tower is `towers.ClipTextTower` on 77 positions, packed up to the EOT as everywhere in this engine.
@@ -151,16 +161,75 @@ class LanguageBindVideoTower(VitTokenTower):
         return out
 
 
+class LanguageBindAudioTower(VitTokenTower):
+    """`LanguageBindAudio` vision side (`vision_model.*`, `visual_projection.weight`) -> one embedding per spectrogram picture
+    [3, num_mel_bins, target_length].  bf16 operands only."""
+
+    def __init__(self, arch: LanguageBindArch, sd: Dict[str, Tensor], device: str, precision: str = "bf16"):
+        if not arch.is_audio:
+            raise ValueError("LanguageBindAudioTower is the tower of an audio part: vision_config.num_mel_bins and vision_config.target_length must "
+                             f"be set (they are {arch.num_mel_bins} and {arch.target_length})")
+        if arch.add_time_attn or arch.num_frames != 1:
+            raise ValueError(f"an audio part is one picture without temporal attention (the checkpoint has add_time_attn = {arch.add_time_attn}, "
+                             f"num_frames = {arch.num_frames})")
+        if arch.num_mel_bins % arch.patch_size or arch.target_length % arch.patch_size:
+            raise ValueError(f"the {arch.num_mel_bins} x {arch.target_length} picture of this audio part is no whole grid of {arch.patch_size}-pixel patches")
+        super().__init__(device, arch, precision, arch.layers)
+        W = arch.width
+        if arch.out_dim % 4 or arch.out_dim > 2048:
+            raise ValueError(f"LanguageBindAudioTower takes a projection dimension that is a multiple of 4, at most 2048 (the checkpoint has {arch.out_dim})")
+        pos = _need(sd, "vision_model.embeddings.position_embedding.weight")
+        if pos.ndim != 2 or pos.shape[0] != arch.tokens:
+            raise ValueError(f"the checkpoint's position_embedding has {pos.shape[0]} rows, the {arch.grid_h} x {arch.grid_w} grid of a "
+                             f"{arch.num_mel_bins} x {arch.target_length} picture at patch {arch.patch_size} needs {arch.tokens} (the reference resizes "
+                             f"the positions before it loads the weights: a saved audio checkpoint already has them; nothing is interpolated here)")
+        self._load_hf_vit(sd, "vision_model.", "pre_layrnorm")
+        self._proj = self._h.bf16(_need(sd, "visual_projection.weight", (arch.out_dim, W)))
+
+    def _forward(self, px: Tensor, out: Tensor, normalize: bool) -> None:
+        """px fp32 [b, 3, bins, L] on the device (contiguous) -> out fp32 [b, D]"""
+        lib, a, s, dev = self.lib, self.arch, self._stream(), self.device
+        b, W, N, D = px.shape[0], a.width, a.tokens, a.out_dim
+        patches = self._patchify_f32(px)
+        x = self._tokens(patches, b)
+        del patches
+        self._encoder(x, b, self._encoder_workspace(b))
+        cls_rows = torch.empty(b, dtype=torch.int32, device=dev)
+        cls_ln = torch.empty(b, W, dtype=torch.bfloat16, device=dev)
+        proj = out if not normalize else torch.empty(b, D, dtype=torch.float32, device=dev)
+        L.check(lib.mq_cls_rows(cls_rows.data_ptr(), b, N, s), "mq_cls_rows")
+        L.check(lib.mq_layernorm(x.data_ptr(), cls_rows.data_ptr(), self._post[0], self._post[1], cls_ln.data_ptr(), None, b, W, a.ln_eps, s), "mq_layernorm")
+        L.check(lib.mq_gemm_bf16(cls_ln.data_ptr(), W, self._proj, W, None, None, proj.data_ptr(), D, b, D, W, L.MQ_EPI_OUT_F32, s), "mq_gemm_bf16")
+        if normalize:
+            L.check(lib.mq_l2_normalize(proj.data_ptr(), out.data_ptr(), b, D, s), "mq_l2_normalize")
+
+    def encode_spectrograms(self, pixel_values: Tensor, normalize: bool = True) -> Tensor:
+        """preprocessed fp32 [b, 3, bins, L] (`pixel_values`, host or device) -> fp32 [b, D] on the device: visual_projection(post_layernorm(class
+        row)), divided by its norm when `normalize`"""
+        a = self.arch
+        want = (3, a.num_mel_bins, a.target_length)
+        if not isinstance(pixel_values, torch.Tensor) or pixel_values.ndim != 4 or tuple(pixel_values.shape[1:]) != want:
+            got = tuple(pixel_values.shape) if isinstance(pixel_values, torch.Tensor) else type(pixel_values).__name__
+            raise ValueError(f"expected pixel_values [b, 3, {a.num_mel_bins}, {a.target_length}] (the checkpoint's num_mel_bins x target_length), got {got}")
+        with torch.cuda.device(self.device):
+            px = pixel_values.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+            n = px.shape[0]
+            out = torch.empty(n, a.out_dim, dtype=torch.float32, device=self.device)
+            for i in range(0, n, self.max_items_per_call):
+                j = min(n, i + self.max_items_per_call)
+                self._forward(px[i:j], out[i:j], bool(normalize))
+        return out
+
+
 class LanguageBindModel:
-    """The parts of one LanguageBind model name on one device: video tower, image tower (when the name has an image part), the text tower of the
-    LAST part in the reference's order (the image part's when present, else the video part's), its tokenizer, and each part's logit_scale."""
+    """The parts of one LanguageBind model name on one device: video tower, audio tower, image tower (each when the name has that part), the text
+    tower of the LAST part in the reference's order (the image part's when present, else the audio part's, else the video part's), its tokenizer,
+    and each part's logit_scale."""
 
     def __init__(self, name: str, localpath: str, device: str, precision: str = "bf16"):
         if name not in MODEL_PARTS:
             raise ValueError(f"Unsupported LanguageBind model: {name}")
         parts = MODEL_PARTS[name]
-        if "audio" in parts:
-            raise ValueError(f"{name}: the audio part {parts['audio']} is not supported (no audio tower in this engine)")
         _check_precision(precision, ("bf16",), f"LanguageBind models run on bf16 operands only ('enginePrecision': {precision!r} is not supported)")
         if not localpath or not os.path.isdir(localpath):
             raise FileNotFoundError(f"{name}: `localpath` must be a directory with one sub-directory per part ({', '.join(parts.values())}); "
@@ -168,6 +237,7 @@ class LanguageBindModel:
         self.name, self.parts, self.device = name, dict(parts), device
         self.logit_scale: Dict[str, float] = {}
         self.video: Optional[LanguageBindVideoTower] = None
+        self.audio: Optional[LanguageBindAudioTower] = None
         self.image: Optional[VitTower] = None
         last_dir = last_sd = last_arch = None
         for kind, part in parts.items():
@@ -182,6 +252,11 @@ class LanguageBindModel:
                 raise ValueError(f"{d}: {e.args[0] if e.args else e}") from e
             if kind == "video":
                 self.video = LanguageBindVideoTower(arch, sd, device)
+            elif kind == "audio":
+                try:
+                    self.audio = LanguageBindAudioTower(arch, sd, device)
+                except ValueError as e:
+                    raise ValueError(f"{d}: {e}") from e
             else:
                 if arch.add_time_attn:
                     raise ValueError(f"{d}: the image part must not have temporal attention (vision_config.add_time_attn)")
@@ -215,7 +290,7 @@ class LanguageBindModel:
         with request_stream(dev, device_output=True):
             return self.text.encode_ids(torch.from_numpy(self.token_ids(list(texts))), normalize=True).to(dev, non_blocking=True)
 
-    # ---- video / image ----------------------------------------------------------------------------------------------------------------------
+    # ---- video / audio / image ----------------------------------------------------------------------------------------------------------------------
     def _scaled(self, unit: Tensor, kind: str, normalize: bool) -> Tensor:
         """languagebind/__init__.py:59-63, multimodal_model_load.py:298-299: the unit row times exp(logit_scale) of its part; unit again with
         `normalize` (the row IS the unit vector then: it is not scaled and divided again)"""
@@ -226,6 +301,21 @@ class LanguageBindModel:
             raise ValueError(f"{self.name} has no video part")
         with request_stream(self.video.device, device_output=True):
             return self._scaled(self.video.encode_clips(pixel_values, normalize=True), "video", normalize)
+
+    def encode_audio(self, pixel_values: Tensor, normalize: bool = True) -> Tensor:
+        """preprocessed fp32 [b, 3, num_mel_bins, target_length] -> fp32 [b, D] on the device"""
+        if self.audio is None:
+            raise ValueError(f"{self.name} has no audio part")
+        with request_stream(self.audio.device, device_output=True):
+            return self._scaled(self.audio.encode_spectrograms(pixel_values, normalize=True), "audio", normalize)
+
+    def audio_preprocessor(self):
+        """engine/audio.py's front end for this model's audio part (waveforms -> `pixel_values`), None without one"""
+        if self.audio is None:
+            return None
+        from marqo_amd.engine.audio import AudioPreprocessor
+        a = self.audio.arch
+        return AudioPreprocessor(str(self.audio.device), a.num_mel_bins, a.target_length, a.audio_sample_rate, a.audio_mean, a.audio_std)
 
     def encode_image_u8(self, u8: Tensor, normalize: bool = True) -> Tensor:
         """uint8 [n, S, S, 3] on the device (resized and cropped) -> fp32 [n, D] on the device"""

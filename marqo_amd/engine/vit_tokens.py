@@ -20,11 +20,12 @@ class VitTokenTower(_ImageTowerBase):
     def __init__(self, device: str, arch, precision: str, enc_layers: int, frames: int = 1):
         super().__init__(device)
         W, P, S, name = arch.width, arch.patch_size, arch.image_size, type(self).__name__
+        H, Wd = getattr(arch, "image_hw", (S, S))       # (a picture that is not square: the LanguageBind audio part's mel bins x frames)
         _check_precision(precision, ("bf16",), f"{name} runs on bf16 operands only, got precision {precision!r}")
-        if arch.heads * 64 != W or W > 2048 or arch.layers < 1 or S % P or arch.tokens > 8192:
+        if arch.heads * 64 != W or W > 2048 or arch.layers < 1 or H % P or Wd % P or arch.tokens > 8192:
             raise ValueError(f"{name} runs 64-wide attention heads, widths up to 2048, a whole grid of at most 8191 patches and at least one block "
-                             f"(width {W} with {arch.heads} heads, image {S} / patch {P}, {arch.layers} blocks)")
-        self.precision, self.arch, self.grid = precision, arch, S // P
+                             f"(width {W} with {arch.heads} heads, image {S if H == Wd else f'{H} x {Wd}'} / patch {P}, {arch.layers} blocks)")
+        self.precision, self.arch, self.grid, self.grid_hw = precision, arch, S // P, (H // P, Wd // P)
         self.enc = _encoder_cfg(W, enc_layers, arch.heads, arch.mlp_dim, arch.quick_gelu, False, L.MQ_MASK_NONE, arch.ln_eps)
         self.enc.residual_stream = 2
         self.max_items_per_call = max(1, MAX_ROWS_PER_CALL // (frames * arch.tokens))
@@ -50,9 +51,19 @@ class VitTokenTower(_ImageTowerBase):
     def _patchify(self, u8: Tensor) -> Tensor:
         """uint8 [m, S, S, 3] on the device -> bf16 im2col rows [m G G, Kp], normalised with the tower's `mean` / `std`"""
         a, m = self.arch, u8.shape[0]
+        if self.grid_hw != (self.grid, self.grid):
+            raise ValueError(f"{type(self).__name__}: mq_patchify takes square uint8 images, this tower's grid is {self.grid_hw[0]} x {self.grid_hw[1]}")
         patches = torch.empty(m * self.grid ** 2, self.Kp, dtype=torch.bfloat16, device=self.device)
         L.check(self.lib.mq_patchify(u8.data_ptr(), 1, patches.data_ptr(), m, a.image_size, a.patch_size, self.Kp, C.addressof(self.mean), C.addressof(self.std),
                                      self._stream()), "mq_patchify")
+        return patches
+
+    def _patchify_f32(self, px: Tensor) -> Tensor:
+        """preprocessed fp32 [m, 3, H, Wd] on the device (contiguous; H x Wd the tower's picture, square or not) -> bf16 im2col rows [m Gh Gw, Kp]"""
+        a, m, (gh, gw) = self.arch, px.shape[0], self.grid_hw
+        patches = torch.empty(m * gh * gw, self.Kp, dtype=torch.bfloat16, device=self.device)
+        L.check(self.lib.mq_patchify_rect(px.data_ptr(), patches.data_ptr(), m, gh * a.patch_size, gw * a.patch_size, a.patch_size, self.Kp, self._stream()),
+                "mq_patchify_rect")
         return patches
 
     def _tokens(self, patches: Tensor, frames: int) -> Tensor:

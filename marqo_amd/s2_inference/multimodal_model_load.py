@@ -1,15 +1,20 @@
 """The `languagebind` loader: the engine's `MultimodalModel` and `LanguageBindEncoder` (reference: s2_inference/multimodal_model_load.py:42-115,
 204-311; the model itself: s2_inference/languagebind/__init__.py:33-64).  Written from the behaviour, not from the text, of those classes.
 
-What is served: the two names whose parts are video, image and text — `LanguageBind/Video_V1.5_FT` and `LanguageBind/Video_V1.5_FT_Image` — on
-the HIP towers of engine/languagebind.py, modalities VIDEO, IMAGE and TEXT.  What is not:
-  * the audio tower (spectrogram front end, non-square grid): the four names with an audio part are refused at load with
-    InvalidModelPropertiesError naming that part;
-  * decoding media: no video / audio decoder is a dependency of this engine, and the reference's video processor applies a RANDOM horizontal
-    flip.  VIDEO content is what the reference's caller hands over after ITS preprocessing: `pixel_values` [b, 3, T, S, S];
+What is served: all six names of the reference's part table (`LanguageBind/Video_V1.5_FT`, `..._Image`, `..._Audio_FT`, `..._Audio_FT_Image`,
+`LanguageBind/Audio_FT`, `LanguageBind/Audio_FT_Image`) on the HIP towers of engine/languagebind.py, modalities VIDEO, AUDIO, IMAGE and TEXT, bf16.
+AUDIO content is the `pixel_values` [b, 3, num_mel_bins, target_length] of the reference's audio processor; `preprocessor(Modality.AUDIO)` of a
+model with an audio part is engine/audio.py's AudioPreprocessor, which makes them on the GPU from 16 kHz waveforms (Kaldi fbank, the three-crop
+fusion).  What is not:
+  * decoding media: no video / audio decoder is a dependency of this engine, and there is no resampler: a waveform at another rate than the
+    checkpoint's is refused.  VIDEO content is what the reference's caller hands over after ITS preprocessing: `pixel_values` [b, 3, T, S, S];
+  * the reference's randomness: its video processor applies a RANDOM horizontal flip, and its audio processor draws the three crop starts of a
+    clip longer than target_length at RANDOM.  AudioPreprocessor takes the middle of each third instead and accepts explicit `starts`
+    (engine/audio.py);
   * fp8 ('enginePrecision': 'fp8' is refused like the ConvNeXt towers: bf16 only);
   * downloads: `localpath` in model_properties names a directory with one sub-directory per part (LanguageBind_Video_V1.5_FT,
-    LanguageBind_Image), each a Hugging Face checkpoint directory (config.json, model.safetensors | pytorch_model.bin, vocab.json, merges.txt).
+    LanguageBind_Audio_FT, LanguageBind_Image), each a Hugging Face checkpoint directory (config.json, model.safetensors | pytorch_model.bin,
+    vocab.json, merges.txt).
 
 The names are reached through `model_properties` (the reference's registry dict for the name, plus `localpath`), as the NLLB-CLIP names are: the
 registry's 204 names and 12 loader keys are pinned by tests.  `s2_inference._load_model`, `validate_model_properties` and `get_encoder`
@@ -29,7 +34,7 @@ import torch
 from marqo_amd.s2_inference.enums import Modality
 from marqo_amd.s2_inference.errors import InvalidModelPropertiesError, ModelLoadError
 
-SERVED_MODALITIES = (Modality.VIDEO, Modality.IMAGE, Modality.TEXT)
+SERVED_MODALITIES = (Modality.VIDEO, Modality.AUDIO, Modality.IMAGE, Modality.TEXT)
 
 
 class MultimodalModelProperties:
@@ -73,13 +78,26 @@ class MultimodalModel:
         raise ValueError(f"Unsupported loader: {self.properties.loader}")
 
     def _load_languagebind_model(self):
+        """A name with an audio part is served when `<localpath>/LanguageBind_Audio_FT` is a checkpoint directory, and that directory is looked
+        for FIRST.  Without it the name is refused with InvalidModelPropertiesError, where a missing video or image directory is a
+        ModelLoadError: the audio names were refused as invalid properties before this engine had an audio tower, and every caller who has no
+        audio checkpoint keeps seeing exactly that — the properties name a part that `localpath` does not hold — while the names that were
+        always served keep their load error."""
+        import os
+        from marqo_amd.engine import checkpoint
         from marqo_amd.engine import languagebind as LB
         if self.model_name not in LB.MODEL_PARTS:
             raise ValueError(f"Unsupported LanguageBind model: {self.model_name}")
         parts = LB.MODEL_PARTS[self.model_name]
         if "audio" in parts:
-            raise InvalidModelPropertiesError(f"{self.model_name}: its audio part {parts['audio']} is not supported by this engine (no audio tower); "
-                                              f"the names served are {[n for n, p in LB.MODEL_PARTS.items() if 'audio' not in p]}")
+            root = self.model_properties.get("localpath")
+            d = os.path.join(str(root), parts["audio"]) if root else None
+            if d is None or not os.path.isfile(os.path.join(d, "config.json")) or checkpoint._first_existing(d, checkpoint.HF_WEIGHT_FILES) is None:
+                raise InvalidModelPropertiesError(
+                    f"{self.model_name}: its audio part {parts['audio']} needs the checkpoint directory "
+                    f"{d if d else '<localpath>/' + parts['audio']} (config.json + {' | '.join(checkpoint.HF_WEIGHT_FILES)}), which was not found"
+                    f"{'' if root else ' (model_properties has no `localpath`)'}; the names without an audio part are "
+                    f"{[n for n, p in LB.MODEL_PARTS.items() if 'audio' not in p]}")
         precision = str(self.model_properties.get("enginePrecision", "bf16")).lower()
         if precision != "bf16":
             raise InvalidModelPropertiesError(f"{self.model_name}: LanguageBind towers run on bf16 operands only ('enginePrecision': {precision!r} is not supported)")
@@ -104,11 +122,11 @@ class MultimodalModel:
         return self.encoder.encode(content, modality, **kwargs)
 
 
-def video_pixel_values(content, modality: Modality = Modality.VIDEO) -> List[torch.Tensor]:
+def video_pixel_values(content, modality: Modality = Modality.VIDEO, ndim: int = 5, tail: Optional[tuple] = None) -> List[torch.Tensor]:
     """What VIDEO content may be -> the list of `pixel_values` tensors to encode, each [b, 3, T, S, S], in order:
     a list of dicts with a `pixel_values` tensor (what the reference's caller hands over, multimodal_model_load.py:285-287; every item, not only
     the first), one such dict, or such a tensor itself.  Anything else — URLs included: nothing here decodes media — raises ValueError with the
-    reference's message (:291)."""
+    reference's message (:291).  AUDIO content is the same with ndim = 4 and `tail` the shape behind the batch axis."""
     bad = lambda: ValueError(f"Unsupported {modality.value} content type: {type(content)}, content: {content}")
     if isinstance(content, torch.Tensor):
         items = [content]
@@ -122,7 +140,7 @@ def video_pixel_values(content, modality: Modality = Modality.VIDEO) -> List[tor
     for it in items:
         if isinstance(it, dict) and isinstance(it.get("pixel_values"), torch.Tensor):
             it = it["pixel_values"]
-        if not isinstance(it, torch.Tensor) or it.ndim != 5:
+        if not isinstance(it, torch.Tensor) or it.ndim != ndim or (tail is not None and tuple(it.shape[1:]) != tuple(tail)):
             raise bad()
         out.append(it)
     return out
@@ -130,16 +148,24 @@ def video_pixel_values(content, modality: Modality = Modality.VIDEO) -> List[tor
 
 class LanguageBindEncoder:
     """multimodal_model_load.py:204-311 on the engine's towers.  encode(content, modality, normalize) -> np.ndarray fp32 [n, D]:
-    with normalize every row is unit; without, a video or image row is the unit vector times exp(logit_scale) of its part and a text row is the
-    unit vector (languagebind/__init__.py:59-63)."""
+    with normalize every row is unit; without, a video, audio or image row is the unit vector times exp(logit_scale) of its part and a text row
+    is the unit vector (languagebind/__init__.py:59-63)."""
 
     def __init__(self, model: MultimodalModel):
         self.model = model
         self._local = threading.local()
+        self._audio_pre = None
 
     def preprocessor(self, modality):
-        """The reference returns its video / audio / image processor objects here; media decoding is out of this engine's scope: None"""
-        return None
+        """The reference returns its video / audio / image processor objects here.  AUDIO on a model with an audio part: the engine's
+        AudioPreprocessor (waveforms at the checkpoint's rate -> `pixel_values` on the GPU; it decodes nothing).  Everything else: None, media
+        decoding is out of this engine's scope"""
+        lb = self.model.model
+        if modality not in (Modality.AUDIO, Modality.AUDIO.value) or getattr(lb, "audio", None) is None:
+            return None
+        if self._audio_pre is None:
+            self._audio_pre = lb.audio_preprocessor()
+        return self._audio_pre
 
     def _image_pre(self):
         p = getattr(self._local, "pre", None)
@@ -181,6 +207,10 @@ class LanguageBindEncoder:
             out = self._encode_images(content, bool(normalize), image_download_headers)
         elif modality == Modality.VIDEO:
             out = torch.cat([lb.encode_video(px, bool(normalize)) for px in video_pixel_values(content, modality)], dim=0)
+        elif modality == Modality.AUDIO and getattr(lb, "audio", None) is not None:
+            a = lb.audio.arch
+            spectrograms = video_pixel_values(content, modality, ndim=4, tail=(3, a.num_mel_bins, a.target_length))
+            out = torch.cat([lb.encode_audio(px, bool(normalize)) for px in spectrograms], dim=0)
         else:
             raise ValueError(f"Unsupported {modality.value} content type: {type(content)}, content: {content}")
         return out.cpu().numpy()

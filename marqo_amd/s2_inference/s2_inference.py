@@ -128,8 +128,8 @@ def infer_modality(content, media_download_headers: Optional[dict] = None, timeo
     """multimodal_model_load.py:148-203, the function the reference's search and add_documents paths import FROM this module
     (tensor_search.py:74, add_docs.py:24-25).  A string that is not a URL is text; a URL is classified by its extension (image / video /
     audio lists of the reference), else by the first 10 KB of what it serves; bytes by their signature; anything else is text.  Video and
-    Video is served by the LanguageBind names (s2_inference/multimodal_model_load.py: preprocessed `pixel_values`, nothing here decodes media);
-    the callers answer it with UnsupportedModalityError for every other model family, and audio for all of them."""
+    audio are served by the LanguageBind names (s2_inference/multimodal_model_load.py: preprocessed `pixel_values`, and 16 kHz waveforms through
+    the audio preprocessor; nothing here decodes media); the callers answer them with UnsupportedModalityError for every other model family."""
     if isinstance(content, str):
         if not validate_url(content):
             return Modality.TEXT
@@ -362,7 +362,8 @@ def load_multimodal_model_and_get_preprocessors(model_name: str, model_propertie
                                                 model_auth=None, normalize_embeddings: bool = get_default_normalization()
                                                 ) -> Tuple[Any, Dict[str, Optional[Any]]]:
     """s2_inference.py:193-235: loads (or renews) the model and returns its per-modality preprocessors; `image` is the model's
-    `.preprocess` (PIL -> Tensor[3, S, S]) for clip / open_clip types, else None."""
+    `.preprocess` (PIL -> Tensor[3, S, S]) for clip / open_clip types, else None; `audio` is the AudioPreprocessor of a LanguageBind model with
+    an audio part (waveforms -> `pixel_values`), else None."""
     if not device:
         raise InternalError(message="vectorise (internal function) cannot be called without setting device!")
     model_cache_key = _create_model_cache_key(model_name, device, model_properties)
@@ -370,7 +371,7 @@ def load_multimodal_model_and_get_preprocessors(model_name: str, model_propertie
     model = _available_models[model_cache_key][AvailableModelsKey.model]
     preprocessors = {
         "image": getattr(model, "preprocess", None) if is_preprocess_image_model(model_properties) else None,
-        "video": None, "audio": None, "text": None,
+        "video": None, "audio": model.preprocessor(Modality.AUDIO) if isinstance(model, _multimodal.MultimodalModel) else None, "text": None,
     }
     return model, preprocessors
 
