@@ -1132,6 +1132,34 @@ int mq_mel_fusion(const float* d_mel, int64_t m, int32_t bins, int64_t start0, i
                   int32_t L, void* stream);
 int mq_patchify_rect(const float* d_in, void* d_out, int64_t n, int32_t H, int32_t Wd, int32_t P, int32_t Kp, void* stream);
 
+/* ---- LanguageBind front ends for media as a decoder hands it over: raw video frames and any-rate audio (csrc/video.hip, csrc/audio.hip;
+ * engine/video.py, engine/audio.py) -------------------------------------------------------------------------------------------------------------
+ * s2_inference/languagebind/video/processing_video.py:20-93 in the reference: np.linspace frame pick, x / 255, NormalizeVideo, pytorchvideo's
+ * ShortSideScale, torchvision's CenterCropVideo, a horizontal flip; audio/processing_audio.py:47-49: torchaudio.functional.resample at its defaults.
+ * Additions to ABI 14: nothing above changes.  Both entry points judge their arguments before any launch (MQ_ERR_INVALID, the message names the entry
+ * point and the bad value), run on `stream` and allocate nothing.  Nothing here decodes a file.
+ *
+ *   mq_video_preprocess: d_frames uint8 [T_in, H, W, 3] (decoded frames, RGB last) -> d_out fp32 [3, T, S, S], one clip of the `b c t h w` tensor
+ *                        mq_patchify_clip reads.  Output frame t is source frame d_pick[t] (int32 [T] on the device; a value outside [0, T_in) is
+ *                        clamped into it).  out[c, t, y, x] is pixel (top + y, left + x') of that frame scaled to new_h x new_w, x' = x, or S - 1 - x
+ *                        with flip == 1: the bilinear taps of torch.nn.functional.interpolate(size = (new_h, new_w), mode = "bilinear",
+ *                        align_corners = False), no antialiasing — source coordinate (dst + 0.5) (in / out) - 0.5 clamped at 0, upper neighbour
+ *                        clamped at in - 1 —, each tap first (u8 / 255 - h_mean[c]) / h_std[c] with both divisions IEEE, blended along x, then
+ *                        along y.  Coordinates are fp64, taps and blend fp32; with new_h == H and new_w == W the output is the normalised input bit
+ *                        for bit.  h_mean, h_std: HOST float[3], std > 0.  The integers new_h, new_w, top, left are the caller's
+ *                        (engine/video.py states the reference's rules).  Served: 1 <= H, W <= 16384, 1 <= T_in < 2^31, 1 <= T <= 4096,
+ *                        1 <= S <= 4096, S <= new_h, new_w <= 16384, 0 <= top <= new_h - S, 0 <= left <= new_w - S.
+ *   mq_resample:         d_wave fp32 [channels, len] -> d_out fp32 [channels, ceil(n len / o)], every channel on its own.  o = orig / gcd,
+ *                        n = new / gcd (coprime, o != n).  d_taps fp64 [n, K = 2 width + o] on the device, 8-byte aligned: the polyphase table of
+ *                        the windowed-sinc filter (engine/audio.py builds it in fp64).  With x_pad = `width` zeros, the channel, zeros:
+ *                        out[f n + p] = sum_k taps[p][k] x_pad[f o + k], summed in fp64 in ascending k, stored as fp32.  Served: K <= 12288,
+ *                        n K <= MQ_RESAMPLE_MAX_TAPS, 1 <= channels <= 65535, 1 <= len < 2^36. */
+#define MQ_RESAMPLE_MAX_TAPS (1 << 21)
+int mq_video_preprocess(const uint8_t* d_frames, int64_t T_in, int32_t H, int32_t W, const int32_t* d_pick, int32_t T, int32_t S, int32_t new_h,
+                        int32_t new_w, int32_t top, int32_t left, const float* h_mean, const float* h_std, int32_t flip, float* d_out, void* stream);
+int mq_resample(const float* d_wave, int64_t channels, int64_t len, const double* d_taps, int32_t o, int32_t n, int32_t width, float* d_out,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 14
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -41,6 +41,7 @@ MQ_COMBINE_RAW, MQ_COMBINE_NORMALIZE, MQ_COMBINE_NORMALIZE_IF_NONZERO = 0, 1, 2
 MQ_IMG_RGB, MQ_IMG_NEAREST, MQ_IMG_RGBA = 0, 1, 2
 MQ_PROF_FAMILIES = 6
 MQ_FBANK_WS_BYTES = 2048      # mq_fbank's device scratch
+MQ_RESAMPLE_MAX_TAPS = 1 << 21  # mq_resample: entries of the polyphase tap table
 PROF_FAMILY_NAMES = ("gemm", "layernorm", "attention", "embed", "pool_head", "preprocess")
 
 
@@ -328,6 +329,10 @@ _SIGNATURES = {
     "mq_fbank": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
     "mq_mel_fusion": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, _P, C.c_int32, _P]),
     "mq_patchify_rect": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    # LanguageBind front ends for raw frames and any-rate audio (csrc/video.hip, csrc/audio.hip; engine/video.py, engine/audio.py)
+    "mq_video_preprocess": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _P, _P]),
+    "mq_resample": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
     "mq_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -14,6 +14,12 @@
 //                    the caller's workspace, summed in a fixed order by every frame's workgroup.
 //   * mel_fusion:    the [3, bins, L] picture from the rows: row (start[c] + t) mod m, transposed through an LDS tile, normalised.
 //   * patchify_rect: mq_patchify's fp32 kernel over an H x Wd picture.
+//   * resample:      torchaudio.functional.resample at its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) as a polyphase
+//                    filter: with o = orig / gcd and n = new / gcd, output f n + p is the dot product of row p of the host's tap table
+//                    [n, K = 2 width + o] with the K samples of the zero-padded waveform from f o on.  A block stages the window of RS_OUT_PER_BLOCK
+//                    or so outputs (whole output frames of n phases) in LDS; a thread then owns one phase of one frame.  ARITHMETIC as the fbank:
+//                    fp32 in and out, the taps and the sum fp64 (the table is the host's fp64 one, never rounded): what is left is the rounding
+//                    of the stored value.
 #include "common.h"
 #include <float.h>
 
@@ -23,6 +29,9 @@ constexpr int FB_SHIFT = 160;      // 10 ms
 constexpr int FB_FFT = 512;        // round_to_power_of_two
 constexpr int FB_MAX_BINS = 128;
 constexpr int FB_MAX_PARTS = MQ_FBANK_WS_BYTES / 8;     // fp64 partial sums of the waveform in the workspace
+constexpr int RS_OUT_PER_BLOCK = 512;                  // outputs a block aims at (whole frames of n phases)
+constexpr int RS_MAX_WINDOW = 12288;                    // floats of LDS a block's window may take (48 KB)
+constexpr int64_t RS_MAX_TAPS = MQ_RESAMPLE_MAX_TAPS;   // entries of the tap table
 constexpr float FB_LOG_EPS = -15.9423847f;              // log(FLT_EPSILON) = -23 ln 2, rounded to nearest
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -46,6 +55,32 @@ __global__ __launch_bounds__(256) void wave_partial_sums_kernel(const float* __r
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) acc += (double)wave[i];
     acc = block_sum_f64(acc, sh4);
     if (threadIdx.x == 0) parts[blockIdx.x] = acc;
+}
+
+// x_pad[j] = x[j - width], zero outside [0, len): block b owns output frames [b fpb, (b + 1) fpb), their window is x_pad[b fpb o, ... + (fpb - 1) o + K)
+__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ wave, int64_t len, const double* __restrict__ taps, int o, int n, int width,
+                                                       int K, int fpb, int64_t out_len, float* __restrict__ out) {
+    extern __shared__ float rs_win[];
+    const float* x = wave + (int64_t)blockIdx.y * len;
+    float* y = out + (int64_t)blockIdx.y * out_len;
+    const int64_t f0 = (int64_t)blockIdx.x * fpb;
+    const int64_t first = f0 * o - width;              // the waveform index of window slot 0
+    const int span = (fpb - 1) * o + K;
+    for (int i = threadIdx.x; i < span; i += 256) {
+        const int64_t j = first + i;
+        rs_win[i] = j >= 0 && j < len ? x[j] : 0.f;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < fpb * n; i += 256) {
+        const int fl = i / n, p = i - fl * n;
+        const int64_t oi = (f0 + fl) * n + p;
+        if (oi >= out_len) continue;
+        const double* tp = taps + (int64_t)p * K;
+        const float* w = rs_win + fl * o;
+        double acc = 0.0;
+        for (int k = 0; k < K; ++k) acc = fma(tp[k], (double)w[k], acc);
+        y[oi] = (float)acc;
+    }
 }
 
 __global__ __launch_bounds__(256) void fbank_kernel(const float* __restrict__ wave, const double* __restrict__ parts, int nparts, int64_t n_mean,
@@ -226,5 +261,44 @@ extern "C" int mq_patchify_rect(const float* d_in, void* d_out, int64_t n, int32
     const unsigned grid = (unsigned)(cdiv64(total, 256) < 16384 ? cdiv64(total, 256) : 16384);
     hipLaunchKernelGGL(patchify_rect_kernel, dim3(grid), dim3(256), 0, s, d_in, (bf16_t*)d_out, total, H, Wd, P, Gh, Gw, Kp);
     MQ_CHECK_LAUNCH("mq_patchify_rect");
+    return MQ_OK;
+}
+
+static int64_t rs_gcd(int64_t a, int64_t b) {
+    while (b) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+extern "C" int mq_resample(const float* d_wave, int64_t channels, int64_t len, const double* d_taps, int32_t o, int32_t n, int32_t width, float* d_out,
+                           void* stream) {
+    MQ_CHECK_ARG(o >= 1 && n >= 1 && width >= 1 && rs_gcd(o, n) == 1, "mq_resample: o=%d, n=%d, width=%d: the reduced rate pair (coprime, positive) and a positive width",
+                 o, n, width);
+    MQ_CHECK_ARG(o != n, "mq_resample: o == n == %d: nothing to resample", o);
+    const int64_t K = 2ll * width + o;
+    MQ_CHECK_ARG(K <= RS_MAX_WINDOW && (int64_t)n * K <= RS_MAX_TAPS,
+                 "mq_resample: o=%d, n=%d, width=%d: a table of n (2 width + o) = %lld taps (at most %lld) with rows of %lld (at most %d) is not served: "
+                 "the two rates share too small a divisor", o, n, width, (long long)((int64_t)n * K), (long long)RS_MAX_TAPS, (long long)K, RS_MAX_WINDOW);
+    MQ_CHECK_ARG(channels >= 1 && channels <= 65535 && len >= 1 && len < (1ll << 36), "mq_resample: channels=%lld, len=%lld: 1 to 65535 channels of 1 to 2^36 - 1 samples",
+                 (long long)channels, (long long)len);
+    MQ_CHECK_ARG(d_wave && d_taps && d_out, "mq_resample: null pointer");
+    MQ_CHECK_ARG(((uintptr_t)d_taps & 7) == 0, "mq_resample: the tap table must be 8-byte aligned");
+    const int64_t out_len = ((int64_t)n * len + o - 1) / o;
+    const int64_t frames = cdiv64(out_len, n);
+    int64_t fpb = cdiv64(RS_OUT_PER_BLOCK, n);
+    const int64_t fit = (RS_MAX_WINDOW - K) / o + 1;           // frames whose window fits the LDS budget
+    fpb = fpb < fit ? fpb : fit;
+    fpb = fpb < frames ? fpb : frames;
+    const int64_t blocks = cdiv64(frames, fpb);
+    MQ_CHECK_ARG(blocks < (1ll << 31), "mq_resample: len=%lld gives %lld blocks (below 2^31)", (long long)len, (long long)blocks);
+    const hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(5, s);
+    const size_t lds = (size_t)((fpb - 1) * o + K) * sizeof(float);
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks, (unsigned)channels), dim3(256), lds, s, d_wave, len, d_taps, o, n, width, (int)K, (int)fpb,
+                       out_len, d_out);
+    MQ_CHECK_LAUNCH("mq_resample");
     return MQ_OK;
 }

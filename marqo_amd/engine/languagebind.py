@@ -25,7 +25,9 @@ weights load), so nothing is interpolated here:
     mq_patchify_rect (fp32 [b, 3, bins, L] -> im2col rows in (py, px) order) -> mq_gemm_bf16 -> mq_vit_assemble -> mq_encoder_forward (all blocks)
     -> mq_cls_rows -> mq_layernorm (post_layernorm) -> mq_gemm_bf16 (visual_projection) -> mq_l2_normalize
 
-The picture comes from engine/audio.py (Kaldi fbank and the three-crop fusion on the GPU) or from the caller's own preprocessing.
+The picture comes from engine/audio.py (an opt-in resampler, Kaldi fbank and the three-crop fusion on the GPU) or from the caller's own
+preprocessing; a clip's `pixel_values` come from engine/video.py (decoded uint8 frames: frame pick, normalisation, short-side scale, centre crop on
+the GPU) or from the caller's.
 
 The image part (`LanguageBind_Image`, no temporal attention) is a plain CLIP ViT under Hugging Face names and runs on `towers.VitTower`; the
 text tower is `towers.ClipTextTower` on 77 positions, packed up to the EOT as everywhere in this engine.
@@ -309,13 +311,24 @@ class LanguageBindModel:
         with request_stream(self.audio.device, device_output=True):
             return self._scaled(self.audio.encode_spectrograms(pixel_values, normalize=True), "audio", normalize)
 
-    def audio_preprocessor(self):
-        """engine/audio.py's front end for this model's audio part (waveforms -> `pixel_values`), None without one"""
+    def audio_preprocessor(self, resample: bool = False):
+        """engine/audio.py's front end for this model's audio part (waveforms -> `pixel_values`), None without one.  `resample`: a (waveform, rate)
+        pair at another rate than the checkpoint's is resampled on the GPU where it is refused otherwise"""
         if self.audio is None:
             return None
         from marqo_amd.engine.audio import AudioPreprocessor
         a = self.audio.arch
-        return AudioPreprocessor(str(self.audio.device), a.num_mel_bins, a.target_length, a.audio_sample_rate, a.audio_mean, a.audio_std)
+        return AudioPreprocessor(str(self.audio.device), a.num_mel_bins, a.target_length, a.audio_sample_rate, a.audio_mean, a.audio_std,
+                                 resample=bool(resample))
+
+    def video_preprocessor(self):
+        """engine/video.py's front end for this model's video part (decoded uint8 frames -> `pixel_values`), None without one.  The side and the
+        frame count are the checkpoint's `image_size` and `num_frames` (the reference hard-codes 224; the released checkpoints are 224)"""
+        if self.video is None:
+            return None
+        from marqo_amd.engine.video import VideoPreprocessor
+        a = self.video.arch
+        return VideoPreprocessor(str(self.video.device), a.image_size, a.num_frames)
 
     def encode_image_u8(self, u8: Tensor, normalize: bool = True) -> Tensor:
         """uint8 [n, S, S, 3] on the device (resized and cropped) -> fp32 [n, D] on the device"""

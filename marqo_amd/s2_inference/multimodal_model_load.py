@@ -5,12 +5,15 @@ What is served: all six names of the reference's part table (`LanguageBind/Video
 `LanguageBind/Audio_FT`, `LanguageBind/Audio_FT_Image`) on the HIP towers of engine/languagebind.py, modalities VIDEO, AUDIO, IMAGE and TEXT, bf16.
 AUDIO content is the `pixel_values` [b, 3, num_mel_bins, target_length] of the reference's audio processor; `preprocessor(Modality.AUDIO)` of a
 model with an audio part is engine/audio.py's AudioPreprocessor, which makes them on the GPU from 16 kHz waveforms (Kaldi fbank, the three-crop
-fusion).  What is not:
-  * decoding media: no video / audio decoder is a dependency of this engine, and there is no resampler: a waveform at another rate than the
-    checkpoint's is refused.  VIDEO content is what the reference's caller hands over after ITS preprocessing: `pixel_values` [b, 3, T, S, S];
+fusion) — and, with `"resampleAudio": true` in model_properties, from (waveform, rate) pairs at any rate its polyphase resampler serves.  VIDEO
+content is `pixel_values` [b, 3, T, S, S], or the decoded frames themselves: a uint8 [T_in, H, W, 3] tensor or ndarray, a list of them, or
+`{"frames": ...}` dicts, which engine/video.py's VideoPreprocessor (`preprocessor(Modality.VIDEO)` of a model with a video part) turns into
+`pixel_values` on the GPU.  What is not:
+  * decoding media: no video / audio decoder is a dependency of this engine; paths, URLs and bytes are refused.  Without `resampleAudio` a
+    waveform at another rate than the checkpoint's is refused;
   * the reference's randomness: its video processor applies a RANDOM horizontal flip, and its audio processor draws the three crop starts of a
-    clip longer than target_length at RANDOM.  AudioPreprocessor takes the middle of each third instead and accepts explicit `starts`
-    (engine/audio.py);
+    clip longer than target_length at RANDOM.  VideoPreprocessor never flips unless told to (`flip`); AudioPreprocessor takes the middle of each
+    third and accepts explicit `starts` (engine/video.py, engine/audio.py);
   * fp8 ('enginePrecision': 'fp8' is refused like the ConvNeXt towers: bf16 only);
   * downloads: `localpath` in model_properties names a directory with one sub-directory per part (LanguageBind_Video_V1.5_FT,
     LanguageBind_Audio_FT, LanguageBind_Image), each a Hugging Face checkpoint directory (config.json, model.safetensors | pytorch_model.bin,
@@ -71,6 +74,10 @@ class MultimodalModel:
         self.model = None
         self.encoder = None
         self.clip_type: Optional[Dict[str, str]] = None
+        resample = self.model_properties.get("resampleAudio", False)
+        if not isinstance(resample, bool):
+            raise InvalidModelPropertiesError(f"model_properties 'resampleAudio' must be true or false, received {resample!r}")
+        self.resample_audio = resample      # AudioPreprocessor resamples a waveform at another rate than the checkpoint's (off: it refuses it)
 
     def _load_multimodal_model(self):
         if self.properties.loader == "languagebind":
@@ -122,6 +129,20 @@ class MultimodalModel:
         return self.encoder.encode(content, modality, **kwargs)
 
 
+def raw_video_clips(content) -> Optional[list]:
+    """VIDEO content that is decoded frames -> the list of clips for engine/video.py's VideoPreprocessor, None for anything else (which is then
+    judged as `pixel_values`, with the messages it always had): one uint8 [T_in, H, W, 3] tensor / ndarray, one {"frames": such an array} dict, or a
+    non-empty list of these"""
+    is_u8 = lambda x: (isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and x.ndim == 4) or \
+        (isinstance(x, np.ndarray) and x.dtype == np.uint8 and x.ndim == 4)
+    is_clip = lambda x: is_u8(x) or (isinstance(x, dict) and set(x) == {"frames"} and is_u8(x["frames"]))
+    if is_clip(content):
+        return [content]
+    if isinstance(content, (list, tuple)) and len(content) > 0 and all(is_clip(x) for x in content):
+        return list(content)
+    return None
+
+
 def video_pixel_values(content, modality: Modality = Modality.VIDEO, ndim: int = 5, tail: Optional[tuple] = None) -> List[torch.Tensor]:
     """What VIDEO content may be -> the list of `pixel_values` tensors to encode, each [b, 3, T, S, S], in order:
     a list of dicts with a `pixel_values` tensor (what the reference's caller hands over, multimodal_model_load.py:285-287; every item, not only
@@ -155,16 +176,22 @@ class LanguageBindEncoder:
         self.model = model
         self._local = threading.local()
         self._audio_pre = None
+        self._video_pre = None
 
     def preprocessor(self, modality):
         """The reference returns its video / audio / image processor objects here.  AUDIO on a model with an audio part: the engine's
-        AudioPreprocessor (waveforms at the checkpoint's rate -> `pixel_values` on the GPU; it decodes nothing).  Everything else: None, media
-        decoding is out of this engine's scope"""
+        AudioPreprocessor (waveforms -> `pixel_values` on the GPU; with `resampleAudio` in model_properties at any served rate, else at the
+        checkpoint's).  VIDEO on a model with a video part: the engine's VideoPreprocessor (decoded uint8 frames -> `pixel_values` on the GPU).
+        Neither decodes anything.  Everything else: None"""
         lb = self.model.model
+        if modality in (Modality.VIDEO, Modality.VIDEO.value) and getattr(lb, "video", None) is not None:
+            if self._video_pre is None:
+                self._video_pre = lb.video_preprocessor()
+            return self._video_pre
         if modality not in (Modality.AUDIO, Modality.AUDIO.value) or getattr(lb, "audio", None) is None:
             return None
         if self._audio_pre is None:
-            self._audio_pre = lb.audio_preprocessor()
+            self._audio_pre = lb.audio_preprocessor(resample=True) if self.model.resample_audio else lb.audio_preprocessor()
         return self._audio_pre
 
     def _image_pre(self):
@@ -206,7 +233,11 @@ class LanguageBindEncoder:
         elif modality == Modality.IMAGE:
             out = self._encode_images(content, bool(normalize), image_download_headers)
         elif modality == Modality.VIDEO:
-            out = torch.cat([lb.encode_video(px, bool(normalize)) for px in video_pixel_values(content, modality)], dim=0)
+            clips = raw_video_clips(content) if getattr(lb, "video", None) is not None else None
+            if clips is not None:        # decoded frames: the GPU front end makes their pixel_values
+                out = lb.encode_video(self.preprocessor(Modality.VIDEO)(clips)["pixel_values"], bool(normalize))
+            else:
+                out = torch.cat([lb.encode_video(px, bool(normalize)) for px in video_pixel_values(content, modality)], dim=0)
         elif modality == Modality.AUDIO and getattr(lb, "audio", None) is not None:
             a = lb.audio.arch
             spectrograms = video_pixel_values(content, modality, ndim=4, tail=(3, a.num_mel_bins, a.target_length))
