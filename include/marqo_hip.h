@@ -47,7 +47,7 @@ extern "C" {
 #define MQ_ERR_WORKSPACE (-3) /* caller's workspace too small */
 #define MQ_ERR_UNSUPPORTED (-4) /* ABI 11: the device is not the one this library is built for (mq_check_device) */
 
-#define MQ_ABI_VERSION 14
+#define MQ_ABI_VERSION 15
 
 /* ---- activation / mask / pooling selectors ---------------------------------------- */
 #define MQ_ACT_NONE 0
@@ -944,27 +944,43 @@ int mq_queue_destroy(mq_queue* q);
 
 
 /* Run-time selection of a kernel variant (benchmark A/B and parity tests of every variant in one process).  TEST / BENCH ONLY: the
- * knobs are relaxed atomics (csrc/common.h, mq_knob) that the launch code of every request thread reads — a new value takes effect from
- * the next launch that reads it, so set them while no request is in flight if one call must run under one setting; the loaders never
- * touch them.
- * keys: "gemm_mt" (0 = auto, else GEMM tile height in 32-row units), "gemm_cgroup" (column tiles per L2 group, 0 = row-major walk),
- * "gemm_nh" (0 = the default tile plan, 1 = the (32 MT) x 128 tiles only, 3 = the 8-wave 256 x 256 tile on every row wherever N >= 256,
- * 4 = the eager row-split plan), "gemm_tail" (1 = the big tile's in-kernel split-K tail for a ragged last row of tiles),
- * "gemm_wd" (csrc/gemm_wd.hip, the W-operand-from-global main loop: 0 = off, 2 / 3 = on with that many LDS stages of A, 6 / 7 = the same
- * with both k-halves' W loads issued together), "rs_finalize" (1 = mq_gemm_bf16_rsf finalises the row statistics inside the GEMM's launch),
- * "gemm_addr_limit_mb" (bytes / 2^20 one launch may address per operand, 0 = the 4 GiB of a 32-bit buffer offset: taller matrices go in
- * row chunks), "row_select" (0 = the towers run their last block on every row instead of the pooled rows only), "ln_fold" (0 = LayerNorm
- * kernels, 1 = folded into the QKV GEMM, 2 = and into fc1; needs the folded weights), "subln_fold" (ABI 12: 0 = the EVA02 sub-LayerNorms run as
- * LayerNorm passes instead of inside the out-projection / fc2 GEMMs; MQ_SUBLN_FOLD), "residual_bf16", "small_m" / "small_m_grouped"
- * (row limits of the skinny GEMM kernels), "ln_prefetch", "xcd_band", "attn_waves" (0 = auto, 4 / 8 wave64s per attention workgroup),
- * "attn_proj" (ABI 13: fewest fixed-length sequences from which a ViT-B/32-shaped block runs mq_attention_proj instead of attention + out-projection +
- * finalise, 0 = never; default 128, MQ_ATTN_PROJ), "panel_gemm" (ABI 13: fewest fixed-length sequences from which the folded QKV / fc1 GEMMs of a 768-wide
- * tower run as mq_panel_gemm_ln; default 0 = never, MQ_PANEL_GEMM), "pool_strided" (0 = the ViT class-token rows of the pooled last block and the head
- * go through an index vector, two gathers and a scatter instead of being read and updated where they lie; default 1, MQ_POOL_STRIDED), "assemble_stats"
- * (0 = a row-statistics pass over x behind the ViT token assembly instead of the (mean, rstd) the assembly leaves itself; default 1, MQ_ASSEMBLE_STATS).
- * Initial values come from the environment (MQ_GEMM_MT, MQ_GEMM_CGROUP, MQ_GEMM_NH, MQ_GEMM_TAIL, MQ_GEMM_WD, MQ_GEMM_RS_FIN, MQ_ROW_SELECT,
- * MQ_LN_FOLD, ...). */
+ * knobs are relaxed atomics (csrc/knobs.h; one table row each in csrc/knobs.hip) that the launch code of every request thread reads — a new
+ * value takes effect from the next launch that reads it, so set them while no request is in flight if one call must run under one setting;
+ * the loaders never touch them.  key (environment variable the initial value comes from, built-in default): values
+ *   "gemm_mt" (MQ_GEMM_MT, 0): 0 = auto, else GEMM tile height in 32-row units (the bf16 and the fp8 tiles)
+ *   "gemm_cgroup" (MQ_GEMM_CGROUP, 8): column tiles per L2 group, 0 = row-major walk
+ *   "gemm_nh" (MQ_GEMM_NH, 0): 0 = the default tile plan, 1 = the (32 MT) x 128 tiles only, 3 = the 8-wave 256 x 256 tile on every row wherever
+ *       N >= 256, 4 = the eager row-split plan.  Setting it also sets the fp8 GEMM's big-tile switch (no key of its own; MQ_GEMM_FP8_NH, 0:
+ *       0 = plan, 1 = never, 3 = always) to the same value, 4 as 0
+ *   "gemm_tail" (MQ_GEMM_TAIL, 0): 1 = the big tile's in-kernel split-K tail for a ragged last row of tiles
+ *   "gemm_wd" (MQ_GEMM_WD, 0): csrc/gemm_wd.hip, the W-operand-from-global main loop: 0 = off, 2 / 3 = on with that many LDS stages of A,
+ *       6 / 7 = the same with both k-halves' W loads issued together
+ *   "rs_finalize" (MQ_GEMM_RS_FIN, 0): 1 = mq_gemm_bf16_rsf finalises the row statistics inside the GEMM's launch
+ *   "row_select" (MQ_ROW_SELECT, 1): 0 = the towers run their last block on every row instead of the pooled rows only
+ *   "ln_fold" (MQ_LN_FOLD, 2): 0 = LayerNorm kernels, 1 = folded into the QKV GEMM, 2 = and into fc1; needs the folded weights
+ *   "subln_fold" (MQ_SUBLN_FOLD, 1; ABI 12): 0 = the EVA02 sub-LayerNorms run as LayerNorm passes instead of inside the out-projection / fc2 GEMMs
+ *   "attn_proj" (MQ_ATTN_PROJ, 128; ABI 13): fewest fixed-length sequences from which a ViT-B/32-shaped block runs mq_attention_proj instead of
+ *       attention + out-projection + finalise, 0 = never
+ *   "panel_gemm" (MQ_PANEL_GEMM, 0; ABI 13): fewest fixed-length sequences from which the folded QKV / fc1 GEMMs of a 768-wide tower run as
+ *       mq_panel_gemm_ln, 0 = never
+ *   "residual_bf16" (MQ_RESIDUAL_BF16, 0): 1 = pre-LN bf16 towers without a policy of their own keep the residual stream in bf16
+ *   "pool_strided" (MQ_POOL_STRIDED, 1): 0 = the ViT class-token rows of the pooled last block and the head go through an index vector, two
+ *       gathers and a scatter instead of being read and updated where they lie
+ *   "assemble_stats" (MQ_ASSEMBLE_STATS, 1): 0 = a row-statistics pass over x behind the ViT token assembly instead of the (mean, rstd) the
+ *       assembly leaves itself
+ *   "small_m" (MQ_SMALL_M, 80), "small_m_grouped" (MQ_SMALL_M_GROUPED, 320): row limits of the skinny GEMM kernels, 0 = never
+ *   "ln_prefetch" (MQ_LN_PREFETCH, 1): 0 = the towers' LayerNorms do not prefetch the weights of the GEMMs behind them
+ *   "ln_rows" (MQ_LN_ROWS, 2): 1 = one row per wave in the generic LayerNorm at any row count, 2 = two from 8192 rows
+ *   "ln_bf16_wide" (MQ_LN_BF16_WIDE, 1): 0 = bf16 rows take the generic LayerNorm, 1 = the 16-byte form above small_m rows, 4 = that form with
+ *       four rows per wave from 16384 rows
+ *   "xcd_band" (MQ_XCD_BAND, 1): 0 = the row-wise kernels do not follow the GEMMs' XCD banding
+ *   "attn_waves" (no variable, 0): 0 = auto, 4 / 8 wave64s per attention workgroup
+ *   "gemm_addr_limit_mb" (no variable, 0): bytes / 2^20 one launch may address per operand, 0 = the 4 GiB of a 32-bit buffer offset: taller
+ *       matrices go in row chunks
+ * An unknown key is MQ_ERR_INVALID ("unknown key"). */
 int mq_tune(const char* key, int value);
+/* ABI 15: the current value of a knob (what mq_tune stored, or the value at load); "gemm_addr_limit_mb" reads 0 at the 4 GiB default */
+int mq_tune_get(const char* key, int* value);
 
 /* ---- per-kernel timing (bench.py roofline) ------------------------------------------- */
 /* When enabled, every launch of a kernel family is bracketed by hipEvents on its stream.

@@ -21,6 +21,7 @@
 // tokens are simply not rows.  MASK_CAUSAL implements the CLIP text tower's mask.
 #include <type_traits>
 #include "common.h"
+#include "knobs.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -313,7 +314,6 @@ __global__ __launch_bounds__(NW * 64) MQ_ATTN_OCC void attention_kernel(
 
 }  // namespace
 
-mq_knob mq_attention_waves{0};  // mq_tune("attn_waves", 0 = auto / 4 / 8 / 5 = five waves for 65..80-token sequences, else auto): A/B knob
 
 static int attention_impl(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq,
                           int32_t fixed_len, int32_t max_len, int32_t W, int32_t heads, int32_t mask,

@@ -20,13 +20,12 @@
 //            the partial-sum path's own order (per 64-column slot, lane chains handed between wave pairs through LDS), so the statistics carry its bits too.
 // The price: 64-row MFMA tiles for 50 tokens (78 % useful) and the whole of Wo (1.2 MB) through every CU's vector-memory path once per image.
 #include "common.h"
+#include "knobs.h"
 #include "gemm_loop.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-extern mq_knob mq_xcd_band;
-extern mq_knob mq_ln_prefetch;   // rowops.hip
 int mq_device_ok();   // runtime.hip
 
 namespace {

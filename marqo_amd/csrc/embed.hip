@@ -5,6 +5,7 @@
 //   * embed_tokens: token (+position, +type) embedding gather (+ LayerNorm for BERT).
 //   * pool: masked mean / CLS pooling (+ L2) over packed sequences.
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -440,7 +441,6 @@ extern "C" int mq_vit_assemble(const float* d_patch_out, const float* cls, const
 // mq_vit_assemble on the bf16 stream with ln_pre, leaving (mean, rstd) of every stored row in d_stats (fp32 [n * T][2]; the row statistics a folded
 // LayerNorm reads: mq_row_stats would compute the same bits from d_x).  W % 8 == 0.
 bool mq_vit_assemble_stats_ok(int32_t W) { return W % 8 == 0 && W >= 8 && W <= 64 * 4 * MAXC; }
-extern mq_knob mq_ln_prefetch;   // rowops.hip
 int mq_vit_assemble_stats(const float* d_patch_out, const float* cls, const float* pos, const float* g, const float* b, void* d_x, float* d_stats, int64_t n,
                           int32_t T, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s) {
     MQ_CHECK_ARG(mq_vit_assemble_stats_ok(W) && g && b && d_stats, "vit_assemble_stats: W=%d unsupported / null pointer", W);

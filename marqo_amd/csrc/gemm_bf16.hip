@@ -31,28 +31,14 @@
 // +1.9 % CLIP text embeddings/s.
 #include <map>
 #include <mutex>
-#include <string>
 #include <type_traits>
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm_loop.h"
 #include "gemm_sched.h"
 
-extern mq_knob mq_tower_row_select;   // towers.hip
-extern mq_knob mq_tower_ln_fold;      // towers.hip
-extern mq_knob mq_tower_subln_fold;
-extern mq_knob mq_tower_attn_proj;
-extern mq_knob mq_tower_panel_gemm;
-extern mq_knob mq_attention_waves;    // attention.hip
-extern mq_knob mq_tower_residual_bf16;  // towers.hip
-extern mq_knob mq_tower_pool_strided, mq_tower_assemble_stats;
-extern mq_knob mq_gemm_small_max_rows;  // gemm_small.hip
 bool mq_gemm_small_ok(int64_t M, int64_t N, int64_t K, bool ln);
 bool mq_gemm_small_grouped_ok(int64_t M, int64_t N, int64_t K);
-extern mq_knob mq_gemm_small_group_rows;
-extern mq_knob mq_ln_prefetch;        // rowops.hip
-extern mq_knob mq_ln_rows_per_wave;
-extern mq_knob mq_ln_bf16_wide;
 int mq_gemm_small(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, const float* d_bias, const void* d_residual, void* d_out,
                   int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, hipStream_t s);
 // gemm_wd.hip: the W-direct main loop on the same tile plan (-1: combination not instantiated, the caller launches its own kernel)
@@ -445,10 +431,6 @@ __attribute__((used)) void* mq_gemm_probe() { return (void*)gemm_nt_kernel<MQ_GE
 }  // namespace
 #else
 }  // namespace
-GemmTune g_tune;   // gemm_sched.h
-// operands are addressed through 32-bit buffer offsets: bytes below 4 GiB per launch and operand; a taller A goes in row chunks.
-// mq_tune("gemm_addr_limit_mb", v) lowers it so that the chunking can be tested at small sizes (0 = back to 4 GiB).
-std::atomic<uint64_t> mq_gemm_addr_limit{0xffffffffull};
 namespace {
 
 // ---- workspace of the big tile's in-kernel tail (GemmSk): partial-sum slots + flags, one block per HIP stream (launches on a stream are ordered, so
@@ -811,47 +793,5 @@ extern "C" int mq_gemm_bf16_rsf(const void* d_A, int64_t lda, const void* d_W, i
     }
     if (in_launch) return MQ_OK;
     return mq_row_stats_finalize_pf(d_partials, nslots, d_stats, M, (int32_t)N, eps, d_pf_a, pf_a_bytes, d_pf_b, pf_b_bytes, s);
-}
-
-// Run-time knobs (A/B benchmarking and the parity tests of every code path in one process).  TEST / BENCH ONLY (the loaders never touch them):
-// atomics (common.h, mq_knob) that the launch code of every request thread reads — a change takes effect from the next launch that reads it,
-// so set them while no request is in flight if one call must run under one setting.
-// keys: "gemm_mt" (0 = auto, else tile height in 32-row units), "gemm_cgroup", "row_select", "ln_fold", "residual_bf16", "small_m", "small_m_grouped",
-// "ln_prefetch", "xcd_band", "attn_waves", "gemm_addr_limit_mb", "gemm_nh" (0 = default plan, 1 = (32*MT) x 128 tiles only, 3 = the big 256 x 256 tile on every row wherever N >= 256, 4 = the eager row-split plan),
-// "gemm_tail", "gemm_wd" (gemm_wd.hip: 0 = off, 2 / 3 / 6 / 7), "rs_finalize" (1 = the row statistics are finalised inside the residual GEMM's launch),
-// "subln_fold" (0 = the EVA02 sub-LayerNorms run as LayerNorm passes instead of inside the out-projection / fc2 GEMMs),
-// "attn_proj" (fewest fixed-length sequences from which a ViT-B/32-shaped block runs attention + out-projection + residual + statistics as ONE launch,
-// attn_proj.hip; 0 = never), "panel_gemm" (fewest fixed-length sequences from which the folded QKV / fc1 GEMMs of a 768-wide tower run one workgroup per
-// sequence, panel_gemm.hip; 0 = never), "ln_rows" (rowops.hip: 1 = one row per wave in the generic LayerNorm at any row count, 2 = two from 8192 rows),
-// "ln_bf16_wide" (0 = bf16 rows take the generic LayerNorm, 1 = the 16-byte form above small_m rows, 4 = that form with four rows per wave from 16384 rows),
-// "pool_strided" (0 = the ViT class-token rows go through an index vector, two gathers and a scatter instead of being used where they lie),
-// "assemble_stats" (0 = a row_stats pass over x behind the ViT token assembly instead of the statistics the assembly leaves itself).
-extern "C" int mq_tune(const char* key, int value) {
-    MQ_CHECK_ARG(key, "mq_tune: null key");
-    const std::string k(key);
-    if (k == "gemm_mt") g_tune.mt = value;   // (the bf16 and the fp8 tiles)
-    else if (k == "gemm_cgroup") g_tune.cgroup = value;
-    else if (k == "gemm_nh") { g_tune.nh = value; g_tune.fp8_big = value == 4 ? 0 : value; }
-    else if (k == "gemm_tail") g_tune.tail = value;
-    else if (k == "gemm_wd") g_tune.wd = value;
-    else if (k == "rs_finalize") g_tune.rs_fin = value;
-    else if (k == "row_select") mq_tower_row_select = value;
-    else if (k == "ln_fold") mq_tower_ln_fold = value;
-    else if (k == "subln_fold") mq_tower_subln_fold = value;
-    else if (k == "attn_proj") mq_tower_attn_proj = value;
-    else if (k == "panel_gemm") mq_tower_panel_gemm = value;
-    else if (k == "xcd_band") mq_xcd_band = value;
-    else if (k == "attn_waves") mq_attention_waves = value;
-    else if (k == "residual_bf16") mq_tower_residual_bf16 = value;
-    else if (k == "pool_strided") mq_tower_pool_strided = value;
-    else if (k == "assemble_stats") mq_tower_assemble_stats = value;
-    else if (k == "small_m") mq_gemm_small_max_rows = value;
-    else if (k == "small_m_grouped") mq_gemm_small_group_rows = value;
-    else if (k == "ln_prefetch") mq_ln_prefetch = value;
-    else if (k == "ln_rows") mq_ln_rows_per_wave = value;
-    else if (k == "ln_bf16_wide") mq_ln_bf16_wide = value;
-    else if (k == "gemm_addr_limit_mb") mq_gemm_addr_limit = value > 0 ? ((uint64_t)value << 20) - 1 : 0xffffffffull;
-    else { mq_set_error("mq_tune: unknown key %s", key); return MQ_ERR_INVALID; }
-    return MQ_OK;
 }
 #endif  // MQ_GEMM_PROBE

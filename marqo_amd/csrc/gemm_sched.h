@@ -1,27 +1,14 @@
 // Host-side schedule of the persistent tiled GEMMs (gemm_bf16.hip, gemm_fp8.hip; gemm_wd.hip launches on the geometry gemm_bf16.hip makes): the tuning
 // knobs, the resident slots, the tile-height cost model, the row chunks under the kernels' 32-bit buffer offsets and each launch's tile grid.
 #pragma once
-#include <stdlib.h>
 #include "common.h"
+#include "knobs.h"
 
-// tuning knobs: initialised from the environment (MQ_GEMM_MT / _CGROUP / _NH / _TAIL / _WD / _RS_FIN / _FP8_NH), overridable through mq_tune()
-// (gemm_bf16.hip).  mt and cgroup steer the bf16 and the fp8 tiles alike.
-struct GemmTune {
-    // tail: the big tile's in-kernel tail (GemmSk).  OFF by default: its rows carry a differently associated k-sum, so an embedding's bits would
-    // depend on whether its tokens sit in the last partial row tile of a batch — the towers promise the same bits wherever an item stands
-    // (tests/test_towers_gpu.py permutation equivariance; the coalescer and the ingest merging lean on it) — for +1.6 % / +3.9 % on the ViT-L/14 rows
-    // (profiles/r05p).  mq_tune("gemm_tail", 1) / MQ_GEMM_TAIL=1 turns it on; without it a ragged last row tile is a tile like any other.
-    // wd: the W-direct main loop (gemm_wd.hip) on the narrow tiles: 0 = off, 2 / 3 = on with that many LDS stages of A
-    // rs_fin: the residual GEMMs of the bf16 stream finalise the row statistics inside their own launch (mq_gemm_bf16_rsf; 0 = a row_stats_finalize_kernel
-    // launch behind them, the round 4-5 form)
-    // fp8_big: the fp8 GEMM's big tile (gemm_fp8.hip, plan_fp8_big): 0 = plan, 1 = never, 3 = always
-    mq_knob mt, cgroup, nh, tail, wd, rs_fin, fp8_big;
-    static int env(const char* k, int d) { const char* v = getenv(k); return v ? atoi(v) : d; }
-    GemmTune() : mt(env("MQ_GEMM_MT", 0)), cgroup(env("MQ_GEMM_CGROUP", 8)), nh(env("MQ_GEMM_NH", 0)), tail(env("MQ_GEMM_TAIL", 0)), wd(env("MQ_GEMM_WD", 0)),
-                 rs_fin(env("MQ_GEMM_RS_FIN", 0)), fp8_big(env("MQ_GEMM_FP8_NH", 0)) {}
-};
-extern GemmTune g_tune;                            // gemm_bf16.hip
-extern std::atomic<uint64_t> mq_gemm_addr_limit;   // gemm_bf16.hip: bytes one launch may address per operand (4 GiB - 1; tests lower it)
+// tuning knobs: g_tune and mq_gemm_addr_limit (knobs.h; keys, environment names, defaults and values in knobs.hip's table).
+// g_tune.tail: the big tile's in-kernel tail (GemmSk).  OFF by default: its rows carry a differently associated k-sum, so an embedding's bits would
+// depend on whether its tokens sit in the last partial row tile of a batch — the towers promise the same bits wherever an item stands
+// (tests/test_towers_gpu.py permutation equivariance; the coalescer and the ingest merging lean on it) — for +1.6 % / +3.9 % on the ViT-L/14 rows
+// (profiles/r05p).  mq_tune("gemm_tail", 1) / MQ_GEMM_TAIL=1 turns it on; without it a ragged last row tile is a tile like any other.
 
 // One launch's tile grid (the kernels' scheduling arguments)
 struct GemmGeom {

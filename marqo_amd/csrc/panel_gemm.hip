@@ -21,9 +21,9 @@
 // pass against 13 us there, and even with the epilogue switched off (53 us) the QKV GEMM only ties the tiled kernel.  mq_tune("panel_gemm", n) / MQ_PANEL_GEMM=n
 // turns it on from n sequences; the towers never take it by themselves.
 #include "common.h"
+#include "knobs.h"
 #include "gemm_loop.h"
 
-extern mq_knob mq_xcd_band;
 int mq_device_ok();   // runtime.hip
 
 namespace {

@@ -1,18 +1,15 @@
 // Row-wise HBM-bound kernels: LayerNorm (K2), L2-normalise (tail of K6/K8/K9), fp32->bf16 cast.
 // One wave64 per row, float4 (16 B/lane) accesses, two-pass statistics held in registers so the
 // row is read from HBM exactly once.
-#include <stdlib.h>
 #include "common.h"
+#include "knobs.h"
 
-mq_knob mq_ln_rows_per_wave{getenv("MQ_LN_ROWS") ? atoi(getenv("MQ_LN_ROWS")) : 2};  // mq_tune("ln_rows", 1 | 2) / MQ_LN_ROWS
-extern mq_knob mq_gemm_small_max_rows;   // gemm_small.hip
 int mq_layernorm_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16, float* d_out_f32,
                     int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 int mq_layernorm_rows_pf(const void* d_x, int x_bf16, const int32_t* d_row_idx, int64_t row_mul, const float* d_g, const float* d_b, void* d_out_bf16,
                          float* d_out_f32, int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
 int mq_layernorm_fp8_pf(const void* d_x, int x_bf16, const float* d_g, const float* d_b, void* d_out_fp8, float* d_row_scale, float* d_out_f32,
                         int64_t rows, int32_t W, float eps, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b, hipStream_t s);
-mq_knob mq_ln_bf16_wide{getenv("MQ_LN_BF16_WIDE") ? atoi(getenv("MQ_LN_BF16_WIDE")) : 1};   // mq_tune("ln_bf16_wide", 0 | 1 | 4) / MQ_LN_BF16_WIDE: 16-byte bf16-input LayerNorm (4: four rows per wave from 16384 rows)
 
 namespace {
 
@@ -398,9 +395,7 @@ extern "C" int mq_layernorm(const float* d_x, const int32_t* d_row_idx, const fl
     return mq_layernorm_ex(d_x, 0, d_row_idx, d_g, d_b, d_out_bf16, d_out_f32, rows, W, eps, stream);
 }
 
-// knob: the LayerNorms of the towers prefetch the weights of the GEMMs behind them (0 = off).  mq_tune("ln_prefetch", v) / MQ_LN_PREFETCH
-mq_knob mq_ln_prefetch{getenv("MQ_LN_PREFETCH") ? atoi(getenv("MQ_LN_PREFETCH")) : 1};
-
+// mq_ln_prefetch (knobs.h): the LayerNorms of the towers prefetch the weights of the GEMMs behind them
 static LnExtra ln_extra(int band, int64_t rows, const void* pf_a, size_t bytes_a, const void* pf_b, size_t bytes_b) {
     LnExtra ex{band, 0u, 0u, nullptr, nullptr, 32u, 1u};
     if (mq_ln_prefetch && rows >= 1024) {   // (a small call is latency-bound: nothing to hide the extra loads behind)

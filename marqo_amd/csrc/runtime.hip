@@ -1,4 +1,3 @@
-#include <stdlib.h>
 // Library-wide host plumbing: thread-local error text, ABI/arch info, per-family launch timing.
 #include <stdarg.h>
 #include <string.h>
@@ -18,7 +17,6 @@ void mq_set_error(const char* fmt, ...) {
 
 extern "C" const char* mq_last_error(void) { return g_err; }
 extern "C" int mq_abi_version(void) { return MQ_ABI_VERSION; }
-mq_knob mq_xcd_band{getenv("MQ_XCD_BAND") ? atoi(getenv("MQ_XCD_BAND")) : 1};   // row-wise kernels follow the GEMMs' XCD banding (common.h)
 extern "C" const char* mq_build_arch(void) { return "gfx950"; }
 
 // ---- the device this library was written for -------------------------------------------------------------------------------------------------

@@ -4,8 +4,8 @@
 //   BERT encoder + pooling   (transformers BertModel + hugging_face_model.py:172-214)
 // Residual stream is fp32 (what fp16-autocast keeps it as in the reference's cuda path:
 // open_clip_model.py:255-260), GEMM inputs bf16, accumulation / LN statistics / softmax fp32.
-#include <stdlib.h>
 #include "common.h"
+#include "knobs.h"
 
 // kernels in the sibling translation units
 int mq_cast_bf16(const float* d_x, void* d_out, int64_t n, hipStream_t s);
@@ -17,47 +17,35 @@ static_assert(sizeof(mq_encoder_cfg) == 112, "mq_encoder_cfg layout");
 static_assert(sizeof(mq_vit_cfg) == 168 && sizeof(mq_clip_text_cfg) == 128 && sizeof(mq_bert_cfg) == 136, "tower cfg layouts");
 static_assert(sizeof(mq_vit_weights) == 11 * 8 && sizeof(mq_map_head) == 11 * 8 && sizeof(mq_clip_text_weights) == 7 * 8, "tower weight layouts");
 
-// mq_tune("row_select", 0) runs the last block on every row (A/B and parity tests of the pooled-rows-only last block)
-mq_knob mq_tower_row_select{getenv("MQ_ROW_SELECT") ? atoi(getenv("MQ_ROW_SELECT")) : 1};
+// The towers' knobs (knobs.h; keys, environment names and defaults: the table in knobs.hip).
 // LayerNorm folding (gemm_epilogue.h, MQ_EPI_LN_APPLY): on the bf16 residual stream the QKV / fc1 GEMMs of a pre-LN block read the stream itself and
 // apply the LayerNorm in their epilogue ((mean, rstd) per row handed in) whenever the block carries the folded tensors (*_wf / *_bf / *_sf,
-// engine/towers.py) and the call is large enough for the tiled GEMM.  mq_tune("ln_fold", v) / MQ_LN_FOLD=v:
+// engine/towers.py) and the call is large enough for the tiled GEMM.  mq_tower_ln_fold:
 // 0 = LayerNorm kernels; 1 = folded, statistics from a read pass over the stream; 2 = folded, statistics from the residual GEMMs' partial sums
-mq_knob mq_tower_ln_fold{getenv("MQ_LN_FOLD") ? atoi(getenv("MQ_LN_FOLD")) : 2};
-// the EVA02 sub-LayerNorms (attn.norm in front of the out-projection, mlp.norm in front of fc2) folded into those GEMMs (round 6, ABI 12; block_eva):
-// mq_tune("subln_fold", 0) / MQ_SUBLN_FOLD=0 keeps them as LayerNorm passes over the attention output / the gated product
-mq_knob mq_tower_subln_fold{getenv("MQ_SUBLN_FOLD") ? atoi(getenv("MQ_SUBLN_FOLD")) : 1};
-// attention + out-projection + residual + statistics in one launch (attn_proj.hip) from this many fixed-length sequences up (0 = never).  One workgroup
+// mq_tower_attn_proj: attention + out-projection + residual + statistics in one launch (attn_proj.hip) from this many fixed-length sequences up (0 = never).  One workgroup
 // per image: below ~half the chip's 256 CUs the three launches it replaces win (measured, profiles/r06x_attn_proj_batch_ab.txt: +3.4 % at 256 images,
 // +2 % at 128, -1 % at 96, -4.5 % at 64)
-mq_knob mq_tower_attn_proj{getenv("MQ_ATTN_PROJ") ? atoi(getenv("MQ_ATTN_PROJ")) : 128};
 // (one workgroup per image: a second round of the 256 CUs has to be filled to 3/4 — 300 images would run 44 workgroups behind 256 — or the launches win)
 static bool attn_proj_fill_ok(int64_t nseq) {
     const int64_t rounds = (nseq + 255) / 256;
     return mq_tower_attn_proj > 0 && nseq >= mq_tower_attn_proj && (rounds == 1 || nseq * 4 >= rounds * 256 * 3);
 }
-// the folded QKV / fc1 GEMMs one workgroup per image (panel_gemm.hip) from this many fixed-length sequences up, when whole rounds of the 256 CUs are filled
+// mq_tower_panel_gemm: the folded QKV / fc1 GEMMs one workgroup per image (panel_gemm.hip) from this many fixed-length sequences up, when whole rounds of the 256 CUs are filled
 // to >= 3/4.  0 = never, the default: bit-identical and 17-30 % slower than the tiled kernel at these shapes (profiles/r06za_panel_gemm_ab.txt)
-mq_knob mq_tower_panel_gemm{getenv("MQ_PANEL_GEMM") ? atoi(getenv("MQ_PANEL_GEMM")) : 0};
 static bool panel_fill_ok(int64_t nseq) {
     const int64_t rounds = (nseq + 255) / 256;
     return mq_tower_panel_gemm > 0 && nseq >= mq_tower_panel_gemm && nseq * 4 >= rounds * 256 * 3;
 }
-// bf16 residual stream for the pre-LN bf16 towers (mq_tune("residual_bf16", 1) / MQ_RESIDUAL_BF16=1): x is kept in bf16 between
+// mq_tower_residual_bf16: bf16 residual stream for the pre-LN bf16 towers: x is kept in bf16 between
 // blocks.  The residual GEMMs of a K = 768 tower are memory-bound on their epilogue (out-proj: 15 GFLOP against 39 MB read + 39 MB
 // written of fp32 residual) and every LayerNorm re-reads the stream: bf16 halves those bytes.  Cost: one bf16 rounding per residual
 // add (measured 1 - cos 5e-5 .. 1.2e-4 against the fp32 oracle at full depth, well inside the 1e-3 tolerance; the reference's own GPU path
 // keeps its activations in fp16 under autocast, open_clip_model.py:255-260).  Post-LN (BERT) and fp8 towers keep the fp32 stream.
-mq_knob mq_tower_residual_bf16{getenv("MQ_RESIDUAL_BF16") ? atoi(getenv("MQ_RESIDUAL_BF16")) : 0};
-// pooled rows at a fixed pitch (the class token of every image: row i * T) are read and written WHERE THEY LIE: the skinny GEMMs of the pooled last block
+// mq_tower_pool_strided: pooled rows at a fixed pitch (the class token of every image: row i * T) are read and written WHERE THEY LIE: the skinny GEMMs of the pooled last block
 // and the head take a row pitch of T * W (gemm_small.hip reads A and the residual with ordinary loads), the LayerNorms a row multiplier — no index
-// vector (cls_rows_kernel), no gathers into a dense copy, no scatter back.  Same kernels on the same values: bit-identical.
-// mq_tune("pool_strided", 0) / MQ_POOL_STRIDED=0: the index vector and the three move_rows launches
-mq_knob mq_tower_pool_strided{getenv("MQ_POOL_STRIDED") ? atoi(getenv("MQ_POOL_STRIDED")) : 1};
-// the ViT front end leaves the first block's (mean, rstd) behind: vit_assemble_kernel holds whole token rows, so it also writes the statistics of the bf16
-// rows it stores (embed.hip, arithmetic and lane order of row_stats_bf16_kernel) and the first QKV GEMM needs no statistics pass.
-// mq_tune("assemble_stats", 0) / MQ_ASSEMBLE_STATS=0: the row_stats_bf16_kernel launch
-mq_knob mq_tower_assemble_stats{getenv("MQ_ASSEMBLE_STATS") ? atoi(getenv("MQ_ASSEMBLE_STATS")) : 1};
+// vector (cls_rows_kernel), no gathers into a dense copy, no scatter back (0: those three move_rows launches).  Same kernels on the same values: bit-identical.
+// mq_tower_assemble_stats: the ViT front end leaves the first block's (mean, rstd) behind: vit_assemble_kernel holds whole token rows, so it also writes the statistics of the bf16
+// rows it stores (embed.hip, arithmetic and lane order of row_stats_bf16_kernel) and the first QKV GEMM needs no statistics pass (0: the row_stats_bf16_kernel launch).
 extern "C" int mq_layernorm_ex(const void* d_x, int x_bf16, const int32_t* d_row_idx, const float* d_g, const float* d_b, void* d_out_bf16,
                                float* d_out_f32, int64_t rows, int32_t W, float eps, void* stream);
 // search path (rows <= 80): LayerNorm fused into the skinny GEMM's prologue (gemm_small.hip)

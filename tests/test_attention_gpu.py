@@ -20,6 +20,7 @@ import torch
 
 from marqo_amd import _lib as L
 from tests import attention_ref as R
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -112,15 +113,12 @@ def test_parity_within_the_rounding_budget(lib, hs, lens, heads, mask):
         if real is not None:
             assert (got.view(-1, heads, hs)[:, :, real:] == 0).all()       # exactly zero, not merely small
         # 4, 8 or (65..80 tokens, 64-wide) 5 waves per workgroup walk the same query blocks: identical bits
-        try:
-            for nw in (4, 8, 5):
-                L.check(lib.mq_tune(b"attn_waves", nw))
+        for nw in (4, 8, 5):
+            with tuned(attn_waves=nw):
                 g2 = Guarded(qkv.shape[0], W)
                 L.check(lib.mq_attention(qkv.data_ptr(), g2.ptr(), L.ptr(cu), nseq, fixed, mx, W, heads, mask, _s()))
                 torch.cuda.synchronize()
-                assert g2.guards_intact() and torch.equal(g2.out, got), (fam, nw)
-        finally:
-            L.check(lib.mq_tune(b"attn_waves", 0))
+            assert g2.guards_intact() and torch.equal(g2.out, got), (fam, nw)
 
 
 # ---- 2. MQ_MASK_CAUSAL_CLS ---------------------------------------------------------------------------------------------------------------
@@ -288,20 +286,17 @@ def test_xcd_banded_grids(lib, nseq, heads):
     `readout` rows shifted by the sequence index, random q / k per (sequence, head): a block that computes another (sequence, head) cannot pass"""
     lens = [50] * nseq
     qkv = R.make_qkv("readout", lens, heads, 64, seed=nseq, device="cuda")
-    try:
-        L.check(lib.mq_tune(b"xcd_band", 1))
+    with tuned(xcd_band=1):
         on = _attn(lib, qkv, lens, heads, 64, NONE)
         _assert_parity("xcd", "readout", on, qkv, lens, heads, 64, NONE)
-        L.check(lib.mq_tune(b"xcd_band", 0))
+        tune(xcd_band=0)
         off = _attn(lib, qkv, lens, heads, 64, NONE)
         assert torch.equal(on, off)
         # packed through cu_seqlens with one shorter sequence: the same map, other row offsets
         lens2 = lens[:-1] + [37]
-        L.check(lib.mq_tune(b"xcd_band", 1))
+        tune(xcd_band=1)
         on2 = _attn(lib, qkv[:sum(lens2)], lens2, heads, 64, CAUSAL)
         _assert_parity("xcd", "readout", on2, qkv[:sum(lens2)], lens2, heads, 64, CAUSAL)
-    finally:
-        L.check(lib.mq_tune(b"xcd_band", 1))
 
 
 # ---- 7. degenerate inputs and argument checks --------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from marqo_amd import _lib as L
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -110,20 +111,16 @@ def test_vit_b32_tower_with_and_without_the_fused_launch():
     """the tower (bf16 residual stream, folded LayerNorms) with the block's attention half as one launch vs as three: bit-identical embeddings, on the oracle"""
     from marqo_amd.engine import archs, towers
     from oracle import towers as O
-    lib = L.load()
     varch, _ = archs.resolve_open_clip("ViT-B-32")
     cfg = O.VitConfig(varch.image_size, varch.patch_size, varch.width, varch.layers, varch.heads, varch.mlp_dim, varch.out_dim)
     sd = O.synthetic_vit_state_dict(cfg, seed=0)
     u8 = O.synthetic_images_u8(72, varch.image_size, seed=2).to("cuda:0")
     tower = towers.VitTower(varch, sd, "cuda:0")
-    try:
-        L.check(lib.mq_tune(b"attn_proj", 0))
+    with tuned(attn_proj=0):
         three = tower.encode_u8(u8).cpu()
-        L.check(lib.mq_tune(b"attn_proj", 1))
+        tune(attn_proj=1)
         one = tower.encode_u8(u8).cpu()
         one_small = tower.encode_u8(u8[:5]).cpu()
-    finally:
-        L.check(lib.mq_tune(b"attn_proj", 128))
     assert torch.equal(one, three)          # rows AND statistics carry the three launches' bits: so do the embeddings
     ref = O.vit_forward(sd, cfg, O.preprocess_u8_exact_size(u8[:6].cpu()))
     for got in (one[:6], three[:6]):

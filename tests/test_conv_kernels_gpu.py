@@ -17,6 +17,7 @@ import torch
 from marqo_amd import _lib as L
 from tests import conv_ref as K
 from tests import rowops_ref as R
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -106,14 +107,11 @@ def test_conv3x3_both_tile_heights_and_store_widths(lib, i, mt):
     """conv3x3_kernel<FLAGS, 2> and <FLAGS, 4> (mq_tune gemm_mt) on every case of conv_ref.CONV_CASES: non-square maps, maps below one tile, a tile that
     spans five images, Cin of 8 / 16 / 24 (several taps per k-step), the wide store (ldy % 8 == 0 on a 16-byte line) and the narrow one"""
     c = K.CONV_CASES[i]
-    try:
-        L.check(lib.mq_tune(b"gemm_mt", mt))
+    with tuned(gemm_mt=mt):
         for fam in K.FAMILIES_MAP:
             x, wk, b, ref, bound = _conv_case(i, fam)
             y = _conv_call(lib, x, wk, b, c["Cout"], c["relu"], c["store"])
             _hold(f"conv3x3/mt{mt}", fam, y, ref, bound, c)
-    finally:
-        L.check(lib.mq_tune(b"gemm_mt", 0))
 
 
 def test_conv3x3_unforced_dispatch_runs_the_tile_heights_that_were_compared(lib):
@@ -126,11 +124,8 @@ def test_conv3x3_unforced_dispatch_runs_the_tile_heights_that_were_compared(lib)
         ref, bound = K.reference_conv3x3(x, wk, b, 1)
         xd, wd, bd = x.to(DEV), wk.to(torch.bfloat16).to(DEV), b.to(DEV)
         auto = _conv_call(lib, xd, wd, bd, 4, 1)
-        try:
-            L.check(lib.mq_tune(b"gemm_mt", forced))
+        with tuned(gemm_mt=forced):
             pinned = _conv_call(lib, xd, wd, bd, 4, 1)
-        finally:
-            L.check(lib.mq_tune(b"gemm_mt", 0))
         assert torch.equal(auto, pinned)
         _hold("conv3x3/auto", "loud_image", auto, ref, bound, (n, H, W))
 

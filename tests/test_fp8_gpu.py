@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from marqo_amd import _lib as L
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -82,8 +83,7 @@ def test_layernorm_fp8_from_the_bf16_stream():
 @pytest.mark.parametrize("mt", [0, 2, 4, 5, 6])
 def test_gemm_fp8_equals_product_of_dequantised_operands(mt):
     lib = L.load()
-    L.check(lib.mq_tune(b"gemm_mt", mt))
-    try:
+    with tuned(gemm_mt=mt):
         g = torch.Generator(device="cuda").manual_seed(2 + mt)
         for (M, N, K) in [(50, 64, 128), (257, 768, 256), (1000, 132, 384), (4097, 2304, 768), (12800, 768, 3072), (16, 4, 128),
                           (300, 176, 128), (300, 1160, 256), (20000, 1168, 128)]:
@@ -129,8 +129,6 @@ def test_gemm_fp8_equals_product_of_dequantised_operands(mt):
             assert abs(amax.item() - want.abs().max().item()) < 1e-3 * want.abs().max().item() + 1e-4
             deq = o.view(torch.float8_e4m3fn).float() * osc
             assert (deq - want).abs().max().item() <= (2 ** -4) * want.abs().max().item() + 1e-3
-    finally:
-        L.check(lib.mq_tune(b"gemm_mt", 0))
 
 
 def test_gemm_fp8_scheduling_knobs_are_bit_identical():
@@ -140,7 +138,7 @@ def test_gemm_fp8_scheduling_knobs_are_bit_identical():
     g = torch.Generator(device="cuda").manual_seed(99)
     knobs_off = dict(gemm_cgroup=0)
     knobs_on = dict(gemm_cgroup=8)
-    try:
+    with tuned(**knobs_off):
         for (M, N, K) in [(12800, 3072, 768), (12800, 2304, 768), (20000, 1168, 128), (300, 176, 256), (5000, 1552, 384)]:
             A8 = torch.randint(0, 256, (M, K), dtype=torch.uint8, device="cuda", generator=g) & 0xBF
             W8 = torch.randint(0, 256, (N, K), dtype=torch.uint8, device="cuda", generator=g) & 0xBF
@@ -150,8 +148,7 @@ def test_gemm_fp8_scheduling_knobs_are_bit_identical():
             osc = torch.tensor([0.05], device="cuda")
             outs = {}
             for name, knobs in (("off", knobs_off), ("on", knobs_on)):
-                for k, v in knobs.items():
-                    L.check(lib.mq_tune(k.encode(), v))
+                tune(**knobs)
                 res = []
                 for flags, dt in ((L.MQ_EPI_BIAS, torch.bfloat16), (L.MQ_EPI_BIAS | L.MQ_EPI_GELU | L.MQ_EPI_OUT_FP8, torch.uint8),
                                   (L.MQ_EPI_OUT_F32, torch.float32)):
@@ -163,9 +160,6 @@ def test_gemm_fp8_scheduling_knobs_are_bit_identical():
                 outs[name] = res
             for a, b in zip(outs["off"], outs["on"]):
                 assert torch.equal(a, b), (M, N, K, a.dtype)
-    finally:
-        for k, v in knobs_on.items():
-            L.check(lib.mq_tune(k.encode(), v))
 
 
 def test_gemm_fp8_taller_than_one_launch_can_address_goes_in_row_chunks():
@@ -196,8 +190,7 @@ def test_gemm_fp8_taller_than_one_launch_can_address_goes_in_row_chunks():
                 outs += [out, amax.clone()]
         return outs
     whole = run_all()
-    try:
-        L.check(lib.mq_tune(b"gemm_addr_limit_mb", 1))
+    with tuned(gemm_addr_limit_mb=1):
         chunked = run_all()
         # a weight above the limit cannot be chunked: refused, loudly
         big_w = torch.zeros(1200, K, dtype=torch.uint8, device="cuda")
@@ -205,8 +198,6 @@ def test_gemm_fp8_taller_than_one_launch_can_address_goes_in_row_chunks():
         rc = lib.mq_gemm_fp8(A8.data_ptr(), K, big_w.data_ptr(), K, sa.data_ptr(), 1, torch.ones(1200, device="cuda").data_ptr(), 0, 0, out.data_ptr(), 1200, 0, 0,
                              M, 1200, K, L.MQ_EPI_OUT_F32, _stream())
         assert rc != 0
-    finally:
-        L.check(lib.mq_tune(b"gemm_addr_limit_mb", 0))
     for a, b in zip(whole, chunked):
         assert torch.equal(a, b), a.dtype
 
@@ -488,11 +479,8 @@ def test_fp8_tower_on_the_bf16_residual_stream(tiled_gemm_only, monkeypatch):
             assert t8.residual_stream == "fp32" or t8.residual_stream_error <= t8.FP8_STREAM_SHARE * t8.FP8_BUDGET
         outs[mode] = out
         if mode == "bf16":
-            try:
-                L.check(L.load().mq_tune(b"row_select", 0))
+            with tuned(row_select=0):
                 full = t8.encode_u8(u8.cuda())
-            finally:
-                L.check(L.load().mq_tune(b"row_select", 1))
             assert torch.equal(full, out)
     assert not torch.equal(outs["fp32"], outs["bf16"])
 
@@ -522,14 +510,11 @@ def test_big_8_wave_tile_is_bit_identical_to_the_narrow_tiles(M, N, K):
         L.check(lib.mq_gemm_fp8(A8.data_ptr(), K, W8.data_ptr(), K, (sa_row if rowscale else sa_one).data_ptr(), rowscale, sw.data_ptr(), bias.data_ptr(),
                                 out.data_ptr() if res is not None else 0, out.data_ptr(), N, osc.data_ptr(), amax.data_ptr(), M, N, K, flags, _stream()))
         return out, amax
-    try:
-        L.check(lib.mq_tune(b"gemm_nh", 1))
+    with tuned(gemm_nh=1):
         narrow = [run(*f) for f in forms]
-        L.check(lib.mq_tune(b"gemm_nh", 3))
+        tune(gemm_nh=3)
         for f, (want, want_amax) in zip(forms, narrow):
             for _ in range(2):
                 got, amax = run(*f)
                 assert torch.equal(got.view(torch.uint8) if got.dtype == torch.uint8 else got, want), f[0]
                 assert torch.equal(amax, want_amax)
-    finally:
-        L.check(lib.mq_tune(b"gemm_nh", 0))

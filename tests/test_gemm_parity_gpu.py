@@ -25,11 +25,11 @@ import torch
 
 from marqo_amd import _lib as L
 from tests import gemm_ref as R
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
 B, G, Q, RS, F, LN, GLU, RELU = R.BIAS, R.GELU, R.QUICK, R.RES, R.F32, R.LN, R.GLU, R.RELU
-DEFAULTS = dict(gemm_mt=0, gemm_cgroup=8, gemm_nh=0, small_m=80, small_m_grouped=320)      # what the existing tests restore
 MARGIN = 1.25
 FILL = 7.0
 DEV = "cuda"
@@ -50,27 +50,16 @@ def _s():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _tune(**kw):
-    lib = L.load()
-    for k, v in kw.items():
-        L.check(lib.mq_tune(k.encode(), v))
-
-
-@contextlib.contextmanager
 def plan(**kw):
-    """the tiled family under the given knobs (the skinny kernels off); every knob back at its default afterwards"""
-    try:
-        _tune(**{**DEFAULTS, "small_m": 0, "small_m_grouped": 0, **kw})
-        yield
-    finally:
-        _tune(**DEFAULTS)
+    """the tiled family under the given knobs (the skinny kernels off); every knob back where it was afterwards"""
+    return tuned(small_m=0, small_m_grouped=0, **kw)
 
 
 def _probe_bits():
     """default-plan GEMMs whose bits depend on the kernel family that runs them: 40 rows (skinny), 200 (row groups), 400 (tiled).
     What this can see: small_m and small_m_grouped away from their defaults (the skinny kernels add the k-chunks in another order).  What it cannot:
     gemm_mt, gemm_nh and gemm_cgroup — every tiled plan gives the same bits by design (csrc/gemm_bf16.hip), so for those the guarantee is the
-    try / finally of plan(), which writes every key of DEFAULTS whatever happened inside."""
+    try / finally of tests/knobs.tuned under plan(), which puts every key it set back whatever happened inside."""
     lib = L.load()
     g = torch.Generator(device=DEV).manual_seed(99)
     outs = []

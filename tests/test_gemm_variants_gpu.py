@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from marqo_amd import _lib as L
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -16,14 +17,8 @@ def _tiled_family(tiled_gemm_only):
     yield
 
 
-DEFAULTS = dict(gemm_mt=0, gemm_cgroup=8, gemm_nh=0, gemm_tail=0)
 SHAPES = [(50, 64, 64), (257, 768, 128), (1000, 132, 192), (4097, 2304, 768), (12800, 768, 3072), (333, 3072, 64), (16, 4, 64),
           (20000, 1160, 64), (3000, 1288, 128)]
-
-
-def _tune(lib, **kw):
-    for k, v in kw.items():
-        L.check(lib.mq_tune(k.encode(), v), "mq_tune")
 
 
 def _gemm(lib, A, W, bias, res, flags, lda=None):
@@ -40,8 +35,7 @@ def _gemm(lib, A, W, bias, res, flags, lda=None):
 @pytest.mark.parametrize("mt", [0, 2, 4, 5, 6])
 def test_every_tile_height_matches_reference(mt, cgroup):
     lib = L.load()
-    try:
-        _tune(lib, gemm_mt=mt, gemm_cgroup=cgroup)
+    with tuned(gemm_mt=mt, gemm_cgroup=cgroup):
         g = torch.Generator(device="cuda").manual_seed(mt * 7 + cgroup)
         for (M, N, K) in SHAPES:
             A = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
@@ -61,29 +55,25 @@ def test_every_tile_height_matches_reference(mt, cgroup):
             out = _gemm(lib, A, W, bias, res16, L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL).float()
             want = ref + bias + res16.float()
             assert (out - want).abs().max().item() / (want.abs().max().item() + 1e-6) < 2e-2
-    finally:
-        _tune(lib, **DEFAULTS)
 
 
 def test_tile_height_and_order_are_bitwise_equal_and_stable():
     """same k-order of MFMAs per output element whatever the tile height and the tile walk -> bit-identical; 25 launches under load screen races"""
     lib = L.load()
     g = torch.Generator(device="cuda").manual_seed(5)
-    try:
+    with tuned(gemm_mt=4, gemm_cgroup=0):
         for (M, N, K) in [(12800, 768, 768), (4099, 384, 3072), (12800, 2304, 768), (700, 260, 64)]:
             A = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
             W = (torch.randn(N, K, device="cuda", generator=g) / K ** 0.5).to(torch.bfloat16)
             b = torch.randn(N, device="cuda", generator=g)
-            _tune(lib, gemm_mt=4, gemm_cgroup=0)
+            tune(gemm_mt=4, gemm_cgroup=0)
             base = _gemm(lib, A, W, b, None, L.MQ_EPI_BIAS | L.MQ_EPI_OUT_F32)
             for mt in (0, 2, 5, 6):
                 for cg in (0, 4, 8):
-                    _tune(lib, gemm_mt=mt, gemm_cgroup=cg)
+                    tune(gemm_mt=mt, gemm_cgroup=cg)
                     for _ in range(25 if (mt, cg) == (0, 8) else 2):
                         out = _gemm(lib, A, W, b, None, L.MQ_EPI_BIAS | L.MQ_EPI_OUT_F32)
                         assert torch.equal(out, base), (mt, cg, (M, N, K))
-    finally:
-        _tune(lib, **DEFAULTS)
 
 
 def test_rows_do_not_depend_on_their_call():
@@ -137,11 +127,8 @@ def test_row_chunks_under_a_lowered_address_limit_are_bit_identical():
     res = torch.randn(M, N, device="cuda", generator=g)
     forms = [(L.MQ_EPI_BIAS | L.MQ_EPI_GELU, None), (L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL | L.MQ_EPI_OUT_F32, res), (L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL, res.to(torch.bfloat16))]
     whole = [_gemm(lib, A, W, b, r, f) for f, r in forms]
-    try:
-        _tune(lib, gemm_addr_limit_mb=2)
+    with tuned(gemm_addr_limit_mb=2):
         chunked = [_gemm(lib, A, W, b, r, f) for f, r in forms]
-    finally:
-        _tune(lib, gemm_addr_limit_mb=0)
     for x, y in zip(whole, chunked):
         assert torch.equal(x, y)
 
@@ -156,7 +143,7 @@ def test_the_big_tile_is_bit_identical_to_the_narrow_one_except_its_tail(nh, tai
     after the store.  The tail is opt-in (gemm_tail = 1): by default a ragged last row tile is a tile like any other and EVERY row is bit-identical."""
     lib = L.load()
     g = torch.Generator(device="cuda").manual_seed(31)
-    try:
+    with tuned(gemm_nh=1, gemm_tail=0):
         for (M, N, K) in [(12800, 768, 768), (4099, 2304, 768), (16448, 1024, 4096), (700, 260, 64), (224, 256, 128), (5000, 132, 192), (9000, 3072, 1024),
                           (16448, 4096, 1024), (12800, 3072, 768), (32896, 1024, 4096)]:
             A = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
@@ -165,9 +152,9 @@ def test_the_big_tile_is_bit_identical_to_the_narrow_one_except_its_tail(nh, tai
             res = torch.randn(M, N, device="cuda", generator=g)
             forms = [(0, None), (L.MQ_EPI_OUT_F32, None), (L.MQ_EPI_BIAS | L.MQ_EPI_GELU, None), (L.MQ_EPI_BIAS | L.MQ_EPI_QUICKGELU, None),
                      (L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL | L.MQ_EPI_OUT_F32, res), (L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL, res.to(torch.bfloat16))]
-            _tune(lib, gemm_nh=1)
+            tune(gemm_nh=1)
             base = [_gemm(lib, A, W, b, r, f) for f, r in forms]
-            _tune(lib, gemm_nh=nh, gemm_tail=tail)
+            tune(gemm_nh=nh, gemm_tail=tail)
             full = (M // 256) * 256 if tail else M          # rows in front of the tail
             first = None
             for rep in range(20 if (M, N, K) in ((12800, 768, 768), (16448, 1024, 4096)) else 2):
@@ -182,8 +169,6 @@ def test_the_big_tile_is_bit_identical_to_the_narrow_one_except_its_tail(nh, tai
                     first = big
                 else:                        # the tail is deterministic: run to run the same bits
                     assert all(torch.equal(p, q) for p, q in zip(first, big)), (nh, (M, N, K), rep)
-    finally:
-        _tune(lib, **DEFAULTS)
 
 
 @pytest.mark.parametrize("M,F,K,ldc_mult", [(4099, 192, 128, 2), (12800, 2048, 768, 2), (300, 64, 64, 1), (1000, 2752, 1024, 2)])
@@ -204,9 +189,8 @@ def test_gated_epilogue_forms_the_swiglu_product(M, F, K, ldc_mult):
     ldc = ldc_mult * F
     GLU = 256
     outs = []
-    try:
-        for kw in (dict(), dict(gemm_mt=2), dict(gemm_mt=6), dict(gemm_nh=3)):
-            _tune(lib, **{**DEFAULTS, **kw})
+    for kw in (dict(), dict(gemm_mt=2), dict(gemm_mt=6), dict(gemm_nh=3)):
+        with tuned(**kw):
             out = torch.full((M, ldc), 7.0, device="cuda", dtype=torch.bfloat16)
             L.check(lib.mq_gemm_bf16(A.data_ptr(), K, W.data_ptr(), K, b.data_ptr(), 0, out.data_ptr(), ldc, M, 2 * F, K, L.MQ_EPI_BIAS | GLU, torch.cuda.current_stream().cuda_stream))
             err = (out[:, :F].float() - want).abs().max().item() / (want.abs().max().item() + 1e-6)
@@ -214,6 +198,4 @@ def test_gated_epilogue_forms_the_swiglu_product(M, F, K, ldc_mult):
             if ldc > F:
                 assert bool((out[:, F:] == 7.0).all())          # nothing is written behind the product
             outs.append(out)
-        assert all(torch.equal(o, outs[0]) for o in outs[1:])   # tile shapes change scheduling only
-    finally:
-        _tune(lib, **DEFAULTS)
+    assert all(torch.equal(o, outs[0]) for o in outs[1:])   # tile shapes change scheduling only

@@ -8,6 +8,7 @@ import torch
 
 from tests import attention_ref as AR
 from tests import rowops_ref as RR
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -176,16 +177,13 @@ def test_attention(lib, lens, heads, causal, hd):
     worst = AR.worst_coords(out, o64, a64, lens, heads, hd)
     assert worst["ratio"] <= 1.25, worst
     # 4 or 8 waves per workgroup (auto: 8 once K + V exceed 80 KiB of LDS) walk the same query blocks: identical bits
-    try:
-        for nw in (4, 8, 5):
-            L.check(lib.mq_tune(b"attn_waves", nw))
+    for nw in (4, 8, 5):
+        with tuned(attn_waves=nw):
             out2 = torch.empty_like(out)
             L.check(lib.mq_attention(qkv.data_ptr(), out2.data_ptr(), 0 if fixed else cu.data_ptr(), len(lens), fixed, max(lens), W, heads,
                                      L.MQ_MASK_CAUSAL if causal else L.MQ_MASK_NONE, _stream()))
             torch.cuda.synchronize()
-            assert torch.equal(out2, out), nw
-    finally:
-        L.check(lib.mq_tune(b"attn_waves", 0))
+        assert torch.equal(out2, out), nw
 
 
 @pytest.mark.parametrize("lens,heads", [([50] * 4, 12), ([5, 77, 1, 33, 64, 65], 12), ([200, 129, 17], 2), ([512], 3)])

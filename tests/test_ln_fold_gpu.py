@@ -10,16 +10,13 @@ import torch
 
 from marqo_amd import _lib as L
 from oracle import towers as O
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tune(key, value):
-    L.check(L.load().mq_tune(key.encode(), value))
 
 
 def _ln_gemm(lib, xb, wf, bf, colsum, out, flags, eps):
@@ -155,12 +152,7 @@ def test_in_launch_finalise_gives_the_finalise_kernels_bits(M, N, K, plan, tiled
     nslots = (N + 63) // 64
     eps = 1e-5
     pf = torch.randn(3 << 20, device="cuda")       # 12 MB "weights of the next GEMM"
-    try:
-        _tune("rs_finalize", 1)
-        if plan == "row_split":
-            _tune("gemm_nh", 4)
-        elif plan == "mt2":
-            _tune("gemm_mt", 2)
+    with tuned(rs_finalize=1, **{"default": {}, "row_split": dict(gemm_nh=4), "mt2": dict(gemm_mt=2)}[plan]):
         x = x0.clone()
         part = torch.full((nslots, M, 2), float("nan"), device="cuda")      # slot-major (ABI 12)
         L.check(lib.mq_gemm_bf16_rs(a.data_ptr(), K, W.data_ptr(), K, b.data_ptr(), x.data_ptr(), x.data_ptr(), N, M, N, K, flags, part.data_ptr(), _stream()))
@@ -178,14 +170,12 @@ def test_in_launch_finalise_gives_the_finalise_kernels_bits(M, N, K, plan, tiled
             assert int(ctr.abs().sum()) == 0
         # the two-launch form behind the same entry point (mq_tune rs_finalize = 0; no counters)
         for kw in (dict(rs=0, ctr=ctr.data_ptr()), dict(rs=1, ctr=0)):
-            _tune("rs_finalize", kw["rs"])
+            tune(rs_finalize=kw["rs"])
             x3 = x0.clone()
             got = torch.full((M, 2), float("nan"), device="cuda")
             L.check(lib.mq_gemm_bf16_rsf(a.data_ptr(), K, W.data_ptr(), K, b.data_ptr(), x3.data_ptr(), x3.data_ptr(), N, M, N, K, flags, part.data_ptr(), got.data_ptr(), eps,
                                          kw["ctr"], 0, 0, 0, 0, _stream()))
             assert torch.equal(got.view(torch.int32), want.view(torch.int32)) and torch.equal(x3.view(torch.int16), x.view(torch.int16))
-    finally:
-        _tune("gemm_nh", 0); _tune("gemm_mt", 0); _tune("rs_finalize", 0)
 
 
 def test_towers_give_the_same_bits_with_the_finalise_in_or_behind_the_launch():
@@ -199,14 +189,11 @@ def test_towers_give_the_same_bits_with_the_finalise_in_or_behind_the_launch():
     sdt = O.synthetic_clip_text_state_dict(O.ClipTextConfig(49408, 77, 512, 3, 8, 2048, 512), seed=19)
     ids = O.synthetic_clip_ids(200, seed=20)
     tt = towers.ClipTextTower(tarch, sdt, "cuda")
-    try:
-        _tune("rs_finalize", 1)
+    with tuned(rs_finalize=1):
         a1, t1 = tower.encode_u8(u8), tt.encode_ids(ids)
         assert torch.equal(a1, tower.encode_u8(u8)) and torch.equal(t1, tt.encode_ids(ids))
-        _tune("rs_finalize", 0)
+        tune(rs_finalize=0)
         a0, t0 = tower.encode_u8(u8), tt.encode_ids(ids)
-    finally:
-        _tune("rs_finalize", 0)
     assert torch.equal(a1, a0) and torch.equal(t1, t0)
 
 
@@ -222,16 +209,13 @@ def test_folded_towers_match_unfolded_and_oracle():
     assert tower._blocks[0].qkv_wf and tower._blocks[0].fc1_sf  # folded tensors are present
     tower.set_residual_stream(1) if hasattr(tower, "set_residual_stream") else None
     cos = lambda a, b: float((1 - torch.nn.functional.cosine_similarity(a.double().cpu(), b.double().cpu(), dim=-1)).max())
-    try:
-        _tune("ln_fold", 2)                          # statistics from the residual GEMMs' partial sums (default)
+    with tuned(ln_fold=2):                           # statistics from the residual GEMMs' partial sums (default)
         folded = tower.encode_u8(u8.cuda())
         assert torch.equal(folded, tower.encode_u8(u8.cuda()))  # deterministic
-        _tune("ln_fold", 1)                          # statistics from a read pass over the stream
+        tune(ln_fold=1)                          # statistics from a read pass over the stream
         folded_rs = tower.encode_u8(u8.cuda())
-        _tune("ln_fold", 0)
+        tune(ln_fold=0)
         plain = tower.encode_u8(u8.cuda())
-    finally:
-        _tune("ln_fold", 2)
     assert cos(folded, folded_rs) < 2e-5 and cos(folded_rs, ref) < 3e-4
     e_f, e_p, e_fp = cos(folded, ref), cos(plain, ref), cos(folded, plain)
     print(f"ViT-B/32 x4 layers ({tower.residual_stream=}): 1-cos vs oracle folded {e_f:.2e} plain {e_p:.2e}; folded vs plain {e_fp:.2e}")
@@ -243,14 +227,11 @@ def test_folded_towers_match_unfolded_and_oracle():
     ids = O.synthetic_clip_ids(40, seed=10)
     tt = towers.ClipTextTower(tarch, sdt, "cuda")
     reft = O.clip_text_forward(sdt, tcfg, ids)
-    try:
-        _tune("ln_fold", 2)
+    with tuned(ln_fold=2):
         f = tt.encode_ids(ids)
-        _tune("ln_fold", 1)
+        tune(ln_fold=1)
         f1 = tt.encode_ids(ids)
-        _tune("ln_fold", 0)
+        tune(ln_fold=0)
         p = tt.encode_ids(ids)
-    finally:
-        _tune("ln_fold", 2)
     assert cos(f, f1) < 2e-5
     assert cos(f, reft) < 3e-4 and cos(p, reft) < 3e-4 and cos(f, p) < 1e-4

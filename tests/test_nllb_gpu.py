@@ -19,6 +19,7 @@ import torch
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs
 from tests import nllb_util as U
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -263,14 +264,11 @@ def test_relu_encoder_with_the_panel_gemm_knob_on():
     x0 = torch.randn(nseq * T, W, device=DEV, generator=torch.Generator(device=DEV).manual_seed(4)).to(torch.bfloat16)
     ws = torch.empty(lib.mq_encoder_workspace_bytes(C.byref(cfg), nseq * T, nseq) + 256, dtype=torch.uint8, device=DEV)
     outs = []
-    try:
-        for knob in (0, 1):
-            L.check(lib.mq_tune(b"panel_gemm", knob))
+    for knob in (0, 1):
+        with tuned(panel_gemm=knob):
             x = x0.clone()
             L.check(lib.mq_encoder_forward(C.byref(cfg), blocks, x.data_ptr(), nseq * T, None, nseq, T, T, ws.data_ptr(), ws.numel(), _stream()), "mq_encoder_forward")
             torch.cuda.synchronize()
             outs.append(x)
-    finally:
-        L.check(lib.mq_tune(b"panel_gemm", 0))
     assert torch.isfinite(outs[1].float()).all() and not torch.equal(outs[1], x0)
     assert torch.equal(outs[0], outs[1])

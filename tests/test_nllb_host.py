@@ -270,7 +270,7 @@ def test_synthetic_state_dict_has_the_checkpoint_keys():
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_encoder_argument_checks_for_relu():
     lib = L.load()
-    assert L.MQ_ACT_RELU == 4 and lib.mq_abi_version() == 14
+    assert L.MQ_ACT_RELU == 4 and lib.mq_abi_version() == 15
     ok = L.EncoderCfg(width=1024, layers=12, heads=16, mlp_dim=4096, act=L.MQ_ACT_RELU, post_ln=0, mask=0, ln_eps=1e-5, precision=L.MQ_PREC_BF16)
     assert lib.mq_encoder_forward(C.byref(ok), None, None, 0, None, 0, 0, 0, None, 0, None) == -1
     assert b"null pointer" in lib.mq_last_error()                    # the configuration itself passed: the next check speaks

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from marqo_amd import _lib as L
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -79,18 +80,14 @@ def test_vit_b32_tower_under_the_knob_has_the_same_bits():
     without the knob (the default: the form is slower, profiles/r06za) run the tiled kernels: the same embeddings, bit for bit"""
     from marqo_amd.engine import archs, towers
     from oracle import towers as O
-    lib = L.load()
     varch, _ = archs.resolve_open_clip("ViT-B-32")
     cfg = O.VitConfig(varch.image_size, varch.patch_size, varch.width, varch.layers, varch.heads, varch.mlp_dim, varch.out_dim)
     sd = O.synthetic_vit_state_dict(cfg, seed=0)
     u8 = O.synthetic_images_u8(200, varch.image_size, seed=4).to("cuda:0")
     tower = towers.VitTower(varch, sd, "cuda:0")
     tiled = tower.encode_u8(u8).cpu()
-    try:
-        L.check(lib.mq_tune(b"panel_gemm", 192))
+    with tuned(panel_gemm=192):
         panel = tower.encode_u8(u8).cpu()
-    finally:
-        L.check(lib.mq_tune(b"panel_gemm", 0))
     assert torch.equal(panel, tiled)
     ref = O.vit_forward(sd, cfg, O.preprocess_u8_exact_size(u8[:4].cpu()))
     c = torch.nn.functional.cosine_similarity(panel[:4].double(), ref.double(), dim=-1)

@@ -11,13 +11,12 @@ Every comparison prints a `ROWOPS_RATIO` line and the module ends with one `ROWO
 |kernel - reference| / budget seen (run with -s).  The float32 model of the kernels sits at 0.48 (fp32 output), 1.00 (bf16 output: the half ulp itself),
 0.05 / 0.24 (mean / rstd), 0.43 / 0.40 (finalise) and 0.38 (L2) on the host.
 """
-import os
-
 import pytest
 import torch
 
 from marqo_amd import _lib as L
 from tests import rowops_ref as R
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -65,28 +64,6 @@ class Guarded:
         return bool((self.bits == self.sentinel).all())
 
 
-class tuned:
-    """with tuned(lib, ln_rows=1): ... ; the values the library started with come back whatever happens inside.  mq_tune has no getter: the
-    starting value of a knob is what its definition reads (rowops.hip, runtime.hip), the environment variable or the built-in default"""
-    DEFAULTS = {"ln_rows": int(os.environ.get("MQ_LN_ROWS", 2)), "ln_bf16_wide": int(os.environ.get("MQ_LN_BF16_WIDE", 1)),
-                "xcd_band": int(os.environ.get("MQ_XCD_BAND", 1))}
-
-    def __init__(self, lib, **kv):
-        self.lib, self.kv = lib, kv
-
-    def __enter__(self):
-        try:
-            for k, v in self.kv.items():
-                L.check(self.lib.mq_tune(k.encode(), v))
-        except BaseException:
-            self.__exit__()
-            raise
-
-    def __exit__(self, *exc):
-        for k in self.kv:
-            L.check(self.lib.mq_tune(k.encode(), self.DEFAULTS[k]))
-
-
 def _ln(lib, x, g, b, eps=EPS, idx=None, outs="both"):
     """-> (bf16 output or None, fp32 output or None), guards checked"""
     rows = x.shape[0] if idx is None else idx.numel()
@@ -127,7 +104,7 @@ def test_generic_fp32_rows(lib, W):
                 ob, of = _ln(lib, x, g, b, eps=1e-12)
                 _assert_ln("ln_generic_fp32", fam, x, g, b, ob, of, eps=1e-12)
             if rows == 8193 and fam in ("randn", "rowscale"):
-                with tuned(lib, ln_rows=1):                 # one row per wave at a row count that otherwise takes two
+                with tuned(ln_rows=1):                 # one row per wave at a row count that otherwise takes two
                     ob1, of1 = _ln(lib, x, g, b)
                 _assert_ln("ln_generic_fp32", fam, x, g, b, ob1, of1)
                 assert torch.equal(of1, of) and torch.equal(ob1, ob)      # same arithmetic per row in both forms
@@ -147,7 +124,7 @@ def test_generic_bf16_rows_up_to_small_m(lib, W):
 def test_generic_bf16_rows_above_small_m(lib, W, wide):
     """above 80 rows the generic kernel is reached by widths the 16-byte form does not take (W % 8 != 0, W > 1024) and by ln_bf16_wide = 0; from 8192
     rows and W <= 1024 it runs two rows per wave"""
-    with tuned(lib, ln_bf16_wide=wide):
+    with tuned(ln_bf16_wide=wide):
         for rows in (81, 8191, 8193):
             for fam in R.FAMILIES:
                 x, g, b = R.make_rows(fam, rows, W, seed=3, device="cuda", bf16=True)
@@ -167,7 +144,7 @@ def test_bf16_rows_eight_byte_aligned_take_the_generic_kernel(lib, rows):
     assert shifted.data_ptr() % 16 == 8
     ob, of = _ln(lib, shifted, g, b)
     _assert_ln("ln_generic_bf16", "rowscale", x, g, b, ob, of)
-    with tuned(lib, ln_bf16_wide=0):
+    with tuned(ln_bf16_wide=0):
         ob0, of0 = _ln(lib, x, g, b)
     assert torch.equal(ob, ob0) and torch.equal(of, of0)
 
@@ -181,7 +158,7 @@ def test_wide_bf16_rows(lib, W):
             ob, of = _ln(lib, x, g, b)
             _assert_ln("ln_wide", fam, x, g, b, ob, of)
             if rows >= 16385:
-                with tuned(lib, ln_bf16_wide=4):            # four rows per wave
+                with tuned(ln_bf16_wide=4):            # four rows per wave
                     ob4, of4 = _ln(lib, x, g, b)
                 _assert_ln("ln_wide_r4", fam, x, g, b, ob4, of4)
 
@@ -194,9 +171,9 @@ def test_the_wide_form_is_what_an_aligned_call_above_small_m_runs(lib, W):
     input 8 bytes off a 16-byte line must not give the bits of the aligned default call"""
     for rows, wide in ((81, 1), (8193, 1), (16399, 1), (16399, 4)):
         x, g, b = R.make_rows("rowscale", rows, W, seed=18, device="cuda", bf16=True)
-        with tuned(lib, ln_bf16_wide=wide):
+        with tuned(ln_bf16_wide=wide):
             _, of = _ln(lib, x, g, b, outs="f32")
-        with tuned(lib, ln_bf16_wide=0):
+        with tuned(ln_bf16_wide=0):
             _, of0 = _ln(lib, x, g, b, outs="f32")
         differing = int((of != of0).sum())
         print(f"ROWOPS_DISPATCH W={W} rows={rows} ln_bf16_wide={wide}: {differing} of {of.numel()} fp32 outputs differ from the generic kernel's")
@@ -243,7 +220,7 @@ def test_banded_grids_that_are_no_multiple_of_eight(lib, bf16, W, rows):
     x, g, b = R.make_rows("rowscale", rows, W, seed=8, device="cuda", bf16=bf16)
     ob, of = _ln(lib, x, g, b)
     _assert_ln("ln_banded", "rowscale", x, g, b, ob, of)
-    with tuned(lib, xcd_band=0):
+    with tuned(xcd_band=0):
         ob0, of0 = _ln(lib, x, g, b)
     assert torch.equal(ob, ob0) and torch.equal(of, of0)
 
@@ -254,7 +231,7 @@ def test_banding_switch_at_4096_rows_keeps_the_bits(lib, bf16):
         x, g, b = R.make_rows("rowscale", rows, 768, seed=9, device="cuda", bf16=bf16)
         ob, of = _ln(lib, x, g, b)
         _assert_ln("ln_banded", "rowscale", x, g, b, ob, of)
-        with tuned(lib, xcd_band=0):
+        with tuned(xcd_band=0):
             ob0, of0 = _ln(lib, x, g, b)
         assert torch.equal(ob, ob0) and torch.equal(of, of0)
         # mq_row_stats bands from the same row count
@@ -279,7 +256,7 @@ def test_wide_form_rows_do_not_depend_on_their_company(lib, W):
     for total in (8193, 16399):
         for pos in (0, 4001, total - 81):
             for wide in (1, 4):
-                with tuned(lib, ln_bf16_wide=wide):
+                with tuned(ln_bf16_wide=wide):
                     eb, ef = _embedded(lib, core, g, b, total, pos)
                 assert torch.equal(eb, ob) and torch.equal(ef, of), (W, total, pos, wide, int((ef != of).sum()))
 
@@ -288,7 +265,7 @@ def test_wide_form_rows_do_not_depend_on_their_company(lib, W):
 @pytest.mark.parametrize("W", (4, 260, 768, 1024))
 def test_generic_form_rows_do_not_depend_on_their_company(lib, W, bf16):
     core, g, b = R.make_rows("rowscale", 81, W, seed=12, device="cuda", bf16=bf16)
-    with tuned(lib, ln_bf16_wide=0):
+    with tuned(ln_bf16_wide=0):
         ob, of = _ln(lib, core, g, b)
         for total in (8191, 8193):                          # one / two rows per wave
             for pos in (0, 4001, total - 81):
@@ -307,7 +284,7 @@ def _row_stats(lib, x, eps=EPS):
 
 
 def _banded_off_stats(lib, x):
-    with tuned(lib, xcd_band=0):
+    with tuned(xcd_band=0):
         return _row_stats(lib, x)
 
 
@@ -544,11 +521,8 @@ def test_argument_checks_launch_nothing(lib):
 
 
 def test_the_layernorm_knobs_exist_and_unknown_keys_are_refused(lib):
-    try:
+    with tuned(ln_rows=1, ln_bf16_wide=0):      # (both are back at their entry values on the way out)
         for key, values in ((b"ln_rows", (1, 2)), (b"ln_bf16_wide", (0, 4, 1))):
             for v in values:
                 assert lib.mq_tune(key, v) == L.MQ_OK
         assert lib.mq_tune(b"ln_no_such_knob", 1) != L.MQ_OK and "unknown key" in lib.mq_last_error().decode()
-    finally:
-        L.check(lib.mq_tune(b"ln_rows", tuned.DEFAULTS["ln_rows"]))
-        L.check(lib.mq_tune(b"ln_bf16_wide", tuned.DEFAULTS["ln_bf16_wide"]))

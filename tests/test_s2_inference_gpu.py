@@ -17,6 +17,7 @@ from PIL import Image
 
 from oracle import preprocess as OP
 from oracle import towers as O
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -305,10 +306,8 @@ def test_every_kernel_family_knob_keeps_vectorise_right(s2):
     seeded weights; 40 images = 2 000 token rows: the tiled GEMM families; 33 texts; one lone query: the skinny families): still the oracle's
     embeddings inside the north-star tolerance, and within 3e-4 of the default configuration's."""
     s2i, _ = s2
-    from marqo_amd import _lib as L
     from marqo_amd.engine import archs, synthetic
     os.environ["MARQO_AMD_SYNTHETIC_WEIGHTS"] = "1"
-    lib = L.load()
     name = "open_clip/ViT-B-32/laion2b_s34b_b79k"
     rng = np.random.default_rng(5)
     pil = [Image.fromarray(rng.integers(0, 256, (224, 224, 3), dtype=np.uint8)) for _ in range(40)]
@@ -320,15 +319,10 @@ def test_every_kernel_family_knob_keeps_vectorise_right(s2):
     sdc = synthetic.random_open_clip_state_dict(vision=varch, text=tarch, seed=0)
     refi = O.vit_forward(sdc, O.VitConfig(224, 32, 768, 12, 12, 3072, 512), torch.from_numpy(np.stack([OP.clip_transform(np.asarray(p)) for p in pil[:6]]))).numpy()
     assert _cos_err(base_i[:6], refi) < COS_TOL and _cos_err(base_q, base_t[3:4]) < 3e-4
-    defaults = {k: 0 for k, _ in KNOB_SWEEP}
-    defaults.update(gemm_cgroup=8, ln_fold=2, small_m=80, small_m_grouped=320, row_select=1, ln_prefetch=1, xcd_band=1, attn_proj=128)
     worst = {}
     for key, value in KNOB_SWEEP:
-        try:
-            L.check(lib.mq_tune(key.encode(), value), "mq_tune")
+        with tuned(**{key: value}):
             i, t, q = run()
-        finally:
-            L.check(lib.mq_tune(key.encode(), defaults[key]), "mq_tune")
         worst[(key, value)] = max(_cos_err(i, base_i), _cos_err(t, base_t), _cos_err(q, base_q))
         assert _cos_err(i[:6], refi) < COS_TOL, (key, value)
         assert worst[(key, value)] < 3e-4, (key, value, worst[(key, value)])

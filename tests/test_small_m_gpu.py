@@ -7,6 +7,7 @@ import torch
 
 from marqo_amd import _lib as L
 from oracle import towers as O
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -108,7 +109,6 @@ def test_single_query_towers_on_the_skinny_path():
     """One query per call, full-size towers (ViT-B/32 text + image, e5-base): skinny path vs the fp32 CPU oracle, vs the tiled kernels on
     the same input, and bit-identical to the same query inside a small batch."""
     from marqo_amd.engine import archs, synthetic, towers
-    lib = L.load()
     v, t = archs.resolve_open_clip("ViT-B-32")
     sd = synthetic.random_open_clip_state_dict(vision=v, text=t, seed=0)
     tt, vt = towers.ClipTextTower(t, sd, "cuda"), towers.VitTower(v, sd, "cuda")
@@ -128,19 +128,18 @@ def test_single_query_towers_on_the_skinny_path():
     bmask = torch.ones(3, 12, dtype=torch.int64)
     bcfg = O.BertConfig(vocab=b.vocab, max_pos=b.max_pos, width=b.width, layers=b.layers, heads=b.heads, mlp_dim=b.mlp_dim, ln_eps=b.ln_eps)
     ref_b = O.hf_encode(bsd, bcfg, bids, bmask)
-    try:
-        skinny_t = torch.cat([tt.encode_ids(ids[i:i + 1]) for i in range(5)])        # graph replay of the skinny path, one query each
-        skinny_v = torch.cat([vt.encode_u8(u8[i:i + 1].cuda()) for i in range(2)])   # 50 rows
-        skinny_b = torch.cat([bt.encode_ids(bids[i:i + 1], bmask[i:i + 1]) for i in range(3)])
-        assert _cos_err(skinny_t, ref_t) < 1e-4 and _cos_err(skinny_v, ref_v) < 1e-4 and _cos_err(skinny_b, ref_b) < 1e-4
-        print(f"single-query skinny path: 1-cos vs fp32 oracle  text {_cos_err(skinny_t, ref_t):.2e}  image {_cos_err(skinny_v, ref_v):.2e}  "
-              f"e5 {_cos_err(skinny_b, ref_b):.2e}")
-        # a query inside a small batch (still <= 80 rows): the same bits as on its own — rows are independent in the skinny kernels, and the
-        # fused LayerNorm (<= 32 rows) has the arithmetic of the stand-alone one
-        short = ids[:3]
-        assert torch.equal(tt.encode_ids(short), skinny_t[:3])
-        assert torch.equal(bt.encode_ids(bids, bmask), skinny_b)
-        L.check(lib.mq_tune(b"small_m", 0))
+    skinny_t = torch.cat([tt.encode_ids(ids[i:i + 1]) for i in range(5)])        # graph replay of the skinny path, one query each
+    skinny_v = torch.cat([vt.encode_u8(u8[i:i + 1].cuda()) for i in range(2)])   # 50 rows
+    skinny_b = torch.cat([bt.encode_ids(bids[i:i + 1], bmask[i:i + 1]) for i in range(3)])
+    assert _cos_err(skinny_t, ref_t) < 1e-4 and _cos_err(skinny_v, ref_v) < 1e-4 and _cos_err(skinny_b, ref_b) < 1e-4
+    print(f"single-query skinny path: 1-cos vs fp32 oracle  text {_cos_err(skinny_t, ref_t):.2e}  image {_cos_err(skinny_v, ref_v):.2e}  "
+          f"e5 {_cos_err(skinny_b, ref_b):.2e}")
+    # a query inside a small batch (still <= 80 rows): the same bits as on its own — rows are independent in the skinny kernels, and the
+    # fused LayerNorm (<= 32 rows) has the arithmetic of the stand-alone one
+    short = ids[:3]
+    assert torch.equal(tt.encode_ids(short), skinny_t[:3])
+    assert torch.equal(bt.encode_ids(bids, bmask), skinny_b)
+    with tuned(small_m=0):
         for tower in (tt, vt, bt):
             tower._graphs.clear()                                                     # the captured single-request graphs hold skinny launches
         tiled_t = torch.cat([tt.encode_ids(ids[i:i + 1]) for i in range(5)])
@@ -148,8 +147,6 @@ def test_single_query_towers_on_the_skinny_path():
         tiled_b = torch.cat([bt.encode_ids(bids[i:i + 1], bmask[i:i + 1]) for i in range(3)])
         for a, c in ((skinny_t, tiled_t), (skinny_v, tiled_v), (skinny_b, tiled_b)):
             assert _cos_err(a, c) < 1e-4   # two summation orders of the same products (and, under the bf16 residual stream, of the same bf16-rounded x)
-    finally:
-        L.check(lib.mq_tune(b"small_m", 80))
 
 
 @pytest.mark.parametrize("M", [81, 100, 192, 256, 320])
@@ -189,17 +186,13 @@ def test_skinny_gemm_in_row_groups(M):
     W = (torch.randn(512, 768, device="cuda", generator=g) / 28).to(torch.bfloat16)
     out = torch.empty(321, 512, device="cuda", dtype=torch.bfloat16)
     assert lib.mq_gemm_small_bf16(A.data_ptr(), 768, W.data_ptr(), 768, 0, 0, out.data_ptr(), 512, 321, 512, 768, 0, _stream()) != 0
-    try:
-        L.check(lib.mq_tune(b"small_m_grouped", 0))
+    with tuned(small_m_grouped=0):
         assert lib.mq_gemm_small_bf16(A.data_ptr(), 768, W.data_ptr(), 768, 0, 0, out.data_ptr(), 512, 256, 512, 768, 0, _stream()) != 0
-    finally:
-        L.check(lib.mq_tune(b"small_m_grouped", 320))
 
 
 def test_few_item_requests_on_the_grouped_path():
     """4 images (200 rows) / 16 short texts: every block's GEMMs run in row groups.  Against the fp32 oracle and against the tiled kernels."""
     from marqo_amd.engine import archs, synthetic, towers
-    lib = L.load()
     v, t = archs.resolve_open_clip("ViT-B-32")
     sd = synthetic.random_open_clip_state_dict(vision=v, text=t, seed=0)
     tt, vt = towers.ClipTextTower(t, sd, "cuda"), towers.VitTower(v, sd, "cuda")
@@ -211,12 +204,9 @@ def test_few_item_requests_on_the_grouped_path():
     u8 = O.synthetic_images_u8(4, v.image_size, seed=4)
     ref_t = O.clip_text_forward(sd, O.ClipTextConfig(t.vocab, t.ctx, t.width, t.layers, t.heads, t.mlp_dim, t.out_dim), ids)
     ref_v = O.vit_forward(sd, O.VitConfig(v.image_size, v.patch_size, v.width, v.layers, v.heads, v.mlp_dim, v.out_dim), O.preprocess_u8_exact_size(u8))
-    try:
-        grouped_t, grouped_v = tt.encode_ids(ids), vt.encode_u8(u8.cuda())
-        assert _cos_err(grouped_t, ref_t) < 1e-4 and _cos_err(grouped_v, ref_v) < 1e-4
-        L.check(lib.mq_tune(b"small_m_grouped", 0))
+    grouped_t, grouped_v = tt.encode_ids(ids), vt.encode_u8(u8.cuda())
+    assert _cos_err(grouped_t, ref_t) < 1e-4 and _cos_err(grouped_v, ref_v) < 1e-4
+    with tuned(small_m_grouped=0):
         tiled_t, tiled_v = tt.encode_ids(ids), vt.encode_u8(u8.cuda())
-        assert _cos_err(grouped_t, tiled_t) < 1e-4 and _cos_err(grouped_v, tiled_v) < 1e-4
-        assert not torch.equal(grouped_v, tiled_v)          # (the knob does switch families)
-    finally:
-        L.check(lib.mq_tune(b"small_m_grouped", 320))
+    assert _cos_err(grouped_t, tiled_t) < 1e-4 and _cos_err(grouped_v, tiled_v) < 1e-4
+    assert not torch.equal(grouped_v, tiled_v)          # (the knob does switch families)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from marqo_amd import _lib as L
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -15,12 +16,6 @@ GLU = 256
 
 def _s():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tune(**kw):
-    lib = L.load()
-    for k, v in kw.items():
-        L.check(lib.mq_tune(k.encode(), v))
 
 
 def _folded(W, b, gam, bet):
@@ -58,8 +53,7 @@ def test_residual_gemm_applies_the_layernorm_of_its_input_and_leaves_row_sums(M,
     stats[:, 1] = (1.0 / torch.sqrt(ad.var(1, unbiased=False) + eps)).float()
     ns = (N + 63) // 64
     flags = L.MQ_EPI_BIAS | L.MQ_EPI_RESIDUAL
-    try:
-        _tune(**plan)
+    with tuned(**{"gemm_mt": 0, "gemm_nh": 0, **plan}):
         x = x0.clone()
         part = torch.full((ns, M, 2), float("nan"), device="cuda")       # slot-major
         L.check(lib.mq_gemm_bf16_lnrs(a.data_ptr(), K, wf.data_ptr(), K, bf.data_ptr(), colsum.data_ptr(), stats.data_ptr(), x.data_ptr(), x.data_ptr(), N, M, N, K, flags, part.data_ptr(), _s()))
@@ -81,12 +75,10 @@ def test_residual_gemm_applies_the_layernorm_of_its_input_and_leaves_row_sums(M,
         x2, part2 = x0.clone(), torch.empty_like(part)
         L.check(lib.mq_gemm_bf16_lnrs(a.data_ptr(), K, wf.data_ptr(), K, bf.data_ptr(), colsum.data_ptr(), stats.data_ptr(), x2.data_ptr(), x2.data_ptr(), N, M, N, K, flags, part2.data_ptr(), _s()))
         assert torch.equal(x2, x) and torch.equal(part2, part)
-        _tune(gemm_mt=0, gemm_nh=0)
+        tune(gemm_mt=0, gemm_nh=0)
         x3, part3 = x0.clone(), torch.empty_like(part)
         L.check(lib.mq_gemm_bf16_lnrs(a.data_ptr(), K, wf.data_ptr(), K, bf.data_ptr(), colsum.data_ptr(), stats.data_ptr(), x3.data_ptr(), x3.data_ptr(), N, M, N, K, flags, part3.data_ptr(), _s()))
         assert torch.equal(x3, x) and torch.equal(part3, part)
-    finally:
-        _tune(gemm_mt=0, gemm_nh=0)
 
 
 @pytest.mark.parametrize("plan", [dict(), dict(gemm_mt=2), dict(gemm_mt=6), dict(gemm_nh=3)])
@@ -107,8 +99,7 @@ def test_gated_gemm_leaves_the_row_sums_of_the_product(M, F, K, plan):
     L.check(lib.mq_row_stats(x.data_ptr(), stats.data_ptr(), M, K, eps, _s()))
     ldc, N = 2 * F, 2 * F
     ns = (N + 63) // 64
-    try:
-        _tune(**plan)
+    with tuned(**plan):
         ref = torch.full((M, ldc), 7.0, device="cuda", dtype=torch.bfloat16)
         L.check(lib.mq_gemm_bf16_ln(x.data_ptr(), K, wf.data_ptr(), K, bf.data_ptr(), colsum.data_ptr(), stats.data_ptr(), ref.data_ptr(), ldc, M, N, K, L.MQ_EPI_BIAS | GLU, _s()))
         out = torch.full((M, ldc), 7.0, device="cuda", dtype=torch.bfloat16)
@@ -127,8 +118,6 @@ def test_gated_gemm_leaves_the_row_sums_of_the_product(M, F, K, plan):
         pd = out[:, :F].double()
         assert torch.allclose(fin[:, 0].double(), pd.mean(1), rtol=1e-4, atol=1e-5)
         assert torch.allclose(fin[:, 1].double(), 1.0 / torch.sqrt(pd.var(1, unbiased=False) + eps), rtol=2e-4)
-    finally:
-        _tune(gemm_mt=0, gemm_nh=0)
 
 
 def test_attention_leaves_the_row_sums_per_head():

@@ -9,6 +9,7 @@ import torch
 
 from oracle import towers as O
 from tests import golden_util as G
+from tests.knobs import tune, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -154,11 +155,6 @@ def test_tower_input_validation():
         T.BertTower(A.BertArch(vocab=V, max_pos=P, width=W, layers=L, heads=H, mlp_dim=F), sd, "cpu")
 
 
-def _tune(key: str, value: int):
-    from marqo_amd import _lib as L
-    L.check(L.load().mq_tune(key.encode(), value))
-
-
 def test_row_selected_last_block_is_bit_identical(tiled_gemm_only):
     """The towers run the out-projection / MLP of the LAST block only on the rows that are pooled afterwards
     (class token, EOT, CLS).  That is dead-row elimination, not an approximation: embeddings must be bit-identical to
@@ -182,16 +178,13 @@ def test_row_selected_last_block_is_bit_identical(tiled_gemm_only):
         "text_padded": lambda: txt.encode_ids(ids, normalize=False, pack=False),
         "bert_cls": lambda: bert.encode_ids(bids, bmask, normalize=False),
     }
-    try:
-        for name, run in runs.items():
-            _tune("row_select", 1)
+    for name, run in runs.items():
+        with tuned(row_select=1):
             sel = run().cpu()
-            _tune("row_select", 0)
+            tune(row_select=0)
             full = run().cpu()
-            assert torch.isfinite(sel).all()
-            assert torch.equal(sel, full), f"{name}: max |diff| = {(sel - full).abs().max().item():.3e}"
-    finally:
-        _tune("row_select", 1)
+        assert torch.isfinite(sel).all()
+        assert torch.equal(sel, full), f"{name}: max |diff| = {(sel - full).abs().max().item():.3e}"
 
 
 def test_row_selected_last_block_full_size_fp8(tiled_gemm_only):
@@ -207,13 +200,10 @@ def test_row_selected_last_block_full_size_fp8(tiled_gemm_only):
         tower = T.VitTower(arch2, sd, "cuda", precision=precision)
         if precision == "fp8":
             tower.calibrate_fp8(lambda: tower.encode_u8(u8))
-        try:
-            _tune("row_select", 1)
+        with tuned(row_select=1):
             sel = tower.encode_u8(u8).cpu()
-            _tune("row_select", 0)
+            tune(row_select=0)
             full = tower.encode_u8(u8).cpu()
-        finally:
-            _tune("row_select", 1)
         assert torch.equal(sel, full), precision
 
 
@@ -531,7 +521,6 @@ def test_eva02_tower_vs_oracle(name, layers, n, monkeypatch):
     the fp32 CPU oracle in seconds) against oracle.eva_vit_forward (restated from timm; unpinned — no timm in this image).  One image (the
     small-row kernel families), un-normalised output, and the fused-qkv checkpoint form."""
     from dataclasses import replace
-    from marqo_amd import _lib as L
     T, A = _towers()
     if name == "tiny":
         varch = A.VitArch(64, 16, 128, layers, 2, 170, 64, ln_eps=1e-6, ln_pre=False, eva=True)
@@ -573,11 +562,8 @@ def test_eva02_tower_vs_oracle(name, layers, n, monkeypatch):
             # round 6 (ABI 12): attn.norm / mlp.norm folded into the out-projection / fc2 GEMMs (default) against the LayerNorm passes (mq_tune("subln_fold", 0))
             assert tw._blocks[0].out_wf and tw._blocks[0].fc2_wf and tw._blocks[0].fc2_sf
             assert torch.equal(tw.encode_u8(big.cuda()), got)                         # deterministic
-            try:
-                L.check(L.load().mq_tune(b"subln_fold", 0))
+            with tuned(subln_fold=0):
                 passes = tw.encode_u8(big.cuda())
-            finally:
-                L.check(L.load().mq_tune(b"subln_fold", 1))
             assert _cos_err(passes[:n], bref) < COS_TIGHT and _cos_err(passes, got) < 1e-4
 
 
@@ -654,37 +640,31 @@ def test_bf16_residual_stream_parity(tiled_gemm_only, monkeypatch):
     forced on (MARQO_AMD_RESIDUAL_STREAM=bf16).  Full registry depth, plain and trained-like weights: still inside the 3e-4 the fp32-stream
     form is held to, and the pooled-rows-only last block stays bit-identical to the all-rows execution in this form too (within the tiled
     GEMM family: the fixture keeps the few pooled rows off the skinny kernel, whose split-K summation order differs)."""
-    from marqo_amd import _lib as L
     from marqo_amd.engine import archs, towers
-    lib = L.load()
     monkeypatch.setenv("MARQO_AMD_RESIDUAL_STREAM", "bf16")
-    try:
-        for arch_name, cfg in (("ViT-B-32", O.VitConfig(224, 32, 768, 12, 12, 3072, 512)), ("ViT-L-14", O.VitConfig(224, 14, 1024, 24, 16, 4096, 768))):
-            varch, tarch = archs.resolve_open_clip(arch_name)
-            for weights in ("plain", "realistic"):
-                sd = O.synthetic_vit_state_dict(cfg, 0) if weights == "plain" else O.synthetic_vit_state_dict_realistic(cfg, 0)
-                u8 = O.synthetic_images_u8(3, 224, seed=9)
-                ref = O.vit_forward(sd, cfg, O.preprocess_u8_exact_size(u8))
-                tower = towers.VitTower(varch, sd, "cuda:0")
-                assert tower.residual_stream == "bf16" and tower.cfg.enc.residual_stream == 1
-                out = tower.encode_u8(u8.to("cuda:0"))
-                e = float((1 - torch.nn.functional.cosine_similarity(out.cpu().double(), ref.double(), dim=-1)).max())
-                print(f"bf16 residual stream, {arch_name} {weights}: 1-cos vs fp32 oracle {e:.2e}")
-                assert e < 3e-4
-                L.check(lib.mq_tune(b"row_select", 0))
+    for arch_name, cfg in (("ViT-B-32", O.VitConfig(224, 32, 768, 12, 12, 3072, 512)), ("ViT-L-14", O.VitConfig(224, 14, 1024, 24, 16, 4096, 768))):
+        varch, tarch = archs.resolve_open_clip(arch_name)
+        for weights in ("plain", "realistic"):
+            sd = O.synthetic_vit_state_dict(cfg, 0) if weights == "plain" else O.synthetic_vit_state_dict_realistic(cfg, 0)
+            u8 = O.synthetic_images_u8(3, 224, seed=9)
+            ref = O.vit_forward(sd, cfg, O.preprocess_u8_exact_size(u8))
+            tower = towers.VitTower(varch, sd, "cuda:0")
+            assert tower.residual_stream == "bf16" and tower.cfg.enc.residual_stream == 1
+            out = tower.encode_u8(u8.to("cuda:0"))
+            e = float((1 - torch.nn.functional.cosine_similarity(out.cpu().double(), ref.double(), dim=-1)).max())
+            print(f"bf16 residual stream, {arch_name} {weights}: 1-cos vs fp32 oracle {e:.2e}")
+            assert e < 3e-4
+            with tuned(row_select=0):
                 full = tower.encode_u8(u8.to("cuda:0"))
-                L.check(lib.mq_tune(b"row_select", 1))
-                assert torch.equal(full, out)
-        tcfg = O.ClipTextConfig(49408, 77, 768, 12, 12, 3072, 768)
-        _, tarch = archs.resolve_open_clip("ViT-L-14")
-        sd = O.synthetic_clip_text_state_dict_realistic(tcfg, 0)
-        ids = O.synthetic_clip_ids(12, seed=6)
-        out = towers.ClipTextTower(tarch, sd, "cuda:0").encode_ids(ids).cpu()
-        e = float((1 - torch.nn.functional.cosine_similarity(out.double(), O.clip_text_forward(sd, tcfg, ids).double(), dim=-1)).max())
-        print(f"bf16 residual stream, CLIP text L/14 realistic: 1-cos vs fp32 oracle {e:.2e}")
-        assert e < 5e-4
-    finally:
-        L.check(lib.mq_tune(b"row_select", 1))
+            assert torch.equal(full, out)
+    tcfg = O.ClipTextConfig(49408, 77, 768, 12, 12, 3072, 768)
+    _, tarch = archs.resolve_open_clip("ViT-L-14")
+    sd = O.synthetic_clip_text_state_dict_realistic(tcfg, 0)
+    ids = O.synthetic_clip_ids(12, seed=6)
+    out = towers.ClipTextTower(tarch, sd, "cuda:0").encode_ids(ids).cpu()
+    e = float((1 - torch.nn.functional.cosine_similarity(out.double(), O.clip_text_forward(sd, tcfg, ids).double(), dim=-1)).max())
+    print(f"bf16 residual stream, CLIP text L/14 realistic: 1-cos vs fp32 oracle {e:.2e}")
+    assert e < 5e-4
 
 
 def test_residual_stream_policy_is_decided_per_model_at_load(monkeypatch):
@@ -777,10 +757,7 @@ def test_weight_prefetch_changes_no_bit():
         if precision == "fp8":
             tower.tune_fp8_default()
         outs = []
-        try:
-            for knob in (0, 1, 2, 3):
-                _tune("ln_prefetch", knob)
+        for knob in (0, 1, 2, 3):
+            with tuned(ln_prefetch=knob):
                 outs.append(tower.encode_u8(u8))
-        finally:
-            _tune("ln_prefetch", 1)
         assert all(torch.equal(outs[0], o) for o in outs[1:]), precision
