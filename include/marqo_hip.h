@@ -833,6 +833,25 @@ int mq_tokenize_clip_bpe(const mq_clip_bpe_vocab* v, const uint8_t* d_text, cons
                          int64_t total_bytes, int32_t ctx, int32_t* d_ids, int32_t* d_lens, int32_t* d_status,
                          void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* GPT-2 / RoBERTa byte-level BPE (vocab.json + merges.txt; transformers RobertaTokenizer without add_prefix_space): no normalisation, the
+ * pre-token pattern 's 't 're 've 'm 'll 'd |  ?\p{L}+ |  ?\p{N}+ |  ?[^\s\p{L}\p{N}]+ | \s+(?!\S) | \s+ over the raw text (classes from
+ * d_unicode), byte symbols without a word-final variant, merges lowest rank first.  d_ids int32 [n, ld] rows = <s> ids... </s> then pad_id,
+ * the first max_length - 2 ids kept; d_lens[i] = tokens in row i including <s> / </s>.  A pre-token of more than 128 bytes sends its text to
+ * the host (d_status[i] = 1).  The caller guarantees that every merge's parts and result are vocabulary ids (< 65536) and routes texts that
+ * spell a special token to the host.  Workspace: mq_tokenize_workspace_bytes(n, total_bytes, max_length).  (Added without an ABI bump:
+ * new symbols only.) */
+typedef struct mq_byte_bpe_vocab {
+    const void*     d_slots;    /* mq_bpe_entry[n_slots], as mq_clip_bpe_vocab */
+    const uint16_t* d_byte_id;  /* [256] id of the one-character string a byte maps to */
+    const uint64_t* d_unicode;  /* [0x30000] character table: the \s / \p{L} / \p{N} classes only */
+    uint32_t n_slots;           /* power of two */
+    int32_t cls_id, sep_id, pad_id;
+} mq_byte_bpe_vocab;
+
+int mq_tokenize_byte_bpe(const mq_byte_bpe_vocab* v, const uint8_t* d_text, const int64_t* d_offsets, int64_t n,
+                         int64_t total_bytes, int32_t max_length, int32_t* d_ids, int64_t ld, int32_t* d_lens,
+                         int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* SentencePiece unigram (XLM-RoBERTa checkpoints of the multilingual-e5 family; T5-style vocabularies of the SigLIP towers): the model's
  * own normaliser as a per-code-point map + whitespace rules, then the unigram Viterbi search (tokenize_algo.h).  Rows are
  * [prefix_id] ids + id_offset ... suffix_id pad_id..., truncated to max_length; <unk> is written as unk_out. */

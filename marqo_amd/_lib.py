@@ -160,6 +160,12 @@ class ClipBpeVocab(C.Structure):
                 ("sot_id", C.c_int32), ("eot_id", C.c_int32), ("lower", C.c_int32), ("d_unicode", C.c_void_p)]
 
 
+class ByteBpeVocab(C.Structure):
+    """mq_byte_bpe_vocab: GPT-2 / RoBERTa byte-level BPE (csrc/tokenize.hip)"""
+    _fields_ = [("d_slots", C.c_void_p), ("d_byte_id", C.c_void_p), ("d_unicode", C.c_void_p), ("n_slots", C.c_uint32), ("cls_id", C.c_int32),
+                ("sep_id", C.c_int32), ("pad_id", C.c_int32)]
+
+
 class SentencePieceVocab(C.Structure):
     _fields_ = [("d_slots", C.c_void_p), ("d_pool", C.c_void_p), ("d_score", C.c_void_p), ("d_nmap", C.c_void_p), ("d_npool", C.c_void_p),
                 ("d_ccc", C.c_void_p), ("n_slots", C.c_uint32), ("unk_id", C.c_int32), ("unk_score", C.c_float), ("add_dummy_prefix", C.c_int32),
@@ -259,6 +265,7 @@ _SIGNATURES = {
     "mq_tokenize_wordpiece": (C.c_int, [C.POINTER(WordPieceVocab), _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P,
                                         C.c_size_t, _P]),
     "mq_tokenize_clip_bpe": (C.c_int, [C.POINTER(ClipBpeVocab), _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mq_tokenize_byte_bpe": (C.c_int, [C.POINTER(ByteBpeVocab), _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "mq_tokenize_sentencepiece_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
     "mq_tokenize_sentencepiece": (C.c_int, [C.POINTER(SentencePieceVocab), _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P,
                                             C.c_size_t, _P]),

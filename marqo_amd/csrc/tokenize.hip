@@ -9,7 +9,8 @@
 #include "tokenize_algo.h"
 
 static_assert(sizeof(mq_wp_entry) == 16 && sizeof(mq_bpe_entry) == 16, "hash-table entry layouts (mirrored in engine/gpu_tokenizers.py)");
-static_assert(sizeof(mq_wordpiece_vocab) == 56 && sizeof(mq_clip_bpe_vocab) == 48 && sizeof(mq_sentencepiece_vocab) == 96 && sizeof(mq_sp_entry) == 16,
+static_assert(sizeof(mq_wordpiece_vocab) == 56 && sizeof(mq_clip_bpe_vocab) == 48 && sizeof(mq_sentencepiece_vocab) == 96 && sizeof(mq_sp_entry) == 16 &&
+                  sizeof(mq_byte_bpe_vocab) == 40,
               "tokeniser vocabulary structs (mirrored in _lib.py)");
 
 namespace {
@@ -182,6 +183,46 @@ __global__ __launch_bounds__(TOK_THREADS) void spb_gather_kernel(mq_sp_table T, 
     lens[t] = ok ? len : 0;
 }
 
+// ---- GPT-2 / RoBERTa byte-level BPE: the three phases of the CLIP path over the RAW text (no normalised copy; the symbols of a pre-token
+// live at its own byte positions: text t at offsets[t]) -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(TOK_THREADS) void bbpe_split_kernel(mq_uni_table U, const uint8_t* __restrict__ text, const int64_t* __restrict__ offsets, int n,
+                                                                 int cap, uint64_t* __restrict__ spans, int32_t* __restrict__ totals,
+                                                                 int32_t* __restrict__ status) {
+    const int t = blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (t >= n) return;
+    const int64_t b0 = offsets[t], b1 = offsets[t + 1];
+    int st;
+    totals[t] = mq_bbpe_split(U, text + b0, (int)(b1 - b0), cap, spans + (int64_t)t * cap, &st);
+    status[t] = st;
+}
+
+__global__ __launch_bounds__(TOK_THREADS) void bbpe_merge_kernel(mq_bpe_table T, const uint8_t* __restrict__ text, const int64_t* __restrict__ offsets,
+                                                                 int cap, int blocks_per_text, const uint64_t* __restrict__ spans,
+                                                                 const int32_t* __restrict__ totals, int16_t* __restrict__ counts,
+                                                                 uint16_t* __restrict__ syms) {
+    __shared__ uint16_t sym[MQ_BPE_MAX_SYMS * TOK_THREADS];
+    const int t = blockIdx.x / blocks_per_text;
+    const int j = (blockIdx.x - t * blocks_per_text) * TOK_THREADS + threadIdx.x;
+    const int nw = min(totals[t], cap);
+    if (j >= nw) return;
+    const int64_t b0 = offsets[t];
+    const uint64_t span = spans[(int64_t)t * cap + j];
+    counts[(int64_t)t * cap + j] = (int16_t)mq_bbpe_merge_span(T, text + b0, span, syms + b0 + mq_span_start(span), sym + threadIdx.x, TOK_THREADS);
+}
+
+__global__ __launch_bounds__(TOK_THREADS) void bbpe_gather_kernel(mq_bbpe_frame F, const int64_t* __restrict__ offsets, int n, int cap, int max_length,
+                                                                  const uint64_t* __restrict__ spans, const int32_t* __restrict__ totals,
+                                                                  const int16_t* __restrict__ counts, const uint16_t* __restrict__ syms,
+                                                                  int32_t* __restrict__ ids, int64_t ld, int32_t* __restrict__ lens,
+                                                                  const int32_t* __restrict__ status) {
+    const int t = blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (t >= n) return;
+    const int ok = status[t] == MQ_TOK_OK;
+    const int len = mq_bbpe_gather(F, spans + (int64_t)t * cap, counts + (int64_t)t * cap, syms + offsets[t], ok ? min(totals[t], cap) : 0, max_length,
+                                   ids + (int64_t)t * ld, (int)ld);
+    lens[t] = ok ? len : 0;
+}
+
 // packed[cu[s] + j] = padded[s, j] for j < cu[s+1] - cu[s]
 __global__ __launch_bounds__(256) void pack_ids_kernel(const int32_t* __restrict__ padded, int64_t ld, const int32_t* __restrict__ cu,
                                                        int32_t* __restrict__ packed) {
@@ -258,6 +299,35 @@ extern "C" int mq_tokenize_clip_bpe(const mq_clip_bpe_vocab* v, const uint8_t* d
     hipLaunchKernelGGL(bpe_gather_kernel, dim3(per_text), dim3(TOK_THREADS), 0, s, T, d_offsets, (int)n, cap, ctx, w.spans, w.totals, w.counts,
                        (const uint16_t*)w.pieces, d_ids, d_lens, d_status);
     MQ_CHECK_LAUNCH("mq_tokenize_clip_bpe");
+    return MQ_OK;
+}
+
+extern "C" int mq_tokenize_byte_bpe(const mq_byte_bpe_vocab* v, const uint8_t* d_text, const int64_t* d_offsets, int64_t n,
+                                    int64_t total_bytes, int32_t max_length, int32_t* d_ids, int64_t ld, int32_t* d_lens,
+                                    int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
+    MQ_CHECK_ARG(v && v->d_slots && v->d_byte_id && v->d_unicode && pow2(v->n_slots), "mq_tokenize_byte_bpe: bad merge table");
+    MQ_CHECK_ARG(max_length >= 2 && ld >= max_length, "mq_tokenize_byte_bpe: need 2 <= max_length (%d) <= ld (%ld)", max_length, (long)ld);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_text && d_offsets && d_ids && d_lens && d_status && d_workspace, "mq_tokenize_byte_bpe: null pointer");
+    MQ_CHECK_ARG(n < (1LL << 24) && total_bytes >= 0 && total_bytes < (1LL << 40), "mq_tokenize_byte_bpe: too many texts / bytes");
+    const int cap = max_length > 2 ? max_length - 2 : 1;   // pre-tokens kept per text: every one yields at least one id
+    const TokWs w = tok_ws(d_workspace, n, total_bytes, cap, 2);
+    if (workspace_bytes < w.bytes) { mq_set_error("mq_tokenize_byte_bpe: workspace %zu < required %zu", workspace_bytes, w.bytes); return MQ_ERR_WORKSPACE; }
+    mq_bpe_table T;
+    T.slots = (const mq_bpe_entry*)v->d_slots; T.byte_id = v->d_byte_id; T.byte_end_id = v->d_byte_id; T.mask = v->n_slots - 1;
+    T.sot_id = v->cls_id; T.eot_id = v->sep_id; T.lower = 0;
+    const mq_bbpe_frame F{v->cls_id, v->sep_id, v->pad_id};
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(3, s);
+    const unsigned per_text = (unsigned)cdiv64(n, TOK_THREADS);
+    const int bpt = (cap + TOK_THREADS - 1) / TOK_THREADS;
+    const mq_uni_table U{v->d_unicode};
+    hipLaunchKernelGGL(bbpe_split_kernel, dim3(per_text), dim3(TOK_THREADS), 0, s, U, d_text, d_offsets, (int)n, cap, w.spans, w.totals, d_status);
+    hipLaunchKernelGGL(bbpe_merge_kernel, dim3((unsigned)(n * bpt)), dim3(TOK_THREADS), 0, s, T, d_text, d_offsets, cap, bpt, w.spans, w.totals, w.counts,
+                       (uint16_t*)w.pieces);
+    hipLaunchKernelGGL(bbpe_gather_kernel, dim3(per_text), dim3(TOK_THREADS), 0, s, F, d_offsets, (int)n, cap, max_length, w.spans, w.totals, w.counts,
+                       (const uint16_t*)w.pieces, d_ids, ld, d_lens, d_status);
+    MQ_CHECK_LAUNCH("mq_tokenize_byte_bpe");
     return MQ_OK;
 }
 

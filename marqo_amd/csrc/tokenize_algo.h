@@ -753,3 +753,101 @@ MQ_TOK_FN int mq_spb_gather(const mq_sp_table& T, const mq_sp_frame& F, const ui
     for (int j = cnt; j < ld; ++j) row[j] = F.pad_id;
     return cnt;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// GPT-2 / RoBERTa byte-level BPE (vocab.json + merges.txt).  Reference behaviour being reproduced (third-party, un-vendored):
+// transformers RobertaTokenizer, restated on the host as engine/tokenizers.py::RobertaBpeTokenizer.  The text is NOT normalised (no
+// lower-casing, cleaning or stripping): pre-tokens are spans of the raw text bytes, found by scanning the pattern
+//   's 't 're 've 'm 'll 'd |  ?\p{L}+ |  ?\p{N}+ |  ?[^\s\p{L}\p{N}]+ | \s+(?!\S) | \s+
+// left to right with \s, \p{L}, \p{N} from the character table (kind "gpt2": classes only).  The contractions are lower-case only and
+// are tried only where a match starts; the optional leading character is U+0020 alone.  A whitespace run that a non-space follows
+// gives up its last character: the rest of the run (when there is one) is a pre-token, the character given up opens the next word when
+// it is U+0020 and is a pre-token by itself otherwise; a run that ends the text is one pre-token.  The symbols of a pre-token are the
+// ids of its bytes' one-character strings (no word-final variant), merged by mq_bpe_merge.  Same three phases as CLIP:
+//   A  mq_bbpe_split       (per text)       spans of the raw text
+//   B  mq_bbpe_merge_span  (per pre-token)  byte symbols + merges, the surviving symbols at the pre-token's own byte positions
+//   C  mq_bbpe_gather      (per text)       <s> ids </s> <pad>..., the first max_length - 2 ids kept
+// ---------------------------------------------------------------------------------------------------------------
+struct mq_bbpe_frame {
+    int32_t cls_id, sep_id, pad_id;
+};
+
+// class (mq_clip_class) and byte length of the character at text[i]; 0 when the text needs the host (malformed, beyond the table, flagged)
+MQ_TOK_FN int mq_bbpe_char(const mq_uni_table& U, const uint8_t* text, int nbytes, int i, int* cls) {
+    uint32_t cp;
+    const int len = mq_utf8_next(text, nbytes, i, &cp);
+    if (len == 0 || cp >= MQ_UNI_LIMIT) return 0;
+    const uint32_t f = mq_u_flags(U.e[cp]);
+    if (f & MQ_U_HOST) return 0;
+    *cls = mq_clip_class(f);
+    return len;
+}
+
+// A: returns the number of pre-tokens written, at most `cap`: a pre-token yields >= 1 id and only the first ids are kept, so the scan
+// stops there.  A pre-token longer than the BPE scratch, or a character that needs the host, sets *status = MQ_TOK_NEEDS_HOST.
+MQ_TOK_FN int mq_bbpe_split(const mq_uni_table& U, const uint8_t* text, int nbytes, int cap, uint64_t* spans, int* status) {
+    *status = MQ_TOK_OK;
+    int cnt = 0, i = 0;
+    while (i < nbytes && cnt < cap) {
+        int cls, end;
+        int len = mq_bbpe_char(U, text, nbytes, i, &cls);
+        if (!len) { *status = MQ_TOK_NEEDS_HOST; return 0; }
+        int clen = 0;   // characters behind the apostrophe of a contraction
+        if (text[i] == '\'') {
+            const uint8_t a = i + 1 < nbytes ? text[i + 1] : 0, b = i + 2 < nbytes ? text[i + 2] : 0;
+            if (a == 's' || a == 't' || a == 'm' || a == 'd') clen = 1;
+            else if ((a == 'r' && b == 'e') || (a == 'v' && b == 'e') || (a == 'l' && b == 'l')) clen = 2;
+        }
+        if (clen) {
+            end = i + 1 + clen;
+        } else {
+            int p = i;   // first character of the run (behind the optional U+0020)
+            if (text[i] == ' ' && i + 1 < nbytes) {
+                int c2;
+                const int l2 = mq_bbpe_char(U, text, nbytes, i + 1, &c2);
+                if (!l2) { *status = MQ_TOK_NEEDS_HOST; return 0; }
+                if (c2 != 0) { p = i + 1; cls = c2; len = l2; }
+            }
+            end = p + len;
+            int last = p;   // (whitespace) first byte of the run's last character
+            while (end < nbytes) {
+                int c2;
+                const int l2 = mq_bbpe_char(U, text, nbytes, end, &c2);
+                if (!l2) { *status = MQ_TOK_NEEDS_HOST; return 0; }
+                if (c2 != cls) break;
+                last = end;
+                end += l2;
+            }
+            if (cls == 0 && end < nbytes && last > i) end = last;   // \s+(?!\S): the run gives up its last character
+        }
+        if (end - i > MQ_BPE_MAX_SYMS) { *status = MQ_TOK_NEEDS_HOST; return 0; }
+        spans[cnt++] = mq_span(i, end - i, 0);
+        i = end;
+    }
+    return cnt;
+}
+
+// B: BPE of one pre-token (bytes of the raw text) -> out[0 .. count) (room for one symbol per byte); returns count.
+MQ_TOK_FN int mq_bbpe_merge_span(const mq_bpe_table& T, const uint8_t* text, uint64_t span, uint16_t* out, uint16_t* sym, int ss) {
+    const int start = mq_span_start(span), len = mq_span_bytes(span);
+    for (int j = 0; j < len; ++j) sym[j * ss] = T.byte_id[text[start + j]];
+    const int L = mq_bpe_merge(T, sym, ss, len);
+    for (int j = 0; j < L; ++j) out[j] = sym[j * ss];
+    return L;
+}
+
+// C: row = <s> ids... </s> <pad>...; returns the row length.  sym_cnt[j] / symbols at sym_buf[start_j ...] are B's output.
+MQ_TOK_FN int mq_bbpe_gather(const mq_bbpe_frame& F, const uint64_t* spans, const int16_t* sym_cnt, const uint16_t* sym_buf, int nspans, int max_length,
+                             int32_t* row, int ld) {
+    const int keep = max_length - 2 > 0 ? max_length - 2 : 0;
+    int cnt = 0;
+    row[cnt++] = F.cls_id;
+    for (int j = 0; j < nspans && cnt <= keep; ++j) {
+        const uint16_t* src = sym_buf + mq_span_start(spans[j]);
+        const int k = sym_cnt[j];
+        for (int e = 0; e < k && cnt <= keep; ++e) row[cnt++] = (int32_t)src[e];
+    }
+    row[cnt++] = F.sep_id;
+    for (int j = cnt; j < ld; ++j) row[j] = F.pad_id;
+    return cnt;
+}

@@ -1,4 +1,5 @@
-"""Device-side tokenisation (K14): hash-table / character-table builders + thin wrappers over mq_tokenize_wordpiece / mq_tokenize_clip_bpe.
+"""Device-side tokenisation (K14): hash-table / character-table builders + thin wrappers over mq_tokenize_wordpiece / mq_tokenize_clip_bpe /
+mq_tokenize_byte_bpe / mq_tokenize_sentencepiece.
 
 The reference tokenises on the host (open_clip_model.py:277, hugging_face_model.py:179-185).  Here the host tokenisers of
 ``engine/tokenizers.py`` stay the definition of record; the same algorithms run on the GPU for ANY UTF-8 text (one thread per text
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from marqo_amd import _lib as L
-from marqo_amd.engine.tokenizers import ClipBpeTokenizer, WordPieceTokenizer, _byte_to_unicode
+from marqo_amd.engine.tokenizers import ClipBpeTokenizer, RobertaBpeTokenizer, WordPieceTokenizer, _byte_to_unicode
 
 WP_ENTRY = np.dtype([("hash", "<u8"), ("id", "<i4"), ("off_len", "<u4")])
 BPE_ENTRY = np.dtype([("key", "<u4"), ("rank", "<u4"), ("merged", "<u4"), ("pad", "<u4")])
@@ -50,9 +51,9 @@ def _entry(flags: int, out: Sequence[int] = ()) -> int:
     return e
 
 
-@functools.lru_cache(maxsize=4)
+@functools.lru_cache(maxsize=8)
 def build_unicode_table(kind: str, lower: bool) -> np.ndarray:
-    """uint64 [UNI_LIMIT]: what the HOST tokeniser of `kind` ('wordpiece' | 'clip') does to each code point on its own, derived by
+    """uint64 [UNI_LIMIT]: what the HOST tokeniser of `kind` ('wordpiece' | 'clip' | 'gpt2') does to each code point on its own, derived by
     calling the host tokeniser's own helpers, plus U_HOST where a code point's treatment depends on its neighbours:
 
       wordpiece (WordPieceTokenizer._basic): drop (U+0000, U+FFFD, category C*) | whitespace (\\t \\n \\r, Zs, anything str.split
@@ -63,6 +64,8 @@ def build_unicode_table(kind: str, lower: bool) -> np.ndarray:
         consonant and anything with a combining class is U_HOST.
       clip (ClipBpeTokenizer.encode): lower() then the regex classes \\s, \\p{L}, \\p{N} (from the `regex` module, as the host);
         U+03A3, U+0130 (two-character lowering) and U+017F (matches 's' under IGNORECASE in the contraction alternatives) are U_HOST.
+      gpt2 (RobertaBpeTokenizer.encode): no normalisation; only the regex classes \\s, \\p{L}, \\p{N} of the character itself (`lower` is
+        ignored).  Nothing is context-dependent: only the surrogates are U_HOST.
     """
     import unicodedata
     import regex
@@ -120,6 +123,10 @@ def build_unicode_table(kind: str, lower: bool) -> np.ndarray:
             if ch.isspace() and not (flags & U_WS):   # _clean_text's str.strip() removes these at the ends of a text (U+001C..U+001F)
                 flags |= U_STRIP
             tab[cp] = _entry(flags, [ord(out)])
+        elif kind == "gpt2":
+            # RobertaBpeTokenizer.PAT over the raw text: classes only, the output code point is the character itself
+            flags = U_WS if re_s.match(ch) else (U_LETTER if re_l.match(ch) else (U_NUMBER if re_n.match(ch) else 0))
+            tab[cp] = _entry(flags, [cp])
         else:
             raise ValueError(kind)
     return tab
@@ -200,6 +207,41 @@ def build_bpe_table(tok: ClipBpeTokenizer) -> Dict[str, object]:
                 lower=int(bool(tok.lower)))
 
 
+def build_byte_bpe_table(tok: RobertaBpeTokenizer) -> Dict[str, object]:
+    """vocab.json + merges.txt of a GPT-2 / RoBERTa byte-level BPE -> pair table (layout: mq_bpe_entry) + the ids of the 256 byte symbols.
+    The host tokeniser merges STRINGS and looks the survivors up at the end (a missing one is <unk>); the device merges IDS, which says
+    the same only when every symbol a merge chain can pass through has an id: a vocabulary without one of the byte symbols, or with a
+    merge whose left part, right part or result is not in vocab.json, is refused (ValueError: the caller keeps the host tokeniser).
+    Python-dict semantics are kept for duplicated merges (the LAST rank wins); a merges.txt line that is no pair can never match."""
+    enc = tok.encoder
+    if len(enc) > 65535 or any(not (0 <= int(i) < 65535) for i in enc.values()):
+        raise ValueError(f"byte-level BPE device path needs a vocabulary of at most 65535 entries with ids below 65535 (got {len(enc)})")
+    b2u = _byte_to_unicode()
+    missing = [b for b in range(256) if b2u[b] not in enc]
+    if missing:
+        raise ValueError(f"vocab.json lacks the symbol of byte 0x{missing[0]:02x} ({len(missing)} byte symbols missing)")
+    pairs: Dict[int, Tuple[int, int]] = {}
+    for pair, r in tok.rank.items():
+        if len(pair) != 2:
+            continue
+        x, y = pair
+        for part in (x, y, x + y):
+            if part not in enc:
+                raise ValueError(f"merge {x!r} + {y!r} (rank {r}): {part!r} is not in vocab.json")
+        pairs[(enc[x] << 16) | enc[y]] = (r, enc[x + y])
+    n_slots = _pow2_at_least(2 * len(pairs) + 1)
+    keys = np.fromiter(pairs.keys(), dtype=np.uint64, count=len(pairs))
+    place = _insert_open_addressing(((keys * np.uint64(0x9e3779b1)) & np.uint64(0xffffffff)) >> np.uint64(7), n_slots)
+    slots = np.zeros(n_slots, dtype=BPE_ENTRY)
+    slots["key"] = 0xffffffff
+    vals = np.array(list(pairs.values()), dtype=np.uint32).reshape(-1, 2)
+    slots["key"][place] = keys.astype(np.uint32)
+    slots["rank"][place] = vals[:, 0]
+    slots["merged"][place] = vals[:, 1]
+    byte_id = np.array([enc[b2u[b]] for b in range(256)], dtype=np.uint16)
+    return dict(slots=slots, byte_id=byte_id, n_slots=n_slots, cls_id=int(tok.cls_id), sep_id=int(tok.sep_id), pad_id=int(tok.pad_id))
+
+
 def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     """texts -> (UTF-8 uint8 blob, int64 byte offsets [n+1]).  Texts that cannot be encoded (lone surrogates) must have been routed to
     the host by the scope test."""
@@ -241,6 +283,13 @@ def clip_in_scope(tok: ClipBpeTokenizer, text: str) -> bool:
         low = text.lower()
         return tok.SOT not in low and tok.EOT not in low
     return True
+
+
+def byte_bpe_in_scope(tok: RobertaBpeTokenizer, text: str) -> bool:
+    """host-side routing test: size, encodability and the spellings of the vocabulary's special tokens (the host maps them to their ids;
+    every one of them starts with '<').  Over-long pre-tokens and characters beyond the table are flagged by the kernel itself."""
+    return (len(text) < MAX_TEXT_BYTES_DEVICE // 4 and _encodable(text)
+            and ("<" not in text or not any(s in text for s in tok._specials)))
 
 
 # A lone short text — the search path's one query — is tokenised faster on the host (0.01-0.07 ms, word cache warm / cold) than by the device
@@ -415,6 +464,71 @@ class DeviceClipBpeTokenizer(_DeviceTokenizerBase):
             texts = [texts]
         ids, _ = self.encode_device(texts, context_length)
         return ids.cpu().numpy().astype(np.int64)
+
+
+class DeviceByteBpeTokenizer(_DeviceTokenizerBase):
+    """GPT-2 / RoBERTa byte-level BPE on the GPU (mq_tokenize_byte_bpe) for in-scope texts: rows <s> ids </s>, <pad> padding.  `host` (a
+    RobertaBpeTokenizer) is the tokeniser of record: it handles texts that spell a special token and texts the kernel flags (a pre-token of
+    more than 128 bytes, code points beyond U+2FFFF); its ids are patched into the same matrix.  A vocabulary the id-based merges cannot
+    express is refused with ValueError (build_byte_bpe_table)."""
+
+    def __init__(self, host: RobertaBpeTokenizer, device: str):
+        super().__init__(device)
+        self.host = host
+        t = build_byte_bpe_table(host)
+        self.pad_id = t["pad_id"]
+        self.vocab = L.ByteBpeVocab(d_slots=self._up(t["slots"]).data_ptr(), d_byte_id=self._up(t["byte_id"]).data_ptr(),
+                                    d_unicode=self._up(build_unicode_table("gpt2", False)).data_ptr(), n_slots=t["n_slots"],
+                                    cls_id=t["cls_id"], sep_id=t["sep_id"], pad_id=t["pad_id"])
+
+    def encode_device(self, texts: Sequence[str], max_length: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (ids int32 [n, max_length] on device, padded with pad_id; lengths int64 [n] on host, <s> and </s> included)"""
+        n = len(texts)
+        ids = torch.full((n, max_length), self.pad_id, dtype=torch.int32, device=self.device)
+        lens_np = np.zeros(n, dtype=np.int64)   # (host bookkeeping in NumPy: see engine/towers.py::_host_i64)
+        lens = torch.from_numpy(lens_np)
+        if n == 0:
+            return ids, lens
+        on_dev = self._split_routes(texts, lambda t: byte_bpe_in_scope(self.host, t))
+        dev_set = set(on_dev)
+        if on_dev:
+            sel = texts if len(on_dev) == n else [texts[i] for i in on_dev]
+            m = len(sel)
+            with self._lock, torch.cuda.device(self.device):
+                d_blob, d_off, total = self._stage(sel)
+                d_ids = ids if m == n else torch.empty(m, max_length, dtype=torch.int32, device=self.device)
+                d_meta = torch.empty(2, m, dtype=torch.int32, device=self.device)
+                ws = self._workspace(m, total, max_length)
+                L.check(self.lib.mq_tokenize_byte_bpe(C.byref(self.vocab), d_blob.data_ptr(), d_off.data_ptr(), m, total, max_length,
+                                                      d_ids.data_ptr(), max_length, d_meta[0].data_ptr(), d_meta[1].data_ptr(), ws.data_ptr(),
+                                                      ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), "mq_tokenize_byte_bpe")
+                meta = d_meta.cpu().numpy()  # (also the sync after which the pinned staging buffer may be reused)
+            if meta[1].any():  # a pre-token longer than the device scratch, a code point beyond the table
+                dev_set.difference_update(on_dev[j] for j in np.nonzero(meta[1])[0].tolist())
+            lens_np[on_dev] = meta[0]
+            if m != n:
+                ids[torch.tensor(on_dev, dtype=torch.int64).to(self.device)] = d_ids
+        rest = [i for i in range(n) if i not in dev_set]
+        if rest:
+            block = np.full((len(rest), max_length), self.pad_id, dtype=np.int32)
+            for j, i in enumerate(rest):
+                e = self.host.encode(texts[i], max_length)
+                block[j, :len(e)] = e
+                lens_np[i] = len(e)
+            ids[torch.tensor(rest, device=self.device)] = torch.from_numpy(block).to(self.device)
+        return ids, lens
+
+    def __call__(self, texts, max_length: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """drop-in for RobertaBpeTokenizer.__call__ (padding to the longest, truncation); at most one id per UTF-8 byte"""
+        if isinstance(texts, str):
+            texts = [texts]
+        cap = max_length if max_length is not None else 2 + 4 * max((len(t) for t in texts), default=0)
+        ids, lens = self.encode_device(texts, max(cap, 2))
+        lens = lens.numpy()
+        S = int(lens.max()) if len(texts) else 0
+        out = ids[:, :S].cpu().numpy().astype(np.int64)
+        mask = (np.arange(S)[None, :] < lens[:, None]).astype(np.int64)
+        return {"input_ids": out, "attention_mask": mask}
 
 
 # =====================================================================================================================================

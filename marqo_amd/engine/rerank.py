@@ -3,7 +3,8 @@
 The reference scores pairs with sentence-transformers' `CrossEncoder` (s2_inference/reranking/model_utils.py load_sbert_cross_encoder_model),
 i.e. a Hugging Face `*ForSequenceClassification` with num_labels = 1 behind the fast tokenizer's pair call (`truncation="longest_first"`).
 Two families are served (`_Family`): BERT (WordPiece, [CLS] a [SEP] b [SEP], two type rows, pooler + classifier) and XLM-RoBERTa /
-SentencePiece RoBERTa (<s> a </s> </s> b </s>, one type row, position ids from padding_idx + 1, classifier.dense + classifier.out_proj).
+RoBERTa with a SentencePiece model or with GPT-2's byte-level BPE (<s> a </s> </s> b </s>, one type row, position ids from padding_idx + 1,
+classifier.dense + classifier.out_proj).
 The texts are tokenised once on the GPU (engine/gpu_tokenizers.py), paired, truncated and packed there (mq_pair_plan_n / mq_pack_pairs |
 mq_pack_pairs_xlmr), and every batch is ONE mq_score_pairs_bert | mq_score_pairs_xlmr call.
 """
@@ -20,7 +21,7 @@ import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
-from marqo_amd.engine.tokenizers import WordPieceTokenizer, XlmRobertaTokenizer
+from marqo_amd.engine.tokenizers import RobertaBpeTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
 from marqo_amd.engine.towers import BertTower, _large_call, _need, request_stream
 
 Tensor = torch.Tensor
@@ -84,6 +85,29 @@ def _tokenizer_settings(directory: str) -> Tuple[bool, int]:
     return lower, max_len
 
 
+def _byte_bpe_refusal(directory: str) -> Optional[str]:
+    """why a directory's GPT-2 / RoBERTa byte-level BPE files (vocab.json + merges.txt) cannot be served, or None"""
+    if not (os.path.isfile(os.path.join(directory, "vocab.json")) and os.path.isfile(os.path.join(directory, "merges.txt"))):
+        return "vocab.json or merges.txt is not there"
+    try:
+        with open(os.path.join(directory, "vocab.json"), encoding="utf-8") as f:
+            vocab = json.load(f)
+    except (OSError, ValueError) as e:
+        return f"vocab.json cannot be read ({e})"
+    gone = [t for t in ("<s>", "<pad>", "</s>", "<unk>") if not isinstance(vocab, dict) or t not in vocab]
+    if gone:
+        return f"vocab.json has no {' / '.join(gone)} token"
+    p = os.path.join(directory, "tokenizer_config.json")
+    if os.path.isfile(p):
+        try:
+            with open(p) as f:
+                if json.load(f).get("add_prefix_space"):
+                    return "its tokenizer_config.json sets add_prefix_space, which the tokeniser here does not implement"
+        except (OSError, ValueError, AttributeError):
+            pass
+    return None
+
+
 def head_tensors(sd: Dict[str, Tensor], family: _Family, W: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(dense weight [W, W], dense bias [W], out weight [1, W], out bias [1]) of a checkpoint's scoring head under the family's names"""
     return (_need(sd, family.dense + ".weight", (W, W)), _need(sd, family.dense + ".bias", (W,)),
@@ -118,30 +142,35 @@ class CrossEncoderTower(BertTower):
             raise ValueError(f"token_type_embeddings must be [{arch.type_vocab}, {W}]")
         self.tokenizer = tokenizer
         self.model_max_length = int(min(model_max_length, arch.max_pos))     # (max_pos counts the usable positions: archs.BertArch)
-        from marqo_amd.engine.gpu_tokenizers import DeviceSentencePieceTokenizer, DeviceWordPieceTokenizer
-        device_cls = DeviceWordPieceTokenizer if family is BERT else DeviceSentencePieceTokenizer
+        from marqo_amd.engine.gpu_tokenizers import DeviceByteBpeTokenizer, DeviceSentencePieceTokenizer, DeviceWordPieceTokenizer
+        device_cls = DeviceWordPieceTokenizer if family is BERT else \
+            DeviceByteBpeTokenizer if isinstance(tokenizer, RobertaBpeTokenizer) else DeviceSentencePieceTokenizer
         self.device_tokenizer = device_cls(tokenizer, str(self.device))
         self.tune_residual_default()      # the same load-time policy as the embedding towers, on the encoder's [CLS] rows
         self.release_unused_folded()
 
     @classmethod
     def from_dir(cls, directory: str, device: str) -> "CrossEncoderTower":
-        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, vocab.txt | sentencepiece.bpe.model,
-        tokenizer_config.json"""
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, vocab.txt | sentencepiece.bpe.model |
+        vocab.json + merges.txt, tokenizer_config.json"""
         cfg, sd = checkpoint.load_hf_dir(directory)
         mtype = cfg.get("model_type", "bert")
+        byte_bpe = False
         if mtype == "bert":
             family = BERT
         elif mtype in ("xlm-roberta", "roberta"):
             family = XLMR
             if not os.path.isfile(os.path.join(directory, "sentencepiece.bpe.model")):
                 if mtype == "roberta" or os.path.isfile(os.path.join(directory, "merges.txt")):
-                    raise ValueError(f"{directory}: model_type={mtype!r} with a byte-level BPE tokeniser (vocab.json + merges.txt) is not served as "
-                                     f"a cross-encoder: RoBERTa checkpoints are served only with a SentencePiece model (sentencepiece.bpe.model)")
-                raise ValueError(f"{directory}: model_type={mtype!r} needs the checkpoint's sentencepiece.bpe.model, which is not there")
+                    byte_bpe = True
+                    why = _byte_bpe_refusal(directory)
+                    if why:
+                        raise ValueError(f"{directory}: model_type={mtype!r} with a byte-level BPE tokeniser (vocab.json + merges.txt) is not served as "
+                                         f"a cross-encoder: {why}")
+                else:
+                    raise ValueError(f"{directory}: model_type={mtype!r} needs the checkpoint's sentencepiece.bpe.model, which is not there")
         else:
-            raise ValueError(f"{directory}: model_type={mtype!r} is not served as a cross-encoder (only 'bert', 'xlm-roberta', and 'roberta' "
-                             f"with a SentencePiece model)")
+            raise ValueError(f"{directory}: model_type={mtype!r} is not served as a cross-encoder (only 'bert', 'xlm-roberta' and 'roberta')")
         labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
         if int(labels) != 1:
             raise ValueError(f"{directory}: num_labels={labels} is not served as a cross-encoder (only one-logit heads)")
@@ -151,7 +180,10 @@ class CrossEncoderTower(BertTower):
             raise ValueError(f"{directory}: {e}") from e
         arch = dataclasses.replace(arch, type_vocab=int(cfg.get("type_vocab_size", 2 if family is BERT else 1)))
         lower, max_len = _tokenizer_settings(directory)
-        tokenizer = WordPieceTokenizer(directory, do_lower_case=lower) if family is BERT else XlmRobertaTokenizer(directory)
+        if family is BERT:
+            tokenizer = WordPieceTokenizer(directory, do_lower_case=lower)
+        else:
+            tokenizer = RobertaBpeTokenizer(directory) if byte_bpe else XlmRobertaTokenizer(directory)
         return cls(arch, sd, device, tokenizer, model_max_length=max_len, family=family)
 
     # ---- scoring -------------------------------------------------------------------------------------------------------------------
@@ -164,6 +196,8 @@ class CrossEncoderTower(BertTower):
         and normalises by NFKC, which can expand a character: a row that fills 4 pieces per character is tokenised again on the host."""
         if self.family is BERT:
             return self._tokenize([query], max(len(query) + 2, 4))
+        if isinstance(self.tokenizer, RobertaBpeTokenizer):     # byte-level BPE: at most one id per byte
+            return self._tokenize([query], len(query.encode("utf-8", "surrogatepass")) + 2)
         cap = 4 * len(query) + 4
         d_q, qlen = self._tokenize([query], cap)
         if int(qlen[0]) >= cap:

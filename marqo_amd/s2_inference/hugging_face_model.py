@@ -18,7 +18,7 @@ from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint, synthetic
 from marqo_amd.engine.gpu_tokenizers import prefers_host
 from marqo_amd.engine.towers import request_stream
-from marqo_amd.engine.tokenizers import SyntheticTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
+from marqo_amd.engine.tokenizers import RobertaBpeTokenizer, SyntheticTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
 from marqo_amd.s2_inference.abstract_models import AbstractEmbeddingModel
 from marqo_amd.s2_inference.errors import InternalError, InvalidModelPropertiesError, ModelLoadError
 
@@ -115,6 +115,16 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                                                   f"'trustRemoteCode': True (type 'hf_stella')")
             if os.path.isfile(os.path.join(directory, "sentencepiece.bpe.model")):  # XLM-RoBERTa checkpoints (multilingual-e5)
                 self._tokenizer = XlmRobertaTokenizer(directory)
+            elif all(os.path.isfile(os.path.join(directory, f)) for f in ("vocab.json", "merges.txt")) and \
+                    not os.path.isfile(os.path.join(directory, "vocab.txt")):
+                # RoBERTa checkpoints (all-roberta-large-v1, all-distilroberta-v1 ...): GPT-2 byte-level BPE
+                if self._adds_prefix_space(directory):
+                    raise InvalidModelPropertiesError(f"{props.name}: its tokenizer_config.json sets add_prefix_space, which the byte-level BPE "
+                                                      f"tokeniser of the marqo_amd engine does not implement")
+                try:
+                    self._tokenizer = RobertaBpeTokenizer(directory)
+                except ValueError as e:   # a vocab.json without <s> / <pad> / </s> / <unk>
+                    raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
             elif arch.rel_buckets:
                 # MPNetTokenizer = BERT's basic + WordPiece tokenisation around "<s> ... </s>" (transformers tokenization_mpnet.py); the
                 # special-token spellings come from the checkpoint's tokenizer_config.json / special_tokens_map.json
@@ -156,6 +166,24 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 self._device_tokenizer = DeviceSentencePieceTokenizer(self._tokenizer, self.device)
             except ValueError:
                 self._device_tokenizer = None
+        elif isinstance(self._tokenizer, RobertaBpeTokenizer) and os.environ.get("MARQO_AMD_HOST_TOKENIZER", "0") != "1":
+            from marqo_amd.engine.gpu_tokenizers import DeviceByteBpeTokenizer
+            try:   # byte-level BPE on the device; a vocabulary whose merges ids cannot express stays on the host
+                self._device_tokenizer = DeviceByteBpeTokenizer(self._tokenizer, self.device)
+            except ValueError:
+                self._device_tokenizer = None
+
+    @staticmethod
+    def _adds_prefix_space(directory: str) -> bool:
+        import json
+        p = os.path.join(directory, "tokenizer_config.json")
+        if os.path.isfile(p):
+            try:
+                with open(p) as f:
+                    return bool(json.load(f).get("add_prefix_space", False))
+            except (OSError, ValueError, AttributeError):
+                pass
+        return False
 
     @staticmethod
     def _special_tokens(directory: str, **defaults) -> dict:
