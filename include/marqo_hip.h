@@ -1195,6 +1195,63 @@ int mq_video_preprocess(const uint8_t* d_frames, int64_t T_in, int32_t H, int32_
 int mq_resample(const float* d_wave, int64_t channels, int64_t len, const double* d_taps, int32_t o, int32_t n, int32_t width, float* d_out,
                 void* stream);
 
+/* ---- ModernBERT text encoders: sliding-window attention and the tower (csrc/attention_window.hip, csrc/modernbert.hip; engine/modernbert.py) ------
+ * transformers' ModernBertModel (model_type "modernbert": gte-modernbert-base, modernbert-embed-base, granite-embedding-*-r2 ...): pre-LN blocks
+ * without any bias, rotary positions, a gated-GELU MLP, and two layers in three attending only a band of keys.
+ * Additions to ABI 15: nothing above changes; the structs below are new.  Every entry point judges its arguments before any launch
+ * (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_window: mq_attention (bf16, 64-wide heads, no causal mask, no bias; packed or fixed-length sequences up to 8192 rows) where query i
+ *                   attends the keys j of its own sequence with |i - j| <= half_window — inclusive on both sides, as transformers' ModernBERT
+ *                   builds its sliding mask with half_window = local_attention / 2.  A band kernel: one workgroup per (sequence, head, 64-query slice)
+ *                   stages only the 64-key tiles the slice can reach, and a 16-query block visits only the tiles that cut its band (masked per key at the
+ *                   band's edges, unmasked inside).  half_window >= 0; half_window >= max_len - 1 is full attention and runs mq_attention's kernel.
+ *   mq_encode_modernbert: token embedding -> LayerNorm -> `layers` blocks  x += Wo(attn(rope(Wqkv(attn_norm(x))))) ; x += mlp.Wo(gelu(input) * gate) with
+ *                   (input | gate) = mlp.Wi(mlp_norm(x))  -> final_norm over all rows -> mean / CLS pooling (+ L2), on packed sequences like
+ *                   mq_encode_bert.  fp32 residual stream, bf16 GEMM operands.  Layer 0 has no attn_norm (attn_norm_g NULL: the embedding
+ *                   LayerNorm's output feeds Wqkv and is the residual).  A layer with sliding != 0 rotates with d_inv_freq_local and runs
+ *                   mq_attention_window(half_window); the others rotate with d_inv_freq_global and run mq_attention.  d_out fp32 [nseq, width]. */
+typedef struct mq_modernbert_layer {
+    const float* attn_norm_g;   /* fp32 [W], NULL: no LayerNorm in front of Wqkv (layer 0) */
+    const void*  qkv_w;         /* bf16 [3W, W]  attn.Wqkv, rows q | k | v */
+    const void*  out_w;         /* bf16 [W, W]   attn.Wo */
+    const float* mlp_norm_g;    /* fp32 [W] */
+    const void*  wi_w;          /* bf16 [2F, W]  mlp.Wi with its halves SWAPPED to mq_glu's (up | gate) order: rows 0 .. F-1 = the checkpoint's `gate`
+                                 * half (rows F .. 2F-1 of mlp.Wi, the plain multiplier), rows F .. 2F-1 = its `input` half (the one GELU is applied to) */
+    const void*  wo_w;          /* bf16 [W, F]   mlp.Wo */
+    int32_t      sliding;       /* 0: full attention, global rotary base; 1: band of half_window, local rotary base */
+    int32_t      reserved;
+} mq_modernbert_layer;
+
+typedef struct mq_modernbert_weights {
+    const float* tok_emb;       /* fp32 [vocab, W] */
+    const float* emb_ln_g;      /* fp32 [W] */
+    const float* final_ln_g;    /* fp32 [W] */
+    const float* zeros;         /* fp32 [W] of zeros: the bias of the bias-free LayerNorms and residual GEMMs */
+    const float* d_inv_freq_global; /* fp32 [32]: theta_global ^ -(2 i / 64) */
+    const float* d_inv_freq_local;  /* fp32 [32]: theta_local ^ -(2 i / 64) */
+    const mq_modernbert_layer* layers;  /* host array, `layers` entries */
+} mq_modernbert_weights;
+
+typedef struct mq_modernbert_cfg {
+    int32_t width;       /* W = heads * 64 */
+    int32_t layers;
+    int32_t heads;
+    int32_t mlp_dim;     /* F, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;     /* longest sequence served (<= 8192) */
+    int32_t half_window; /* local_attention / 2 */
+    int32_t pool;        /* MQ_POOL_* */
+    float   ln_eps;
+    int32_t reserved;
+} mq_modernbert_cfg;
+
+int mq_attention_window(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len, int32_t W,
+                        int32_t heads, int32_t half_window, void* stream);
+size_t mq_modernbert_workspace_bytes(const mq_modernbert_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_modernbert(const mq_modernbert_cfg* cfg, const mq_modernbert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                         const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

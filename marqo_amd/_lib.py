@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -192,6 +192,22 @@ class ScoreHeadWeights(C.Structure):
     _fields_ = [("pooler_w", C.c_void_p), ("pooler_b", C.c_void_p), ("cls_w", C.c_void_p), ("cls_b", C.c_float), ("type_vocab", C.c_int32)]
 
 
+class ModernBertLayer(C.Structure):
+    """mq_modernbert_layer: one ModernBERT block (csrc/modernbert.hip)"""
+    _fields_ = [("attn_norm_g", C.c_void_p), ("qkv_w", C.c_void_p), ("out_w", C.c_void_p), ("mlp_norm_g", C.c_void_p), ("wi_w", C.c_void_p),
+                ("wo_w", C.c_void_p), ("sliding", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ModernBertWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("emb_ln_g", C.c_void_p), ("final_ln_g", C.c_void_p), ("zeros", C.c_void_p), ("d_inv_freq_global", C.c_void_p),
+                ("d_inv_freq_local", C.c_void_p), ("layers", C.POINTER(ModernBertLayer))]
+
+
+class ModernBertCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("vocab", C.c_int32), ("max_pos", C.c_int32),
+                ("half_window", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -340,6 +356,10 @@ _SIGNATURES = {
     "mq_video_preprocess": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _P, _P]),
     "mq_resample": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    # ModernBERT text encoders: sliding-window attention and the tower (csrc/attention_window.hip, csrc/modernbert.hip; engine/modernbert.py)
+    "mq_attention_window": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_modernbert_workspace_bytes": (C.c_size_t, [C.POINTER(ModernBertCfg), C.c_int64, C.c_int64]),
+    "mq_encode_modernbert": (C.c_int, [C.POINTER(ModernBertCfg), C.POINTER(ModernBertWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

@@ -234,6 +234,73 @@ class BertArch:
 
 
 @dataclass(frozen=True)
+class ModernBertArch:
+    """transformers' ModernBertModel (model_type "modernbert"): pre-LN blocks without any bias, rotary positions with one base per layer kind, a
+    gated-GELU MLP (mlp.Wi [2F, W] -> input, gate = chunk(2); Wo(gelu(input) * gate)), no attn_norm in layer 0, and `sliding` layers that attend
+    only the keys within half_window = local_attention // 2 positions (inclusive on both sides)."""
+    vocab: int = 50368
+    max_pos: int = 8192
+    width: int = 768
+    layers: int = 22
+    heads: int = 12
+    mlp_dim: int = 1152
+    ln_eps: float = 1e-5
+    sliding: Tuple[bool, ...] = ()        # per layer: True = sliding_attention, False = full_attention
+    half_window: int = 64
+    theta_global: float = 160000.0
+    theta_local: float = 10000.0
+
+    def inv_freq(self, local: bool):
+        """[head_dim / 2] inverse frequencies as ModernBertRotaryEmbedding.compute_default_rope_parameters builds them: base^-(2i/d)"""
+        import torch
+        d = self.width // self.heads
+        base = self.theta_local if local else self.theta_global
+        return 1.0 / (base ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F = tokens, self.width, self.mlp_dim
+        full = 2 * T * W * (3 * W) + 2 * T * W * W + 2 * 3 * T * W * F
+        attn = sum(4 * T * min(T, 2 * self.half_window + 1) * W if s else 4 * T * T * W for s in self.sliding)
+        return (self.layers * full + attn) / 1e9
+
+
+def modernbert_arch_from_hf_config(cfg: dict) -> ModernBertArch:
+    """A local ModernBERT `config.json` -> ModernBertArch.  The layer kinds come from `layer_types`, else from `global_attn_every_n_layers` (layer i is
+    full when i % n == 0); the rotary bases from `rope_parameters` {full_attention, sliding_attention}.rope_theta, else the older `global_rope_theta` /
+    `local_rope_theta` keys, else 160000 / 10000."""
+    for k in ("norm_bias", "attention_bias", "mlp_bias"):
+        if cfg.get(k, False):
+            raise KeyError(f"ModernBERT checkpoints with {k}=true are not supported (the tower runs bias-free blocks)")
+    if cfg.get("hidden_activation", "gelu") != "gelu":
+        raise KeyError(f"hidden_activation={cfg.get('hidden_activation')} unsupported")
+    W, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    if heads < 1 or W != heads * 64:
+        raise KeyError(f"ModernBERT runs 64-wide attention heads only: hidden_size / num_attention_heads = {W} / {heads} is not 64")
+    F = int(cfg["intermediate_size"])
+    if F % 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    kinds = cfg.get("layer_types")
+    if kinds is None:
+        n = int(cfg.get("global_attn_every_n_layers", 3))
+        kinds = ["sliding_attention" if i % n else "full_attention" for i in range(layers)]
+    if len(kinds) != layers or any(k not in ("full_attention", "sliding_attention") for k in kinds):
+        raise KeyError(f"layer_types={kinds} must name full_attention / sliding_attention for each of the {layers} layers")
+    rp = cfg.get("rope_parameters") or {}
+    thetas = {}
+    for kind, old, default in (("full_attention", "global_rope_theta", 160000.0), ("sliding_attention", "local_rope_theta", 10000.0)):
+        sub = rp.get(kind) or {}
+        if sub.get("rope_type", "default") != "default":
+            raise KeyError(f"rope_parameters[{kind}].rope_type={sub.get('rope_type')} unsupported (default only)")
+        thetas[kind] = float(sub.get("rope_theta", cfg.get(old, default)))
+    if cfg.get("rope_scaling"):
+        raise KeyError(f"rope_scaling={cfg.get('rope_scaling')} unsupported")
+    return ModernBertArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 8192)), 8192), width=W, layers=layers, heads=heads,
+                          mlp_dim=F, ln_eps=float(cfg.get("norm_eps", 1e-5)), sliding=tuple(k == "sliding_attention" for k in kinds),
+                          half_window=int(cfg.get("local_attention", 128)) // 2, theta_global=thetas["full_attention"],
+                          theta_local=thetas["sliding_attention"])
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -505,10 +572,14 @@ STELLA_EN_400M = BertArch(vocab=30528, max_pos=8192, width=1024, layers=24, head
 HF_BERT_ARCHS["Marqo/dunzhang-stella_en_400M_v5"] = STELLA_EN_400M
 
 
-def bert_arch_from_hf_config(cfg: dict) -> BertArch:
-    """A local HF `config.json` -> BertArch.  model_type bert, or xlm-roberta / roberta: the same encoder with the position ids
-    shifted by padding_idx + 1 (the multilingual-e5 family)."""
+def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch]:
+    """A local HF `config.json` -> the arch of the text encoder the `hf` loader builds.  model_type bert, or xlm-roberta / roberta (the same encoder
+    with the position ids shifted by padding_idx + 1: the multilingual-e5 family), mpnet and `new` give a BertArch (engine/towers.py::BertTower);
+    model_type modernbert gives a ModernBertArch (engine/modernbert.py::ModernBertTower) — callers that can only run a BertArch (the cross-encoders of
+    engine/rerank.py, which select their model types before they call) must not pass one through.  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
+    if mtype == "modernbert":   # transformers ModernBertModel: its own arch and tower (engine/modernbert.py)
+        return modernbert_arch_from_hf_config(cfg)
     if mtype == "new":  # Alibaba-NLP/new-impl NewModel (custom remote code in the reference: hf_stella)
         if cfg.get("position_embedding_type", "rope") != "rope" or cfg.get("hidden_act", "gelu") != "gelu":
             raise KeyError("NewModel checkpoints are supported with rotary positions and the gated-GELU MLP")

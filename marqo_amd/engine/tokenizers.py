@@ -21,6 +21,7 @@ import hashlib
 import html
 import json
 import os
+import threading
 import unicodedata
 from functools import lru_cache
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
@@ -606,6 +607,49 @@ class SyntheticTokenizer:
             if max_length is not None:
                 ids = ids[:max(max_length - 2, 0)]
             enc.append([self.cls_id] + ids + [self.sep_id])
+        S = max((len(e) for e in enc), default=0)
+        ids = np.full((len(enc), S), self.pad_id, dtype=np.int64)
+        mask = np.zeros((len(enc), S), dtype=np.int64)
+        for i, e in enumerate(enc):
+            ids[i, :len(e)] = e
+            mask[i, :len(e)] = 1
+        return {"input_ids": ids, "attention_mask": mask}
+
+
+# ---------------------------------------------------------------------------------------------------
+# ModernBERT checkpoints: the `tokenizers` library over the directory's tokenizer.json
+# ---------------------------------------------------------------------------------------------------
+class HfJsonTokenizer:
+    """A checkpoint's `tokenizer.json` run by the `tokenizers` library on the host (what transformers' PreTrainedTokenizerFast wraps): rows
+    [CLS] pieces... [SEP], truncated to max_length with both specials kept, padded to the longest of the call with the pad token.  The file's own
+    post-processor supplies the template; a file without one gets "[CLS] $A [SEP]" from the spellings the caller passes."""
+
+    def __init__(self, directory: str, cls: str = "[CLS]", sep: str = "[SEP]", pad: str = "[PAD]"):
+        from tokenizers import Tokenizer
+        from tokenizers.processors import TemplateProcessing
+        path = os.path.join(directory, "tokenizer.json")
+        if not os.path.isfile(path):
+            raise ValueError(f"{directory} has no tokenizer.json")
+        self.tk = Tokenizer.from_file(path)
+        ids = {name: self.tk.token_to_id(tok) for name, tok in (("cls", cls), ("sep", sep), ("pad", pad))}
+        missing = [name for name, i in ids.items() if i is None]
+        if missing:
+            raise ValueError(f"tokenizer.json lacks the special tokens {missing} ({cls} / {sep} / {pad})")
+        self.cls_id, self.sep_id, self.pad_id = ids["cls"], ids["sep"], ids["pad"]
+        if self.tk.post_processor is None:
+            self.tk.post_processor = TemplateProcessing(single=f"{cls} $A {sep}", special_tokens=[(cls, self.cls_id), (sep, self.sep_id)])
+        self.tk.no_padding()
+        self._lock = threading.Lock()   # (truncation is a setting of the shared Tokenizer object)
+
+    def __call__(self, texts: Union[str, Sequence[str]], max_length: Optional[int] = None) -> Dict[str, np.ndarray]:
+        if isinstance(texts, str):
+            texts = [texts]
+        with self._lock:
+            if max_length:
+                self.tk.enable_truncation(max_length=int(max_length))
+            else:
+                self.tk.no_truncation()
+            enc = [e.ids for e in self.tk.encode_batch(list(texts), add_special_tokens=True)]
         S = max((len(e) for e in enc), default=0)
         ids = np.full((len(enc), S), self.pad_id, dtype=np.int64)
         mask = np.zeros((len(enc), S), dtype=np.int64)

@@ -397,3 +397,29 @@ def resnet_attnpool_weights(sd: Dict[str, Tensor], arch) -> Dict[str, Tensor]:
             "kv_w": torch.cat([f32(ap + "k_proj.weight", (Cw, Cw)), f32(ap + "v_proj.weight", (Cw, Cw))]),
             "kv_b": torch.cat([f32(ap + "k_proj.bias", (Cw,)), f32(ap + "v_proj.bias", (Cw,))]),
             "c_w": f32(ap + "c_proj.weight", (E, Cw)), "c_b": f32(ap + "c_proj.bias", (E,))}
+
+
+def modernbert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' ModernBertModel tensors (with or without a `model.` prefix; heads of task models are ignored) -> the fp32 tensors the tower
+    hands to the kernels, under the checkpoint's own names.  `layers.N.mlp.Wi.weight` [2F, W] comes back with its halves SWAPPED: the module computes
+    input, gate = Wi(x).chunk(2) and gelu(input) * gate, mq_glu computes up * act(gate) from (up | gate) — so the checkpoint's `gate` rows go first
+    and its `input` rows (the ones GELU is applied to) second.  Layer 0 has no attn_norm (nn.Identity in the module): it is absent here too."""
+    if "embeddings.tok_embeddings.weight" not in sd and "model.embeddings.tok_embeddings.weight" in sd:
+        sd = {k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")}
+    W, F = arch.width, arch.mlp_dim
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    if any(k.endswith(".bias") and (k.startswith("layers.") or k.startswith("embeddings.") or k.startswith("final_norm.")) for k in sd):
+        raise ValueError("the ModernBERT tower runs bias-free blocks; this checkpoint carries bias tensors")
+    out = {"embeddings.tok_embeddings.weight": f32("embeddings.tok_embeddings.weight", (arch.vocab, W)),
+           "embeddings.norm.weight": f32("embeddings.norm.weight", (W,)), "final_norm.weight": f32("final_norm.weight", (W,))}
+    for l in range(arch.layers):
+        p = f"layers.{l}."
+        if l > 0:
+            out[p + "attn_norm.weight"] = f32(p + "attn_norm.weight", (W,))
+        out[p + "attn.Wqkv.weight"] = f32(p + "attn.Wqkv.weight", (3 * W, W))
+        out[p + "attn.Wo.weight"] = f32(p + "attn.Wo.weight", (W, W))
+        out[p + "mlp_norm.weight"] = f32(p + "mlp_norm.weight", (W,))
+        wi = f32(p + "mlp.Wi.weight", (2 * F, W))
+        out[p + "mlp.Wi.weight"] = torch.cat([wi[F:], wi[:F]], 0)
+        out[p + "mlp.Wo.weight"] = f32(p + "mlp.Wo.weight", (W, F))
+    return out

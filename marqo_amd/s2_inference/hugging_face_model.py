@@ -35,6 +35,14 @@ class HuggingFaceModelProperties:
         if self.type not in ("hf", "hf_stella"):
             raise ValueError("The type of the model should be 'hf' or 'hf_stella'.")
         self.name: Optional[str] = p.get("name")
+        # engine extension: `localpath` = a checkpoint directory on disk (config.json + weights + tokenizer files), as the open_clip loader takes
+        # one; it is looked up exactly like a directory given as `name`
+        self.localpath: Optional[str] = p.get("localpath")
+        if self.localpath is not None:
+            if not isinstance(self.localpath, str) or not self.localpath:
+                raise ValueError("'localpath' must be a directory path")
+            if self.name is None:
+                self.name = self.localpath
         self.tokens: int = int(p.get("tokens", 128))
         self.url: Optional[str] = p.get("url")
         self.model_location = p.get("model_location", p.get("modelLocation"))
@@ -109,6 +117,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 arch = archs.bert_arch_from_hf_config(cfg)
             except KeyError as e:
                 raise InvalidModelPropertiesError(f"{props.name}: {e}. Only BERT-family encoders run on the marqo_amd engine.") from e
+            if isinstance(arch, archs.ModernBertArch):
+                self._load_modernbert(directory, arch, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -172,6 +183,32 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 self._device_tokenizer = DeviceByteBpeTokenizer(self._tokenizer, self.device)
             except ValueError:
                 self._device_tokenizer = None
+
+    def _load_modernbert(self, directory: str, arch, sd) -> None:
+        """a transformers ModernBertModel checkpoint (model_type "modernbert"; no remote code in the reference either): host tokenisation by the
+        `tokenizers` library from the directory's tokenizer.json, the tower of engine/modernbert.py.  bf16 operands only."""
+        from marqo_amd.engine.modernbert import ModernBertTower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        props = self.model_properties
+        if props.engine_precision == "fp8":
+            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for ModernBERT encoders (their rotary / "
+                                              f"gated-GELU blocks run on bf16 operands only)")
+        if self._check_dimensions and arch.width != props.dimensions:
+            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {arch.width}")
+        try:
+            self._tokenizer = HfJsonTokenizer(directory, **self._special_tokens(directory, cls="[CLS]", sep="[SEP]", pad="[PAD]"))
+        except ValueError as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        props.tokens = min(props.tokens, arch.max_pos)
+        pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
+        self.arch = arch
+        self.weights_source = directory
+        try:
+            self._model = ModernBertTower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision)
+        except (ValueError, KeyError) as e:   # a missing / mis-shaped tensor, bias tensors
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        self._pooling_func = pooling
+        self._device_tokenizer = None   # (the GPU byte-level BPE tokeniser does not implement this family's added-token / whitespace-token handling)
 
     @staticmethod
     def _adds_prefix_space(directory: str) -> bool:
