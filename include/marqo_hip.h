@@ -1252,6 +1252,71 @@ size_t mq_modernbert_workspace_bytes(const mq_modernbert_cfg* cfg, int64_t rows,
 int mq_encode_modernbert(const mq_modernbert_cfg* cfg, const mq_modernbert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                          const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Qwen3 / Qwen2 text embedders: grouped-query causal attention and the tower (csrc/attention_gqa.hip, csrc/qwen.hip; engine/qwen.py) --------------
+ * transformers' Qwen3Model / Qwen2Model (model_type "qwen3" / "qwen2": Qwen3-Embedding-0.6B, gte-Qwen2-1.5B-instruct, Qwen2-0.5B fine-tunes): pre-norm
+ * decoder blocks with RMSNorm, fewer K/V heads than query heads, rotary positions, a gated-SiLU MLP, a causal mask and last-token (or mean) pooling.
+ * Additions to ABI 15: nothing above changes; the selector, structs and entry points below are new.  Every entry point judges its arguments before any
+ * launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_gqa: d_qkv bf16 [rows, (q_heads + 2 kv_heads) head_dim] = (q | k | v), head h of each part at columns h head_dim ..; d_out bf16
+ *                   [rows, q_heads head_dim].  q_heads % kv_heads == 0; query head h reads K/V head h / (q_heads / kv_heads) (transformers' repeat_kv).
+ *                   head_dim 64 or 128, softmax scale 1/sqrt(head_dim); mask MQ_MASK_NONE or MQ_MASK_CAUSAL; sequences packed or fixed-length as for
+ *                   mq_attention, max_len <= 8192.  One workgroup per (sequence, K/V head, 128-query slice) stages that head's K and V once for every
+ *                   query head that reads it; under the causal mask a slice stages, and a 16-query block visits, only the keys it can see.
+ *   mq_rmsnorm:     y = x * rsqrt(mean(x^2) + eps) * g over the last dim, fp32 statistics; x fp32 [rows, W] gathered through an optional row index as
+ *                   for mq_layernorm; writes bf16 and / or fp32 (d_out_f32 may be d_x when there is no row index).  W % 4 == 0, W <= 2048.
+ *   mq_qk_norm_rope: in place on the q and k parts of the layout above (V is not touched): per head, RMSNorm over head_dim with d_q_g / d_k_g (fp32
+ *                   [head_dim]; both NULL: no norm), then rotary positions in rotate_half form, angle = float(t) * d_inv_freq[i] with t the row's position
+ *                   in its sequence, exactly as mq_rope forms it.  fp32 from the bf16 input to the one rounding of the bf16 output.  head_dim 64 or 128.
+ *   mq_encode_qwen: token gather -> `layers` blocks  x += Wo(attn(qk_norm_rope(Wqkv(rmsnorm(x))))) ; x += Wdown(up * silu(gate)) with
+ *                   (up | gate) = Wug(rmsnorm(x))  -> final RMSNorm -> pooling (+ L2), on packed sequences like mq_encode_bert; fp32 residual stream,
+ *                   bf16 GEMM operands.  MQ_POOL_LAST: the last row of every sequence, normalised alone; MQ_POOL_MEAN: every row is normalised, then
+ *                   mq_pool.  width <= 2048 (a multiple of 64), head_dim 64 or 128, mlp_dim % 64 == 0, max_pos <= 8192.  d_out fp32 [nseq, width]. */
+#define MQ_POOL_LAST 2 /* mq_encode_qwen only: the last token of every sequence (mq_pool itself takes MQ_POOL_MEAN / MQ_POOL_CLS) */
+
+typedef struct mq_qwen_layer {
+    const float* input_norm_g;  /* fp32 [W]  input_layernorm */
+    const void*  qkv_w;         /* bf16 [(Q + 2 KV) hd, W]  rows: q_proj | k_proj | v_proj */
+    const float* qkv_b;         /* fp32 [(Q + 2 KV) hd] (Qwen2) or NULL (Qwen3) */
+    const float* q_norm_g;      /* fp32 [hd] (Qwen3) or NULL */
+    const float* k_norm_g;      /* fp32 [hd] (Qwen3) or NULL */
+    const void*  out_w;         /* bf16 [W, Q hd]  o_proj */
+    const float* post_norm_g;   /* fp32 [W]  post_attention_layernorm */
+    const void*  ug_w;          /* bf16 [2F, W]  rows: up_proj | gate_proj (mq_glu's order) */
+    const void*  down_w;        /* bf16 [W, F]  down_proj */
+} mq_qwen_layer;
+
+typedef struct mq_qwen_weights {
+    const float* tok_emb;       /* fp32 [vocab, W] */
+    const float* final_norm_g;  /* fp32 [W] */
+    const float* zeros;         /* fp32 [W] of zeros: the bias of the residual GEMMs */
+    const float* d_inv_freq;    /* fp32 [hd / 2]: rope_theta ^ -(2 i / hd) */
+    const mq_qwen_layer* layers;  /* host array, `layers` entries */
+} mq_qwen_weights;
+
+typedef struct mq_qwen_cfg {
+    int32_t width;       /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t q_heads;     /* Q */
+    int32_t kv_heads;    /* KV, divides Q */
+    int32_t head_dim;    /* hd: 64 or 128; Q hd need not be W */
+    int32_t mlp_dim;     /* F, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;     /* longest sequence served (<= 8192) */
+    int32_t pool;        /* MQ_POOL_LAST or MQ_POOL_MEAN */
+    float   rms_eps;
+} mq_qwen_cfg;
+
+int mq_attention_gqa(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len, int32_t q_heads,
+                     int32_t kv_heads, int32_t head_dim, int32_t mask, void* stream);
+int mq_rmsnorm(const float* d_x, const int32_t* d_row_idx, const float* d_g, void* d_out_bf16, float* d_out_f32, int64_t rows, int32_t W, float eps,
+               void* stream);
+int mq_qk_norm_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                    const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, void* stream);
+size_t mq_qwen_workspace_bytes(const mq_qwen_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_qwen(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
+                   int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,12 +28,12 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
 MQ_MASK_NONE, MQ_MASK_CAUSAL, MQ_MASK_CAUSAL_CLS = 0, 1, 2
-MQ_POOL_MEAN, MQ_POOL_CLS = 0, 1
+MQ_POOL_MEAN, MQ_POOL_CLS, MQ_POOL_LAST = 0, 1, 2   # (MQ_POOL_LAST: mq_encode_qwen only)
 MQ_VIT_POOL_CLS, MQ_VIT_POOL_MAP, MQ_VIT_POOL_AVG, MQ_VIT_POOL_QUERY = 0, 1, 2, 3
 MQ_EPI_BIAS, MQ_EPI_GELU, MQ_EPI_QUICKGELU, MQ_EPI_RESIDUAL, MQ_EPI_OUT_F32, MQ_EPI_OUT_FP8 = 1, 2, 4, 8, 16, 32
 MQ_EPI_ROW_STATS, MQ_EPI_LN_APPLY = 64, 128
@@ -208,6 +208,20 @@ class ModernBertCfg(C.Structure):
                 ("half_window", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+class QwenLayer(C.Structure):
+    """mq_qwen_layer: one Qwen3 / Qwen2 block (csrc/qwen.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("input_norm_g", "qkv_w", "qkv_b", "q_norm_g", "k_norm_g", "out_w", "post_norm_g", "ug_w", "down_w")]
+
+
+class QwenWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("final_norm_g", C.c_void_p), ("zeros", C.c_void_p), ("d_inv_freq", C.c_void_p), ("layers", C.POINTER(QwenLayer))]
+
+
+class QwenCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
+                ("vocab", C.c_int32), ("max_pos", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -360,6 +374,12 @@ _SIGNATURES = {
     "mq_attention_window": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_modernbert_workspace_bytes": (C.c_size_t, [C.POINTER(ModernBertCfg), C.c_int64, C.c_int64]),
     "mq_encode_modernbert": (C.c_int, [C.POINTER(ModernBertCfg), C.POINTER(ModernBertWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # Qwen3 / Qwen2 text embedders: grouped-query causal attention, RMSNorm, q/k norm + rotary, the tower (csrc/attention_gqa.hip, csrc/qwen.hip; engine/qwen.py)
+    "mq_attention_gqa": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_rmsnorm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
+    "mq_qk_norm_rope": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P]),
+    "mq_qwen_workspace_bytes": (C.c_size_t, [C.POINTER(QwenCfg), C.c_int64, C.c_int64]),
+    "mq_encode_qwen": (C.c_int, [C.POINTER(QwenCfg), C.POINTER(QwenWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

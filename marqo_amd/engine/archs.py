@@ -301,6 +301,75 @@ def modernbert_arch_from_hf_config(cfg: dict) -> ModernBertArch:
 
 
 @dataclass(frozen=True)
+class QwenArch:
+    """transformers' Qwen3Model / Qwen2Model (model_type "qwen3" / "qwen2") as the engine runs them: pre-norm decoder blocks with RMSNorm, `kv_heads` K/V
+    heads shared by `heads` query heads (query head h reads K/V head h // (heads // kv_heads)), rotary positions, a gated-SiLU MLP and a causal mask.
+    qk_norm: per-head RMSNorm of q and k in front of the rotary step (Qwen3); qkv_bias: biases on q / k / v_proj (Qwen2).  heads * head_dim need not be
+    the width."""
+    vocab: int = 151669
+    max_pos: int = 8192
+    width: int = 1024
+    layers: int = 28
+    heads: int = 16
+    kv_heads: int = 8
+    head_dim: int = 128
+    mlp_dim: int = 3072
+    rms_eps: float = 1e-6
+    rope_theta: float = 1000000.0
+    qk_norm: bool = True
+    qkv_bias: bool = False
+
+    def inv_freq(self):
+        """[head_dim / 2] inverse frequencies as transformers' default rope initialisation builds them: theta^-(2i/d)"""
+        import torch
+        d = self.head_dim
+        return 1.0 / (self.rope_theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F, A = tokens, self.width, self.mlp_dim, self.heads * self.head_dim
+        layer = 2 * T * W * (A + 2 * self.kv_heads * self.head_dim) + 2 * T * A * W + 2 * 3 * T * W * F + 2 * T * T * A   # (causal: half of 4 T T A)
+        return self.layers * layer / 1e9
+
+
+def qwen_arch_from_hf_config(cfg: dict) -> QwenArch:
+    """A local Qwen3 / Qwen2 `config.json` -> QwenArch.  rope_theta comes from `rope_parameters`, else the older top-level key.  Refused, each by the
+    name of its key: a non-default rope_type, rope_scaling, use_sliding_window, layer_types other than full_attention, hidden_act other than silu,
+    head_dim other than 64 / 128, hidden_size above 2048 (the 4B / 8B sizes)."""
+    mtype = cfg.get("model_type")
+    if mtype not in ("qwen3", "qwen2"):
+        raise KeyError(f"model_type={mtype} is not a Qwen3 / Qwen2 model")
+    if cfg.get("hidden_act", "silu") != "silu":
+        raise KeyError(f"hidden_act={cfg.get('hidden_act')} unsupported (silu only)")
+    rp = cfg.get("rope_parameters") or {}
+    rtype = rp.get("rope_type", rp.get("type", "default"))
+    if rtype != "default":
+        raise KeyError(f"rope_parameters.rope_type={rtype} unsupported (default only)")
+    if cfg.get("rope_scaling"):
+        raise KeyError(f"rope_scaling={cfg.get('rope_scaling')} unsupported")
+    if cfg.get("use_sliding_window", False):
+        raise KeyError("use_sliding_window=true unsupported (full causal attention only)")
+    W, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    kinds = cfg.get("layer_types")
+    if kinds is not None and (len(kinds) != layers or any(k != "full_attention" for k in kinds)):
+        raise KeyError(f"layer_types={kinds} unsupported (full_attention for each of the {layers} layers only)")
+    kv = int(cfg.get("num_key_value_heads") or heads)
+    if heads < 1 or kv < 1 or heads % kv:
+        raise KeyError(f"num_attention_heads={heads} must be a multiple of num_key_value_heads={kv}")
+    hd = int(cfg.get("head_dim") or W // heads)
+    if hd not in (64, 128):
+        raise KeyError(f"head_dim={hd} unsupported (64 or 128)")
+    if W > 2048 or W % 64:
+        raise KeyError(f"hidden_size={W} unsupported (a multiple of 64 up to 2048: the 4B / 8B sizes of this family are not served)")
+    F = int(cfg["intermediate_size"])
+    if F % 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    return QwenArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 8192)), 8192), width=W, layers=layers, heads=heads,
+                    kv_heads=kv, head_dim=hd, mlp_dim=F, rms_eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                    rope_theta=float(rp.get("rope_theta", cfg.get("rope_theta", 10000.0))), qk_norm=mtype == "qwen3",
+                    qkv_bias=bool(cfg.get("attention_bias", mtype == "qwen2")))
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -572,12 +641,15 @@ STELLA_EN_400M = BertArch(vocab=30528, max_pos=8192, width=1024, layers=24, head
 HF_BERT_ARCHS["Marqo/dunzhang-stella_en_400M_v5"] = STELLA_EN_400M
 
 
-def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch]:
+def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch]:
     """A local HF `config.json` -> the arch of the text encoder the `hf` loader builds.  model_type bert, or xlm-roberta / roberta (the same encoder
     with the position ids shifted by padding_idx + 1: the multilingual-e5 family), mpnet and `new` give a BertArch (engine/towers.py::BertTower);
     model_type modernbert gives a ModernBertArch (engine/modernbert.py::ModernBertTower) — callers that can only run a BertArch (the cross-encoders of
-    engine/rerank.py, which select their model types before they call) must not pass one through.  Anything else: KeyError."""
+    engine/rerank.py, which select their model types before they call) must not pass one through; model_type qwen3 / qwen2 gives a QwenArch
+    (engine/qwen.py::QwenTower) under the same rule.  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
+    if mtype in ("qwen3", "qwen2"):   # transformers Qwen3Model / Qwen2Model: decoder-style embedders (engine/qwen.py)
+        return qwen_arch_from_hf_config(cfg)
     if mtype == "modernbert":   # transformers ModernBertModel: its own arch and tower (engine/modernbert.py)
         return modernbert_arch_from_hf_config(cfg)
     if mtype == "new":  # Alibaba-NLP/new-impl NewModel (custom remote code in the reference: hf_stella)

@@ -622,15 +622,41 @@ class SyntheticTokenizer:
 class HfJsonTokenizer:
     """A checkpoint's `tokenizer.json` run by the `tokenizers` library on the host (what transformers' PreTrainedTokenizerFast wraps): rows
     [CLS] pieces... [SEP], truncated to max_length with both specials kept, padded to the longest of the call with the pad token.  The file's own
-    post-processor supplies the template; a file without one gets "[CLS] $A [SEP]" from the spellings the caller passes."""
+    post-processor supplies the template; a file without one gets "[CLS] $A [SEP]" from the spellings the caller passes.
 
-    def __init__(self, directory: str, cls: str = "[CLS]", sep: str = "[SEP]", pad: str = "[PAD]"):
+    template=False (HfJsonTokenizer.plain: the decoder-style embedders, whose files know no [CLS] / [SEP]): no class / separator token is required and no
+    template is installed — the rows are whatever the file's own post-processor makes of the pieces (Qwen3-Embedding's appends <|endoftext|>; a file
+    without a post-processor appends nothing), truncated by the library with what the post-processor appends kept, padded with `pad`."""
+
+    @classmethod
+    def plain(cls, directory: str, pad_fallback: str = "<|endoftext|>") -> "HfJsonTokenizer":
+        """the template-free form; the pad token is tokenizer_config.json's `pad_token`, else `pad_fallback`"""
+        import json
+        pad = None
+        try:
+            with open(os.path.join(directory, "tokenizer_config.json")) as f:
+                pad = json.load(f).get("pad_token")
+        except (OSError, ValueError, AttributeError):
+            pad = None
+        if isinstance(pad, dict):   # AddedToken serialisation
+            pad = pad.get("content")
+        return cls(directory, pad=pad if isinstance(pad, str) and pad else pad_fallback, template=False)
+
+    def __init__(self, directory: str, cls: str = "[CLS]", sep: str = "[SEP]", pad: str = "[PAD]", template: bool = True):
         from tokenizers import Tokenizer
         from tokenizers.processors import TemplateProcessing
         path = os.path.join(directory, "tokenizer.json")
         if not os.path.isfile(path):
             raise ValueError(f"{directory} has no tokenizer.json")
         self.tk = Tokenizer.from_file(path)
+        if not template:
+            self.cls_id = self.sep_id = None
+            self.pad_id = self.tk.token_to_id(pad)
+            if self.pad_id is None:
+                raise ValueError(f"tokenizer.json lacks the pad token {pad}")
+            self.tk.no_padding()
+            self._lock = threading.Lock()
+            return
         ids = {name: self.tk.token_to_id(tok) for name, tok in (("cls", cls), ("sep", sep), ("pad", pad))}
         missing = [name for name, i in ids.items() if i is None]
         if missing:

@@ -423,3 +423,36 @@ def modernbert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
         out[p + "mlp.Wi.weight"] = torch.cat([wi[F:], wi[:F]], 0)
         out[p + "mlp.Wo.weight"] = f32(p + "mlp.Wo.weight", (W, F))
     return out
+
+
+def qwen_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' Qwen3Model / Qwen2Model tensors (with or without a `model.` prefix; `lm_head.*` of the causal-LM classes is ignored) -> the fp32
+    tensors the tower hands to the kernels.  Per layer the three projections are fused into `layers.N.self_attn.qkv.weight` [(Q + 2 KV) hd, W] = rows
+    q_proj | k_proj | v_proj (and `.bias` when arch.qkv_bias), and the MLP's two input projections into `layers.N.mlp.up_gate.weight` [2F, W] = rows
+    up_proj | gate_proj — mq_glu computes up * silu(gate) from (up | gate), the module down_proj(silu(gate_proj(x)) * up_proj(x)).  Everything else keeps the
+    checkpoint's name."""
+    if "embed_tokens.weight" not in sd and "model.embed_tokens.weight" in sd:
+        sd = {k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")}
+    W, F, hd = arch.width, arch.mlp_dim, arch.head_dim
+    A, KVW = arch.heads * hd, arch.kv_heads * hd
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    out = {"embed_tokens.weight": f32("embed_tokens.weight", (arch.vocab, W)), "norm.weight": f32("norm.weight", (W,))}
+    for l in range(arch.layers):
+        p = f"layers.{l}."
+        a = p + "self_attn."
+        if not arch.qkv_bias and any((a + n + "_proj.bias") in sd for n in "qkv"):
+            raise ValueError(f"{a}*_proj.bias present but the config says attention_bias=false")
+        if (a + "o_proj.bias") in sd:
+            raise ValueError(f"{a}o_proj.bias: the Qwen tower runs a bias-free output projection")
+        out[p + "input_layernorm.weight"] = f32(p + "input_layernorm.weight", (W,))
+        out[a + "qkv.weight"] = torch.cat([f32(a + "q_proj.weight", (A, W)), f32(a + "k_proj.weight", (KVW, W)), f32(a + "v_proj.weight", (KVW, W))], 0)
+        if arch.qkv_bias:
+            out[a + "qkv.bias"] = torch.cat([f32(a + "q_proj.bias", (A,)), f32(a + "k_proj.bias", (KVW,)), f32(a + "v_proj.bias", (KVW,))], 0)
+        if arch.qk_norm:
+            out[a + "q_norm.weight"] = f32(a + "q_norm.weight", (hd,))
+            out[a + "k_norm.weight"] = f32(a + "k_norm.weight", (hd,))
+        out[a + "o_proj.weight"] = f32(a + "o_proj.weight", (W, A))
+        out[p + "post_attention_layernorm.weight"] = f32(p + "post_attention_layernorm.weight", (W,))
+        out[p + "mlp.up_gate.weight"] = torch.cat([f32(p + "mlp.up_proj.weight", (F, W)), f32(p + "mlp.gate_proj.weight", (F, W))], 0)
+        out[p + "mlp.down_proj.weight"] = f32(p + "mlp.down_proj.weight", (W, F))
+    return out

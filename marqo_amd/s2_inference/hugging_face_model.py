@@ -26,6 +26,8 @@ from marqo_amd.s2_inference.errors import InternalError, InvalidModelPropertiesE
 class HuggingFaceModelProperties:
     """Validated view of model_properties (reference: hugging_face_model_properties.py:40-137)."""
 
+    POOLING_ERROR = "pooling_method must be 'mean' or 'cls'"
+
     def __init__(self, **p):
         dims = p.get("dimensions")
         if not isinstance(dims, int) or dims < 1:
@@ -51,9 +53,11 @@ class HuggingFaceModelProperties:
         if not self.name and not (self.url or self.model_location):
             raise ValueError("At least one of 'name', 'url', or 'model_location' should be provided.")
         pm = p.get("pooling_method", p.get("poolingMethod"))
-        if pm is not None and pm not in ("mean", "cls"):
-            raise ValueError("pooling_method must be 'mean' or 'cls'")
-        self.pooling_method: Optional[str] = pm  # None: inferred at load from 1_Pooling/config.json, default mean
+        if pm is not None and pm not in ("mean", "cls", "last"):
+            raise ValueError(self.POOLING_ERROR)
+        # None: inferred at load from 1_Pooling/config.json, default mean.  'last' (last-token pooling) is taken by the Qwen3 / Qwen2 checkpoints only:
+        # the other families refuse it at load with the same text
+        self.pooling_method: Optional[str] = pm
         self.trust_remote_code: bool = bool(p.get("trust_remote_code", p.get("trustRemoteCode", False)))
         # engine extension: operand type of the encoder-block GEMMs, "bf16" (default) or "fp8" (e4m3 MX-MFMA; calibrated at load on
         # fixed seeded inputs, 'fp8Budget' bounds the error), see open_clip_model.OpenCLIPModelProperties
@@ -120,6 +124,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             if isinstance(arch, archs.ModernBertArch):
                 self._load_modernbert(directory, arch, sd)
                 return
+            if isinstance(arch, archs.QwenArch):
+                self._load_qwen(directory, arch, cfg, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -155,6 +162,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 f"{checkpoint.model_dir()} or the Hugging Face cache (there is no network download in the marqo_amd engine).")
         if self._check_dimensions and arch.width != props.dimensions:
             raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {arch.width}")
+        self._refuse_last_pooling()
         pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
         self.arch = arch
         try:
@@ -200,6 +208,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         except ValueError as e:
             raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
         props.tokens = min(props.tokens, arch.max_pos)
+        self._refuse_last_pooling()
         pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
         self.arch = arch
         self.weights_source = directory
@@ -209,6 +218,51 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
         self._pooling_func = pooling
         self._device_tokenizer = None   # (the GPU byte-level BPE tokeniser does not implement this family's added-token / whitespace-token handling)
+
+    def _refuse_last_pooling(self) -> None:
+        """'last' is the pooling of the decoder-style checkpoints only: every other family refuses it as the property parser did before it knew the word"""
+        if self.model_properties.pooling_method == "last":
+            raise InvalidModelPropertiesError(f"Invalid model properties: {self.model_properties.dict()}. Original error "
+                                              f"{HuggingFaceModelProperties.POOLING_ERROR}")
+
+    def _load_qwen(self, directory: str, arch, cfg: dict, sd) -> None:
+        """a transformers Qwen3Model / Qwen2Model checkpoint (model_type "qwen3" / "qwen2": Qwen3-Embedding-0.6B, gte-Qwen2-1.5B-instruct ...; AutoModel in
+        the reference): host tokenisation by the `tokenizers` library from the directory's tokenizer.json with the file's own post-processor, the tower
+        of engine/qwen.py.  Pooling: the property, else 1_Pooling/config.json (last token / mean), else last token.  bf16 operands only."""
+        import json
+        from marqo_amd.engine.qwen import QwenTower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        props = self.model_properties
+        if props.engine_precision == "fp8":
+            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for Qwen3 / Qwen2 encoders (their RMSNorm / rotary / "
+                                              f"gated-SiLU blocks run on bf16 operands only)")
+        if self._check_dimensions and arch.width != props.dimensions:
+            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {arch.width}")
+        pooling = props.pooling_method
+        if pooling is None:
+            try:
+                with open(os.path.join(directory, "1_Pooling", "config.json")) as f:
+                    pc = json.load(f)
+            except (OSError, ValueError):
+                pc = None
+            if isinstance(pc, dict):
+                pooling = "last" if pc.get("pooling_mode_lasttoken") is True else "mean" if pc.get("pooling_mode_mean_tokens") is True else None
+        pooling = pooling or "last"
+        if pooling not in ("last", "mean"):
+            raise InvalidModelPropertiesError(f"{props.name}: pooling_method {pooling!r} is not available for Qwen3 / Qwen2 encoders ('last' or 'mean')")
+        try:
+            self._tokenizer = HfJsonTokenizer.plain(directory)
+        except ValueError as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        props.tokens = min(props.tokens, int(cfg.get("max_position_embeddings", 8192)), 8192)
+        self.arch = arch
+        self.weights_source = directory
+        try:
+            self._model = QwenTower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision)
+        except (ValueError, KeyError) as e:   # a missing / mis-shaped tensor, unexpected bias tensors
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        self._pooling_func = pooling
+        self._device_tokenizer = None   # (the GPU byte-level BPE tokeniser does not implement this family's added-token handling)
 
     @staticmethod
     def _adds_prefix_space(directory: str) -> bool:
