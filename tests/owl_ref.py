@@ -1,5 +1,5 @@
 """References, rounding budgets and shared fixtures for the tests of OWL-ViT image reranking (csrc/owl_head.hip, engine/owl.py,
-s2_inference/reranking): tests/test_owl_host.py, tests/test_owl_gpu.py.  A plain helper module: nothing here calls the library.
+s2_inference/reranking): tests/test_owl_host.py, tests/test_owl_gpu.py, tests/test_owl_shapes_gpu.py.  A plain helper module: nothing here calls the library.
 u = 2**-24 throughout; reference_ln / half_ulp_bf16 / ratio are rowops_ref's.  All references are float64 NumPy on the exact input values.
 
 MERGE + LAYERNORM (owl_merge_ln_kernel).  c = LN(x_0; post), p = LN(x_j; post), m = p c, f = LN(m; ln).  B_c, B_p: rowops_ref.reference_ln's
@@ -42,7 +42,10 @@ FLT_MIN_LOGIT = -float(np.finfo(np.float32).max)
 CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
 # name -> image, patch, vision / text width, heads, layers, MLP width.  The query dimension is the text width: the class head's dense0 maps
 # to text_config.hidden_size and its rows meet text embeddings of projection_dim columns, so OwlViTForObjectDetection needs the two equal.
-SHAPES = {"g3": dict(image=96, patch=32, W=128, heads=2, layers=2, mlp=256), "g5": dict(image=160, patch=32, W=128, heads=2, layers=2, mlp=256)}
+SHAPES = {"g3": dict(image=96, patch=32, W=128, heads=2, layers=2, mlp=256), "g5": dict(image=160, patch=32, W=128, heads=2, layers=2, mlp=256),
+          # google/owlvit-base-patch32's geometry with one layer per encoder (P = 576, T = 577, Dq = 512): the chain at a served checkpoint's widths
+          "b32x1": dict(image=768, patch=32, W=768, heads=12, layers=1, mlp=3072, text_W=512, text_heads=8, text_mlp=2048)}
+TOY_SHAPES = ("g3", "g5")
 CTX = 16
 
 
@@ -207,10 +210,11 @@ def owl_config(shape):
     from transformers import OwlViTConfig
     s = SHAPES[shape]
     side = dict(hidden_size=s["W"], intermediate_size=s["mlp"], num_hidden_layers=s["layers"], num_attention_heads=s["heads"])
+    text = dict(side, hidden_size=s.get("text_W", s["W"]), intermediate_size=s.get("text_mlp", s["mlp"]), num_attention_heads=s.get("text_heads", s["heads"]))
     vocab = 512 + len(MERGES) + 2
     return OwlViTConfig(text_config=dict(vocab_size=vocab, max_position_embeddings=CTX, bos_token_id=vocab - 2, eos_token_id=vocab - 1, pad_token_id=0,
-                                         **side),
-                        vision_config=dict(image_size=s["image"], patch_size=s["patch"], **side), projection_dim=s["W"])
+                                         **text),
+                        vision_config=dict(image_size=s["image"], patch_size=s["patch"], **side), projection_dim=text["hidden_size"])
 
 
 def write_owl_dir(directory, shape, seed=0):
@@ -221,6 +225,7 @@ def write_owl_dir(directory, shape, seed=0):
     torch.manual_seed(seed)
     model = OwlViTForObjectDetection(owl_config(shape)).eval()
     W = SHAPES[shape]["W"]
+    Dq = SHAPES[shape].get("text_W", W)               # the text width = the projection = the query dimension
     g = torch.Generator().manual_seed(1000 + seed)
     rn = lambda *s: torch.randn(*s, generator=g)
     with torch.no_grad():
@@ -233,14 +238,14 @@ def write_owl_dir(directory, shape, seed=0):
         model.owlvit.vision_model.embeddings.position_embedding.weight.copy_(rn(*model.owlvit.vision_model.embeddings.position_embedding.weight.shape) * 0.3)
         model.owlvit.vision_model.embeddings.class_embedding.copy_(rn(W))
         model.owlvit.text_model.embeddings.token_embedding.weight.copy_(rn(*model.owlvit.text_model.embeddings.token_embedding.weight.shape))
-        model.owlvit.text_model.embeddings.position_embedding.weight.copy_(rn(CTX, W) * 0.3)
-        model.owlvit.text_projection.weight.copy_(rn(W, W) / math.sqrt(W))
+        model.owlvit.text_model.embeddings.position_embedding.weight.copy_(rn(CTX, Dq) * 0.3)
+        model.owlvit.text_projection.weight.copy_(rn(Dq, Dq) / math.sqrt(Dq))
         for ln in (model.owlvit.vision_model.pre_layernorm, model.owlvit.vision_model.post_layernorm, model.layer_norm, model.owlvit.text_model.final_layer_norm):
-            ln.weight.copy_(1 + 0.1 * rn(W))
-            ln.bias.copy_(0.1 * rn(W))
+            ln.weight.copy_(1 + 0.1 * rn(ln.weight.shape[0]))
+            ln.bias.copy_(0.1 * rn(ln.weight.shape[0]))
         ch, bh = model.class_head, model.box_head
-        ch.dense0.weight.copy_(rn(W, W) / math.sqrt(W))
-        ch.dense0.bias.copy_(0.1 * rn(W))
+        ch.dense0.weight.copy_(rn(Dq, W) / math.sqrt(W))
+        ch.dense0.bias.copy_(0.1 * rn(Dq))
         ch.logit_shift.weight.copy_(rn(1, W) * (0.5 / math.sqrt(W)))
         ch.logit_shift.bias.fill_(-0.2)
         ch.logit_scale.weight.copy_(rn(1, W) * (1.5 / math.sqrt(W)))
@@ -302,6 +307,132 @@ def hf_forward(model, ids, pix, target):
 def load_hf(directory):
     from transformers import OwlViTForObjectDetection
     return OwlViTForObjectDetection.from_pretrained(str(directory), torch_dtype=torch.float32).eval()
+
+
+# ---- fixtures of the kernel tests at the served shapes (tests/test_owl_shapes_gpu.py runs them, tests/test_owl_host.py checks their premises) -----------
+TOPK_P = (255, 256, 257, 576, 8191)                 # one below / at / one above one trip of the 256 threads, owlvit-base-patch32's, the limit
+TOPK_KINDS = ("distinct", "ties", "nan")
+TIE_VALUES = (0.0, 0.25, 0.5, 0.75, 1.0)            # a saturated sigmoid gives exactly 0.0f and 1.0f
+NAN_BITS = (0x7FC00000, 0xFFC00000, 0x7FC00001, 0x7F800001, 0xFFFFFFFF)          # quiet, negative, with payload, signalling, all ones
+
+
+def topk_ks(P):
+    return sorted({min(k, P) for k in (1, 7, 256, 257, P)})
+
+
+def topk_nan_patches(P):
+    return sorted({0, 255, 256, P - 1} & set(range(P)))
+
+
+def topk_fixture(kind, P):
+    """score fp32 [3, P], boxes fp32 [3, P, 4].
+    distinct: a permutation of P different values per image, the maximum moved to patch 0 / patch 256 (P // 2 where there is none) / patch P - 1.
+    ties:     five values only, so nearly every rank is decided by the lower-patch rule; patch 0 and patch 256 hold the same value where both exist.
+    nan:      image 0 distinct with NaNs (different bit patterns) at patches 0, 255, 256 and P - 1; image 1 all NaN; image 2 ties with a NaN in every
+              seventh patch."""
+    g = np.random.default_rng(P * 10 + TOPK_KINDS.index(kind))
+    boxes = g.uniform(0, 240, (3, P, 4)).astype(np.float32)
+    distinct = np.stack([(g.permutation(P) + 0.5) / (P + 1) for _ in range(3)]).astype(np.float32)
+    for img, at in enumerate((0, 256 if P > 256 else P // 2, P - 1)):
+        top = int(distinct[img].argmax())
+        distinct[img, [at, top]] = distinct[img, [top, at]]
+    ties = np.asarray(TIE_VALUES, dtype=np.float32)[g.integers(0, len(TIE_VALUES), (3, P))]
+    if P > 256:
+        ties[:, 256] = ties[:, 0]
+    if kind == "distinct":
+        return distinct, boxes
+    if kind == "ties":
+        return ties, boxes
+    nan = lambda m: np.resize(np.asarray(NAN_BITS, dtype=np.uint32), m).view(np.float32)
+    score = np.stack([distinct[0], nan(P), ties[2]])
+    where = topk_nan_patches(P)
+    score[0, where] = nan(len(where))
+    score[2, ::7] = nan(len(score[2, ::7]))
+    return score, boxes
+
+
+MERGE_W = (4, 260, 768, 1024, 1280, 1536, 2048)     # MQ_DISPATCH_CH: CH = 1, 2 (one live lane in the second chunk), 3, 4, 6 via case 5, 6 via case 6, 8
+MERGE_NT = ((1, 2), (3, 4))                         # one patch row; 9 rows: not a multiple of the 4 rows of a block
+MERGE_CASES = [(n, T, W) for W in MERGE_W for n, T in MERGE_NT] + [(2, 577, 768)]
+MERGE_CONST = 0.7                                   # the constant patch row's value: not a dyadic number, so its computed mean is a rounded one
+
+
+def merge_fixture(n, T, W):
+    """x fp32 [n T, W] and the two LayerNorms' (weight, bias): random rows of spread 0.3 .. 3 and mean -1 .. 1; image 0's class row has a mean 50 x its
+    spread; the last patch row of the last image is constant where there is more than one patch row (index: merge_const_row)."""
+    g = np.random.default_rng(100 * n + T + W)
+    x = (g.standard_normal((n * T, W)) * g.uniform(0.3, 3.0, (n * T, 1)) + g.uniform(-1, 1, (n * T, 1))).astype(np.float32)
+    z = g.standard_normal(W)
+    x[0] = (0.5 * ((z - z.mean()) / z.std() + 50.0)).astype(np.float32)          # (the sample's own mean and spread: 50 at every W)
+    if n * (T - 1) > 1:
+        x[n * T - 1] = np.float32(MERGE_CONST)
+    pg, lg = ((1 + 0.2 * g.standard_normal(W)).astype(np.float32) for _ in range(2))
+    pb, lb = ((0.2 * g.standard_normal(W)).astype(np.float32) for _ in range(2))
+    return x, pg, pb, lg, lb
+
+
+def merge_const_row(n, T):
+    """the output row of merge_fixture's constant patch row, or None"""
+    return n * (T - 1) - 1 if n * (T - 1) > 1 else None
+
+
+# (n, P, W, Dq, Q, per_image, tie): the query limit at owlvit-base-patch32's and owlvit-large-patch14's widths, and widths ragged against the 64 lanes
+CLASS_CASES = {"base_q8": (2, 61, 768, 512, 8, 0, None), "base_q8_tie": (2, 61, 768, 512, 8, 0, (2, 5)), "large_q8_masked": (2, 61, 1024, 768, 8, 1, None),
+               "ragged": (3, 7, 100, 70, 5, 1, None)}
+
+
+def class_fixture(name):
+    """dict(e, f, t, mask, sw, sb, cw, cb, n, P, W, Dq, Q, per_image, tie) of CLASS_CASES[name].  Row 3 of e is zero (a zero-norm embedding).  The
+    masked case keeps only query 7 in image 0 and only query 0 in image 1.  tie = (a, b): query row b is a copy of query row a."""
+    n, P, W, Dq, Q, per_image, tie = CLASS_CASES[name]
+    g = np.random.default_rng(zlib.crc32(name.encode()))
+    rows = n * P
+    e = g.standard_normal((rows, Dq)).astype(np.float32)
+    e[3] = 0.0
+    f = g.standard_normal((rows, W)).astype(np.float32)
+    t = g.standard_normal((n, Q, Dq) if per_image else (Q, Dq)).astype(np.float32)
+    if tie:
+        t[..., tie[1], :] = t[..., tie[0], :]
+    mask = None
+    if name == "large_q8_masked":
+        mask = np.zeros((n, Q), dtype=np.int32)
+        mask[0, 7] = mask[1, 0] = 1
+    sw, cw = (g.standard_normal(W) / np.sqrt(W)).astype(np.float32), (1.5 * g.standard_normal(W) / np.sqrt(W)).astype(np.float32)
+    return dict(e=e, f=f, t=t, mask=mask, sw=sw, sb=-0.2, cw=cw, cb=0.4, n=n, P=P, W=W, Dq=Dq, Q=Q, per_image=per_image, tie=tie)
+
+
+def class_reference(fx):
+    return class_head_reference(fx["e"], fx["f"], fx["t"], fx["mask"], fx["sw"], np.float32(fx["sb"]), fx["cw"], np.float32(fx["cb"]), fx["P"])
+
+
+def sure_apart_from_twin(ref, twin):
+    """label_sure with query column `twin` (an exact copy of another query) left out: the best logit leads every OTHER query by more than 2 B"""
+    z = np.delete(ref["logits"], twin, axis=1)
+    order = np.sort(z, axis=-1)
+    return order[:, -1] - order[:, -2] > 2 * ref["B_best"]
+
+
+BOX_TARGET = (320, 200)                             # not square: a swapped width and height shows
+BOX_CASES = {"grid24": (2, 24, 768, False), "grid7": (2, 7, 1024, False), "grid3_ragged": (3, 3, 100, False), "grid24_same_rows": (2, 24, 768, True)}
+
+
+def box_fixture(name):
+    """dict(h (bf16 values in fp32) [n P, W], w2 [4, W], b2 [4], n, grid, P, W) of BOX_CASES[name].  same_rows: every row of h is one vector, scaled so
+    that h . w2 stays of order one half: the rows then differ through the grid bias alone, and no sigmoid saturates."""
+    n, grid, W, same = BOX_CASES[name]
+    P = grid * grid
+    g = np.random.default_rng(zlib.crc32(name.encode()))
+    w2 = (2.0 * g.standard_normal((4, W)) / np.sqrt(W)).astype(np.float32)
+    b2 = np.array([0.3, -0.3, 0.2, -0.2], dtype=np.float32)
+    if same:
+        h = np.tile(R.round_bf16((0.25 * np.abs(g.standard_normal((1, W)))).astype(np.float32)), (n * P, 1))
+    else:
+        h = R.round_bf16(np.abs(g.standard_normal((n * P, W))).astype(np.float32))
+    return dict(h=h, w2=w2, b2=b2, n=n, grid=grid, P=P, W=W)
+
+
+# the chain at owlvit-base-patch32's widths: 8 queries, the fourth empty (masked), the others from the tiny vocabulary
+CHAIN_QUERIES = [QUERY_SHORT, "a cat", "the dog", "", "red", QUERY_FULL, "cat on the dog", "a red dog on a cat"]
 
 
 def fake_detection(pixels_u8, P=9):

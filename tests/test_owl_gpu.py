@@ -198,7 +198,7 @@ def test_topk(k):
 def dirs(tmp_path_factory):
     root = tmp_path_factory.mktemp("owl")
     out = {}
-    for shape in O.SHAPES:
+    for shape in O.TOY_SHAPES:
         out[shape] = str(root / "hf" / "google" / ("owlvit-base-patch32" if shape == "g5" else "owlvit-" + shape))
         O.write_owl_dir(out[shape], shape, seed=TOWER_SEED)
     out["root"] = str(root)

@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import owl_ref as O  # noqa: E402
 import test_owl_gpu as G  # noqa: E402  (the measured tolerances and the seeds of the tower tests)
+import test_owl_shapes_gpu as S  # noqa: E402  (... and of the chain at owlvit-base-patch32's widths)
 from marqo_amd import _lib as L  # noqa: E402
 from marqo_amd.engine import archs  # noqa: E402
 from marqo_amd.engine.hf_clip import load_tokenizer  # noqa: E402
@@ -31,7 +32,7 @@ def oracle(tmp_path_factory):
     """per shape: the checkpoint directory, the fp32 model, and its outputs on the tower tests' images for both queries"""
     root = tmp_path_factory.mktemp("owl_host")
     out = {}
-    for shape in O.SHAPES:
+    for shape in O.TOY_SHAPES:
         d = str(root / shape)
         O.write_owl_dir(d, shape, seed=G.TOWER_SEED)
         model, tok = O.load_hf(d), load_tokenizer(d, O.CTX)
@@ -86,6 +87,131 @@ def test_topk_reference_ties_and_clamp():
     b = np.arange(16, dtype=np.float32).reshape(1, 4, 4)
     ts, tb, tp = O.topk_reference(s, b, 9)
     assert tp.tolist() == [[1, 2, 0, 3]] and ts.tolist() == [[np.float32(0.9), np.float32(0.9), np.float32(0.2), np.float32(0.1)]] and tb[0, 0].tolist() == [4, 5, 6, 7]
+
+
+# ---- premises of the fixtures of tests/test_owl_shapes_gpu.py --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("grid", [24, 48, 60])
+def test_box_bias_at_the_served_grids(grid):
+    assert {a.grid for a in archs.OWL_ARCHS.values()} == {24, 48, 60}
+    got = box_bias(grid)
+    assert got.dtype == O.torch.float32 and tuple(got.shape) == (grid * grid, 4)
+    assert np.array_equal(got.numpy().astype(np.float64), O.box_bias_reference(grid)), "the grid bias is the model's float32 constant, exactly"
+
+
+@pytest.mark.parametrize("P", O.TOPK_P)
+def test_topk_fixtures_hold_what_they_promise(P):
+    d, _ = O.topk_fixture("distinct", P)
+    assert all(len(set(row.tolist())) == P for row in d), "distinct scores"
+    assert tuple(d.argmax(1)) == (0, 256 if P > 256 else P // 2, P - 1)
+    t, _ = O.topk_fixture("ties", P)
+    assert set(np.unique(t).tolist()) == set(O.TIE_VALUES) and np.float32(1.0) in t and np.float32(0.0) in t
+    assert len(O.topk_ks(P)) >= 3 and O.topk_ks(P)[-1] == P
+    if P > 256:
+        for row in t:       # a tie between two threads' patches on either side of the first trip, and one within a thread (a and a + 256)
+            assert any(row[a] == row[b] for a in range(0, 256, 37) for b in range(256, P)), "no tie a < 256 <= b"
+            assert row[0] == row[256], "no tie between a and a + 256"
+    s, _ = O.topk_fixture("nan", P)
+    assert sorted(np.nonzero(np.isnan(s[0]))[0].tolist()) == O.topk_nan_patches(P) and np.isnan(s[1]).all() and np.isnan(s[2]).sum() == len(range(0, P, 7))
+    assert len(set(s[1].view(np.uint32)[:5].tolist())) == 5, "NaNs of different bit patterns"
+    rs, _, rp = O.topk_reference(s, np.zeros((3, P, 4), np.float32), P)
+    assert rp[0, -len(O.topk_nan_patches(P)):].tolist() == O.topk_nan_patches(P) and rp[1].tolist() == list(range(P))
+    assert not np.isnan(rs[0, :P - len(O.topk_nan_patches(P))]).any()
+
+
+@pytest.mark.parametrize("n,T,W", O.MERGE_CASES)
+def test_merge_budget_of_the_offset_and_the_constant_row(n, T, W):
+    """The class row of image 0 has a mean 50 x its spread: its LayerNorm's budget carries the mean's error c = D u A with A = 50 sigma, so
+    B_c ~ |g| 50 D u (1e-4 at D = 40), and every row of image 0 inherits it through |p| B_c.
+
+    The constant patch row x = a has d = 0 and sigma' = sqrt(eps), so rowops_ref.reference_ln gives it exactly
+        B_p,j = |pg_j| D u |a| / sqrt(eps) + 2 u |pb_j|                 D = ceil(W / 64) + 8
+    This is no slack.  The kernel's mean of W copies of a rounded a is off by up to D u |a|; EVERY deviation of the row is that one error, and
+    rstd = 1 / sqrt(eps) = 316 multiplies it: p_j = pb_j + pg_j s with one s, |s| <= D u |a| / sqrt(eps) (8e-4 at W = 2048, a = 0.7).  The product
+    with the class row scales it by |c_j| (up to ~3) and the last LayerNorm by |lg_j| / sigma'(m) (2 + |d_j| / sigma'(m)), where m = pb c has a
+    spread of only ~0.2 (the bias's): about 1e-2 at W = 768 and 4e-2 at W = 2048, for outputs whose spread is 1.  So the budget of that row cannot be
+    1e-3 max|ln bias| (6e-4) unless |a| is below 0.03; it has to be what the two-pass algorithm's amplification makes it.  Asserted: B_p equals the
+    closed form, the row's budget is finite, below 5 % of the spread of the row's own output (a row that took another row's statistics, or skipped a
+    LayerNorm, is off by the spread itself), and within the closed form carried through the last LayerNorm's push."""
+    x, pg, pb, lg, lb = O.merge_fixture(n, T, W)
+    f, B = O.merge_ln_reference(x, n, T, pg, pb, lg, lb, 1e-5)
+    assert np.isfinite(B).all() and (B > 0).all()
+    x0 = x[0].astype(np.float64)
+    assert 49 * x0.std() < abs(x0.mean()) < 51 * x0.std(),"image 0's class row: a mean of 50 x the spread"
+    assert B[:T - 1].max() < 0.01 * f[:T - 1].std(), "the offset class row leaves its image a budget of under 1 % of the outputs' spread"
+    r = O.merge_const_row(n, T)
+    if r is None:
+        return
+    a, D, se = float(np.float32(O.MERGE_CONST)), int(np.ceil(W / 64)) + 8, np.sqrt(1e-5)
+    assert (x[n * T - 1] == np.float32(O.MERGE_CONST)).all()
+    _, Bp = O._ln(x[n * T - 1:], pg, pb, 1e-5)
+    lead = np.abs(pg.astype(np.float64)) * D * O.U * a / se + 2 * O.U * np.abs(pb.astype(np.float64))
+    assert np.allclose(Bp[0], lead, rtol=1e-9, atol=0)
+    assert B[r].max() < 0.05 * f[r].std()
+    # carried through: e_j <= |c_j| lead_j + (|pb_j| + lead_j) B_c,j + u |m_j|, then owl_ref's push of the last LayerNorm
+    c, Bc = O._ln(x[(n - 1) * T:(n - 1) * T + 1], pg, pb, 1e-5)
+    m = pb.astype(np.float64) * c[0]
+    e = np.abs(c[0]) * lead + (np.abs(pb) + lead) * Bc[0] + O.U * np.abs(m)
+    _, Bm = O._ln(m[None], lg, lb, 1e-5)
+    bound = 1.01 * Bm[0] + O._ln_push(m[None], lg.astype(np.float64), e[None], 1e-5)[0]
+    assert (B[r] <= bound * (1 + 1e-9)).all() and (B[r] >= 0.99 * bound).all(), "the constant row's budget is the derived one"
+
+
+@pytest.mark.parametrize("name", list(O.CLASS_CASES))
+def test_class_fixtures_decide_their_labels(name):
+    fx = O.class_fixture(name)
+    ref = O.class_reference(fx)
+    rows = fx["n"] * fx["P"]
+    assert (ref["pre"] < -0.5).any() and (ref["pre"] > 0.5).any(), "the fixture must reach both ELU branches"
+    assert not fx["e"][3].any() and np.isfinite(ref["best"][3]), "the zero-norm embedding row"
+    sure = ref["label_sure"] if fx["tie"] is None else O.sure_apart_from_twin(ref, fx["tie"][1])
+    assert sure.sum() * 4 >= rows * 3, "three quarters of the rows must have a sure label"
+    assert fx["Q"] == 8 or (fx["W"] % 64 and fx["Dq"] % 64), "the query limit, or widths ragged against the 64 lanes"
+    if fx["mask"] is not None:
+        assert (ref["label"][:fx["P"]] == 7).all() and (ref["label"][fx["P"]:] == 0).all() and ref["label_sure"].all()
+    if fx["tie"] is not None:
+        a, b = fx["tie"]
+        assert np.array_equal(ref["logits"][:, a], ref["logits"][:, b]) and not (ref["label"] == b).any()
+        assert (sure & (ref["label"] == a)).sum() >= rows // 8, "rows that the tied pair wins, surely ahead of the other six"
+    else:
+        assert len(np.unique(ref["label"][ref["label_sure"]])) >= min(fx["Q"], 5) or fx["mask"] is not None, "several queries win somewhere"
+
+
+def test_box_fixture_of_equal_rows_tells_every_patch_apart():
+    fx = O.box_fixture("grid24_same_rows")
+    P = fx["P"]
+    assert (fx["h"] == fx["h"][0]).all()
+    pred, boxes, B = O.box_head_reference(fx["h"], fx["w2"], fx["b2"], box_bias(24).numpy(), P, O.BOX_TARGET)
+    assert np.array_equal(boxes[:P], boxes[P:])
+    b = boxes[:P]
+    assert (np.abs(b[1:] - b[:-1]).max(-1) > 100 * B.max()).all(), "neighbouring patches differ by more than 100 x the budget"
+    apart = np.abs(b[:, None, :] - b[None, :, :]).max(-1) + np.diag(np.full(P, np.inf))
+    assert apart.min() > 100 * B.max(), "so do any two patches: no mix-up of bias rows fits the budget"
+    assert pred.min() > 0.01 and pred.max() < 0.9999, "no sigmoid saturates"
+
+
+@pytest.fixture(scope="module")
+def chain_oracle(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("owl_chain") / S.CHAIN_SHAPE)
+    O.write_owl_dir(d, S.CHAIN_SHAPE, seed=0)
+    model, tok = O.load_hf(d), load_tokenizer(d, O.CTX)
+    stub = types.SimpleNamespace(arch=archs.owl_arch_from_hf_config(json.load(open(os.path.join(d, "config.json")))), tokenizer=tok)
+    live = [i for i, q in enumerate(O.CHAIN_QUERIES) if q]
+    ids = np.zeros((len(O.CHAIN_QUERIES), O.CTX), dtype=np.int64)
+    ids[live] = OwlTower.query_ids(stub, [O.CHAIN_QUERIES[i] for i in live])
+    return stub, O.hf_forward(model, ids, O.pixel_values(S.chain_images(), O.SHAPES[S.CHAIN_SHAPE]["image"]), TARGET)
+
+
+def test_chain_shape_is_base_patch32s_and_the_oracle_decides_both_images(chain_oracle):
+    stub, r = chain_oracle
+    a, served = stub.arch, archs.OWL_ARCHS["google/owlvit-base-patch32"]
+    assert (a.image_size, a.patch_size, a.width, a.heads, a.mlp_dim, a.text_width, a.query_dim, a.ctx, a.tokens, a.layers) == \
+        (served.image_size, served.patch_size, served.width, served.heads, served.mlp_dim, served.text_width, served.query_dim, served.ctx, 577, 1)
+    assert r["logits"].shape == (2, 576, 8) and (r["logits"][..., 3] < -1e30).all(), "the empty query is masked by the oracle too"
+    assert len(np.unique(r["logits"].argmax(-1))) >= 4, "several queries win somewhere"
+    assert r["best"].std() >= 0.5, "the reference logits must spread"
+    srt = np.sort(r["best"], axis=1)
+    assert S.LOGIT_TOL < r["best"].std() / 4
+    assert (srt[:, -1] - srt[:, -2] > 2 * S.LOGIT_TOL).all(), srt[:, -1] - srt[:, -2]
 
 
 # ---- names, attributes, checkpoints, the query limit ---------------------------------------------------------------------------------------------
