@@ -1267,7 +1267,7 @@ int mq_encode_modernbert(const mq_modernbert_cfg* cfg, const mq_modernbert_weigh
  *                   for mq_layernorm; writes bf16 and / or fp32 (d_out_f32 may be d_x when there is no row index).  W % 4 == 0, W <= 2048.
  *   mq_qk_norm_rope: in place on the q and k parts of the layout above (V is not touched): per head, RMSNorm over head_dim with d_q_g / d_k_g (fp32
  *                   [head_dim]; both NULL: no norm), then rotary positions in rotate_half form, angle = float(t) * d_inv_freq[i] with t the row's position
- *                   in its sequence, exactly as mq_rope forms it.  fp32 from the bf16 input to the one rounding of the bf16 output.  head_dim 64 or 128.
+ *                   in its sequence, exactly as mq_rope forms it.  fp32 from the bf16 input to the one rounding of the bf16 output.  head_dim 64, 128 or 256.
  *   mq_encode_qwen: token gather -> `layers` blocks  x += Wo(attn(qk_norm_rope(Wqkv(rmsnorm(x))))) ; x += Wdown(up * silu(gate)) with
  *                   (up | gate) = Wug(rmsnorm(x))  -> final RMSNorm -> pooling (+ L2), on packed sequences like mq_encode_bert; fp32 residual stream,
  *                   bf16 GEMM operands.  MQ_POOL_LAST: the last row of every sequence, normalised alone; MQ_POOL_MEAN: every row is normalised, then
@@ -1316,6 +1316,77 @@ int mq_qk_norm_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixe
 size_t mq_qwen_workspace_bytes(const mq_qwen_cfg* cfg, int64_t rows, int64_t nseq);
 int mq_encode_qwen(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                    int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- EmbeddingGemma text embedders: 256-wide-head grouped-query band attention and the tower (csrc/attention_gqa256.hip, csrc/gemma.hip;
+ * engine/gemma.py) ------------------------------------------------------------------------------------------------------------------------------------
+ * transformers' Gemma3TextModel with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its fine-tunes): blocks with
+ * four RMSNorms (one in front of and one behind each sub-layer), 256-wide heads with fewer K/V heads than query heads, per-head q / k RMSNorm, rotary
+ * positions with one base per layer kind, a gated tanh-GELU MLP, no causal mask, and `sliding` layers that attend only the keys within half_window
+ * positions.  Additions to ABI 15: nothing above changes but mq_qk_norm_rope, which now also takes head_dim 256; the structs and entry points below are
+ * new.  Every entry point judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on
+ * `stream` and allocates nothing.
+ *
+ *   mq_attention_gqa_band: mq_attention_gqa's layout — d_qkv bf16 [rows, (q_heads + 2 kv_heads) head_dim] = (q | k | v), d_out bf16 [rows, q_heads
+ *                   head_dim], query head h reads K/V head h / (q_heads / kv_heads), sequences packed or fixed-length, max_len <= 8192 — at head_dim 256,
+ *                   unmasked and bidirectional.  half_window == 0: every key of the sequence; half_window = hw > 0: query i sees keys j with
+ *                   |i - j| <= hw.  `scale` is the softmax scale (> 0; Gemma: query_pre_attn_scalar ** -0.5).  One workgroup of 8 waves per (sequence,
+ *                   K/V head, 64-query slice) stages the 64-key tiles the slice's band reaches, two tiles (128 KiB of LDS) at a time, once per round
+ *                   for every query head that reads them; a 16-query block visits only the tiles that cut its own band.  Compiler report (gfx950):
+ *                   213 VGPRs, 68 SGPRs, no scratch, no static LDS.
+ *   mq_rmsnorm_add_norm: d_x fp32 [rows, W] += rmsnorm(d_o bf16 [rows, W]; d_g_post), then — when d_g_next and d_h are given (together or not at all) —
+ *                   d_h bf16 [rows, W] = rmsnorm(d_x; d_g_next).  fp32 statistics, mq_rmsnorm's order of operations.  W % 4 == 0, W <= 2048.
+ *   mq_glu_tanh:    mq_glu's (up | gate) layout, in place: buf[:, :F] = up * gelu_tanh(gate), gelu_tanh(x) = x / (1 + exp(-2 sqrt(2 / pi) (x + 0.044715
+ *                   x^3))) (transformers' gelu_pytorch_tanh; not the erf form of MQ_ACT_GELU).  F % 8 == 0.
+ *   mq_encode_gemma: token gather * sqrt(width) -> `layers` blocks  x += norm(Wo(attn(qk_norm_rope(Wqkv(norm(x)))))) ; x += norm(Wdown(up *
+ *                   gelu_tanh(gate))) with (up | gate) = Wug(norm(x))  -> final RMSNorm -> mq_pool (MQ_POOL_MEAN or MQ_POOL_CLS) (+ L2), on packed
+ *                   sequences like mq_encode_bert; fp32 residual stream, bf16 GEMM operands.  Every norm weight is the checkpoint's 1 + w.  width <= 2048
+ *                   (a multiple of 64), head_dim 256, mlp_dim % 64 == 0, max_pos <= 8192.  d_out fp32 [nseq, width]. */
+typedef struct mq_gemma_layer {
+    const float* input_norm_g;      /* fp32 [W]  1 + input_layernorm */
+    const void*  qkv_w;             /* bf16 [(Q + 2 KV) hd, W]  rows: q_proj | k_proj | v_proj */
+    const float* q_norm_g;          /* fp32 [hd]  1 + q_norm */
+    const float* k_norm_g;          /* fp32 [hd]  1 + k_norm */
+    const void*  out_w;             /* bf16 [W, Q hd]  o_proj */
+    const float* post_attn_norm_g;  /* fp32 [W]  1 + post_attention_layernorm */
+    const float* pre_ffn_norm_g;    /* fp32 [W]  1 + pre_feedforward_layernorm */
+    const void*  ug_w;              /* bf16 [2F, W]  rows: up_proj | gate_proj (mq_glu's order) */
+    const void*  down_w;            /* bf16 [W, F]  down_proj */
+    const float* post_ffn_norm_g;   /* fp32 [W]  1 + post_feedforward_layernorm */
+    int32_t sliding;                /* 1: sliding_attention (cfg.half_window, d_inv_freq_local); 0: full_attention (d_inv_freq_global) */
+    int32_t reserved;
+} mq_gemma_layer;
+
+typedef struct mq_gemma_weights {
+    const float* tok_emb;            /* fp32 [vocab, W] */
+    const float* final_norm_g;       /* fp32 [W]  1 + norm */
+    const float* d_inv_freq_global;  /* fp32 [hd / 2]: rope_theta ^ -(2 i / hd) */
+    const float* d_inv_freq_local;   /* fp32 [hd / 2]: rope_local_base_freq ^ -(2 i / hd) */
+    const mq_gemma_layer* layers;    /* host array, `layers` entries */
+} mq_gemma_weights;
+
+typedef struct mq_gemma_cfg {
+    int32_t width;        /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t q_heads;      /* Q */
+    int32_t kv_heads;     /* KV, divides Q */
+    int32_t head_dim;     /* hd: 256; Q hd need not be W */
+    int32_t mlp_dim;      /* F, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;      /* longest sequence served (<= 8192) */
+    int32_t half_window;  /* of the sliding layers: config sliding_window / 2 */
+    int32_t pool;         /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    float   rms_eps;
+    float   attn_scale;   /* query_pre_attn_scalar ^ -0.5 */
+} mq_gemma_cfg;
+
+int mq_attention_gqa_band(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len, int32_t q_heads,
+                          int32_t kv_heads, int32_t head_dim, int32_t half_window, float scale, void* stream);
+int mq_rmsnorm_add_norm(float* d_x, const void* d_o, const float* d_g_post, const float* d_g_next, void* d_h, int64_t rows, int32_t W, float eps,
+                        void* stream);
+int mq_glu_tanh(void* d_buf, int64_t rows, int32_t F, void* stream);
+size_t mq_gemma_workspace_bytes(const mq_gemma_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_gemma(const mq_gemma_cfg* cfg, const mq_gemma_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
+                    int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

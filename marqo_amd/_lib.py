@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -222,6 +222,22 @@ class QwenCfg(C.Structure):
                 ("vocab", C.c_int32), ("max_pos", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float)]
 
 
+class GemmaLayer(C.Structure):
+    """mq_gemma_layer: one EmbeddingGemma block (csrc/gemma.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("input_norm_g", "qkv_w", "q_norm_g", "k_norm_g", "out_w", "post_attn_norm_g", "pre_ffn_norm_g", "ug_w", "down_w",
+                                          "post_ffn_norm_g")] + [("sliding", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GemmaWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("final_norm_g", C.c_void_p), ("d_inv_freq_global", C.c_void_p), ("d_inv_freq_local", C.c_void_p),
+                ("layers", C.POINTER(GemmaLayer))]
+
+
+class GemmaCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
+                ("vocab", C.c_int32), ("max_pos", C.c_int32), ("half_window", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float), ("attn_scale", C.c_float)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -380,6 +396,13 @@ _SIGNATURES = {
     "mq_qk_norm_rope": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P]),
     "mq_qwen_workspace_bytes": (C.c_size_t, [C.POINTER(QwenCfg), C.c_int64, C.c_int64]),
     "mq_encode_qwen": (C.c_int, [C.POINTER(QwenCfg), C.POINTER(QwenWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # EmbeddingGemma text embedders: 256-wide grouped-query band attention, the fused post-norm / add / pre-norm, the tanh-GELU gated product, the tower
+    # (csrc/attention_gqa256.hip, csrc/gemma.hip; engine/gemma.py)
+    "mq_attention_gqa_band": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_rmsnorm_add_norm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
+    "mq_glu_tanh": (C.c_int, [_P, C.c_int64, C.c_int32, _P]),
+    "mq_gemma_workspace_bytes": (C.c_size_t, [C.POINTER(GemmaCfg), C.c_int64, C.c_int64]),
+    "mq_encode_gemma": (C.c_int, [C.POINTER(GemmaCfg), C.POINTER(GemmaWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

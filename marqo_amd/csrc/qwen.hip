@@ -61,7 +61,7 @@ template <int HD, bool NORM>
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ qkv, const int32_t* __restrict__ cu, int fixed_len, int q_heads, int kv_heads,
                                                            const float* __restrict__ q_g, const float* __restrict__ k_g, float eps,
                                                            const float* __restrict__ inv_freq) {
-    constexpr int LPH = HD / 4;            // lanes per head (16 or 32)
+    constexpr int LPH = HD / 4;            // lanes per head (16, 32 or 64)
     constexpr int UPB = 256 / LPH;         // (row, head) units per block and step
     const int row0 = cu ? cu[blockIdx.x] : blockIdx.x * fixed_len;
     const int len = cu ? cu[blockIdx.x + 1] - row0 : fixed_len;
@@ -155,7 +155,7 @@ extern "C" int mq_rmsnorm(const float* d_x, const int32_t* d_row_idx, const floa
 extern "C" int mq_qk_norm_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
                                const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, void* stream) {
     MQ_CHECK_ARG(d_qkv && d_inv_freq, "mq_qk_norm_rope: null pointer");
-    MQ_CHECK_ARG(head_dim == 64 || head_dim == 128, "mq_qk_norm_rope: head_dim %d unsupported (64 or 128)", head_dim);
+    MQ_CHECK_ARG(head_dim == 64 || head_dim == 128 || head_dim == 256, "mq_qk_norm_rope: head_dim %d unsupported (64, 128 or 256)", head_dim);
     MQ_CHECK_ARG(q_heads >= 1 && kv_heads >= 1 && q_heads <= 1024 && kv_heads <= q_heads, "mq_qk_norm_rope: q_heads %d / kv_heads %d", q_heads, kv_heads);
     MQ_CHECK_ARG((d_q_g == nullptr) == (d_k_g == nullptr), "mq_qk_norm_rope: q and k norm weights come together or not at all");
     MQ_CHECK_ARG(d_cu || fixed_len > 0, "mq_qk_norm_rope: need fixed_len or cu_seqlens");
@@ -168,6 +168,9 @@ extern "C" int mq_qk_norm_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, i
     if (head_dim == 64) {
         if (d_q_g) hipLaunchKernelGGL((qk_norm_rope_kernel<64, true>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
         else hipLaunchKernelGGL((qk_norm_rope_kernel<64, false>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
+    } else if (head_dim == 256) {   // (EmbeddingGemma: one wave64 per (row, head))
+        if (d_q_g) hipLaunchKernelGGL((qk_norm_rope_kernel<256, true>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
+        else hipLaunchKernelGGL((qk_norm_rope_kernel<256, false>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
     } else {
         if (d_q_g) hipLaunchKernelGGL((qk_norm_rope_kernel<128, true>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
         else hipLaunchKernelGGL((qk_norm_rope_kernel<128, false>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);

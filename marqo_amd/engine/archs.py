@@ -370,6 +370,109 @@ def qwen_arch_from_hf_config(cfg: dict) -> QwenArch:
 
 
 @dataclass(frozen=True)
+class GemmaArch:
+    """transformers' Gemma3TextModel with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its fine-tunes) as the
+    engine runs it: blocks with an RMSNorm in front of and behind each sub-layer (weights applied as 1 + w), `kv_heads` K/V heads of width 256 shared by
+    `heads` query heads, per-head q / k RMSNorm, rotary positions with one base per layer kind, a gated tanh-GELU MLP, the token table scaled by
+    sqrt(width), no causal mask; `sliding` layers attend only the keys within half_window positions (inclusive on both sides)."""
+    vocab: int = 262144
+    max_pos: int = 2048
+    width: int = 768
+    layers: int = 24
+    heads: int = 3
+    kv_heads: int = 1
+    head_dim: int = 256
+    mlp_dim: int = 1152
+    rms_eps: float = 1e-6
+    sliding: Tuple[bool, ...] = ()        # per layer: True = sliding_attention, False = full_attention
+    half_window: int = 256
+    theta_global: float = 1000000.0
+    theta_local: float = 10000.0
+    query_pre_attn_scalar: float = 256.0
+
+    @property
+    def attn_scale(self) -> float:
+        return float(self.query_pre_attn_scalar) ** -0.5
+
+    def inv_freq(self, local: bool):
+        """[head_dim / 2] inverse frequencies as transformers' default rope initialisation builds them: base^-(2i/d)"""
+        import torch
+        d = self.head_dim
+        base = self.theta_local if local else self.theta_global
+        return 1.0 / (base ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F, A = tokens, self.width, self.mlp_dim, self.heads * self.head_dim
+        full = 2 * T * W * (A + 2 * self.kv_heads * self.head_dim) + 2 * T * A * W + 2 * 3 * T * W * F
+        attn = sum(4 * T * min(T, 2 * self.half_window + 1) * A if s else 4 * T * T * A for s in self.sliding)
+        return (self.layers * full + attn) / 1e9
+
+
+def gemma_arch_from_hf_config(cfg: dict) -> GemmaArch:
+    """A local EmbeddingGemma `config.json` (model_type "gemma3_text") -> GemmaArch.  The rotary bases come from the per-layer-type `rope_parameters`
+    {full_attention, sliding_attention}.rope_theta of newer files, else from `rope_theta` / `rope_local_base_freq`, else 1e6 / 1e4; the layer kinds from
+    `layer_types`, else from `sliding_window_pattern` (layer i is full when (i + 1) % pattern == 0, pattern 6 when absent).
+
+    The window: the file says `sliding_window` (512 for the served checkpoint); transformers' Gemma3TextConfig turns that into sliding_window // 2 + 1 when
+    use_bidirectional_attention is set and masks |i - j| < that, so half_window = sliding_window // 2 (256), inclusive.
+
+    Refused, each by the name of its key: use_bidirectional_attention false or absent (the causal Gemma3 language models are not embedders), a non-null
+    attn_logit_softcapping, rope_scaling or a non-default rope_type, head_dim other than 256, hidden_activation other than gelu_pytorch_tanh,
+    max_position_embeddings above 8192, hidden_size above 2048."""
+    mtype = cfg.get("model_type")
+    if mtype != "gemma3_text":
+        raise KeyError(f"model_type={mtype} is not a Gemma3 text model")
+    if not cfg.get("use_bidirectional_attention", False):
+        raise KeyError(f"use_bidirectional_attention={cfg.get('use_bidirectional_attention')} unsupported (the causal Gemma3 language models are not "
+                       f"embedders: EmbeddingGemma checkpoints set it to true)")
+    if cfg.get("attn_logit_softcapping") is not None:
+        raise KeyError(f"attn_logit_softcapping={cfg.get('attn_logit_softcapping')} unsupported (null only)")
+    act = cfg.get("hidden_activation", cfg.get("hidden_act", "gelu_pytorch_tanh"))
+    if act != "gelu_pytorch_tanh":
+        raise KeyError(f"hidden_activation={act} unsupported (gelu_pytorch_tanh only)")
+    if cfg.get("rope_scaling"):
+        raise KeyError(f"rope_scaling={cfg.get('rope_scaling')} unsupported")
+    rp = cfg.get("rope_parameters") or {}
+    thetas = {}
+    for kind, old, default in (("full_attention", "rope_theta", 1000000.0), ("sliding_attention", "rope_local_base_freq", 10000.0)):
+        sub = rp.get(kind) or {}
+        rtype = sub.get("rope_type", sub.get("type", "default"))
+        if rtype != "default" or sub.get("factor") is not None:
+            raise KeyError(f"rope_parameters[{kind}].rope_type={rtype} unsupported (default, without scaling, only)")
+        thetas[kind] = float(sub.get("rope_theta", cfg.get(old, default)))
+    if rp.get("rope_type", rp.get("type", "default")) != "default" or rp.get("factor") is not None:
+        raise KeyError(f"rope_parameters.rope_type={rp.get('rope_type', rp.get('type'))} unsupported (default, without scaling, only)")
+    W, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    kv = int(cfg.get("num_key_value_heads") or heads)
+    if heads < 1 or kv < 1 or heads % kv:
+        raise KeyError(f"num_attention_heads={heads} must be a multiple of num_key_value_heads={kv}")
+    hd = int(cfg.get("head_dim") or 256)
+    if hd != 256:
+        raise KeyError(f"head_dim={hd} unsupported (256 only)")
+    if W > 2048 or W % 64:
+        raise KeyError(f"hidden_size={W} unsupported (a multiple of 64 up to 2048)")
+    F = int(cfg["intermediate_size"])
+    if F % 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    max_pos = int(cfg.get("max_position_embeddings", 2048))
+    if max_pos > 8192:
+        raise KeyError(f"max_position_embeddings={max_pos} unsupported (at most 8192)")
+    kinds = cfg.get("layer_types")
+    if kinds is None:
+        n = int(cfg.get("sliding_window_pattern", 6))
+        kinds = ["sliding_attention" if (i + 1) % n else "full_attention" for i in range(layers)]
+    if len(kinds) != layers or any(k not in ("full_attention", "sliding_attention") for k in kinds):
+        raise KeyError(f"layer_types={kinds} must name full_attention / sliding_attention for each of the {layers} layers")
+    sw = cfg.get("sliding_window", 4096)
+    if any(k == "sliding_attention" for k in kinds) and (not isinstance(sw, int) or sw < 2):
+        raise KeyError(f"sliding_window={sw} unsupported (an integer >= 2)")
+    return GemmaArch(vocab=int(cfg["vocab_size"]), max_pos=max_pos, width=W, layers=layers, heads=heads, kv_heads=kv, head_dim=hd, mlp_dim=F,
+                     rms_eps=float(cfg.get("rms_norm_eps", 1e-6)), sliding=tuple(k == "sliding_attention" for k in kinds),
+                     half_window=int(sw) // 2 if isinstance(sw, int) else 0, theta_global=thetas["full_attention"],
+                     theta_local=thetas["sliding_attention"], query_pre_attn_scalar=float(cfg.get("query_pre_attn_scalar", 256)))
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -641,13 +744,15 @@ STELLA_EN_400M = BertArch(vocab=30528, max_pos=8192, width=1024, layers=24, head
 HF_BERT_ARCHS["Marqo/dunzhang-stella_en_400M_v5"] = STELLA_EN_400M
 
 
-def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch]:
+def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch]:
     """A local HF `config.json` -> the arch of the text encoder the `hf` loader builds.  model_type bert, or xlm-roberta / roberta (the same encoder
     with the position ids shifted by padding_idx + 1: the multilingual-e5 family), mpnet and `new` give a BertArch (engine/towers.py::BertTower);
     model_type modernbert gives a ModernBertArch (engine/modernbert.py::ModernBertTower) — callers that can only run a BertArch (the cross-encoders of
     engine/rerank.py, which select their model types before they call) must not pass one through; model_type qwen3 / qwen2 gives a QwenArch
-    (engine/qwen.py::QwenTower) under the same rule.  Anything else: KeyError."""
+    (engine/qwen.py::QwenTower) and model_type gemma3_text a GemmaArch (engine/gemma.py::GemmaTower) under the same rule.  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
+    if mtype == "gemma3_text":   # transformers Gemma3TextModel with bidirectional attention: EmbeddingGemma (engine/gemma.py::GemmaTower)
+        return gemma_arch_from_hf_config(cfg)
     if mtype in ("qwen3", "qwen2"):   # transformers Qwen3Model / Qwen2Model: decoder-style embedders (engine/qwen.py)
         return qwen_arch_from_hf_config(cfg)
     if mtype == "modernbert":   # transformers ModernBertModel: its own arch and tower (engine/modernbert.py)

@@ -456,3 +456,32 @@ def qwen_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
         out[p + "mlp.up_gate.weight"] = torch.cat([f32(p + "mlp.up_proj.weight", (F, W)), f32(p + "mlp.gate_proj.weight", (F, W))], 0)
         out[p + "mlp.down_proj.weight"] = f32(p + "mlp.down_proj.weight", (W, F))
     return out
+
+
+def gemma_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' Gemma3TextModel tensors (with or without a `model.` prefix; `lm_head.*` is ignored) -> the fp32 tensors the tower hands to the
+    kernels.  Every norm weight (the four of each block, q_norm, k_norm, the final one) comes back as 1 + w: Gemma3RMSNorm multiplies by (1 + weight), the
+    kernels by their weight.  Per layer the three projections are fused into `layers.N.self_attn.qkv.weight` [(Q + 2 KV) hd, W] = rows q_proj | k_proj |
+    v_proj and the MLP's two input projections into `layers.N.mlp.up_gate.weight` [2F, W] = rows up_proj | gate_proj — mq_glu_tanh computes
+    up * gelu_tanh(gate) from (up | gate), the module down_proj(gelu_tanh(gate_proj(x)) * up_proj(x))."""
+    if "embed_tokens.weight" not in sd and "model.embed_tokens.weight" in sd:
+        sd = {k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")}
+    W, F, hd = arch.width, arch.mlp_dim, arch.head_dim
+    A, KVW = arch.heads * hd, arch.kv_heads * hd
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    norm = lambda k, shape: 1.0 + f32(k, shape)
+    if any(k.endswith(".bias") and k.startswith("layers.") for k in sd):
+        raise ValueError("the Gemma tower runs bias-free blocks; this checkpoint carries bias tensors")
+    out = {"embed_tokens.weight": f32("embed_tokens.weight", (arch.vocab, W)), "norm.weight": norm("norm.weight", (W,))}
+    for l in range(arch.layers):
+        p = f"layers.{l}."
+        a = p + "self_attn."
+        for n in ("input_layernorm", "post_attention_layernorm", "pre_feedforward_layernorm", "post_feedforward_layernorm"):
+            out[p + n + ".weight"] = norm(p + n + ".weight", (W,))
+        out[a + "qkv.weight"] = torch.cat([f32(a + "q_proj.weight", (A, W)), f32(a + "k_proj.weight", (KVW, W)), f32(a + "v_proj.weight", (KVW, W))], 0)
+        out[a + "q_norm.weight"] = norm(a + "q_norm.weight", (hd,))
+        out[a + "k_norm.weight"] = norm(a + "k_norm.weight", (hd,))
+        out[a + "o_proj.weight"] = f32(a + "o_proj.weight", (W, A))
+        out[p + "mlp.up_gate.weight"] = torch.cat([f32(p + "mlp.up_proj.weight", (F, W)), f32(p + "mlp.gate_proj.weight", (F, W))], 0)
+        out[p + "mlp.down_proj.weight"] = f32(p + "mlp.down_proj.weight", (W, F))
+    return out

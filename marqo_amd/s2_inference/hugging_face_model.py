@@ -127,6 +127,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             if isinstance(arch, archs.QwenArch):
                 self._load_qwen(directory, arch, cfg, sd)
                 return
+            if isinstance(arch, archs.GemmaArch):
+                self._load_gemma(directory, arch, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -263,6 +266,68 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
         self._pooling_func = pooling
         self._device_tokenizer = None   # (the GPU byte-level BPE tokeniser does not implement this family's added-token handling)
+
+    # sentence-transformers Dense module directories (relative to the checkpoint) to apply behind the pooling: set by the `sbert` loader for an
+    # EmbeddingGemma pipeline, empty for `hf` (AutoModel in the reference: the bare encoder)
+    _dense_modules = ()
+
+    def _load_gemma(self, directory: str, arch, sd) -> None:
+        """a transformers Gemma3TextModel checkpoint with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its
+        fine-tunes; AutoModel in the reference): host tokenisation by the `tokenizers` library from the directory's tokenizer.json with the file's own
+        post-processor (<bos> ... <eos>), right-padded, truncated at min(tokens, max_position_embeddings); the tower of engine/gemma.py.  Pooling: the
+        property, else 1_Pooling/config.json, else mean.  The task prompts of the model card stay the caller's text_query_prefix / text_chunk_prefix.
+        bf16 operands only."""
+        from marqo_amd.engine.gemma import GemmaTower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        props = self.model_properties
+        if props.engine_precision == "fp8":
+            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for EmbeddingGemma encoders (their RMSNorm / "
+                                              f"rotary / gated tanh-GELU blocks run on bf16 operands only)")
+        try:
+            dense = [self._read_dense_module(directory, d) for d in self._dense_modules]
+        except (OSError, ValueError, KeyError) as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        out_width = dense[-1].shape[0] if dense else arch.width
+        if self._check_dimensions and out_width != props.dimensions:
+            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {out_width}")
+        try:
+            self._tokenizer = HfJsonTokenizer.plain(directory, pad_fallback="<pad>")
+        except ValueError as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        props.tokens = min(props.tokens, arch.max_pos)
+        self._refuse_last_pooling()
+        pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
+        self.arch = arch
+        self.weights_source = directory
+        try:
+            self._model = GemmaTower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision, dense=dense)
+        except (ValueError, KeyError) as e:   # a missing / mis-shaped tensor, bias tensors, a Dense module that does not fit
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        self._pooling_func = pooling
+        self._device_tokenizer = None   # (no GPU tokeniser for this vocabulary)
+
+    @staticmethod
+    def _read_dense_module(directory: str, sub: str):
+        """one sentence-transformers Dense module directory -> its weight [out, in]; a bias or a non-identity activation is refused (ValueError)"""
+        import json
+        from safetensors.torch import load_file
+        d = os.path.join(directory, sub)
+        with open(os.path.join(d, "config.json")) as f:
+            dc = json.load(f)
+        act = str(dc.get("activation_function", "torch.nn.modules.linear.Identity"))
+        if dc.get("bias", False):
+            raise ValueError(f"Dense module {sub} has a bias: only bias-free Dense modules with identity activation are served")
+        if not act.endswith("Identity"):
+            raise ValueError(f"Dense module {sub} has activation {act}: only bias-free Dense modules with identity activation are served")
+        t = load_file(os.path.join(d, "model.safetensors"))
+        if "linear.bias" in t:
+            raise ValueError(f"Dense module {sub} has a bias: only bias-free Dense modules with identity activation are served")
+        if "linear.weight" not in t:
+            raise KeyError(f"Dense module {sub}: model.safetensors has no 'linear.weight'")
+        w = t["linear.weight"]
+        if tuple(w.shape) != (int(dc.get("out_features", w.shape[0])), int(dc.get("in_features", w.shape[1]))):
+            raise ValueError(f"Dense module {sub}: linear.weight {tuple(w.shape)} does not match its config.json")
+        return w
 
     @staticmethod
     def _adds_prefix_space(directory: str) -> bool:

@@ -11,6 +11,8 @@ constructor / `encode` contract over it:
     (`_convert_output`: numpy on every device);
   * a checkpoint whose pipeline ends in a `Normalize` module returns unit vectors even for `normalize=False`, as it does in the reference
     (`model.encode` runs the whole pipeline);
+  * an EmbeddingGemma checkpoint (config.json model_type "gemma3_text") also runs the bias-free, identity-activation `Dense` modules its `modules.json`
+    lists, behind the pooling; the Dense modules of other families are not served (unchanged);
   * `TEST` keeps the first 16 dimensions before normalising (sbert_utils.py:80-111) and returns a tensor, as the reference does.
 
 There is no CPU path: a non-cuda device raises like every other engine loader."""
@@ -73,6 +75,22 @@ def _sentence_transformer_info(directory: Optional[str]):
     return max_len, normalizes
 
 
+def _gemma_dense_modules(directory: Optional[str]) -> List[str]:
+    """the Dense module directories of an EmbeddingGemma SentenceTransformer checkpoint (config.json model_type "gemma3_text"), in pipeline order; empty
+    for every other family — their pipelines are served without Dense modules, as before"""
+    if not directory:
+        return []
+    try:
+        with open(os.path.join(directory, "config.json")) as f:
+            if json.load(f).get("model_type") != "gemma3_text":
+                return []
+        with open(os.path.join(directory, "modules.json")) as f:
+            mods = json.load(f)
+    except (OSError, ValueError, AttributeError):
+        return []
+    return [str(m.get("path", "")) for m in mods if isinstance(m, dict) and str(m.get("type", "")).endswith("models.Dense")]
+
+
 class SBERT(Model):
     """class for SBERT models (sbert_utils.py:39-77)"""
     supports_dynamic_batching = True
@@ -97,6 +115,8 @@ class SBERT(Model):
         if pooled:
             props["poolingMethod"] = pooled
         self.model = _SentenceTransformerHF(props, self.device)
+        # EmbeddingGemma: the pipeline's Dense modules (2_Dense, 3_Dense) run behind the pooling, in front of Normalize, as SentenceTransformer.encode runs them
+        self.model._dense_modules = tuple(_gemma_dense_modules(directory))
         self.model.load()
 
     def _convert_output(self, output):
