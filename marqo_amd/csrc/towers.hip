@@ -268,7 +268,8 @@ namespace {
 // Every row still feeds K and V, so LN1 (pre-LN), the QKV GEMM and the attention run on all rows; the out-projection,
 // the MLP and their LayerNorms are row-wise, so they run on the gathered rows only and are scattered back.  The
 // selected rows come out bit-identical to the full block (same k-order of MFMAs per output element); the other rows
-// of d_x are left as they were after the previous block.
+// of d_x are left as they were after the previous block (on the post-LN bf16 stream, where the blocks keep the stream in `h`, the block in front
+// writes its fp32 rows to d_x for that: block_post_ln_bf16).
 // Scratch reuse: a_sel -> head of `h`, LN2 output -> head of `a`, fc1 output -> head of `qf`, x_sel (fp32) -> `qf`
 // behind the fc1 output (all of h / a / qkv are dead by the time they are overwritten).
 int last_block_selected(const mq_encoder_cfg* cfg, const mq_block_weights& b, int l, float* d_x, int64_t rows,
@@ -373,6 +374,7 @@ struct EncoderPass {
     int act_flag, res_flags, first8;
     const float* stats0;             // (mean, rstd) of the rows of d_x as the caller hands them in (the ViT front end leaves them), or nullptr
     bool has_sel;                    // the caller reads only `nsel` pooled rows afterwards (d_sel, or rows at a fixed pitch)
+    bool select_last;                // ... and the last block runs as last_block_selected
 
     int block_fp8(const mq_block_weights& b, int l);            // e4m3 GEMM operands, post-LN or pre-LN
     int block_eva(const mq_block_weights& b, int l);            // pre-LN with rotary table / sub-LayerNorms / gated MLP (EVA02)
@@ -579,7 +581,10 @@ int EncoderPass::block_post_ln_bf16(const mq_block_weights& b, int l) {
     MQ_TRY(mq_gemm_bf16(h, W, b.fc1_w, W, b.fc1_b, nullptr, qf, F, rows, F, W, MQ_EPI_BIAS | act_flag, s));
     MQ_TRY(mq_gemm_bf16(qf, F, b.fc2_w, F, b.fc2_b, (const float*)h, h, W, rows, W, F, rflags, s));
     const mq_block_weights* nb = !last ? &blocks[l + 1] : nullptr;
-    MQ_TRY(mq_layernorm_pf(h, 1, nullptr, b.ln2_g, b.ln2_b, last ? nullptr : h, last ? d_x : nullptr, rows, W, cfg->ln_eps,
+    // (in front of a row-selected last block the LayerNorm writes the fp32 rows as well: last_block_selected scatters its rows into d_x and leaves the
+    // others as THIS block left the stream — the rows a call of one block fewer returns, same kernel, same bits)
+    const bool feeds_selected = select_last && l == cfg->layers - 2;
+    MQ_TRY(mq_layernorm_pf(h, 1, nullptr, b.ln2_g, b.ln2_b, last ? nullptr : h, last || feeds_selected ? d_x : nullptr, rows, W, cfg->ln_eps,
                            pf(nb ? nb->qkv_w : nullptr), (size_t)3 * Wa * W * 2, pf(nb ? nb->out_w : nullptr), (size_t)W * Wa * 2, s));
     return MQ_OK;
 }
@@ -662,7 +667,7 @@ int encoder_forward_impl(const mq_encoder_cfg* cfg, const mq_block_weights* bloc
     else if (cfg->post_ln) MQ_TRY(mq_cast_bf16(d_x, h, rows * W, s));
 
     EncoderPass p{cfg, blocks, d_x, rows, d_cu_seqlens, nseq, fixed_len, max_len, d_sel, nsel, s, W, F, Wa, h, a, qf, row_scale, row_stats, row_part, xn, band_ctr,
-                  /*x_has_partials*/ false, act_epi(cfg->act), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32, first8, stats0, has_sel};
+                  /*x_has_partials*/ false, act_epi(cfg->act), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32, first8, stats0, has_sel, select_last};
     for (int l = 0; l < cfg->layers; ++l) {
         const mq_block_weights& b = blocks[l];
         const bool f8 = l >= first8;
