@@ -21,9 +21,10 @@ Which launch counts tell forms apart (LayerNorm family, attention family, gather
   or finalise launches), block_post_ln against block_post_ln_bf16 (5 / 2 / 0 both), the EVA sub-LayerNorm fold against its kernels (printed, not asserted),
   the panel GEMM against the tiled GEMM (one GEMM launch each; the attention + out-projection launch is seen: 1 LayerNorm-family launch instead of 2).
 
+The e4m3 forms — block_fp8, the MLP-only e4m3 block and the e4m3 body of last_block_selected — are held to their own rounding model in
+tests/test_encoder_fp8_forms_gpu.py, which runs them through this file's _Engine.
+
 Not covered here:
-  - block_fp8 and the e4m3 body of last_block_selected: they need an e4m3 rounding model and calibrated scales of their own (tests/test_fp8_gpu.py and
-    the row-select bit tests keep what they hold) — the remaining gap;
   - the fixed-pitch selected body (sel_strided_ok) and the `stats0` hand-in: encoder_forward_impl takes both from the image tower only
     (mq_encode_image_*), where the stream is not observable; they stay with the tower tests.
 
@@ -97,6 +98,19 @@ class _Engine:
             cfg.d_rel_bias, cfg.rel_span = self.keep[-1].data_ptr(), max(case.lens)
         if case.kind == "eva" and case.sub_ln:
             cfg.mlp_ln_dim = F
+        self.f8 = None
+        if case.form.first8 is not None:
+            # the e4m3 forms (tests/test_encoder_fp8_forms_gpu.py): the engine's own class quantises the weights; the reference takes the codes and scales it
+            # wrote (Case.q8); the static activation scales come from the float64 reference (E.f8_setup), never from a recording run
+            n0 = len(self.holder.tensors)
+            self.f8 = towers._Fp8State(L.load(), self.holder, self.blocks, n, W, F, torch.device(DEV))
+            torch.cuda.synchronize()
+            t = self.holder.tensors[n0:]
+            assert len(t) == 8 * n
+            case.q8 = [{name: (t[(i * 4 + j) * 2], t[(i * 4 + j) * 2 + 1]) for j, name in enumerate(E.F8_NAMES)} for i in range(n)]
+            self.f8.scale.copy_(E.f8_setup(case, DEV)["scales"])
+            self.f8.attach(cfg, calibrating=False)
+            cfg.fp8_first_layer, cfg.fp8_mlp_extra = case.form.first8, case.form.mlp_extra
         self.cfg = cfg
         self.bf16_io = case.stream == 1 and not case.post_ln      # the caller of a pre-LN bf16-stream encoder hands bf16 rows in and gets bf16 rows back
         fixed = len(set(case.lens)) == 1
@@ -105,9 +119,12 @@ class _Engine:
         self.cu = None if fixed else A.cu_seqlens(case.lens, DEV)
         self.x0 = case.x0().to(DEV)
 
-    def run(self, layers, sel=None, ws_fill=SENTINEL, profile=False):
-        """one call on a fresh guarded stream and workspace -> (stream [rows, W] in its stored type, launches per family or None)"""
+    def run(self, layers, sel=None, ws_fill=SENTINEL, profile=False, amax=None):
+        """one call on a fresh guarded stream and workspace -> (stream [rows, W] in its stored type, launches per family or None).  `amax`: the fp32
+        [layers, 2] accumulator of a recording call of an e4m3 form (d_fp8_act_amax)"""
         lib, case = L.load(), self.case
+        if self.f8 is not None:
+            self.cfg.d_fp8_act_amax = amax.data_ptr() if amax is not None else None
         rows, W = case.rows, case.W
         dt = torch.bfloat16 if self.bf16_io else torch.float32
         rb = W * (2 if self.bf16_io else 4)

@@ -7,7 +7,11 @@
    or behind the GEMM) stay within MARGIN of each other's yardstick: the bar admits every correct form.  (An fp32-stream and a bf16-stream form do NOT
    share a yardstick — the bf16 stream rounds x itself, 2^-9 of a channel of size 6 against 2^-9 of a block's output — which is why every GPU case is
    measured against the model of its own form; the ratio between the two is printed for the record.)
-3. The bar sees the defects this suite is there for: each is injected into `model` and leaves the bar by at least 10 x, or breaks the bit comparison."""
+3. The bar sees the defects this suite is there for: each is injected into `model` and leaves the bar by at least 10 x, or breaks the bit comparison.
+4. The e4m3 forms (tests/test_encoder_fp8_forms_gpu.py): the six static scales of every case lie a factor of two apart; with every store switched off a form's
+   dataflow IS the exact reference on the dequantised weights, and the e4m3 stores are the larger part of its yardstick; the yardstick is positive in every
+   row; a second rounding history of the same form (fp32 GEMM sums over reversed 64-wide k chunks) stays within MARGIN of the first on every case — the
+   condition under which the bar is fair to a correct kernel; and each hand-off defect of the fp8 orchestration leaves the bar on every case it applies to."""
 import dataclasses
 import math
 
@@ -199,3 +203,125 @@ def test_mutation_scatter_over_the_other_rows_breaks_the_bit_comparison(prefix):
     n_bad = int((bad[keep] != good[keep]).any(dim=1).sum())
     print(f"MUTATION the non-selected rows are overwritten by the scatter [{case.form.name}]: {n_bad} of {int(keep.sum())} other rows differ in bits")
     assert n_bad > 0 and not torch.equal(bad[keep], good[keep])
+
+
+# ---- the e4m3 forms ---------------------------------------------------------------------------------------------------------------------------
+
+F8 = E.f8_cases()
+_f8_cache = {}
+
+
+def _f8(case, layers=None, **form_changes):
+    """(setup, exact stream, model stream of the case's form with `form_changes`) after `layers` blocks, as the GPU test measures that call"""
+    n = case.layers if layers is None else layers
+    key = (case.id, n)
+    if key not in _f8_cache:
+        s = E.f8_setup(case, "cpu", n)
+        _f8_cache[key] = (s, E.exact(s["cfg"], s["blocks"], s["x0"], case.lens, n)[-1])
+    s, ex = _f8_cache[key]
+    return s, ex, _f8_model(case, s, n, **form_changes)
+
+
+def _f8_sel(case, n):
+    sel = case.sel_rows()
+    return torch.tensor(sel) if (sel is not None and not case.post_ln and n == case.layers) else None
+
+
+def _f8_model(case, s, n, mut=None, **form_changes):
+    form = dataclasses.replace(s["form"], **form_changes)
+    return E.model(s["cfg"], s["blocks"], s["x0"], case.lens, form, n, _f8_sel(case, n), mut)[-1]
+
+
+@pytest.mark.parametrize("case", F8, ids=lambda c: c.id)
+def test_f8_scales_lie_a_factor_of_two_apart(case):
+    s = E.f8_setup(case)
+    v = sorted(s["scales"].flatten().tolist())
+    gaps = [b / a for a, b in zip(v, v[1:])]
+    print(f"F8_SCALES case={case.id}: max|tensor| = {[round(x * 448 * case.scale_div, 2) for x in s['scales'].flatten().tolist()]}, smallest ratio of two scales {min(gaps):.2f}")
+    assert len(v) == 2 * case.layers and min(v) > 0 and min(gaps) >= 2.0
+    ex = {k: m for k, m in s["amax_exact"].items()}
+    assert all(abs(float(s["scales"][l, k]) * case.scale_div * 448.0 - ex[(l, k)]) <= 1e-6 * ex[(l, k)] for l in range(case.layers) for k in (0, 1))
+
+
+@pytest.mark.parametrize("case", F8, ids=lambda c: c.id)
+def test_f8_rounding_switched_off_is_the_exact_reference(case):
+    for n in (1, case.layers):
+        s, ex, off = _f8(case, n, rounds=False, fold=False)
+        if _f8_sel(case, n) is None:
+            assert torch.equal(off, ex)
+        else:
+            sel = _f8_sel(case, n)
+            assert torch.equal(off[sel], ex[sel])
+        if n == case.layers:        # the e4m3 stores are what the yardstick of these forms is made of: without them the model lies closer to exact
+            mo, no8 = _f8_model(case, s, n), _f8_model(case, s, n, e4m3=False)
+            rows = _f8_sel(case, n)
+            y, y0 = (mo - ex).norm(dim=1), (no8 - ex).norm(dim=1)
+            if rows is not None:
+                y, y0 = y[rows], y0[rows]
+            print(f"F8_SHARE case={case.id}: median row error with / without the e4m3 stores {float(y.median()):.3e} / {float(y0.median()):.3e}")
+            assert float(y0.median()) < float(y.median())
+
+
+@pytest.mark.parametrize("case", F8, ids=lambda c: c.id)
+def test_f8_yardstick_is_positive_on_every_gpu_input(case):
+    for n in (1, case.layers):
+        s, ex, mo = _f8(case, n)
+        rows = _f8_sel(case, n)
+        r = E.row_ratio(mo, ex, mo, rows)
+        y = (mo - ex).norm(dim=1)
+        y = y if rows is None else y[rows]
+        print(f"YARDSTICK case={case.id} layers={n}: row error of the model min {float(y.min()):.3e} median {float(y.median()):.3e} max {float(y.max()):.3e}")
+        assert float(y.min()) > 0 and r["ratio"] == 1.0 and torch.isfinite(mo).all()
+
+
+@pytest.mark.parametrize("case", F8, ids=lambda c: c.id)
+def test_f8_second_rounding_history_stays_within_margin(case):
+    for n in (1, case.layers):
+        s, ex, mo = _f8(case, n)
+        m2 = _f8_model(case, s, n, hist=1)
+        rows = _f8_sel(case, n)
+        a, b = E.row_ratio(m2, ex, mo, rows), E.row_ratio(mo, ex, m2, rows)
+        n_diff = int((m2 != mo).any(dim=1).sum())
+        print(f"F8_HISTORY case={case.id} layers={n}: second history against the first {a['ratio']:.3f} (row {a['row']}), first against second {b['ratio']:.3f}; "
+              f"{n_diff} rows differ")
+        assert max(a["ratio"], b["ratio"]) <= MARGIN
+
+
+_SAT = "[scales/4:saturating]"
+_plain = lambda c: _SAT not in c.id                                          # noqa: E731
+F8_MUTATIONS = [
+    # (name, kind, the cases it applies to)
+    ("s_attn and s_mlp swapped", "swap_scales", _plain),
+    ("the scales of layer l - 1 used", "prev_layer_scales", _plain),
+    ("row_scale of the neighbouring row", "row_scale_neighbour", _plain),
+    ("row_scale of LN1 re-used for LN2", "row_scale_ln1_for_ln2", _plain),
+    ("rowquant skipped at the post-LN transition", "skip_rowquant", lambda c: c.post_ln and c.form.first8 > 0),
+    ("e4m3 stores truncated instead of rounded to nearest", "e4m3_truncate", _plain),
+    ("no saturation", "no_saturation", lambda c: _SAT in c.id),
+    ("the selected body gathers attention rows at 2 * Wa bytes", "gather_2wa", lambda c: c.sel is not None and not c.post_ln),
+]
+_F8_MUT_PAIRS = [(name, kind, c) for name, kind, ok in F8_MUTATIONS for c in F8 if ok(c)]
+
+
+@pytest.mark.parametrize("name,kind,case", _F8_MUT_PAIRS, ids=[f"{k}-{c.id}" for _, k, c in _F8_MUT_PAIRS])
+def test_f8_mutation_leaves_the_bar(name, kind, case):
+    """in one of the two calls the GPU test measures: all blocks (the selected rows of a row selection), or the first block alone"""
+    worst = []
+    for n in (case.layers, 1):
+        s, ex, mo = _f8(case, n)
+        bad = _f8_model(case, s, n, mut=dict(kind=kind))
+        worst.append(E.row_ratio(bad, ex, mo, _f8_sel(case, n))["ratio"])
+    print(f"F8_MUTATION {name} [{case.form.name}] case={case.id}: worst row ratio {worst[0]:.1f} after all blocks, {worst[1]:.1f} after the first alone = "
+          f"{max(worst) / MARGIN:.1f} x the bar")
+    assert max(worst) > MARGIN
+
+
+def test_f8_quantize_rows_is_the_kernels_rule():
+    """the host stand-in for the engine's weight quantiser: scale = max|row| / 448 (1 for a zero row), codes within half an e4m3 step"""
+    from tests.gemm_fp8_ref import decode
+    w = (torch.randn(40, 128, generator=torch.Generator().manual_seed(3)) * torch.rand(40, 1, generator=torch.Generator().manual_seed(4))).to(torch.bfloat16)
+    w[7] = 0
+    codes, sc = E.quantize_rows(w.double())
+    assert float(sc[7]) == 1.0 and torch.equal(sc[torch.arange(40) != 7], (w.float().abs().amax(1) / 448.0)[torch.arange(40) != 7])
+    err = (decode(codes) * sc.double()[:, None] - w.double()).abs().amax(1)
+    assert bool((err <= w.double().abs().amax(1) * 2.0 ** -4 / 1.75 + 1e-12).all())       # half a step of the top binade: 2^-4 of 256 / 448 of the maximum
