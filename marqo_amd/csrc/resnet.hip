@@ -470,7 +470,9 @@ int rn_forward(const mq_resnet_cfg* c, const mq_resnet_weights* w, const void* d
         const int P = pad64(wd << st), out = 4 * (wd << st);
         for (int j = 0; j < c->layers[st]; ++j, ++blk) {
             const bool down = st > 0 && j == 0;
-            const bool has_ds = down || inp != out;
+            // the first block of every stage has the downsample branch (stage 1: the module's inplanes w != 4 w).  `inp` is the PADDED width here:
+            // at w = 16 pad64(w) == 4 w, so comparing it with `out` would take layer1.0 for an identity block
+            const bool has_ds = j == 0;
             MQ_CHECK_ARG(blk->conv1_w && blk->conv1_b && blk->conv2_w && blk->conv2_b && blk->conv3_w && blk->conv3_b && (!has_ds || (blk->ds_w && blk->ds_b)),
                          "mq_encode_resnet: missing weights of stage %d block %d", st + 1, j);
             MQ_TRY(mq_gemm_bf16(X, inp, blk->conv1_w, inp, blk->conv1_b, nullptr, A, P, rows, P, inp, BR, s));

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, synthetic, towers
 from marqo_amd.engine.archs import OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
+from tests.convtower_ref import _head, _torch_trunk      # the fp32 restatements (they run on the device of their input)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -111,37 +112,6 @@ def _hf_convnext(sd, arch):
         mapped[k] = v
     m.load_state_dict(mapped, strict=True)
     return m.to(DEV)
-
-
-def _torch_trunk(sd, arch, x):
-    """the timm trunk restated in torch fp32 (NCHW), any LayerNorm eps -> the pooled, normed [n, C3] row"""
-    t, eps = "visual.trunk.", arch.ln_eps
-    p = lambda k: sd[t + k].to(DEV)
-
-    def ln_cf(x, name):
-        return F.layer_norm(x.permute(0, 2, 3, 1), (x.shape[1],), p(name + ".weight"), p(name + ".bias"), eps).permute(0, 3, 1, 2)
-
-    x = ln_cf(F.conv2d(x, p("stem.0.weight"), p("stem.0.bias"), stride=4), "stem.1")
-    for i, depth in enumerate(arch.depths):
-        s = f"stages.{i}."
-        if i > 0:
-            x = F.conv2d(ln_cf(x, s + "downsample.0"), p(s + "downsample.1.weight"), p(s + "downsample.1.bias"), stride=2)
-        for j in range(depth):
-            b = f"{s}blocks.{j}."
-            C = x.shape[1]
-            y = F.conv2d(x, p(b + "conv_dw.weight"), p(b + "conv_dw.bias"), padding=3, groups=C).permute(0, 2, 3, 1)
-            y = F.layer_norm(y, (C,), p(b + "norm.weight"), p(b + "norm.bias"), eps)
-            y = F.linear(F.gelu(F.linear(y, p(b + "mlp.fc1.weight"), p(b + "mlp.fc1.bias"))), p(b + "mlp.fc2.weight"), p(b + "mlp.fc2.bias"))
-            x = x + (y * p(b + "gamma")).permute(0, 3, 1, 2)
-    return F.layer_norm(x.mean((2, 3)), (x.shape[1],), p("head.norm.weight"), p("head.norm.bias"), eps)
-
-
-def _head(sd, arch, pooled):
-    if arch.head == "linear":
-        return F.linear(pooled, sd["visual.head.proj.weight"].to(DEV))
-    h = F.gelu(F.linear(pooled, sd["visual.head.mlp.fc1.weight"].to(DEV), sd["visual.head.mlp.fc1.bias"].to(DEV)))
-    b2 = sd.get("visual.head.mlp.fc2.bias")
-    return F.linear(h, sd["visual.head.mlp.fc2.weight"].to(DEV), None if b2 is None else b2.to(DEV))
 
 
 def _pixels(u8):

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, synthetic, towers
 from marqo_amd.engine.archs import OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
+from tests.convtower_ref import _torch_resnet      # the fp32 restatement of ModifiedResNet (it runs on the device of its input)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -171,44 +172,6 @@ def test_attnpool_tokens_and_attend_match_torch(C, HW):
 
 
 # ---- the fp32 restatement of ModifiedResNet ---------------------------------------------------------------------------------------------------
-def _torch_resnet(sd, arch, x):
-    """OpenAI CLIP's ModifiedResNet (= open_clip's) in fp32, NCHW, eval mode -> attnpool output [n, E]"""
-    p = lambda k: sd[k].to(DEV).float()
-    v = "visual."
-
-    def bn(t, name):
-        return F.batch_norm(t, p(name + ".running_mean"), p(name + ".running_var"), p(name + ".weight"), p(name + ".bias"), False, 0.0, 1e-5)
-
-    x = F.relu(bn(F.conv2d(x, p(v + "conv1.weight"), stride=2, padding=1), v + "bn1"))
-    x = F.relu(bn(F.conv2d(x, p(v + "conv2.weight"), padding=1), v + "bn2"))
-    x = F.relu(bn(F.conv2d(x, p(v + "conv3.weight"), padding=1), v + "bn3"))
-    x = F.avg_pool2d(x, 2)
-    for i, depth in enumerate(arch.layers):
-        for j in range(depth):
-            b = f"{v}layer{i + 1}.{j}."
-            stride = 2 if (i > 0 and j == 0) else 1
-            out = F.relu(bn(F.conv2d(x, p(b + "conv1.weight")), b + "bn1"))
-            out = F.relu(bn(F.conv2d(out, p(b + "conv2.weight"), padding=1), b + "bn2"))
-            if stride > 1:
-                out = F.avg_pool2d(out, stride)
-            out = bn(F.conv2d(out, p(b + "conv3.weight")), b + "bn3")
-            idn = x
-            if b + "downsample.0.weight" in sd:
-                idn = bn(F.conv2d(F.avg_pool2d(x, stride) if stride > 1 else x, p(b + "downsample.0.weight")), b + "downsample.1")
-            x = F.relu(out + idn)
-    n, C = x.shape[:2]
-    t = x.flatten(2).permute(2, 0, 1)
-    t = torch.cat([t.mean(0, keepdim=True), t]) + p(v + "attnpool.positional_embedding")[:, None, :]
-    a = v + "attnpool."
-    out, _ = F.multi_head_attention_forward(
-        query=t[:1], key=t, value=t, embed_dim_to_check=C, num_heads=C // 64, q_proj_weight=p(a + "q_proj.weight"),
-        k_proj_weight=p(a + "k_proj.weight"), v_proj_weight=p(a + "v_proj.weight"), in_proj_weight=None,
-        in_proj_bias=torch.cat([p(a + "q_proj.bias"), p(a + "k_proj.bias"), p(a + "v_proj.bias")]), bias_k=None, bias_v=None,
-        add_zero_attn=False, dropout_p=0.0, out_proj_weight=p(a + "c_proj.weight"), out_proj_bias=p(a + "c_proj.bias"),
-        use_separate_proj_weight=True, training=False, need_weights=False)
-    return out[0]
-
-
 def _bf16_exact_state_dict(sd):
     """the synthetic checkpoint made exactly representable on the tower's path: every convolution and attention-pool projection weight rounded
     to bf16, and every BatchNorm scale gamma / sqrt(var + eps) moved to the nearest power of two (gamma adjusted), so that the load-time fold
