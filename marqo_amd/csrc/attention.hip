@@ -4,26 +4,15 @@
 //
 // One workgroup (4 or 8 wave64s) per (sequence, head).  The whole K [len,64] and V [len,64] of that
 // (sequence, head) are staged ONCE in LDS by LDS-DMA (sequences longer than the LDS holds — 640 keys at 128-byte rows, 320 at
-// 256-byte rows — stream through it in pieces, re-staged for every round of query blocks) (global_load_lds: every 1-KiB piece is in flight at once, no
-// register round trip; 160 KB/CU makes this possible up to 512 keys: 64 KB + 64 KB), both row-major with the 16-B
-// chunks XOR-swizzled by (key & 7).  Each wave then owns 16-query blocks and runs a flash-style online softmax over
-// 64-key tiles with both GEMMs on v_mfma_f32_16x16x32_bf16; the V^T operand of the second GEMM is produced by
-// ds_read_b64_tr_b16 (the hardware 4x4 transpose read) straight from the row-major V — no transposed copy exists:
-//
-//   S^T = K . Q^T  (operands swapped so every lane's 16 scores belong to ONE query: the row max /
-//                   row sum need only two xor-shuffles, no LDS round trip)
-//   O^T = V^T . P^T  (the P^T fragment a lane needs as MFMA B-operand is exactly the set of
-//                   probabilities it already holds; the k-slot <-> key permutation is applied
-//                   identically to the V^T A-operand, which is legal because the contraction is
-//                   permutation-invariant)
+// 256-byte rows — stream through it in pieces, re-staged for every round of query blocks; 160 KB/CU makes the single staging possible up to 512 keys:
+// 64 KB + 64 KB).  Each wave then owns 16-query blocks and runs the tile core of attention_core.h over the sequence's 64-key tiles; the LDS image, the
+// swapped-operand MFMA forms and the V^T transpose read are explained there.
 //
 // Sequences are packed (cu_seqlens) or fixed-length; there is no key-padding mask: padded
 // tokens are simply not rows.  MASK_CAUSAL implements the CLIP text tower's mask.
 #include <type_traits>
-#include "common.h"
+#include "attention_core.h"
 #include "knobs.h"
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -59,7 +48,6 @@ __global__ __launch_bounds__(NW * 64) MQ_ATTN_OCC void attention_kernel(
     constexpr int NCS = HS / 8;      // chunks a head really has in global memory (slots past them are never consumed)
     constexpr int NKK = (HS + 31) / 32;  // 32-deep MFMA k-chunks of a Q.K dot product (2 .. 4)
     constexpr int NDT = HS / 16;     // 16-wide output-dim tiles (4 .. 8)
-    constexpr int RPP = 1024 / RB;   // rows per 1-KiB LDS-DMA piece (8 or 4)
     char* sK = smem;                      // [kpad][RB], 16-B chunks XOR-swizzled by (key & (NC-1))
     char* sV = smem + (size_t)kpad * RB;  // [kpad][RB], same image
 
@@ -77,27 +65,12 @@ __global__ __launch_bounds__(NW * 64) MQ_ATTN_OCC void attention_kernel(
     const int kp = nkt << 6;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
-    // ---- stage K and V: RPP rows x RB bytes per LDS-DMA; lane -> (row = RPP*piece + lane/NC, physical chunk = lane%NC) fetches
-    // the logical chunk that lives there.  Rows past the sequence re-read its last row (finite values; their scores are
-    // masked and their probabilities are exactly 0).  The LDS holds kpad keys: the whole sequence when it fits (nchunks == 1,
-    // staged once), else the sequence goes through it in nchunks pieces of kpad keys for every round of query blocks.
+    // The LDS holds kpad keys: the whole sequence when it fits (nchunks == 1, staged once), else the sequence goes through it in nchunks pieces of kpad
+    // keys for every round of query blocks.
     const int nchunks = (kp + kpad - 1) / kpad;
     auto stage = [&](int c) {
         const int base = c * kpad;
-        const int rows_here = kp - base < kpad ? kp - base : kpad;
-        const int np8 = rows_here / RPP;
-        const int srow = lane / NC, pchunk = lane % NC;
-        for (int p = wave; p < 2 * np8; p += NW) {
-            const bool is_v = p >= np8;
-            const int piece = is_v ? p - np8 : p;
-            const int row = piece * RPP + srow;        // LDS row; the key is base + row (base is a multiple of 64: same swizzle)
-            const int key = base + row < len ? base + row : len - 1;
-            int lc = pchunk ^ (row & (NC - 1));
-            if (HS < HD) lc = lc < NCS ? lc : 0;  // slots of chunks the head does not have: any finite filler (they meet zero Q dims)
-            const bf16_t* src = (is_v ? vb : kb) + (int64_t)key * ld + (lc << 3);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)((is_v ? sV : sK) + piece * 1024), 16, 0, 0);
-        }
+        attn_stage_piece<RB, NC, NC - 1, NW, NCS>(sK, sV, kb, vb, ld, base, kp - base < kpad ? kp - base : kpad, len, lane, wave);
     };
     if (nchunks == 1) stage(0);
     const int l15 = lane & 15, g = lane >> 4;
@@ -162,18 +135,9 @@ __global__ __launch_bounds__(NW * 64) MQ_ATTN_OCC void attention_kernel(
         const int kt1 = !active ? kt0 : (kt_end < kt0 + (kpad >> 6) ? kt_end : kt0 + (kpad >> 6));
         const int cb = c * kpad;                         // LDS row of global key `key` is key - cb (cb is a multiple of 64)
         for (int kt = kt0; kt < kt1; ++kt) {
-            // ---- S^T tile: keys 64kt + 16t + 4g + r for this lane's query -----------------------
             f32x4 sc[4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                const int key = kt * 64 + t * 16 + l15;  // A-operand row
-#pragma unroll
-                for (int kk = 0; kk < NKK; ++kk) {
-                    const bf16x8 kf = *(const bf16x8*)(sK + (key - cb) * RB + (((g + 4 * kk) ^ (key & (NC - 1))) << 4));
-                    sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], sc[t], 0, 0, 0);
-                }
-            }
+            for (int t = 0; t < 4; ++t) sc[t] = attn_score_keys<RB, NKK, NC - 1>(sK, kt * 64 + t * 16 + l15, cb, g, qf);
             if (BIAS) {   // (rows of padded query lanes / key columns past the sequence are clamped: their scores are masked or never stored)
                 const float* rb = rel_bias + (int64_t)h * (2 * rel_span - 1) + (rel_span - 1) - (q < len ? q : len - 1);
 #pragma unroll
@@ -184,76 +148,13 @@ __global__ __launch_bounds__(NW * 64) MQ_ATTN_OCC void attention_kernel(
                         sc[t][r] += rb[key < len ? key : len - 1];
                     }
             }
-            // masking is needed only on the ragged last tile and (causal) on tiles that reach past the block's first query:
-            // a wave-uniform test, so interior tiles skip the per-element compares / selects
-            bool need_mask = (kt == nkt - 1) && (len & 63);
-            if (MASK != MQ_MASK_NONE) need_mask = need_mask || (kt * 64 + 63 > qblk * 16);
-            if (need_mask) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = kt * 64 + t * 16 + g * 4 + r;
-                        bool valid = key < len;
-                        if (MASK != MQ_MASK_NONE) valid = valid && (key <= q);
-                        // CoCa's class-token row (the sequence's LAST row) does not see its own key (open_clip build_cls_mask, see marqo_hip.h)
-                        if (MASK == MQ_MASK_CAUSAL_CLS) valid = valid && !(q == len - 1 && key == q && len > 1);
-                        sc[t][r] = valid ? sc[t][r] : -INFINITY;
-                    }
-            }
-            // running max on the RAW scores (the softmax scale is positive); scale and shift fold into one FMA per element
-            float mx = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])), fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
-            mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(sc[2][0], sc[2][1]), fmaxf(sc[2][2], sc[2][3])), fmaxf(fmaxf(sc[3][0], sc[3][1]), fmaxf(sc[3][2], sc[3][3]))));
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);   // finite: every query sees at least key 0
-            const float neg_mc = -m_new * scale_log2e;
-            float psum = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    sc[t][r] = __builtin_amdgcn_exp2f(fmaf(sc[t][r], scale_log2e, neg_mc));
-                    psum += sc[t][r];
-                }
-            if (__any(m_new != m_run)) {  // rescale only when some query's running max moved (rare after the first tiles)
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
-                l_run *= alpha;
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
-            }
-            l_run += psum;
-            m_run = m_new;
-
-            // ---- O^T += V^T . P^T over the tile's two 32-key halves --------------------------------
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                union { uint32_t w[4]; bf16x8 v; } pf;
-                pf.w[0] = pack_bf16x2(sc[2 * u][0], sc[2 * u][1]);
-                pf.w[1] = pack_bf16x2(sc[2 * u][2], sc[2 * u][3]);
-                pf.w[2] = pack_bf16x2(sc[2 * u + 1][0], sc[2 * u + 1][1]);
-                pf.w[3] = pack_bf16x2(sc[2 * u + 1][2], sc[2 * u + 1][3]);
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) {
-                    // lane (d = dt*16 + l15, g) needs V[keys 16*(2u) + 4g .. +3][d] and V[keys 16*(2u+1) + 4g .. +3][d]:
-                    // ds_read_b64_tr_b16 hands output lane 4r+c of a 16-lane block element c of the 8 bytes fetched by
-                    // lanes r, r+4, r+8, r+12 of that block, so source lane (g, l15) fetches V[key0 + 4g + l15/4][4*(l15%4) .. +3]
-                    union { s16x4 t[2]; bf16x8 v; } vf;
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) {
-                        const int key = kt * 64 + (2 * u + tt) * 16 + vkey;
-                        const char* vp = sV + (key - cb) * RB + ((((dt << 1) | vcol) ^ (key & (NC - 1))) << 4) + vhalf;
-                        vf.t[tt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)vp);
-                    }
-                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf.v, pf.v, o[dt], 0, 0, 0);
-                }
-            }
+            attn_mask_causal<MASK>(sc, kt, nkt, g, q, qblk * 16, len);
+            attn_softmax_step<NDT>(sc, m_run, l_run, o, scale_log2e);   // (m_run is finite after the first tile: every query sees at least key 0)
+            attn_pv_tile<RB, NDT, NC - 1>(sV, kt, cb, vkey, vcol, vhalf, sc, o);
         }
         }  // chunks
         if (!active) continue;
-        float l_tot = l_run + __shfl_xor(l_run, 16, 64);
-        l_tot += __shfl_xor(l_tot, 32, 64);
-        const float inv = 1.0f / l_tot;
+        const float inv = attn_inv_denominator(l_run);
         if (q < len) {
             if (OUT_FP8) {
                 const float qs = 1.0f / out_scale[0];
@@ -319,27 +220,25 @@ static int attention_impl(const void* d_qkv, void* d_out, const int32_t* d_cu_se
                           int32_t fixed_len, int32_t max_len, int32_t W, int32_t heads, int32_t mask,
                           int32_t out_fp8, const float* d_out_scale, float* d_amax, const float* d_rel_bias, int32_t rel_span, void* stream,
                           float* d_row_part = nullptr, int64_t part_ld = 0) {
-    MQ_CHECK_ARG(d_qkv && d_out, "mq_attention: null pointer");
+    ATTN_ARG_PTRS("mq_attention", d_qkv, d_out);
     MQ_CHECK_ARG(!d_row_part || (!out_fp8 && !d_rel_bias), "mq_attention_stats: bf16 output, no relative-position bias");
     MQ_CHECK_ARG(heads >= 1 && W % heads == 0, "mq_attention: W=%d is not a multiple of heads=%d", W, heads);
     const int hs = W / heads;             // head stride in memory = dims computed
     MQ_CHECK_ARG(hs == 64 || hs == 96 || hs == 112 || hs == 128, "mq_attention: head dim must be 64, 96, 112 or 128 (W=%d heads=%d)", W, heads);
     const int hd = hs == 64 ? 64 : 128;   // LDS row width
-    MQ_CHECK_ARG(fixed_len > 0 || d_cu_seqlens, "mq_attention: need fixed_len or cu_seqlens");
+    ATTN_ARG_SEQS("mq_attention", fixed_len, d_cu_seqlens);
     MQ_CHECK_ARG(mask == MQ_MASK_NONE || mask == MQ_MASK_CAUSAL || mask == MQ_MASK_CAUSAL_CLS, "mq_attention: bad mask %d", mask);
     MQ_CHECK_ARG(mask != MQ_MASK_CAUSAL_CLS || !out_fp8, "mq_attention: MQ_MASK_CAUSAL_CLS runs with bf16 output only");
     if (nseq <= 0) return MQ_OK;
     const int maxl = fixed_len > 0 ? fixed_len : max_len;
-    MQ_CHECK_ARG(maxl >= 1 && maxl <= 8192, "mq_attention: max sequence length %d unsupported (1..8192)", maxl);
+    ATTN_ARG_MAXL("mq_attention", maxl);
     MQ_CHECK_ARG(!d_rel_bias || (hs == 64 && mask == MQ_MASK_NONE && !out_fp8 && rel_span >= maxl),
                  "mq_attention_bias: the relative-position bias runs with 64-wide heads, no mask, bf16 output and rel_span (%d) >= the longest "
                  "sequence (%d)", rel_span, maxl);
-    MQ_CHECK_ARG(nseq * heads < (1LL << 31), "mq_attention: grid too large");
+    ATTN_ARG_GRID("mq_attention", nseq * heads);
     // K + V rows of hd bf16 each live in the CU's 160 KiB of LDS: whole sequences up to 640 keys (hd 64) / 320 keys (hd 128),
     // longer ones stream through it in pieces of that many keys (ViT-H-14-378: 730 tokens, ViT-B-16-SigLIP-512: 1024)
-    const int cap = hd == 64 ? 640 : 320;
-    const int need = ((maxl + 63) / 64) * 64;
-    const int kpad = need < cap ? need : cap;
+    const int kpad = attn_kpad(maxl, hd == 64 ? 640 : 320);
     const size_t lds = (size_t)kpad * hd * 4;
     hipStream_t s = (hipStream_t)stream;
     // 8 waves from 9 query blocks up (measured, profiles/r01f_attention_waves_ab.txt: -25..-33 % at 257 / 512 / 577 tokens, where a

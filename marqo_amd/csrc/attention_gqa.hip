@@ -2,9 +2,7 @@
 // kv_heads K/V heads, query head h reads K/V head h / G with G = q_heads / kv_heads (transformers' repeat_kv: consecutive query heads share), causal or
 // unmasked, bf16, 64- or 128-wide heads, packed or fixed-length sequences.
 //
-// The pieces are those of attention.hip — K and V row-major in LDS by LDS-DMA with the 16-B chunks XOR-swizzled by (key & (NC - 1)), S^T = K . Q^T and
-// O^T = V^T . P^T on v_mfma_f32_16x16x32_bf16, V^T through ds_read_b64_tr_b16, the online softmax over 64-key tiles in the swapped-operand form — what
-// differs is the work split:
+// The tile math is attention_core.h's (chunks swizzled by key & (NC - 1)); what is this file's own is the work split:
 //
 //   - A sequence's queries are split into SLICES of 128 (eight 16-query blocks).  One workgroup (8 wave64s) per (sequence, K/V head, slice): it stages
 //     that head's K and V ONCE for all G query heads that read it — expanding K/V to q_heads and running mq_attention would stage them G times.
@@ -15,9 +13,7 @@
 //     query — slice s of a long sequence stages 128 (s + 1) keys, not the sequence.
 //   - What the slice needs goes through the LDS in pieces of kpad keys when it is more than the LDS holds (320 keys at 256-byte rows, 640 at 128-byte
 //     rows), re-staged for every round of work items, as attention.hip does it.
-#include "common.h"
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+#include "attention_core.h"
 
 namespace {
 
@@ -32,7 +28,6 @@ __global__ __launch_bounds__(GQA_NW * 64) void attention_gqa_kernel(const bf16_t
     constexpr int NC = HD / 8;       // 16-byte chunk slots per LDS row (8 or 16)
     constexpr int NKK = HD / 32;     // 32-deep MFMA k-chunks of a Q.K dot product
     constexpr int NDT = HD / 16;     // 16-wide output-dim tiles
-    constexpr int RPP = 1024 / RB;   // rows per 1-KiB LDS-DMA piece (8 or 4)
     char* sK = smem;                      // [kpad][RB], 16-B chunks XOR-swizzled by (key & (NC - 1))
     char* sV = smem + (size_t)kpad * RB;  // [kpad][RB], same image
 
@@ -60,24 +55,9 @@ __global__ __launch_bounds__(GQA_NW * 64) void attention_gqa_kernel(const bf16_t
     const int nchunks = (skt + tpc - 1) / tpc;
     const int nitems = G * nblk;
     const int nrounds = (nitems + GQA_NW - 1) / GQA_NW;
-
-    // ---- stage K and V of piece c: RPP rows x RB bytes per LDS-DMA; lane -> (row = RPP piece + lane / NC, physical chunk = lane % NC) fetches the
-    // logical chunk that lives there.  Rows past the sequence re-read its last row (finite values; their scores are masked).
     auto stage = [&](int c) {
-        const int base = (c * tpc) << 6;       // first key of the piece: a multiple of 64, so LDS row & (NC - 1) == key & (NC - 1)
         const int tiles_here = skt - c * tpc < tpc ? skt - c * tpc : tpc;
-        const int np8 = (tiles_here << 6) / RPP;
-        const int srow = lane / NC, pchunk = lane % NC;
-        for (int p = wave; p < 2 * np8; p += GQA_NW) {
-            const bool is_v = p >= np8;
-            const int piece = is_v ? p - np8 : p;
-            const int row = piece * RPP + srow;
-            const int key = base + row < len ? base + row : len - 1;
-            const int lc = pchunk ^ (row & (NC - 1));
-            const bf16_t* src = (is_v ? vb : kb) + (int64_t)key * ld + (lc << 3);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)((is_v ? sV : sK) + piece * 1024), 16, 0, 0);
-        }
+        attn_stage_piece<RB, NC, NC - 1, GQA_NW>(sK, sV, kb, vb, ld, (c * tpc) << 6, tiles_here << 6, len, lane, wave);
     };
     if (nchunks == 1) {
         stage(0);
@@ -86,8 +66,7 @@ __global__ __launch_bounds__(GQA_NW * 64) void attention_gqa_kernel(const bf16_t
     }
 
     const int l15 = lane & 15, g = lane >> 4;
-    // per-lane constants of the V^T transpose reads: source lane (g, l15) fetches 4 consecutive d of key 4g + l15/4
-    const int vkey = 4 * g + (l15 >> 2);
+    const int vkey = 4 * g + (l15 >> 2);     // per-lane constants of the V^T transpose reads
     const int vcol = (l15 & 3) >> 1, vhalf = (l15 & 1) << 3;
 
     for (int rnd = 0; rnd < nrounds; ++rnd) {
@@ -128,92 +107,16 @@ __global__ __launch_bounds__(GQA_NW * 64) void attention_gqa_kernel(const bf16_t
             const int kt1 = !active ? kt0 : (kt_end < kt0 + tpc ? kt_end : kt0 + tpc);
             const int cb = kt0 << 6;                         // LDS row of global key `key` is key - cb (cb is a multiple of 64)
             for (int kt = kt0; kt < kt1; ++kt) {
-                // ---- S^T tile: keys 64kt + 16t + 4g + r for this lane's query -----------------------
                 f32x4 sc[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const int key = kt * 64 + t * 16 + l15;  // A-operand row
-#pragma unroll
-                    for (int kk = 0; kk < NKK; ++kk) {
-                        const bf16x8 kf = *(const bf16x8*)(sK + (key - cb) * RB + (((g + 4 * kk) ^ (key & (NC - 1))) << 4));
-                        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], sc[t], 0, 0, 0);
-                    }
-                }
-                // masking is needed only on the ragged last tile and (causal) on tiles that reach past the block's first query: a wave-uniform test
-                bool need_mask = (kt == nkt - 1) && (len & 63);
-                if (MASK == MQ_MASK_CAUSAL) need_mask = need_mask || (kt * 64 + 63 > qb0);
-                if (need_mask) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int key = kt * 64 + t * 16 + g * 4 + r;
-                            bool valid = key < len;
-                            if (MASK == MQ_MASK_CAUSAL) valid = valid && (key <= q);
-                            sc[t][r] = valid ? sc[t][r] : -INFINITY;
-                        }
-                }
-                // running max on the RAW scores (the softmax scale is positive); scale and shift fold into one FMA per element
-                float mx = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])), fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
-                mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(sc[2][0], sc[2][1]), fmaxf(sc[2][2], sc[2][3])), fmaxf(fmaxf(sc[3][0], sc[3][1]), fmaxf(sc[3][2], sc[3][3]))));
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run, mx);   // finite: every query sees at least key 0, in the first tile it visits
-                const float neg_mc = -m_new * scale_log2e;
-                float psum = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        sc[t][r] = __builtin_amdgcn_exp2f(fmaf(sc[t][r], scale_log2e, neg_mc));
-                        psum += sc[t][r];
-                    }
-                if (__any(m_new != m_run)) {  // rescale only when some query's running max moved
-                    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
-                    l_run *= alpha;
-#pragma unroll
-                    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
-                }
-                l_run += psum;
-                m_run = m_new;
-
-                // ---- O^T += V^T . P^T over the tile's two 32-key halves (operand layout: attention.hip) --------------------------------
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    union { uint32_t w[4]; bf16x8 v; } pf;
-                    pf.w[0] = pack_bf16x2(sc[2 * u][0], sc[2 * u][1]);
-                    pf.w[1] = pack_bf16x2(sc[2 * u][2], sc[2 * u][3]);
-                    pf.w[2] = pack_bf16x2(sc[2 * u + 1][0], sc[2 * u + 1][1]);
-                    pf.w[3] = pack_bf16x2(sc[2 * u + 1][2], sc[2 * u + 1][3]);
-#pragma unroll
-                    for (int dt = 0; dt < NDT; ++dt) {
-                        union { s16x4 t[2]; bf16x8 v; } vf;
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt) {
-                            const int key = kt * 64 + (2 * u + tt) * 16 + vkey;
-                            const char* vp = sV + (key - cb) * RB + ((((dt << 1) | vcol) ^ (key & (NC - 1))) << 4) + vhalf;
-                            vf.t[tt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)vp);
-                        }
-                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf.v, pf.v, o[dt], 0, 0, 0);
-                    }
-                }
+                attn_score_tile<RB, NKK, NC - 1>(sK, kt, cb, l15, g, qf, sc);
+                attn_mask_causal<MASK>(sc, kt, nkt, g, q, qb0, len);
+                attn_softmax_step<NDT>(sc, m_run, l_run, o, scale_log2e);   // (every query sees at least key 0, in the first tile it visits)
+                attn_pv_tile<RB, NDT, NC - 1>(sV, kt, cb, vkey, vcol, vhalf, sc, o);
             }
         }  // pieces
         if (!active) continue;
-        float l_tot = l_run + __shfl_xor(l_run, 16, 64);
-        l_tot += __shfl_xor(l_tot, 32, 64);
-        const float inv = 1.0f / l_tot;
-        if (q < len) {
-            bf16_t* orow = out + (int64_t)(row0 + q) * ldo + h * HD + 4 * g;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                uint2 p;
-                p.x = pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv);
-                p.y = pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv);
-                *(uint2*)(orow + dt * 16) = p;
-            }
-        }
+        const float inv = attn_inv_denominator(l_run);
+        if (q < len) attn_store_bf16<NDT>(out + (int64_t)(row0 + q) * ldo + h * HD + 4 * g, o, inv);
     }
 }
 
@@ -221,13 +124,9 @@ template <int MASK, int HD>
 int launch_gqa(const void* d_qkv, void* d_out, const int32_t* d_cu, int64_t nseq, int fixed_len, int q_heads, int kv_heads, int nslices, int kpad,
                hipStream_t s) {
     const size_t lds = (size_t)kpad * HD * 4;
-    if (lds > 64 * 1024) {
-        // `lds` varies from call to call and the opt-in is latched once per device: it is made for the most the kernel ever asks for (160 KiB), so a
-        // call with short sequences in front of one with long sequences leaves the limit where the long one needs it
-        static std::atomic<uint64_t> done{0};
-        hipError_t e = mq_ensure_dyn_lds((const void*)attention_gqa_kernel<MASK, HD>, 160 * 1024, done);
-        if (e != hipSuccess) { mq_set_error("mq_attention_gqa: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MQ_ERR_HIP; }
-    }
+    static std::atomic<uint64_t> done{0};
+    const int rc = attn_ensure_lds((const void*)attention_gqa_kernel<MASK, HD>, lds, 160 * 1024, done, "mq_attention_gqa");
+    if (rc != MQ_OK) return rc;
     const float scale_log2e = 1.44269504088896340736f / sqrtf((float)HD);   // 1 / sqrt(head dim) * log2(e)
     hipLaunchKernelGGL((attention_gqa_kernel<MASK, HD>), dim3((unsigned)(nseq * kv_heads * nslices)), dim3(GQA_NW * 64), lds, s, (const bf16_t*)d_qkv,
                        (bf16_t*)d_out, d_cu, fixed_len, q_heads, kv_heads, nslices, kpad, scale_log2e);
@@ -240,21 +139,18 @@ int launch_gqa(const void* d_qkv, void* d_out, const int32_t* d_cu, int64_t nseq
 // sequences packed (d_cu_seqlens int32 [nseq + 1]; max_len = the longest) or fixed_len > 0 (d_cu_seqlens NULL ok).
 extern "C" int mq_attention_gqa(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
                                 int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t mask, void* stream) {
-    MQ_CHECK_ARG(d_qkv && d_out, "mq_attention_gqa: null pointer");
+    ATTN_ARG_PTRS("mq_attention_gqa", d_qkv, d_out);
     MQ_CHECK_ARG(head_dim == 64 || head_dim == 128, "mq_attention_gqa: head_dim %d unsupported (64 or 128)", head_dim);
-    MQ_CHECK_ARG(q_heads >= 1 && kv_heads >= 1 && q_heads <= 1024 && q_heads % kv_heads == 0,
-                 "mq_attention_gqa: q_heads %d must be a multiple of kv_heads %d (1..1024 query heads)", q_heads, kv_heads);
+    ATTN_ARG_GROUPS("mq_attention_gqa", q_heads, kv_heads);
     MQ_CHECK_ARG(mask == MQ_MASK_NONE || mask == MQ_MASK_CAUSAL, "mq_attention_gqa: mask %d unsupported (MQ_MASK_NONE or MQ_MASK_CAUSAL)", mask);
-    MQ_CHECK_ARG(fixed_len > 0 || d_cu_seqlens, "mq_attention_gqa: need fixed_len or cu_seqlens");
+    ATTN_ARG_SEQS("mq_attention_gqa", fixed_len, d_cu_seqlens);
     if (nseq <= 0) return MQ_OK;
     const int maxl = fixed_len > 0 ? fixed_len : max_len;
-    MQ_CHECK_ARG(maxl >= 1 && maxl <= 8192, "mq_attention_gqa: max sequence length %d unsupported (1..8192)", maxl);
+    ATTN_ARG_MAXL("mq_attention_gqa", maxl);
     const int nslices = (maxl + GQA_SLICE - 1) / GQA_SLICE;
-    MQ_CHECK_ARG(nseq * kv_heads * nslices < (1LL << 31), "mq_attention_gqa: grid too large");
+    ATTN_ARG_GRID("mq_attention_gqa", nseq * kv_heads * nslices);
     // K + V rows of head_dim bf16 each live in the CU's 160 KiB of LDS: 640 keys (head_dim 64) / 320 keys (128); what a slice needs beyond that streams
-    const int cap = head_dim == 64 ? 640 : 320;
-    const int need = ((maxl + 63) / 64) * 64;
-    const int kpad = need < cap ? need : cap;
+    const int kpad = attn_kpad(maxl, head_dim == 64 ? 640 : 320);
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(2, s);
     int rc;

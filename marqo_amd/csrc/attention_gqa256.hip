@@ -2,9 +2,7 @@
 // kv_heads K/V heads, query head h reads K/V head h / G with G = q_heads / kv_heads; bidirectional, never causal; query i sees the keys j of its own
 // sequence with |i - j| <= half_window (half_window == 0: every key); bf16; packed or fixed-length sequences; the softmax scale is an argument.
 //
-// The pieces are those of attention.hip / attention_window.hip / attention_gqa.hip — K and V row-major in LDS by LDS-DMA with the 16-B chunks
-// XOR-swizzled, S^T = K . Q^T and O^T = V^T . P^T on v_mfma_f32_16x16x32_bf16, V^T through ds_read_b64_tr_b16, the online softmax over 64-key tiles in
-// the swapped-operand form.  What a 512-byte row changes:
+// The tile math is attention_core.h's.  What a 512-byte row changes:
 //
 //   - A row has 32 chunk slots (two 256-B bank rows).  Chunk c of key k lives in slot c ^ (k & 15) — the 16-slot swizzle of the 128-wide heads, which
 //     leaves the row's half (slot bit 4) alone: the 16 keys of a K fragment read land on 16 different slots of the bank row, and because a fragment's
@@ -23,12 +21,10 @@
 //     sequence masks per key.
 //
 // Registers per wave: 16 output tiles = 64 fp32 accumulators, 8 Q fragments = 32, one S^T tile = 16.  Compiler report for gfx950
-// (-Rpass-analysis=kernel-resource-usage): 213 VGPRs, 0 AGPRs, 68 SGPRs, scratch 0 bytes / lane, no spill, no static LDS (dynamic: 64 KiB or 128 KiB
+// (-Rpass-analysis=kernel-resource-usage): 212 VGPRs, 0 AGPRs, 68 SGPRs, scratch 0 bytes / lane, no spill, no static LDS (dynamic: 64 KiB or 128 KiB
 // per workgroup), 2 waves per SIMD — one 8-wave workgroup per CU, which is also what a two-tile piece of LDS admits.  Four waves per workgroup would
 // allow 512 registers but take three rounds (three re-stagings of the band) for the checkpoint's G = 3 where eight take two.
-#include "common.h"
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+#include "attention_core.h"
 
 namespace {
 
@@ -46,7 +42,6 @@ __global__ __launch_bounds__(G256_NW * 64) void attention_gqa256_kernel(const bf
     constexpr int NC = HD / 8;       // 32 16-byte chunk slots per LDS row
     constexpr int NKK = HD / 32;     // 8 32-deep MFMA k-chunks of a Q.K dot product
     constexpr int NDT = HD / 16;     // 16 16-wide output-dim tiles
-    constexpr int RPP = 1024 / RB;   // 2 rows per 1-KiB LDS-DMA piece
     constexpr int SWZ = 15;          // chunk c of key k lives in slot c ^ (k & 15): the swizzle stays inside one 256-B half of the row
     char* sK = smem;                      // [kpad][RB], 16-B chunks XOR-swizzled by (key & 15)
     char* sV = smem + (size_t)kpad * RB;  // [kpad][RB], same image
@@ -76,24 +71,9 @@ __global__ __launch_bounds__(G256_NW * 64) void attention_gqa256_kernel(const bf
     const int nchunks = (kt_hi - kt_lo + tpc - 1) / tpc;
     const int nitems = G * nblk;
     const int nrounds = (nitems + G256_NW - 1) / G256_NW;
-
-    // ---- stage K and V of piece c: 2 rows x 512 bytes per LDS-DMA; lane -> (row = 2 piece + lane / 32, physical chunk = lane % 32) fetches the logical
-    // chunk that lives there.  Rows past the sequence re-read its last row (finite values; their scores are masked).
     auto stage = [&](int c) {
-        const int base = (kt_lo + c * tpc) << 6;      // first key of the piece: a multiple of 64, so LDS row & 15 == key & 15
         const int tiles_here = kt_hi - (kt_lo + c * tpc) < tpc ? kt_hi - (kt_lo + c * tpc) : tpc;
-        const int np8 = (tiles_here << 6) / RPP;
-        const int srow = lane / NC, pchunk = lane % NC;
-        for (int p = wave; p < 2 * np8; p += G256_NW) {
-            const bool is_v = p >= np8;
-            const int piece = is_v ? p - np8 : p;
-            const int row = piece * RPP + srow;
-            const int key = base + row < len ? base + row : len - 1;
-            const int lc = pchunk ^ (row & SWZ);
-            const bf16_t* src = (is_v ? vb : kb) + (int64_t)key * ld + (lc << 3);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)((is_v ? sV : sK) + piece * 1024), 16, 0, 0);
-        }
+        attn_stage_piece<RB, NC, SWZ, G256_NW>(sK, sV, kb, vb, ld, (kt_lo + c * tpc) << 6, tiles_here << 6, len, lane, wave);
     };
     if (nchunks == 1) {
         stage(0);
@@ -102,8 +82,7 @@ __global__ __launch_bounds__(G256_NW * 64) void attention_gqa256_kernel(const bf
     }
 
     const int l15 = lane & 15, g = lane >> 4;
-    // per-lane constants of the V^T transpose reads: source lane (g, l15) fetches 4 consecutive d of key 4g + l15/4
-    const int vkey = 4 * g + (l15 >> 2);
+    const int vkey = 4 * g + (l15 >> 2);     // per-lane constants of the V^T transpose reads
     const int vcol = (l15 & 3) >> 1, vhalf = (l15 & 1) << 3;
 
     for (int rnd = 0; rnd < nrounds; ++rnd) {
@@ -144,91 +123,16 @@ __global__ __launch_bounds__(G256_NW * 64) void attention_gqa256_kernel(const bf
             const int t1 = !active ? t0 : (bk_hi < ct1 ? bk_hi : ct1);
             const int cb = ct0 << 6;                         // LDS row of global key `key` is key - cb (cb is a multiple of 64)
             for (int kt = t0; kt < t1; ++kt) {
-                // ---- S^T tile: keys 64kt + 16t + 4g + r for this lane's query -----------------------
                 f32x4 sc[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const int key = kt * 64 + t * 16 + l15;  // A-operand row
-#pragma unroll
-                    for (int kk = 0; kk < NKK; ++kk) {
-                        const bf16x8 kf = *(const bf16x8*)(sK + (key - cb) * RB + (((g + 4 * kk) ^ (key & SWZ)) << 4));
-                        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], sc[t], 0, 0, 0);
-                    }
-                }
-                // a tile wholly inside the band of all 16 queries and inside the sequence skips the per-key compares (a wave-uniform test)
-                const bool interior = kt * 64 >= qb0 + 15 - hw && kt * 64 + 63 <= qb0 + hw && kt * 64 + 63 < len;
-                if (!interior) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int key = kt * 64 + t * 16 + g * 4 + r;
-                            const bool valid = key < len && key >= q - hw && key <= q + hw;
-                            sc[t][r] = valid ? sc[t][r] : -INFINITY;
-                        }
-                }
-                // running max on the RAW scores (the softmax scale is positive); scale and shift fold into one FMA per element.  A query whose band
-                // misses this tile keeps m_run (from -1e30): its probabilities here are exp2(-inf) = 0 and alpha = 1
-                float mx = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])), fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
-                mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(sc[2][0], sc[2][1]), fmaxf(sc[2][2], sc[2][3])), fmaxf(fmaxf(sc[3][0], sc[3][1]), fmaxf(sc[3][2], sc[3][3]))));
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run, mx);
-                const float neg_mc = -m_new * scale_log2e;
-                float psum = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        sc[t][r] = __builtin_amdgcn_exp2f(fmaf(sc[t][r], scale_log2e, neg_mc));
-                        psum += sc[t][r];
-                    }
-                if (__any(m_new != m_run)) {  // rescale only when some query's running max moved
-                    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
-                    l_run *= alpha;
-#pragma unroll
-                    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
-                }
-                l_run += psum;
-                m_run = m_new;
-
-                // ---- O^T += V^T . P^T over the tile's two 32-key halves (operand layout: attention.hip) --------------------------------
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    union { uint32_t w[4]; bf16x8 v; } pf;
-                    pf.w[0] = pack_bf16x2(sc[2 * u][0], sc[2 * u][1]);
-                    pf.w[1] = pack_bf16x2(sc[2 * u][2], sc[2 * u][3]);
-                    pf.w[2] = pack_bf16x2(sc[2 * u + 1][0], sc[2 * u + 1][1]);
-                    pf.w[3] = pack_bf16x2(sc[2 * u + 1][2], sc[2 * u + 1][3]);
-#pragma unroll
-                    for (int dt = 0; dt < NDT; ++dt) {
-                        union { s16x4 t[2]; bf16x8 v; } vf;
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt) {
-                            const int key = kt * 64 + (2 * u + tt) * 16 + vkey;
-                            const char* vp = sV + (key - cb) * RB + ((((dt << 1) | vcol) ^ (key & SWZ)) << 4) + vhalf;
-                            vf.t[tt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)vp);
-                        }
-                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf.v, pf.v, o[dt], 0, 0, 0);
-                    }
-                }
+                attn_score_tile<RB, NKK, SWZ>(sK, kt, cb, l15, g, qf, sc);
+                attn_mask_band(sc, kt, g, q, qb0, hw, len);
+                attn_softmax_step<NDT>(sc, m_run, l_run, o, scale_log2e);
+                attn_pv_tile<RB, NDT, SWZ>(sV, kt, cb, vkey, vcol, vhalf, sc, o);
             }
         }  // pieces
         if (!active) continue;
-        float l_tot = l_run + __shfl_xor(l_run, 16, 64);
-        l_tot += __shfl_xor(l_tot, 32, 64);
-        const float inv = 1.0f / l_tot;
-        if (q < len) {
-            bf16_t* orow = out + (int64_t)(row0 + q) * ldo + h * HD + 4 * g;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                uint2 p;
-                p.x = pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv);
-                p.y = pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv);
-                *(uint2*)(orow + dt * 16) = p;
-            }
-        }
+        const float inv = attn_inv_denominator(l_run);
+        if (q < len) attn_store_bf16<NDT>(out + (int64_t)(row0 + q) * ldo + h * HD + 4 * g, o, inv);
     }
 }
 
@@ -239,32 +143,26 @@ __global__ __launch_bounds__(G256_NW * 64) void attention_gqa256_kernel(const bf
 // half_window > 0: query i sees keys i - half_window .. i + half_window.  scale: the softmax scale (query_pre_attn_scalar ** -0.5), > 0.
 extern "C" int mq_attention_gqa_band(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
                                      int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t half_window, float scale, void* stream) {
-    MQ_CHECK_ARG(d_qkv && d_out, "mq_attention_gqa_band: null pointer");
+    ATTN_ARG_PTRS("mq_attention_gqa_band", d_qkv, d_out);
     MQ_CHECK_ARG(head_dim == G256_HD, "mq_attention_gqa_band: head_dim %d unsupported (256; mq_attention_gqa serves 64 and 128)", head_dim);
-    MQ_CHECK_ARG(q_heads >= 1 && kv_heads >= 1 && q_heads <= 1024 && q_heads % kv_heads == 0,
-                 "mq_attention_gqa_band: q_heads %d must be a multiple of kv_heads %d (1..1024 query heads)", q_heads, kv_heads);
+    ATTN_ARG_GROUPS("mq_attention_gqa_band", q_heads, kv_heads);
     MQ_CHECK_ARG(half_window >= 0, "mq_attention_gqa_band: half_window %d < 0", half_window);
     MQ_CHECK_ARG(scale > 0.f && scale <= 1e6f, "mq_attention_gqa_band: softmax scale %g must be positive and finite", (double)scale);
-    MQ_CHECK_ARG(fixed_len > 0 || d_cu_seqlens, "mq_attention_gqa_band: need fixed_len or cu_seqlens");
+    ATTN_ARG_SEQS("mq_attention_gqa_band", fixed_len, d_cu_seqlens);
     if (nseq <= 0) return MQ_OK;
     const int maxl = fixed_len > 0 ? fixed_len : max_len;
-    MQ_CHECK_ARG(maxl >= 1 && maxl <= 8192, "mq_attention_gqa_band: max sequence length %d unsupported (1..8192)", maxl);
+    ATTN_ARG_MAXL("mq_attention_gqa_band", maxl);
     const int nslices = (maxl + G256_SLICE - 1) / G256_SLICE;
-    MQ_CHECK_ARG(nseq * kv_heads * nslices < (1LL << 31), "mq_attention_gqa_band: grid too large");
-    // no band, or one that covers every sequence whole: every key (the kernel's tile and mask arithmetic runs on hw >= the longest sequence)
+    ATTN_ARG_GRID("mq_attention_gqa_band", nseq * kv_heads * nslices);
+    // no band, or one that covers every sequence whole: every key (the kernel's tile and mask arithmetic runs on hw >= the longest sequence; a slice then
+    // reaches more tiles than any sequence has).  The LDS holds two tiles
     const int hw = (half_window == 0 || half_window >= maxl - 1) ? 16384 : half_window;
-    // tiles a slice can reach: its own and ceil(hw / 64) on either side, never more than the sequence has; the LDS holds two
-    const int reach = hw >= 16384 ? 1 << 20 : 1 + 2 * ((hw + 63) / 64), seq_tiles = (maxl + 63) / 64;
-    const int need = (reach < seq_tiles ? reach : seq_tiles) * 64;
-    const int kpad = need < G256_PIECE_KEYS ? need : G256_PIECE_KEYS;
+    const int kpad = attn_band_kpad(hw, maxl, G256_PIECE_KEYS);
     const size_t lds = (size_t)kpad * G256_HD * 4;
     hipStream_t s = (hipStream_t)stream;
-    if (lds > 64 * 1024) {
-        // `lds` varies from call to call and the opt-in is latched once per device: it is made for the most the kernel ever asks for (128 KiB)
-        static std::atomic<uint64_t> done{0};
-        hipError_t e = mq_ensure_dyn_lds((const void*)attention_gqa256_kernel, (size_t)G256_PIECE_KEYS * G256_HD * 4, done);
-        if (e != hipSuccess) { mq_set_error("mq_attention_gqa_band: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MQ_ERR_HIP; }
-    }
+    static std::atomic<uint64_t> done{0};
+    const int rc = attn_ensure_lds((const void*)attention_gqa256_kernel, lds, (size_t)G256_PIECE_KEYS * G256_HD * 4, done, "mq_attention_gqa_band");
+    if (rc != MQ_OK) return rc;
     MqProfScope prof(2, s);
     const float scale_log2e = 1.44269504088896340736f * scale;
     hipLaunchKernelGGL(attention_gqa256_kernel, dim3((unsigned)(nseq * kv_heads * nslices)), dim3(G256_NW * 64), lds, s, (const bf16_t*)d_qkv,
