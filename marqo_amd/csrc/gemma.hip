@@ -10,7 +10,9 @@
 //   (up | gate) = h Wug^T ; p = up * gelu_tanh(gate) ; o = p Wdown^T (bf16)
 //   x += rmsnorm(o, post_feedforward_layernorm) ; h = rmsnorm(x, the next block's input_layernorm)                     (one pass; none after the last)
 // then the final RMSNorm and the pooling (+ L2).
-#include "common.h"
+//
+// The checks in front of the first launch and the workspace arithmetic are the packed-token scaffold of packed_text.h.
+#include "packed_text.h"
 
 static_assert(sizeof(mq_gemma_layer) == 88 && sizeof(mq_gemma_weights) == 40 && sizeof(mq_gemma_cfg) == 48, "Gemma layouts (marqo_amd/_lib.py)");
 
@@ -105,32 +107,26 @@ __global__ __launch_bounds__(256) void embed_scaled_kernel(const int32_t* __rest
     for (int c = lane; c < (W >> 2); c += 64) *(f32x4*)(x + row * W + c * 4) = *(const f32x4*)(tr + c * 4) * scale;
 }
 
-constexpr size_t WS_ALIGN = 256;
 struct Plan { size_t off_x, off_h, off_a, off_o, off_big, total; };
 Plan plan(const mq_gemma_cfg* c, int64_t rows) {
     Plan p;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = align_up(off, WS_ALIGN); const size_t o = off; off += bytes; return o; };
+    Off ws;
     const size_t aw = (size_t)c->q_heads * c->head_dim, qkvw = (size_t)(c->q_heads + 2 * c->kv_heads) * c->head_dim;
     const size_t big = qkvw > 2 * (size_t)c->mlp_dim ? qkvw : 2 * (size_t)c->mlp_dim;
-    p.off_x = take((size_t)rows * c->width * 4);     // residual stream, fp32
-    p.off_h = take((size_t)rows * c->width * 2);     // normalised rows, bf16
-    p.off_a = take((size_t)rows * aw * 2);           // attention output, bf16
-    p.off_o = take((size_t)rows * c->width * 2);     // a sub-layer's output in front of its post-norm, bf16
-    p.off_big = take((size_t)rows * big * 2);        // qkv, then (up | gate)
-    p.total = align_up(off, WS_ALIGN);
+    p.off_x = ws.take((size_t)rows * c->width * 4);     // residual stream, fp32
+    p.off_h = ws.take((size_t)rows * c->width * 2);     // normalised rows, bf16
+    p.off_a = ws.take((size_t)rows * aw * 2);           // attention output, bf16
+    p.off_o = ws.take((size_t)rows * c->width * 2);     // a sub-layer's output in front of its post-norm, bf16
+    p.off_big = ws.take((size_t)rows * big * 2);        // qkv, then (up | gate)
+    p.total = ws.end();
     return p;
 }
 int check_cfg(const mq_gemma_cfg* c) {
     MQ_CHECK_ARG(c, "mq_encode_gemma: null cfg");
     MQ_CHECK_ARG(c->head_dim == 256, "mq_encode_gemma: head_dim %d unsupported (256)", c->head_dim);
-    MQ_CHECK_ARG(c->q_heads >= 1 && c->kv_heads >= 1 && c->q_heads % c->kv_heads == 0, "mq_encode_gemma: q_heads %d must be a multiple of kv_heads %d",
-                 c->q_heads, c->kv_heads);
-    MQ_CHECK_ARG(c->width >= 64 && c->width % 64 == 0, "mq_encode_gemma: width %d must be a multiple of 64", c->width);
+    MQ_TRY(check_gqa_shape("mq_encode_gemma", c->q_heads, c->kv_heads, c->width));
     MQ_CHECK_ARG(c->width <= 2048, "mq_encode_gemma: width %d > 2048", c->width);
-    MQ_CHECK_ARG(c->mlp_dim >= 64 && c->mlp_dim % 64 == 0, "mq_encode_gemma: mlp_dim %d must be a multiple of 64", c->mlp_dim);
-    MQ_CHECK_ARG(c->layers >= 1 && c->vocab >= 1, "mq_encode_gemma: layers %d / vocab %d", c->layers, c->vocab);
-    MQ_CHECK_ARG(c->max_pos >= 1 && c->max_pos <= 8192, "mq_encode_gemma: max_pos %d outside [1, 8192]", c->max_pos);
+    MQ_TRY(check_tower_sizes("mq_encode_gemma", c->mlp_dim, c->layers, c->vocab, c->max_pos));
     MQ_CHECK_ARG(c->half_window >= 0, "mq_encode_gemma: half_window %d < 0", c->half_window);
     MQ_CHECK_ARG(c->attn_scale > 0.f && c->attn_scale <= 1e6f, "mq_encode_gemma: attn_scale %g must be positive and finite", (double)c->attn_scale);
     MQ_CHECK_ARG(c->pool == MQ_POOL_MEAN || c->pool == MQ_POOL_CLS, "mq_encode_gemma: bad pooling %d (MQ_POOL_MEAN or MQ_POOL_CLS)", c->pool);
@@ -180,17 +176,11 @@ extern "C" int mq_encode_gemma(const mq_gemma_cfg* cfg, const mq_gemma_weights* 
                          b.post_ffn_norm_g, "mq_encode_gemma: layer %d has null weights", l);
     }
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_ids && d_cu_seqlens && h_cu_seqlens && d_workspace, "mq_encode_gemma: null input / workspace");
-    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "mq_encode_gemma: cu_seqlens[0] must be 0");
     int maxl = 0;
-    for (int64_t i = 0; i < nseq; ++i) {
-        const int ln = h_cu_seqlens[i + 1] - h_cu_seqlens[i];
-        MQ_CHECK_ARG(ln >= 1 && ln <= cfg->max_pos, "mq_encode_gemma: sequence lengths must be in [1, max_pos=%d]", cfg->max_pos);
-        maxl = ln > maxl ? ln : maxl;
-    }
-    const int64_t rows = h_cu_seqlens[nseq];
+    int64_t rows = 0;
+    MQ_TRY(packed_begin("mq_encode_gemma", d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
     const Plan p = plan(cfg, rows);
-    if (workspace_bytes < p.total) { mq_set_error("mq_encode_gemma: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    MQ_TRY(packed_workspace("mq_encode_gemma", workspace_bytes, p.total));
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)(base + p.off_x);

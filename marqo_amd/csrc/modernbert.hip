@@ -8,34 +8,32 @@
 //   x += a Wo^T
 //   (up | gate) = mlp_norm(x) Wi'^T  (Wi' = mlp.Wi with its halves swapped at load) ; p = up * gelu(gate) ; x += p mlp.Wo^T
 // then final_norm over every row and the loaders' mean / CLS pooling (+ L2).
-#include "common.h"
+//
+// The checks in front of the first launch and the workspace arithmetic are the packed-token scaffold of packed_text.h.
+#include "packed_text.h"
 
 int mq_cast_bf16(const float* d_x, void* d_out, int64_t n, hipStream_t s);   // rowops.hip
 
 static_assert(sizeof(mq_modernbert_layer) == 56 && sizeof(mq_modernbert_weights) == 56 && sizeof(mq_modernbert_cfg) == 40, "ModernBERT layouts (marqo_amd/_lib.py)");
 
 namespace {
-constexpr size_t WS_ALIGN = 256;
 struct Plan { size_t off_x, off_h, off_a, off_big, total; };
 Plan plan(const mq_modernbert_cfg* c, int64_t rows) {
     Plan p;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = align_up(off, WS_ALIGN); const size_t o = off; off += bytes; return o; };
+    Off ws;
     const size_t big = (size_t)(3 * c->width > 2 * c->mlp_dim ? 3 * c->width : 2 * c->mlp_dim);
-    p.off_x = take((size_t)rows * c->width * 4);     // residual stream, fp32
-    p.off_h = take((size_t)rows * c->width * 2);     // normalised rows, bf16
-    p.off_a = take((size_t)rows * c->width * 2);     // attention output, bf16
-    p.off_big = take((size_t)rows * big * 2);        // qkv, then (up | gate)
-    p.total = align_up(off, WS_ALIGN);
+    p.off_x = ws.take((size_t)rows * c->width * 4);     // residual stream, fp32
+    p.off_h = ws.take((size_t)rows * c->width * 2);     // normalised rows, bf16
+    p.off_a = ws.take((size_t)rows * c->width * 2);     // attention output, bf16
+    p.off_big = ws.take((size_t)rows * big * 2);        // qkv, then (up | gate)
+    p.total = ws.end();
     return p;
 }
 int check_cfg(const mq_modernbert_cfg* c) {
     MQ_CHECK_ARG(c, "mq_encode_modernbert: null cfg");
     MQ_CHECK_ARG(c->heads >= 1 && c->width == c->heads * 64, "mq_encode_modernbert: 64-wide heads only (width %d, heads %d)", c->width, c->heads);
     MQ_CHECK_ARG(c->width <= 2048, "mq_encode_modernbert: width %d > 2048", c->width);
-    MQ_CHECK_ARG(c->mlp_dim >= 64 && c->mlp_dim % 64 == 0, "mq_encode_modernbert: mlp_dim %d must be a multiple of 64", c->mlp_dim);
-    MQ_CHECK_ARG(c->layers >= 1 && c->vocab >= 1, "mq_encode_modernbert: layers %d / vocab %d", c->layers, c->vocab);
-    MQ_CHECK_ARG(c->max_pos >= 1 && c->max_pos <= 8192, "mq_encode_modernbert: max_pos %d outside [1, 8192]", c->max_pos);
+    MQ_TRY(check_tower_sizes("mq_encode_modernbert", c->mlp_dim, c->layers, c->vocab, c->max_pos));
     MQ_CHECK_ARG(c->half_window >= 0, "mq_encode_modernbert: half_window %d < 0", c->half_window);
     MQ_CHECK_ARG(c->pool == MQ_POOL_MEAN || c->pool == MQ_POOL_CLS, "mq_encode_modernbert: bad pooling %d", c->pool);
     return MQ_OK;
@@ -59,17 +57,11 @@ extern "C" int mq_encode_modernbert(const mq_modernbert_cfg* cfg, const mq_moder
         MQ_CHECK_ARG(b.qkv_w && b.out_w && b.mlp_norm_g && b.wi_w && b.wo_w && (l == 0 || b.attn_norm_g), "mq_encode_modernbert: layer %d has null weights", l);
     }
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_ids && d_cu_seqlens && h_cu_seqlens && d_workspace, "mq_encode_modernbert: null input / workspace");
-    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "mq_encode_modernbert: cu_seqlens[0] must be 0");
     int maxl = 0;
-    for (int64_t i = 0; i < nseq; ++i) {
-        const int ln = h_cu_seqlens[i + 1] - h_cu_seqlens[i];
-        MQ_CHECK_ARG(ln >= 1 && ln <= cfg->max_pos, "mq_encode_modernbert: sequence lengths must be in [1, max_pos=%d]", cfg->max_pos);
-        maxl = ln > maxl ? ln : maxl;
-    }
-    const int64_t rows = h_cu_seqlens[nseq];
+    int64_t rows = 0;
+    MQ_TRY(packed_begin("mq_encode_modernbert", d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
     const Plan p = plan(cfg, rows);
-    if (workspace_bytes < p.total) { mq_set_error("mq_encode_modernbert: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    MQ_TRY(packed_workspace("mq_encode_modernbert", workspace_bytes, p.total));
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)(base + p.off_x);

@@ -12,7 +12,9 @@
 //   (up | gate) = h Wug^T                       Wug = cat(up_proj, gate_proj) at load
 //   p = up * silu(gate) ; x += p Wdown^T
 // then the final RMSNorm — over the pooled last rows only under MQ_POOL_LAST — and the pooling (+ L2).
-#include "common.h"
+//
+// The checks in front of the first launch and the workspace arithmetic are the packed-token scaffold of packed_text.h.
+#include "packed_text.h"
 
 static_assert(sizeof(mq_qwen_layer) == 72 && sizeof(mq_qwen_weights) == 40 && sizeof(mq_qwen_cfg) == 40, "Qwen layouts (marqo_amd/_lib.py)");
 
@@ -108,32 +110,26 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ 
     }
 }
 
-constexpr size_t WS_ALIGN = 256;
 struct Plan { size_t off_x, off_h, off_a, off_big, off_rows, total; };
 Plan plan(const mq_qwen_cfg* c, int64_t rows, int64_t nseq) {
     Plan p;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = align_up(off, WS_ALIGN); const size_t o = off; off += bytes; return o; };
+    Off ws;
     const size_t aw = (size_t)c->q_heads * c->head_dim, qkvw = (size_t)(c->q_heads + 2 * c->kv_heads) * c->head_dim;
     const size_t big = qkvw > 2 * (size_t)c->mlp_dim ? qkvw : 2 * (size_t)c->mlp_dim;
-    p.off_x = take((size_t)rows * c->width * 4);     // residual stream, fp32
-    p.off_h = take((size_t)rows * c->width * 2);     // normalised rows, bf16
-    p.off_a = take((size_t)rows * aw * 2);           // attention output, bf16
-    p.off_big = take((size_t)rows * big * 2);        // qkv, then (up | gate)
-    p.off_rows = take((size_t)nseq * 4);             // the pooled (last) row of every sequence
-    p.total = align_up(off, WS_ALIGN);
+    p.off_x = ws.take((size_t)rows * c->width * 4);     // residual stream, fp32
+    p.off_h = ws.take((size_t)rows * c->width * 2);     // normalised rows, bf16
+    p.off_a = ws.take((size_t)rows * aw * 2);           // attention output, bf16
+    p.off_big = ws.take((size_t)rows * big * 2);        // qkv, then (up | gate)
+    p.off_rows = ws.take((size_t)nseq * 4);             // the pooled (last) row of every sequence
+    p.total = ws.end();
     return p;
 }
 int check_cfg(const mq_qwen_cfg* c) {
     MQ_CHECK_ARG(c, "mq_encode_qwen: null cfg");
     MQ_CHECK_ARG(c->head_dim == 64 || c->head_dim == 128, "mq_encode_qwen: head_dim %d unsupported (64 or 128)", c->head_dim);
-    MQ_CHECK_ARG(c->q_heads >= 1 && c->kv_heads >= 1 && c->q_heads % c->kv_heads == 0, "mq_encode_qwen: q_heads %d must be a multiple of kv_heads %d",
-                 c->q_heads, c->kv_heads);
-    MQ_CHECK_ARG(c->width >= 64 && c->width % 64 == 0, "mq_encode_qwen: width %d must be a multiple of 64", c->width);
+    MQ_TRY(check_gqa_shape("mq_encode_qwen", c->q_heads, c->kv_heads, c->width));
     MQ_CHECK_ARG(c->width <= 2048, "mq_encode_qwen: width %d > 2048 (the 4B / 8B sizes of this family are not served)", c->width);
-    MQ_CHECK_ARG(c->mlp_dim >= 64 && c->mlp_dim % 64 == 0, "mq_encode_qwen: mlp_dim %d must be a multiple of 64", c->mlp_dim);
-    MQ_CHECK_ARG(c->layers >= 1 && c->vocab >= 1, "mq_encode_qwen: layers %d / vocab %d", c->layers, c->vocab);
-    MQ_CHECK_ARG(c->max_pos >= 1 && c->max_pos <= 8192, "mq_encode_qwen: max_pos %d outside [1, 8192]", c->max_pos);
+    MQ_TRY(check_tower_sizes("mq_encode_qwen", c->mlp_dim, c->layers, c->vocab, c->max_pos));
     MQ_CHECK_ARG(c->pool == MQ_POOL_MEAN || c->pool == MQ_POOL_LAST, "mq_encode_qwen: bad pooling %d (MQ_POOL_MEAN or MQ_POOL_LAST)", c->pool);
     return MQ_OK;
 }
@@ -195,17 +191,11 @@ extern "C" int mq_encode_qwen(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, 
         MQ_CHECK_ARG((b.q_norm_g == nullptr) == (b.k_norm_g == nullptr), "mq_encode_qwen: layer %d has one of q_norm / k_norm only", l);
     }
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_ids && d_cu_seqlens && h_cu_seqlens && d_workspace, "mq_encode_qwen: null input / workspace");
-    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "mq_encode_qwen: cu_seqlens[0] must be 0");
     int maxl = 0;
-    for (int64_t i = 0; i < nseq; ++i) {
-        const int ln = h_cu_seqlens[i + 1] - h_cu_seqlens[i];
-        MQ_CHECK_ARG(ln >= 1 && ln <= cfg->max_pos, "mq_encode_qwen: sequence lengths must be in [1, max_pos=%d]", cfg->max_pos);
-        maxl = ln > maxl ? ln : maxl;
-    }
-    const int64_t rows = h_cu_seqlens[nseq];
+    int64_t rows = 0;
+    MQ_TRY(packed_begin("mq_encode_qwen", d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
     const Plan p = plan(cfg, rows, nseq);
-    if (workspace_bytes < p.total) { mq_set_error("mq_encode_qwen: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    MQ_TRY(packed_workspace("mq_encode_qwen", workspace_bytes, p.total));
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)(base + p.off_x);

@@ -7,7 +7,8 @@
 //   * mq_score_pairs_bert: typed embedding -> encoder (the [CLS] row selection of mq_encode_bert) -> head.
 //   * mq_score_pairs_xlmr: the same with mq_encode_bert's own embedding (one type row; the position table starts at the offset row).
 // All of it is bandwidth-trivial next to the encoder: coalesced, bounds-guarded, untuned.
-#include "common.h"
+// WS_ALIGN and score_pairs' packed-sequence checks are packed_text.h's.
+#include "packed_text.h"
 
 int mq_cast_bf16(const float* d_x, void* d_out, int64_t n, hipStream_t s);   // rowops.hip
 
@@ -15,7 +16,6 @@ static_assert(sizeof(mq_score_head_weights) == 32, "mq_score_head_weights layout
 
 namespace {
 constexpr int MAXC = 8;          // W <= 2048
-constexpr size_t WS_ALIGN = 256;
 
 // ---- LongestFirst truncation of a pair to B pieces ----------------------------------------------------------------------------------
 // tokenizers' truncate_encodings: n1 = the shorter (the FIRST text on a tie), n2 = n1 when n1 > B else max(n1, B - n1); when that
@@ -310,18 +310,13 @@ int score_pairs(const char* what, const mq_bert_cfg* cfg, const mq_bert_weights*
     MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "%s: W=%d must be a multiple of 64, at most %d", what, W, 64 * 4 * MAXC);
     MQ_CHECK_ARG(nseq < (1ll << 31), "%s: nseq=%lld too large", what, (long long)nseq);
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_ids && (d_type_ids || !typed) && d_cu_seqlens && h_cu_seqlens && d_workspace, "%s: null input / workspace", what);
-    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "%s: cu_seqlens[0] must be 0", what);
+    MQ_CHECK_ARG(d_type_ids || !typed, "%s: null input / workspace", what);
     int maxl = 0;
-    for (int64_t i = 0; i < nseq; ++i) {
-        const int l = h_cu_seqlens[i + 1] - h_cu_seqlens[i];
-        MQ_CHECK_ARG(l >= 1 && l <= cfg->max_pos, "%s: sequence lengths must be in [1, max_pos=%d]", what, cfg->max_pos);
-        if (l > maxl) maxl = l;
-    }
-    const int64_t rows = h_cu_seqlens[nseq];
+    int64_t rows = 0;
+    MQ_TRY(packed_begin(what, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
     const PairsPlan p = pairs_plan(cfg, rows, nseq);
     const size_t enc_need = mq_encoder_workspace_bytes(&cfg->enc, rows, nseq);
-    if (workspace_bytes < p.total) { mq_set_error("%s: workspace %zu < required %zu", what, workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    MQ_TRY(packed_workspace(what, workspace_bytes, p.total));
     if (p.enc_bytes < enc_need) { mq_set_error("%s: encoder scratch %zu < required %zu", what, p.enc_bytes, enc_need); return MQ_ERR_WORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;

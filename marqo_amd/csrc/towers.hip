@@ -4,7 +4,8 @@
 //   BERT encoder + pooling   (transformers BertModel + hugging_face_model.py:172-214)
 // Residual stream is fp32 (what fp16-autocast keeps it as in the reference's cuda path:
 // open_clip_model.py:255-260), GEMM inputs bf16, accumulation / LN statistics / softmax fp32.
-#include "common.h"
+// The workspace bump helper (Off) and the packed-sequence checks of the two text entry points are packed_text.h's.
+#include "packed_text.h"
 #include "knobs.h"
 
 // kernels in the sibling translation units
@@ -164,20 +165,6 @@ inline int attn_bf16(const mq_encoder_cfg* cfg, const void* qf, void* a, const i
 }  // namespace
 
 namespace {
-
-constexpr size_t WS_ALIGN = 256;
-
-// bump allocator over the caller's workspace: take() returns the (256-B aligned) OFFSET
-struct Off {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        off = align_up(off, WS_ALIGN);
-        const size_t o = off;
-        off += bytes;
-        return o;
-    }
-    size_t end() const { return align_up(off, WS_ALIGN); }
-};
 
 int check_encoder_cfg(const mq_encoder_cfg* c) {
     MQ_CHECK_ARG(c, "encoder cfg is null");
@@ -926,16 +913,6 @@ TextPlan text_plan(const mq_encoder_cfg* enc, int64_t rows, int64_t nseq) {
     p.total = p.off_enc + encoder_ws(enc, rows);
     return p;
 }
-int max_seq_len(const int32_t* h_cu, int64_t nseq, int64_t* rows_out) {
-    int mx = 0;
-    for (int64_t i = 0; i < nseq; ++i) {
-        const int l = h_cu[i + 1] - h_cu[i];
-        if (l < 1) return -1;
-        if (l > mx) mx = l;
-    }
-    *rows_out = h_cu[nseq] - h_cu[0];
-    return mx;
-}
 }  // namespace
 
 extern "C" size_t mq_clip_text_workspace_bytes(const mq_clip_text_cfg* cfg, int64_t rows, int64_t nseq) {
@@ -959,7 +936,7 @@ extern "C" int mq_encode_clip_text(const mq_clip_text_cfg* cfg, const mq_clip_te
     MQ_CHECK_ARG(maxl >= 1 && maxl <= cfg->ctx + (cfg->cls_pos > 0 ? 1 : 0), "mq_encode_clip_text: sequence lengths must be in [1, ctx=%d]", cfg->ctx);
     MQ_CHECK_ARG(cfg->cls_pos >= 0 && cfg->cls_pos < cfg->ctx, "mq_encode_clip_text: cls_pos %d outside the position table [0, %d)", cfg->cls_pos, cfg->ctx);
     const TextPlan p = text_plan(&cfg->enc, rows, nseq);
-    if (workspace_bytes < p.total) { mq_set_error("mq_encode_clip_text: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    MQ_TRY(packed_workspace("mq_encode_clip_text", workspace_bytes, p.total));
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)(base + p.off_x);
@@ -1011,13 +988,11 @@ extern "C" int mq_encode_bert(const mq_bert_cfg* cfg, const mq_bert_weights* w, 
                      "(<= 3 W: the MLP head) or neither (one biased Linear)");
     MQ_CHECK_ARG(w->word_emb && (w->pos_emb || cfg->enc.d_rope_inv_freq) && w->emb_ln_g && w->emb_ln_b, "mq_encode_bert: null weight pointer");
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_ids && d_cu_seqlens && h_cu_seqlens && d_workspace, "mq_encode_bert: null input / workspace");
-    MQ_CHECK_ARG(h_cu_seqlens[0] == 0, "mq_encode_bert: cu_seqlens[0] must be 0");
+    int maxl = 0;
     int64_t rows = 0;
-    const int maxl = max_seq_len(h_cu_seqlens, nseq, &rows);
-    MQ_CHECK_ARG(maxl >= 1 && maxl <= cfg->max_pos, "mq_encode_bert: sequence lengths must be in [1, max_pos=%d]", cfg->max_pos);
+    MQ_TRY(packed_begin("mq_encode_bert", d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
     const TextPlan p = text_plan(&cfg->enc, rows, nseq);
-    if (workspace_bytes < p.total) { mq_set_error("mq_encode_bert: workspace %zu < required %zu", workspace_bytes, p.total); return MQ_ERR_WORKSPACE; }
+    MQ_TRY(packed_workspace("mq_encode_bert", workspace_bytes, p.total));
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)(base + p.off_x);

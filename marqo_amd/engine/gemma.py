@@ -7,22 +7,21 @@ bf16 GEMM operands, fp32 residual stream, 256-wide heads.  The checkpoint-to-ten
 activation) applied to the pooled rows in front of the L2 normalisation — the `sbert` pipeline of the model card; the bare encoder (`hf`) has none."""
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Dict, Sequence
 
-import numpy as np
 import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine.archs import GemmaArch
 from marqo_amd.engine.tower_weights import gemma_state_dict
-from marqo_amd.engine.towers import _TextTowerBase, _check_precision, _host_i64, _large_call
+from marqo_amd.engine.towers import _PackedTextTower, _check_precision
 
 Tensor = torch.Tensor
 
 
-class GemmaTower(_TextTowerBase):
-    """EmbeddingGemma encoder + mean / CLS pooling (+ Dense modules) (+ L2), the interface of BertTower: encode_ids(ids, attention_mask, normalize)."""
+class GemmaTower(_PackedTextTower):
+    """EmbeddingGemma encoder + mean / CLS pooling (+ Dense modules) (+ L2); the call loop and the input checks are _PackedTextTower's."""
+    family = "gemma"
 
     def __init__(self, arch: GemmaArch, sd: Dict[str, Tensor], device: str, pooling: str = "mean", precision: str = "bf16",
                  dense: Sequence[Tensor] = ()):
@@ -73,11 +72,8 @@ class GemmaTower(_TextTowerBase):
     def out_width(self) -> int:
         return self._out_width
 
-    def release_unused_folded(self) -> int:
-        return 0     # (no folded norm copies are made for this tower)
-
-    def queue_rows_ids(self, ids_h: np.ndarray, mask_h: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
-        return None  # (the native request queue serves mq_encode_bert / mq_encode_clip_text: this tower keeps the direct path)
+    def _tail(self):
+        return self._apply_dense if self._dense else None
 
     def _apply_dense(self, rows: Tensor, normalize: bool) -> Tensor:
         """pooled fp32 [n, W] -> Dense modules on the bf16 GEMM (fp32 out) -> L2 when asked"""
@@ -92,30 +88,3 @@ class GemmaTower(_TextTowerBase):
         if normalize:
             L.check(self.lib.mq_l2_normalize(x.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1], s), "mq_l2_normalize")
         return x
-
-    def encode_ids(self, ids: Tensor, attention_mask: Tensor, normalize: bool = True) -> Tensor:
-        """ids / attention_mask: int [n, S], right-padded.  Only mask == 1 tokens are run: attention is bidirectional over the real tokens of a sequence,
-        padded positions are masked keys in the reference and neither pooling reads one -> fp32 [n, out_width] on the device."""
-        if ids.shape != attention_mask.shape or ids.ndim != 2:
-            raise ValueError("ids and attention_mask must both be [n, S]")
-        ids_h, mask_h = _host_i64(ids), _host_i64(attention_mask)
-        n, S = ids_h.shape
-        lengths = mask_h.sum(axis=1)
-        if bool((lengths < 1).any()):
-            raise ValueError("every sequence needs at least one unmasked token")
-        if not bool(((mask_h != 0) == (np.arange(S)[None, :] < lengths[:, None])).all()):
-            raise ValueError("attention_mask must be right-padded (a prefix of ones per row); left-padded input is not served")
-        if n and int(lengths.max()) > self.arch.max_pos:
-            raise ValueError(f"sequence longer than max_position_embeddings={self.arch.max_pos}")
-        out = torch.empty(n, self.arch.width, dtype=torch.float32, device=self.device)
-        tower_l2 = bool(normalize) and not self._dense
-        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
-            for a, b in self._chunks(lengths):
-                d_packed, d_cu, cu = self._stage_host(ids_h, lengths, a, b)
-                ws = self._workspace(self.lib.mq_gemma_workspace_bytes(C.byref(self.cfg), d_packed.numel(), b - a))
-                L.check(self.lib.mq_encode_gemma(C.byref(self.cfg), C.byref(self.w), d_packed.data_ptr(), d_cu.data_ptr(), cu.data_ptr(), b - a,
-                                                 out[a:b].data_ptr(), 1 if tower_l2 else 0, ws.data_ptr(), ws.numel(), self._stream()),
-                        "mq_encode_gemma")
-            if self._dense:
-                out = self._apply_dense(out, bool(normalize))
-        return out

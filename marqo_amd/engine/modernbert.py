@@ -5,22 +5,21 @@ bf16 GEMM operands, fp32 residual stream, 64-wide heads.  The checkpoint-to-tens
 engine/tower_weights.py::modernbert_state_dict."""
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, Optional
+from typing import Dict
 
-import numpy as np
 import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine.archs import ModernBertArch
 from marqo_amd.engine.tower_weights import modernbert_state_dict
-from marqo_amd.engine.towers import _TextTowerBase, _check_precision, _host_i64, _large_call
+from marqo_amd.engine.towers import _PackedTextTower, _check_precision
 
 Tensor = torch.Tensor
 
 
-class ModernBertTower(_TextTowerBase):
-    """ModernBERT encoder + mean / CLS pooling (+ L2), the interface of BertTower: encode_ids(ids, attention_mask, normalize)."""
+class ModernBertTower(_PackedTextTower):
+    """ModernBERT encoder + mean / CLS pooling (+ L2); the call loop and the input checks are _PackedTextTower's."""
+    family = "modernbert"
 
     def __init__(self, arch: ModernBertArch, sd: Dict[str, Tensor], device: str, pooling: str = "mean", precision: str = "bf16"):
         super().__init__(device)
@@ -50,37 +49,3 @@ class ModernBertTower(_TextTowerBase):
             layers=self._layers)
         self.cfg = L.ModernBertCfg(width=W, layers=arch.layers, heads=arch.heads, mlp_dim=arch.mlp_dim, vocab=arch.vocab, max_pos=arch.max_pos,
                                    half_window=arch.half_window, pool=L.MQ_POOL_MEAN if pooling == "mean" else L.MQ_POOL_CLS, ln_eps=arch.ln_eps, reserved=0)
-
-    @property
-    def out_width(self) -> int:
-        return self.arch.width
-
-    def release_unused_folded(self) -> int:
-        return 0     # (no folded LayerNorm copies are made for this tower)
-
-    def queue_rows_ids(self, ids_h: np.ndarray, mask_h: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
-        return None  # (the native request queue serves mq_encode_bert / mq_encode_clip_text: this tower keeps the direct path)
-
-    def encode_ids(self, ids: Tensor, attention_mask: Tensor, normalize: bool = True) -> Tensor:
-        """ids / attention_mask: int [n, S], right-padded.  Only mask == 1 tokens are run (padded keys are masked out of every real row in the
-        reference, and padded rows are not pooled) -> fp32 [n, width] on the device."""
-        if ids.shape != attention_mask.shape or ids.ndim != 2:
-            raise ValueError("ids and attention_mask must both be [n, S]")
-        ids_h, mask_h = _host_i64(ids), _host_i64(attention_mask)
-        n, S = ids_h.shape
-        lengths = mask_h.sum(axis=1)
-        if bool((lengths < 1).any()):
-            raise ValueError("every sequence needs at least one unmasked token")
-        if not bool(((mask_h != 0) == (np.arange(S)[None, :] < lengths[:, None])).all()):
-            raise ValueError("attention_mask must be right-padded (a prefix of ones per row)")
-        if n and int(lengths.max()) > self.arch.max_pos:
-            raise ValueError(f"sequence longer than max_position_embeddings={self.arch.max_pos}")
-        out = torch.empty(n, self.arch.width, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
-            for a, b in self._chunks(lengths):
-                d_packed, d_cu, cu = self._stage_host(ids_h, lengths, a, b)
-                ws = self._workspace(self.lib.mq_modernbert_workspace_bytes(C.byref(self.cfg), d_packed.numel(), b - a))
-                L.check(self.lib.mq_encode_modernbert(C.byref(self.cfg), C.byref(self.w), d_packed.data_ptr(), d_cu.data_ptr(), cu.data_ptr(), b - a,
-                                                      out[a:b].data_ptr(), 1 if normalize else 0, ws.data_ptr(), ws.numel(), self._stream()),
-                        "mq_encode_modernbert")
-        return out

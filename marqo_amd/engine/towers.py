@@ -886,6 +886,22 @@ def _pack(ids: np.ndarray, lengths: np.ndarray) -> Tuple[Tensor, Tensor]:
     return torch.from_numpy(packed), torch.from_numpy(cu)
 
 
+def _ids_and_lengths(ids, attention_mask, max_pos: int) -> Tuple[np.ndarray, np.ndarray]:
+    """right-padded (ids, attention_mask), int [n, S] each -> (ids, lengths) as host int64 ndarrays; the inputs every mask-taking tower refuses"""
+    if ids.shape != attention_mask.shape or ids.ndim != 2:
+        raise ValueError("ids and attention_mask must both be [n, S]")
+    ids_h, mask_h = _host_i64(ids), _host_i64(attention_mask)
+    n, S = ids_h.shape
+    lengths = mask_h.sum(axis=1)
+    if bool((lengths < 1).any()):
+        raise ValueError("every sequence needs at least one unmasked token")
+    if not bool(((mask_h != 0) == (np.arange(S)[None, :] < lengths[:, None])).all()):
+        raise ValueError("attention_mask must be right-padded (a prefix of ones per row); left-padded input is not served")
+    if n and int(lengths.max()) > max_pos:
+        raise ValueError(f"sequence longer than max_position_embeddings={max_pos}")
+    return ids_h, lengths
+
+
 class _TextTowerBase(_TowerBase):
     # rows (tokens) per engine call.  Towers may lower it: the post-LN BERT encoders (fp32 stream: ~10 KB of activations per row and layer) run
     # 4-6 % faster per item at 20-40 k rows per call than at 79 k (profiles/r03v_batch_sweep.txt); the pre-LN towers do not (ViT-L/14: larger is better)
@@ -1051,6 +1067,45 @@ class _TextTowerBase(_TowerBase):
                 d_packed, d_cu, cu, d_pool = stage(a, b)
                 rows, nseq = d_packed.numel(), b - a
                 self._call_text(clip, d_packed, d_cu, cu, nseq, d_pool, out[a:b], normalize, self._workspace(ws_bytes(C.byref(self.cfg), rows, nseq)))
+        return out
+
+
+class _PackedTextTower(_TextTowerBase):
+    """A text tower that is one library call per batch of packed sequences, behind the host scaffold of csrc/packed_text.h (ModernBERT, Qwen, Gemma),
+    with the interface of BertTower: encode_ids(ids, attention_mask, normalize).  A subclass is its constructor — it validates the arch and builds
+    self.arch / self.cfg / self.w — and `family`, which names its two library functions."""
+    family = ""        # "qwen": mq_encode_qwen, mq_qwen_workspace_bytes
+
+    @property
+    def out_width(self) -> int:
+        return self.arch.width
+
+    def release_unused_folded(self) -> int:
+        return 0     # (no folded norm copies are made for these towers)
+
+    def queue_rows_ids(self, ids_h: np.ndarray, mask_h: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
+        return None  # (the native request queue serves mq_encode_bert / mq_encode_clip_text: these towers keep the direct path)
+
+    def _tail(self):
+        """None, or `tail(rows, normalize)`: what follows the tower on the pooled rows of a call; the L2 normalisation is then the tail's"""
+        return None
+
+    def encode_ids(self, ids: Tensor, attention_mask: Tensor, normalize: bool = True) -> Tensor:
+        """ids / attention_mask: int [n, S], right-padded.  Only mask == 1 tokens are run (no padded position reaches a real row in the reference, and no
+        pooling reads one) -> fp32 [n, out_width] on the device."""
+        ids_h, lengths = _ids_and_lengths(ids, attention_mask, self.arch.max_pos)
+        name = f"mq_encode_{self.family}"
+        ws_bytes, encode, tail = getattr(self.lib, f"mq_{self.family}_workspace_bytes"), getattr(self.lib, name), self._tail()
+        tower_l2 = 1 if normalize and tail is None else 0
+        out = torch.empty(int(lengths.size), self.arch.width, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):
+            for a, b in self._chunks(lengths):
+                d_packed, d_cu, cu = self._stage_host(ids_h, lengths, a, b)
+                ws = self._workspace(ws_bytes(C.byref(self.cfg), d_packed.numel(), b - a))
+                L.check(encode(C.byref(self.cfg), C.byref(self.w), d_packed.data_ptr(), d_cu.data_ptr(), cu.data_ptr(), b - a, out[a:b].data_ptr(),
+                               tower_l2, ws.data_ptr(), ws.numel(), self._stream()), name)
+            if tail is not None:
+                out = tail(out, bool(normalize))
         return out
 
 
@@ -1367,23 +1422,11 @@ class BertTower(_TextTowerBase):
     def encode_ids(self, ids: Tensor, attention_mask: Tensor, normalize: bool = True) -> Tensor:
         """ids / attention_mask: int [n, S] as produced by the HF tokenizer call of the reference
         (hugging_face_model.py:179-185: padding=True, right-padded).  Only mask==1 tokens are run."""
-        if ids.shape != attention_mask.shape or ids.ndim != 2:
-            raise ValueError("ids and attention_mask must both be [n, S]")
-        ids_h = _host_i64(ids)
-        mask_h = _host_i64(attention_mask)
-        n, S = ids_h.shape
-        lengths = mask_h.sum(axis=1)
-        if bool((lengths < 1).any()):
-            raise ValueError("every sequence needs at least one unmasked token")
-        prefix = np.arange(S)[None, :] < lengths[:, None]
-        if not bool(((mask_h != 0) == prefix).all()):
-            raise ValueError("attention_mask must be right-padded (a prefix of ones per row)")
-        if n and int(lengths.max()) > self.arch.max_pos:
-            raise ValueError(f"sequence longer than max_position_embeddings={self.arch.max_pos}")
+        ids_h, lengths = _ids_and_lengths(ids, attention_mask, self.arch.max_pos)
         small = self._small_call(ids_h, lengths, normalize, clip=False)
         if small is not None:
             return small
-        if n == 1 and self._graphs_ok():
+        if lengths.size == 1 and self._graphs_ok():
             one = self._encode_one(torch.from_numpy(ids_h[0, :int(lengths[0])]), normalize, clip=False)
             if one is not None:
                 return one

@@ -200,33 +200,50 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         `tokenizers` library from the directory's tokenizer.json, the tower of engine/modernbert.py.  bf16 operands only."""
         from marqo_amd.engine.modernbert import ModernBertTower
         from marqo_amd.engine.tokenizers import HfJsonTokenizer
-        props = self.model_properties
-        if props.engine_precision == "fp8":
-            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for ModernBERT encoders (their rotary / "
-                                              f"gated-GELU blocks run on bf16 operands only)")
-        if self._check_dimensions and arch.width != props.dimensions:
-            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {arch.width}")
-        try:
-            self._tokenizer = HfJsonTokenizer(directory, **self._special_tokens(directory, cls="[CLS]", sep="[SEP]", pad="[PAD]"))
-        except ValueError as e:
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        props.tokens = min(props.tokens, arch.max_pos)
-        self._refuse_last_pooling()
-        pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
-        self.arch = arch
-        self.weights_source = directory
-        try:
-            self._model = ModernBertTower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision)
-        except (ValueError, KeyError) as e:   # a missing / mis-shaped tensor, bias tensors
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        self._pooling_func = pooling
-        self._device_tokenizer = None   # (the GPU byte-level BPE tokeniser does not implement this family's added-token / whitespace-token handling)
+        self._refuse_fp8("ModernBERT encoders (their rotary / gated-GELU blocks run on bf16 operands only)")
+        self._check_width(arch.width)
+        self._finish_packed(directory, arch, arch.max_pos, ModernBertTower, sd,
+                            lambda: HfJsonTokenizer(directory, **self._special_tokens(directory, cls="[CLS]", sep="[SEP]", pad="[PAD]")))
 
     def _refuse_last_pooling(self) -> None:
         """'last' is the pooling of the decoder-style checkpoints only: every other family refuses it as the property parser did before it knew the word"""
         if self.model_properties.pooling_method == "last":
             raise InvalidModelPropertiesError(f"Invalid model properties: {self.model_properties.dict()}. Original error "
                                               f"{HuggingFaceModelProperties.POOLING_ERROR}")
+
+    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma) share ----------------------------------------------------------
+    def _refuse_fp8(self, family: str) -> None:
+        props = self.model_properties
+        if props.engine_precision == "fp8":
+            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for {family}")
+
+    def _check_width(self, width: int) -> None:
+        props = self.model_properties
+        if self._check_dimensions and width != props.dimensions:
+            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {width}")
+
+    def _finish_packed(self, directory: str, arch, max_tokens: int, tower, sd, tokenizer, pooling: Optional[str] = None, **tower_args) -> None:
+        """the tokenizer (`tokenizer()`: an HfJsonTokenizer), the truncation length, the pooling — None: the BERT rule (the property, 'last' refused, else
+        1_Pooling/config.json, else mean) — and the tower; a ValueError / KeyError of either constructor (a tokenizer.json without the expected tokens, a
+        missing / mis-shaped / unexpected tensor, a Dense module that does not fit) is the caller's InvalidModelPropertiesError.  These families have no
+        GPU tokeniser (the byte-level BPE one does not implement their added-token handling)."""
+        props = self.model_properties
+        try:
+            self._tokenizer = tokenizer()
+        except ValueError as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        props.tokens = min(props.tokens, max_tokens)
+        if pooling is None:
+            self._refuse_last_pooling()
+            pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
+        self.arch = arch
+        self.weights_source = directory
+        try:
+            self._model = tower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision, **tower_args)
+        except (ValueError, KeyError) as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        self._pooling_func = pooling
+        self._device_tokenizer = None
 
     def _load_qwen(self, directory: str, arch, cfg: dict, sd) -> None:
         """a transformers Qwen3Model / Qwen2Model checkpoint (model_type "qwen3" / "qwen2": Qwen3-Embedding-0.6B, gte-Qwen2-1.5B-instruct ...; AutoModel in
@@ -236,11 +253,8 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         from marqo_amd.engine.qwen import QwenTower
         from marqo_amd.engine.tokenizers import HfJsonTokenizer
         props = self.model_properties
-        if props.engine_precision == "fp8":
-            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for Qwen3 / Qwen2 encoders (their RMSNorm / rotary / "
-                                              f"gated-SiLU blocks run on bf16 operands only)")
-        if self._check_dimensions and arch.width != props.dimensions:
-            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {arch.width}")
+        self._refuse_fp8("Qwen3 / Qwen2 encoders (their RMSNorm / rotary / gated-SiLU blocks run on bf16 operands only)")
+        self._check_width(arch.width)
         pooling = props.pooling_method
         if pooling is None:
             try:
@@ -253,19 +267,8 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         pooling = pooling or "last"
         if pooling not in ("last", "mean"):
             raise InvalidModelPropertiesError(f"{props.name}: pooling_method {pooling!r} is not available for Qwen3 / Qwen2 encoders ('last' or 'mean')")
-        try:
-            self._tokenizer = HfJsonTokenizer.plain(directory)
-        except ValueError as e:
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        props.tokens = min(props.tokens, int(cfg.get("max_position_embeddings", 8192)), 8192)
-        self.arch = arch
-        self.weights_source = directory
-        try:
-            self._model = QwenTower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision)
-        except (ValueError, KeyError) as e:   # a missing / mis-shaped tensor, unexpected bias tensors
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        self._pooling_func = pooling
-        self._device_tokenizer = None   # (the GPU byte-level BPE tokeniser does not implement this family's added-token handling)
+        self._finish_packed(directory, arch, min(int(cfg.get("max_position_embeddings", 8192)), 8192), QwenTower, sd,
+                            lambda: HfJsonTokenizer.plain(directory), pooling=pooling)
 
     # sentence-transformers Dense module directories (relative to the checkpoint) to apply behind the pooling: set by the `sbert` loader for an
     # EmbeddingGemma pipeline, empty for `hf` (AutoModel in the reference: the bare encoder)
@@ -279,32 +282,13 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         bf16 operands only."""
         from marqo_amd.engine.gemma import GemmaTower
         from marqo_amd.engine.tokenizers import HfJsonTokenizer
-        props = self.model_properties
-        if props.engine_precision == "fp8":
-            raise InvalidModelPropertiesError(f"{props.name}: 'enginePrecision': 'fp8' is not available for EmbeddingGemma encoders (their RMSNorm / "
-                                              f"rotary / gated tanh-GELU blocks run on bf16 operands only)")
+        self._refuse_fp8("EmbeddingGemma encoders (their RMSNorm / rotary / gated tanh-GELU blocks run on bf16 operands only)")
         try:
             dense = [self._read_dense_module(directory, d) for d in self._dense_modules]
         except (OSError, ValueError, KeyError) as e:
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        out_width = dense[-1].shape[0] if dense else arch.width
-        if self._check_dimensions and out_width != props.dimensions:
-            raise InvalidModelPropertiesError(f"'dimensions'={props.dimensions} but the encoder width is {out_width}")
-        try:
-            self._tokenizer = HfJsonTokenizer.plain(directory, pad_fallback="<pad>")
-        except ValueError as e:
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        props.tokens = min(props.tokens, arch.max_pos)
-        self._refuse_last_pooling()
-        pooling = props.pooling_method or checkpoint.read_pooling_config(directory) or "mean"
-        self.arch = arch
-        self.weights_source = directory
-        try:
-            self._model = GemmaTower(arch, sd, self.device, pooling=pooling, precision=props.engine_precision, dense=dense)
-        except (ValueError, KeyError) as e:   # a missing / mis-shaped tensor, bias tensors, a Dense module that does not fit
-            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
-        self._pooling_func = pooling
-        self._device_tokenizer = None   # (no GPU tokeniser for this vocabulary)
+            raise InvalidModelPropertiesError(f"{self.model_properties.name}: {e}") from e
+        self._check_width(dense[-1].shape[0] if dense else arch.width)
+        self._finish_packed(directory, arch, arch.max_pos, GemmaTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="<pad>"), dense=dense)
 
     @staticmethod
     def _read_dense_module(directory: str, sub: str):
