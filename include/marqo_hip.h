@@ -1252,6 +1252,42 @@ size_t mq_modernbert_workspace_bytes(const mq_modernbert_cfg* cfg, int64_t rows,
 int mq_encode_modernbert(const mq_modernbert_cfg* cfg, const mq_modernbert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                          const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- text reranking on the ModernBERT tower (csrc/rerank.hip; engine/rerank.py ModernBertCrossEncoderTower) --------------------------------
+ * transformers' ModernBertForSequenceClassification with num_labels = 1 (gte-reranker-modernbert-base, reranker-ModernBERT-*-gooaq-bce, the
+ * cross-encoder/ms-marco-ModernBERT-* shape): the encoder of mq_encode_modernbert, mean or CLS pooling of the final-normed rows, and a head that is
+ * NOT mq_score_head's: dense -> erf GELU -> LayerNorm -> one-logit classifier (dropout does nothing at inference).  Pairs are planned and packed by
+ * mq_pair_plan_n / mq_pack_pairs with specials = 3 ([CLS] q [SEP] d [SEP]; the type ids mq_pack_pairs writes are not read).  Additions to ABI 15:
+ * nothing above changes.  Both entry
+ * points judge their arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), run on `stream` and
+ * allocate nothing.
+ *
+ *   mq_score_head_ln: d_h fp32 [n, W] (the pooled rows) -> a = gelu(dense_w bf16(h) + dense_b) (mq_gemm_bf16: bf16 operands, fp32 accumulation and
+ *                   output, the erf GELU of MQ_EPI_GELU in its epilogue; a head without dense_b adds a bias of zeros from the scratch), then one
+ *                   wave64 per pair: mu and rstd = rsqrt(mean((a - mu)^2) + ln_eps) in two passes over the row held in registers, and
+ *                   z = sum_j ((a_j - mu) rstd norm_g[j] + norm_b[j]) cls_w[j] + cls_b -> d_logits fp32 [n]; d_scores (NULL ok) = 1 / (1 + exp(-z)).
+ *                   The normalised row is never written.  W % 64 == 0, W <= 2048, n >= 1.  Scratch: mq_score_head_ln_workspace_bytes(n, W).
+ *   mq_score_pairs_modernbert: mq_encode_modernbert(cfg, w, ..., normalize = 0) into a scratch slot (d_pooled fp32 [nseq, W], NULL ok, receives a
+ *                   copy: bit-identical to that entry point on the same ids, because it IS that entry point) -> mq_score_head_ln.  The encoder's
+ *                   refusals (cfg, weights, sequence lengths) are mq_encode_modernbert's.  Scratch:
+ *                   mq_score_pairs_modernbert_workspace_bytes(cfg, rows, nseq). */
+typedef struct mq_score_head_ln_weights {
+    const void*  dense_w;    /* bf16 [W, W]: head.dense.weight */
+    const float* dense_b;    /* fp32 [W]: head.dense.bias, NULL when the config has classifier_bias = false */
+    const float* norm_g;     /* fp32 [W]: head.norm.weight */
+    const float* norm_b;     /* fp32 [W]: head.norm.bias, NULL when the config has norm_bias = false */
+    const float* cls_w;      /* fp32 [W]: classifier.weight (num_labels = 1) */
+    float        cls_b;      /* classifier.bias */
+    float        ln_eps;     /* norm_eps */
+} mq_score_head_ln_weights;
+
+size_t mq_score_head_ln_workspace_bytes(int64_t n, int32_t W);
+int mq_score_head_ln(const float* d_h, int64_t n, int32_t W, const mq_score_head_ln_weights* head, float* d_logits, float* d_scores,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+size_t mq_score_pairs_modernbert_workspace_bytes(const mq_modernbert_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_score_pairs_modernbert(const mq_modernbert_cfg* cfg, const mq_modernbert_weights* w, const mq_score_head_ln_weights* head,
+                              const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits,
+                              float* d_scores, float* d_pooled, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Qwen3 / Qwen2 text embedders: grouped-query causal attention and the tower (csrc/attention_gqa.hip, csrc/qwen.hip; engine/qwen.py) --------------
  * transformers' Qwen3Model / Qwen2Model (model_type "qwen3" / "qwen2": Qwen3-Embedding-0.6B, gte-Qwen2-1.5B-instruct, Qwen2-0.5B fine-tunes): pre-norm
  * decoder blocks with RMSNorm, fewer K/V heads than query heads, rotary positions, a gated-SiLU MLP, a causal mask and last-token (or mean) pooling.

@@ -208,6 +208,12 @@ class ModernBertCfg(C.Structure):
                 ("half_window", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+class ScoreHeadLnWeights(C.Structure):
+    """mq_score_head_ln_weights: ModernBERT's classification head, dense -> GELU -> LayerNorm -> one-logit classifier (csrc/rerank.hip)"""
+    _fields_ = [("dense_w", C.c_void_p), ("dense_b", C.c_void_p), ("norm_g", C.c_void_p), ("norm_b", C.c_void_p), ("cls_w", C.c_void_p),
+                ("cls_b", C.c_float), ("ln_eps", C.c_float)]
+
+
 class QwenLayer(C.Structure):
     """mq_qwen_layer: one Qwen3 / Qwen2 block (csrc/qwen.hip)"""
     _fields_ = [(n, C.c_void_p) for n in ("input_norm_g", "qkv_w", "qkv_b", "q_norm_g", "k_norm_g", "out_w", "post_norm_g", "ug_w", "down_w")]
@@ -390,6 +396,12 @@ _SIGNATURES = {
     "mq_attention_window": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_modernbert_workspace_bytes": (C.c_size_t, [C.POINTER(ModernBertCfg), C.c_int64, C.c_int64]),
     "mq_encode_modernbert": (C.c_int, [C.POINTER(ModernBertCfg), C.POINTER(ModernBertWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # text reranking on the ModernBERT tower: the LayerNorm head and the scoring call (csrc/rerank.hip; engine/rerank.py)
+    "mq_score_head_ln_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "mq_score_head_ln": (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(ScoreHeadLnWeights), _P, _P, _P, C.c_size_t, _P]),
+    "mq_score_pairs_modernbert_workspace_bytes": (C.c_size_t, [C.POINTER(ModernBertCfg), C.c_int64, C.c_int64]),
+    "mq_score_pairs_modernbert": (C.c_int, [C.POINTER(ModernBertCfg), C.POINTER(ModernBertWeights), C.POINTER(ScoreHeadLnWeights), _P, _P, _P, C.c_int64,
+                                            _P, _P, _P, _P, C.c_size_t, _P]),
     # Qwen3 / Qwen2 text embedders: grouped-query causal attention, RMSNorm, q/k norm + rotary, the tower (csrc/attention_gqa.hip, csrc/qwen.hip; engine/qwen.py)
     "mq_attention_gqa": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mq_rmsnorm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),

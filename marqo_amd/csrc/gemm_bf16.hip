@@ -672,6 +672,7 @@ extern "C" int mq_gemm_bf16(const void* d_A, int64_t lda, const void* d_W, int64
         MQ_GEMM_CASE(MQ_EPI_BIAS | MQ_EPI_OUT_F32);   // biased fp32 heads (M-CLIP LinearTransformation)
         MQ_GEMM_CASE(MQ_EPI_BIAS);
         MQ_GEMM_CASE(MQ_EPI_BIAS | MQ_EPI_GELU);
+        MQ_GEMM_CASE(MQ_EPI_BIAS | MQ_EPI_GELU | MQ_EPI_OUT_F32);   // the dense layer of ModernBERT's classification head (mq_score_head_ln)
         MQ_GEMM_CASE(MQ_EPI_BIAS | MQ_EPI_QUICKGELU);
         MQ_GEMM_CASE(MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32);
         MQ_GEMM_CASE(MQ_EPI_BIAS | MQ_EPI_RESIDUAL);   // bf16 residual in (d_residual is bf16), bf16 out

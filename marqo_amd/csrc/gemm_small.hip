@@ -299,6 +299,7 @@ int mq_gemm_small(const void* d_A, int64_t lda, const void* d_W, int64_t ldw, co
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_OUT_F32);
         MQ_SM_CASE(MQ_EPI_BIAS);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_GELU);
+        MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_GELU | MQ_EPI_OUT_F32);   // the dense layer of ModernBERT's classification head (mq_score_head_ln)
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_QUICKGELU);
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_RELU);   // fc1 of an MQ_ACT_RELU block (the NLLB text tower)
         MQ_SM_CASE(MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32);

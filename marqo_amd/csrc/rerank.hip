@@ -6,6 +6,8 @@
 //   * score_head: pooler (tanh(Linear), through mq_gemm_bf16) + the one-logit classifier (+ sigmoid).
 //   * mq_score_pairs_bert: typed embedding -> encoder (the [CLS] row selection of mq_encode_bert) -> head.
 //   * mq_score_pairs_xlmr: the same with mq_encode_bert's own embedding (one type row; the position table starts at the offset row).
+//   * score_head_ln: ModernBERT's classification head: dense + erf-GELU (mq_gemm_bf16's epilogue), then LayerNorm and the one-logit classifier
+//     fused in one wave64 per pair (+ sigmoid).  mq_score_pairs_modernbert: mq_encode_modernbert (normalize = 0) -> that head.
 // All of it is bandwidth-trivial next to the encoder: coalesced, bounds-guarded, untuned.
 // WS_ALIGN and score_pairs' packed-sequence checks are packed_text.h's.
 #include "packed_text.h"
@@ -13,6 +15,7 @@
 int mq_cast_bf16(const float* d_x, void* d_out, int64_t n, hipStream_t s);   // rowops.hip
 
 static_assert(sizeof(mq_score_head_weights) == 32, "mq_score_head_weights layout");   // (marqo_amd/_lib.py ScoreHeadWeights)
+static_assert(sizeof(mq_score_head_ln_weights) == 48, "mq_score_head_ln_weights layout");   // (marqo_amd/_lib.py ScoreHeadLnWeights)
 
 namespace {
 constexpr int MAXC = 8;          // W <= 2048
@@ -165,6 +168,58 @@ __global__ __launch_bounds__(256) void score_tail_kernel(const float* __restrict
         logits[r] = z;
         if (scores) scores[r] = 1.0f / (1.0f + expf(-z));
     }
+}
+
+// ---- LayerNorm + classifier on the dense layer's GELU output: one wave64 per pair --------------------------------------------------------
+// z = sum_j ((a_j - mu) rstd g_j + b_j) c_j + c_b.  Lane c holds columns c, c + 64, ... of the row (W / 64 <= 32 registers, read once); the mean
+// and the sum of squared deviations (two-pass, as ln_normalize_row) and the classifier's dot product each go through the xor butterfly.  The
+// normalised row exists in registers only.  norm_b may be null (no LayerNorm bias).
+constexpr int TAIL_LN_MAXJ = 4 * MAXC;     // columns per lane at W = 2048
+__global__ __launch_bounds__(256) void score_tail_ln_kernel(const float* __restrict__ a, const float* __restrict__ norm_g, const float* __restrict__ norm_b,
+                                                            const float* __restrict__ cls_w, float cls_b, float eps, int64_t n, int W,
+                                                            float* __restrict__ logits, float* __restrict__ scores) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;                    // (the whole wave leaves: r is wave-uniform)
+    const float* ar = a + r * W;
+    const int nc = W >> 6;
+    float v[TAIL_LN_MAXJ];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < TAIL_LN_MAXJ; ++i) {
+        v[i] = i < nc ? ar[lane + i * 64] : 0.f;
+        s += v[i];
+    }
+    const float mean = wave_sum(s) / (float)W;
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < TAIL_LN_MAXJ; ++i)
+        if (i < nc) { const float d = v[i] - mean; s2 = fmaf(d, d, s2); }
+    const float rstd = rsqrtf(wave_sum(s2) / (float)W + eps);
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < TAIL_LN_MAXJ; ++i)
+        if (i < nc) {
+            const int j = lane + i * 64;
+            const float y = fmaf((v[i] - mean) * rstd, norm_g[j], norm_b ? norm_b[j] : 0.f);
+            acc = fmaf(y, cls_w[j], acc);
+        }
+    const float z = wave_sum(acc) + cls_b;
+    if (lane == 0) {
+        logits[r] = z;
+        if (scores) scores[r] = 1.0f / (1.0f + expf(-z));
+    }
+}
+
+struct HeadLnPlan { size_t off_hb, off_a, off_zero, total; };
+HeadLnPlan head_ln_plan(int64_t n, int W) {
+    HeadLnPlan h;
+    Off ws;
+    h.off_hb = ws.take((size_t)n * W * 2);        // bf16 [n, W]: the pooled rows as the GEMM's operand
+    h.off_a = ws.take((size_t)n * W * 4);         // fp32 [n, W]: gelu(dense_w h + dense_b)
+    h.off_zero = ws.take((size_t)W * 4);          // fp32 [W] of zeros: the GEMM's bias when the head has none
+    h.total = ws.end();
+    return h;
 }
 
 struct HeadPlan { size_t off_hb, off_p, total; };
@@ -350,4 +405,87 @@ extern "C" int mq_score_pairs_xlmr(const mq_bert_cfg* cfg, const mq_bert_weights
                                    float* d_cls_rows, void* d_workspace, size_t workspace_bytes, void* stream) {
     return score_pairs("mq_score_pairs_xlmr", cfg, w, head, d_ids, nullptr, false, d_cu_seqlens, h_cu_seqlens, nseq, d_logits, d_scores,
                        d_cls_rows, d_workspace, workspace_bytes, stream);
+}
+
+// ---- ModernBERT cross-encoders ------------------------------------------------------------------------------------------------------------
+extern "C" size_t mq_score_head_ln_workspace_bytes(int64_t n, int32_t W) {
+    if (n <= 0 || W <= 0) return 0;
+    return head_ln_plan(n, W).total;
+}
+
+extern "C" int mq_score_head_ln(const float* d_h, int64_t n, int32_t W, const mq_score_head_ln_weights* head, float* d_logits, float* d_scores,
+                                void* d_workspace, size_t workspace_bytes, void* stream) {
+    MQ_CHECK_ARG(head, "mq_score_head_ln: null head");
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * TAIL_LN_MAXJ, "mq_score_head_ln: W=%d must be a multiple of 64, at most %d", W, 64 * TAIL_LN_MAXJ);
+    MQ_CHECK_ARG(n >= 1 && n < (1ll << 31), "mq_score_head_ln: n=%lld must be in [1, 2^31)", (long long)n);
+    MQ_CHECK_ARG(head->dense_w && head->norm_g && head->cls_w, "mq_score_head_ln: null weight pointer (dense_w / norm_g / cls_w)");
+    MQ_CHECK_ARG(head->ln_eps >= 0.f, "mq_score_head_ln: ln_eps=%g must not be negative", (double)head->ln_eps);
+    MQ_CHECK_ARG(d_h && d_logits && d_workspace, "mq_score_head_ln: null input / output / workspace");
+    const HeadLnPlan hp = head_ln_plan(n, W);
+    MQ_TRY(packed_workspace("mq_score_head_ln", workspace_bytes, hp.total));
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_workspace;
+    void* hb = base + hp.off_hb;
+    float* a = (float*)(base + hp.off_a);
+    const float* bias = head->dense_b;
+    if (!bias) {   // (the GEMM family has one fp32-out GELU epilogue, the biased one: a head without a dense bias adds zeros)
+        MQ_CHECK_HIP(hipMemsetAsync(base + hp.off_zero, 0, (size_t)W * 4, s));
+        bias = (const float*)(base + hp.off_zero);
+    }
+    MQ_TRY(mq_cast_bf16(d_h, hb, n * W, s));
+    MQ_TRY(mq_gemm_bf16(hb, W, head->dense_w, W, bias, nullptr, a, W, n, W, W, MQ_EPI_BIAS | MQ_EPI_GELU | MQ_EPI_OUT_F32, s));
+    MqProfScope prof(4, s);
+    hipLaunchKernelGGL(score_tail_ln_kernel, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, s, a, head->norm_g, head->norm_b, head->cls_w, head->cls_b,
+                       head->ln_eps, n, W, d_logits, d_scores);
+    MQ_CHECK_LAUNCH("mq_score_head_ln");
+    return MQ_OK;
+}
+
+namespace {
+struct PairsMbPlan { size_t off_enc, enc_bytes, off_pooled, off_head, total; };
+// [ mq_modernbert_workspace_bytes: the encoder's own scratch ] [ pooled rows fp32 [nseq, W] ] [ head scratch ]
+PairsMbPlan pairs_mb_plan(const mq_modernbert_cfg* cfg, int64_t rows, int64_t nseq) {
+    PairsMbPlan p;
+    Off ws;
+    p.enc_bytes = mq_modernbert_workspace_bytes(cfg, rows, nseq);
+    p.off_enc = ws.take(p.enc_bytes);
+    p.off_pooled = ws.take((size_t)nseq * cfg->width * 4);
+    p.off_head = ws.take(head_ln_plan(nseq, cfg->width).total);
+    p.total = ws.end();
+    return p;
+}
+}  // namespace
+
+extern "C" size_t mq_score_pairs_modernbert_workspace_bytes(const mq_modernbert_cfg* cfg, int64_t rows, int64_t nseq) {
+    if (!cfg || rows <= 0 || nseq <= 0 || cfg->width <= 0) return 0;
+    return pairs_mb_plan(cfg, rows, nseq).total;
+}
+
+// The encoder IS mq_encode_modernbert (normalize = 0, the cfg's pooling) writing into this call's pooled slot: the pooled rows cannot differ from
+// that entry point's.  What it refuses (cfg, weights, sequence lengths) it refuses here, under its own name; the checks below are this call's own.
+extern "C" int mq_score_pairs_modernbert(const mq_modernbert_cfg* cfg, const mq_modernbert_weights* w, const mq_score_head_ln_weights* head,
+                                         const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq,
+                                         float* d_logits, float* d_scores, float* d_pooled, void* d_workspace, size_t workspace_bytes,
+                                         void* stream) {
+    const char* what = "mq_score_pairs_modernbert";
+    MQ_CHECK_ARG(cfg && w, "%s: null cfg / weights", what);
+    MQ_CHECK_ARG(head, "%s: null head", what);
+    MQ_CHECK_ARG(cfg->pool == MQ_POOL_MEAN || cfg->pool == MQ_POOL_CLS, "%s: bad pooling %d (MQ_POOL_MEAN or MQ_POOL_CLS)", what, cfg->pool);
+    const int W = cfg->width;
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * TAIL_LN_MAXJ, "%s: W=%d must be a multiple of 64, at most %d", what, W, 64 * TAIL_LN_MAXJ);
+    MQ_CHECK_ARG(head->dense_w && head->norm_g && head->cls_w, "%s: null weight pointer (dense_w / norm_g / cls_w)", what);
+    MQ_CHECK_ARG(head->ln_eps >= 0.f, "%s: ln_eps=%g must not be negative", what, (double)head->ln_eps);
+    MQ_CHECK_ARG(nseq >= 1 && nseq < (1ll << 31), "%s: nseq=%lld must be in [1, 2^31)", what, (long long)nseq);
+    MQ_CHECK_ARG(d_logits, "%s: null output", what);
+    int maxl = 0;
+    int64_t rows = 0;
+    MQ_TRY(packed_begin(what, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
+    const PairsMbPlan p = pairs_mb_plan(cfg, rows, nseq);
+    MQ_TRY(packed_workspace(what, workspace_bytes, p.total));
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_workspace;
+    float* pooled = (float*)(base + p.off_pooled);
+    MQ_TRY(mq_encode_modernbert(cfg, w, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, pooled, 0, base + p.off_enc, p.enc_bytes, stream));
+    if (d_pooled) MQ_CHECK_HIP(hipMemcpyAsync(d_pooled, pooled, (size_t)nseq * W * 4, hipMemcpyDeviceToDevice, s));
+    return mq_score_head_ln(pooled, nseq, W, head, d_logits, d_scores, base + p.off_head, workspace_bytes - p.off_head, stream);
 }

@@ -7,6 +7,10 @@ RoBERTa with a SentencePiece model or with GPT-2's byte-level BPE (<s> a </s> </
 classifier.dense + classifier.out_proj).
 The texts are tokenised once on the GPU (engine/gpu_tokenizers.py), paired, truncated and packed there (mq_pair_plan_n / mq_pack_pairs |
 mq_pack_pairs_xlmr), and every batch is ONE mq_score_pairs_bert | mq_score_pairs_xlmr call.
+A third family runs on the ModernBERT tower (ModernBertCrossEncoderTower: `ModernBertForSequenceClassification`, [CLS] a [SEP] b [SEP], mean or CLS
+pooling, dense -> GELU -> LayerNorm -> classifier; one mq_score_pairs_modernbert call per batch).  Its texts are tokenised once on the HOST, by the
+`tokenizers` library from the checkpoint's tokenizer.json; pairing, truncation and packing are the same GPU calls.  What the towers share — the
+length cap, the longest-first order, the batch loop — is `_PairScorer.score`.
 """
 from __future__ import annotations
 
@@ -21,7 +25,9 @@ import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
-from marqo_amd.engine.tokenizers import RobertaBpeTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
+from marqo_amd.engine.modernbert import ModernBertTower
+from marqo_amd.engine.tokenizers import HfJsonTokenizer, RobertaBpeTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
+from marqo_amd.engine.tower_weights import modernbert_head_tensors
 from marqo_amd.engine.towers import BertTower, _large_call, _need, request_stream
 
 Tensor = torch.Tensor
@@ -67,17 +73,17 @@ def pair_lengths(la, lb, max_length: int, specials: int = 3):
     return (int(a), int(b)) if scalar else (a, b)
 
 
-def _tokenizer_settings(directory: str) -> Tuple[bool, int]:
+def _tokenizer_settings(directory: str, default_max: int = 512) -> Tuple[bool, int]:
     """(do_lower_case, model_max_length) of a checkpoint's tokenizer_config.json (BERT's defaults when absent; XLM-R's model_max_length
-    defaults to 512 as well)"""
-    lower, max_len = True, 512
+    defaults to 512 as well; ModernBERT's to what its caller passes)"""
+    lower, max_len = True, default_max
     p = os.path.join(directory, "tokenizer_config.json")
     if os.path.isfile(p):
         try:
             with open(p) as f:
                 j = json.load(f)
             lower = bool(j.get("do_lower_case", True))
-            m = j.get("model_max_length", 512)
+            m = j.get("model_max_length", default_max)
             if isinstance(m, (int, float)) and 4 <= m < 1 << 20:    # (transformers writes 1e30 for "no limit")
                 max_len = int(m)
         except (OSError, ValueError):
@@ -114,7 +120,75 @@ def head_tensors(sd: Dict[str, Tensor], family: _Family, W: int) -> Tuple[Tensor
             _need(sd, family.out + ".weight", (1, W)), _need(sd, family.out + ".bias", (1,)))
 
 
-class CrossEncoderTower(BertTower):
+class _PairScorer:
+    """score() of the cross-encoder towers: ONE query against n documents.  The tower supplies
+      pair_specials                      special tokens of a packed pair
+      pair_id_rows                       rows of the packed id buffer: 1, or 2 when the pack call also writes token-type ids
+      tokenizer.cls_id / .sep_id         the two ids the pack call inserts
+      model_max_length                   the longest pair the checkpoint takes
+      _tokenize_query(query)             -> (ids int32 [1, >= len] on the device: CLS pieces SEP, its length [1]) at the query's FULL length
+      _tokenize(texts, cap)              -> (ids int32 [n, cap] on the device: CLS pieces SEP pad, lengths int64 [n]), rows cut to cap tokens
+      _pack_chunk(pack, d_ids, rows, stream)                        the pack call of one batch (pack: the arguments the pack entry points share)
+      _score_chunk(d_ids, d_cu, cu, logits, scores, rows, m)        the scoring call of one batch of m pairs / `rows` tokens
+    and _chunks / _to_device / _stream of the text towers; batches are sized by ROWS (_chunks), whatever the pairs' lengths are."""
+
+    def score(self, query: str, docs: Sequence[str], max_length: int = 512) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (logits, sigmoid(logits)) fp32 [len(docs)] on the host, in the order of `docs`.  Texts are stripped as CrossEncoder strips
+        them; the pair is cut to min(max_length, the tokenizer's model_max_length) tokens by `pair_lengths`.  An empty text contributes no
+        piece, as in the fast tokenizer's pair call: the pair keeps all of its special tokens."""
+        if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
+            raise TypeError("a cross-encoder scores (str, str) pairs")
+        n = len(docs)
+        if n == 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        specials = int(self.pair_specials)
+        cap = int(min(max_length, self.model_max_length))
+        if cap < specials + 1:
+            raise ValueError(f"max_length={max_length} must be at least {specials + 1}")
+        query, docs = query.strip(), [d.strip() for d in docs]
+        lib, dev, tok = self.lib, self.device, self.tokenizer
+        with request_stream(dev), torch.cuda.device(dev):
+            # the query once (its full length: which text is the longer decides who loses a piece), the documents once.  A document cut
+            # to cap - 2 pieces is still longer than B = cap - specials, and still at least as long as any query of <= cap - 2 pieces; for
+            # a longer query the documents are read up to the query's length, which keeps every comparison of pair_lengths exact.
+            d_q, qlen = self._tokenize_query(query)
+            la = int(qlen[0]) - 2
+            ld = cap if la <= cap - 2 else la + 2
+            d_docs, dlen = self._tokenize(docs, ld)
+            a, b = pair_lengths(la, dlen - 2, cap, specials)
+            total = (a + b + specials).astype(np.int64)
+            order = np.argsort(-total, kind="stable")          # longest first: a batch holds sequences of similar length
+            inv = np.empty(n, dtype=np.int64)
+            inv[order] = np.arange(n)
+            sorted_total = total[order]
+            d_order = self._to_device(torch.from_numpy(order))
+            d_docs = d_docs.index_select(0, d_order)            # (row gather: memory movement, as torch is used throughout the engine)
+            d_dlen = self._to_device(torch.from_numpy(dlen[order].astype(np.int32)))
+            d_query = d_q[0, 1:1 + max(la, 0)].contiguous()
+            logits = torch.empty(n, dtype=torch.float32, device=dev)
+            scores = torch.empty(n, dtype=torch.float32, device=dev)
+            stream = self._stream()
+            with _large_call(dev, int(sorted_total.sum())):
+                for s0, s1 in self._chunks(sorted_total):
+                    m = s1 - s0
+                    cu_np = np.zeros(m + 1, dtype=np.int32)
+                    np.cumsum(sorted_total[s0:s1], out=cu_np[1:])
+                    rows = int(cu_np[-1])
+                    cu = torch.from_numpy(cu_np)
+                    d_cu = self._to_device(cu)
+                    plan = torch.empty(3, m, dtype=torch.int32, device=dev)
+                    d_ids = torch.empty(int(self.pair_id_rows), rows, dtype=torch.int32, device=dev)
+                    L.check(lib.mq_pair_plan_n(la, d_dlen[s0:s1].data_ptr(), m, ld, cap, specials, plan[0].data_ptr(), plan[1].data_ptr(),
+                                               plan[2].data_ptr(), stream), "mq_pair_plan_n")
+                    pack = (d_query.data_ptr() if la > 0 else None, la, d_docs[s0:s1].data_ptr(), ld, plan[0].data_ptr(), plan[1].data_ptr(),
+                            d_cu.data_ptr(), m, tok.cls_id, tok.sep_id, d_ids[0].data_ptr())
+                    self._pack_chunk(pack, d_ids, rows, stream)
+                    self._score_chunk(d_ids, d_cu, cu, logits[s0:s1], scores[s0:s1], rows, m)
+            out = torch.stack((logits, scores)).cpu().numpy()
+        return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
+
+
+class CrossEncoderTower(_PairScorer, BertTower):
     """`BertForSequenceClassification` / `XLMRobertaForSequenceClassification` (num_labels = 1): `bert.*` | `roberta.*` = the encoder (prepared
     exactly as for the embedding towers: engine/tower_weights.py; XLM-R's position table is handed over from row padding_idx + 1 on),
     `bert.pooler.dense.*` + `classifier.*` | `classifier.dense.*` + `classifier.out_proj.*` = the head (a `roberta.pooler.*` is not read: the
@@ -155,6 +229,8 @@ class CrossEncoderTower(BertTower):
         vocab.json + merges.txt, tokenizer_config.json"""
         cfg, sd = checkpoint.load_hf_dir(directory)
         mtype = cfg.get("model_type", "bert")
+        if mtype == "modernbert":       # its own tower and head (below)
+            return ModernBertCrossEncoderTower._from_loaded(directory, cfg, sd, device)
         byte_bpe = False
         if mtype == "bert":
             family = BERT
@@ -205,64 +281,24 @@ class CrossEncoderTower(BertTower):
             return self._to_device(torch.from_numpy(row[None, :])), np.asarray([row.size], dtype=np.int64)
         return d_q, qlen
 
-    def score(self, query: str, docs: Sequence[str], max_length: int = 512) -> Tuple[np.ndarray, np.ndarray]:
-        """-> (logits, sigmoid(logits)) fp32 [len(docs)] on the host, in the order of `docs`.  Texts are stripped as CrossEncoder strips
-        them; the pair is cut to min(max_length, the tokenizer's model_max_length) tokens by `pair_lengths`.  An empty text contributes no
-        piece, as in the fast tokenizer's pair call: the pair keeps all of its special tokens."""
-        if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
-            raise TypeError("a cross-encoder scores (str, str) pairs")
-        n = len(docs)
-        if n == 0:
-            return np.zeros(0, np.float32), np.zeros(0, np.float32)
-        fam = self.family
-        cap = int(min(max_length, self.model_max_length))
-        if cap < fam.specials + 1:
-            raise ValueError(f"max_length={max_length} must be at least {fam.specials + 1}")
-        query, docs = query.strip(), [d.strip() for d in docs]
-        lib, dev, tok = self.lib, self.device, self.tokenizer
-        with request_stream(dev), torch.cuda.device(dev):
-            # the query once (its full length: which text is the longer decides who loses a piece), the documents once.  A document cut
-            # to cap - 2 pieces is still longer than B = cap - specials, and still at least as long as any query of <= cap - 2 pieces; for
-            # a longer query the documents are read up to the query's length, which keeps every comparison of pair_lengths exact.
-            d_q, qlen = self._tokenize_query(query)
-            la = int(qlen[0]) - 2
-            ld = cap if la <= cap - 2 else la + 2
-            d_docs, dlen = self._tokenize(docs, ld)
-            a, b = pair_lengths(la, dlen - 2, cap, fam.specials)
-            total = (a + b + fam.specials).astype(np.int64)
-            order = np.argsort(-total, kind="stable")          # longest first: a batch holds sequences of similar length
-            inv = np.empty(n, dtype=np.int64)
-            inv[order] = np.arange(n)
-            sorted_total = total[order]
-            d_order = self._to_device(torch.from_numpy(order))
-            d_docs = d_docs.index_select(0, d_order)            # (row gather: memory movement, as torch is used throughout the engine)
-            d_dlen = self._to_device(torch.from_numpy(dlen[order].astype(np.int32)))
-            d_query = d_q[0, 1:1 + max(la, 0)].contiguous()
-            logits = torch.empty(n, dtype=torch.float32, device=dev)
-            scores = torch.empty(n, dtype=torch.float32, device=dev)
-            stream = self._stream()
-            with _large_call(dev, int(sorted_total.sum())):
-                for s0, s1 in self._chunks(sorted_total):
-                    m = s1 - s0
-                    cu_np = np.zeros(m + 1, dtype=np.int32)
-                    np.cumsum(sorted_total[s0:s1], out=cu_np[1:])
-                    rows = int(cu_np[-1])
-                    cu = torch.from_numpy(cu_np)
-                    d_cu = self._to_device(cu)
-                    plan = torch.empty(3, m, dtype=torch.int32, device=dev)
-                    d_ids = torch.empty(2 if fam.typed else 1, rows, dtype=torch.int32, device=dev)
-                    L.check(lib.mq_pair_plan_n(la, d_dlen[s0:s1].data_ptr(), m, ld, cap, fam.specials, plan[0].data_ptr(), plan[1].data_ptr(),
-                                               plan[2].data_ptr(), stream), "mq_pair_plan_n")
-                    pack = (d_query.data_ptr() if la > 0 else None, la, d_docs[s0:s1].data_ptr(), ld, plan[0].data_ptr(), plan[1].data_ptr(),
-                            d_cu.data_ptr(), m, tok.cls_id, tok.sep_id, d_ids[0].data_ptr())
-                    if fam.typed:
-                        L.check(lib.mq_pack_pairs(*pack, d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
-                    else:
-                        L.check(lib.mq_pack_pairs_xlmr(*pack, rows, stream), "mq_pack_pairs_xlmr")
-                    ws = self._workspace(lib.mq_score_pairs_workspace_bytes(C.byref(self.cfg), rows, m))
-                    self.score_packed(d_ids[0], d_ids[1] if fam.typed else None, d_cu, cu, logits[s0:s1], scores[s0:s1], None, ws)
-            out = torch.stack((logits, scores)).cpu().numpy()
-        return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
+    # ---- what _PairScorer.score asks of this tower ------------------------------------------------------------------------------------
+    @property
+    def pair_specials(self) -> int:
+        return self.family.specials
+
+    @property
+    def pair_id_rows(self) -> int:
+        return 2 if self.family.typed else 1
+
+    def _pack_chunk(self, pack: tuple, d_ids: Tensor, rows: int, stream: int) -> None:
+        if self.family.typed:
+            L.check(self.lib.mq_pack_pairs(*pack, d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
+        else:
+            L.check(self.lib.mq_pack_pairs_xlmr(*pack, rows, stream), "mq_pack_pairs_xlmr")
+
+    def _score_chunk(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Tensor, rows: int, m: int) -> None:
+        ws = self._workspace(self.lib.mq_score_pairs_workspace_bytes(C.byref(self.cfg), rows, m))
+        self.score_packed(d_ids[0], d_ids[1] if self.family.typed else None, d_cu, cu, logits, scores, None, ws)
 
     def score_packed(self, d_ids: Tensor, d_type_ids: Optional[Tensor], d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Optional[Tensor],
                      cls_rows: Optional[Tensor], ws: Tensor) -> None:
@@ -279,3 +315,108 @@ class CrossEncoderTower(BertTower):
         L.check(self.lib.mq_score_pairs_bert(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_type_ids.data_ptr(),
                                              d_cu.data_ptr(), cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores),
                                              L.ptr(cls_rows), ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_bert")
+
+
+def _special_spellings(directory: str, **defaults) -> Dict[str, str]:
+    """cls / sep / pad spellings of a checkpoint (special_tokens_map.json, then tokenizer_config.json), else the family's"""
+    out = dict(defaults)
+    for name in ("special_tokens_map.json", "tokenizer_config.json"):
+        try:
+            with open(os.path.join(directory, name)) as f:
+                j = json.load(f)
+        except (OSError, ValueError):
+            continue
+        for k in out:
+            v = j.get(k + "_token") if isinstance(j, dict) else None
+            if isinstance(v, dict):       # AddedToken serialisation
+                v = v.get("content")
+            if isinstance(v, str) and v:
+                out[k] = v
+    return out
+
+
+class ModernBertCrossEncoderTower(_PairScorer, ModernBertTower):
+    """`ModernBertForSequenceClassification` (num_labels = 1): `model.*` = the encoder (engine/tower_weights.py::modernbert_state_dict, as for the
+    embedding tower), pooled as the config's `classifier_pooling` says, `head.dense` -> GELU -> `head.norm` -> `classifier` = the head
+    (mq_score_head_ln_weights).  Pairs are [CLS] a [SEP] b [SEP]; a pair may be as long as the encoder serves (8192 tokens at most).  score() returns
+    the raw logits and their sigmoid."""
+    pair_specials = 3
+    pair_id_rows = 2        # mq_pack_pairs also writes token-type ids: a scratch row nobody reads
+
+    def __init__(self, arch: archs.ModernBertArch, sd: Dict[str, Tensor], device: str, tokenizer, model_max_length: int = 8192, pooling: str = "cls",
+                 classifier_bias: bool = False, norm_bias: bool = False):
+        W = arch.width
+        dense_w, dense_b, norm_g, norm_b, cls_w, cls_b = modernbert_head_tensors(sd, W, classifier_bias, norm_bias)
+        super().__init__(arch, sd, device, pooling=pooling, precision="bf16")
+        h = self._h
+        self.head = L.ScoreHeadLnWeights(dense_w=h.bf16(dense_w), dense_b=h.f32(dense_b) if dense_b is not None else None, norm_g=h.f32(norm_g),
+                                         norm_b=h.f32(norm_b) if norm_b is not None else None, cls_w=h.f32(cls_w.reshape(W)),
+                                         cls_b=float(cls_b.reshape(-1)[0]), ln_eps=float(arch.ln_eps))
+        self.tokenizer = tokenizer
+        self.model_max_length = int(min(model_max_length, arch.max_pos, 8192))
+
+    @classmethod
+    def from_dir(cls, directory: str, device: str) -> "ModernBertCrossEncoderTower":
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, tokenizer.json, tokenizer_config.json"""
+        cfg, sd = checkpoint.load_hf_dir(directory)
+        if cfg.get("model_type") != "modernbert":
+            raise ValueError(f"{directory}: model_type={cfg.get('model_type')!r} is not a ModernBERT checkpoint")
+        return cls._from_loaded(directory, cfg, sd, device)
+
+    @classmethod
+    def _from_loaded(cls, directory: str, cfg: dict, sd: Dict[str, Tensor], device: str) -> "ModernBertCrossEncoderTower":
+        labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
+        if int(labels) != 1:
+            raise ValueError(f"{directory}: num_labels={labels} is not served as a cross-encoder (only one-logit heads)")
+        act = cfg.get("classifier_activation", "gelu")
+        if act != "gelu":
+            raise ValueError(f"{directory}: classifier_activation={act!r} is not served (the head's dense layer runs the erf GELU only)")
+        pooling = cfg.get("classifier_pooling", "cls")
+        if pooling not in ("cls", "mean"):
+            raise ValueError(f"{directory}: classifier_pooling={pooling!r} must be 'cls' or 'mean'")
+        try:
+            arch = archs.modernbert_arch_from_hf_config(cfg)      # 64-wide heads only, no biases in the encoder, the default rope type
+        except KeyError as e:
+            raise ValueError(f"{directory}: {e.args[0] if e.args else e}") from e
+        if not os.path.isfile(os.path.join(directory, "tokenizer.json")):
+            raise ValueError(f"{directory}: a ModernBERT cross-encoder needs the checkpoint's tokenizer.json, which is not there")
+        tokenizer = HfJsonTokenizer(directory, **_special_spellings(directory, cls="[CLS]", sep="[SEP]", pad="[PAD]"))
+        _, max_len = _tokenizer_settings(directory, default_max=arch.max_pos)
+        return cls(arch, sd, device, tokenizer, model_max_length=max_len, pooling=pooling, classifier_bias=bool(cfg.get("classifier_bias", False)),
+                   norm_bias=bool(cfg.get("norm_bias", False)))
+
+    # ---- what _PairScorer.score asks of this tower ------------------------------------------------------------------------------------
+    def _tokenize(self, texts: Sequence[str], cap: int) -> Tuple[Tensor, np.ndarray]:
+        """each text ONCE, alone, through the file's own post-processor: rows [CLS] pieces [SEP] pad of exactly `cap` columns (the layout
+        mq_pair_plan_n / mq_pack_pairs read: lengths count the two specials, pieces start at column 1)"""
+        ids, lens = hf_rows(self.tokenizer, texts, cap)
+        return self._to_device(torch.from_numpy(ids)), lens
+
+    def _tokenize_query(self, query: str) -> Tuple[Tensor, np.ndarray]:
+        return self._tokenize([query], None)
+
+    def _pack_chunk(self, pack: tuple, d_ids: Tensor, rows: int, stream: int) -> None:
+        L.check(self.lib.mq_pack_pairs(*pack, d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
+
+    def _score_chunk(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Tensor, rows: int, m: int) -> None:
+        ws = self._workspace(self.lib.mq_score_pairs_modernbert_workspace_bytes(C.byref(self.cfg), rows, m))
+        self.score_packed(d_ids[0], d_cu, cu, logits, scores, None, ws)
+
+    def score_packed(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Optional[Tensor], pooled: Optional[Tensor],
+                     ws: Tensor) -> None:
+        """one mq_score_pairs_modernbert call on this thread's current stream: packed ids int32 [rows], cu_seqlens on the device and the host,
+        logits / scores fp32 [nseq] (scores may be None), pooled fp32 [nseq, W] or None"""
+        L.check(self.lib.mq_score_pairs_modernbert(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_cu.data_ptr(),
+                                                   cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores), L.ptr(pooled),
+                                                   ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_modernbert")
+
+
+def hf_rows(tokenizer: HfJsonTokenizer, texts: Sequence[str], cap: Optional[int]) -> Tuple[np.ndarray, np.ndarray]:
+    """texts -> (ids int32 [n, cap], lengths int64 [n]): every text encoded alone by the `tokenizers` library, cut to `cap` tokens with both specials
+    kept, right-padded to exactly `cap` columns (cap None: no cut, padded to the longest row)"""
+    enc = tokenizer(list(texts), max_length=cap)
+    got, lens = enc["input_ids"], enc["attention_mask"].sum(axis=1).astype(np.int64)
+    width = int(cap) if cap else max(int(got.shape[1]), 2)
+    ids = np.full((len(texts), width), tokenizer.pad_id, dtype=np.int32)
+    ids[:, :got.shape[1]] = got[:, :width]
+    return ids, lens

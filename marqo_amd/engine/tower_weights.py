@@ -425,6 +425,22 @@ def modernbert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     return out
 
 
+def modernbert_head_tensors(sd: Dict[str, Tensor], W: int, classifier_bias: bool = False, norm_bias: bool = False):
+    """(dense weight [W, W], dense bias [W] | None, norm weight [W], norm bias [W] | None, classifier weight [1, W], classifier bias [1]) of a
+    ModernBertForSequenceClassification checkpoint, fp32: `head.dense.*`, `head.norm.*`, `classifier.*`.  The two optional biases are read when the
+    config says they exist (classifier_bias / norm_bias); a tensor the config promises and the checkpoint lacks is an error that names it, and so is
+    a bias the config denies."""
+    def f32(k, shape):
+        if k not in sd:
+            raise ValueError(f"checkpoint is missing tensor '{k}'")
+        return _need(sd, k, shape).detach().to(torch.float32)
+    for flag, key, knob in ((classifier_bias, "head.dense.bias", "classifier_bias"), (norm_bias, "head.norm.bias", "norm_bias")):
+        if not flag and key in sd:
+            raise ValueError(f"{key} present but the config says {knob}=false")
+    return (f32("head.dense.weight", (W, W)), f32("head.dense.bias", (W,)) if classifier_bias else None, f32("head.norm.weight", (W,)),
+            f32("head.norm.bias", (W,)) if norm_bias else None, f32("classifier.weight", (1, W)), f32("classifier.bias", (1,)))
+
+
 def qwen_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     """transformers' Qwen3Model / Qwen2Model tensors (with or without a `model.` prefix; `lm_head.*` of the causal-LM classes is ignored) -> the fp32
     tensors the tower hands to the kernels.  Per layer the three projections are fused into `layers.N.self_attn.qkv.weight` [(Q + 2 KV) hd, W] = rows
