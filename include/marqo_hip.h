@@ -1424,6 +1424,61 @@ size_t mq_gemma_workspace_bytes(const mq_gemma_cfg* cfg, int64_t rows, int64_t n
 int mq_encode_gemma(const mq_gemma_cfg* cfg, const mq_gemma_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                     int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- T5 encoder text embedders: clamped relative-bias attention and the tower (csrc/attention_relbias.hip, csrc/t5.hip; engine/t5.py) -----------------
+ * transformers' T5EncoderModel (model_type "t5": sentence-t5, gtr-t5, flan-t5 / T5 v1.1 encoder fine-tunes): pre-norm blocks with RMSNorms (T5LayerNorm),
+ * bias-free Linears, an inner attention width heads * d_kv that need not be d_model, NO softmax scale, one relative-position bias table (block 0's)
+ * shared by every block, a ReLU or a gated gelu_new MLP, no position table.  Additions to ABI 15: nothing above changes; the structs and entry points
+ * below are new.  Every entry point judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on
+ * `stream` and allocates nothing.
+ *
+ *   mq_attention_relbias: d_qkv bf16 [rows, 3 inner] = (q | k | v), inner = heads head_dim, head h at columns h head_dim .. of each third; d_out bf16
+ *                   [rows, inner]; head_dim 64 or 128; sequences packed or fixed-length as mq_attention, max_len <= 8192.  Unmasked, bidirectional:
+ *                   scores[q, k] = scale (q . k) + d_rel_bias[h][clamp(k - q, -D, D) + D], D = max_distance in [1, 1024], d_rel_bias fp32 [heads][2 D + 1]
+ *                   used as it is (nothing is pre-divided by the scale); scale > 0 is the caller's (T5: 1.0).  One workgroup of 4 waves per (sequence,
+ *                   head, 64-query slice); the head's table lies in LDS behind the K / V image (576 keys at head_dim 64, 256 at 128; longer sequences
+ *                   stream through in pieces).  Compiler report (gfx950): csrc/attention_relbias.hip's header.
+ *   mq_encode_t5:   token gather -> `layers` blocks  x += Wo(attn(Wqkv(norm(x)))) ; x += Wo_ff(relu(Wi(norm(x))))  or, gated,  x += Wo_ff(up *
+ *                   gelu_new(gate)) with (up | gate) = Wi'(norm(x))  -> final RMSNorm -> mq_pool (MQ_POOL_MEAN or MQ_POOL_CLS) (+ L2), on packed
+ *                   sequences like mq_encode_bert; fp32 residual stream, bf16 GEMM operands.  width (d_model) a multiple of 64, <= 2048; head_dim (d_kv)
+ *                   64 or 128; heads * head_dim <= 4096; mlp_dim (d_ff) % 64 == 0; max_pos <= 8192; max_distance in [1, 1024].  d_out fp32 [nseq, width]. */
+typedef struct mq_t5_layer {
+    const float* attn_norm_g;   /* fp32 [W]  layer.0.layer_norm */
+    const void*  qkv_w;         /* bf16 [3 A, W]  rows: q | k | v, A = heads * head_dim */
+    const void*  out_w;         /* bf16 [W, A]  SelfAttention.o */
+    const float* ff_norm_g;     /* fp32 [W]  layer.1.layer_norm */
+    const void*  wi_w;          /* bf16 [F, W] wi (relu), or [2F, W] rows: wi_1 | wi_0 = up | gate (mq_glu_tanh's order) */
+    const void*  wo_w;          /* bf16 [W, F]  DenseReluDense.wo */
+} mq_t5_layer;
+
+typedef struct mq_t5_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  shared.weight */
+    const float* final_norm_g;  /* fp32 [W]  final_layer_norm */
+    const float* zeros;         /* fp32 [max(W, F)] of zeros: the bias of the residual and ReLU GEMM epilogues */
+    const float* d_rel_bias;    /* fp32 [heads][2 max_distance + 1]: block 0's relative_attention_bias by clamped key - query */
+    const mq_t5_layer* layers;  /* host array, `layers` entries */
+} mq_t5_weights;
+
+typedef struct mq_t5_cfg {
+    int32_t width;         /* W = d_model, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t heads;
+    int32_t head_dim;      /* d_kv: 64 or 128; heads * head_dim (<= 4096) need not be W */
+    int32_t mlp_dim;       /* F = d_ff, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;       /* longest sequence served (<= 8192) */
+    int32_t pool;          /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    int32_t max_distance;  /* D = relative_attention_max_distance, 1 .. 1024 */
+    int32_t gated;         /* 0: relu MLP; 1: gated gelu_new (T5 v1.1) */
+    float   rms_eps;       /* layer_norm_epsilon */
+    int32_t reserved;
+} mq_t5_cfg;
+
+int mq_attention_relbias(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len, int32_t heads,
+                         int32_t head_dim, const float* d_rel_bias, int32_t max_distance, float scale, void* stream);
+size_t mq_t5_workspace_bytes(const mq_t5_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_t5(const mq_t5_cfg* cfg, const mq_t5_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
+                 int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

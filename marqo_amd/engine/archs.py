@@ -473,6 +473,99 @@ def gemma_arch_from_hf_config(cfg: dict) -> GemmaArch:
 
 
 @dataclass(frozen=True)
+class T5Arch:
+    """transformers' T5EncoderModel (model_type "t5": sentence-t5, gtr-t5, flan-t5 / T5 v1.1 encoder fine-tunes) as the engine runs it: pre-norm blocks with
+    RMSNorms, bias-free Linears, `heads` attention heads of width head_dim (d_kv) whose total need not be `width` (d_model), no softmax scale, ONE
+    relative-position bias table (block 0's) shared by every block, a ReLU MLP or (gated) a gated gelu_new one, no position table."""
+    vocab: int = 32128
+    max_pos: int = 8192                   # no position table: the longest sequence the attention kernel serves
+    width: int = 768
+    layers: int = 12
+    heads: int = 12
+    head_dim: int = 64
+    mlp_dim: int = 3072
+    rms_eps: float = 1e-6
+    gated: bool = False                   # feed_forward_proj "gated-gelu" (T5 v1.1 / flan-t5)
+    rel_buckets: int = 32
+    max_distance: int = 128
+
+    @property
+    def inner(self) -> int:
+        return self.heads * self.head_dim
+
+    def bucket_of(self, relative_position):
+        """transformers' T5Attention._relative_position_bucket(bidirectional=True), the same torch ops in the same order: int64 tensor of key - query ->
+        int64 bucket ids"""
+        import math
+        import torch
+        num_buckets = self.rel_buckets // 2
+        relative_buckets = (relative_position > 0).to(torch.long) * num_buckets
+        relative_position = torch.abs(relative_position)
+        max_exact = num_buckets // 2
+        is_small = relative_position < max_exact
+        relative_position_if_large = max_exact + (
+            torch.log(relative_position.float() / max_exact) / math.log(self.max_distance / max_exact) * (num_buckets - max_exact)
+        ).to(torch.long)
+        relative_position_if_large = torch.min(relative_position_if_large, torch.full_like(relative_position_if_large, num_buckets - 1))
+        return relative_buckets + torch.where(is_small, relative_position, relative_position_if_large)
+
+    def rel_bias_table(self, weight):
+        """block 0's relative_attention_bias.weight [rel_buckets, heads] -> fp32 [heads, 2 D + 1], D = max_distance: entry (h, d + D) is the bias of
+        key - query == d.  The bucket function is constant for |d| >= D, so the two ends stand for everything beyond (mq_attention_relbias clamps its
+        index); that is checked here against the largest distance the engine serves."""
+        import torch
+        D = self.max_distance
+        if tuple(weight.shape) != (self.rel_buckets, self.heads):
+            raise ValueError(f"relative_attention_bias.weight {tuple(weight.shape)} is not [relative_attention_num_buckets={self.rel_buckets}, "
+                             f"num_heads={self.heads}]")
+        buckets = self.bucket_of(torch.arange(-D, D + 1, dtype=torch.long))
+        far = self.bucket_of(torch.tensor([-self.max_pos, self.max_pos], dtype=torch.long))
+        if int(buckets[0]) != int(far[0]) or int(buckets[-1]) != int(far[1]):
+            raise ValueError(f"the bucket function of relative_attention_num_buckets={self.rel_buckets} / relative_attention_max_distance={D} is not "
+                             f"constant from distance {D} on")
+        return weight.detach().to(torch.float32)[buckets].t().contiguous()
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F, A = tokens, self.width, self.mlp_dim, self.inner
+        return self.layers * (2 * T * W * 3 * A + 2 * T * A * W + 4 * T * T * A + 2 * (3 if self.gated else 2) * T * W * F) / 1e9
+
+
+def t5_arch_from_hf_config(cfg: dict) -> T5Arch:
+    """A local T5 `config.json` (model_type "t5") -> T5Arch.  Refused, each by the name of its key: a feed_forward_proj other than relu / gated-gelu (or
+    an is_gated_act / dense_act_fn that contradicts it), d_kv other than 64 / 128, d_model above 2048 or no multiple of 64, num_heads * d_kv above 4096,
+    d_ff no multiple of 64, an odd relative_attention_num_buckets, relative_attention_max_distance outside [1, 1024]."""
+    mtype = cfg.get("model_type")
+    if mtype != "t5":
+        raise KeyError(f"model_type={mtype} is not a T5 model")
+    ffp = str(cfg.get("feed_forward_proj", "relu"))
+    if ffp not in ("relu", "gated-gelu"):
+        raise KeyError(f"feed_forward_proj={ffp} unsupported (relu or gated-gelu)")
+    gated = ffp == "gated-gelu"
+    if "is_gated_act" in cfg and bool(cfg["is_gated_act"]) != gated:
+        raise KeyError(f"is_gated_act={cfg['is_gated_act']} contradicts feed_forward_proj={ffp}")
+    act = cfg.get("dense_act_fn")
+    if act is not None and act != ("gelu_new" if gated else "relu"):
+        raise KeyError(f"dense_act_fn={act} unsupported with feed_forward_proj={ffp} ({'gelu_new' if gated else 'relu'} only)")
+    W, hd, heads, F = int(cfg["d_model"]), int(cfg.get("d_kv", 64)), int(cfg["num_heads"]), int(cfg["d_ff"])
+    if hd not in (64, 128):
+        raise KeyError(f"d_kv={hd} unsupported (64 or 128)")
+    if W > 2048 or W % 64 or W < 64:
+        raise KeyError(f"d_model={W} unsupported (a multiple of 64 up to 2048)")
+    if heads < 1 or heads * hd > 4096:
+        raise KeyError(f"num_heads={heads} x d_kv={hd} unsupported (an inner width of at most 4096)")
+    if F % 64 or F < 64:
+        raise KeyError(f"d_ff={F} must be a multiple of 64")
+    nb = int(cfg.get("relative_attention_num_buckets", 32))
+    if nb < 4 or nb % 2:
+        raise KeyError(f"relative_attention_num_buckets={nb} unsupported (an even number >= 4)")
+    D = int(cfg.get("relative_attention_max_distance", 128))
+    if not 1 <= D <= 1024 or D <= nb // 4:
+        raise KeyError(f"relative_attention_max_distance={D} unsupported (above relative_attention_num_buckets / 4, at most 1024)")
+    return T5Arch(vocab=int(cfg["vocab_size"]), width=W, layers=int(cfg["num_layers"]), heads=heads, head_dim=hd, mlp_dim=F,
+                  rms_eps=float(cfg.get("layer_norm_epsilon", 1e-6)), gated=gated, rel_buckets=nb, max_distance=D)
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -744,13 +837,16 @@ STELLA_EN_400M = BertArch(vocab=30528, max_pos=8192, width=1024, layers=24, head
 HF_BERT_ARCHS["Marqo/dunzhang-stella_en_400M_v5"] = STELLA_EN_400M
 
 
-def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch]:
+def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch, T5Arch]:
     """A local HF `config.json` -> the arch of the text encoder the `hf` loader builds.  model_type bert, or xlm-roberta / roberta (the same encoder
     with the position ids shifted by padding_idx + 1: the multilingual-e5 family), mpnet and `new` give a BertArch (engine/towers.py::BertTower);
     model_type modernbert gives a ModernBertArch (engine/modernbert.py::ModernBertTower) — callers that can only run a BertArch (the cross-encoders of
     engine/rerank.py, which select their model types before they call) must not pass one through; model_type qwen3 / qwen2 gives a QwenArch
-    (engine/qwen.py::QwenTower) and model_type gemma3_text a GemmaArch (engine/gemma.py::GemmaTower) under the same rule.  Anything else: KeyError."""
+    (engine/qwen.py::QwenTower), model_type gemma3_text a GemmaArch (engine/gemma.py::GemmaTower) and model_type t5 a T5Arch (engine/t5.py::T5Tower) under
+    the same rule.  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
+    if mtype == "t5":   # transformers T5EncoderModel: sentence-t5, gtr-t5, flan-t5 encoders (engine/t5.py::T5Tower)
+        return t5_arch_from_hf_config(cfg)
     if mtype == "gemma3_text":   # transformers Gemma3TextModel with bidirectional attention: EmbeddingGemma (engine/gemma.py::GemmaTower)
         return gemma_arch_from_hf_config(cfg)
     if mtype in ("qwen3", "qwen2"):   # transformers Qwen3Model / Qwen2Model: decoder-style embedders (engine/qwen.py)

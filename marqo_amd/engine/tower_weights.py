@@ -501,3 +501,36 @@ def gemma_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
         out[p + "mlp.up_gate.weight"] = torch.cat([f32(p + "mlp.up_proj.weight", (F, W)), f32(p + "mlp.gate_proj.weight", (F, W))], 0)
         out[p + "mlp.down_proj.weight"] = f32(p + "mlp.down_proj.weight", (W, F))
     return out
+
+
+def t5_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' T5EncoderModel / T5Model / T5ForConditionalGeneration tensors -> the fp32 tensors the tower hands to the kernels.  The encoder's keys
+    are taken with or without their `encoder.` prefix; the token table is `shared.weight`, else `encoder.embed_tokens.weight` / `embed_tokens.weight`;
+    `decoder.*` and `lm_head.*` are ignored.  Per block l (`block.l.layer.0` = attention, `.layer.1` = MLP) the three projections are fused into
+    `block.l.attn.qkv.weight` [3 A, W] = rows q | k | v; the ReLU MLP keeps `block.l.ff.wi.weight` [F, W]; the gated one fuses its two input projections
+    into `block.l.ff.wi.weight` [2F, W] = rows wi_1 | wi_0 — mq_glu_tanh computes up * gelu_new(gate) from (up | gate), the module
+    wo(gelu_new(wi_0(x)) * wi_1(x)).  `rel_bias` [heads, 2 D + 1] is arch.rel_bias_table of block 0's relative_attention_bias, the only one there is."""
+    if "block.0.layer.0.SelfAttention.q.weight" not in sd and "encoder.block.0.layer.0.SelfAttention.q.weight" in sd:
+        enc = {k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}
+        if "shared.weight" in sd:
+            enc["shared.weight"] = sd["shared.weight"]
+        sd = enc
+    W, F, A = arch.width, arch.mlp_dim, arch.inner
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    tok = "shared.weight" if "shared.weight" in sd else "embed_tokens.weight"
+    out = {"embed_tokens.weight": f32(tok, (arch.vocab, W)), "final_layer_norm.weight": f32("final_layer_norm.weight", (W,)),
+           "rel_bias": arch.rel_bias_table(f32("block.0.layer.0.SelfAttention.relative_attention_bias.weight", (arch.rel_buckets, arch.heads)))}
+    for l in range(arch.layers):
+        a, m = f"block.{l}.layer.0.", f"block.{l}.layer.1."
+        if l > 0 and (a + "SelfAttention.relative_attention_bias.weight") in sd:
+            raise ValueError(f"{a}SelfAttention.relative_attention_bias.weight: a bias table per block (mt5 / umt5) is not served")
+        out[f"block.{l}.attn_norm.weight"] = f32(a + "layer_norm.weight", (W,))
+        out[f"block.{l}.attn.qkv.weight"] = torch.cat([f32(a + f"SelfAttention.{c}.weight", (A, W)) for c in "qkv"], 0)
+        out[f"block.{l}.attn.o.weight"] = f32(a + "SelfAttention.o.weight", (W, A))
+        out[f"block.{l}.ff_norm.weight"] = f32(m + "layer_norm.weight", (W,))
+        if arch.gated:
+            out[f"block.{l}.ff.wi.weight"] = torch.cat([f32(m + "DenseReluDense.wi_1.weight", (F, W)), f32(m + "DenseReluDense.wi_0.weight", (F, W))], 0)
+        else:
+            out[f"block.{l}.ff.wi.weight"] = f32(m + "DenseReluDense.wi.weight", (F, W))
+        out[f"block.{l}.ff.wo.weight"] = f32(m + "DenseReluDense.wo.weight", (W, F))
+    return out

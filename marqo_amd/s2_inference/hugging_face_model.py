@@ -130,6 +130,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             if isinstance(arch, archs.GemmaArch):
                 self._load_gemma(directory, arch, sd)
                 return
+            if isinstance(arch, archs.T5Arch):
+                self._load_t5(directory, arch, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -211,7 +214,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             raise InvalidModelPropertiesError(f"Invalid model properties: {self.model_properties.dict()}. Original error "
                                               f"{HuggingFaceModelProperties.POOLING_ERROR}")
 
-    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma) share ----------------------------------------------------------
+    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma, T5) share ----------------------------------------------------------
     def _refuse_fp8(self, family: str) -> None:
         props = self.model_properties
         if props.engine_precision == "fp8":
@@ -271,8 +274,35 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                             lambda: HfJsonTokenizer.plain(directory), pooling=pooling)
 
     # sentence-transformers Dense module directories (relative to the checkpoint) to apply behind the pooling: set by the `sbert` loader for an
-    # EmbeddingGemma pipeline, empty for `hf` (AutoModel in the reference: the bare encoder)
+    # EmbeddingGemma or a T5 encoder pipeline, empty for `hf` (AutoModel in the reference: the bare encoder)
     _dense_modules = ()
+
+    def _read_dense_modules(self, directory: str) -> list:
+        try:
+            return [self._read_dense_module(directory, d) for d in self._dense_modules]
+        except (OSError, ValueError, KeyError) as e:
+            raise InvalidModelPropertiesError(f"{self.model_properties.name}: {e}") from e
+
+    def _load_t5(self, directory: str, arch, sd) -> None:
+        """a transformers T5EncoderModel checkpoint (model_type "t5": sentence-t5, gtr-t5, flan-t5 / T5 v1.1 encoder fine-tunes; the decoder tensors of a
+        full T5 checkpoint are ignored): host tokenisation by the `tokenizers` library from the directory's tokenizer.json with the file's own
+        post-processor (which appends </s>), right-padded with the file's <pad>, truncated at min(tokens, sentence_bert_config.json max_seq_length, 8192);
+        the tower of engine/t5.py.  Pooling: the property, else 1_Pooling/config.json, else mean.  bf16 operands only."""
+        import json
+        from marqo_amd.engine.t5 import T5Tower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        self._refuse_fp8("T5 encoders (their RMSNorm / relative-bias attention blocks run on bf16 operands only)")
+        dense = self._read_dense_modules(directory)
+        self._check_width(dense[-1].shape[0] if dense else arch.width)
+        cap = arch.max_pos
+        try:
+            with open(os.path.join(directory, "sentence_bert_config.json")) as f:
+                st_len = json.load(f).get("max_seq_length")
+            if isinstance(st_len, int) and st_len >= 1:
+                cap = min(cap, st_len)
+        except (OSError, ValueError, AttributeError):
+            pass
+        self._finish_packed(directory, arch, cap, T5Tower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="<pad>"), dense=dense)
 
     def _load_gemma(self, directory: str, arch, sd) -> None:
         """a transformers Gemma3TextModel checkpoint with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its
@@ -283,10 +313,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         from marqo_amd.engine.gemma import GemmaTower
         from marqo_amd.engine.tokenizers import HfJsonTokenizer
         self._refuse_fp8("EmbeddingGemma encoders (their RMSNorm / rotary / gated tanh-GELU blocks run on bf16 operands only)")
-        try:
-            dense = [self._read_dense_module(directory, d) for d in self._dense_modules]
-        except (OSError, ValueError, KeyError) as e:
-            raise InvalidModelPropertiesError(f"{self.model_properties.name}: {e}") from e
+        dense = self._read_dense_modules(directory)
         self._check_width(dense[-1].shape[0] if dense else arch.width)
         self._finish_packed(directory, arch, arch.max_pos, GemmaTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="<pad>"), dense=dense)
 

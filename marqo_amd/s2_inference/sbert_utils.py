@@ -11,8 +11,8 @@ constructor / `encode` contract over it:
     (`_convert_output`: numpy on every device);
   * a checkpoint whose pipeline ends in a `Normalize` module returns unit vectors even for `normalize=False`, as it does in the reference
     (`model.encode` runs the whole pipeline);
-  * an EmbeddingGemma checkpoint (config.json model_type "gemma3_text") also runs the bias-free, identity-activation `Dense` modules its `modules.json`
-    lists, behind the pooling; the Dense modules of other families are not served (unchanged);
+  * an EmbeddingGemma or a T5 encoder checkpoint (config.json model_type "gemma3_text" / "t5": sentence-t5, gtr-t5) also runs the bias-free,
+    identity-activation `Dense` modules its `modules.json` lists, behind the pooling; the Dense modules of other families are not served (unchanged);
   * `TEST` keeps the first 16 dimensions before normalising (sbert_utils.py:80-111) and returns a tensor, as the reference does.
 
 There is no CPU path: a non-cuda device raises like every other engine loader."""
@@ -75,14 +75,17 @@ def _sentence_transformer_info(directory: Optional[str]):
     return max_len, normalizes
 
 
-def _gemma_dense_modules(directory: Optional[str]) -> List[str]:
-    """the Dense module directories of an EmbeddingGemma SentenceTransformer checkpoint (config.json model_type "gemma3_text"), in pipeline order; empty
-    for every other family — their pipelines are served without Dense modules, as before"""
+_DENSE_FAMILIES = ("gemma3_text", "t5")     # config.json model_type of the families whose Dense modules are served
+
+
+def _dense_modules(directory: Optional[str]) -> List[str]:
+    """the Dense module directories of an EmbeddingGemma or T5 encoder SentenceTransformer checkpoint (config.json model_type "gemma3_text" / "t5"), in
+    pipeline order; empty for every other family — their pipelines are served without Dense modules, as before"""
     if not directory:
         return []
     try:
         with open(os.path.join(directory, "config.json")) as f:
-            if json.load(f).get("model_type") != "gemma3_text":
+            if json.load(f).get("model_type") not in _DENSE_FAMILIES:
                 return []
         with open(os.path.join(directory, "modules.json")) as f:
             mods = json.load(f)
@@ -115,8 +118,9 @@ class SBERT(Model):
         if pooled:
             props["poolingMethod"] = pooled
         self.model = _SentenceTransformerHF(props, self.device)
-        # EmbeddingGemma: the pipeline's Dense modules (2_Dense, 3_Dense) run behind the pooling, in front of Normalize, as SentenceTransformer.encode runs them
-        self.model._dense_modules = tuple(_gemma_dense_modules(directory))
+        # EmbeddingGemma, sentence-t5 / gtr-t5: the pipeline's Dense modules (2_Dense, 3_Dense) run behind the pooling, in front of Normalize, as
+        # SentenceTransformer.encode runs them
+        self.model._dense_modules = tuple(_dense_modules(directory))
         self.model.load()
 
     def _convert_output(self, output):
