@@ -1479,6 +1479,65 @@ size_t mq_t5_workspace_bytes(const mq_t5_cfg* cfg, int64_t rows, int64_t nseq);
 int mq_encode_t5(const mq_t5_cfg* cfg, const mq_t5_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                  int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- JinaBERT text embedders: ALiBi attention and the tower (csrc/attention_alibi.hip, csrc/jina_bert.hip; engine/jina_bert.py) ------------------------
+ * jina-embeddings-v2-small-en / -base-en, their fine-tunes and MosaicBERT-style ALiBi encoders with the same block (config.json: model_type "bert" with
+ * position_embedding_type "alibi"): post-LN blocks, Linears with biases, a bias-free gated erf-GELU MLP (GEGLU), no position table, a score bias of
+ * -slope_h |key - query|.  The block semantics restate the published architecture; they are not pinned to a run of the original modelling code.
+ * Additions to ABI 15: nothing above changes; the structs and entry points below are new.  Every entry point judges its arguments before any launch
+ * (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_alibi: d_qkv bf16 [rows, 3 inner] = (q | k | v), inner = heads head_dim, head h at columns h head_dim .. of each third; d_out bf16
+ *                   [rows, inner]; head_dim 64; sequences packed or fixed-length as mq_attention, max_len <= 8192.  Unmasked, bidirectional, every key
+ *                   of the sequence contributes: scores[q, k] = fmaf(q . k, scale, -d_slopes[h] |k - q|) in fp32, d_slopes fp32 [heads] the caller's
+ *                   (the kernel knows nothing about how slopes are derived); scale > 0 is the caller's.  One workgroup of 4 waves per (sequence, head,
+ *                   64-query slice); the bias is formed in registers, the K / V image has the whole LDS (640 keys; longer sequences stream through in
+ *                   pieces).  Compiler report (gfx950): csrc/attention_alibi.hip's header.
+ *   mq_encode_jina_bert: token gather + type row 0 + LayerNorm -> `layers` blocks  x = LN(Wo(attn(Wqkv(x))) + x) ; x = LN(Wwo(up * gelu(gate)) + x) with
+ *                   (up | gate) = Wg'(x)  -> mq_pool (MQ_POOL_MEAN or MQ_POOL_CLS) (+ L2), on packed sequences like mq_encode_bert; fp32 residual
+ *                   stream, bf16 GEMM operands; softmax scale 1 / sqrt(head_dim).  width a multiple of 64, <= 2048; head_dim 64; heads * 64 == width;
+ *                   mlp_dim % 64 == 0; max_pos <= 8192.  d_out fp32 [nseq, width]. */
+typedef struct mq_jina_bert_layer {
+    const void*  qkv_w;         /* bf16 [3 W, W]  rows: query | key | value */
+    const float* qkv_b;         /* fp32 [3 W] */
+    const void*  out_w;         /* bf16 [W, W]  attention.output.dense */
+    const float* out_b;         /* fp32 [W] */
+    const float* attn_ln_g;     /* fp32 [W]  attention.output.LayerNorm */
+    const float* attn_ln_b;
+    const void*  wg_w;          /* bf16 [2F, W]  rows: up | gate = mlp.gated_layers rows [F:] | [:F] (mq_glu's order), no bias */
+    const void*  wo_w;          /* bf16 [W, F]  mlp.wo */
+    const float* wo_b;          /* fp32 [W] */
+    const float* mlp_ln_g;      /* fp32 [W]  mlp.layernorm */
+    const float* mlp_ln_b;
+} mq_jina_bert_layer;
+
+typedef struct mq_jina_bert_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  embeddings.word_embeddings */
+    const float* type0;         /* fp32 [W]  row 0 of embeddings.token_type_embeddings */
+    const float* emb_ln_g;      /* fp32 [W]  embeddings.LayerNorm */
+    const float* emb_ln_b;
+    const float* d_slopes;      /* fp32 [heads]: the ALiBi slope of every head */
+    const mq_jina_bert_layer* layers;  /* host array, `layers` entries */
+} mq_jina_bert_weights;
+
+typedef struct mq_jina_bert_cfg {
+    int32_t width;         /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t heads;         /* heads * 64 == W */
+    int32_t head_dim;      /* 64 */
+    int32_t mlp_dim;       /* F = intermediate_size, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;       /* longest sequence served (<= 8192) */
+    int32_t pool;          /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    float   ln_eps;        /* layer_norm_eps */
+    int32_t reserved;
+} mq_jina_bert_cfg;
+
+int mq_attention_alibi(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len, int32_t heads,
+                       int32_t head_dim, const float* d_slopes, float scale, void* stream);
+size_t mq_jina_bert_workspace_bytes(const mq_jina_bert_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_jina_bert(const mq_jina_bert_cfg* cfg, const mq_jina_bert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                        const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -566,6 +566,60 @@ def t5_arch_from_hf_config(cfg: dict) -> T5Arch:
 
 
 @dataclass(frozen=True)
+class JinaBertArch:
+    """JinaBERT (jina-embeddings-v2-small-en / -base-en, their fine-tunes, MosaicBERT-style ALiBi encoders with the same block; config.json: model_type
+    "bert" with position_embedding_type "alibi") as the engine runs it: post-LN blocks, Linears with biases, a bias-free gated erf-GELU MLP, no position
+    table, a score bias of -slope_h |key - query|.  The block semantics restate the published architecture (the checkpoints are custom remote code)."""
+    vocab: int = 30528
+    max_pos: int = 8192                   # no position table: min(max_position_embeddings, what the attention kernel serves)
+    width: int = 768
+    layers: int = 12
+    heads: int = 12
+    head_dim: int = 64
+    mlp_dim: int = 3072
+    ln_eps: float = 1e-12
+    type_vocab: int = 2
+
+    def slopes(self) -> list:
+        """the ALiBi slope of every head, in float64: for a power-of-two head count n, s = 2^(-8 / n) and head i gets s^(i + 1); otherwise, with p the
+        largest power of two below n, the p slopes of p followed by the first n - p of slopes(2 p)[0::2]"""
+        def pow2(n):
+            s = 2.0 ** (-8.0 / n)
+            return [s ** (i + 1) for i in range(n)]
+        n = self.heads
+        p = 1 << (n.bit_length() - 1)
+        return pow2(n) if p == n else pow2(p) + pow2(2 * p)[0::2][:n - p]
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F = tokens, self.width, self.mlp_dim
+        return self.layers * (2 * T * W * 3 * W + 2 * T * W * W + 4 * T * T * W + 2 * 3 * T * W * F) / 1e9
+
+
+def jina_bert_arch_from_hf_config(cfg: dict) -> JinaBertArch:
+    """A local JinaBERT `config.json` (model_type "bert", position_embedding_type "alibi") -> JinaBertArch.  Refused, each by the name of its key: a
+    feed_forward_type other than geglu, a hidden_act other than gelu, heads that are not 64 wide, a hidden_size above 2048, an intermediate_size that is no
+    multiple of 64."""
+    mtype, pet = cfg.get("model_type", "bert"), cfg.get("position_embedding_type", "absolute")
+    if mtype != "bert" or pet != "alibi":
+        raise KeyError(f"model_type={mtype} with position_embedding_type={pet} is not a JinaBERT model")
+    fft = cfg.get("feed_forward_type", "original")
+    if fft != "geglu":
+        raise KeyError(f"feed_forward_type={fft} unsupported (geglu only)")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise KeyError(f"hidden_act={cfg.get('hidden_act')} unsupported (gelu only)")
+    W, heads, F = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["intermediate_size"])
+    if heads < 1 or W != heads * 64:
+        raise KeyError(f"hidden_size={W} / num_attention_heads={heads} unsupported (64-wide heads only)")
+    if W > 2048:
+        raise KeyError(f"hidden_size={W} unsupported (at most 2048)")
+    if F % 64 or F < 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    return JinaBertArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 8192)), 8192), width=W,
+                        layers=int(cfg["num_hidden_layers"]), heads=heads, mlp_dim=F, ln_eps=float(cfg.get("layer_norm_eps", 1e-12)),
+                        type_vocab=int(cfg.get("type_vocab_size", 2)))
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -837,13 +891,14 @@ STELLA_EN_400M = BertArch(vocab=30528, max_pos=8192, width=1024, layers=24, head
 HF_BERT_ARCHS["Marqo/dunzhang-stella_en_400M_v5"] = STELLA_EN_400M
 
 
-def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch, T5Arch]:
+def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch, T5Arch, JinaBertArch]:
     """A local HF `config.json` -> the arch of the text encoder the `hf` loader builds.  model_type bert, or xlm-roberta / roberta (the same encoder
     with the position ids shifted by padding_idx + 1: the multilingual-e5 family), mpnet and `new` give a BertArch (engine/towers.py::BertTower);
     model_type modernbert gives a ModernBertArch (engine/modernbert.py::ModernBertTower) — callers that can only run a BertArch (the cross-encoders of
     engine/rerank.py, which select their model types before they call) must not pass one through; model_type qwen3 / qwen2 gives a QwenArch
     (engine/qwen.py::QwenTower), model_type gemma3_text a GemmaArch (engine/gemma.py::GemmaTower) and model_type t5 a T5Arch (engine/t5.py::T5Tower) under
-    the same rule.  Anything else: KeyError."""
+    the same rule; so does model_type bert with position_embedding_type alibi, a JinaBertArch (engine/jina_bert.py::JinaBertTower).  Anything else:
+    KeyError."""
     mtype = cfg.get("model_type", "bert")
     if mtype == "t5":   # transformers T5EncoderModel: sentence-t5, gtr-t5, flan-t5 encoders (engine/t5.py::T5Tower)
         return t5_arch_from_hf_config(cfg)
@@ -875,6 +930,8 @@ def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenA
                         rel_buckets=int(cfg.get("relative_attention_num_buckets", 32)))
     if mtype not in ("bert", "xlm-roberta", "roberta"):
         raise KeyError(f"model_type={mtype} is not a BERT-family encoder")
+    if mtype == "bert" and cfg.get("position_embedding_type", "absolute") == "alibi":   # JinaBERT: jina-embeddings-v2 (engine/jina_bert.py::JinaBertTower)
+        return jina_bert_arch_from_hf_config(cfg)
     if cfg.get("position_embedding_type", "absolute") != "absolute":
         raise KeyError("only absolute position embeddings are supported")
     if cfg.get("hidden_act", "gelu") != "gelu":

@@ -254,6 +254,8 @@ class CrossEncoderTower(_PairScorer, BertTower):
             arch = archs.bert_arch_from_hf_config(cfg)
         except KeyError as e:
             raise ValueError(f"{directory}: {e}") from e
+        if isinstance(arch, archs.JinaBertArch):
+            raise ValueError(f"{directory}: position_embedding_type='alibi' (JinaBERT) is not served as a cross-encoder")
         arch = dataclasses.replace(arch, type_vocab=int(cfg.get("type_vocab_size", 2 if family is BERT else 1)))
         lower, max_len = _tokenizer_settings(directory)
         if family is BERT:

@@ -534,3 +534,38 @@ def t5_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
             out[f"block.{l}.ff.wi.weight"] = f32(m + "DenseReluDense.wi.weight", (F, W))
         out[f"block.{l}.ff.wo.weight"] = f32(m + "DenseReluDense.wo.weight", (W, F))
     return out
+
+
+def jina_bert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """JinaBERT tensors (JinaBertModel, or JinaBertFor... with their `bert.` prefix) -> the fp32 tensors the tower hands to the kernels.  Per block l the
+    three attention projections are fused into `layer.l.attn.qkv.weight` [3 W, W] / `.bias` [3 W] = rows query | key | value; `mlp.gated_layers.weight`
+    [2F, W] holds the activated ("gated") half in rows [:F] and the linear half in rows [F:] — the module computes wo(gelu(x W[:F]^T) * x W[F:]^T) — and is
+    reordered into `layer.l.mlp.up_gate.weight` = rows W[F:] | W[:F], (up | gate) as mq_glu reads it.  `type0` is row 0 of the token-type table (every
+    token of a single text has type 0).  Ignored: `pooler.*`, a stray `embeddings.position_embeddings.weight`, `embeddings.position_ids`.  Refused: a
+    state dict with `attention.self.layer_norm_q.*` / `layer_norm_k.*` — the qk-post-norm variants behind the -de / -es / -zh / -code checkpoints."""
+    if "embeddings.word_embeddings.weight" not in sd and "bert.embeddings.word_embeddings.weight" in sd:
+        sd = {k[len("bert."):]: v for k, v in sd.items() if k.startswith("bert.")}
+    qk_norm = sorted(k for k in sd if ".attention.self.layer_norm_q." in k or ".attention.self.layer_norm_k." in k)
+    if qk_norm:
+        raise ValueError(f"'{qk_norm[0]}': the qk-post-norm JinaBERT variants (the jina-embeddings-v2-base-de / -es / -zh / -code checkpoints normalise "
+                         f"query and key per head) are not served")
+    W, F = arch.width, arch.mlp_dim
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    out = {"word_embeddings.weight": f32("embeddings.word_embeddings.weight", (arch.vocab, W)),
+           "type0": f32("embeddings.token_type_embeddings.weight", (arch.type_vocab, W))[0].contiguous(),
+           "emb_ln.weight": f32("embeddings.LayerNorm.weight", (W,)), "emb_ln.bias": f32("embeddings.LayerNorm.bias", (W,))}
+    for l in range(arch.layers):
+        src, p = f"encoder.layer.{l}.", f"layer.{l}."
+        out[p + "attn.qkv.weight"] = torch.cat([f32(src + f"attention.self.{c}.weight", (W, W)) for c in ("query", "key", "value")], 0)
+        out[p + "attn.qkv.bias"] = torch.cat([f32(src + f"attention.self.{c}.bias", (W,)) for c in ("query", "key", "value")], 0)
+        out[p + "attn.o.weight"] = f32(src + "attention.output.dense.weight", (W, W))
+        out[p + "attn.o.bias"] = f32(src + "attention.output.dense.bias", (W,))
+        out[p + "attn_ln.weight"] = f32(src + "attention.output.LayerNorm.weight", (W,))
+        out[p + "attn_ln.bias"] = f32(src + "attention.output.LayerNorm.bias", (W,))
+        g = f32(src + "mlp.gated_layers.weight", (2 * F, W))
+        out[p + "mlp.up_gate.weight"] = torch.cat([g[F:], g[:F]], 0)
+        out[p + "mlp.wo.weight"] = f32(src + "mlp.wo.weight", (W, F))
+        out[p + "mlp.wo.bias"] = f32(src + "mlp.wo.bias", (W,))
+        out[p + "mlp_ln.weight"] = f32(src + "mlp.layernorm.weight", (W,))
+        out[p + "mlp_ln.bias"] = f32(src + "mlp.layernorm.bias", (W,))
+    return out

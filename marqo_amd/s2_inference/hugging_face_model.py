@@ -133,6 +133,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             if isinstance(arch, archs.T5Arch):
                 self._load_t5(directory, arch, sd)
                 return
+            if isinstance(arch, archs.JinaBertArch):
+                self._load_jina_bert(directory, arch, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -214,7 +217,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             raise InvalidModelPropertiesError(f"Invalid model properties: {self.model_properties.dict()}. Original error "
                                               f"{HuggingFaceModelProperties.POOLING_ERROR}")
 
-    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma, T5) share ----------------------------------------------------------
+    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma, T5, JinaBERT) share ------------------------------------------------
     def _refuse_fp8(self, family: str) -> None:
         props = self.model_properties
         if props.engine_precision == "fp8":
@@ -303,6 +306,22 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         except (OSError, ValueError, AttributeError):
             pass
         self._finish_packed(directory, arch, cap, T5Tower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="<pad>"), dense=dense)
+
+    def _load_jina_bert(self, directory: str, arch, sd) -> None:
+        """a JinaBERT checkpoint (model_type "bert" with position_embedding_type "alibi": jina-embeddings-v2-small-en / -base-en and their fine-tunes;
+        custom remote code to the reference's AutoModel, so refused unless trustRemoteCode is set): host tokenisation by the `tokenizers` library from the
+        directory's tokenizer.json with the file's own post-processor ([CLS] ... [SEP]), right-padded with [PAD], truncated at min(tokens,
+        max_position_embeddings, 8192); the tower of engine/jina_bert.py.  Pooling: the property, else 1_Pooling/config.json, else mean.  bf16 operands
+        only; no GPU tokeniser and no native request queue for this family."""
+        from marqo_amd.engine.jina_bert import JinaBertTower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        props = self.model_properties
+        if not props.trust_remote_code:
+            raise InvalidModelPropertiesError(f"{props.name} is a custom-code (JinaBERT) checkpoint: the reference loads it only with "
+                                              f"'trustRemoteCode': True")
+        self._refuse_fp8("JinaBERT encoders (their ALiBi attention / gated-GELU blocks run on bf16 operands only)")
+        self._check_width(arch.width)
+        self._finish_packed(directory, arch, arch.max_pos, JinaBertTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="[PAD]"))
 
     def _load_gemma(self, directory: str, arch, sd) -> None:
         """a transformers Gemma3TextModel checkpoint with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its
