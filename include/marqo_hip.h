@@ -1538,6 +1538,88 @@ size_t mq_jina_bert_workspace_bytes(const mq_jina_bert_cfg* cfg, int64_t rows, i
 int mq_encode_jina_bert(const mq_jina_bert_cfg* cfg, const mq_jina_bert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                         const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DeBERTa-v2 / -v3 rerankers: disentangled attention, the tower and the scoring call (csrc/attention_disentangled.hip, csrc/deberta.hip,
+ * csrc/rerank.hip; engine/deberta.py, engine/rerank.py) ---------------------------------------------------------------------------------------------------
+ * transformers' DebertaV2ForSequenceClassification with one label as the mxbai-rerank-*-v1 and cross-encoder/*-deberta-v3-* checkpoints configure it
+ * (config.json: model_type "deberta-v2", relative_attention, pos_att_type c2p | p2c, position_biased_input false, type_vocab_size 0, norm_rel_ebd
+ * "layer_norm", no convolution): post-LN BERT blocks with biases and an erf-GELU MLP, no position table, and
+ *   scores[q, k] = scale (Q_q . K_k + Q_q . Kr[idx(q - k)] + K_k . Qr[idx(q - k)]),  scale = 1 / sqrt(3 head_dim).
+ * Additions to ABI 15: nothing above changes; the structs and entry points below are new.  Every entry point judges its arguments before any launch
+ * (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_disentangled: d_qkv bf16 [.., 3 inner] = (q | k | v), inner = heads head_dim, head h at columns h head_dim .. of each third; d_out bf16
+ *                   [.., inner]; head_dim 64; sequences packed (d_cu_seqlens int32 [nseq + 1] holds ABSOLUTE row offsets into d_qkv / d_out: its first
+ *                   entry need not be 0, so a batch can run in groups behind a moved pointer) or fixed_len > 0; max_len <= 8192.  rows = the call's token
+ *                   rows (d_cu_seqlens[nseq] - d_cu_seqlens[0], or nseq fixed_len).  d_pos_key / d_pos_query bf16 [heads][2 span][64] = Kr / Qr, span in
+ *                   [1, 1024].  d_idx int32 [2 reach + 1]: entry d + reach = idx(d) in [0, 2 span - 1], the bucket of query - key == d, non-decreasing in
+ *                   d, built by the caller on the host (the kernel forms no logarithm); max_len > reach + 1 is refused.  [win_lo, win_hi] = [idx(-(max_len
+ *                   - 1)), idx(max_len - 1)]: the buckets the call can touch.  The position scores pass through the workspace as fp32 strips
+ *                   [rows][heads][2][win rounded up to 16] (mq_attention_disentangled_workspace_bytes; MQ_ERR_WORKSPACE when short); no [T, T] tensor
+ *                   exists in global memory.  nseq <= 0: MQ_OK, nothing is written.  Compiler report (gfx950): csrc/attention_disentangled.hip's header.
+ *   mq_encode_deberta: token gather + LayerNorm -> `layers` blocks  x = LN(Wo(attn(Wqkv(x))) + x) ; x = LN(W2(gelu(W1(x))) + x)  -> mq_pool (MQ_POOL_CLS or
+ *                   MQ_POOL_MEAN) (+ L2), on packed sequences like mq_encode_bert; fp32 residual stream, bf16 GEMM operands.  width a multiple of 64, <=
+ *                   2048; head_dim 64; heads * 64 == width; mlp_dim % 64 == 0; max_pos <= min(8192, reach + 1).  The attention runs over groups of whole
+ *                   sequences whose strips stay under 256 MiB (or one sequence's, when that alone is larger).  d_out fp32 [nseq, width].
+ *   mq_score_head_gelu: mq_score_head with the erf GELU in place of tanh (ContextPooler: pooler.dense -> GELU -> classifier); the same weights struct
+ *                   (type_vocab is not read) and scratch (mq_score_head_workspace_bytes).
+ *   mq_score_pairs_deberta: mq_encode_deberta(cfg, w, ..., normalize = 0) with cfg->pool == MQ_POOL_CLS into a scratch slot (d_pooled fp32 [nseq, W],
+ *                   NULL ok, receives a copy) -> mq_score_head_gelu.  d_logits fp32 [nseq]; d_scores (NULL ok) = sigmoid.  Scratch:
+ *                   mq_score_pairs_deberta_workspace_bytes(cfg, rows, nseq). */
+typedef struct mq_deberta_layer {
+    const void*  qkv_w;         /* bf16 [3 W, W]  rows: query_proj | key_proj | value_proj */
+    const float* qkv_b;         /* fp32 [3 W] */
+    const void*  out_w;         /* bf16 [W, W]  attention.output.dense */
+    const float* out_b;         /* fp32 [W] */
+    const float* attn_ln_g;     /* fp32 [W]  attention.output.LayerNorm */
+    const float* attn_ln_b;
+    const void*  fc1_w;         /* bf16 [F, W]  intermediate.dense */
+    const float* fc1_b;         /* fp32 [F] */
+    const void*  fc2_w;         /* bf16 [W, F]  output.dense */
+    const float* fc2_b;         /* fp32 [W] */
+    const float* mlp_ln_g;      /* fp32 [W]  output.LayerNorm */
+    const float* mlp_ln_b;
+    const void*  pos_key;       /* bf16 [heads][2 span][64]  Kr = key_proj | pos_key_proj of LayerNorm(rel_embeddings), split into heads */
+    const void*  pos_query;     /* bf16 [heads][2 span][64]  Qr = query_proj | pos_query_proj of the same rows */
+} mq_deberta_layer;
+
+typedef struct mq_deberta_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  embeddings.word_embeddings */
+    const float* emb_ln_g;      /* fp32 [W]  embeddings.LayerNorm */
+    const float* emb_ln_b;
+    const int32_t* d_idx;       /* device int32 [2 reach + 1]: entry d + reach = the bucket of query - key == d */
+    const int32_t* h_idx;       /* the same table on the host */
+    const mq_deberta_layer* layers;  /* host array, `layers` entries */
+} mq_deberta_weights;
+
+typedef struct mq_deberta_cfg {
+    int32_t width;         /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t heads;         /* heads * 64 == W */
+    int32_t head_dim;      /* 64 */
+    int32_t mlp_dim;       /* F = intermediate_size, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;       /* longest sequence served (<= 8192, <= reach + 1) */
+    int32_t pool;          /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    int32_t span;          /* S = position_buckets: the position tables have 2 S rows */
+    int32_t reach;         /* the index table covers |query - key| <= reach */
+    float   ln_eps;        /* layer_norm_eps */
+    int32_t reserved;
+} mq_deberta_cfg;
+
+size_t mq_attention_disentangled_workspace_bytes(int64_t rows, int32_t heads, int32_t win_lo, int32_t win_hi);
+int mq_attention_disentangled(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int64_t rows, int32_t fixed_len, int32_t max_len,
+                              int32_t heads, int32_t head_dim, const void* d_pos_key, const void* d_pos_query, const int32_t* d_idx, int32_t reach,
+                              int32_t span, int32_t win_lo, int32_t win_hi, float scale, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t mq_deberta_workspace_bytes(const mq_deberta_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_deberta(const mq_deberta_cfg* cfg, const mq_deberta_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                      const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+int mq_score_head_gelu(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores, void* d_workspace,
+                       size_t workspace_bytes, void* stream);
+size_t mq_score_pairs_deberta_workspace_bytes(const mq_deberta_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_score_pairs_deberta(const mq_deberta_cfg* cfg, const mq_deberta_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                           const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits, float* d_scores, float* d_pooled,
+                           void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attention_disentangled", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -273,6 +273,22 @@ class JinaBertCfg(C.Structure):
                 ("max_pos", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+class DebertaLayer(C.Structure):
+    """mq_deberta_layer: one DeBERTa-v2 block with its projected position tables (csrc/deberta.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "qkv_b", "out_w", "out_b", "attn_ln_g", "attn_ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "mlp_ln_g",
+                                          "mlp_ln_b", "pos_key", "pos_query")]
+
+
+class DebertaWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("emb_ln_g", C.c_void_p), ("emb_ln_b", C.c_void_p), ("d_idx", C.c_void_p), ("h_idx", C.c_void_p),
+                ("layers", C.POINTER(DebertaLayer))]
+
+
+class DebertaCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32), ("vocab", C.c_int32),
+                ("max_pos", C.c_int32), ("pool", C.c_int32), ("span", C.c_int32), ("reach", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -452,6 +468,17 @@ _SIGNATURES = {
     "mq_attention_alibi": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P]),
     "mq_jina_bert_workspace_bytes": (C.c_size_t, [C.POINTER(JinaBertCfg), C.c_int64, C.c_int64]),
     "mq_encode_jina_bert": (C.c_int, [C.POINTER(JinaBertCfg), C.POINTER(JinaBertWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # DeBERTa-v2 / -v3 rerankers: disentangled attention, the tower, the GELU head and the scoring call (csrc/attention_disentangled.hip,
+    # csrc/deberta.hip, csrc/rerank.hip; engine/deberta.py, engine/rerank.py)
+    "mq_attention_disentangled_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "mq_attention_disentangled": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_float, _P, C.c_size_t, _P]),
+    "mq_deberta_workspace_bytes": (C.c_size_t, [C.POINTER(DebertaCfg), C.c_int64, C.c_int64]),
+    "mq_encode_deberta": (C.c_int, [C.POINTER(DebertaCfg), C.POINTER(DebertaWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    "mq_score_head_gelu": (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(ScoreHeadWeights), _P, _P, _P, C.c_size_t, _P]),
+    "mq_score_pairs_deberta_workspace_bytes": (C.c_size_t, [C.POINTER(DebertaCfg), C.c_int64, C.c_int64]),
+    "mq_score_pairs_deberta": (C.c_int, [C.POINTER(DebertaCfg), C.POINTER(DebertaWeights), C.POINTER(ScoreHeadWeights), _P, _P, _P, C.c_int64,
+                                         _P, _P, _P, _P, C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

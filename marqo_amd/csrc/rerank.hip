@@ -8,6 +8,8 @@
 //   * mq_score_pairs_xlmr: the same with mq_encode_bert's own embedding (one type row; the position table starts at the offset row).
 //   * score_head_ln: ModernBERT's classification head: dense + erf-GELU (mq_gemm_bf16's epilogue), then LayerNorm and the one-logit classifier
 //     fused in one wave64 per pair (+ sigmoid).  mq_score_pairs_modernbert: mq_encode_modernbert (normalize = 0) -> that head.
+//   * mq_score_head_gelu: DeBERTa's ContextPooler head: dense -> erf GELU -> one-logit classifier (+ sigmoid); mq_score_head with the tail's activation
+//     swapped (score_tail_kernel's template parameter).  mq_score_pairs_deberta: mq_encode_deberta (CLS rows, normalize = 0) -> that head.
 // All of it is bandwidth-trivial next to the encoder: coalesced, bounds-guarded, untuned.
 // WS_ALIGN and score_pairs' packed-sequence checks are packed_text.h's.
 #include "packed_text.h"
@@ -154,7 +156,10 @@ __global__ __launch_bounds__(256, (CH <= 2 ? 8 : 4)) void embed_tokens_typed_ker
 }
 
 // ---- classifier on the pooler's pre-activation: one wave64 per pair --------------------------------------------------------------------
-// z = sum_j cls_w[j] tanhf(p[j]) + cls_b: lane c takes columns c, c + 64, ... (fma chain), the xor butterfly adds the lanes
+// z = sum_j cls_w[j] act(p[j]) + cls_b: lane c takes columns c, c + 64, ... (fma chain), the xor butterfly adds the lanes.  GELU = false: act = tanhf
+// (BERT's pooler, RoBERTa's classification head); GELU = true: the erf GELU 0.5 x (1 + erff(x / sqrt(2))) with libm's erff (DeBERTa's ContextPooler —
+// n W values per call: the GEMM epilogues' polynomial, rounded to bf16 there, would be the largest error of a logit here)
+template <bool GELU>
 __global__ __launch_bounds__(256) void score_tail_kernel(const float* __restrict__ p, const float* __restrict__ cls_w, float cls_b, int64_t n,
                                                          int W, float* __restrict__ logits, float* __restrict__ scores) {
     const int lane = threadIdx.x & 63;
@@ -162,7 +167,10 @@ __global__ __launch_bounds__(256) void score_tail_kernel(const float* __restrict
     if (r >= n) return;
     const float* pr = p + r * W;
     float acc = 0.f;
-    for (int j = lane; j < W; j += 64) acc = fmaf(cls_w[j], tanhf(pr[j]), acc);
+    for (int j = lane; j < W; j += 64) {
+        const float x = pr[j];
+        acc = fmaf(cls_w[j], GELU ? 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)) : tanhf(x), acc);
+    }
     const float z = wave_sum(acc) + cls_b;
     if (lane == 0) {
         logits[r] = z;
@@ -321,16 +329,19 @@ extern "C" size_t mq_score_head_workspace_bytes(int64_t n, int32_t W) {
     return head_plan(n, W).total;
 }
 
-extern "C" int mq_score_head(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
-                             void* d_workspace, size_t workspace_bytes, void* stream) {
-    MQ_CHECK_ARG(head, "mq_score_head: null head");
-    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "mq_score_head: W=%d must be a multiple of 64, at most %d", W, 64 * 4 * MAXC);
-    MQ_CHECK_ARG(head->pooler_w && head->pooler_b && head->cls_w, "mq_score_head: null weight pointer");
-    MQ_CHECK_ARG(n < (1ll << 31), "mq_score_head: n=%lld too large", (long long)n);
+namespace {
+// dense (mq_gemm_bf16, fp32 pre-activation) -> score_tail_kernel<GELU>; `what` (the entry point's name) opens every message
+template <bool GELU>
+int score_head(const char* what, const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
+               void* d_workspace, size_t workspace_bytes, void* stream) {
+    MQ_CHECK_ARG(head, "%s: null head", what);
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "%s: W=%d must be a multiple of 64, at most %d", what, W, 64 * 4 * MAXC);
+    MQ_CHECK_ARG(head->pooler_w && head->pooler_b && head->cls_w, "%s: null weight pointer", what);
+    MQ_CHECK_ARG(n < (1ll << 31), "%s: n=%lld too large", what, (long long)n);
     if (n <= 0) return MQ_OK;
-    MQ_CHECK_ARG(d_h && d_logits && d_workspace, "mq_score_head: null input / output / workspace");
+    MQ_CHECK_ARG(d_h && d_logits && d_workspace, "%s: null input / output / workspace", what);
     const HeadPlan hp = head_plan(n, W);
-    if (workspace_bytes < hp.total) { mq_set_error("mq_score_head: workspace %zu < required %zu", workspace_bytes, hp.total); return MQ_ERR_WORKSPACE; }
+    if (workspace_bytes < hp.total) { mq_set_error("%s: workspace %zu < required %zu", what, workspace_bytes, hp.total); return MQ_ERR_WORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     void* hb = base + hp.off_hb;
@@ -338,9 +349,22 @@ extern "C" int mq_score_head(const float* d_h, int64_t n, int32_t W, const mq_sc
     MQ_TRY(mq_cast_bf16(d_h, hb, n * W, s));
     MQ_TRY(mq_gemm_bf16(hb, W, head->pooler_w, W, head->pooler_b, nullptr, p, W, n, W, W, MQ_EPI_BIAS | MQ_EPI_OUT_F32, s));
     MqProfScope prof(4, s);
-    hipLaunchKernelGGL(score_tail_kernel, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, s, p, head->cls_w, head->cls_b, n, W, d_logits, d_scores);
-    MQ_CHECK_LAUNCH("mq_score_head");
+    hipLaunchKernelGGL(score_tail_kernel<GELU>, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, s, p, head->cls_w, head->cls_b, n, W, d_logits, d_scores);
+    MQ_CHECK_LAUNCH(what);
     return MQ_OK;
+}
+}  // namespace
+
+extern "C" int mq_score_head(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
+                             void* d_workspace, size_t workspace_bytes, void* stream) {
+    return score_head<false>("mq_score_head", d_h, n, W, head, d_logits, d_scores, d_workspace, workspace_bytes, stream);
+}
+
+// DeBERTa's ContextPooler head: gelu(pooler_w bf16(h) + pooler_b) . cls_w + cls_b; the weights struct, the scratch (mq_score_head_workspace_bytes) and the
+// checks are mq_score_head's, type_vocab is not read
+extern "C" int mq_score_head_gelu(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
+                                  void* d_workspace, size_t workspace_bytes, void* stream) {
+    return score_head<true>("mq_score_head_gelu", d_h, n, W, head, d_logits, d_scores, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mq_score_pairs_workspace_bytes(const mq_bert_cfg* cfg, int64_t rows, int64_t nseq) {
@@ -488,4 +512,51 @@ extern "C" int mq_score_pairs_modernbert(const mq_modernbert_cfg* cfg, const mq_
     MQ_TRY(mq_encode_modernbert(cfg, w, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, pooled, 0, base + p.off_enc, p.enc_bytes, stream));
     if (d_pooled) MQ_CHECK_HIP(hipMemcpyAsync(d_pooled, pooled, (size_t)nseq * W * 4, hipMemcpyDeviceToDevice, s));
     return mq_score_head_ln(pooled, nseq, W, head, d_logits, d_scores, base + p.off_head, workspace_bytes - p.off_head, stream);
+}
+
+// ---- DeBERTa-v2 / -v3 cross-encoders ---------------------------------------------------------------------------------------------------------
+namespace {
+struct PairsDebPlan { size_t off_enc, enc_bytes, off_pooled, off_head, total; };
+// [ mq_deberta_workspace_bytes: the encoder's own scratch ] [ CLS rows fp32 [nseq, W] ] [ head scratch ]
+PairsDebPlan pairs_deb_plan(const mq_deberta_cfg* cfg, int64_t rows, int64_t nseq) {
+    PairsDebPlan p;
+    Off ws;
+    p.enc_bytes = mq_deberta_workspace_bytes(cfg, rows, nseq);
+    p.off_enc = ws.take(p.enc_bytes);
+    p.off_pooled = ws.take((size_t)nseq * cfg->width * 4);
+    p.off_head = ws.take(head_plan(nseq, cfg->width).total);
+    p.total = ws.end();
+    return p;
+}
+}  // namespace
+
+extern "C" size_t mq_score_pairs_deberta_workspace_bytes(const mq_deberta_cfg* cfg, int64_t rows, int64_t nseq) {
+    if (!cfg || rows <= 0 || nseq <= 0 || cfg->width <= 0) return 0;
+    return pairs_deb_plan(cfg, rows, nseq).total;
+}
+
+// The encoder IS mq_encode_deberta (normalize = 0, CLS pooling) writing into this call's pooled slot; what it refuses it refuses here, under its own name.
+extern "C" int mq_score_pairs_deberta(const mq_deberta_cfg* cfg, const mq_deberta_weights* w, const mq_score_head_weights* head, const int32_t* d_ids,
+                                      const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits, float* d_scores,
+                                      float* d_pooled, void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "mq_score_pairs_deberta";
+    MQ_CHECK_ARG(cfg && w, "%s: null cfg / weights", what);
+    MQ_CHECK_ARG(head, "%s: null head", what);
+    MQ_CHECK_ARG(cfg->pool == MQ_POOL_CLS, "%s: bad pooling %d (MQ_POOL_CLS: the ContextPooler reads the first row)", what, cfg->pool);
+    const int W = cfg->width;
+    MQ_CHECK_ARG(W >= 64 && W % 64 == 0 && W <= 64 * 4 * MAXC, "%s: W=%d must be a multiple of 64, at most %d", what, W, 64 * 4 * MAXC);
+    MQ_CHECK_ARG(head->pooler_w && head->pooler_b && head->cls_w, "%s: null weight pointer (pooler_w / pooler_b / cls_w)", what);
+    MQ_CHECK_ARG(nseq >= 1 && nseq < (1ll << 31), "%s: nseq=%lld must be in [1, 2^31)", what, (long long)nseq);
+    MQ_CHECK_ARG(d_logits, "%s: null output", what);
+    int maxl = 0;
+    int64_t rows = 0;
+    MQ_TRY(packed_begin(what, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
+    const PairsDebPlan p = pairs_deb_plan(cfg, rows, nseq);
+    MQ_TRY(packed_workspace(what, workspace_bytes, p.total));
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_workspace;
+    float* pooled = (float*)(base + p.off_pooled);
+    MQ_TRY(mq_encode_deberta(cfg, w, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, pooled, 0, base + p.off_enc, p.enc_bytes, stream));
+    if (d_pooled) MQ_CHECK_HIP(hipMemcpyAsync(d_pooled, pooled, (size_t)nseq * W * 4, hipMemcpyDeviceToDevice, s));
+    return mq_score_head_gelu(pooled, nseq, W, head, d_logits, d_scores, base + p.off_head, workspace_bytes - p.off_head, stream);
 }

@@ -620,6 +620,100 @@ def jina_bert_arch_from_hf_config(cfg: dict) -> JinaBertArch:
 
 
 @dataclass(frozen=True)
+class DebertaArch:
+    """DeBERTa-v2 / -v3 (transformers DebertaV2Model, config.json model_type "deberta-v2") as the engine runs it for the one-label rerankers: post-LN BERT
+    blocks with biases and an erf-GELU MLP, no position table and no type row, disentangled attention — content-to-content plus the c2p and p2c terms
+    read from the projected, LayerNorm-ed `rel_embeddings` [2 span, W] through the log-bucket index of query - key — and a ContextPooler head."""
+    vocab: int = 128100
+    max_pos: int = 8192                   # no position table: what the attention kernel serves
+    width: int = 768
+    layers: int = 12
+    heads: int = 12
+    head_dim: int = 64
+    mlp_dim: int = 3072
+    ln_eps: float = 1e-7
+    span: int = 256                       # S = position_buckets: rel_embeddings has 2 S rows
+    max_rel: int = 512                    # max_relative_positions (below 1 in the config: max_position_embeddings)
+    share_att_key: bool = True            # the position tables go through key_proj / query_proj (false: pos_key_proj / pos_query_proj)
+
+    def idx_table(self, reach: int):
+        """int32 [2 reach + 1]: entry d + reach = clamp(span + b(d), 0, 2 span - 1), b = the log bucket of the distance d = query - key — the row of the
+        position tables both disentangled terms read.  The arithmetic is the modelling code's own, step for step in its dtypes (the integer quotient and
+        the logarithms in fp32): a ceil(log(.)) formed in another precision moves a bucket with one ulp.  The kernel needs the table non-decreasing
+        (a call touches only the window between the buckets of its longest sequence's two ends): checked here."""
+        import torch
+        S, mid = self.span, self.span // 2
+        d = torch.arange(-int(reach), int(reach) + 1, dtype=torch.long)
+        sign = torch.sign(d)
+        a = torch.where((d < mid) & (d > -mid), torch.tensor(mid - 1).type_as(d), torch.abs(d))
+        log_pos = torch.ceil(torch.log(a / mid) / torch.log(torch.tensor((self.max_rel - 1) / mid)) * (mid - 1)) + mid
+        b = torch.where(a <= mid, d.type_as(log_pos), log_pos * sign).to(torch.long)
+        t = (b + S).clamp(0, 2 * S - 1).to(torch.int32)
+        if bool((t[1:] < t[:-1]).any()):
+            raise ValueError(f"position_buckets={S} with max_relative_positions={self.max_rel}: the bucket index is not monotone in the distance")
+        return t
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F = tokens, self.width, self.mlp_dim
+        win = min(2 * self.span, 2 * T - 1)
+        return self.layers * (2 * T * W * 3 * W + 2 * T * W * W + 4 * T * T * W + 4 * T * win * W + 2 * 2 * T * W * F) / 1e9
+
+
+def deberta_arch_from_hf_config(cfg: dict) -> DebertaArch:
+    """A local DeBERTa-v2 / -v3 `config.json` -> DebertaArch.  Refused, each with a ValueError that names its key: model_type other than deberta-v2
+    (DeBERTa v1 has another attention), relative_attention false, pos_att_type other than exactly {c2p, p2c}, position_biased_input true,
+    conv_kernel_size > 0, norm_rel_ebd other than layer_norm, type_vocab_size > 0, embedding_size != hidden_size, pooler_hidden_size != hidden_size,
+    pooler_hidden_act / hidden_act other than gelu, heads that are not 64 wide, hidden_size above 2048, position_buckets outside [2, 1024] (1: the
+    bucket formula divides by position_buckets // 2), max_relative_positions too small for the log buckets, an intermediate_size that is no multiple
+    of 64."""
+    mtype = cfg.get("model_type")
+    if mtype != "deberta-v2":
+        raise ValueError(f"model_type={mtype!r} is not served (DeBERTa-v2 / -v3 only: model_type 'deberta-v2'; DeBERTa v1 has another attention)")
+    if not cfg.get("relative_attention", False):
+        raise ValueError("relative_attention=false is not served (the tower runs disentangled attention only)")
+    pat = cfg.get("pos_att_type") or []
+    if isinstance(pat, str):
+        pat = [x.strip() for x in pat.lower().split("|") if x.strip()]
+    if sorted(pat) != ["c2p", "p2c"]:
+        raise ValueError(f"pos_att_type={cfg.get('pos_att_type')!r} is not served (exactly c2p and p2c)")
+    if cfg.get("position_biased_input", True):
+        raise ValueError("position_biased_input=true is not served (no absolute position table is added)")
+    if int(cfg.get("conv_kernel_size", 0) or 0) > 0:
+        raise ValueError(f"conv_kernel_size={cfg.get('conv_kernel_size')} is not served (no convolution layer)")
+    nre = cfg.get("norm_rel_ebd", "none")
+    if [x.strip() for x in str(nre).lower().split("|")] != ["layer_norm"]:
+        raise ValueError(f"norm_rel_ebd={nre!r} is not served (layer_norm only)")
+    if int(cfg.get("type_vocab_size", 0) or 0) > 0:
+        raise ValueError(f"type_vocab_size={cfg.get('type_vocab_size')} is not served (no token-type row is added)")
+    W, heads, F = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["intermediate_size"])
+    if int(cfg.get("embedding_size", W) or W) != W:
+        raise ValueError(f"embedding_size={cfg.get('embedding_size')} != hidden_size={W} is not served (no embedding projection)")
+    if int(cfg.get("pooler_hidden_size", W) or W) != W:
+        raise ValueError(f"pooler_hidden_size={cfg.get('pooler_hidden_size')} != hidden_size={W} is not served")
+    if cfg.get("pooler_hidden_act", "gelu") != "gelu":
+        raise ValueError(f"pooler_hidden_act={cfg.get('pooler_hidden_act')!r} is not served (gelu only)")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"hidden_act={cfg.get('hidden_act')!r} is not served (gelu only)")
+    if heads < 1 or W != heads * 64:
+        raise ValueError(f"hidden_size={W} / num_attention_heads={heads} is not served (64-wide heads only)")
+    if W > 2048:
+        raise ValueError(f"hidden_size={W} is not served (at most 2048)")
+    if F % 64 or F < 64:
+        raise ValueError(f"intermediate_size={F} must be a multiple of 64")
+    S = int(cfg.get("position_buckets", -1))
+    if S < 2 or S > 1024:
+        raise ValueError(f"position_buckets={S} is not served (2 .. 1024)")
+    max_rel = int(cfg.get("max_relative_positions", -1))
+    if max_rel < 1:
+        max_rel = int(cfg["max_position_embeddings"])
+    if max_rel - 1 <= S // 2:
+        raise ValueError(f"max_relative_positions={max_rel} is not served with position_buckets={S} (the log buckets need max_relative_positions - 1 > "
+                         f"position_buckets // 2)")
+    return DebertaArch(vocab=int(cfg["vocab_size"]), max_pos=8192, width=W, layers=int(cfg["num_hidden_layers"]), heads=heads, mlp_dim=F,
+                       ln_eps=float(cfg.get("layer_norm_eps", 1e-7)), span=S, max_rel=max_rel, share_att_key=bool(cfg.get("share_att_key", False)))
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,

@@ -9,8 +9,10 @@ The texts are tokenised once on the GPU (engine/gpu_tokenizers.py), paired, trun
 mq_pack_pairs_xlmr), and every batch is ONE mq_score_pairs_bert | mq_score_pairs_xlmr call.
 A third family runs on the ModernBERT tower (ModernBertCrossEncoderTower: `ModernBertForSequenceClassification`, [CLS] a [SEP] b [SEP], mean or CLS
 pooling, dense -> GELU -> LayerNorm -> classifier; one mq_score_pairs_modernbert call per batch).  Its texts are tokenised once on the HOST, by the
-`tokenizers` library from the checkpoint's tokenizer.json; pairing, truncation and packing are the same GPU calls.  What the towers share — the
-length cap, the longest-first order, the batch loop — is `_PairScorer.score`.
+`tokenizers` library from the checkpoint's tokenizer.json; pairing, truncation and packing are the same GPU calls.  A fourth runs on the DeBERTa tower
+(DebertaCrossEncoderTower: `DebertaV2ForSequenceClassification`, [CLS] a [SEP] b [SEP], disentangled attention, ContextPooler head; one
+mq_score_pairs_deberta call per batch), tokenised on the host in the same way.  What the towers share — the length cap, the longest-first order, the
+batch loop — is `_PairScorer.score`.  `load_cross_encoder_tower` picks the class from a directory's config.json.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch
 
 from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
+from marqo_amd.engine.deberta import DebertaTower
 from marqo_amd.engine.modernbert import ModernBertTower
 from marqo_amd.engine.tokenizers import HfJsonTokenizer, RobertaBpeTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
 from marqo_amd.engine.tower_weights import modernbert_head_tensors
@@ -411,6 +414,86 @@ class ModernBertCrossEncoderTower(_PairScorer, ModernBertTower):
         L.check(self.lib.mq_score_pairs_modernbert(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_cu.data_ptr(),
                                                    cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores), L.ptr(pooled),
                                                    ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_modernbert")
+
+
+class DebertaCrossEncoderTower(_PairScorer, DebertaTower):
+    """`DebertaV2ForSequenceClassification` (num_labels = 1; the mxbai-rerank-*-v1 and cross-encoder/*-deberta-v3-* checkpoints): `deberta.*` = the encoder
+    (engine/tower_weights.py::deberta_state_dict), `pooler.dense` -> GELU -> `classifier` on the final [CLS] row = the head (mq_score_head_gelu).  Pairs
+    are [CLS] a [SEP] b [SEP]; token-type ids are not read (type_vocab_size 0).  score() returns the raw logits and their sigmoid."""
+    pair_specials = 3
+    pair_id_rows = 2        # mq_pack_pairs also writes token-type ids: a scratch row nobody reads
+
+    def __init__(self, arch: archs.DebertaArch, sd: Dict[str, Tensor], device: str, tokenizer, model_max_length: int = 512, precision: str = "bf16"):
+        super().__init__(arch, sd, device, pooling="cls", precision=precision, max_len=int(min(model_max_length, 8192)))
+        h, t, W = self._h, self.tensors, arch.width
+        self.head = L.ScoreHeadWeights(pooler_w=h.bf16(t["pooler.weight"]), pooler_b=h.f32(t["pooler.bias"]), cls_w=h.f32(t["classifier.weight"].reshape(W)),
+                                       cls_b=float(t["classifier.bias"].reshape(-1)[0]), type_vocab=1)
+        self.tokenizer = tokenizer
+        self.model_max_length = int(self.arch.max_pos)      # min(the tokenizer's, 8192): the index table is built for it
+
+    @classmethod
+    def from_dir(cls, directory: str, device: str, precision: str = "bf16") -> "DebertaCrossEncoderTower":
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, tokenizer.json, tokenizer_config.json"""
+        cfg, sd = checkpoint.load_hf_dir(directory)
+        return cls._from_loaded(directory, cfg, sd, device, precision)
+
+    @classmethod
+    def _from_loaded(cls, directory: str, cfg: dict, sd: Dict[str, Tensor], device: str, precision: str = "bf16") -> "DebertaCrossEncoderTower":
+        if precision != "bf16":
+            raise ValueError(f"{directory}: enginePrecision={precision!r} is not served for DeBERTa cross-encoders (bf16 operands only)")
+        try:
+            arch = archs.deberta_arch_from_hf_config(cfg)
+        except KeyError as e:
+            raise ValueError(f"{directory}: config.json has no {e.args[0] if e.args else e}") from e
+        except ValueError as e:
+            raise ValueError(f"{directory}: {e}") from e
+        labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
+        if int(labels) != 1:
+            raise ValueError(f"{directory}: num_labels={labels} is not served as a cross-encoder (only one-logit heads)")
+        if not os.path.isfile(os.path.join(directory, "tokenizer.json")):
+            only_spm = " (spm.model alone is not read: export the fast tokenizer)" if os.path.isfile(os.path.join(directory, "spm.model")) else ""
+            raise ValueError(f"{directory}: a DeBERTa cross-encoder needs the checkpoint's tokenizer.json, which is not there{only_spm}")
+        tokenizer = HfJsonTokenizer(directory, **_special_spellings(directory, cls="[CLS]", sep="[SEP]", pad="[PAD]"))
+        _, max_len = _tokenizer_settings(directory, default_max=512)
+        return cls(arch, sd, device, tokenizer, model_max_length=max_len, precision=precision)
+
+    # ---- what _PairScorer.score asks of this tower ------------------------------------------------------------------------------------
+    def _tokenize(self, texts: Sequence[str], cap: int) -> Tuple[Tensor, np.ndarray]:
+        ids, lens = hf_rows(self.tokenizer, texts, cap)
+        return self._to_device(torch.from_numpy(ids)), lens
+
+    def _tokenize_query(self, query: str) -> Tuple[Tensor, np.ndarray]:
+        return self._tokenize([query], None)
+
+    def _pack_chunk(self, pack: tuple, d_ids: Tensor, rows: int, stream: int) -> None:
+        L.check(self.lib.mq_pack_pairs(*pack, d_ids[1].data_ptr(), rows, stream), "mq_pack_pairs")
+
+    def _score_chunk(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Tensor, rows: int, m: int) -> None:
+        ws = self._workspace(self.lib.mq_score_pairs_deberta_workspace_bytes(C.byref(self.cfg), rows, m))
+        self.score_packed(d_ids[0], d_cu, cu, logits, scores, None, ws)
+
+    def score_packed(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, logits: Tensor, scores: Optional[Tensor], pooled: Optional[Tensor],
+                     ws: Tensor) -> None:
+        """one mq_score_pairs_deberta call on this thread's current stream: packed ids int32 [rows], cu_seqlens on the device and the host, logits /
+        scores fp32 [nseq] (scores may be None), pooled fp32 [nseq, W] or None"""
+        L.check(self.lib.mq_score_pairs_deberta(C.byref(self.cfg), C.byref(self.w), C.byref(self.head), d_ids.data_ptr(), d_cu.data_ptr(),
+                                                cu.data_ptr(), int(cu.numel()) - 1, logits.data_ptr(), L.ptr(scores), L.ptr(pooled),
+                                                ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_deberta")
+
+
+def load_cross_encoder_tower(directory: str, device: str):
+    """the cross-encoder tower of a local Hugging Face directory, by its config.json: model_type "deberta-v2" -> DebertaCrossEncoderTower.from_dir,
+    "deberta" (v1) is refused here by name, everything else -> CrossEncoderTower.from_dir (which picks among BERT, XLM-RoBERTa / RoBERTa and ModernBERT
+    and refuses the rest)"""
+    mtype = None
+    try:
+        with open(os.path.join(directory, "config.json")) as f:
+            mtype = json.load(f).get("model_type")
+    except (OSError, ValueError, AttributeError):
+        pass                                 # (the loader below reports a missing or broken config.json in its own words)
+    if mtype in ("deberta-v2", "deberta"):   # ("deberta": deberta_arch_from_hf_config refuses it, naming model_type)
+        return DebertaCrossEncoderTower.from_dir(directory, device)
+    return CrossEncoderTower.from_dir(directory, device)
 
 
 def hf_rows(tokenizer: HfJsonTokenizer, texts: Sequence[str], cap: Optional[int]) -> Tuple[np.ndarray, np.ndarray]:

@@ -569,3 +569,46 @@ def jina_bert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
         out[p + "mlp_ln.weight"] = f32(src + "mlp.layernorm.weight", (W,))
         out[p + "mlp_ln.bias"] = f32(src + "mlp.layernorm.bias", (W,))
     return out
+
+
+def deberta_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' DebertaV2ForSequenceClassification tensors (`deberta.*` + `pooler.dense.*` + `classifier.*`) -> the fp32 tensors the tower hands to
+    the kernels.  Per block l the three attention projections are fused into `layer.l.attn.qkv.weight` [3 W, W] / `.bias` [3 W] = rows query_proj |
+    key_proj | value_proj.  The position tables depend on weights only and are folded here: rel = LayerNorm_encoder(encoder.rel_embeddings.weight)
+    [2 S, W], and per block `layer.l.pos_key` = key_proj(rel) and `layer.l.pos_query` = query_proj(rel) when arch.share_att_key, else pos_key_proj(rel)
+    / pos_query_proj(rel) — biases included, split into heads: [heads, 2 S, 64].  They are formed in float64 and stored as fp32 (the tower converts to
+    bf16).  The head comes back as `pooler.weight` [W, W], `pooler.bias` [W], `classifier.weight` [1, W], `classifier.bias` [1].  Ignored:
+    `lm_predictions.*`, `mask_predictions.*`, `deberta.embeddings.position_ids`."""
+    W, F, S, H = arch.width, arch.mlp_dim, arch.span, arch.heads
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    f64 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float64)
+    for k in ("deberta.embeddings.position_embeddings.weight", "deberta.embeddings.token_type_embeddings.weight", "deberta.embeddings.embed_proj.weight",
+              "deberta.encoder.conv.conv.weight"):
+        if k in sd:
+            raise ValueError(f"'{k}' is present: the DeBERTa tower adds no position table, no type row, no embedding projection and no convolution")
+    out = {"word_embeddings.weight": f32("deberta.embeddings.word_embeddings.weight", (arch.vocab, W)),
+           "emb_ln.weight": f32("deberta.embeddings.LayerNorm.weight", (W,)), "emb_ln.bias": f32("deberta.embeddings.LayerNorm.bias", (W,))}
+    rel = torch.nn.functional.layer_norm(f64("deberta.encoder.rel_embeddings.weight", (2 * S, W)), (W,), f64("deberta.encoder.LayerNorm.weight", (W,)),
+                                         f64("deberta.encoder.LayerNorm.bias", (W,)), arch.ln_eps)
+    names = ("key_proj", "query_proj") if arch.share_att_key else ("pos_key_proj", "pos_query_proj")
+    for l in range(arch.layers):
+        src, p = f"deberta.encoder.layer.{l}.", f"layer.{l}."
+        att = src + "attention.self."
+        out[p + "attn.qkv.weight"] = torch.cat([f32(att + f"{c}.weight", (W, W)) for c in ("query_proj", "key_proj", "value_proj")], 0)
+        out[p + "attn.qkv.bias"] = torch.cat([f32(att + f"{c}.bias", (W,)) for c in ("query_proj", "key_proj", "value_proj")], 0)
+        for dst, name in zip(("pos_key", "pos_query"), names):
+            t = rel @ f64(att + name + ".weight", (W, W)).T + f64(att + name + ".bias", (W,))
+            out[p + dst] = t.reshape(2 * S, H, W // H).transpose(0, 1).to(torch.float32).contiguous()
+        out[p + "attn.o.weight"] = f32(src + "attention.output.dense.weight", (W, W))
+        out[p + "attn.o.bias"] = f32(src + "attention.output.dense.bias", (W,))
+        out[p + "attn_ln.weight"] = f32(src + "attention.output.LayerNorm.weight", (W,))
+        out[p + "attn_ln.bias"] = f32(src + "attention.output.LayerNorm.bias", (W,))
+        out[p + "mlp.fc1.weight"] = f32(src + "intermediate.dense.weight", (F, W))
+        out[p + "mlp.fc1.bias"] = f32(src + "intermediate.dense.bias", (F,))
+        out[p + "mlp.fc2.weight"] = f32(src + "output.dense.weight", (W, F))
+        out[p + "mlp.fc2.bias"] = f32(src + "output.dense.bias", (W,))
+        out[p + "mlp_ln.weight"] = f32(src + "output.LayerNorm.weight", (W,))
+        out[p + "mlp_ln.bias"] = f32(src + "output.LayerNorm.bias", (W,))
+    out["pooler.weight"], out["pooler.bias"] = f32("pooler.dense.weight", (W, W)), f32("pooler.dense.bias", (W,))
+    out["classifier.weight"], out["classifier.bias"] = f32("classifier.weight", (1, W)), f32("classifier.bias", (1,))
+    return out

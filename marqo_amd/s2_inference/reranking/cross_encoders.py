@@ -45,8 +45,8 @@ class EngineCrossEncoder:
     """predict() of sentence-transformers' CrossEncoder on the engine: [[query, passage], ...] -> sigmoid(logit) fp32 [n]"""
 
     def __init__(self, directory: str, device: str, max_length: int = 512):
-        from marqo_amd.engine.rerank import CrossEncoderTower
-        self.tower = CrossEncoderTower.from_dir(directory, device)
+        from marqo_amd.engine.rerank import load_cross_encoder_tower
+        self.tower = load_cross_encoder_tower(directory, device)     # (by the directory's model_type: BERT-family towers or the DeBERTa tower)
         # (model_utils.py:266-270: a max_length above the tokenizer's model_max_length is lowered to it)
         self.max_length = min(int(max_length), self.tower.model_max_length)
         self.weights_source = directory
@@ -179,7 +179,7 @@ class ReRanker:
 
 
 class ReRankerText(ReRanker):
-    """reranking with a Hugging Face cross-encoder (BertForSequenceClassification / XLMRobertaForSequenceClassification with one logit)"""
+    """reranking with a Hugging Face cross-encoder (Bert / XLMRoberta / Roberta / ModernBert / DebertaV2 ForSequenceClassification with one logit)"""
 
     def __init__(self, model_name: str, device: str, max_length: int = 512, num_highlights: int = 1,
                  split_params: Optional[Dict] = get_default_text_processing_parameters()):
