@@ -1620,6 +1620,64 @@ int mq_score_pairs_deberta(const mq_deberta_cfg* cfg, const mq_deberta_weights* 
                            const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, float* d_logits, float* d_scores, float* d_pooled,
                            void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- NomicBERT text embedders: sliced full attention and the tower (csrc/attention_full.hip, csrc/nomic_bert.hip; engine/nomic_bert.py) ----------------
+ * nomic-embed-text-v1 / -v1.5 / -v1-unsupervised, their fine-tunes and snowflake-arctic-embed-m-long (config.json: model_type "nomic_bert"): post-LN
+ * blocks with biased LayerNorms, bias-free Linears, a gated-SiLU MLP, full-width rotate-half rotary positions, a token-type row, no position table, plain
+ * bidirectional softmax attention over up to 8192 tokens.  The block semantics are pinned to transformers' NomicBertModel in float64.
+ * Additions to ABI 15: nothing above changes; the structs and entry points below are new.  Every entry point judges its arguments before any launch
+ * (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_full: d_qkv bf16 [rows, 3 inner] = (q | k | v), inner = heads head_dim, head h at columns h head_dim .. of each third; d_out bf16
+ *                   [rows, inner]; head_dim 64; sequences packed or fixed-length as mq_attention, max_len <= 8192.  Unmasked, bidirectional, every key
+ *                   of the sequence contributes: out = softmax(scale (q . k)) V, scale > 0 the caller's.  The function mq_attention computes at
+ *                   MQ_MASK_NONE, with the work split over (sequence, head, 64-query slice) instead of (sequence, head): one workgroup of 4 waves per
+ *                   slice, the K / V image has the whole LDS (640 keys; longer sequences stream through in pieces).  Compiler report (gfx950):
+ *                   csrc/attention_full.hip's header.
+ *   mq_encode_nomic_bert: token gather + type row 0 + LayerNorm -> `layers` blocks  x = LN(Wo(attn(rope(Wqkv(x)))) + x) ; x = LN(Wdown(up * silu(gate)) + x)
+ *                   with (up | gate) = Wug(x)  -> mq_pool (MQ_POOL_MEAN or MQ_POOL_CLS) (+ L2), on packed sequences like mq_encode_bert; fp32 residual
+ *                   stream, bf16 GEMM operands; softmax scale 1 / sqrt(head_dim); rotary angle = position in the sequence * d_inv_freq[i], rotate_half
+ *                   form over the whole head (mq_rope).  width a multiple of 64, <= 2048; head_dim 64; heads * 64 == width; mlp_dim % 64 == 0;
+ *                   max_pos <= 8192.  d_out fp32 [nseq, width]. */
+typedef struct mq_nomic_bert_layer {
+    const void*  qkv_w;         /* bf16 [3 W, W]  rows: q | k | v, no bias */
+    const void*  out_w;         /* bf16 [W, W]  self_attn.o_proj, no bias */
+    const float* attn_ln_g;     /* fp32 [W]  post_attention_layernorm */
+    const float* attn_ln_b;
+    const void*  ug_w;          /* bf16 [2F, W]  rows: up_proj | gate_proj (mq_glu's order), no bias */
+    const void*  down_w;        /* bf16 [W, F]  mlp.down_proj, no bias */
+    const float* mlp_ln_g;      /* fp32 [W]  post_mlp_layernorm */
+    const float* mlp_ln_b;
+} mq_nomic_bert_layer;
+
+typedef struct mq_nomic_bert_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  embeddings.word_embeddings */
+    const float* type0;         /* fp32 [W]  row 0 of embeddings.token_type_embeddings */
+    const float* emb_ln_g;      /* fp32 [W]  embeddings.LayerNorm */
+    const float* emb_ln_b;
+    const float* zeros;         /* fp32 [W] of 0: the bias operand of the residual epilogues (no Linear has a bias) */
+    const float* d_inv_freq;    /* fp32 [32]: rope_theta ^ -(2 i / 64) */
+    const mq_nomic_bert_layer* layers;  /* host array, `layers` entries */
+} mq_nomic_bert_weights;
+
+typedef struct mq_nomic_bert_cfg {
+    int32_t width;         /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t heads;         /* heads * 64 == W */
+    int32_t head_dim;      /* 64 */
+    int32_t mlp_dim;       /* F = intermediate_size, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;       /* longest sequence served (<= 8192) */
+    int32_t pool;          /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    float   ln_eps;        /* layer_norm_eps */
+    int32_t reserved;
+} mq_nomic_bert_cfg;
+
+int mq_attention_full(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len, int32_t heads,
+                      int32_t head_dim, float scale, void* stream);
+size_t mq_nomic_bert_workspace_bytes(const mq_nomic_bert_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_nomic_bert(const mq_nomic_bert_cfg* cfg, const mq_nomic_bert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                         const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

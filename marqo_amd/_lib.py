@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attention_disentangled", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -289,6 +289,21 @@ class DebertaCfg(C.Structure):
                 ("max_pos", C.c_int32), ("pool", C.c_int32), ("span", C.c_int32), ("reach", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+class NomicBertLayer(C.Structure):
+    """mq_nomic_bert_layer: one NomicBERT block (csrc/nomic_bert.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "out_w", "attn_ln_g", "attn_ln_b", "ug_w", "down_w", "mlp_ln_g", "mlp_ln_b")]
+
+
+class NomicBertWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("type0", C.c_void_p), ("emb_ln_g", C.c_void_p), ("emb_ln_b", C.c_void_p), ("zeros", C.c_void_p),
+                ("d_inv_freq", C.c_void_p), ("layers", C.POINTER(NomicBertLayer))]
+
+
+class NomicBertCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32), ("vocab", C.c_int32),
+                ("max_pos", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -479,6 +494,10 @@ _SIGNATURES = {
     "mq_score_pairs_deberta_workspace_bytes": (C.c_size_t, [C.POINTER(DebertaCfg), C.c_int64, C.c_int64]),
     "mq_score_pairs_deberta": (C.c_int, [C.POINTER(DebertaCfg), C.POINTER(DebertaWeights), C.POINTER(ScoreHeadWeights), _P, _P, _P, C.c_int64,
                                          _P, _P, _P, _P, C.c_size_t, _P]),
+    # NomicBERT text embedders: sliced full attention and the tower (csrc/attention_full.hip, csrc/nomic_bert.hip; engine/nomic_bert.py)
+    "mq_attention_full": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_nomic_bert_workspace_bytes": (C.c_size_t, [C.POINTER(NomicBertCfg), C.c_int64, C.c_int64]),
+    "mq_encode_nomic_bert": (C.c_int, [C.POINTER(NomicBertCfg), C.POINTER(NomicBertWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

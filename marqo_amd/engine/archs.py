@@ -714,6 +714,109 @@ def deberta_arch_from_hf_config(cfg: dict) -> DebertaArch:
 
 
 @dataclass(frozen=True)
+class NomicBertArch:
+    """NomicBERT (nomic-embed-text-v1 / -v1.5 / -v1-unsupervised, their fine-tunes, snowflake-arctic-embed-m-long; transformers NomicBertModel,
+    model_type "nomic_bert") as the engine runs it: post-LN blocks with biased LayerNorms, bias-free Linears, a gated-SiLU MLP, full-width rotate-half
+    rotary positions, a token-type row, no position table, plain bidirectional attention."""
+    vocab: int = 30528
+    max_pos: int = 8192                   # no position table: min(max_position_embeddings, what the attention kernel serves)
+    width: int = 768
+    layers: int = 12
+    heads: int = 12
+    head_dim: int = 64
+    mlp_dim: int = 3072
+    ln_eps: float = 1e-12
+    type_vocab: int = 2
+    rope_theta: float = 1000.0
+
+    def inv_freq(self):
+        """[head_dim / 2] inverse frequencies as NomicBertRotaryEmbedding.compute_default_rope_parameters builds them: theta^-(2i/d), in the plain
+        order mq_rope reads (dims i and i + head_dim / 2 share entry i)"""
+        import torch
+        d = self.head_dim
+        return 1.0 / (self.rope_theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F = tokens, self.width, self.mlp_dim
+        return self.layers * (2 * T * W * 3 * W + 2 * T * W * W + 4 * T * T * W + 2 * 3 * T * W * F) / 1e9
+
+
+# the hub's original NomicBERT config.json is GPT-2-style: its key -> transformers' key
+_NOMIC_HUB_ALIASES = {"n_embd": "hidden_size", "n_head": "num_attention_heads", "n_layer": "num_hidden_layers", "n_inner": "intermediate_size",
+                      "n_positions": "max_position_embeddings", "layer_norm_epsilon": "layer_norm_eps"}
+
+
+def nomic_bert_arch_from_hf_config(cfg: dict) -> NomicBertArch:
+    """A local NomicBERT `config.json` (model_type "nomic_bert") -> NomicBertArch, in either of two dialects.
+
+    transformers' own keys (NomicBertConfig): hidden_size, num_hidden_layers, num_attention_heads, intermediate_size, hidden_act, max_position_embeddings,
+    type_vocab_size, layer_norm_eps, rope_parameters {rope_theta, rope_type}, head_dim.  Refused, each by the name of its key: a hidden_act other than
+    silu, a rope_parameters.rope_type other than default (dynamic / NTK scaling), a head_dim other than 64 or heads that are not 64 wide, a hidden_size
+    above 2048, an intermediate_size that is no multiple of 64.  max_position_embeddings above 8192 is clamped to 8192.
+
+    The hub's original GPT-2-style keys, taken when `hidden_size` is absent and `n_embd` is there — UNVERIFIED against a real hub file: the table is
+    written from memory of the published checkpoints' config.json, no such file was at hand: n_embd, n_head, n_layer, n_inner (null: 4 n_embd),
+    n_positions, layer_norm_epsilon, rotary_emb_base, rotary_emb_fraction, rotary_emb_interleaved, rotary_scaling_factor, activation_function,
+    qkv_proj_bias, mlp_fc1_bias, mlp_fc2_bias, prenorm, use_rms_norm.  Refused by name: a bias set true, prenorm, use_rms_norm, rotary_emb_fraction
+    other than 1, rotary_emb_interleaved, a non-null rotary_scaling_factor, an activation_function other than swiglu.  In both dialects the
+    mixture-of-experts keys of nomic-embed-text-v2-moe (moe_every_n_layers > 0, num_experts > 1) are refused."""
+    mtype = cfg.get("model_type")
+    if mtype != "nomic_bert":
+        raise KeyError(f"model_type={mtype} is not a NomicBERT model")
+    if int(cfg.get("moe_every_n_layers") or 0) > 0:
+        raise KeyError(f"moe_every_n_layers={cfg['moe_every_n_layers']} unsupported (mixture-of-experts NomicBERT, nomic-embed-text-v2-moe, is not served)")
+    if int(cfg.get("num_experts") or 0) > 1:
+        raise KeyError(f"num_experts={cfg['num_experts']} unsupported (mixture-of-experts NomicBERT, nomic-embed-text-v2-moe, is not served)")
+    theta = 1000.0
+    if "hidden_size" not in cfg and "n_embd" in cfg:
+        for k in ("qkv_proj_bias", "mlp_fc1_bias", "mlp_fc2_bias"):
+            if cfg.get(k, False):
+                raise KeyError(f"{k}={cfg[k]} unsupported (the served block's Linears have no bias)")
+        if cfg.get("prenorm", False):
+            raise KeyError(f"prenorm={cfg['prenorm']} unsupported (post-LN blocks only)")
+        if cfg.get("use_rms_norm", False):
+            raise KeyError(f"use_rms_norm={cfg['use_rms_norm']} unsupported (LayerNorm only)")
+        if float(cfg.get("rotary_emb_fraction", 1.0)) != 1.0:
+            raise KeyError(f"rotary_emb_fraction={cfg['rotary_emb_fraction']} unsupported (the whole head is rotated)")
+        if cfg.get("rotary_emb_interleaved", False):
+            raise KeyError(f"rotary_emb_interleaved={cfg['rotary_emb_interleaved']} unsupported (rotate_half pairs only)")
+        if cfg.get("rotary_scaling_factor") is not None:
+            raise KeyError(f"rotary_scaling_factor={cfg['rotary_scaling_factor']} unsupported (dynamic NTK rope scaling is not served)")
+        act = cfg.get("activation_function", "swiglu")
+        if act != "swiglu":
+            raise KeyError(f"activation_function={act} unsupported (swiglu only)")
+        theta = float(cfg.get("rotary_emb_base", 1000.0))
+        hub = cfg
+        cfg = {k: v for k, v in hub.items() if k not in _NOMIC_HUB_ALIASES}
+        cfg.update({new: hub[old] for old, new in _NOMIC_HUB_ALIASES.items() if hub.get(old) is not None})
+        cfg.setdefault("intermediate_size", 4 * int(hub["n_embd"]))
+        cfg["hidden_act"] = "silu"
+    else:
+        if cfg.get("hidden_act", "silu") != "silu":
+            raise KeyError(f"hidden_act={cfg.get('hidden_act')} unsupported (silu only)")
+        rp = cfg.get("rope_parameters") or {}
+        rtype = rp.get("rope_type", rp.get("type", "default"))
+        if rtype != "default":
+            raise KeyError(f"rope_parameters.rope_type={rtype} unsupported (default only: dynamic / NTK rope scaling is not served)")
+        theta = float(rp.get("rope_theta", cfg.get("rope_theta", 1000.0)))
+    W, heads, F = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["intermediate_size"])
+    hd = cfg.get("head_dim")
+    if hd is not None and int(hd) != 64:
+        raise KeyError(f"head_dim={hd} unsupported (64 only)")
+    if heads < 1 or W != heads * 64:
+        raise KeyError(f"hidden_size={W} / num_attention_heads={heads} unsupported (64-wide heads only)")
+    if W > 2048:
+        raise KeyError(f"hidden_size={W} unsupported (at most 2048)")
+    if F % 64 or F < 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    if not theta > 0:
+        raise KeyError(f"rope_theta={theta} must be positive")
+    return NomicBertArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 2048)), 8192), width=W,
+                         layers=int(cfg["num_hidden_layers"]), heads=heads, mlp_dim=F, ln_eps=float(cfg.get("layer_norm_eps", 1e-12)),
+                         type_vocab=int(cfg.get("type_vocab_size", 2)), rope_theta=theta)
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -985,15 +1088,17 @@ STELLA_EN_400M = BertArch(vocab=30528, max_pos=8192, width=1024, layers=24, head
 HF_BERT_ARCHS["Marqo/dunzhang-stella_en_400M_v5"] = STELLA_EN_400M
 
 
-def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch, T5Arch, JinaBertArch]:
+def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenArch, GemmaArch, T5Arch, JinaBertArch, NomicBertArch]:
     """A local HF `config.json` -> the arch of the text encoder the `hf` loader builds.  model_type bert, or xlm-roberta / roberta (the same encoder
     with the position ids shifted by padding_idx + 1: the multilingual-e5 family), mpnet and `new` give a BertArch (engine/towers.py::BertTower);
     model_type modernbert gives a ModernBertArch (engine/modernbert.py::ModernBertTower) — callers that can only run a BertArch (the cross-encoders of
     engine/rerank.py, which select their model types before they call) must not pass one through; model_type qwen3 / qwen2 gives a QwenArch
     (engine/qwen.py::QwenTower), model_type gemma3_text a GemmaArch (engine/gemma.py::GemmaTower) and model_type t5 a T5Arch (engine/t5.py::T5Tower) under
-    the same rule; so does model_type bert with position_embedding_type alibi, a JinaBertArch (engine/jina_bert.py::JinaBertTower).  Anything else:
-    KeyError."""
+    the same rule; so do model_type bert with position_embedding_type alibi, a JinaBertArch (engine/jina_bert.py::JinaBertTower), and model_type
+    nomic_bert, a NomicBertArch (engine/nomic_bert.py::NomicBertTower).  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
+    if mtype == "nomic_bert":   # transformers NomicBertModel: nomic-embed-text-v1 / -v1.5, arctic-embed-m-long (engine/nomic_bert.py::NomicBertTower)
+        return nomic_bert_arch_from_hf_config(cfg)
     if mtype == "t5":   # transformers T5EncoderModel: sentence-t5, gtr-t5, flan-t5 encoders (engine/t5.py::T5Tower)
         return t5_arch_from_hf_config(cfg)
     if mtype == "gemma3_text":   # transformers Gemma3TextModel with bidirectional attention: EmbeddingGemma (engine/gemma.py::GemmaTower)

@@ -248,6 +248,8 @@ class CrossEncoderTower(_PairScorer, BertTower):
                                          f"a cross-encoder: {why}")
                 else:
                     raise ValueError(f"{directory}: model_type={mtype!r} needs the checkpoint's sentencepiece.bpe.model, which is not there")
+        elif mtype == "nomic_bert":
+            raise ValueError(f"{directory}: model_type='nomic_bert' (NomicBERT) is not served as a cross-encoder")
         else:
             raise ValueError(f"{directory}: model_type={mtype!r} is not served as a cross-encoder (only 'bert', 'xlm-roberta' and 'roberta')")
         labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)

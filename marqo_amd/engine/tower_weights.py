@@ -612,3 +612,54 @@ def deberta_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     out["pooler.weight"], out["pooler.bias"] = f32("pooler.dense.weight", (W, W)), f32("pooler.dense.bias", (W,))
     out["classifier.weight"], out["classifier.bias"] = f32("classifier.weight", (1, W)), f32("classifier.bias", (1,))
     return out
+
+
+def nomic_bert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """NomicBERT tensors -> the fp32 tensors the tower hands to the kernels, from either naming (the correspondence is the "nomic_bert" entry of
+    transformers' conversion_mapping.py):
+
+      transformers' NomicBertModel            the hub's original checkpoints
+      embeddings.LayerNorm                    emb_ln
+      layers.l.self_attn.{q,k,v}_proj         encoder.layers.l.attn.Wqkv        [3 W, W], chunked along dim 0 into q, k, v
+      layers.l.self_attn.o_proj               encoder.layers.l.attn.out_proj
+      layers.l.mlp.up_proj / gate_proj        encoder.layers.l.mlp.fc11 / fc12
+      layers.l.mlp.down_proj                  encoder.layers.l.mlp.fc2
+      layers.l.post_attention_layernorm       encoder.layers.l.norm1
+      layers.l.post_mlp_layernorm             encoder.layers.l.norm2
+
+    (either with the task-head classes' `nomic_bert.` / `bert.` prefix).  Per block l: `layer.l.attn.qkv.weight` [3 W, W] = rows q | k | v;
+    `layer.l.mlp.up_gate.weight` [2F, W] = rows up | gate, as mq_glu reads them (the module computes down(silu(gate(x)) * up(x))).  `type0` is row 0 of the
+    token-type table.  Ignored: pooler, MLM-head and classifier tensors (`pooler.*`, `cls.*`, `classifier.*`), `embeddings.position_ids`, rotary
+    `inv_freq` buffers.  Refused by name: a missing or mis-shaped tensor, and a bias on any Linear (the served block has none)."""
+    for prefix in ("nomic_bert.", "bert."):
+        if "embeddings.word_embeddings.weight" not in sd and prefix + "embeddings.word_embeddings.weight" in sd:
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    hub = any(k.startswith("encoder.layers.") for k in sd) or "emb_ln.weight" in sd
+    W, F = arch.width, arch.mlp_dim
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    emb_ln = "emb_ln" if hub else "embeddings.LayerNorm"
+    out = {"word_embeddings.weight": f32("embeddings.word_embeddings.weight", (arch.vocab, W)),
+           "type0": f32("embeddings.token_type_embeddings.weight", (arch.type_vocab, W))[0].contiguous(),
+           "emb_ln.weight": f32(emb_ln + ".weight", (W,)), "emb_ln.bias": f32(emb_ln + ".bias", (W,))}
+    for l in range(arch.layers):
+        p = f"layer.{l}."
+        if hub:
+            src = f"encoder.layers.{l}."
+            linears = dict(qkv=src + "attn.Wqkv", o=src + "attn.out_proj", up=src + "mlp.fc11", gate=src + "mlp.fc12", down=src + "mlp.fc2")
+            ln1, ln2 = src + "norm1", src + "norm2"
+            out[p + "attn.qkv.weight"] = f32(linears["qkv"] + ".weight", (3 * W, W)).contiguous()
+        else:
+            src = f"layers.{l}."
+            linears = dict(q=src + "self_attn.q_proj", k=src + "self_attn.k_proj", v=src + "self_attn.v_proj", o=src + "self_attn.o_proj",
+                           up=src + "mlp.up_proj", gate=src + "mlp.gate_proj", down=src + "mlp.down_proj")
+            ln1, ln2 = src + "post_attention_layernorm", src + "post_mlp_layernorm"
+            out[p + "attn.qkv.weight"] = torch.cat([f32(linears[c] + ".weight", (W, W)) for c in ("q", "k", "v")], 0)
+        for name in linears.values():
+            if name + ".bias" in sd:
+                raise ValueError(f"checkpoint tensor '{name}.bias' is unexpected: the NomicBERT block that is served has no bias on its Linears")
+        out[p + "attn.o.weight"] = f32(linears["o"] + ".weight", (W, W))
+        out[p + "attn_ln.weight"], out[p + "attn_ln.bias"] = f32(ln1 + ".weight", (W,)), f32(ln1 + ".bias", (W,))
+        out[p + "mlp.up_gate.weight"] = torch.cat([f32(linears["up"] + ".weight", (F, W)), f32(linears["gate"] + ".weight", (F, W))], 0)
+        out[p + "mlp.down.weight"] = f32(linears["down"] + ".weight", (W, F))
+        out[p + "mlp_ln.weight"], out[p + "mlp_ln.bias"] = f32(ln2 + ".weight", (W,)), f32(ln2 + ".bias", (W,))
+    return out

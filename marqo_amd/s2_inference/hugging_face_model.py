@@ -136,6 +136,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             if isinstance(arch, archs.JinaBertArch):
                 self._load_jina_bert(directory, arch, sd)
                 return
+            if isinstance(arch, archs.NomicBertArch):
+                self._load_nomic_bert(directory, arch, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -217,7 +220,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             raise InvalidModelPropertiesError(f"Invalid model properties: {self.model_properties.dict()}. Original error "
                                               f"{HuggingFaceModelProperties.POOLING_ERROR}")
 
-    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma, T5, JinaBERT) share ------------------------------------------------
+    # ---- what the loaders of the packed-token families (ModernBERT, Qwen, Gemma, T5, JinaBERT, NomicBERT) share -------------------------------------
     def _refuse_fp8(self, family: str) -> None:
         props = self.model_properties
         if props.engine_precision == "fp8":
@@ -322,6 +325,20 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         self._refuse_fp8("JinaBERT encoders (their ALiBi attention / gated-GELU blocks run on bf16 operands only)")
         self._check_width(arch.width)
         self._finish_packed(directory, arch, arch.max_pos, JinaBertTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="[PAD]"))
+
+    def _load_nomic_bert(self, directory: str, arch, sd) -> None:
+        """a NomicBERT checkpoint (model_type "nomic_bert": nomic-embed-text-v1 / -v1.5 / -v1-unsupervised, snowflake-arctic-embed-m-long and their
+        fine-tunes, in transformers' tensor names or the hub's original ones; native in transformers, so trustRemoteCode is not required — it is accepted
+        and ignored): host tokenisation by the `tokenizers` library from the directory's tokenizer.json with the file's own post-processor
+        ([CLS] ... [SEP]), right-padded with [PAD], truncated at min(tokens, max_position_embeddings, 8192); the tower of engine/nomic_bert.py.  Pooling:
+        the property, else 1_Pooling/config.json, else mean.  The search_query: / search_document: prefixes are the caller's text_query_prefix /
+        text_chunk_prefix; v1.5's Matryoshka truncation is not applied (the full vector is returned).  bf16 operands only; no GPU tokeniser and no
+        native request queue for this family."""
+        from marqo_amd.engine.nomic_bert import NomicBertTower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        self._refuse_fp8("NomicBERT encoders (their rotary / gated-SiLU blocks run on bf16 operands only)")
+        self._check_width(arch.width)
+        self._finish_packed(directory, arch, arch.max_pos, NomicBertTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="[PAD]"))
 
     def _load_gemma(self, directory: str, arch, sd) -> None:
         """a transformers Gemma3TextModel checkpoint with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its
