@@ -1678,6 +1678,109 @@ size_t mq_nomic_bert_workspace_bytes(const mq_nomic_bert_cfg* cfg, int64_t rows,
 int mq_encode_nomic_bert(const mq_nomic_bert_cfg* cfg, const mq_nomic_bert_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                          const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Jina v3 text embedders: per-sequence task LoRA adapters and the tower (csrc/lora.hip, csrc/jina_v3.hip; engine/jina_v3.py) -----------------------
+ * jina-embeddings-v3 (config.json: model_type "jina_embeddings_v3", transformers' JinaEmbeddingsV3Model): the NomicBERT block with biases on all four
+ * Linears and a plain fc1 -> erf-GELU -> fc2 MLP, plus one low-rank adapter per task on every Linear and on the token table.  Adapters are NOT merged into
+ * the weights: the base GEMM runs once for all rows and a row of sequence s with task t = task[s] gets  y += scale_t (x A_t^T) B_t^T  on top, so one batch
+ * may hold sequences of different tasks and sequences without adapter (task[s] < 0: the row's delta is not computed, its bits are what the base model
+ * leaves).  Additions to ABI 15: nothing above changes; the structs and entry points below are new.  Every entry point judges its arguments before any
+ * launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ * The sequence arguments of the three LoRA entry points: d_seq_task int32 [nseq] on the device and h_seq_task, its host copy (the host copy is judged — an
+ * id >= tasks is refused — and decides whether anything is launched; the kernels read the device copy and treat ids outside [0, tasks) as "no adapter");
+ * sequences packed (d_cu_seqlens int32 [nseq + 1], cu[0] == 0, cu[nseq] == rows) or fixed_len > 0 rows each (rows == nseq fixed_len, d_cu_seqlens NULL ok).
+ *
+ *   mq_lora_down:   d_T fp32 [rows, R] = scale_t (x A_t^T): d_x bf16 [rows, K] with leading dimension lda, d_A bf16 [tasks][R][K], d_scale fp32 [tasks].
+ *                   R a multiple of 4 in [4, 64] (a rank that is none is padded with zero rows at load), K % 64 == 0, lda % 8 == 0.  Rows without adapter
+ *                   get T = 0.  When NO sequence has an adapter nothing is launched and d_T is not written.
+ *   mq_lora_up:     delta[m, n] = sum_j T[m, (n / (N / nblocks)) r + j] B_t[n, j]: d_T fp32 [rows, R], R = nblocks r; d_B bf16 [tasks][N][r]; r in
+ *                   {4, 8, 12, 16}; N % 4 == 0, N % nblocks == 0, (N / nblocks) % 4 == 0 (q | k | v stacked: nblocks = 3); ldc % 4 == 0.  mode:
+ *                   MQ_LORA_ACCUM d_out fp32 [rows, ldc] += delta ; MQ_LORA_WRITE d_out fp32 = delta (0 for rows without adapter) ; MQ_LORA_INPLACE d_out
+ *                   bf16 [rows, ldc] = act(d_out + delta) with act 0 or MQ_ACT_GELU (the erf GELU of MQ_EPI_GELU).  Rows without adapter: not touched
+ *                   (ACCUM; INPLACE with act 0), act(d_out) (INPLACE with MQ_ACT_GELU).  When no sequence has an adapter only MQ_LORA_WRITE and the GELU
+ *                   form launch.
+ *   mq_lora_gather: d_T fp32 [rows, r] = scale_t A_emb_t[id[m], :]: d_ids int32 [rows], d_A_emb fp32 [tasks][vocab][r] (PEFT's lora_embedding_A,
+ *                   transposed).  The embedding adapter's up half is mq_lora_up in MQ_LORA_ACCUM (B_emb in bf16).
+ *   mq_encode_jina_v3: token gather + type row 0 (+ embedding adapter) -> LayerNorm -> `layers` blocks  x = LN(Wo(attn(rope(Wqkv(x)))) + x) ;
+ *                   x = LN(W2(gelu(W1(x))) + x), every Linear with its bias and, with `lora`, its per-row correction -> mq_pool (MQ_POOL_MEAN or
+ *                   MQ_POOL_CLS) (+ L2), on packed sequences like mq_encode_nomic_bert.  lora NULL: the base model, d_seq_task / h_seq_task are not read
+ *                   and no LoRA kernel is launched.  lora != NULL: the task lists are required; with every task negative only fc1's activation pass
+ *                   (mq_lora_up, MQ_LORA_INPLACE + MQ_ACT_GELU) is launched, so that a sequence without adapter gets the same bits in any batch.  Where
+ *                   the corrections sit: csrc/jina_v3.hip's header.  Limits: mq_encode_nomic_bert's.  Compiler report: csrc/lora.hip's header. */
+#define MQ_LORA_ACCUM 0
+#define MQ_LORA_WRITE 1
+#define MQ_LORA_INPLACE 2
+
+typedef struct mq_jina_v3_layer {
+    const void*  qkv_w;         /* bf16 [3 W, W]  rows: q | k | v */
+    const float* qkv_b;         /* fp32 [3 W] */
+    const void*  out_w;         /* bf16 [W, W]  self_attn.o_proj */
+    const float* out_b;         /* fp32 [W] */
+    const float* attn_ln_g;     /* fp32 [W]  post_attention_layernorm */
+    const float* attn_ln_b;
+    const void*  fc1_w;         /* bf16 [F, W]  mlp.fc1 */
+    const float* fc1_b;         /* fp32 [F] */
+    const void*  fc2_w;         /* bf16 [W, F]  mlp.fc2 */
+    const float* fc2_b;         /* fp32 [W] */
+    const float* mlp_ln_g;      /* fp32 [W]  post_mlp_layernorm */
+    const float* mlp_ln_b;
+} mq_jina_v3_layer;
+
+typedef struct mq_jina_v3_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  embeddings.word_embeddings */
+    const float* type0;         /* fp32 [W]  row 0 of embeddings.token_type_embeddings */
+    const float* emb_ln_g;      /* fp32 [W]  embeddings.LayerNorm */
+    const float* emb_ln_b;
+    const float* d_inv_freq;    /* fp32 [32]: rope_theta ^ -(2 i / 64) */
+    const mq_jina_v3_layer* layers;  /* host array, `layers` entries */
+} mq_jina_v3_weights;
+
+typedef struct mq_jina_v3_lora_layer {      /* every tensor [tasks] x ..., bf16; a Linear that a task does not adapt carries zeros for it */
+    const void* qkv_a;          /* [tasks][3 r][W]  rows: A_q | A_k | A_v */
+    const void* qkv_b;          /* [tasks][3 W][r]  rows: B_q | B_k | B_v */
+    const void* out_a;          /* [tasks][r][W] */
+    const void* out_b;          /* [tasks][W][r] */
+    const void* fc1_a;          /* [tasks][r][W] */
+    const void* fc1_b;          /* [tasks][F][r] */
+    const void* fc2_a;          /* [tasks][r][F] */
+    const void* fc2_b;          /* [tasks][W][r] */
+} mq_jina_v3_lora_layer;
+
+typedef struct mq_jina_v3_lora {
+    int32_t tasks;              /* adapters, 1 .. 1024 */
+    int32_t rank;               /* r: 4, 8, 12 or 16 (zero-padded at load) */
+    const float* d_scale;       /* fp32 [tasks]: lora_alpha / r, or lora_alpha / sqrt(r) (rsLoRA) */
+    const float* emb_a;         /* fp32 [tasks][vocab][r], or NULL with emb_b: no embedding adapter */
+    const void*  emb_b;         /* bf16 [tasks][W][r] */
+    const mq_jina_v3_lora_layer* layers;  /* host array, `layers` entries */
+} mq_jina_v3_lora;
+
+typedef struct mq_jina_v3_cfg {
+    int32_t width;         /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t heads;         /* heads * 64 == W */
+    int32_t head_dim;      /* 64 */
+    int32_t mlp_dim;       /* F = intermediate_size, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;       /* longest sequence served (<= 8192) */
+    int32_t pool;          /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    float   ln_eps;        /* layer_norm_eps */
+    int32_t reserved;
+} mq_jina_v3_cfg;
+
+int mq_lora_down(const void* d_x, int64_t lda, const void* d_A, const float* d_scale, const int32_t* d_seq_task, const int32_t* h_seq_task,
+                 const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int64_t rows, int32_t tasks, int32_t R, int32_t K, float* d_T, void* stream);
+int mq_lora_up(const float* d_T, int32_t R, const void* d_B, int32_t r, int32_t nblocks, const int32_t* d_seq_task, const int32_t* h_seq_task,
+               const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int64_t rows, int32_t tasks, void* d_out, int64_t ldc, int32_t N, int32_t mode,
+               int32_t act, void* stream);
+int mq_lora_gather(const int32_t* d_ids, const float* d_A_emb, const float* d_scale, const int32_t* d_seq_task, const int32_t* h_seq_task,
+                   const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int64_t rows, int32_t tasks, int32_t r, int32_t vocab, float* d_T,
+                   void* stream);
+size_t mq_jina_v3_workspace_bytes(const mq_jina_v3_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_jina_v3(const mq_jina_v3_cfg* cfg, const mq_jina_v3_weights* w, const mq_jina_v3_lora* lora, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                      const int32_t* h_cu_seqlens, const int32_t* d_seq_task, const int32_t* h_seq_task, int64_t nseq, float* d_out, int normalize,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -304,6 +304,35 @@ class NomicBertCfg(C.Structure):
                 ("max_pos", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+MQ_LORA_ACCUM, MQ_LORA_WRITE, MQ_LORA_INPLACE = 0, 1, 2
+
+
+class JinaV3Layer(C.Structure):
+    """mq_jina_v3_layer: one Jina v3 block (csrc/jina_v3.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "qkv_b", "out_w", "out_b", "attn_ln_g", "attn_ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "mlp_ln_g",
+                                          "mlp_ln_b")]
+
+
+class JinaV3Weights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("type0", C.c_void_p), ("emb_ln_g", C.c_void_p), ("emb_ln_b", C.c_void_p), ("d_inv_freq", C.c_void_p),
+                ("layers", C.POINTER(JinaV3Layer))]
+
+
+class JinaV3LoraLayer(C.Structure):
+    """mq_jina_v3_lora_layer: the stacked task adapters of one block's four Linears"""
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_a", "qkv_b", "out_a", "out_b", "fc1_a", "fc1_b", "fc2_a", "fc2_b")]
+
+
+class JinaV3Lora(C.Structure):
+    _fields_ = [("tasks", C.c_int32), ("rank", C.c_int32), ("d_scale", C.c_void_p), ("emb_a", C.c_void_p), ("emb_b", C.c_void_p),
+                ("layers", C.POINTER(JinaV3LoraLayer))]
+
+
+class JinaV3Cfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32), ("vocab", C.c_int32),
+                ("max_pos", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -498,6 +527,14 @@ _SIGNATURES = {
     "mq_attention_full": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     "mq_nomic_bert_workspace_bytes": (C.c_size_t, [C.POINTER(NomicBertCfg), C.c_int64, C.c_int64]),
     "mq_encode_nomic_bert": (C.c_int, [C.POINTER(NomicBertCfg), C.POINTER(NomicBertWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # Jina v3 text embedders: per-sequence task LoRA adapters and the tower (csrc/lora.hip, csrc/jina_v3.hip; engine/jina_v3.py)
+    "mq_lora_down": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mq_lora_up": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32,
+                             C.c_int32, C.c_int32, _P]),
+    "mq_lora_gather": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mq_jina_v3_workspace_bytes": (C.c_size_t, [C.POINTER(JinaV3Cfg), C.c_int64, C.c_int64]),
+    "mq_encode_jina_v3": (C.c_int, [C.POINTER(JinaV3Cfg), C.POINTER(JinaV3Weights), C.POINTER(JinaV3Lora), _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int, _P,
+                                    C.c_size_t, _P]),
     "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

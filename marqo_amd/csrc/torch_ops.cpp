@@ -210,6 +210,48 @@ at::Tensor l2_normalize(const at::Tensor& x) {
     return out;
 }
 
+// ---- per-sequence LoRA corrections (csrc/lora.hip) ----------------------------------------------------------------------------------
+// the sequence arguments the two ops share: seq_task int32 [nseq] on the device, its CPU copy, cu_seqlens int32 [nseq + 1] or fixed_len > 0
+const int32_t* check_lora_seqs(const at::Tensor& seq_task, const at::Tensor& seq_task_host, const c10::optional<at::Tensor>& cu_seqlens, int64_t fixed_len) {
+    need_dev(seq_task, at::kInt, "seq_task");
+    TORCH_CHECK(seq_task_host.device().is_cpu() && seq_task_host.scalar_type() == at::kInt && seq_task_host.is_contiguous() &&
+                seq_task_host.numel() == seq_task.numel(), "marqo_hip: seq_task_host must be the CPU int32 copy of seq_task");
+    if (!cu_seqlens.has_value()) {
+        TORCH_CHECK(fixed_len > 0, "marqo_hip: packed sequences need cu_seqlens (or give fixed_len > 0)");
+        return nullptr;
+    }
+    need_dev(*cu_seqlens, at::kInt, "cu_seqlens");
+    TORCH_CHECK(cu_seqlens->numel() == seq_task.numel() + 1, "cu_seqlens must be [nseq + 1]");
+    return (const int32_t*)cu_seqlens->data_ptr();
+}
+
+at::Tensor lora_down(const at::Tensor& x, const at::Tensor& A, const at::Tensor& scale, const at::Tensor& seq_task, const at::Tensor& seq_task_host,
+                     const c10::optional<at::Tensor>& cu_seqlens, int64_t fixed_len) {
+    need_dev(x, at::kBFloat16, "x");
+    need_dev(A, at::kBFloat16, "A");
+    need_dev(scale, at::kFloat, "scale");
+    TORCH_CHECK(x.dim() == 2 && A.dim() == 3 && A.size(2) == x.size(1) && scale.numel() == A.size(0), "marqo_hip::mq_lora_down: x [rows,K], A [tasks,R,K], scale [tasks]");
+    const int32_t* cu = check_lora_seqs(seq_task, seq_task_host, cu_seqlens, fixed_len);
+    at::Tensor T = at::zeros({x.size(0), A.size(1)}, x.options().dtype(at::kFloat));     // (zeros: with no adapter in the batch the kernel is not launched)
+    check_rc(mq_lora_down(x.data_ptr(), x.size(1), A.data_ptr(), (const float*)scale.data_ptr(), (const int32_t*)seq_task.data_ptr(),
+                          (const int32_t*)seq_task_host.data_ptr(), cu, seq_task.numel(), (int32_t)fixed_len, x.size(0), (int32_t)A.size(0),
+                          (int32_t)A.size(1), (int32_t)x.size(1), (float*)T.data_ptr(), stream_of(x)), "mq_lora_down");
+    return T;
+}
+
+void lora_up(const at::Tensor& T, const at::Tensor& B, int64_t nblocks, const at::Tensor& seq_task, const at::Tensor& seq_task_host,
+             const c10::optional<at::Tensor>& cu_seqlens, int64_t fixed_len, at::Tensor out, int64_t mode, int64_t act) {
+    need_dev(T, at::kFloat, "T");
+    need_dev(B, at::kBFloat16, "B");
+    need_dev(out, mode == MQ_LORA_INPLACE ? at::kBFloat16 : at::kFloat, "out");
+    TORCH_CHECK(T.dim() == 2 && B.dim() == 3 && out.dim() == 2 && out.size(0) == T.size(0) && out.size(1) >= B.size(1),
+                "marqo_hip::mq_lora_up: T [rows,R], B [tasks,N,r], out [rows, ldc >= N]");
+    const int32_t* cu = check_lora_seqs(seq_task, seq_task_host, cu_seqlens, fixed_len);
+    check_rc(mq_lora_up((const float*)T.data_ptr(), (int32_t)T.size(1), B.data_ptr(), (int32_t)B.size(2), (int32_t)nblocks, (const int32_t*)seq_task.data_ptr(),
+                        (const int32_t*)seq_task_host.data_ptr(), cu, seq_task.numel(), (int32_t)fixed_len, T.size(0), (int32_t)B.size(0), out.data_ptr(),
+                        out.size(1), (int32_t)B.size(1), (int32_t)mode, (int32_t)act, stream_of(T)), "mq_lora_up");
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -227,6 +269,9 @@ TORCH_LIBRARY(marqo_hip, m) {
     m.def("layernorm(Tensor x, Tensor gamma, Tensor beta, float eps, bool out_bf16) -> Tensor");
     m.def("attention(Tensor qkv, Tensor? cu_seqlens, int nseq, int fixed_len, int max_len, int heads, int mask) -> Tensor");
     m.def("l2_normalize(Tensor x) -> Tensor");
+    m.def("mq_lora_down(Tensor x, Tensor A, Tensor scale, Tensor seq_task, Tensor seq_task_host, Tensor? cu_seqlens, int fixed_len) -> Tensor");
+    m.def("mq_lora_up(Tensor T, Tensor B, int nblocks, Tensor seq_task, Tensor seq_task_host, Tensor? cu_seqlens, int fixed_len, Tensor(a!) out, "
+          "int mode, int act) -> ()");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -241,4 +286,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("layernorm", &layernorm);
     m.impl("attention", &attention);
     m.impl("l2_normalize", &l2_normalize);
+    m.impl("mq_lora_down", &lora_down);
+    m.impl("mq_lora_up", &lora_up);
 }

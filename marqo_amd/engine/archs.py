@@ -817,6 +817,65 @@ def nomic_bert_arch_from_hf_config(cfg: dict) -> NomicBertArch:
 
 
 @dataclass(frozen=True)
+class JinaV3Arch:
+    """jina-embeddings-v3 (transformers JinaEmbeddingsV3Model, model_type "jina_embeddings_v3") as the engine runs it: the NomicBERT block with biases on
+    its four Linears and a plain fc1 -> erf-GELU -> fc2 MLP; post-LN, full-width rotate-half rotary positions, row 0 of the token-type table, no position
+    table, plain bidirectional attention.  The task adapters are not part of the arch (engine/jina_v3.py::load_adapters)."""
+    vocab: int = 250002
+    max_pos: int = 8192                   # no position table: min(max_position_embeddings - 2, what the attention kernel serves)
+    width: int = 1024
+    layers: int = 24
+    heads: int = 16
+    head_dim: int = 64
+    mlp_dim: int = 4096
+    ln_eps: float = 1e-5
+    type_vocab: int = 1
+    rope_theta: float = 20000.0
+
+    def inv_freq(self):
+        """[head_dim / 2] inverse frequencies of the default rope parameters: theta^-(2i/d), in the plain order mq_rope reads"""
+        import torch
+        d = self.head_dim
+        return 1.0 / (self.rope_theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F = tokens, self.width, self.mlp_dim
+        return self.layers * (2 * T * W * 3 * W + 2 * T * W * W + 4 * T * T * W + 2 * 2 * T * W * F) / 1e9
+
+
+def resolve_jina_v3(cfg: dict) -> JinaV3Arch:
+    """A local `config.json` with model_type "jina_embeddings_v3" (transformers' JinaEmbeddingsV3Config keys: hidden_size, num_hidden_layers,
+    num_attention_heads, intermediate_size, hidden_act, max_position_embeddings, type_vocab_size, layer_norm_eps, rope_parameters {rope_theta, rope_type})
+    -> JinaV3Arch.  Refused, each by the name of its key: a hidden_act other than gelu, a rope_parameters.rope_type other than default, heads that are
+    not 64 wide, a hidden_size above 2048, an intermediate_size that is no multiple of 64.  rope_theta defaults to 20000.  The longest sequence is
+    min(max_position_embeddings - 2, 8192): the checkpoint's 8194 counts the two XLM-RoBERTa offset positions."""
+    mtype = cfg.get("model_type")
+    if mtype != "jina_embeddings_v3":
+        raise KeyError(f"model_type={mtype} is not a Jina v3 model")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise KeyError(f"hidden_act={cfg.get('hidden_act')} unsupported (gelu only)")
+    rp = cfg.get("rope_parameters") or {}
+    rtype = rp.get("rope_type", rp.get("type", "default"))
+    if rtype != "default":
+        raise KeyError(f"rope_parameters.rope_type={rtype} unsupported (default only: rope scaling is not served)")
+    theta = float(rp.get("rope_theta", cfg.get("rope_theta", 20000.0)))
+    if not theta > 0:
+        raise KeyError(f"rope_theta={theta} must be positive")
+    W, heads, F = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["intermediate_size"])
+    if heads < 1 or W != heads * 64:
+        raise KeyError(f"hidden_size={W} / num_attention_heads={heads} unsupported (64-wide heads only)")
+    if W > 2048:
+        raise KeyError(f"hidden_size={W} unsupported (at most 2048)")
+    if F % 64 or F < 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    max_pos = int(cfg.get("max_position_embeddings", 8194)) - 2
+    if max_pos < 1:
+        raise KeyError(f"max_position_embeddings={cfg.get('max_position_embeddings')} leaves no position (it counts two offset positions)")
+    return JinaV3Arch(vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, 8192), width=W, layers=int(cfg["num_hidden_layers"]), heads=heads, mlp_dim=F,
+                      ln_eps=float(cfg.get("layer_norm_eps", 1e-5)), type_vocab=int(cfg.get("type_vocab_size", 1)), rope_theta=theta)
+
+
+@dataclass(frozen=True)
 class HfClipTextArch:
     """open_clip's HFTextEncoder text tower (CustomTextCLIP checkpoints `text.transformer.*` + `text.proj.*`): a Hugging Face encoder
     (XLM-RoBERTa here), masked-mean pooler, projection MLP Linear(W, hidden) -> GELU -> Linear(hidden, out_dim) without biases,
@@ -1097,6 +1156,11 @@ def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenA
     the same rule; so do model_type bert with position_embedding_type alibi, a JinaBertArch (engine/jina_bert.py::JinaBertTower), and model_type
     nomic_bert, a NomicBertArch (engine/nomic_bert.py::NomicBertTower).  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
+    if mtype == "jina_embeddings_v3":   # transformers JinaEmbeddingsV3Model: jina-embeddings-v3 with its task adapters (engine/jina_v3.py::JinaV3Tower)
+        return resolve_jina_v3(cfg)
+    if mtype == "xlm-roberta" and cfg.get("lora_adaptations") is not None:
+        raise KeyError("model_type=xlm-roberta with lora_adaptations is the original jina-embeddings-v3 repository's custom-code naming, which is not "
+                       "served: bring the checkpoint in transformers' own form (model_type jina_embeddings_v3, jinaai/jina-embeddings-v3-hf)")
     if mtype == "nomic_bert":   # transformers NomicBertModel: nomic-embed-text-v1 / -v1.5, arctic-embed-m-long (engine/nomic_bert.py::NomicBertTower)
         return nomic_bert_arch_from_hf_config(cfg)
     if mtype == "t5":   # transformers T5EncoderModel: sentence-t5, gtr-t5, flan-t5 encoders (engine/t5.py::T5Tower)

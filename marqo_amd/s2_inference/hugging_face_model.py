@@ -68,6 +68,15 @@ class HuggingFaceModelProperties:
         if b is not None and not (isinstance(b, (int, float)) and b > 0):
             raise ValueError("'fp8Budget' must be a positive number")
         self.fp8_budget: Optional[float] = None if b is None else float(b)
+        # engine extension (Jina v3 checkpoints): 'loraTask' = the task adapter every text of this model runs (None: the base model, what the
+        # reference's AutoModel returns), 'loraAdapters' = {task name: PEFT adapter directory} on top of the checkpoint's own adapter sub-directories
+        self.lora_task: Optional[str] = p.get("loraTask", p.get("lora_task"))
+        if self.lora_task is not None and (not isinstance(self.lora_task, str) or not self.lora_task):
+            raise ValueError("'loraTask' must be a task name")
+        self.lora_adapters: Optional[dict] = p.get("loraAdapters", p.get("lora_adapters"))
+        if self.lora_adapters is not None and not (isinstance(self.lora_adapters, dict) and
+                                                   all(isinstance(k, str) and isinstance(v, str) and k and v for k, v in self.lora_adapters.items())):
+            raise ValueError("'loraAdapters' must map task names to adapter directories")
 
     def dict(self) -> dict:
         return dict(self.__dict__)
@@ -138,6 +147,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 return
             if isinstance(arch, archs.NomicBertArch):
                 self._load_nomic_bert(directory, arch, sd)
+                return
+            if isinstance(arch, archs.JinaV3Arch):
+                self._load_jina_v3(directory, arch, sd)
                 return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
@@ -340,6 +352,29 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         self._check_width(arch.width)
         self._finish_packed(directory, arch, arch.max_pos, NomicBertTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="[PAD]"))
 
+    def _load_jina_v3(self, directory: str, arch, sd) -> None:
+        """a Jina v3 checkpoint in transformers' own form (model_type "jina_embeddings_v3": jinaai/jina-embeddings-v3-hf; native in transformers, so
+        trustRemoteCode is not required — it is accepted and ignored): host tokenisation by the `tokenizers` library from the directory's tokenizer.json
+        with the file's own post-processor (<s> ... </s>), right-padded with <pad>, truncated at min(tokens, max_position_embeddings - 2, 8192); the tower
+        of engine/jina_v3.py.  Pooling: the property, else 1_Pooling/config.json, else mean.  Task adapters: every sub-directory of the checkpoint with
+        adapter_config.json + adapter_model.safetensors (PEFT's layout), and the directories of 'loraAdapters'; the task is the directory's name / the
+        dict's key.  'loraTask' selects the adapter of every text (encode(..., task=...) overrides it per call); with neither the base model runs.  The
+        Matryoshka truncation of the model card is not applied (the full vector is returned).  bf16 operands only; no GPU tokeniser and no native
+        request queue for this family."""
+        from marqo_amd.engine import jina_v3
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        props = self.model_properties
+        self._refuse_fp8("Jina v3 encoders (their rotary blocks and LoRA corrections run on bf16 operands only)")
+        self._check_width(arch.width)
+        dirs = jina_v3.find_adapter_dirs(directory)
+        dirs.update(props.lora_adapters or {})
+        try:
+            adapters = jina_v3.load_adapters(arch, dirs)
+        except (ValueError, OSError) as e:
+            raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
+        self._finish_packed(directory, arch, arch.max_pos, jina_v3.JinaV3Tower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="<pad>"),
+                            adapters=adapters, default_task=props.lora_task)
+
     def _load_gemma(self, directory: str, arch, sd) -> None:
         """a transformers Gemma3TextModel checkpoint with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its
         fine-tunes; AutoModel in the reference): host tokenisation by the `tokenizers` library from the directory's tokenizer.json with the file's own
@@ -458,7 +493,16 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 if tok is None:
                     tok = self._tokenizer(sentence, max_length=self.model_properties.tokens)
                 ids, mask = torch.from_numpy(tok["input_ids"]), torch.from_numpy(tok["attention_mask"])
-                out = self._model.encode_ids(ids, mask, normalize=bool(normalize))
+                if kwargs.get("task") is not None:   # one task adapter for this call's texts (Jina v3; any other family has no adapters to name)
+                    if not hasattr(self._model, "task_ids"):
+                        raise InvalidModelPropertiesError(f"{self.model_properties.name}: encode(task={kwargs['task']!r}) needs a checkpoint with LoRA task "
+                                                          f"adapters (model_type jina_embeddings_v3)")
+                    try:
+                        out = self._model.encode(ids, mask, [kwargs["task"]] * len(sentence), normalize=bool(normalize))
+                    except ValueError as e:   # an unknown task name
+                        raise InvalidModelPropertiesError(f"{self.model_properties.name}: {e}") from e
+                else:
+                    out = self._model.encode_ids(ids, mask, normalize=bool(normalize))
             return out if return_device else out.cpu().numpy()
 
 
