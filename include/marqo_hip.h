@@ -1353,6 +1353,37 @@ size_t mq_qwen_workspace_bytes(const mq_qwen_cfg* cfg, int64_t rows, int64_t nse
 int mq_encode_qwen(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                    int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Qwen3 rerankers: prefix-sharing causal attention and the pair-scoring tower (csrc/attention_gqa.hip, csrc/qwen.hip, csrc/rerank.hip;
+ * engine/rerank.py QwenRerankerTower) -------------------------------------------------------------------------------------------------------------------
+ * transformers' Qwen3ForCausalLM used as a yes / no judge (Qwen/Qwen3-Reranker-0.6B) or Qwen3ForSequenceClassification with one label: one query against
+ * n documents.  Under the causal mask everything in front of the document (system prompt, instruction, query) is the same for every hit, so it is
+ * computed once: P + sum(d_i) rows instead of n P + sum(d_i).  Additions to ABI 15: nothing above changes; the entry points below are new.  Each judges
+ * its arguments before any launch, runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_gqa_prefix: mq_attention_gqa's layout.  Rows [0, prefix_len) of d_qkv are the shared prefix, the nseq segments follow: d_cu_seqlens
+ *                   int32 [nseq + 1] with d_cu_seqlens[0] = prefix_len, max_len = the longest SEGMENT, prefix_len + max_len <= 8192.  The query at local
+ *                   position t of a segment sees the prefix_len prefix keys and its own segment's keys 0 .. t, nothing of other segments.  Only the
+ *                   segments' rows of d_out are written (the prefix rows' own attention is mq_attention_gqa on one fixed-length causal sequence).
+ *                   prefix_len need not be a multiple of 64.  With prefix_len = 0 the result is bit-identical to mq_attention_gqa with MQ_MASK_CAUSAL.
+ *   mq_qk_norm_rope_at: mq_qk_norm_rope with a position offset in [0, 8192]: row t of a sequence rotates at position offset + t.  offset 0 is
+ *                   bit-identical to mq_qk_norm_rope.
+ *   mq_score_dot:   d_logits[i] = d_h[i] . d_w  (fp32 [n, W] rows, one fp32 [W] row, fp32 accumulation), d_scores (may be NULL) = sigmoid.  W <= 2048.
+ *   mq_score_qwen_pairs: mq_encode_qwen's tower over packed rows [prefix | seg_1 | ... | seg_n].  The prefix is sequence 0 of the batch:
+ *                   d_cu_seqlens / h_cu_seqlens int32 [nseq + 2] = {0, prefix_len, prefix_len + d_1, ...}; prefix_len may be 0 (every segment is then a
+ *                   whole sequence: the unshared path).  The rotary step runs on the prefix at offset 0 and on the segments at offset prefix_len;
+ *                   attention is mq_attention_gqa (causal) on the prefix and mq_attention_gqa_prefix on the segments; the final RMSNorm runs on every
+ *                   segment's last row only; d_logits fp32 [nseq] = that row . d_score_w (fp32 [width]), d_scores (may be NULL) its sigmoid.
+ *                   prefix_len + the longest segment <= cfg->max_pos.  cfg->pool is not read beyond mq_encode_qwen's check of it. */
+int mq_attention_gqa_prefix(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t prefix_len, int32_t max_len,
+                            int32_t q_heads, int32_t kv_heads, int32_t head_dim, void* stream);
+int mq_qk_norm_rope_at(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                       const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, int32_t offset, void* stream);
+int mq_score_dot(const float* d_h, const float* d_w, int64_t n, int32_t W, float* d_logits, float* d_scores, void* stream);
+size_t mq_score_qwen_pairs_workspace_bytes(const mq_qwen_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_score_qwen_pairs(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, const float* d_score_w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                        const int32_t* h_cu_seqlens, int64_t nseq, int32_t prefix_len, float* d_logits, float* d_scores, void* d_workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- EmbeddingGemma text embedders: 256-wide-head grouped-query band attention and the tower (csrc/attention_gqa256.hip, csrc/gemma.hip;
  * engine/gemma.py) ------------------------------------------------------------------------------------------------------------------------------------
  * transformers' Gemma3TextModel with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its fine-tunes): blocks with

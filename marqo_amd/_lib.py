@@ -497,6 +497,13 @@ _SIGNATURES = {
     "mq_qk_norm_rope": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P]),
     "mq_qwen_workspace_bytes": (C.c_size_t, [C.POINTER(QwenCfg), C.c_int64, C.c_int64]),
     "mq_encode_qwen": (C.c_int, [C.POINTER(QwenCfg), C.POINTER(QwenWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # Qwen3 rerankers: prefix-sharing causal attention, the rotary step at a position offset, the one-row head, the pair-scoring tower
+    # (csrc/attention_gqa.hip, csrc/qwen.hip, csrc/rerank.hip; engine/rerank.py QwenRerankerTower)
+    "mq_attention_gqa_prefix": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_qk_norm_rope_at": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, C.c_int32, _P]),
+    "mq_score_dot": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "mq_score_qwen_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(QwenCfg), C.c_int64, C.c_int64]),
+    "mq_score_qwen_pairs": (C.c_int, [C.POINTER(QwenCfg), C.POINTER(QwenWeights), _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
     # EmbeddingGemma text embedders: 256-wide grouped-query band attention, the fused post-norm / add / pre-norm, the tanh-GELU gated product, the tower
     # (csrc/attention_gqa256.hip, csrc/gemma.hip; engine/gemma.py)
     "mq_attention_gqa_band": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* x /* may alia
 template <int HD, bool NORM>
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ qkv, const int32_t* __restrict__ cu, int fixed_len, int q_heads, int kv_heads,
                                                            const float* __restrict__ q_g, const float* __restrict__ k_g, float eps,
-                                                           const float* __restrict__ inv_freq) {
+                                                           const float* __restrict__ inv_freq, int offset) {
     constexpr int LPH = HD / 4;            // lanes per head (16, 32 or 64)
     constexpr int UPB = 256 / LPH;         // (row, head) units per block and step
     const int row0 = cu ? cu[blockIdx.x] : blockIdx.x * fixed_len;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ 
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             float sn, cs;
-            sincosf((float)t * (k ? f1 : f0), &sn, &cs);
+            sincosf((float)(offset + t) * (k ? f1 : f0), &sn, &cs);   // (offset: the rows in front of the sequence, mq_qk_norm_rope_at; else 0)
             y1[k] = x1[k] * cs - x2[k] * sn;
             y2[k] = x2[k] * cs + x1[k] * sn;
         }
@@ -148,31 +148,46 @@ extern "C" int mq_rmsnorm(const float* d_x, const int32_t* d_row_idx, const floa
     return MQ_OK;
 }
 
-extern "C" int mq_qk_norm_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
-                               const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, void* stream) {
-    MQ_CHECK_ARG(d_qkv && d_inv_freq, "mq_qk_norm_rope: null pointer");
-    MQ_CHECK_ARG(head_dim == 64 || head_dim == 128 || head_dim == 256, "mq_qk_norm_rope: head_dim %d unsupported (64, 128 or 256)", head_dim);
-    MQ_CHECK_ARG(q_heads >= 1 && kv_heads >= 1 && q_heads <= 1024 && kv_heads <= q_heads, "mq_qk_norm_rope: q_heads %d / kv_heads %d", q_heads, kv_heads);
-    MQ_CHECK_ARG((d_q_g == nullptr) == (d_k_g == nullptr), "mq_qk_norm_rope: q and k norm weights come together or not at all");
-    MQ_CHECK_ARG(d_cu || fixed_len > 0, "mq_qk_norm_rope: need fixed_len or cu_seqlens");
+namespace {
+// mq_qk_norm_rope (offset 0) and mq_qk_norm_rope_at: the same checks under the entry point's name `fn`, the same launch
+int qk_norm_rope(const char* fn, void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                 const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, int32_t offset, void* stream) {
+    MQ_CHECK_ARG(d_qkv && d_inv_freq, "%s: null pointer", fn);
+    MQ_CHECK_ARG(head_dim == 64 || head_dim == 128 || head_dim == 256, "%s: head_dim %d unsupported (64, 128 or 256)", fn, head_dim);
+    MQ_CHECK_ARG(q_heads >= 1 && kv_heads >= 1 && q_heads <= 1024 && kv_heads <= q_heads, "%s: q_heads %d / kv_heads %d", fn, q_heads, kv_heads);
+    MQ_CHECK_ARG((d_q_g == nullptr) == (d_k_g == nullptr), "%s: q and k norm weights come together or not at all", fn);
+    MQ_CHECK_ARG(d_cu || fixed_len > 0, "%s: need fixed_len or cu_seqlens", fn);
+    MQ_CHECK_ARG(offset >= 0 && offset <= 8192, "%s: offset %d outside [0, 8192]", fn, offset);
     if (nseq <= 0) return MQ_OK;
-    MQ_CHECK_ARG(nseq < (1LL << 31), "mq_qk_norm_rope: grid too large");
+    MQ_CHECK_ARG(nseq < (1LL << 31), "%s: grid too large", fn);
     hipStream_t s = (hipStream_t)stream;
     MqProfScope prof(3, s);
     const dim3 grid((unsigned)nseq, nseq >= 2048 ? 1 : 8), block(256);
     const int fl = d_cu ? 0 : fixed_len;
+#define MQ_QK_ROPE(HD, NORM) \
+    hipLaunchKernelGGL((qk_norm_rope_kernel<HD, NORM>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq, offset)
     if (head_dim == 64) {
-        if (d_q_g) hipLaunchKernelGGL((qk_norm_rope_kernel<64, true>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
-        else hipLaunchKernelGGL((qk_norm_rope_kernel<64, false>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
+        if (d_q_g) MQ_QK_ROPE(64, true); else MQ_QK_ROPE(64, false);
     } else if (head_dim == 256) {   // (EmbeddingGemma: one wave64 per (row, head))
-        if (d_q_g) hipLaunchKernelGGL((qk_norm_rope_kernel<256, true>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
-        else hipLaunchKernelGGL((qk_norm_rope_kernel<256, false>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
+        if (d_q_g) MQ_QK_ROPE(256, true); else MQ_QK_ROPE(256, false);
     } else {
-        if (d_q_g) hipLaunchKernelGGL((qk_norm_rope_kernel<128, true>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
-        else hipLaunchKernelGGL((qk_norm_rope_kernel<128, false>), grid, block, 0, s, (bf16_t*)d_qkv, d_cu, fl, q_heads, kv_heads, d_q_g, d_k_g, eps, d_inv_freq);
+        if (d_q_g) MQ_QK_ROPE(128, true); else MQ_QK_ROPE(128, false);
     }
-    MQ_CHECK_LAUNCH("mq_qk_norm_rope");
+#undef MQ_QK_ROPE
+    MQ_CHECK_LAUNCH(fn);
     return MQ_OK;
+}
+}  // namespace
+
+extern "C" int mq_qk_norm_rope(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                               const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, void* stream) {
+    return qk_norm_rope("mq_qk_norm_rope", d_qkv, d_cu, nseq, fixed_len, q_heads, kv_heads, head_dim, d_q_g, d_k_g, eps, d_inv_freq, 0, stream);
+}
+
+// mq_qk_norm_rope with a position offset: row t of a sequence rotates at position offset + t (the segments behind a shared prefix of `offset` rows)
+extern "C" int mq_qk_norm_rope_at(void* d_qkv, const int32_t* d_cu, int64_t nseq, int32_t fixed_len, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                                  const float* d_q_g, const float* d_k_g, float eps, const float* d_inv_freq, int32_t offset, void* stream) {
+    return qk_norm_rope("mq_qk_norm_rope_at", d_qkv, d_cu, nseq, fixed_len, q_heads, kv_heads, head_dim, d_q_g, d_k_g, eps, d_inv_freq, offset, stream);
 }
 
 extern "C" size_t mq_qwen_workspace_bytes(const mq_qwen_cfg* cfg, int64_t rows, int64_t nseq) {
@@ -230,4 +245,89 @@ extern "C" int mq_encode_qwen(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, 
         MQ_TRY(mq_pool(x, d_cu_seqlens, nseq, d_out, W, MQ_POOL_MEAN, normalize, s));
     }
     return MQ_OK;
+}
+
+// ---- Qwen3 rerankers: one query against n documents, the part every pair shares computed once ---------------------------------------------------------
+// Packed rows [prefix | seg_1 | ... | seg_n]: the prefix (system prompt, instruction, query: identical for every hit of a search, and under the causal
+// mask independent of what follows it) is sequence 0 of the batch, so cu_seqlens has nseq + 2 entries {0, P, P + d_1, ...}; P = prefix_len may be 0 (no
+// sharing: every segment is a whole pair).  The token gather, the norms, the GEMMs, the gated product and the residuals are row-wise and run over all
+// rows at once; the rotary step runs on the prefix at offset 0 and on the segments at offset P; attention is mq_attention_gqa (causal) on the prefix and
+// mq_attention_gqa_prefix on the segments.  The final norm runs on every segment's last row only, and the logit is one fp32 dot product with the score row.
+namespace {
+struct PairsPlan { Plan tower; size_t off_pooled, total; };
+PairsPlan pairs_plan(const mq_qwen_cfg* c, int64_t rows, int64_t nseq) {
+    PairsPlan p;
+    p.tower = plan(c, rows, nseq);
+    Off ws;
+    ws.take(p.tower.total);
+    p.off_pooled = ws.take((size_t)nseq * c->width * 4);   // the normalised last row of every segment, fp32
+    p.total = ws.end();
+    return p;
+}
+}  // namespace
+
+extern "C" size_t mq_score_qwen_pairs_workspace_bytes(const mq_qwen_cfg* cfg, int64_t rows, int64_t nseq) {
+    if (!cfg || rows <= 0 || nseq <= 0) return 0;
+    return pairs_plan(cfg, rows, nseq).total;
+}
+
+extern "C" int mq_score_qwen_pairs(const mq_qwen_cfg* cfg, const mq_qwen_weights* w, const float* d_score_w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                                   const int32_t* h_cu_seqlens, int64_t nseq, int32_t prefix_len, float* d_logits, float* d_scores, void* d_workspace,
+                                   size_t workspace_bytes, void* stream) {
+    const char* what = "mq_score_qwen_pairs";
+    MQ_TRY(check_cfg(cfg));
+    MQ_CHECK_ARG(w && d_score_w && d_logits, "%s: null pointer", what);
+    MQ_CHECK_ARG(w->tok_emb && w->final_norm_g && w->zeros && w->d_inv_freq && w->layers, "%s: null weight pointer", what);
+    for (int l = 0; l < cfg->layers; ++l) {
+        const mq_qwen_layer& b = w->layers[l];
+        MQ_CHECK_ARG(b.input_norm_g && b.qkv_w && b.out_w && b.post_norm_g && b.ug_w && b.down_w, "%s: layer %d has null weights", what, l);
+        MQ_CHECK_ARG((b.q_norm_g == nullptr) == (b.k_norm_g == nullptr), "%s: layer %d has one of q_norm / k_norm only", what, l);
+    }
+    MQ_CHECK_ARG(prefix_len >= 0 && prefix_len < cfg->max_pos, "%s: prefix_len %d outside [0, max_pos=%d)", what, prefix_len, cfg->max_pos);
+    if (nseq <= 0) return MQ_OK;
+    MQ_CHECK_ARG(nseq < (1ll << 31) - 1, "%s: nseq=%lld too large", what, (long long)nseq);
+    MQ_CHECK_ARG(h_cu_seqlens && h_cu_seqlens[0] == 0 && h_cu_seqlens[1] == prefix_len, "%s: cu_seqlens must begin {0, prefix_len=%d}", what, prefix_len);
+    const int P = prefix_len;
+    int maxl = 0, maxseg = 0;
+    int64_t rows = 0, seg_rows = 0;
+    // every length in [1, max_pos]: the segments' always, the prefix's (sequence 0) when there is one
+    MQ_TRY(packed_begin(what, d_ids, d_cu_seqlens, h_cu_seqlens + (P ? 0 : 1), nseq + (P ? 1 : 0), cfg->max_pos, d_workspace, &maxl, &rows));
+    maxseg = max_seq_len(h_cu_seqlens + 1, nseq, &seg_rows);
+    MQ_CHECK_ARG(maxseg >= 1 && P + maxseg <= cfg->max_pos, "%s: prefix_len %d + the longest segment %d exceeds max_pos=%d", what, P, maxseg, cfg->max_pos);
+    const PairsPlan pp = pairs_plan(cfg, rows, nseq);
+    const Plan& p = pp.tower;
+    MQ_TRY(packed_workspace(what, workspace_bytes, pp.total));
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_workspace;
+    float* x = (float*)(base + p.off_x);
+    void* h = base + p.off_h;
+    void* a = base + p.off_a;
+    void* big = base + p.off_big;
+    int32_t* last = (int32_t*)(base + p.off_rows);
+    float* pooled = (float*)(base + pp.off_pooled);
+    const int32_t* d_seg_cu = d_cu_seqlens + 1;     // {P, P + d_1, ...}: the segments, as mq_attention_gqa_prefix reads them
+    const int W = cfg->width, F = cfg->mlp_dim, Q = cfg->q_heads, KV = cfg->kv_heads, hd = cfg->head_dim;
+    const int AW = Q * hd, QKVW = (Q + 2 * KV) * hd;
+    const int res_flags = MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32;   // (the bias is w->zeros)
+
+    MQ_TRY(mq_embed_tokens(d_ids, d_cu_seqlens, nseq + 1, w->tok_emb, nullptr, nullptr, nullptr, nullptr, x, nullptr, W, cfg->vocab, cfg->rms_eps, 0, s));
+    for (int l = 0; l < cfg->layers; ++l) {
+        const mq_qwen_layer& b = w->layers[l];
+        MQ_TRY(mq_rmsnorm(x, nullptr, b.input_norm_g, h, nullptr, rows, W, cfg->rms_eps, s));
+        MQ_TRY(mq_gemm_bf16(h, W, b.qkv_w, W, b.qkv_b, nullptr, big, QKVW, rows, QKVW, W, b.qkv_b ? MQ_EPI_BIAS : 0, s));
+        if (P) {   // the prefix: one fixed-length causal sequence of P rows at positions 0 .. P - 1
+            MQ_TRY(mq_qk_norm_rope(big, nullptr, 1, P, Q, KV, hd, b.q_norm_g, b.k_norm_g, cfg->rms_eps, w->d_inv_freq, s));
+            MQ_TRY(mq_attention_gqa(big, a, nullptr, 1, P, P, Q, KV, hd, MQ_MASK_CAUSAL, s));
+        }
+        MQ_TRY(mq_qk_norm_rope_at(big, d_seg_cu, nseq, 0, Q, KV, hd, b.q_norm_g, b.k_norm_g, cfg->rms_eps, w->d_inv_freq, P, s));
+        MQ_TRY(mq_attention_gqa_prefix(big, a, d_seg_cu, nseq, P, maxseg, Q, KV, hd, s));
+        MQ_TRY(mq_gemm_bf16(a, AW, b.out_w, AW, w->zeros, x, x, W, rows, W, AW, res_flags, s));
+        MQ_TRY(mq_rmsnorm(x, nullptr, b.post_norm_g, h, nullptr, rows, W, cfg->rms_eps, s));
+        MQ_TRY(mq_gemm_bf16(h, W, b.ug_w, W, nullptr, nullptr, big, 2 * F, rows, 2 * F, W, 0, s));
+        MQ_TRY(mq_glu(big, rows, F, MQ_ACT_SILU, 0, s));
+        MQ_TRY(mq_gemm_bf16(big, 2 * F, b.down_w, F, w->zeros, x, x, W, rows, W, F, res_flags, s));
+    }
+    MQ_TRY(mq_last_rows(d_seg_cu, last, nseq, s));
+    MQ_TRY(mq_rmsnorm(x, last, w->final_norm_g, nullptr, pooled, nseq, W, cfg->rms_eps, s));
+    return mq_score_dot(pooled, d_score_w, nseq, W, d_logits, d_scores, s);
 }

@@ -178,6 +178,23 @@ __global__ __launch_bounds__(256) void score_tail_kernel(const float* __restrict
     }
 }
 
+// ---- the head of the decoder rerankers (Qwen3-Reranker): z = x . w, one fp32 weight row, no dense layer and no bias: one wave64 per pair ------------
+// (lane c takes columns c, c + 64, ... in an fma chain, the xor butterfly adds the lanes)
+__global__ __launch_bounds__(256) void score_dot_kernel(const float* __restrict__ x, const float* __restrict__ w, int64_t n, int W,
+                                                        float* __restrict__ logits, float* __restrict__ scores) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const float* xr = x + r * W;
+    float acc = 0.f;
+    for (int j = lane; j < W; j += 64) acc = fmaf(w[j], xr[j], acc);
+    const float z = wave_sum(acc);
+    if (lane == 0) {
+        logits[r] = z;
+        if (scores) scores[r] = 1.0f / (1.0f + expf(-z));
+    }
+}
+
 // ---- LayerNorm + classifier on the dense layer's GELU output: one wave64 per pair --------------------------------------------------------
 // z = sum_j ((a_j - mu) rstd g_j + b_j) c_j + c_b.  Lane c holds columns c, c + 64, ... of the row (W / 64 <= 32 registers, read once); the mean
 // and the sum of squared deviations (two-pass, as ln_normalize_row) and the classifier's dot product each go through the xor butterfly.  The
@@ -365,6 +382,19 @@ extern "C" int mq_score_head(const float* d_h, int64_t n, int32_t W, const mq_sc
 extern "C" int mq_score_head_gelu(const float* d_h, int64_t n, int32_t W, const mq_score_head_weights* head, float* d_logits, float* d_scores,
                                   void* d_workspace, size_t workspace_bytes, void* stream) {
     return score_head<true>("mq_score_head_gelu", d_h, n, W, head, d_logits, d_scores, d_workspace, workspace_bytes, stream);
+}
+
+// The decoder rerankers' head: d_logits[i] = d_h[i] . d_w (fp32 [n, W] rows against one fp32 [W] row), d_scores (optional) its sigmoid
+extern "C" int mq_score_dot(const float* d_h, const float* d_w, int64_t n, int32_t W, float* d_logits, float* d_scores, void* stream) {
+    MQ_CHECK_ARG(W >= 1 && W <= 64 * 4 * MAXC, "mq_score_dot: W=%d must be in [1, %d]", W, 64 * 4 * MAXC);
+    MQ_CHECK_ARG(n < (1ll << 31), "mq_score_dot: n=%lld too large", (long long)n);
+    if (n <= 0) return MQ_OK;
+    MQ_CHECK_ARG(d_h && d_w && d_logits, "mq_score_dot: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(4, s);
+    hipLaunchKernelGGL(score_dot_kernel, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, s, d_h, d_w, n, (int)W, d_logits, d_scores);
+    MQ_CHECK_LAUNCH("mq_score_dot");
+    return MQ_OK;
 }
 
 extern "C" size_t mq_score_pairs_workspace_bytes(const mq_bert_cfg* cfg, int64_t rows, int64_t nseq) {

@@ -252,6 +252,44 @@ void lora_up(const at::Tensor& T, const at::Tensor& B, int64_t nblocks, const at
                         out.size(1), (int32_t)B.size(1), (int32_t)mode, (int32_t)act, stream_of(T)), "mq_lora_up");
 }
 
+// ---- the Qwen3 rerankers' two kernels (csrc/attention_gqa.hip, csrc/qwen.hip) ---------------------------------------------------------------------------
+// qkv bf16 [rows, (q_heads + 2 kv_heads) head_dim], rows = prefix | segments; cu_seqlens int32 [nseq + 1] on the device, cu_seqlens[0] = prefix_len.
+// `out` bf16 [rows, q_heads head_dim]: only the segments' rows are written.
+void attention_gqa_prefix(const at::Tensor& qkv, const at::Tensor& cu_seqlens, int64_t prefix_len, int64_t max_len, int64_t q_heads, int64_t kv_heads,
+                          int64_t head_dim, at::Tensor out) {
+    need_dev(qkv, at::kBFloat16, "qkv");
+    need_dev(out, at::kBFloat16, "out");
+    need_dev(cu_seqlens, at::kInt, "cu_seqlens");
+    TORCH_CHECK(q_heads >= 1 && kv_heads >= 1 && head_dim >= 1 && qkv.dim() == 2 && out.dim() == 2 && cu_seqlens.numel() >= 1 &&
+                qkv.size(1) == (q_heads + 2 * kv_heads) * head_dim && out.size(0) == qkv.size(0) && out.size(1) == q_heads * head_dim,
+                "marqo_hip::mq_attention_gqa_prefix: qkv [rows, (Q + 2 KV) hd], out [rows, Q hd], cu_seqlens [nseq + 1]");
+    check_rc(mq_attention_gqa_prefix(qkv.data_ptr(), out.data_ptr(), (const int32_t*)cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, (int32_t)prefix_len,
+                                     (int32_t)max_len, (int32_t)q_heads, (int32_t)kv_heads, (int32_t)head_dim, stream_of(qkv)), "mq_attention_gqa_prefix");
+}
+
+// in place on the q and k parts of qkv; q_norm / k_norm fp32 [head_dim] or both None; inv_freq fp32 [head_dim / 2]
+void qk_norm_rope_at(at::Tensor qkv, const c10::optional<at::Tensor>& cu_seqlens, int64_t nseq, int64_t fixed_len, int64_t q_heads, int64_t kv_heads,
+                     int64_t head_dim, const c10::optional<at::Tensor>& q_norm, const c10::optional<at::Tensor>& k_norm, double eps, const at::Tensor& inv_freq,
+                     int64_t offset) {
+    need_dev(qkv, at::kBFloat16, "qkv");
+    need_dev(inv_freq, at::kFloat, "inv_freq");
+    TORCH_CHECK(q_heads >= 1 && kv_heads >= 1 && head_dim >= 2 && qkv.dim() == 2 && qkv.size(1) == (q_heads + 2 * kv_heads) * head_dim &&
+                inv_freq.numel() == head_dim / 2, "marqo_hip::mq_qk_norm_rope_at: qkv [rows, (Q + 2 KV) hd], inv_freq [hd / 2]");
+    const int32_t* cu = nullptr;
+    if (cu_seqlens.has_value()) {
+        need_dev(*cu_seqlens, at::kInt, "cu_seqlens");
+        TORCH_CHECK(cu_seqlens->numel() == nseq + 1, "cu_seqlens must be [nseq + 1]");
+        cu = (const int32_t*)cu_seqlens->data_ptr();
+    } else {
+        TORCH_CHECK(fixed_len > 0 && nseq * fixed_len <= qkv.size(0), "marqo_hip::mq_qk_norm_rope_at: nseq * fixed_len rows must lie in qkv");
+    }
+    const float *qg = nullptr, *kg = nullptr;
+    if (q_norm.has_value()) { need_dev(*q_norm, at::kFloat, "q_norm"); TORCH_CHECK(q_norm->numel() == head_dim, "q_norm must be [head_dim]"); qg = (const float*)q_norm->data_ptr(); }
+    if (k_norm.has_value()) { need_dev(*k_norm, at::kFloat, "k_norm"); TORCH_CHECK(k_norm->numel() == head_dim, "k_norm must be [head_dim]"); kg = (const float*)k_norm->data_ptr(); }
+    check_rc(mq_qk_norm_rope_at(qkv.data_ptr(), cu, nseq, (int32_t)fixed_len, (int32_t)q_heads, (int32_t)kv_heads, (int32_t)head_dim, qg, kg, (float)eps,
+                                (const float*)inv_freq.data_ptr(), (int32_t)offset, stream_of(qkv)), "mq_qk_norm_rope_at");
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -272,6 +310,10 @@ TORCH_LIBRARY(marqo_hip, m) {
     m.def("mq_lora_down(Tensor x, Tensor A, Tensor scale, Tensor seq_task, Tensor seq_task_host, Tensor? cu_seqlens, int fixed_len) -> Tensor");
     m.def("mq_lora_up(Tensor T, Tensor B, int nblocks, Tensor seq_task, Tensor seq_task_host, Tensor? cu_seqlens, int fixed_len, Tensor(a!) out, "
           "int mode, int act) -> ()");
+    m.def("mq_attention_gqa_prefix(Tensor qkv, Tensor cu_seqlens, int prefix_len, int max_len, int q_heads, int kv_heads, int head_dim, "
+          "Tensor(a!) out) -> ()");
+    m.def("mq_qk_norm_rope_at(Tensor(a!) qkv, Tensor? cu_seqlens, int nseq, int fixed_len, int q_heads, int kv_heads, int head_dim, Tensor? q_norm, "
+          "Tensor? k_norm, float eps, Tensor inv_freq, int offset) -> ()");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -288,4 +330,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("l2_normalize", &l2_normalize);
     m.impl("mq_lora_down", &lora_down);
     m.impl("mq_lora_up", &lora_up);
+    m.impl("mq_attention_gqa_prefix", &attention_gqa_prefix);
+    m.impl("mq_qk_norm_rope_at", &qk_norm_rope_at);
 }

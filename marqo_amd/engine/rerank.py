@@ -12,7 +12,10 @@ pooling, dense -> GELU -> LayerNorm -> classifier; one mq_score_pairs_modernbert
 `tokenizers` library from the checkpoint's tokenizer.json; pairing, truncation and packing are the same GPU calls.  A fourth runs on the DeBERTa tower
 (DebertaCrossEncoderTower: `DebertaV2ForSequenceClassification`, [CLS] a [SEP] b [SEP], disentangled attention, ContextPooler head; one
 mq_score_pairs_deberta call per batch), tokenised on the host in the same way.  What the towers share — the length cap, the longest-first order, the
-batch loop — is `_PairScorer.score`.  `load_cross_encoder_tower` picks the class from a directory's config.json.
+batch loop — is `_PairScorer.score`.  A fifth is a decoder: the Qwen3 rerankers (QwenRerankerTower: `Qwen3ForCausalLM` judged by yes / no or its one-logit
+`Qwen3ForSequenceClassification` conversion, the model card's chat template, tokenised on the host; one mq_score_qwen_pairs call per batch in which the
+system prompt, the instruction and the query — the same for every document under the causal mask — are computed once).
+`load_cross_encoder_tower` picks the class from a directory's config.json.
 """
 from __future__ import annotations
 
@@ -20,6 +23,8 @@ import ctypes as C
 import dataclasses
 import json
 import os
+import threading
+import unicodedata
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -29,6 +34,7 @@ from marqo_amd import _lib as L
 from marqo_amd.engine import archs, checkpoint
 from marqo_amd.engine.deberta import DebertaTower
 from marqo_amd.engine.modernbert import ModernBertTower
+from marqo_amd.engine.qwen import QwenTower
 from marqo_amd.engine.tokenizers import HfJsonTokenizer, RobertaBpeTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
 from marqo_amd.engine.tower_weights import modernbert_head_tensors
 from marqo_amd.engine.towers import BertTower, _large_call, _need, request_stream
@@ -483,10 +489,189 @@ class DebertaCrossEncoderTower(_PairScorer, DebertaTower):
                                                 ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_deberta")
 
 
+# ---- Qwen3 rerankers: a decoder judged by one logit, the part every pair of a search shares computed once -------------------------------------------------
+# The template, restated from the model card of Qwen/Qwen3-Reranker-0.6B (no real checkpoint has been run here: README.md)
+QWEN_RERANK_PREFIX = ('<|im_start|>system\nJudge whether the Document meets the requirements based on the Query and the Instruct provided. '
+                      'Note that the answer can only be "yes" or "no".<|im_end|>\n<|im_start|>user\n')
+QWEN_RERANK_SUFFIX = "<|im_end|>\n<|im_start|>assistant\n<think>\n\n</think>\n\n"
+QWEN_RERANK_INSTRUCTION = "Given a web search query, retrieve relevant passages that answer the query"
+
+
+def qwen_rerank_head(instruction: str, query: str) -> str:
+    """the body of the template up to and including `<Document>:` — with the prefix, the part every document of a search shares"""
+    return f"<Instruct>: {instruction}\n<Query>: {query}\n<Document>:"
+
+
+def qwen_split_is_safe(doc: str) -> bool:
+    """the cheap test of a document's text: may ids(head + " " + doc) be formed as ids(head) + ids(" " + doc)?  The Qwen pre-tokeniser starts a new
+    piece at that space whatever follows it, and BPE merges stay inside a piece; the NFC normaliser runs in front of it and is the one step that looks
+    across characters.  A starter (canonical combining class 0, not a mark) behind the space leaves the space alone under NFC; a leading combining mark
+    attaches to it, and that case is not argued here: the call is scored unshared."""
+    return not doc or (unicodedata.combining(doc[0]) == 0 and not unicodedata.category(doc[0]).startswith("M"))
+
+
+def qwen_rerank_rows(tk, prefix_ids: Sequence[int], suffix_ids: Sequence[int], head: str, docs: Sequence[str], budget: int,
+                     normalizer_ok: bool = True) -> Tuple[np.ndarray, list]:
+    """One query's call as token rows -> (shared int32 [P], segments: list of int32 arrays).  The reference forms every pair on its own:
+    prefix + ids(head + " " + doc)[:budget] + suffix.  Shared form (P > 0): shared = prefix + ids(head), segment i = ids(" " + doc_i)[:budget -
+    len(ids(head))] + suffix, the same ids in the same order.  It is taken only when the tokeniser's normaliser is none or NFC (`normalizer_ok`), every
+    document passes qwen_split_is_safe, the head's ids do not change when text follows the head (probed on this call's head), and the head leaves room
+    for at least one document token under the cap.  Otherwise P = 0 and every segment is a whole pair."""
+    enc = lambda s: tk.encode(s, add_special_tokens=False).ids
+    head_ids = enc(head)
+    shared_ok = (normalizer_ok and len(head_ids) < budget and all(qwen_split_is_safe(d) for d in docs)
+                 and enc(head + " a")[:len(head_ids)] == head_ids and enc(head + " a")[len(head_ids):] == enc(" a"))
+    if shared_ok:
+        room = budget - len(head_ids)
+        rows = tk.encode_batch([" " + d for d in docs], add_special_tokens=False)
+        return (np.asarray(list(prefix_ids) + head_ids, dtype=np.int32),
+                [np.asarray(e.ids[:room] + list(suffix_ids), dtype=np.int32) for e in rows])
+    rows = tk.encode_batch([head + " " + d for d in docs], add_special_tokens=False)
+    return np.zeros(0, dtype=np.int32), [np.asarray(list(prefix_ids) + e.ids[:budget] + list(suffix_ids), dtype=np.int32) for e in rows]
+
+
+def qwen_score_row(cfg: dict, sd: Dict[str, Tensor], tk, W: int, where: str) -> Tensor:
+    """the one fp32 weight row [W] whose dot product with the final hidden state of a pair's last token is the logit.  Qwen3ForCausalLM (the published
+    form): lm_head[yes] - lm_head[no], formed here in fp32 (lm_head.weight, else the tied embed_tokens.weight), so that sigmoid(logit) is the model
+    card's softmax over (no, yes); Qwen3ForSequenceClassification with one label (the one-logit conversions): score.weight."""
+    arch_names = cfg.get("architectures") or []
+    if "Qwen3ForSequenceClassification" in arch_names:
+        labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
+        if int(labels) != 1:
+            raise ValueError(f"{where}: num_labels={labels} is not served as a Qwen3 reranker (only one-logit heads)")
+        return _need(sd, "score.weight", (1, W)).detach().to(torch.float32).reshape(W)
+    if "Qwen3ForCausalLM" in arch_names:
+        ids = {t: tk.token_to_id(t) for t in ("yes", "no")}
+        gone = [t for t, i in ids.items() if i is None]
+        if gone:
+            raise ValueError(f"{where}: tokenizer.json has no {' / '.join(repr(t) for t in gone)} token, which the yes / no judgement reads")
+        name = next((k for k in ("lm_head.weight", "model.embed_tokens.weight", "embed_tokens.weight") if k in sd), None)
+        if name is None:
+            raise ValueError(f"{where}: neither lm_head.weight nor embed_tokens.weight is in the checkpoint")
+        head = _need(sd, name, (int(cfg["vocab_size"]), W)).detach()
+        return head[ids["yes"]].to(torch.float32) - head[ids["no"]].to(torch.float32)
+    raise ValueError(f"{where}: architectures={arch_names} is not served as a Qwen3 reranker (Qwen3ForCausalLM or Qwen3ForSequenceClassification)")
+
+
+class QwenRerankerTower(_PairScorer, QwenTower):
+    """`Qwen3ForCausalLM` read as a yes / no judge (Qwen/Qwen3-Reranker-0.6B) or `Qwen3ForSequenceClassification` with one label: the decoder of
+    engine/qwen.py, the final norm on every pair's last token, one fp32 dot product (qwen_score_row).  One query against n documents is ONE
+    mq_score_qwen_pairs call per batch of documents over the rows [shared | segment_1 | ... | segment_n] (qwen_rerank_rows): the system prompt, the
+    instruction and the query are computed once per batch, not once per document.  score() is this class's own: a pair here is one templated string cut
+    from the right, not two texts under LongestFirst, so _PairScorer's pairing and packing calls have nothing to do; its contract (logits and sigmoid in
+    the order of `docs`) is kept."""
+
+    def __init__(self, arch: archs.QwenArch, sd: Dict[str, Tensor], device: str, tokenizer, score_row: Tensor, model_max_length: int = 8192,
+                 instruction: str = QWEN_RERANK_INSTRUCTION):
+        if not arch.qk_norm:
+            raise ValueError("Qwen2-based rerankers are not served (the Qwen3 form only)")
+        QwenTower.__init__(self, arch, sd, device, pooling="last", precision="bf16")
+        if tuple(score_row.shape) != (arch.width,):
+            raise ValueError(f"the score row must be [{arch.width}], got {tuple(score_row.shape)}")
+        self.score_w = self._h.f32(score_row)           # (a device pointer; the holder keeps the tensor)
+        self.tokenizer = tokenizer
+        tokenizer.no_truncation()
+        tokenizer.no_padding()
+        self.instruction = instruction
+        self.model_max_length = int(min(model_max_length, arch.max_pos, 8192))
+        self.prefix_ids = tokenizer.encode(QWEN_RERANK_PREFIX, add_special_tokens=False).ids
+        self.suffix_ids = tokenizer.encode(QWEN_RERANK_SUFFIX, add_special_tokens=False).ids
+        norm = json.loads(tokenizer.to_str()).get("normalizer")
+        self.normalizer_ok = norm is None or norm.get("type") == "NFC"
+        self._lock = threading.Lock()
+        self.last_prefix_len = None      # of the latest score(): 0 = it ran unshared
+
+    @classmethod
+    def from_dir(cls, directory: str, device: str) -> "QwenRerankerTower":
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, tokenizer.json, tokenizer_config.json"""
+        cfg, sd = checkpoint.load_hf_dir(directory)
+        return cls._from_loaded(directory, cfg, sd, device)
+
+    @classmethod
+    def _from_loaded(cls, directory: str, cfg: dict, sd: Dict[str, Tensor], device: str) -> "QwenRerankerTower":
+        mtype = cfg.get("model_type")
+        if mtype == "qwen2":
+            raise ValueError(f"{directory}: model_type='qwen2' is not served as a reranker (Qwen2-based rerankers such as mxbai-rerank-v2 are out of scope)")
+        if mtype != "qwen3":
+            raise ValueError(f"{directory}: model_type={mtype!r} is not a Qwen3 reranker")
+        try:
+            arch = archs.qwen_arch_from_hf_config(cfg)      # (refuses widths above 2048 — the 4B / 8B sizes —, other head widths, rope scaling ...)
+        except KeyError as e:
+            raise ValueError(f"{directory}: {e.args[0] if e.args else e}") from e
+        if not os.path.isfile(os.path.join(directory, "tokenizer.json")):
+            raise ValueError(f"{directory}: a Qwen3 reranker needs the checkpoint's tokenizer.json, which is not there")
+        from tokenizers import Tokenizer
+        tk = Tokenizer.from_file(os.path.join(directory, "tokenizer.json"))
+        row = qwen_score_row(cfg, sd, tk, arch.width, directory)
+        _, max_len = _tokenizer_settings(directory, default_max=8192)
+        return cls(arch, sd, device, tk, row, model_max_length=max_len)
+
+    # ---- scoring ----------------------------------------------------------------------------------------------------------------------------
+    def rows_for(self, query: str, docs: Sequence[str], max_length: int = 512, instruction: Optional[str] = None) -> Tuple[np.ndarray, list]:
+        """(shared ids, segments) of one call (qwen_rerank_rows): the host half of score(), no GPU work"""
+        cap = int(min(max_length, self.model_max_length))
+        budget = cap - len(self.prefix_ids) - len(self.suffix_ids)
+        if budget < 1:
+            raise ValueError(f"max_length={max_length} leaves no room behind the template's {len(self.prefix_ids) + len(self.suffix_ids)} tokens")
+        head = qwen_rerank_head(self.instruction if instruction is None else instruction, query)
+        with self._lock:
+            return qwen_rerank_rows(self.tokenizer, self.prefix_ids, self.suffix_ids, head, docs, budget, self.normalizer_ok)
+
+    def score(self, query: str, docs: Sequence[str], max_length: int = 512, instruction: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (logits, sigmoid(logits)) fp32 [len(docs)] on the host, in the order of `docs`.  Texts are taken as they are (the model card strips
+        nothing); the templated body is cut to min(max_length, model_max_length) - len(prefix) - len(suffix) tokens from the right."""
+        if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
+            raise TypeError("a cross-encoder scores (str, str) pairs")
+        if len(docs) == 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        shared, segs = self.rows_for(query, docs, max_length, instruction)
+        self.last_prefix_len = int(shared.size)
+        return self.score_rows(shared, segs)
+
+    def score_rows(self, shared: np.ndarray, segs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+        """token rows -> (logits, scores): batches of segments, longest first, each behind its own copy of the shared rows (the prefix is recomputed per
+        batch); a batch holds at most max_rows_per_call rows (one segment at least)"""
+        n, P, dev = len(segs), int(shared.size), self.device
+        lens = np.asarray([s.size for s in segs], dtype=np.int64)
+        if n == 0 or int(lens.min()) < 1 or P + int(lens.max()) > self.arch.max_pos:
+            raise ValueError(f"segments must hold 1 .. max_pos - prefix = {self.arch.max_pos - P} tokens")
+        order = np.argsort(-lens, kind="stable")
+        inv = np.empty(n, dtype=np.int64)
+        inv[order] = np.arange(n)
+        limit = max(int(self.max_rows_per_call) - P, int(lens.max()))
+        with request_stream(dev), torch.cuda.device(dev):
+            logits = torch.empty(n, dtype=torch.float32, device=dev)
+            scores = torch.empty(n, dtype=torch.float32, device=dev)
+            with _large_call(dev, int(lens.sum()) + P):
+                a = 0
+                while a < n:
+                    b, rows = a + 1, int(lens[order[a]])
+                    while b < n and rows + int(lens[order[b]]) <= limit:
+                        rows += int(lens[order[b]])
+                        b += 1
+                    cu = torch.zeros(b - a + 2, dtype=torch.int32)
+                    cu[1] = P
+                    cu[2:] = torch.from_numpy(P + np.cumsum(lens[order[a:b]])).to(torch.int32)
+                    packed = torch.from_numpy(np.concatenate([shared] + [segs[i] for i in order[a:b]]).astype(np.int32))
+                    d_ids, d_cu = self._to_device(packed), self._to_device(cu)
+                    ws = self._workspace(self.lib.mq_score_qwen_pairs_workspace_bytes(C.byref(self.cfg), P + rows, b - a))
+                    self.score_packed(d_ids, d_cu, cu, P, logits[a:b], scores[a:b], ws)
+                    a = b
+            out = torch.stack((logits, scores)).cpu().numpy()
+        return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
+
+    def score_packed(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, prefix_len: int, logits: Tensor, scores: Optional[Tensor], ws: Tensor) -> None:
+        """one mq_score_qwen_pairs call on this thread's current stream: packed ids int32 [prefix_len + segment rows], cu_seqlens int32 [nseq + 2] =
+        {0, prefix_len, ...} on the device and the host, logits / scores fp32 [nseq] (scores may be None)"""
+        L.check(self.lib.mq_score_qwen_pairs(C.byref(self.cfg), C.byref(self.w), self.score_w, d_ids.data_ptr(), d_cu.data_ptr(), cu.data_ptr(),
+                                             int(cu.numel()) - 2, int(prefix_len), logits.data_ptr(), L.ptr(scores), ws.data_ptr(), ws.numel(),
+                                             self._stream()), "mq_score_qwen_pairs")
+
+
 def load_cross_encoder_tower(directory: str, device: str):
     """the cross-encoder tower of a local Hugging Face directory, by its config.json: model_type "deberta-v2" -> DebertaCrossEncoderTower.from_dir,
-    "deberta" (v1) is refused here by name, everything else -> CrossEncoderTower.from_dir (which picks among BERT, XLM-RoBERTa / RoBERTa and ModernBERT
-    and refuses the rest)"""
+    "deberta" (v1) is refused here by name, "qwen3" -> QwenRerankerTower.from_dir, everything else -> CrossEncoderTower.from_dir (which picks among BERT,
+    XLM-RoBERTa / RoBERTa and ModernBERT and refuses the rest, "qwen3" included when it is called directly)"""
     mtype = None
     try:
         with open(os.path.join(directory, "config.json")) as f:
@@ -495,6 +680,8 @@ def load_cross_encoder_tower(directory: str, device: str):
         pass                                 # (the loader below reports a missing or broken config.json in its own words)
     if mtype in ("deberta-v2", "deberta"):   # ("deberta": deberta_arch_from_hf_config refuses it, naming model_type)
         return DebertaCrossEncoderTower.from_dir(directory, device)
+    if mtype == "qwen3":
+        return QwenRerankerTower.from_dir(directory, device)
     return CrossEncoderTower.from_dir(directory, device)
 
 

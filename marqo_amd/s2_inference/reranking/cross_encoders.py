@@ -46,12 +46,19 @@ class EngineCrossEncoder:
 
     def __init__(self, directory: str, device: str, max_length: int = 512):
         from marqo_amd.engine.rerank import load_cross_encoder_tower
-        self.tower = load_cross_encoder_tower(directory, device)     # (by the directory's model_type: BERT-family towers or the DeBERTa tower)
+        self.tower = load_cross_encoder_tower(directory, device)     # (by the directory's model_type: BERT-family towers, the DeBERTa or the Qwen3 tower)
         # (model_utils.py:266-270: a max_length above the tokenizer's model_max_length is lowered to it)
         self.max_length = min(int(max_length), self.tower.model_max_length)
         self.weights_source = directory
 
-    def predict(self, inputs: Sequence[Sequence[str]]) -> np.ndarray:
+    def predict(self, inputs: Sequence[Sequence[str]], instruction: Optional[str] = None) -> np.ndarray:
+        """`instruction`: the task description of an instruction-following reranker (the Qwen3 rerankers; None = the tower's default).  A tower
+        whose template has no instruction refuses one."""
+        kw = {}
+        if instruction is not None:
+            if not hasattr(self.tower, "instruction"):
+                raise ValueError(f"{type(self.tower).__name__} takes no instruction (only the Qwen3 rerankers do)")
+            kw["instruction"] = instruction
         scores = np.zeros(len(inputs), dtype=np.float32)
         by_query: Dict[str, List[int]] = {}
         for i, pair in enumerate(inputs):
@@ -59,7 +66,7 @@ class EngineCrossEncoder:
                 raise TypeError(f"expected [query, text] pairs of strings, found {pair!r}")
             by_query.setdefault(pair[0], []).append(i)
         for query, idx in by_query.items():       # (one query per search: one pass)
-            scores[idx] = self.tower.score(query, [inputs[i][1] for i in idx], self.max_length)[1]
+            scores[idx] = self.tower.score(query, [inputs[i][1] for i in idx], self.max_length, **kw)[1]
         return scores
 
 
@@ -179,11 +186,14 @@ class ReRanker:
 
 
 class ReRankerText(ReRanker):
-    """reranking with a Hugging Face cross-encoder (Bert / XLMRoberta / Roberta / ModernBert / DebertaV2 ForSequenceClassification with one logit)"""
+    """reranking with a Hugging Face cross-encoder (Bert / XLMRoberta / Roberta / ModernBert / DebertaV2 ForSequenceClassification with one logit) or
+    a Qwen3 reranker (Qwen3ForCausalLM judged by yes / no, or its one-logit conversion); `instruction` (Qwen3 rerankers only) replaces the template's
+    default task description"""
 
     def __init__(self, model_name: str, device: str, max_length: int = 512, num_highlights: int = 1,
-                 split_params: Optional[Dict] = get_default_text_processing_parameters()):
+                 split_params: Optional[Dict] = get_default_text_processing_parameters(), instruction: Optional[str] = None):
         super().__init__()
+        self.instruction = instruction
         self.model_name = model_name
         self.device = device
         self.max_length = max_length
@@ -226,7 +236,8 @@ class ReRankerText(ReRanker):
             self.inputs = self.explode_nested_content_field(self.inputs)
             logger.info(f"chunking field content, went from length {n} to {len(self.inputs)}")
         self.model_inputs = self._prepare_inputs(self.inputs)
-        self.scores = [float(s) for s in np.asarray(self.model.predict(self.model_inputs)).reshape(-1)]
+        extra = {} if self.instruction is None else {"instruction": self.instruction}
+        self.scores = [float(s) for s in np.asarray(self.model.predict(self.model_inputs, **extra)).reshape(-1)]
         if len(self.scores) != len(self.inputs):
             raise RuntimeError(f"the model returned {len(self.scores)} scores for {len(self.inputs)} pairs")
         for row, s in zip(self.inputs, self.scores):
