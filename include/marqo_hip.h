@@ -1812,6 +1812,70 @@ int mq_encode_jina_v3(const mq_jina_v3_cfg* cfg, const mq_jina_v3_weights* w, co
                       const int32_t* h_cu_seqlens, const int32_t* d_seq_task, const int32_t* h_seq_task, int64_t nseq, float* d_out, int normalize,
                       void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Gemma rerankers: causal and prefix-sharing grouped-query attention at 256-wide heads, and the pair-scoring tower
+ * (csrc/attention_gqa256_causal.hip, csrc/gemma_causal.hip; engine/rerank.py GemmaRerankerTower) ----------------------------------------------------------
+ * transformers' GemmaForCausalLM (model_type "gemma": BAAI/bge-reranker-v2-gemma = Gemma-2B, 18 blocks, width 2048, 8 query heads over ONE K/V head of
+ * width 256) read as a judge whose score is the logit of `Yes` at the last token, or GemmaForSequenceClassification with one label: pre-norm blocks with
+ * two RMSNorms (weights applied as 1 + w), rotary positions, no q / k norm, no soft-capping, no sliding window, a gated tanh-GELU MLP, the token table
+ * scaled by sqrt(width), a causal mask.  One query against n documents: `[bos] A: query` is the same token row for every hit and is computed once.
+ * Additions to ABI 15: nothing above changes; the structs and entry points below are new.  Each judges its arguments before any launch (MQ_ERR_INVALID,
+ * the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_gqa256_causal: mq_attention_gqa_band's layout at head_dim 256 under the causal mask: query i of a sequence sees keys 0 .. i of that
+ *                   sequence.  Sequences packed (d_cu_seqlens int32 [nseq + 1], max_len = the longest) or fixed_len > 0.  `scale` is the softmax scale.
+ *   mq_attention_gqa256_prefix: mq_attention_gqa_prefix's conventions at head_dim 256, with the softmax scale as an argument: rows [0, prefix_len) of
+ *                   d_qkv are the shared prefix, d_cu_seqlens int32 [nseq + 1] with d_cu_seqlens[0] = prefix_len are the segments, max_len = the longest
+ *                   SEGMENT, prefix_len + max_len <= 8192; the query at local position t of a segment sees the prefix_len prefix keys and its own
+ *                   segment's keys 0 .. t.  Only the segments' rows of d_out are written.  prefix_len need not be a multiple of 64; prefix_len = 0 gives
+ *                   the bits of mq_attention_gqa256_causal on the same packed batch (it is the same kernel).  One workgroup of 8 waves per (sequence,
+ *                   K/V head, slice of max(1, 8 / G) 16-query blocks) stages the K/V head's tiles once for all G query heads, two 64-key tiles (128 KiB
+ *                   of LDS) at a time, and only the prefix's tiles and the own tiles up to the slice's last query.
+ *   mq_score_gemma_pairs: mq_score_qwen_pairs' contract on the Gemma blocks: packed rows [prefix | seg_1 | ... | seg_n], d_cu_seqlens / h_cu_seqlens
+ *                   int32 [nseq + 2] = {0, prefix_len, prefix_len + d_1, ...}; prefix_len may be 0 (the unshared path).  Per block
+ *                   x += Wo(attn(rope(Wqkv(norm(x))))) ; x += Wdown(up * gelu_tanh(gate)) with (up | gate) = Wug(norm(x)); the rotary step runs on the
+ *                   prefix at offset 0 and on the segments at offset prefix_len; attention is mq_attention_gqa256_causal on the prefix and
+ *                   mq_attention_gqa256_prefix on the segments at cfg->attn_scale; the final RMSNorm runs on every segment's last row only; d_logits fp32
+ *                   [nseq] = that row . d_score_w (fp32 [width]), d_scores (may be NULL) its sigmoid.  width <= 2048 (a multiple of 64), head_dim 256,
+ *                   mlp_dim % 64 == 0, max_pos <= 8192, prefix_len + the longest segment <= cfg->max_pos. */
+typedef struct mq_gemma_causal_layer {
+    const float* input_norm_g;  /* fp32 [W]  1 + input_layernorm */
+    const void*  qkv_w;         /* bf16 [(Q + 2 KV) hd, W]  rows: q_proj | k_proj | v_proj */
+    const void*  out_w;         /* bf16 [W, Q hd]  o_proj */
+    const float* post_norm_g;   /* fp32 [W]  1 + post_attention_layernorm */
+    const void*  ug_w;          /* bf16 [2F, W]  rows: up_proj | gate_proj (mq_glu's order) */
+    const void*  down_w;        /* bf16 [W, F]  down_proj */
+} mq_gemma_causal_layer;
+
+typedef struct mq_gemma_causal_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  embed_tokens * sqrtf(W): the fp32 product mq_encode_gemma forms per row, formed once at load */
+    const float* final_norm_g;  /* fp32 [W]  1 + norm */
+    const float* zeros;         /* fp32 [W] zeros (the bias slot of the residual GEMMs) */
+    const float* d_inv_freq;    /* fp32 [hd / 2]: rope_theta ^ -(2 i / hd) */
+    const mq_gemma_causal_layer* layers;  /* host array, `layers` entries */
+} mq_gemma_causal_weights;
+
+typedef struct mq_gemma_causal_cfg {
+    int32_t width;       /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t q_heads;     /* Q */
+    int32_t kv_heads;    /* KV, divides Q */
+    int32_t head_dim;    /* hd: 256; Q hd need not be W */
+    int32_t mlp_dim;     /* F, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;     /* longest pair served (<= 8192) */
+    float   rms_eps;
+    float   attn_scale;  /* head_dim ^ -0.5 */
+} mq_gemma_causal_cfg;
+
+int mq_attention_gqa256_causal(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
+                               int32_t q_heads, int32_t kv_heads, int32_t head_dim, float scale, void* stream);
+int mq_attention_gqa256_prefix(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t prefix_len, int32_t max_len,
+                               int32_t q_heads, int32_t kv_heads, int32_t head_dim, float scale, void* stream);
+size_t mq_score_gemma_pairs_workspace_bytes(const mq_gemma_causal_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_score_gemma_pairs(const mq_gemma_causal_cfg* cfg, const mq_gemma_causal_weights* w, const float* d_score_w, const int32_t* d_ids,
+                         const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, int32_t prefix_len, float* d_logits, float* d_scores,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

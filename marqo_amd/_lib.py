@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -242,6 +242,21 @@ class GemmaWeights(C.Structure):
 class GemmaCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
                 ("vocab", C.c_int32), ("max_pos", C.c_int32), ("half_window", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float), ("attn_scale", C.c_float)]
+
+
+class GemmaCausalLayer(C.Structure):
+    """mq_gemma_causal_layer: one block of the Gemma rerankers (csrc/gemma_causal.hip)"""
+    _fields_ = [(n, C.c_void_p) for n in ("input_norm_g", "qkv_w", "out_w", "post_norm_g", "ug_w", "down_w")]
+
+
+class GemmaCausalWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("final_norm_g", C.c_void_p), ("zeros", C.c_void_p), ("d_inv_freq", C.c_void_p),
+                ("layers", C.POINTER(GemmaCausalLayer))]
+
+
+class GemmaCausalCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
+                ("vocab", C.c_int32), ("max_pos", C.c_int32), ("rms_eps", C.c_float), ("attn_scale", C.c_float)]
 
 
 class T5Layer(C.Structure):
@@ -542,7 +557,14 @@ _SIGNATURES = {
     "mq_jina_v3_workspace_bytes": (C.c_size_t, [C.POINTER(JinaV3Cfg), C.c_int64, C.c_int64]),
     "mq_encode_jina_v3": (C.c_int, [C.POINTER(JinaV3Cfg), C.POINTER(JinaV3Weights), C.POINTER(JinaV3Lora), _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int, _P,
                                     C.c_size_t, _P]),
-    "mq_tune": (C.c_int, [C.c_char_p, C.c_int]),
+    # Gemma rerankers: causal and prefix-sharing grouped-query attention at 256-wide heads, the pair-scoring tower
+    # (csrc/attention_gqa256_causal.hip, csrc/gemma_causal.hip; engine/rerank.py GemmaRerankerTower)
+    "mq_attention_gqa256_causal": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_attention_gqa256_prefix": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_score_gemma_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(GemmaCausalCfg), C.c_int64, C.c_int64]),
+    "mq_score_gemma_pairs": (C.c_int, [C.POINTER(GemmaCausalCfg), C.POINTER(GemmaCausalWeights), _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P,
+                                       C.c_size_t, _P]),
+    "mq_tune":(C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
     "mq_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -290,6 +290,20 @@ void qk_norm_rope_at(at::Tensor qkv, const c10::optional<at::Tensor>& cu_seqlens
                                 (const float*)inv_freq.data_ptr(), (int32_t)offset, stream_of(qkv)), "mq_qk_norm_rope_at");
 }
 
+// the Gemma rerankers' attention (csrc/attention_gqa256_causal.hip): attention_gqa_prefix's arguments at head_dim 256, with the softmax scale
+void attention_gqa256_prefix(const at::Tensor& qkv, const at::Tensor& cu_seqlens, int64_t prefix_len, int64_t max_len, int64_t q_heads, int64_t kv_heads,
+                             int64_t head_dim, double scale, at::Tensor out) {
+    need_dev(qkv, at::kBFloat16, "qkv");
+    need_dev(out, at::kBFloat16, "out");
+    need_dev(cu_seqlens, at::kInt, "cu_seqlens");
+    TORCH_CHECK(q_heads >= 1 && kv_heads >= 1 && head_dim >= 1 && qkv.dim() == 2 && out.dim() == 2 && cu_seqlens.numel() >= 1 &&
+                qkv.size(1) == (q_heads + 2 * kv_heads) * head_dim && out.size(0) == qkv.size(0) && out.size(1) == q_heads * head_dim,
+                "marqo_hip::mq_attention_gqa256_prefix: qkv [rows, (Q + 2 KV) hd], out [rows, Q hd], cu_seqlens [nseq + 1]");
+    check_rc(mq_attention_gqa256_prefix(qkv.data_ptr(), out.data_ptr(), (const int32_t*)cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, (int32_t)prefix_len,
+                                        (int32_t)max_len, (int32_t)q_heads, (int32_t)kv_heads, (int32_t)head_dim, (float)scale, stream_of(qkv)),
+             "mq_attention_gqa256_prefix");
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -314,6 +328,8 @@ TORCH_LIBRARY(marqo_hip, m) {
           "Tensor(a!) out) -> ()");
     m.def("mq_qk_norm_rope_at(Tensor(a!) qkv, Tensor? cu_seqlens, int nseq, int fixed_len, int q_heads, int kv_heads, int head_dim, Tensor? q_norm, "
           "Tensor? k_norm, float eps, Tensor inv_freq, int offset) -> ()");
+    m.def("mq_attention_gqa256_prefix(Tensor qkv, Tensor cu_seqlens, int prefix_len, int max_len, int q_heads, int kv_heads, int head_dim, float scale, "
+          "Tensor(a!) out) -> ()");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -332,4 +348,5 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_lora_up", &lora_up);
     m.impl("mq_attention_gqa_prefix", &attention_gqa_prefix);
     m.impl("mq_qk_norm_rope_at", &qk_norm_rope_at);
+    m.impl("mq_attention_gqa256_prefix", &attention_gqa256_prefix);
 }

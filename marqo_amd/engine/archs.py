@@ -473,6 +473,92 @@ def gemma_arch_from_hf_config(cfg: dict) -> GemmaArch:
 
 
 @dataclass(frozen=True)
+class GemmaCausalArch:
+    """transformers' GemmaForCausalLM / GemmaModel (model_type "gemma": Gemma-2B, the body of BAAI/bge-reranker-v2-gemma) as the engine runs it: pre-norm
+    decoder blocks with two RMSNorms (weights applied as 1 + w), `kv_heads` K/V heads of width 256 shared by `heads` query heads, rotary positions with
+    one base, no q / k norm, no soft-capping, no sliding window, a gated tanh-GELU MLP, the token table scaled by sqrt(width), a causal mask."""
+    vocab: int = 256000
+    max_pos: int = 8192
+    width: int = 2048
+    layers: int = 18
+    heads: int = 8
+    kv_heads: int = 1
+    head_dim: int = 256
+    mlp_dim: int = 16384
+    rms_eps: float = 1e-6
+    rope_theta: float = 10000.0
+    qk_norm: bool = False      # (the two switches qwen_state_dict reads: the tensors are Qwen's, minus the q / k norms and the biases)
+    qkv_bias: bool = False
+
+    @property
+    def attn_scale(self) -> float:
+        return float(self.head_dim) ** -0.5
+
+    def inv_freq(self):
+        """[head_dim / 2] inverse frequencies as transformers' default rope initialisation builds them: theta^-(2i/d)"""
+        import torch
+        d = self.head_dim
+        return 1.0 / (self.rope_theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F, A = tokens, self.width, self.mlp_dim, self.heads * self.head_dim
+        layer = 2 * T * W * (A + 2 * self.kv_heads * self.head_dim) + 2 * T * A * W + 2 * 3 * T * W * F + 2 * T * T * A   # (causal: half of 4 T T A)
+        return self.layers * layer / 1e9
+
+
+def gemma_causal_arch_from_hf_config(cfg: dict) -> GemmaCausalArch:
+    """A local Gemma `config.json` (model_type "gemma") -> GemmaCausalArch.  rope_theta comes from `rope_parameters`, else the older top-level key.
+
+    The activation: `hidden_activation` when the file has a non-null one, else `hidden_act`, else gelu_pytorch_tanh.  Only gelu_pytorch_tanh is served.
+    The legacy spelling hidden_act="gelu" (with no hidden_activation) is REFUSED, because it does not name one function: transformers 4.39 .. 4.x ran
+    the tanh form for it (with a warning), transformers 5.15 — the installed one — reads `hidden_act` alone and runs the erf form.
+
+    Refused with a ValueError that names the key: model_type gemma2 / gemma3 / gemma3_text (and anything else), rope_scaling or a non-default rope_type,
+    attention_bias true, another activation, head_dim other than 256, hidden_size above 2048 (the 7B), max_position_embeddings above 8192, a non-null
+    attn_logit_softcapping / final_logit_softcapping / sliding_window (keys of the later families)."""
+    mtype = cfg.get("model_type")
+    if mtype in ("gemma2", "gemma3", "gemma3_text"):
+        raise ValueError(f"model_type={mtype} is not served as a reranker (Gemma2 / Gemma3 are out of scope: only model_type 'gemma')")
+    if mtype != "gemma":
+        raise ValueError(f"model_type={mtype} is not a Gemma model")
+    if cfg.get("rope_scaling"):
+        raise ValueError(f"rope_scaling={cfg.get('rope_scaling')} unsupported")
+    rp = cfg.get("rope_parameters") or {}
+    rtype = rp.get("rope_type", rp.get("type", "default"))
+    if rtype != "default" or rp.get("factor") is not None:
+        raise ValueError(f"rope_parameters.rope_type={rtype} unsupported (default, without scaling, only)")
+    if cfg.get("attention_bias", False):
+        raise ValueError("attention_bias=true unsupported (bias-free projections only)")
+    for key in ("attn_logit_softcapping", "final_logit_softcapping", "sliding_window"):
+        if cfg.get(key) is not None:
+            raise ValueError(f"{key}={cfg.get(key)} unsupported (a key of Gemma2 / Gemma3; null only)")
+    key = "hidden_activation" if cfg.get("hidden_activation") is not None else "hidden_act"
+    act = cfg.get(key, "gelu_pytorch_tanh")
+    if act == "gelu" and key == "hidden_act":
+        raise ValueError("hidden_act=gelu is ambiguous (transformers 4.x ran the tanh form for it, transformers 5 runs the erf form): write "
+                         "hidden_activation=gelu_pytorch_tanh, what Gemma was trained with, into config.json")
+    if act != "gelu_pytorch_tanh":
+        raise ValueError(f"{key}={act} unsupported (gelu_pytorch_tanh only)")
+    W, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    kv = int(cfg.get("num_key_value_heads") or heads)
+    if heads < 1 or kv < 1 or heads % kv:
+        raise ValueError(f"num_attention_heads={heads} must be a multiple of num_key_value_heads={kv}")
+    hd = int(cfg.get("head_dim") or 256)
+    if hd != 256:
+        raise ValueError(f"head_dim={hd} unsupported (256 only)")
+    if W > 2048 or W % 64:
+        raise ValueError(f"hidden_size={W} unsupported (a multiple of 64 up to 2048: the 7B size of this family is not served)")
+    F = int(cfg["intermediate_size"])
+    if F % 64:
+        raise ValueError(f"intermediate_size={F} must be a multiple of 64")
+    max_pos = int(cfg.get("max_position_embeddings", 8192))
+    if max_pos > 8192:
+        raise ValueError(f"max_position_embeddings={max_pos} unsupported (at most 8192)")
+    return GemmaCausalArch(vocab=int(cfg["vocab_size"]), max_pos=max_pos, width=W, layers=layers, heads=heads, kv_heads=kv, head_dim=hd, mlp_dim=F,
+                           rms_eps=float(cfg.get("rms_norm_eps", 1e-6)), rope_theta=float(rp.get("rope_theta", cfg.get("rope_theta", 10000.0))))
+
+
+@dataclass(frozen=True)
 class T5Arch:
     """transformers' T5EncoderModel (model_type "t5": sentence-t5, gtr-t5, flan-t5 / T5 v1.1 encoder fine-tunes) as the engine runs it: pre-norm blocks with
     RMSNorms, bias-free Linears, `heads` attention heads of width head_dim (d_kv) whose total need not be `width` (d_model), no softmax scale, ONE

@@ -14,7 +14,9 @@ pooling, dense -> GELU -> LayerNorm -> classifier; one mq_score_pairs_modernbert
 mq_score_pairs_deberta call per batch), tokenised on the host in the same way.  What the towers share — the length cap, the longest-first order, the
 batch loop — is `_PairScorer.score`.  A fifth is a decoder: the Qwen3 rerankers (QwenRerankerTower: `Qwen3ForCausalLM` judged by yes / no or its one-logit
 `Qwen3ForSequenceClassification` conversion, the model card's chat template, tokenised on the host; one mq_score_qwen_pairs call per batch in which the
-system prompt, the instruction and the query — the same for every document under the causal mask — are computed once).
+system prompt, the instruction and the query — the same for every document under the causal mask — are computed once).  A sixth is Gemma-2B
+(GemmaRerankerTower: BAAI/bge-reranker-v2-gemma, `GemmaForCausalLM` judged by the logit of `Yes`, or its one-logit `GemmaForSequenceClassification`
+conversion; FlagEmbedding's piecewise-tokenised input, on the host; one mq_score_gemma_pairs call per batch with `[bos] A: query` computed once).
 `load_cross_encoder_tower` picks the class from a directory's config.json.
 """
 from __future__ import annotations
@@ -36,8 +38,8 @@ from marqo_amd.engine.deberta import DebertaTower
 from marqo_amd.engine.modernbert import ModernBertTower
 from marqo_amd.engine.qwen import QwenTower
 from marqo_amd.engine.tokenizers import HfJsonTokenizer, RobertaBpeTokenizer, WordPieceTokenizer, XlmRobertaTokenizer
-from marqo_amd.engine.tower_weights import modernbert_head_tensors
-from marqo_amd.engine.towers import BertTower, _large_call, _need, request_stream
+from marqo_amd.engine.tower_weights import gemma_causal_state_dict, modernbert_head_tensors
+from marqo_amd.engine.towers import BertTower, _PackedTextTower, _check_precision, _large_call, _need, request_stream
 
 Tensor = torch.Tensor
 
@@ -489,6 +491,52 @@ class DebertaCrossEncoderTower(_PairScorer, DebertaTower):
                                                 ws.data_ptr(), ws.numel(), self._stream()), "mq_score_pairs_deberta")
 
 
+class _PrefixPairScorer(_PairScorer):
+    """what the decoder rerankers (QwenRerankerTower, GemmaRerankerTower) share behind their own templates: token rows [shared | segment_1 | ... |
+    segment_n] -> one `pairs_entry` call (mq_score_qwen_pairs' contract) per batch of segments.  The tower supplies cfg / w / score_w, arch.max_pos and
+    max_rows_per_call."""
+    pairs_entry = "mq_score_qwen_pairs"
+
+    def score_rows(self, shared: np.ndarray, segs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+        """token rows -> (logits, scores): batches of segments, longest first, each behind its own copy of the shared rows (the prefix is recomputed per
+        batch); a batch holds at most max_rows_per_call rows (one segment at least)"""
+        n, P, dev = len(segs), int(shared.size), self.device
+        lens = np.asarray([s.size for s in segs], dtype=np.int64)
+        if n == 0 or int(lens.min()) < 1 or P + int(lens.max()) > self.arch.max_pos:
+            raise ValueError(f"segments must hold 1 .. max_pos - prefix = {self.arch.max_pos - P} tokens")
+        order = np.argsort(-lens, kind="stable")
+        inv = np.empty(n, dtype=np.int64)
+        inv[order] = np.arange(n)
+        limit = max(int(self.max_rows_per_call) - P, int(lens.max()))
+        with request_stream(dev), torch.cuda.device(dev):
+            logits = torch.empty(n, dtype=torch.float32, device=dev)
+            scores = torch.empty(n, dtype=torch.float32, device=dev)
+            with _large_call(dev, int(lens.sum()) + P):
+                a = 0
+                while a < n:
+                    b, rows = a + 1, int(lens[order[a]])
+                    while b < n and rows + int(lens[order[b]]) <= limit:
+                        rows += int(lens[order[b]])
+                        b += 1
+                    cu = torch.zeros(b - a + 2, dtype=torch.int32)
+                    cu[1] = P
+                    cu[2:] = torch.from_numpy(P + np.cumsum(lens[order[a:b]])).to(torch.int32)
+                    packed = torch.from_numpy(np.concatenate([shared] + [segs[i] for i in order[a:b]]).astype(np.int32))
+                    d_ids, d_cu = self._to_device(packed), self._to_device(cu)
+                    ws = self._workspace(getattr(self.lib, self.pairs_entry + "_workspace_bytes")(C.byref(self.cfg), P + rows, b - a))
+                    self.score_packed(d_ids, d_cu, cu, P, logits[a:b], scores[a:b], ws)
+                    a = b
+            out = torch.stack((logits, scores)).cpu().numpy()
+        return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
+
+    def score_packed(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, prefix_len: int, logits: Tensor, scores: Optional[Tensor], ws: Tensor) -> None:
+        """one mq_score_qwen_pairs | mq_score_gemma_pairs call (`pairs_entry`) on this thread's current stream: packed ids int32 [prefix_len + segment rows], cu_seqlens int32 [nseq + 2] =
+        {0, prefix_len, ...} on the device and the host, logits / scores fp32 [nseq] (scores may be None)"""
+        L.check(getattr(self.lib, self.pairs_entry)(C.byref(self.cfg), C.byref(self.w), self.score_w, d_ids.data_ptr(), d_cu.data_ptr(), cu.data_ptr(),
+                                             int(cu.numel()) - 2, int(prefix_len), logits.data_ptr(), L.ptr(scores), ws.data_ptr(), ws.numel(),
+                                             self._stream()), self.pairs_entry)
+
+
 # ---- Qwen3 rerankers: a decoder judged by one logit, the part every pair of a search shares computed once -------------------------------------------------
 # The template, restated from the model card of Qwen/Qwen3-Reranker-0.6B (no real checkpoint has been run here: README.md)
 QWEN_RERANK_PREFIX = ('<|im_start|>system\nJudge whether the Document meets the requirements based on the Query and the Instruct provided. '
@@ -553,7 +601,7 @@ def qwen_score_row(cfg: dict, sd: Dict[str, Tensor], tk, W: int, where: str) -> 
     raise ValueError(f"{where}: architectures={arch_names} is not served as a Qwen3 reranker (Qwen3ForCausalLM or Qwen3ForSequenceClassification)")
 
 
-class QwenRerankerTower(_PairScorer, QwenTower):
+class QwenRerankerTower(_PrefixPairScorer, QwenTower):
     """`Qwen3ForCausalLM` read as a yes / no judge (Qwen/Qwen3-Reranker-0.6B) or `Qwen3ForSequenceClassification` with one label: the decoder of
     engine/qwen.py, the final norm on every pair's last token, one fp32 dot product (qwen_score_row).  One query against n documents is ONE
     mq_score_qwen_pairs call per batch of documents over the rows [shared | segment_1 | ... | segment_n] (qwen_rerank_rows): the system prompt, the
@@ -628,50 +676,167 @@ class QwenRerankerTower(_PairScorer, QwenTower):
         self.last_prefix_len = int(shared.size)
         return self.score_rows(shared, segs)
 
-    def score_rows(self, shared: np.ndarray, segs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
-        """token rows -> (logits, scores): batches of segments, longest first, each behind its own copy of the shared rows (the prefix is recomputed per
-        batch); a batch holds at most max_rows_per_call rows (one segment at least)"""
-        n, P, dev = len(segs), int(shared.size), self.device
-        lens = np.asarray([s.size for s in segs], dtype=np.int64)
-        if n == 0 or int(lens.min()) < 1 or P + int(lens.max()) > self.arch.max_pos:
-            raise ValueError(f"segments must hold 1 .. max_pos - prefix = {self.arch.max_pos - P} tokens")
-        order = np.argsort(-lens, kind="stable")
-        inv = np.empty(n, dtype=np.int64)
-        inv[order] = np.arange(n)
-        limit = max(int(self.max_rows_per_call) - P, int(lens.max()))
-        with request_stream(dev), torch.cuda.device(dev):
-            logits = torch.empty(n, dtype=torch.float32, device=dev)
-            scores = torch.empty(n, dtype=torch.float32, device=dev)
-            with _large_call(dev, int(lens.sum()) + P):
-                a = 0
-                while a < n:
-                    b, rows = a + 1, int(lens[order[a]])
-                    while b < n and rows + int(lens[order[b]]) <= limit:
-                        rows += int(lens[order[b]])
-                        b += 1
-                    cu = torch.zeros(b - a + 2, dtype=torch.int32)
-                    cu[1] = P
-                    cu[2:] = torch.from_numpy(P + np.cumsum(lens[order[a:b]])).to(torch.int32)
-                    packed = torch.from_numpy(np.concatenate([shared] + [segs[i] for i in order[a:b]]).astype(np.int32))
-                    d_ids, d_cu = self._to_device(packed), self._to_device(cu)
-                    ws = self._workspace(self.lib.mq_score_qwen_pairs_workspace_bytes(C.byref(self.cfg), P + rows, b - a))
-                    self.score_packed(d_ids, d_cu, cu, P, logits[a:b], scores[a:b], ws)
-                    a = b
-            out = torch.stack((logits, scores)).cpu().numpy()
-        return np.ascontiguousarray(out[0][inv]), np.ascontiguousarray(out[1][inv])
 
-    def score_packed(self, d_ids: Tensor, d_cu: Tensor, cu: Tensor, prefix_len: int, logits: Tensor, scores: Optional[Tensor], ws: Tensor) -> None:
-        """one mq_score_qwen_pairs call on this thread's current stream: packed ids int32 [prefix_len + segment rows], cu_seqlens int32 [nseq + 2] =
-        {0, prefix_len, ...} on the device and the host, logits / scores fp32 [nseq] (scores may be None)"""
-        L.check(self.lib.mq_score_qwen_pairs(C.byref(self.cfg), C.byref(self.w), self.score_w, d_ids.data_ptr(), d_cu.data_ptr(), cu.data_ptr(),
-                                             int(cu.numel()) - 2, int(prefix_len), logits.data_ptr(), L.ptr(scores), ws.data_ptr(), ws.numel(),
-                                             self._stream()), "mq_score_qwen_pairs")
+# ---- Gemma rerankers: Gemma-2B judged by the logit of `Yes`, `[bos] A: query` computed once per batch ------------------------------------------------------
+# The input format, restated from memory of FlagEmbedding's FlagLLMReranker (the package is not installed here and no real checkpoint has been run:
+# README.md).  The reference tokenises the query, the passage, the separator and the prompt SEPARATELY and concatenates ids, so the shared part is the
+# same token row for every hit by construction: no test of the text is needed.
+GEMMA_RERANK_PROMPT = ("Given a query A and a passage B, determine whether the passage contains an answer to the query by providing a prediction of "
+                       "either 'Yes' or 'No'.")
+
+
+def gemma_rerank_rows(tk, bos_id: int, query: str, docs: Sequence[str], prompt: str, max_length: int, share: bool = True) -> Tuple[np.ndarray, list]:
+    """One query's call as token rows -> (shared int32 [P], segments: list of int32 arrays).  Per pair the reference forms
+        [bos] + ids("A: " + query)[:max_length * 3 // 4] + ids("\\n") + ids("B: " + passage)[:room] + ids("\\n") + ids(prompt)
+    with room = max_length - len([bos] + query ids) - len(ids("\\n")), at least 0: the passage is cut from the right so that shared + "\\n" + passage fits
+    max_length; the second separator and the prompt ride on top of the cap.  Every piece is tokenised on its own, without specials.  share: shared =
+    [bos] + query ids (P >= 1 always), segment = the rest; not share: P = 0 and every segment is the whole pair (the same ids in the same order)."""
+    enc = lambda s: tk.encode(s, add_special_tokens=False).ids
+    q_ids = [int(bos_id)] + enc("A: " + query)[:max_length * 3 // 4]
+    sep, tail = enc("\n"), enc(prompt)
+    room = max(max_length - len(q_ids) - len(sep), 0)
+    rows = tk.encode_batch(["B: " + d for d in docs], add_special_tokens=False)
+    segs = [sep + e.ids[:room] + sep + tail for e in rows]
+    if share:
+        return np.asarray(q_ids, dtype=np.int32), [np.asarray(s, dtype=np.int32) for s in segs]
+    return np.zeros(0, dtype=np.int32), [np.asarray(q_ids + s, dtype=np.int32) for s in segs]
+
+
+def gemma_score_row(cfg: dict, sd: Dict[str, Tensor], tk, W: int, where: str) -> Tensor:
+    """the one fp32 weight row [W] whose dot product with the final hidden state of a pair's last token is the logit.  GemmaForCausalLM (the published
+    form): lm_head.weight[yes], else — Gemma ties them — embed_tokens.weight[yes], UNSCALED (the sqrt(width) belongs to the input side only); yes = the
+    first id of "Yes" encoded without specials.  GemmaForSequenceClassification with one label: score.weight."""
+    arch_names = cfg.get("architectures") or []
+    if "GemmaForSequenceClassification" in arch_names:
+        labels = cfg.get("num_labels", len(cfg["id2label"]) if isinstance(cfg.get("id2label"), dict) else 2)
+        if int(labels) != 1:
+            raise ValueError(f"{where}: num_labels={labels} is not served as a Gemma reranker (only one-logit heads)")
+        return _need(sd, "score.weight", (1, W)).detach().to(torch.float32).reshape(W)
+    if "GemmaForCausalLM" in arch_names:
+        try:
+            ids = tk.encode("Yes", add_special_tokens=False).ids
+        except Exception:       # (a vocabulary without the piece and without an unknown token raises)
+            ids = []
+        if not ids:
+            raise ValueError(f"{where}: tokenizer.json gives no token for 'Yes', which the judgement reads")
+        name = next((k for k in ("lm_head.weight", "model.embed_tokens.weight", "embed_tokens.weight") if k in sd), None)
+        if name is None:
+            raise ValueError(f"{where}: neither lm_head.weight nor embed_tokens.weight is in the checkpoint")
+        return _need(sd, name, (int(cfg["vocab_size"]), W)).detach()[int(ids[0])].to(torch.float32)
+    raise ValueError(f"{where}: architectures={arch_names} is not served as a Gemma reranker (GemmaForCausalLM or GemmaForSequenceClassification)")
+
+
+class GemmaRerankerTower(_PrefixPairScorer, _PackedTextTower):
+    """`GemmaForCausalLM` read as a judge (BAAI/bge-reranker-v2-gemma: the score is the logit of `Yes` at the last token) or
+    `GemmaForSequenceClassification` with one label: the Gemma decoder (csrc/gemma_causal.hip; 256-wide heads, causal and prefix-sharing attention of
+    csrc/attention_gqa256_causal.hip), the final norm on every pair's last token, one fp32 dot product (gemma_score_row).  One query against n documents
+    is ONE mq_score_gemma_pairs call per batch of documents over the rows [shared | segment_1 | ... | segment_n] (gemma_rerank_rows): `[bos] A: query` is
+    computed once per batch, not once per document.  Batching, the longest-first order and max_rows_per_call are _PrefixPairScorer.score_rows'.
+    `instruction` is the prompt behind the passage; score(..., instruction=...) replaces it for one call.  Not an embedder: encode_ids refuses."""
+    family = "gemma_causal"
+    pairs_entry = "mq_score_gemma_pairs"
+
+    def __init__(self, arch: archs.GemmaCausalArch, sd: Dict[str, Tensor], device: str, tokenizer, score_row: Tensor, bos_id: int,
+                 model_max_length: int = 8192, instruction: str = GEMMA_RERANK_PROMPT, precision: str = "bf16"):
+        _PackedTextTower.__init__(self, device)
+        _check_precision(precision, ("bf16",), f"the Gemma reranker runs on bf16 operands only (fp8 is out of scope), got precision {precision!r}")
+        if arch.head_dim != 256:
+            raise ValueError(f"the Gemma reranker runs 256-wide attention heads only (head_dim {arch.head_dim})")
+        if arch.heads < 1 or arch.kv_heads < 1 or arch.heads % arch.kv_heads:
+            raise ValueError(f"heads {arch.heads} must be a multiple of kv_heads {arch.kv_heads}")
+        if arch.width > 2048 or arch.width % 64:
+            raise ValueError(f"the Gemma reranker runs widths that are multiples of 64 up to 2048 (width {arch.width}: the 7B size is not served)")
+        if tuple(score_row.shape) != (arch.width,):
+            raise ValueError(f"the score row must be [{arch.width}], got {tuple(score_row.shape)}")
+        if not 0 <= int(bos_id) < arch.vocab:
+            raise ValueError(f"bos id {bos_id} outside the vocabulary of {arch.vocab}")
+        self.precision, self.arch, self.pooling = precision, arch, "last"
+        self._fp8 = None
+        h, W = self._h, arch.width
+        t = gemma_causal_state_dict(arch, sd)
+        self._layers = (L.GemmaCausalLayer * arch.layers)()
+        for l in range(arch.layers):
+            p = f"layers.{l}."
+            self._layers[l] = L.GemmaCausalLayer(
+                input_norm_g=h.f32(t[p + "input_layernorm.weight"]), qkv_w=h.bf16(t[p + "self_attn.qkv.weight"]),
+                out_w=h.bf16(t[p + "self_attn.o_proj.weight"]), post_norm_g=h.f32(t[p + "post_attention_layernorm.weight"]),
+                ug_w=h.bf16(t[p + "mlp.up_gate.weight"]), down_w=h.bf16(t[p + "mlp.down_proj.weight"]))
+        self.w = L.GemmaCausalWeights(tok_emb=h.f32(t["embed_tokens.weight"]), final_norm_g=h.f32(t["norm.weight"]), zeros=h.f32(torch.zeros(W)),
+                                      d_inv_freq=h.f32(arch.inv_freq()), layers=self._layers)
+        self.cfg = L.GemmaCausalCfg(width=W, layers=arch.layers, q_heads=arch.heads, kv_heads=arch.kv_heads, head_dim=arch.head_dim, mlp_dim=arch.mlp_dim,
+                                    vocab=arch.vocab, max_pos=arch.max_pos, rms_eps=arch.rms_eps, attn_scale=arch.attn_scale)
+        self.score_w = h.f32(score_row)                 # (a device pointer; the holder keeps the tensor)
+        self.tokenizer = tokenizer
+        tokenizer.no_truncation()
+        tokenizer.no_padding()
+        self.bos_id = int(bos_id)
+        self.instruction = instruction
+        self.model_max_length = int(min(model_max_length, arch.max_pos, 8192))
+        self._lock = threading.Lock()
+        self.last_prefix_len = None      # of the latest score(): 0 = it ran unshared
+
+    def encode_ids(self, ids: Tensor, attention_mask: Tensor, normalize: bool = True) -> Tensor:
+        raise ValueError("the Gemma tower is served as a reranker only (Gemma as an embedder is out of scope)")
+
+    @classmethod
+    def from_dir(cls, directory: str, device: str) -> "GemmaRerankerTower":
+        """a local Hugging Face directory: config.json, model.safetensors | pytorch_model.bin, tokenizer.json, tokenizer_config.json"""
+        cfg, sd = checkpoint.load_hf_dir(directory)
+        return cls._from_loaded(directory, cfg, sd, device)
+
+    @classmethod
+    def _from_loaded(cls, directory: str, cfg: dict, sd: Dict[str, Tensor], device: str) -> "GemmaRerankerTower":
+        try:
+            arch = archs.gemma_causal_arch_from_hf_config(cfg)    # (refuses gemma2 / gemma3, the 7B, other head widths, rope scaling ... by key)
+        except KeyError as e:
+            raise ValueError(f"{directory}: config.json has no {e.args[0] if e.args else e}") from e
+        except ValueError as e:
+            raise ValueError(f"{directory}: {e}") from e
+        if not os.path.isfile(os.path.join(directory, "tokenizer.json")):
+            raise ValueError(f"{directory}: a Gemma reranker needs the checkpoint's tokenizer.json, which is not there (GPU tokenisation and "
+                             f"tokenizer.model alone are not served for this family)")
+        from tokenizers import Tokenizer
+        tk = Tokenizer.from_file(os.path.join(directory, "tokenizer.json"))
+        row = gemma_score_row(cfg, sd, tk, arch.width, directory)
+        bos = tk.token_to_id(_special_spellings(directory, bos="<bos>")["bos"])
+        if bos is None:
+            bos = cfg.get("bos_token_id")
+        if bos is None:
+            raise ValueError(f"{directory}: neither the tokenizer's bos token nor config.json's bos_token_id names the first token of a pair")
+        _, max_len = _tokenizer_settings(directory, default_max=8192)
+        return cls(arch, sd, device, tk, row, int(bos), model_max_length=max_len)
+
+    # ---- scoring ----------------------------------------------------------------------------------------------------------------------------
+    def rows_for(self, query: str, docs: Sequence[str], max_length: int = 512, instruction: Optional[str] = None) -> Tuple[np.ndarray, list]:
+        """(shared ids, segments) of one call (gemma_rerank_rows): the host half of score(), no GPU work.  The reference puts the second separator and
+        the prompt on top of max_length; a pair that would then pass the positions the tower serves is refused (a query that alone reaches the cap keeps
+        its 3/4 cut and runs SHARED like any other: the passage is then cut to nothing)."""
+        cap = int(min(max_length, self.model_max_length))
+        if cap < 4:
+            raise ValueError(f"max_length={max_length} must be at least 4")
+        with self._lock:
+            shared, segs = gemma_rerank_rows(self.tokenizer, self.bos_id, query, docs, self.instruction if instruction is None else instruction, cap)
+        longest = int(shared.size) + max(int(s.size) for s in segs)
+        if longest > self.arch.max_pos:
+            raise ValueError(f"a pair of {longest} tokens (max_length={cap} + the separator and the prompt) exceeds the {self.arch.max_pos} positions served")
+        return shared, segs
+
+    def score(self, query: str, docs: Sequence[str], max_length: int = 512, instruction: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (logits, sigmoid(logits)) fp32 [len(docs)] on the host, in the order of `docs`.  Texts are taken as they are."""
+        if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
+            raise TypeError("a cross-encoder scores (str, str) pairs")
+        if len(docs) == 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        shared, segs = self.rows_for(query, docs, max_length, instruction)
+        self.last_prefix_len = int(shared.size)
+        return self.score_rows(shared, segs)
 
 
 def load_cross_encoder_tower(directory: str, device: str):
     """the cross-encoder tower of a local Hugging Face directory, by its config.json: model_type "deberta-v2" -> DebertaCrossEncoderTower.from_dir,
-    "deberta" (v1) is refused here by name, "qwen3" -> QwenRerankerTower.from_dir, everything else -> CrossEncoderTower.from_dir (which picks among BERT,
-    XLM-RoBERTa / RoBERTa and ModernBERT and refuses the rest, "qwen3" included when it is called directly)"""
+    "deberta" (v1) is refused here by name, "qwen3" -> QwenRerankerTower.from_dir, "gemma" -> GemmaRerankerTower.from_dir ("gemma2", "gemma3" and
+    "gemma3_text" are refused there by name), everything else -> CrossEncoderTower.from_dir (which picks among BERT, XLM-RoBERTa / RoBERTa and ModernBERT
+    and refuses the rest, "qwen3" and "gemma" included when it is called directly)"""
     mtype = None
     try:
         with open(os.path.join(directory, "config.json")) as f:
@@ -682,6 +847,8 @@ def load_cross_encoder_tower(directory: str, device: str):
         return DebertaCrossEncoderTower.from_dir(directory, device)
     if mtype == "qwen3":
         return QwenRerankerTower.from_dir(directory, device)
+    if mtype in ("gemma", "gemma2", "gemma3", "gemma3_text"):   # (the later families: gemma_causal_arch_from_hf_config refuses them, naming model_type)
+        return GemmaRerankerTower.from_dir(directory, device)
     return CrossEncoderTower.from_dir(directory, device)
 
 

@@ -503,6 +503,21 @@ def gemma_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     return out
 
 
+def gemma_causal_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' GemmaModel tensors (with or without a `model.` prefix; `lm_head.*` / `score.*` are ignored) -> the fp32 tensors the reranker tower
+    hands to the kernels: qwen_state_dict's names and fusions (no q / k norm, no bias), then every norm weight as 1 + w (GemmaRMSNorm multiplies by
+    1 + weight, the kernels by their weight) and the token table times sqrtf(width) — the fp32 product mq_encode_gemma forms per gathered row, formed
+    once here (the same rounding).  The UNSCALED table is what a tied lm_head reads: engine/rerank.py takes its score row from `sd`, not from here."""
+    if any(k.endswith(".bias") and ".layers." in "." + k for k in sd):
+        raise ValueError("the Gemma reranker tower runs bias-free blocks; this checkpoint carries bias tensors")
+    out = qwen_state_dict(arch, sd)
+    for k in out:
+        if k.endswith("layernorm.weight") or k == "norm.weight":
+            out[k] = 1.0 + out[k]
+    out["embed_tokens.weight"] = out["embed_tokens.weight"] * torch.tensor(float(arch.width) ** 0.5, dtype=torch.float32)
+    return out
+
+
 def t5_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     """transformers' T5EncoderModel / T5Model / T5ForConditionalGeneration tensors -> the fp32 tensors the tower hands to the kernels.  The encoder's keys
     are taken with or without their `encoder.` prefix; the token table is `shared.weight`, else `encoder.embed_tokens.weight` / `embed_tokens.weight`;

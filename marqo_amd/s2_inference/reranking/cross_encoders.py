@@ -46,18 +46,18 @@ class EngineCrossEncoder:
 
     def __init__(self, directory: str, device: str, max_length: int = 512):
         from marqo_amd.engine.rerank import load_cross_encoder_tower
-        self.tower = load_cross_encoder_tower(directory, device)     # (by the directory's model_type: BERT-family towers, the DeBERTa or the Qwen3 tower)
+        self.tower = load_cross_encoder_tower(directory, device)     # (by the directory's model_type: BERT-family towers, the DeBERTa, the Qwen3 or the Gemma tower)
         # (model_utils.py:266-270: a max_length above the tokenizer's model_max_length is lowered to it)
         self.max_length = min(int(max_length), self.tower.model_max_length)
         self.weights_source = directory
 
     def predict(self, inputs: Sequence[Sequence[str]], instruction: Optional[str] = None) -> np.ndarray:
-        """`instruction`: the task description of an instruction-following reranker (the Qwen3 rerankers; None = the tower's default).  A tower
+        """`instruction`: the task description of an instruction-following reranker (the Qwen3 rerankers; the Gemma rerankers' prompt; None = the tower's default).  A tower
         whose template has no instruction refuses one."""
         kw = {}
         if instruction is not None:
             if not hasattr(self.tower, "instruction"):
-                raise ValueError(f"{type(self.tower).__name__} takes no instruction (only the Qwen3 rerankers do)")
+                raise ValueError(f"{type(self.tower).__name__} takes no instruction (only the Qwen3 and Gemma rerankers do)")
             kw["instruction"] = instruction
         scores = np.zeros(len(inputs), dtype=np.float32)
         by_query: Dict[str, List[int]] = {}
@@ -187,8 +187,8 @@ class ReRanker:
 
 class ReRankerText(ReRanker):
     """reranking with a Hugging Face cross-encoder (Bert / XLMRoberta / Roberta / ModernBert / DebertaV2 ForSequenceClassification with one logit) or
-    a Qwen3 reranker (Qwen3ForCausalLM judged by yes / no, or its one-logit conversion); `instruction` (Qwen3 rerankers only) replaces the template's
-    default task description"""
+    a Qwen3 reranker (Qwen3ForCausalLM judged by yes / no, or its one-logit conversion) or a Gemma reranker (GemmaForCausalLM judged by `Yes`, or its
+    one-logit conversion); `instruction` (the Qwen3 and Gemma rerankers only) replaces the template's default task description / prompt"""
 
     def __init__(self, model_name: str, device: str, max_length: int = 512, num_highlights: int = 1,
                  split_params: Optional[Dict] = get_default_text_processing_parameters(), instruction: Optional[str] = None):
