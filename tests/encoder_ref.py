@@ -363,7 +363,7 @@ def _run(cfg: Cfg, blocks: List[dict], x0: Tensor, lens: Sequence[int], form: Op
         last = l == layers - 1
         selected = sel is not None and last
         f8, mlp8 = l >= first8, l >= mlp_from
-        fold, fold_mlp = fold_form and not f8, fold_form and not mlp8
+        fold, fold_mlp = fold_form and not f8, fold_form and not mlp8 and not selected      # (last_block_selected: LN2 + fc1 on the gathered rows, never folded)
         s_attn = s_mlp = None
         if f8form:
             sl = max(l - 1, 0) if kind == "prev_layer_scales" else l
@@ -384,6 +384,8 @@ def _run(cfg: Cfg, blocks: List[dict], x0: Tensor, lens: Sequence[int], form: Op
             qkv = R.b(_linear(deq(h8) if f8 else h, b["qkv_w"], b["qkv_b"], hist))
         else:
             st1 = _stats(x, cfg.eps)
+            if kind == "stats0_neighbour" and l == 0:     # the first block's statistics handed in by the caller (the image tower's stats0), one row off
+                st1 = (torch.roll(st1[0], -1, 0), torch.roll(st1[1], -1, 0))
             if kind == "stale_stats":
                 if l == 0:
                     stale["st1"] = st1

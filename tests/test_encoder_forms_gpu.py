@@ -26,7 +26,8 @@ tests/test_encoder_fp8_forms_gpu.py, which runs them through this file's _Engine
 
 Not covered here:
   - the fixed-pitch selected body (sel_strided_ok) and the `stats0` hand-in: encoder_forward_impl takes both from the image tower only
-    (mq_encode_image_*), where the stream is not observable; they stay with the tower tests.
+    (mq_encode_image_*); tests/test_tower_passes_gpu.py reads the stream and the stats0 region of those calls from the tower's workspace and holds
+    them to the float64 reference of tests/tower_ref.py.
 
 Measured on an MI355X (worst ENCODER_RATIO per form over its cases, all blocks / first block alone; bar 4.0):
   pre_ln/f32 1.55 / 1.75     pre_ln/bf16 1.61 / 1.29     pre_ln/bf16+fold 2.52 / 1.10 (the 768-wide one-workgroup-per-image case 1.54)
@@ -34,6 +35,8 @@ Measured on an MI355X (worst ENCODER_RATIO per form over its cases, all blocks /
   eva/f32 1.43 / 1.21        eva/bf16+fold+glu_epi 1.33 / 1.01     eva/bf16+fold+glu_epi+subln_fold 1.21 / 1.03
   (the folded sub-LayerNorms measured 4.05 against the model of the un-folded ones, in the 24-unit outlier channel: the fold multiplies bf16(g W) with
   the un-normalised rows, a rounding the un-folded model does not make — it went into the model as Form.sub_fold, the margin stayed)
+(encoder_ref no longer folds fc1 in a row-selected last block, as last_block_selected does not: no case of this file selects rows on a folded form, so the
+references of its cases, and with them the figures here, are the same numbers as before)
 Selected rows (mq_encoder_forward_rows, 10 of 217 rows): 1.26 / 1.02 / 1.51 / 2.34 for pre_ln/f32, pre_ln/bf16, post_ln/f32, post_ln_bf16; the other 207
 rows equal the 1-block stream bit for bit in all four.
 
