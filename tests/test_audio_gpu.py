@@ -1,5 +1,6 @@
 """The LanguageBind audio part on the GPU: the three kernels of csrc/audio.hip against the restatements of tests/audio_ref.py, the audio tower
 against the fp32 restatement, and vectorise() end to end on a synthetic `Audio_FT_Image` directory.
+The tower's row-level bars — every stream row against float64 — are in tests/test_languagebind_passes_gpu.py; here it is held at the pooled output.
 
 BOUND of mq_fbank.  The yardstick is what the same formula gives in torch float32 on the CPU (AR.fbank_torch, every step in float32 in torchaudio's
 order): its largest absolute error against the float64 reference on the SAME waveform.  The kernel may err by at most 4 times that.  Both numbers

@@ -1,5 +1,6 @@
 """LanguageBind on the GPU: the three kernels of csrc/temporal.hip against float64 computed from the same inputs, the video tower against the
 restatement (tests/languagebind_ref.py), and vectorise() end to end on a synthetic checkpoint directory.
+The tower's row-level bars — every stream row against float64 — are in tests/test_languagebind_passes_gpu.py; here it is held at the pooled output.
 
 BOUND of mq_temporal_attention.  The kernel keeps its probabilities in fp32 (they are never rounded to bf16: there is no MFMA operand to feed), so
 of the budget tests/attention_ref.py derives for mq_attention, u (P|V| + |out|) with u = 2**-8, the probability term u P|V| does not apply and what
