@@ -1876,6 +1876,53 @@ int mq_score_gemma_pairs(const mq_gemma_causal_cfg* cfg, const mq_gemma_causal_w
                          const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, int64_t nseq, int32_t prefix_len, float* d_logits, float* d_scores,
                          void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mistral / Llama text embedders: causal sliding-window grouped-query attention, row kernels up to 4096 wide and the tower
+ * (csrc/attention_gqa.hip, csrc/llama.hip; engine/llama.py) -------------------------------------------------------------------------------------------------
+ * transformers' MistralModel / LlamaModel (model_type "mistral" / "llama": e5-mistral-7b-instruct, SFR-Embedding-Mistral, Linq-Embed-Mistral, Llama-2-shaped
+ * fine-tunes): mq_encode_qwen's block without q / k norm and without a QKV bias, up to 4096 wide, with Mistral's sliding window.  Additions to ABI 15:
+ * nothing above changes (mq_rmsnorm, mq_embed_tokens, mq_pool, mq_encode_qwen keep their 2048 bound and their refusals); the struct and entry points
+ * below are new.  Each judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and
+ * allocates nothing.
+ *
+ *   mq_attention_gqa_window: mq_attention_gqa's layout and sequence arguments; the query at position i of a sequence sees the keys j of that sequence
+ *                   with i - window < j <= i (transformers' sliding_window_causal_mask_function).  window >= 1; a window of at least the longest
+ *                   sequence gives the bits of mq_attention_gqa with MQ_MASK_CAUSAL.  A 128-query slice stages only the key tiles its band cuts and a
+ *                   16-query block visits only its own: the cost of a long sequence is O(T window).
+ *   mq_rmsnorm_wide: mq_rmsnorm's contract (row gather, bf16 and / or fp32 output, in place on the fp32 rows) for W % 64 == 0, W <= 4096.  W <= 2048:
+ *                   mq_rmsnorm itself (the same bits).
+ *   mq_embed_tokens_wide: d_x fp32 [rows, W] = tok[clamp(id)] over packed sequences: the gather of mq_embed_tokens without positions, types or
+ *                   LayerNorm, W % 64 == 0, W <= 4096.  W <= 2048: mq_embed_tokens itself.
+ *   mq_pool_wide:   mq_pool's MQ_POOL_MEAN (+ L2 as F.normalize forms it) for W % 64 == 0, W <= 4096.  W <= 2048: mq_pool itself.  (The last-token
+ *                   tail is mq_last_rows, mq_rmsnorm_wide through the row index and mq_l2_normalize, which has no width bound.)
+ *   mq_encode_llama: mq_encode_qwen's tower on mq_qwen_weights whose layers carry no qkv_b / q_norm_g / k_norm_g (all three must be NULL), through the
+ *                   wide row kernels.  cfg->window > 0 and smaller than the longest sequence of the call: every layer attends through
+ *                   mq_attention_gqa_window; otherwise through mq_attention_gqa (causal).  width <= 4096 (a multiple of 64), head_dim 64 or 128,
+ *                   mlp_dim % 64 == 0, max_pos <= 8192.  d_out fp32 [nseq, width]. */
+typedef struct mq_llama_cfg {
+    int32_t width;       /* W, multiple of 64, <= 4096 */
+    int32_t layers;
+    int32_t q_heads;     /* Q */
+    int32_t kv_heads;    /* KV, divides Q */
+    int32_t head_dim;    /* hd: 64 or 128; Q hd need not be W */
+    int32_t mlp_dim;     /* F, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;     /* longest sequence served (<= 8192) */
+    int32_t pool;        /* MQ_POOL_LAST or MQ_POOL_MEAN */
+    int32_t window;      /* sliding_window (>= 1), or 0: none */
+    float   rms_eps;
+    int32_t reserved0;   /* 0 */
+} mq_llama_cfg;
+
+int mq_attention_gqa_window(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
+                            int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t window, void* stream);
+int mq_rmsnorm_wide(const float* d_x, const int32_t* d_row_idx, const float* d_g, void* d_out_bf16, float* d_out_f32, int64_t rows, int32_t W, float eps,
+                    void* stream);
+int mq_embed_tokens_wide(const int32_t* d_ids, const int32_t* d_cu, int64_t nseq, const float* tok, float* d_x, int32_t W, int32_t vocab, void* stream);
+int mq_pool_wide(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_out, int32_t W, int32_t normalize, void* stream);
+size_t mq_llama_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
+                    int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

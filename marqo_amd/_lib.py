@@ -33,7 +33,7 @@ ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
 MQ_MASK_NONE, MQ_MASK_CAUSAL, MQ_MASK_CAUSAL_CLS = 0, 1, 2
-MQ_POOL_MEAN, MQ_POOL_CLS, MQ_POOL_LAST = 0, 1, 2   # (MQ_POOL_LAST: mq_encode_qwen only)
+MQ_POOL_MEAN, MQ_POOL_CLS, MQ_POOL_LAST = 0, 1, 2   # (MQ_POOL_LAST: mq_encode_qwen / mq_encode_llama only)
 MQ_VIT_POOL_CLS, MQ_VIT_POOL_MAP, MQ_VIT_POOL_AVG, MQ_VIT_POOL_QUERY = 0, 1, 2, 3
 MQ_EPI_BIAS, MQ_EPI_GELU, MQ_EPI_QUICKGELU, MQ_EPI_RESIDUAL, MQ_EPI_OUT_F32, MQ_EPI_OUT_FP8 = 1, 2, 4, 8, 16, 32
 MQ_EPI_ROW_STATS, MQ_EPI_LN_APPLY = 64, 128
@@ -226,6 +226,12 @@ class QwenWeights(C.Structure):
 class QwenCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
                 ("vocab", C.c_int32), ("max_pos", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float)]
+
+
+class LlamaCfg(C.Structure):
+    """mq_llama_cfg: the Mistral / Llama tower (csrc/llama.hip); its weights are QwenWeights / QwenLayer without qkv_b, q_norm_g, k_norm_g"""
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
+                ("vocab", C.c_int32), ("max_pos", C.c_int32), ("pool", C.c_int32), ("window", C.c_int32), ("rms_eps", C.c_float), ("reserved0", C.c_int32)]
 
 
 class GemmaLayer(C.Structure):
@@ -564,6 +570,14 @@ _SIGNATURES = {
     "mq_score_gemma_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(GemmaCausalCfg), C.c_int64, C.c_int64]),
     "mq_score_gemma_pairs": (C.c_int, [C.POINTER(GemmaCausalCfg), C.POINTER(GemmaCausalWeights), _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P,
                                        C.c_size_t, _P]),
+    # Mistral / Llama text embedders: causal sliding-window grouped-query attention, the row kernels up to 4096 wide, the tower
+    # (csrc/attention_gqa.hip, csrc/llama.hip; engine/llama.py)
+    "mq_attention_gqa_window": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_rmsnorm_wide": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
+    "mq_embed_tokens_wide": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P]),
+    "mq_pool_wide": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P]),
+    "mq_llama_workspace_bytes": (C.c_size_t, [C.POINTER(LlamaCfg), C.c_int64, C.c_int64]),
+    "mq_encode_llama": (C.c_int, [C.POINTER(LlamaCfg), C.POINTER(QwenWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune":(C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

@@ -19,12 +19,17 @@ import torch
 from marqo_amd import _lib as L
 
 RAW, NORMALIZE, NORMALIZE_IF_NONZERO = L.MQ_COMBINE_RAW, L.MQ_COMBINE_NORMALIZE, L.MQ_COMBINE_NORMALIZE_IF_NONZERO
+MAX_DIM = 2048   # mq_weighted_combine's bound on D (csrc/combine.hip); wider embeddings are refused here, by name, in front of the library call
 
 
 def combine_weighted(embeddings: Union[np.ndarray, torch.Tensor], groups: Sequence[Sequence[Tuple[int, float]]], mode: int,
                      device: str = "cuda") -> torch.Tensor:
     """embeddings fp32 [n, D] (ndarray, or a tensor already on `device`); groups[g] = [(row, weight), ...].
     Returns the combined fp32 [len(groups), D] tensor on `device` (async on the current stream)."""
+    if getattr(embeddings, "ndim", 0) == 2 and embeddings.shape[1] > MAX_DIM:
+        raise ValueError(f"combine_weighted: embeddings of {embeddings.shape[1]} dimensions are not served: the combination kernel (mq_weighted_combine) "
+                         f"takes at most {MAX_DIM}.  Models wider than that (the 4096-wide Mistral / Llama embedders) embed single fields and queries; "
+                         f"weighted multimodal fields and weighted multi-term queries are not available for them")
     dev = torch.device(device)
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise L.MarqoHipUnavailableError(f"combine_weighted needs a cuda device (got {device!r}); there is no CPU fallback")

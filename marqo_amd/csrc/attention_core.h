@@ -107,6 +107,22 @@ __device__ __forceinline__ void attn_mask_band(f32x4 (&sc)[4], int kt, int g, in
     }
 }
 
+// Causal band q - window < key <= q (Mistral's sliding window): a tile at or behind the block's first query, inside the sequence, and at or past the
+// lowest key the block's LAST query sees is interior.  With window >= len no key is cut below, and what is left is attn_mask_causal<MQ_MASK_CAUSAL>.
+__device__ __forceinline__ void attn_mask_causal_window(f32x4 (&sc)[4], int kt, int nkt, int g, int q, int qb0, int window, int len) {
+    const bool need_mask = ((kt == nkt - 1) && (len & 63)) || (kt * 64 + 63 > qb0) || (kt * 64 <= qb0 + 15 - window);
+    if (need_mask) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = kt * 64 + t * 16 + g * 4 + r;
+                const bool valid = key < len && key <= q && key > q - window;
+                sc[t][r] = valid ? sc[t][r] : -INFINITY;
+            }
+    }
+}
+
 // ---- online-softmax step: sc becomes the tile's probabilities relative to the new running max.  The max runs on the RAW scores (the softmax scale is
 // positive); scale and shift fold into one FMA per element.  A query that sees no key of this tile keeps m_run (from -1e30): its probabilities here are
 // exp2(-inf) = 0 and alpha = 1.  o and l_run are rescaled only when some query's running max moved (rare after the first tiles).

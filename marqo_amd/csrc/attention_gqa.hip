@@ -260,6 +260,133 @@ int launch_gqa_prefix(const void* d_qkv, void* d_out, const int32_t* d_cu, int64
     return MQ_OK;
 }
 
+// ---- causal sliding-window form (Mistral-7B-v0.1's sliding_window: transformers masking_utils, sliding_window_overlay AND causal_mask_function) -------
+// The query at position i of a sequence sees the keys j with i - window < j <= i.  The work split is attention_gqa_kernel's; what differs is the LOWER
+// end of what a slice stages and a block walks:
+//
+//   - the slice [q0, q_last] stages the key tiles [st0, skt): st0 = the tile of key max(0, q0 - window + 1), skt as under the causal mask — at most
+//     2 + ceil((window - 1) / 64) tiles, which is what the entry point sizes kpad by, so a long sequence costs O(T window), not O(T^2);
+//   - a 16-query block visits the tiles [kt_begin, kt_end): kt_begin = the tile of key max(0, qb0 - window + 1), kt_end as under the causal mask;
+//   - the tiles that cut the band — above (the diagonal), below (the first tile or two of the block), the ragged last — are masked per key.
+//
+// The tiles of a block that lie below the band of its LATER queries give those queries no key: attn_softmax_step keeps m_run = -1e30 for them, their
+// probabilities are exp2(-inf) = 0, and the first tile with a key rescales the empty accumulators by exp2(-huge) = 0.  With window >= len: st0 = 0 and
+// kt_begin = 0, and every statement below reduces to attention_gqa_kernel<MQ_MASK_CAUSAL>'s, in its order (bit-identical output).
+template <int HD>
+__global__ __launch_bounds__(GQA_NW * 64) void attention_gqa_window_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, const int32_t* __restrict__ cu,
+                                                                           int fixed_len, int q_heads, int kv_heads, int nslices, int kpad, int window,
+                                                                           float scale_log2e) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RB = HD * 2;
+    constexpr int NC = HD / 8;
+    constexpr int NKK = HD / 32;
+    constexpr int NDT = HD / 16;
+    char* sK = smem;
+    char* sV = smem + (size_t)kpad * RB;
+
+    const unsigned sk = blockIdx.x / (unsigned)nslices;
+    const int slice = (int)(blockIdx.x - sk * (unsigned)nslices);
+    const int seq = sk / kv_heads, kvh = sk - seq * kv_heads;
+    int row0, len;
+    if (fixed_len > 0) { row0 = seq * fixed_len; len = fixed_len; }
+    else { row0 = cu[seq]; len = cu[seq + 1] - row0; }
+    const int q0 = slice * GQA_SLICE;
+    if (len <= 0 || q0 >= len) return;     // (the whole workgroup: no barrier has been reached)
+    const int G = q_heads / kv_heads;
+    const int ld = (q_heads + 2 * kv_heads) * HD, ldo = q_heads * HD;
+    const bf16_t* qrow = qkv + (int64_t)row0 * ld;
+    const bf16_t* kb = qrow + (q_heads + kvh) * HD;
+    const bf16_t* vb = kb + kv_heads * HD;
+    const int nkt = (len + 63) >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    // the slice: its 16-query blocks, the key tiles [st0, skt) it stages, the pieces they pass through the LDS in
+    const int q_last = q0 + GQA_SLICE - 1 < len - 1 ? q0 + GQA_SLICE - 1 : len - 1;
+    const int nblk = ((q_last - q0) >> 4) + 1;
+    const int st0 = q0 - window + 1 > 0 ? (q0 - window + 1) >> 6 : 0;
+    const int skt = (q_last >> 6) + 1;
+    const int tpc = kpad >> 6;
+    const int nchunks = (skt - st0 + tpc - 1) / tpc;
+    const int nitems = G * nblk;
+    const int nrounds = (nitems + GQA_NW - 1) / GQA_NW;
+    auto stage = [&](int c) {
+        const int t0 = st0 + c * tpc;
+        const int tiles_here = skt - t0 < tpc ? skt - t0 : tpc;
+        attn_stage_piece<RB, NC, NC - 1, GQA_NW>(sK, sV, kb, vb, ld, t0 << 6, tiles_here << 6, len, lane, wave);
+    };
+    if (nchunks == 1) {
+        stage(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+
+    const int l15 = lane & 15, g = lane >> 4;
+    const int vkey = 4 * g + (l15 >> 2);
+    const int vcol = (l15 & 3) >> 1, vhalf = (l15 & 1) << 3;
+
+    for (int rnd = 0; rnd < nrounds; ++rnd) {
+        const int item = rnd * GQA_NW + wave;
+        const bool active = item < nitems;       // wave-uniform; with nchunks > 1 an idle wave still stages and keeps the barriers
+        if (nchunks == 1 && !active) break;
+        const int gh = active ? item / nblk : 0;
+        int blk = active ? item - gh * nblk : 0;
+        if (gh & 1) blk = nblk - 1 - blk;
+        const int h = kvh * G + gh;
+        const int qb0 = q0 + blk * 16;
+        const int q = qb0 + l15;
+        bf16x8 qf[NKK];
+        {
+            const int qr = q < len ? q : len - 1;
+#pragma unroll
+            for (int kk = 0; kk < NKK; ++kk) qf[kk] = *(const bf16x8*)(qrow + (int64_t)qr * ld + h * HD + 8 * g + 32 * kk);
+        }
+
+        float m_run = -1e30f, l_run = 0.f;
+        f32x4 o[NDT];
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        const int kt_begin = qb0 - window + 1 > 0 ? (qb0 - window + 1) >> 6 : 0;   // the tile of the lowest key the block's first query sees (>= st0)
+        const int last = (qb0 + 15) >> 6;                                          // the tile of the block's last query
+        const int kt_end = last + 1 < skt ? last + 1 : skt;
+        for (int c = 0; c < nchunks; ++c) {
+            if (nchunks > 1) {   // (re)fill the LDS with key tiles [st0 + c tpc, st0 + (c + 1) tpc) of the slice
+                __syncthreads();
+                stage(c);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+            const int kt0 = st0 + c * tpc;
+            const int ks = kt_begin > kt0 ? kt_begin : kt0;
+            const int ke = !active ? ks : (kt_end < kt0 + tpc ? kt_end : kt0 + tpc);
+            const int cb = kt0 << 6;                         // LDS row of global key `key` is key - cb (cb is a multiple of 64)
+            for (int kt = ks; kt < ke; ++kt) {
+                f32x4 sc[4];
+                attn_score_tile<RB, NKK, NC - 1>(sK, kt, cb, l15, g, qf, sc);
+                attn_mask_causal_window(sc, kt, nkt, g, q, qb0, window, len);
+                attn_softmax_step<NDT>(sc, m_run, l_run, o, scale_log2e);
+                attn_pv_tile<RB, NDT, NC - 1>(sV, kt, cb, vkey, vcol, vhalf, sc, o);
+            }
+        }  // pieces
+        if (!active) continue;
+        const float inv = attn_inv_denominator(l_run);
+        if (q < len) attn_store_bf16<NDT>(out + (int64_t)(row0 + q) * ldo + h * HD + 4 * g, o, inv);
+    }
+}
+
+template <int HD>
+int launch_gqa_window(const void* d_qkv, void* d_out, const int32_t* d_cu, int64_t nseq, int fixed_len, int q_heads, int kv_heads, int nslices, int kpad,
+                      int window, hipStream_t s) {
+    const size_t lds = (size_t)kpad * HD * 4;
+    static std::atomic<uint64_t> done{0};
+    const int rc = attn_ensure_lds((const void*)attention_gqa_window_kernel<HD>, lds, 160 * 1024, done, "mq_attention_gqa_window");
+    if (rc != MQ_OK) return rc;
+    const float scale_log2e = 1.44269504088896340736f / sqrtf((float)HD);
+    hipLaunchKernelGGL((attention_gqa_window_kernel<HD>), dim3((unsigned)(nseq * kv_heads * nslices)), dim3(GQA_NW * 64), lds, s, (const bf16_t*)d_qkv,
+                       (bf16_t*)d_out, d_cu, fixed_len, q_heads, kv_heads, nslices, kpad, window, scale_log2e);
+    return MQ_OK;
+}
+
 }  // namespace
 
 // d_qkv bf16 [rows, (q_heads + 2 kv_heads) head_dim] = (q | k | v), head h of each part at columns h head_dim ..; d_out bf16 [rows, q_heads head_dim];
@@ -314,5 +441,33 @@ extern "C" int mq_attention_gqa_prefix(const void* d_qkv, void* d_out, const int
                                   : launch_gqa_prefix<128>(d_qkv, d_out, d_cu_seqlens, nseq, prefix_len, q_heads, kv_heads, nslices, kpad, s);
     if (rc != MQ_OK) return rc;
     MQ_CHECK_LAUNCH("mq_attention_gqa_prefix");
+    return MQ_OK;
+}
+
+// The causal sliding-window form: mq_attention_gqa's layout and sequence arguments; query i of a sequence sees the keys j with i - window < j <= i.
+// window >= the longest sequence: the bits of mq_attention_gqa with MQ_MASK_CAUSAL.
+extern "C" int mq_attention_gqa_window(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
+                                       int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t window, void* stream) {
+    ATTN_ARG_PTRS("mq_attention_gqa_window", d_qkv, d_out);
+    MQ_CHECK_ARG(head_dim == 64 || head_dim == 128, "mq_attention_gqa_window: head_dim %d unsupported (64 or 128)", head_dim);
+    ATTN_ARG_GROUPS("mq_attention_gqa_window", q_heads, kv_heads);
+    MQ_CHECK_ARG(window >= 1, "mq_attention_gqa_window: window %d must be at least 1 (a query sees itself)", window);
+    ATTN_ARG_SEQS("mq_attention_gqa_window", fixed_len, d_cu_seqlens);
+    if (nseq <= 0) return MQ_OK;
+    const int maxl = fixed_len > 0 ? fixed_len : max_len;
+    ATTN_ARG_MAXL("mq_attention_gqa_window", maxl);
+    const int nslices = (maxl + GQA_SLICE - 1) / GQA_SLICE;
+    ATTN_ARG_GRID("mq_attention_gqa_window", nseq * kv_heads * nslices);
+    // (a window past the longest sequence cuts nothing: clamped, the kernel's position arithmetic stays far inside int32)
+    const int w = window < maxl ? window : maxl;
+    // a slice's band spans at most 2 + ceil((w - 1) / 64) key tiles (its own two and what the window reaches below them), never more than the sequence
+    const int band = (2 + (w - 1 + 63) / 64) * 64;
+    const int kpad = attn_kpad(band < maxl ? band : maxl, head_dim == 64 ? 640 : 320);
+    hipStream_t s = (hipStream_t)stream;
+    MqProfScope prof(2, s);
+    const int rc = head_dim == 64 ? launch_gqa_window<64>(d_qkv, d_out, d_cu_seqlens, nseq, fixed_len, q_heads, kv_heads, nslices, kpad, w, s)
+                                  : launch_gqa_window<128>(d_qkv, d_out, d_cu_seqlens, nseq, fixed_len, q_heads, kv_heads, nslices, kpad, w, s);
+    if (rc != MQ_OK) return rc;
+    MQ_CHECK_LAUNCH("mq_attention_gqa_window");
     return MQ_OK;
 }

@@ -1,6 +1,6 @@
 // Host scaffold of the entry points that take packed token sequences (ids [rows] + cu_seqlens): the workspace bump helper, the sequence-length walk, the
 // checks in front of the first launch and the cfg checks the decoder-style towers share.  Host code only: no kernel lives here.
-// Users: modernbert.hip, qwen.hip, gemma.hip (all of it), towers.hip (mq_encode_bert, mq_encode_clip_text) and rerank.hip (score_pairs).
+// Users: modernbert.hip, qwen.hip, llama.hip, gemma.hip (all of it), towers.hip (mq_encode_bert, mq_encode_clip_text) and rerank.hip (score_pairs).
 #pragma once
 #include "common.h"
 

@@ -304,6 +304,21 @@ void attention_gqa256_prefix(const at::Tensor& qkv, const at::Tensor& cu_seqlens
              "mq_attention_gqa256_prefix");
 }
 
+// the Mistral / Llama towers' attention (csrc/attention_gqa.hip): causal inside a sliding window, query i sees the keys j with i - window < j <= i.
+// cu_seqlens int32 [nseq + 1] on the device; `out` bf16 [rows, q_heads head_dim]
+void attention_gqa_window(const at::Tensor& qkv, const at::Tensor& cu_seqlens, int64_t max_len, int64_t q_heads, int64_t kv_heads, int64_t head_dim,
+                          int64_t window, at::Tensor out) {
+    need_dev(qkv, at::kBFloat16, "qkv");
+    need_dev(out, at::kBFloat16, "out");
+    need_dev(cu_seqlens, at::kInt, "cu_seqlens");
+    TORCH_CHECK(q_heads >= 1 && kv_heads >= 1 && head_dim >= 1 && qkv.dim() == 2 && out.dim() == 2 && cu_seqlens.numel() >= 1 &&
+                qkv.size(1) == (q_heads + 2 * kv_heads) * head_dim && out.size(0) == qkv.size(0) && out.size(1) == q_heads * head_dim,
+                "marqo_hip::mq_attention_gqa_window: qkv [rows, (Q + 2 KV) hd], out [rows, Q hd], cu_seqlens [nseq + 1]");
+    TORCH_CHECK(window >= 1 && window <= INT32_MAX, "marqo_hip::mq_attention_gqa_window: window must be in [1, 2^31)");
+    check_rc(mq_attention_gqa_window(qkv.data_ptr(), out.data_ptr(), (const int32_t*)cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, 0, (int32_t)max_len,
+                                     (int32_t)q_heads, (int32_t)kv_heads, (int32_t)head_dim, (int32_t)window, stream_of(qkv)), "mq_attention_gqa_window");
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -330,6 +345,8 @@ TORCH_LIBRARY(marqo_hip, m) {
           "Tensor? k_norm, float eps, Tensor inv_freq, int offset) -> ()");
     m.def("mq_attention_gqa256_prefix(Tensor qkv, Tensor cu_seqlens, int prefix_len, int max_len, int q_heads, int kv_heads, int head_dim, float scale, "
           "Tensor(a!) out) -> ()");
+    m.def("mq_attention_gqa_window(Tensor qkv, Tensor cu_seqlens, int max_len, int q_heads, int kv_heads, int head_dim, int window, "
+          "Tensor(a!) out) -> ()");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -349,4 +366,5 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_attention_gqa_prefix", &attention_gqa_prefix);
     m.impl("mq_qk_norm_rope_at", &qk_norm_rope_at);
     m.impl("mq_attention_gqa256_prefix", &attention_gqa256_prefix);
+    m.impl("mq_attention_gqa_window", &attention_gqa_window);
 }

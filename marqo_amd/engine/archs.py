@@ -370,6 +370,75 @@ def qwen_arch_from_hf_config(cfg: dict) -> QwenArch:
 
 
 @dataclass(frozen=True)
+class LlamaArch:
+    """transformers' MistralModel / LlamaModel (model_type "mistral" / "llama") as the engine runs them: QwenArch's block without q / k norm and without
+    biases, up to 4096 wide.  window: Mistral's sliding_window — query i sees the keys j with i - window < j <= i — or None (no window: Llama, and the
+    Mistral checkpoints whose config says null).  The defaults are Mistral-7B-v0.1's."""
+    vocab: int = 32000
+    max_pos: int = 8192
+    width: int = 4096
+    layers: int = 32
+    heads: int = 32
+    kv_heads: int = 8
+    head_dim: int = 128
+    mlp_dim: int = 14336
+    rms_eps: float = 1e-5
+    rope_theta: float = 10000.0
+    window: Optional[int] = 4096
+    qk_norm = False        # (the two switches tower_weights.qwen_state_dict reads: the tensors are Qwen's, minus the q / k norms and the biases)
+    qkv_bias = False
+
+    inv_freq = QwenArch.inv_freq
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F, A = tokens, self.width, self.mlp_dim, self.heads * self.head_dim
+        keys = min(T, self.window) if self.window else T
+        layer = 2 * T * W * (A + 2 * self.kv_heads * self.head_dim) + 2 * T * A * W + 2 * 3 * T * W * F + 4 * T * keys * A - 2 * keys * keys * A
+        return self.layers * layer / 1e9
+
+
+def llama_arch_from_hf_config(cfg: dict) -> LlamaArch:
+    """A local Mistral / Llama `config.json` -> LlamaArch.  rope_theta comes from `rope_parameters`, else the older top-level key.  Refused, each by the
+    name of its key: rope_scaling or a non-default rope_type (Llama-3.1's llama3 scaling among them), hidden_act other than silu, attention_bias,
+    mlp_bias, head_dim other than 64 / 128, hidden_size above 4096 or no multiple of 64, intermediate_size no multiple of 64, a sliding_window below 1.
+    `sliding_window` null or absent: no window.  bert_arch_from_hf_config does not route here — it keeps refusing the two model types for the callers
+    that run BERT-family encoders only (the cross-encoders); the `hf` loader selects them before it calls."""
+    mtype = cfg.get("model_type")
+    if mtype not in ("mistral", "llama"):
+        raise KeyError(f"model_type={mtype} is not a Mistral / Llama model")
+    if cfg.get("hidden_act", "silu") != "silu":
+        raise KeyError(f"hidden_act={cfg.get('hidden_act')} unsupported (silu only)")
+    rp = cfg.get("rope_parameters") or {}
+    rtype = rp.get("rope_type", rp.get("type", "default"))
+    if rtype != "default":
+        raise KeyError(f"rope_parameters.rope_type={rtype} unsupported (default only)")
+    if cfg.get("rope_scaling"):
+        raise KeyError(f"rope_scaling={cfg.get('rope_scaling')} unsupported")
+    if cfg.get("attention_bias", False):
+        raise KeyError("attention_bias=true unsupported (bias-free projections only)")
+    if cfg.get("mlp_bias", False):
+        raise KeyError("mlp_bias=true unsupported (bias-free MLP only)")
+    W, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    kv = int(cfg.get("num_key_value_heads") or heads)
+    if heads < 1 or kv < 1 or heads % kv:
+        raise KeyError(f"num_attention_heads={heads} must be a multiple of num_key_value_heads={kv}")
+    hd = int(cfg.get("head_dim") or W // heads)
+    if hd not in (64, 128):
+        raise KeyError(f"head_dim={hd} unsupported (64 or 128)")
+    if W > 4096 or W % 64:
+        raise KeyError(f"hidden_size={W} unsupported (a multiple of 64 up to 4096)")
+    F = int(cfg["intermediate_size"])
+    if F % 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    window = cfg.get("sliding_window")
+    if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
+        raise KeyError(f"sliding_window={window} unsupported (a positive integer or null)")
+    return LlamaArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 8192)), 8192), width=W, layers=layers, heads=heads,
+                     kv_heads=kv, head_dim=hd, mlp_dim=F, rms_eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                     rope_theta=float(rp.get("rope_theta", cfg.get("rope_theta", 10000.0))), window=window)
+
+
+@dataclass(frozen=True)
 class GemmaArch:
     """transformers' Gemma3TextModel with use_bidirectional_attention (model_type "gemma3_text": google/embeddinggemma-300m and its fine-tunes) as the
     engine runs it: blocks with an RMSNorm in front of and behind each sub-layer (weights applied as 1 + w), `kv_heads` K/V heads of width 256 shared by

@@ -27,6 +27,8 @@ from marqo_amd.s2_inference.enums import EnvVars
 
 OPEN_CLIP_FILES = ("open_clip_model.safetensors", "open_clip_pytorch_model.bin", "model.safetensors", "pytorch_model.bin")
 HF_WEIGHT_FILES = ("model.safetensors", "pytorch_model.bin")
+HF_SHARD_INDEX = "model.safetensors.index.json"     # sharded checkpoints (the 7B sizes): {"weight_map": {tensor name: shard file}}
+HF_PICKLE_SHARD_INDEX = "pytorch_model.bin.index.json"
 
 
 def synthetic_weights_enabled() -> bool:
@@ -99,16 +101,55 @@ def find_hf_dir(name: str) -> Optional[str]:
     candidates = [name, os.path.join(model_dir(), "hf", *name.split("/")), os.path.join(model_dir(), *name.split("/"))]
     candidates += _hub_cache_dirs(name)
     for d in candidates:
-        if os.path.isdir(d) and os.path.isfile(os.path.join(d, "config.json")) and _first_existing(d, HF_WEIGHT_FILES):
+        if os.path.isdir(d) and os.path.isfile(os.path.join(d, "config.json")) and _first_existing(d, HF_WEIGHT_FILES + (HF_SHARD_INDEX, HF_PICKLE_SHARD_INDEX)):
             return d
     return None
 
 
-def load_hf_dir(directory: str):
+class ShardedCheckpointError(ValueError):
+    """a sharded checkpoint that cannot be read as its index describes it: a missing shard, a tensor that is not where the index places it, torch-pickle shards"""
+
+
+def load_sharded_state_dict(directory: str, device: Optional[str] = None) -> Dict[str, torch.Tensor]:
+    """model.safetensors.index.json -> flat {name: tensor}: the shards its weight_map names are read one after the other, each shard's tensors moved to
+    `device` (None: they stay on the host) before the next is opened, so the host never holds more than one shard.  A shard the index names but the
+    directory lacks, and a tensor the index places in a shard that does not hold it, are ShardedCheckpointErrors that name the file."""
+    from safetensors.torch import load_file
+    index_path = os.path.join(directory, HF_SHARD_INDEX)
+    with open(index_path) as f:
+        weight_map = json.load(f).get("weight_map")
+    if not isinstance(weight_map, dict) or not weight_map:
+        raise ShardedCheckpointError(f"{index_path}: no weight_map")
+    sd: Dict[str, torch.Tensor] = {}
+    for shard in sorted(set(weight_map.values())):
+        path = os.path.join(directory, shard)
+        if not os.path.isfile(path):
+            raise ShardedCheckpointError(f"{index_path} names the shard {shard}, which is missing from {directory}")
+        part = load_file(path, device="cpu")
+        for name, file in weight_map.items():
+            if file != shard:
+                continue
+            if name not in part:
+                raise ShardedCheckpointError(f"{index_path} places {name} in {shard}, which does not hold it")
+            sd[name] = part[name] if device is None else part[name].to(device)
+        del part
+    if sd and all(k.startswith("module.") for k in sd):
+        sd = {k[len("module."):]: v for k, v in sd.items()}
+    return sd
+
+
+def load_hf_dir(directory: str, device: Optional[str] = None):
+    """(config.json, state dict) of a checkpoint directory: the single weight file as it always was, else the shards of model.safetensors.index.json
+    (`device`: where a sharded checkpoint's tensors go, shard by shard).  A directory with only pytorch_model.bin.index.json is refused."""
     with open(os.path.join(directory, "config.json")) as f:
         cfg = json.load(f)
-    sd = load_state_dict(_first_existing(directory, HF_WEIGHT_FILES))
-    return cfg, sd
+    single = _first_existing(directory, HF_WEIGHT_FILES)
+    if single:
+        return cfg, load_state_dict(single)
+    if os.path.isfile(os.path.join(directory, HF_SHARD_INDEX)):
+        return cfg, load_sharded_state_dict(directory, device)
+    raise ShardedCheckpointError(f"{directory} holds a sharded torch-pickle checkpoint ({HF_PICKLE_SHARD_INDEX}), which is not read: bring it as safetensors shards "
+                     f"({HF_SHARD_INDEX})")
 
 
 def read_pooling_config(directory: Optional[str]) -> Optional[str]:

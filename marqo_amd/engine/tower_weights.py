@@ -441,12 +441,12 @@ def modernbert_head_tensors(sd: Dict[str, Tensor], W: int, classifier_bias: bool
             f32("head.norm.bias", (W,)) if norm_bias else None, f32("classifier.weight", (1, W)), f32("classifier.bias", (1,)))
 
 
-def qwen_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+def qwen_state_dict(arch, sd: Dict[str, Tensor], tower: str = "Qwen") -> Dict[str, Tensor]:
     """transformers' Qwen3Model / Qwen2Model tensors (with or without a `model.` prefix; `lm_head.*` of the causal-LM classes is ignored) -> the fp32
     tensors the tower hands to the kernels.  Per layer the three projections are fused into `layers.N.self_attn.qkv.weight` [(Q + 2 KV) hd, W] = rows
     q_proj | k_proj | v_proj (and `.bias` when arch.qkv_bias), and the MLP's two input projections into `layers.N.mlp.up_gate.weight` [2F, W] = rows
     up_proj | gate_proj — mq_glu computes up * silu(gate) from (up | gate), the module down_proj(silu(gate_proj(x)) * up_proj(x)).  Everything else keeps the
-    checkpoint's name."""
+    checkpoint's name.  `tower` names the family in the messages (the Mistral / Llama tower runs the same transform)."""
     if "embed_tokens.weight" not in sd and "model.embed_tokens.weight" in sd:
         sd = {k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")}
     W, F, hd = arch.width, arch.mlp_dim, arch.head_dim
@@ -459,7 +459,7 @@ def qwen_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
         if not arch.qkv_bias and any((a + n + "_proj.bias") in sd for n in "qkv"):
             raise ValueError(f"{a}*_proj.bias present but the config says attention_bias=false")
         if (a + "o_proj.bias") in sd:
-            raise ValueError(f"{a}o_proj.bias: the Qwen tower runs a bias-free output projection")
+            raise ValueError(f"{a}o_proj.bias: the {tower} tower runs a bias-free output projection")
         out[p + "input_layernorm.weight"] = f32(p + "input_layernorm.weight", (W,))
         out[a + "qkv.weight"] = torch.cat([f32(a + "q_proj.weight", (A, W)), f32(a + "k_proj.weight", (KVW, W)), f32(a + "v_proj.weight", (KVW, W))], 0)
         if arch.qkv_bias:

@@ -55,7 +55,7 @@ class HuggingFaceModelProperties:
         pm = p.get("pooling_method", p.get("poolingMethod"))
         if pm is not None and pm not in ("mean", "cls", "last"):
             raise ValueError(self.POOLING_ERROR)
-        # None: inferred at load from 1_Pooling/config.json, default mean.  'last' (last-token pooling) is taken by the Qwen3 / Qwen2 checkpoints only:
+        # None: inferred at load from 1_Pooling/config.json, default mean.  'last' (last-token pooling) is taken by the decoder-style checkpoints (Qwen3 / Qwen2, Mistral / Llama) only:
         # the other families refuse it at load with the same text
         self.pooling_method: Optional[str] = pm
         self.trust_remote_code: bool = bool(p.get("trust_remote_code", p.get("trustRemoteCode", False)))
@@ -125,9 +125,13 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                                  "engine; unpack the archive on disk and pass its directory as 'name'")
         directory = checkpoint.find_hf_dir(props.name)
         if directory is not None:
-            cfg, sd = checkpoint.load_hf_dir(directory)
+            try:   # (a sharded checkpoint's tensors go to the device shard by shard)
+                cfg, sd = checkpoint.load_hf_dir(directory, device=self.device)
+            except checkpoint.ShardedCheckpointError as e:   # a shard the index names is missing, torch-pickle shards (single-file directories: as before)
+                raise ModelLoadError(f"{props.name}: {e}") from e
             try:
-                arch = archs.bert_arch_from_hf_config(cfg)
+                # (Mistral / Llama are selected here: bert_arch_from_hf_config keeps refusing them for the callers that run BERT-family encoders only)
+                arch = archs.llama_arch_from_hf_config(cfg) if cfg.get("model_type") in ("mistral", "llama") else archs.bert_arch_from_hf_config(cfg)
             except KeyError as e:
                 raise InvalidModelPropertiesError(f"{props.name}: {e}. Only BERT-family encoders run on the marqo_amd engine.") from e
             if isinstance(arch, archs.ModernBertArch):
@@ -135,6 +139,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 return
             if isinstance(arch, archs.QwenArch):
                 self._load_qwen(directory, arch, cfg, sd)
+                return
+            if isinstance(arch, archs.LlamaArch):
+                self._load_llama(directory, arch, cfg, sd)
                 return
             if isinstance(arch, archs.GemmaArch):
                 self._load_gemma(directory, arch, sd)
@@ -270,11 +277,24 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         """a transformers Qwen3Model / Qwen2Model checkpoint (model_type "qwen3" / "qwen2": Qwen3-Embedding-0.6B, gte-Qwen2-1.5B-instruct ...; AutoModel in
         the reference): host tokenisation by the `tokenizers` library from the directory's tokenizer.json with the file's own post-processor, the tower
         of engine/qwen.py.  Pooling: the property, else 1_Pooling/config.json (last token / mean), else last token.  bf16 operands only."""
-        import json
         from marqo_amd.engine.qwen import QwenTower
+        self._load_decoder(directory, arch, cfg, sd, QwenTower, "Qwen3 / Qwen2 encoders")
+
+    def _load_llama(self, directory: str, arch, cfg: dict, sd) -> None:
+        """a transformers MistralModel / LlamaModel checkpoint (model_type "mistral" / "llama": e5-mistral-7b-instruct, SFR-Embedding-Mistral,
+        Linq-Embed-Mistral ...; AutoModel in the reference), loaded as the Qwen checkpoints are: the file's own post-processor decides what is appended
+        to a text (the </s> that e5-mistral's model card appends by hand is the caller's business unless tokenizer.json adds it), the tower of
+        engine/llama.py.  Pooling: the property, else 1_Pooling/config.json (last token / mean), else last token.  bf16 operands only."""
+        from marqo_amd.engine.llama import LlamaTower
+        self._load_decoder(directory, arch, cfg, sd, LlamaTower, "Mistral / Llama encoders", pad_fallback="</s>")
+
+    def _load_decoder(self, directory: str, arch, cfg: dict, sd, tower, family: str, **tokenizer_args) -> None:
+        """what the decoder-style families share: fp8 refused, the width checked, last-token / mean pooling resolved, right-padded input truncated at
+        min(tokens, max_position_embeddings, 8192); tokenizer_args: HfJsonTokenizer.plain's (the pad token to fall back to: a pad position never reaches a row)"""
+        import json
         from marqo_amd.engine.tokenizers import HfJsonTokenizer
         props = self.model_properties
-        self._refuse_fp8("Qwen3 / Qwen2 encoders (their RMSNorm / rotary / gated-SiLU blocks run on bf16 operands only)")
+        self._refuse_fp8(f"{family} (their RMSNorm / rotary / gated-SiLU blocks run on bf16 operands only)")
         self._check_width(arch.width)
         pooling = props.pooling_method
         if pooling is None:
@@ -287,9 +307,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 pooling = "last" if pc.get("pooling_mode_lasttoken") is True else "mean" if pc.get("pooling_mode_mean_tokens") is True else None
         pooling = pooling or "last"
         if pooling not in ("last", "mean"):
-            raise InvalidModelPropertiesError(f"{props.name}: pooling_method {pooling!r} is not available for Qwen3 / Qwen2 encoders ('last' or 'mean')")
-        self._finish_packed(directory, arch, min(int(cfg.get("max_position_embeddings", 8192)), 8192), QwenTower, sd,
-                            lambda: HfJsonTokenizer.plain(directory), pooling=pooling)
+            raise InvalidModelPropertiesError(f"{props.name}: pooling_method {pooling!r} is not available for {family} ('last' or 'mean')")
+        self._finish_packed(directory, arch, min(int(cfg.get("max_position_embeddings", 8192)), 8192), tower, sd,
+                            lambda: HfJsonTokenizer.plain(directory, **tokenizer_args), pooling=pooling)
 
     # sentence-transformers Dense module directories (relative to the checkpoint) to apply behind the pooling: set by the `sbert` loader for an
     # EmbeddingGemma or a T5 encoder pipeline, empty for `hf` (AutoModel in the reference: the bare encoder)
