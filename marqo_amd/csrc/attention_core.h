@@ -1,4 +1,6 @@
-// The tile core of the LDS-staged flash-style attention kernels (attention.hip, attention_window.hip, attention_gqa.hip, attention_gqa256.hip): what one
+// The tile core of the LDS-staged flash-style attention kernels (included by attention.hip, attention_alibi.hip, attention_disentangled.hip,
+// attention_full.hip, attention_gqa256.hip, attention_relbias.hip and attention_window.hip; by attention_gqa.hip and attention_gqa256_causal.hip through
+// attention_gqa_core.h, which holds the one work split those two share): what one
 // wave does with one 64-key tile for its 16 queries, and the host arithmetic their entry points share.  The kernels differ in the work split — which keys
 // a workgroup stages, which tiles a query block visits — and keep that, their register budgets and their measured choices in their own files.
 //

@@ -24,6 +24,12 @@
 // (-Rpass-analysis=kernel-resource-usage): 212 VGPRs, 0 AGPRs, 68 SGPRs, scratch 0 bytes / lane, no spill, no static LDS (dynamic: 64 KiB or 128 KiB
 // per workgroup), 2 waves per SIMD — one 8-wave workgroup per CU, which is also what a two-tile piece of LDS admits.  Four waves per workgroup would
 // allow 512 registers but take three rounds (three re-stagings of the band) for the checkpoint's G = 3 where eight take two.
+//
+// This kernel KEEPS ITS OWN BODY of the work split that its four siblings share (attention_gqa_core.h's attn_gqa_body; it would be that body with
+// 64-query slices dealt forward, no reversed block order and a band key space).  Tried: on the shared body the bits were the parent's and the compiler
+// reported 212 VGPRs / 2 waves per SIMD again (254 until the block's end tile was clipped to the slice's per piece, as below), but a differently
+// scheduled stream, and 16 sequences of 512 tokens at (3, 1) heads measured 85.7 µs [85.5 – 87.4] against 81.2 µs [80.8 – 84.9] here at half_window 256,
+// 87.0 µs against 82.6 µs at 0 (MI355X, interleaved medians of 15 launches, 7 repeats): 5 % slower, outside the spread.
 #include "attention_core.h"
 
 namespace {

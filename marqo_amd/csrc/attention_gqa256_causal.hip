@@ -12,13 +12,13 @@
 // swizzle that keeps the swizzled chunk offsets per-lane constants of the whole kernel (see that file's header: with k & 31 the compiler spilled).  A
 // 64-key tile of K plus V is 64 KiB, the LDS holds two: a PIECE is at most 128 keys, and everything longer streams through the LDS in pieces.
 //
-// Key space.  A slice stages and a block walks VIRTUAL key tiles, as attention_gqa_prefix_kernel does:
+// Key space.  A slice stages and a block walks VIRTUAL key tiles, as attention_gqa_prefix_kernel does (attention_gqa_core.h's AttnKeysPrefix):
 //   tiles [0, npt), npt = ceil(P / 64)   the prefix keys (rows 0 .. P - 1); the last one is partial when P % 64 != 0: its keys >= P are masked
 //   tiles npt ..                         the segment's own keys, own key j at virtual key 64 npt + j: a FRESH tile, no tile straddles the two ranges
 // so P need not be a multiple of 64: the segment's first key tile starts on a tile boundary of the LDS image whatever P is, a virtual key and its LDS row
 // agree modulo 64, and the swizzle holds unchanged.  The price is one more partly empty tile per block when P % 64 != 0.
 //
-// Work split:
+// Work split (the body is attention_gqa_core.h's attn_gqa_body; this kernel's policy is AttnSliceBlocks{nb} and AttnKeysPrefix{P}):
 //   - One workgroup of 8 wave64s per (sequence, K/V head, slice of nb 16-query blocks).  It stages that K/V head's tiles once per piece for ALL G query
 //     heads that read it; K/V are never expanded to q_heads.
 //   - It stages only the prefix tiles and the own tiles up to the slice's last query; a 16-query block visits only the prefix tiles and the own tiles
@@ -37,122 +37,23 @@
 //     flight.  Overlapping the next piece with this one's MFMAs is left open.
 //
 // Registers per wave: 16 output tiles = 64 fp32 accumulators, 8 Q fragments = 32, one S^T tile = 16.  Compiler report for gfx950
-// (-Rpass-analysis=kernel-resource-usage): 250 VGPRs, 0 AGPRs, 80 SGPRs, scratch 0 bytes / lane, no spill, no static LDS (dynamic: 64 KiB or 128 KiB
+// (-Rpass-analysis=kernel-resource-usage): 224 VGPRs, 0 AGPRs, 80 SGPRs, scratch 0 bytes / lane, no spill, no static LDS (dynamic: 64 KiB or 128 KiB
 // per workgroup), 2 waves per SIMD — one 8-wave workgroup per CU, which is also what a two-tile piece of LDS admits.  (The two mask forms and the two
-// staging sources cost 38 registers over the band kernel's 212; the unit is in _lib.NO_SCRATCH_UNITS, so a build that spills is refused.)
-#include "attention_core.h"
+// staging sources cost 12 registers over the band kernel's 212; the unit is in _lib.NO_SCRATCH_UNITS, so a build that spills is refused.)
+#include "attention_gqa_core.h"
 
 namespace {
 
 constexpr int C256_NW = 8;           // wave64s per workgroup
 constexpr int C256_PIECE_KEYS = 128; // keys of K + V the LDS holds at 512-byte rows: 128 KiB of the 160 KiB
 constexpr int C256_HD = 256;
+constexpr int C256_SWZ = 15;         // chunk c of key k lives in slot c ^ (k & 15): the swizzle stays inside one 256-B half of the row
 
 __global__ __launch_bounds__(C256_NW * 64) void attention_gqa256_causal_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                                               const int32_t* __restrict__ cu, int fixed_len, int P, int q_heads, int kv_heads,
-                                                                               int nslices, int nb, int kpad, float scale_log2e) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int HD = C256_HD;
-    constexpr int RB = HD * 2;       // 512 bytes per K / V row in LDS
-    constexpr int NC = HD / 8;       // 32 16-byte chunk slots per LDS row
-    constexpr int NKK = HD / 32;     // 8 32-deep MFMA k-chunks of a Q.K dot product
-    constexpr int NDT = HD / 16;     // 16 16-wide output-dim tiles
-    constexpr int SWZ = 15;          // chunk c of key k lives in slot c ^ (k & 15): the swizzle stays inside one 256-B half of the row
-    char* sK = smem;                      // [kpad][RB]
-    char* sV = smem + (size_t)kpad * RB;  // [kpad][RB], same image
-
-    const unsigned sk = blockIdx.x / (unsigned)nslices;
-    const int slice = nslices - 1 - (int)(blockIdx.x - sk * (unsigned)nslices);   // longest first
-    const int seq = sk / kv_heads, kvh = sk - seq * kv_heads;
-    int row0, len;
-    if (fixed_len > 0) { row0 = seq * fixed_len; len = fixed_len; }
-    else { row0 = cu[seq]; len = cu[seq + 1] - row0; }
-    const int q0 = slice * nb * 16;
-    if (len <= 0 || q0 >= len) return;     // (the whole workgroup: no barrier has been reached)
-    const int G = q_heads / kv_heads;
-    const int ld = (q_heads + 2 * kv_heads) * HD, ldo = q_heads * HD;
-    const bf16_t* qrow = qkv + (int64_t)row0 * ld;
-    const bf16_t* kb = qrow + (q_heads + kvh) * HD;      // the sequence's own keys / values
-    const bf16_t* vb = kb + kv_heads * HD;
-    const bf16_t* pkb = qkv + (q_heads + kvh) * HD;      // the prefix's: rows 0 .. P - 1 of the same buffer (never read when P = 0)
-    const bf16_t* pvb = pkb + kv_heads * HD;
-    const int npt = (P + 63) >> 6;
-    const int nkt = (len + 63) >> 6;                     // own tiles of the sequence
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int q_last = q0 + nb * 16 - 1 < len - 1 ? q0 + nb * 16 - 1 : len - 1;
-    const int nblk = ((q_last - q0) >> 4) + 1;
-    const int skt = npt + (q_last >> 6) + 1;             // virtual tiles [0, skt) the slice stages
-    const int tpc = kpad >> 6;
-    const int nchunks = (skt + tpc - 1) / tpc;
-    const int nitems = G * nblk;
-    const int nrounds = (nitems + C256_NW - 1) / C256_NW;
-    auto stage = [&](int c) {   // virtual tiles [t0, t1) -> LDS rows 0 ..: the prefix tiles among them, then the own tiles
-        const int t0 = c * tpc, t1 = skt < t0 + tpc ? skt : t0 + tpc;
-        const int pe = t1 < npt ? t1 : npt;              // one past the last prefix tile of the piece
-        const int os = t0 > npt ? t0 : npt;              // its first own tile
-        if (pe > t0) attn_stage_piece<RB, NC, SWZ, C256_NW>(sK, sV, pkb, pvb, ld, t0 << 6, (pe - t0) << 6, P, lane, wave);
-        if (t1 > os) {
-            const size_t off = (size_t)((os - t0) << 6) * RB;
-            attn_stage_piece<RB, NC, SWZ, C256_NW>(sK + off, sV + off, kb, vb, ld, (os - npt) << 6, (t1 - os) << 6, len, lane, wave);
-        }
-    };
-    if (nchunks == 1) {
-        stage(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-
-    const int l15 = lane & 15, g = lane >> 4;
-    const int vkey = 4 * g + (l15 >> 2);     // per-lane constants of the V^T transpose reads
-    const int vcol = (l15 & 3) >> 1, vhalf = (l15 & 1) << 3;
-
-    for (int rnd = 0; rnd < nrounds; ++rnd) {
-        const int item = rnd * C256_NW + wave;
-        const bool active = item < nitems;       // wave-uniform; with nchunks > 1 an idle wave still stages and keeps the barriers
-        if (nchunks == 1 && !active) break;
-        const int gh = active ? item / nblk : 0;
-        const int blk = active ? item - gh * nblk : 0;
-        const int h = kvh * G + gh;              // repeat_kv: K/V head kvh serves query heads kvh G .. kvh G + G - 1
-        const int qb0 = q0 + blk * 16;
-        const int q = qb0 + l15;                 // this lane's query (B-operand column / output row)
-        bf16x8 qf[NKK];
-        {
-            const int qr = q < len ? q : len - 1;
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) qf[kk] = *(const bf16x8*)(qrow + (int64_t)qr * ld + h * HD + 8 * g + 32 * kk);
-        }
-
-        float m_run = -1e30f, l_run = 0.f;
-        f32x4 o[NDT];
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-        const int last = npt + ((qb0 + 15) >> 6);        // the virtual tile of the block's last query: own tiles behind it start past every query
-        const int kt_end = last + 1 < skt ? last + 1 : skt;
-        for (int c = 0; c < nchunks; ++c) {
-            if (nchunks > 1) {   // (re)fill the LDS with virtual tiles [c tpc, (c + 1) tpc) of the slice
-                __syncthreads();
-                stage(c);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-            }
-            const int kt0 = c * tpc;
-            const int kt1 = !active ? kt0 : (kt_end < kt0 + tpc ? kt_end : kt0 + tpc);
-            const int cb = kt0 << 6;                         // LDS row of virtual key `key` is key - cb (cb is a multiple of 64)
-            for (int kt = kt0; kt < kt1; ++kt) {
-                f32x4 sc[4];
-                attn_score_tile<RB, NKK, SWZ>(sK, kt, cb, l15, g, qf, sc);
-                if (kt < npt) attn_mask_causal<MQ_MASK_NONE>(sc, kt, npt, g, q, qb0, P);                     // prefix: only keys >= P of its partial last tile
-                else attn_mask_causal<MQ_MASK_CAUSAL>(sc, kt - npt, nkt, g, q, qb0, len);                    // own: the diagonal tile, per key
-                attn_softmax_step<NDT>(sc, m_run, l_run, o, scale_log2e);   // (first tile visited: prefix key 0 when P >= 1, else own key 0)
-                attn_pv_tile<RB, NDT, SWZ>(sV, kt, cb, vkey, vcol, vhalf, sc, o);
-            }
-        }  // pieces
-        if (!active) continue;
-        const float inv = attn_inv_denominator(l_run);
-        if (q < len) attn_store_bf16<NDT>(out + (int64_t)(row0 + q) * ldo + h * HD + 4 * g, o, inv);
-    }
+                                                                               const int32_t* __restrict__ cu, int fixed_len, int q_heads, int kv_heads,
+                                                                               int nslices, int kpad, float scale_log2e, int nb, int P) {
+    attn_gqa_body<C256_HD, C256_SWZ, C256_NW>(qkv, out, cu, fixed_len, q_heads, kv_heads, nslices, kpad, scale_log2e,
+                                              AttnGqaPolicy<AttnSliceBlocks, AttnKeysPrefix>{{nb}, {P}});
 }
 
 // the checks both entry points make behind their own, and the launch.  maxl = the longest sequence / segment
@@ -165,17 +66,9 @@ int launch_gqa256_causal(const char* fn, const void* d_qkv, void* d_out, const i
     MQ_CHECK_ARG(nseq * kv_heads * nslices < (1LL << 31), "%s: grid too large", fn);
     // the virtual key space: the prefix in whole tiles, then the longest sequence in whole tiles; the LDS holds two tiles of it
     const int kpad = attn_kpad(((P + 63) / 64) * 64 + maxl, C256_PIECE_KEYS);
-    const size_t lds = (size_t)kpad * C256_HD * 4;
-    hipStream_t s = (hipStream_t)stream;
-    static std::atomic<uint64_t> done{0};
-    const int rc = attn_ensure_lds((const void*)attention_gqa256_causal_kernel, lds, (size_t)C256_PIECE_KEYS * C256_HD * 4, done, fn);
-    if (rc != MQ_OK) return rc;
-    MqProfScope prof(2, s);
-    const float scale_log2e = 1.44269504088896340736f * scale;
-    hipLaunchKernelGGL(attention_gqa256_causal_kernel, dim3((unsigned)(nseq * kv_heads * nslices)), dim3(C256_NW * 64), lds, s, (const bf16_t*)d_qkv,
-                       (bf16_t*)d_out, d_cu, fixed_len, P, q_heads, kv_heads, nslices, nb, kpad, scale_log2e);
-    MQ_CHECK_LAUNCH(fn);
-    return MQ_OK;
+    return attn_gqa_launch<attention_gqa256_causal_kernel, C256_HD, C256_NW>(fn, (size_t)C256_PIECE_KEYS * C256_HD * 4, d_qkv, d_out, d_cu, nseq, fixed_len,
+                                                                             q_heads, kv_heads, nslices, kpad, 1.44269504088896340736f * scale,
+                                                                             (hipStream_t)stream, nb, P);
 }
 
 }  // namespace

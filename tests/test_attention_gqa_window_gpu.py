@@ -2,7 +2,7 @@
 device.  The assertion is that of tests/test_attention_gqa_gpu.py, whose bar is imported:  |kernel - reference| <= 1.25 x budget,
 budget = 2**-8 * (P|V| + |out|)  (attention_ref.budget).  Query i sees the keys j with i - window < j <= i (transformers' masking_utils).
 
-Cases: head_dim 64 and 128; (q_heads, kv_heads) (4, 2), (7, 1) = a group of seven, (2, 2) = no grouping; one packed call of lengths 1, 17, 129, 300 and
+Cases: head_dim 64 and 128; (q_heads, kv_heads) (4, 2), (7, 1) = a group of seven, (2, 2) = no grouping, (8, 1) = a group that fills a round of waves; one packed call of lengths 1, 17, 129, 300 and
 one fixed-length call; windows 1, 16 (the lower edge inside a 16-query block), 63 / 64 / 65 (on and on either side of a 64-key tile boundary), 128 (a
 slice boundary) and 200; and one length past twice what the LDS holds with a window of more than the LDS holds, so that a slice's band goes through the
 LDS in two pieces.  Inputs: `readout` (one-hot V rows: one wrong key is one wrong column) and `peaked`.
@@ -23,7 +23,7 @@ from tests.test_attention_gpu import MARGIN
 pytestmark = pytest.mark.gpu
 
 GUARD = 64
-HEADS = [(4, 2), (7, 1), (2, 2)]
+HEADS = [(4, 2), (7, 1), (2, 2), (8, 1)]
 WINDOWS = (1, 16, 63, 64, 65, 128, 200)
 PACK = [1, 17, 129, 300]
 

@@ -44,7 +44,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 GUARD = 64
-HEADS = [(4, 2, 128), (4, 1, 64), (7, 1, 64)]
+HEADS = [(4, 2, 128), (4, 1, 64), (7, 1, 64), (2, 2, 64), (8, 1, 64)]   # groups of 2, 4, 7 (an idle wave), 1 (no grouping) and 8 (a full round)
 PREFIXES = (1, 63, 64, 65, 200)
 SEGMENTS = [1, 15, 16, 17, 64, 65, 129]
 NAN16 = 0x7FC0      # a bf16 NaN as int16
