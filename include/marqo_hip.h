@@ -1923,6 +1923,92 @@ size_t mq_llama_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows, int64_t n
 int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                     int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mixture-of-experts NomicBERT (nomic-embed-text-v2-moe): router, device-side plan, grouped bf16 GEMM, and the tower
+ * (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py) ---------------------------------------------------------------------------------------------------
+ * The Jina v3 base block (post-LN, biased Wqkv / out_proj, rotate-half rope over 64-wide heads, full attention) whose MLP is, layer by layer, either
+ * dense (fc1 + b -> erf-GELU -> fc2 + b) or routed:  p = softmax_fp32(x Wr^T), top-k of p (not renormalised),
+ * y = sum_j w_j gelu(x W1[e_j]^T) W2[e_j] + b_experts, x = LN(y + x).  Additions to ABI 15: nothing above changes; the structs and entry points below
+ * are new.  Each judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream`,
+ * allocates nothing and never synchronises: the segment sizes stay on the device.
+ *
+ *   mq_moe_tile_rows: the tile height (128 or 32 slots) the grouped GEMM runs for `rows` rows: 128 when k rows / experts > 64.
+ *   mq_moe_max_tiles: floor(k rows / bm) + experts, the bound on sum_e ceil(n_e / bm) that sizes the tile table (1 + 2 max_tiles int32) and the grid.
+ *   mq_moe_route:   d_x fp32 [rows, W] (the fp32 stream), d_router_w fp32 [E, W] -> d_top_e int32 [rows, k], d_top_w fp32 [rows, k]: fp32 logits,
+ *                   fp32 softmax over E, the k largest with the lower index winning a tie.  E in 2 .. 16, k in {1, 2}, W % 64 == 0, W <= 2048.
+ *   mq_moe_plan:    a stable counting sort of the flat entries i = row k + j by expert d_top_e[i] (ids outside [0, E) are clamped): d_expert_off
+ *                   int32 [E + 1]; d_slot_row int32 [k rows] and d_slot_w fp32 [k rows] (row and routing weight of a slot; slots are expert-major,
+ *                   ascending row within an expert); d_row_slot int32 [rows, k] (the inverse); d_tiles int32 [1 + 2 mq_moe_max_tiles]: the tile count,
+ *                   then (expert, first slot) per tile of bm slots.  One workgroup, no atomics: the order is a function of the entries alone.
+ *   mq_moe_gemm:    MQ_MOE_UP:   d_out bf16 [k rows, N] in slot order = gelu_erf(d_A[slot_row[slot], :] d_W[e]^T), d_A bf16 [rows, K] (gathered);
+ *                   MQ_MOE_DOWN: d_out fp32 [k rows, N] = slot_w[slot] (d_A[slot, :] d_W[e]^T), d_A bf16 [k rows, K] in slot order.
+ *                   d_W bf16 [E][N][K].  N, K % 64 == 0, N K 2 < 2^32, rows K 2 < 2^32; bm = the plan's.  One accumulation chain per element over
+ *                   k = 0, 32, 64, ... at either tile height: a row's bits do not depend on bm, on its slot or on the other rows.
+ *   mq_moe_combine_ln: d_x fp32 [rows, W] = LN(((x + Y[row_slot[r, 0]]) + Y[row_slot[r, 1]]) + bias) (k = 1: (x + Y[..]) + bias), in place, and its
+ *                   bf16 copy d_h_bf16.  W % 64 == 0, W <= 2048.
+ *   mq_encode_nomic_moe: token gather + type row 0 -> LayerNorm -> `layers` blocks (a layer with router_w != NULL runs route, plan, UP, DOWN,
+ *                   combine; else the dense MLP and mq_layernorm) -> mean / CLS pooling (+ L2), on packed sequences like mq_encode_nomic_bert.  The fp32
+ *                   stream is the workspace's first slice.  Limits: mq_encode_nomic_bert's, experts 2 .. 16, top_k 1 or 2.  Compiler report and the
+ *                   tile design: csrc/moe.hip's header. */
+#define MQ_MOE_UP 0
+#define MQ_MOE_DOWN 1
+
+typedef struct mq_nomic_moe_layer {
+    const void*  qkv_w;         /* bf16 [3 W, W]  attn.Wqkv */
+    const float* qkv_b;         /* fp32 [3 W] */
+    const void*  out_w;         /* bf16 [W, W]  attn.out_proj */
+    const float* out_b;         /* fp32 [W] */
+    const float* attn_ln_g;     /* fp32 [W]  norm1 */
+    const float* attn_ln_b;
+    const void*  fc1_w;         /* dense layer: bf16 [F, W]  mlp.fc1 (NULL in a routed layer, as fc1_b, fc2_w, fc2_b) */
+    const float* fc1_b;         /* fp32 [F] */
+    const void*  fc2_w;         /* bf16 [W, F]  mlp.fc2 */
+    const float* fc2_b;         /* fp32 [W] */
+    const float* router_w;      /* routed layer: fp32 [E, W]  mlp.router.layer.weight; NULL: a dense layer */
+    const void*  w1;            /* bf16 [E][F][W]  mlp.experts.mlp.w1 */
+    const void*  w2t;           /* bf16 [E][W][F]  mlp.experts.mlp.w2, each expert transposed at load */
+    const float* experts_b;     /* fp32 [W]  mlp.experts.bias */
+    const float* mlp_ln_g;      /* fp32 [W]  norm2 */
+    const float* mlp_ln_b;
+} mq_nomic_moe_layer;
+
+typedef struct mq_nomic_moe_weights {
+    const float* tok_emb;       /* fp32 [vocab, W]  embeddings.word_embeddings */
+    const float* type0;         /* fp32 [W]  row 0 of embeddings.token_type_embeddings */
+    const float* emb_ln_g;      /* fp32 [W]  emb_ln */
+    const float* emb_ln_b;
+    const float* d_inv_freq;    /* fp32 [32]: rotary_emb_base ^ -(2 i / 64) */
+    const mq_nomic_moe_layer* layers;  /* host array, `layers` entries */
+} mq_nomic_moe_weights;
+
+typedef struct mq_nomic_moe_cfg {
+    int32_t width;         /* W, multiple of 64, <= 2048 */
+    int32_t layers;
+    int32_t heads;         /* heads * 64 == W */
+    int32_t head_dim;      /* 64 */
+    int32_t mlp_dim;       /* F = n_inner, multiple of 64 (dense and per expert) */
+    int32_t vocab;
+    int32_t max_pos;       /* longest sequence served (<= 8192) */
+    int32_t pool;          /* MQ_POOL_MEAN or MQ_POOL_CLS */
+    float   ln_eps;
+    int32_t experts;       /* E: 2 .. 16 */
+    int32_t top_k;         /* 1 or 2, <= E */
+    int32_t reserved;
+} mq_nomic_moe_cfg;
+
+int32_t mq_moe_tile_rows(int64_t rows, int32_t experts, int32_t top_k);
+int64_t mq_moe_max_tiles(int64_t rows, int32_t experts, int32_t top_k, int32_t bm);
+int mq_moe_route(const float* d_x, const float* d_router_w, int32_t* d_top_e, float* d_top_w, int64_t rows, int32_t W, int32_t experts, int32_t top_k,
+                 void* stream);
+int mq_moe_plan(const int32_t* d_top_e, const float* d_top_w, int64_t rows, int32_t experts, int32_t top_k, int32_t bm, int32_t* d_expert_off,
+                int32_t* d_slot_row, float* d_slot_w, int32_t* d_row_slot, int32_t* d_tiles, void* stream);
+int mq_moe_gemm(int32_t form, const void* d_A, const void* d_W, const int32_t* d_tiles, const int32_t* d_expert_off, const int32_t* d_slot_row,
+                const float* d_slot_w, void* d_out, int64_t rows, int32_t experts, int32_t top_k, int32_t bm, int32_t N, int32_t K, void* stream);
+int mq_moe_combine_ln(float* d_x, const float* d_Y, const int32_t* d_row_slot, const float* d_bias, const float* d_g, const float* d_b, void* d_h_bf16,
+                      int64_t rows, int32_t W, int32_t top_k, float eps, void* stream);
+size_t mq_nomic_moe_workspace_bytes(const mq_nomic_moe_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_nomic_moe(const mq_nomic_moe_cfg* cfg, const mq_nomic_moe_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                        const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

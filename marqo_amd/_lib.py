@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -354,6 +354,25 @@ class JinaV3Cfg(C.Structure):
                 ("max_pos", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+MQ_MOE_UP, MQ_MOE_DOWN = 0, 1
+
+
+class NomicMoeLayer(C.Structure):
+    """mq_nomic_moe_layer: one block of the mixture-of-experts NomicBERT (csrc/nomic_moe.hip); router_w NULL: a dense layer"""
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "qkv_b", "out_w", "out_b", "attn_ln_g", "attn_ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "router_w", "w1",
+                                          "w2t", "experts_b", "mlp_ln_g", "mlp_ln_b")]
+
+
+class NomicMoeWeights(C.Structure):
+    _fields_ = [("tok_emb", C.c_void_p), ("type0", C.c_void_p), ("emb_ln_g", C.c_void_p), ("emb_ln_b", C.c_void_p), ("d_inv_freq", C.c_void_p),
+                ("layers", C.POINTER(NomicMoeLayer))]
+
+
+class NomicMoeCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32), ("vocab", C.c_int32),
+                ("max_pos", C.c_int32), ("pool", C.c_int32), ("ln_eps", C.c_float), ("experts", C.c_int32), ("top_k", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -578,6 +597,15 @@ _SIGNATURES = {
     "mq_pool_wide": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P]),
     "mq_llama_workspace_bytes": (C.c_size_t, [C.POINTER(LlamaCfg), C.c_int64, C.c_int64]),
     "mq_encode_llama": (C.c_int, [C.POINTER(LlamaCfg), C.POINTER(QwenWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # mixture-of-experts NomicBERT: router, plan, grouped GEMM, combine and the tower (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py)
+    "mq_moe_tile_rows": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32]),
+    "mq_moe_max_tiles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "mq_moe_route": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_moe_plan": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mq_moe_gemm": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mq_moe_combine_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_nomic_moe_workspace_bytes": (C.c_size_t, [C.POINTER(NomicMoeCfg), C.c_int64, C.c_int64]),
+    "mq_encode_nomic_moe": (C.c_int, [C.POINTER(NomicMoeCfg), C.POINTER(NomicMoeWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune":(C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
@@ -608,12 +636,14 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     common_mtime = max(os.path.getmtime(p) for p in common)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-Rpass-analysis=kernel-resource-usage"]  # the remarks feed the no-scratch check below
+    # units compiled without the packed fp32 VALU forms (v_pk_add / mul / fma_f32): the compiler then pairs no fp32 arithmetic of their epilogues
+    unit_flags = {"moe": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
     def compile_one(src: str):
         obj = obj_dir / (Path(src).stem + ".o")
         if not force and obj.exists() and os.path.getmtime(obj) >= max(os.path.getmtime(src), common_mtime):
             return str(obj), False
-        cmd = [hipcc, *flags, "-c", src, "-o", str(obj)]
+        cmd = [hipcc, *flags, *unit_flags.get(Path(src).stem, []), "-c", src, "-o", str(obj)]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         res = subprocess.run(cmd, capture_output=True, text=True)

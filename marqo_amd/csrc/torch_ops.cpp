@@ -17,6 +17,9 @@
 #include <Python.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <tuple>
+
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -319,6 +322,52 @@ void attention_gqa_window(const at::Tensor& qkv, const at::Tensor& cu_seqlens, i
                                      (int32_t)q_heads, (int32_t)kv_heads, (int32_t)head_dim, (int32_t)window, stream_of(qkv)), "mq_attention_gqa_window");
 }
 
+// ---- routed mixture-of-experts MLP (csrc/moe.hip) ------------------------------------------------------------------------------------------------------
+// x fp32 [rows, W] (the fp32 stream), router_w fp32 [E, W] -> (top_e int32 [rows, k], top_w fp32 [rows, k])
+std::tuple<at::Tensor, at::Tensor> moe_route(const at::Tensor& x, const at::Tensor& router_w, int64_t top_k) {
+    need_dev(x, at::kFloat, "x");
+    need_dev(router_w, at::kFloat, "router_w");
+    TORCH_CHECK(x.dim() == 2 && router_w.dim() == 2 && router_w.size(1) == x.size(1) && top_k >= 1 && top_k <= 2,
+                "marqo_hip::mq_moe_route: x [rows,W], router_w [E,W], top_k 1 or 2");
+    at::Tensor top_e = at::empty({x.size(0), top_k}, x.options().dtype(at::kInt)), top_w = at::empty({x.size(0), top_k}, x.options());
+    check_rc(mq_moe_route((const float*)x.data_ptr(), (const float*)router_w.data_ptr(), (int32_t*)top_e.data_ptr(), (float*)top_w.data_ptr(), x.size(0),
+                          (int32_t)x.size(1), (int32_t)router_w.size(0), (int32_t)top_k, stream_of(x)), "mq_moe_route");
+    return {top_e, top_w};
+}
+
+// plan + UP + DOWN under a given routing: h bf16 [rows, W], top_e int32 / top_w fp32 [rows, k], w1 bf16 [E, F, W], w2t bf16 [E, W, F]; bm: the tile
+// height (128 / 32), 0: the host's choice; Y fp32 [k rows, W] is written in slot order -> (row_slot [rows, k], slot_row [k rows], expert_off [E + 1])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_mlp(const at::Tensor& h, const at::Tensor& top_e, const at::Tensor& top_w, const at::Tensor& w1,
+                                                       const at::Tensor& w2t, int64_t bm, at::Tensor Y) {
+    need_dev(h, at::kBFloat16, "h");
+    need_dev(top_e, at::kInt, "top_e");
+    need_dev(top_w, at::kFloat, "top_w");
+    need_dev(w1, at::kBFloat16, "w1");
+    need_dev(w2t, at::kBFloat16, "w2t");
+    need_dev(Y, at::kFloat, "Y");
+    TORCH_CHECK(h.dim() == 2 && top_e.dim() == 2 && top_e.size(0) == h.size(0) && top_w.sizes() == top_e.sizes() && w1.dim() == 3 && w2t.dim() == 3 &&
+                w1.size(2) == h.size(1) && w2t.size(0) == w1.size(0) && w2t.size(1) == h.size(1) && w2t.size(2) == w1.size(1),
+                "marqo_hip::mq_moe_mlp: h [rows,W], top_e / top_w [rows,k], w1 [E,F,W], w2t [E,W,F]");
+    const int64_t rows = h.size(0), W = h.size(1), F = w1.size(1);
+    const int32_t E = (int32_t)w1.size(0), k = (int32_t)top_e.size(1);
+    TORCH_CHECK(Y.dim() == 2 && Y.size(0) == rows * k && Y.size(1) == W, "marqo_hip::mq_moe_mlp: Y [k rows, W]");
+    const int32_t tile = bm ? (int32_t)bm : mq_moe_tile_rows(rows, E, k);
+    const auto io = h.options().dtype(at::kInt);
+    at::Tensor expert_off = at::empty({E + 1}, io), slot_row = at::empty({rows * k}, io), row_slot = at::empty({rows, k}, io);
+    at::Tensor tiles = at::empty({1 + 2 * std::max<int64_t>(mq_moe_max_tiles(rows, E, k, tile), 0)}, io);
+    at::Tensor slot_w = at::empty({rows * k}, top_w.options()), P = at::empty({rows * k, F}, h.options());
+    void* s = stream_of(h);
+    check_rc(mq_moe_plan((const int32_t*)top_e.data_ptr(), (const float*)top_w.data_ptr(), rows, E, k, tile, (int32_t*)expert_off.data_ptr(),
+                         (int32_t*)slot_row.data_ptr(), (float*)slot_w.data_ptr(), (int32_t*)row_slot.data_ptr(), (int32_t*)tiles.data_ptr(), s), "mq_moe_plan");
+    check_rc(mq_moe_gemm(MQ_MOE_UP, h.data_ptr(), w1.data_ptr(), (const int32_t*)tiles.data_ptr(), (const int32_t*)expert_off.data_ptr(),
+                         (const int32_t*)slot_row.data_ptr(), (const float*)slot_w.data_ptr(), P.data_ptr(), rows, E, k, tile, (int32_t)F, (int32_t)W, s),
+             "mq_moe_gemm (up)");
+    check_rc(mq_moe_gemm(MQ_MOE_DOWN, P.data_ptr(), w2t.data_ptr(), (const int32_t*)tiles.data_ptr(), (const int32_t*)expert_off.data_ptr(),
+                         (const int32_t*)slot_row.data_ptr(), (const float*)slot_w.data_ptr(), Y.data_ptr(), rows, E, k, tile, (int32_t)W, (int32_t)F, s),
+             "mq_moe_gemm (down)");
+    return {row_slot, slot_row, expert_off};
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -347,6 +396,8 @@ TORCH_LIBRARY(marqo_hip, m) {
           "Tensor(a!) out) -> ()");
     m.def("mq_attention_gqa_window(Tensor qkv, Tensor cu_seqlens, int max_len, int q_heads, int kv_heads, int head_dim, int window, "
           "Tensor(a!) out) -> ()");
+    m.def("mq_moe_route(Tensor x, Tensor router_w, int top_k) -> (Tensor, Tensor)");
+    m.def("mq_moe_mlp(Tensor h, Tensor top_e, Tensor top_w, Tensor w1, Tensor w2t, int bm, Tensor(a!) Y) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -367,4 +418,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_qk_norm_rope_at", &qk_norm_rope_at);
     m.impl("mq_attention_gqa256_prefix", &attention_gqa256_prefix);
     m.impl("mq_attention_gqa_window", &attention_gqa_window);
+    m.impl("mq_moe_route", &moe_route);
+    m.impl("mq_moe_mlp", &moe_mlp);
 }

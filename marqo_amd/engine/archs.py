@@ -914,7 +914,8 @@ def nomic_bert_arch_from_hf_config(cfg: dict) -> NomicBertArch:
     n_positions, layer_norm_epsilon, rotary_emb_base, rotary_emb_fraction, rotary_emb_interleaved, rotary_scaling_factor, activation_function,
     qkv_proj_bias, mlp_fc1_bias, mlp_fc2_bias, prenorm, use_rms_norm.  Refused by name: a bias set true, prenorm, use_rms_norm, rotary_emb_fraction
     other than 1, rotary_emb_interleaved, a non-null rotary_scaling_factor, an activation_function other than swiglu.  In both dialects the
-    mixture-of-experts keys of nomic-embed-text-v2-moe (moe_every_n_layers > 0, num_experts > 1) are refused."""
+    mixture-of-experts keys of nomic-embed-text-v2-moe (moe_every_n_layers > 0, num_experts > 1) are refused here: a file with both goes to
+    nomic_moe_arch_from_hf_config (bert_arch_from_hf_config decides), a file with one of them is not a model that is served."""
     mtype = cfg.get("model_type")
     if mtype != "nomic_bert":
         raise KeyError(f"model_type={mtype} is not a NomicBERT model")
@@ -969,6 +970,96 @@ def nomic_bert_arch_from_hf_config(cfg: dict) -> NomicBertArch:
     return NomicBertArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 2048)), 8192), width=W,
                          layers=int(cfg["num_hidden_layers"]), heads=heads, mlp_dim=F, ln_eps=float(cfg.get("layer_norm_eps", 1e-12)),
                          type_vocab=int(cfg.get("type_vocab_size", 2)), rope_theta=theta)
+
+
+@dataclass(frozen=True)
+class NomicMoeArch:
+    """The mixture-of-experts NomicBERT (nomic-embed-text-v2-moe; config.json model_type "nomic_bert" in the hub's GPT-2-style dialect with
+    moe_every_n_layers / num_experts / moe_top_k) as the engine runs it: the Jina v3 base block (post-LN, biased Wqkv / out_proj, full-width rotate-half
+    rotary positions, row 0 of the token-type table, plain bidirectional attention) whose MLP is dense (fc1 + b -> erf-GELU -> fc2 + b) or routed (top-k of
+    an fp32 softmax over `experts` bias-free expert MLPs, weights not renormalised, one shared output bias).  WHICH layers are routed is read from the
+    checkpoint's tensors (engine/tower_weights.py::nomic_moe_state_dict), not computed from moe_every_n_layers."""
+    vocab: int = 250048
+    max_pos: int = 2048
+    width: int = 768
+    layers: int = 12
+    heads: int = 12
+    head_dim: int = 64
+    mlp_dim: int = 3072
+    ln_eps: float = 1e-5
+    type_vocab: int = 1
+    rope_theta: float = 10000.0
+    experts: int = 8
+    top_k: int = 2
+    moe_every: int = 2                    # recorded from the file; used by nothing but gflop_per_text
+
+    def inv_freq(self):
+        """[head_dim / 2] inverse frequencies theta^-(2i/d), in the plain order mq_rope reads"""
+        import torch
+        d = self.head_dim
+        return 1.0 / (self.rope_theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F = tokens, self.width, self.mlp_dim
+        routed = self.layers // max(self.moe_every, 1)
+        mlp = (self.layers - routed) * 2 * 2 * T * W * F + routed * (self.top_k * 2 * 2 * T * W * F + 2 * T * W * self.experts)
+        return (self.layers * (2 * T * W * 3 * W + 2 * T * W * W + 4 * T * T * W) + mlp) / 1e9
+
+
+def nomic_moe_arch_from_hf_config(cfg: dict) -> NomicMoeArch:
+    """A local `config.json` of the mixture-of-experts NomicBERT (model_type "nomic_bert" with BOTH moe_every_n_layers > 0 and num_experts > 1) ->
+    NomicMoeArch.  UNVERIFIED against a real hub file: the keys are written from memory of nomic-embed-text-v2-moe's config.json and of the hub's
+    modeling_hf_nomic_bert.py; neither was at hand.  Read: n_embd, n_head, n_layer, n_inner (null: 4 n_embd), n_positions, layer_norm_epsilon,
+    rotary_emb_base, vocab_size, type_vocab_size, num_experts, moe_top_k, moe_every_n_layers (transformers' spellings hidden_size ... are taken when n_embd
+    is absent).  Refused, each by the name of its key: moe_top_k outside {1, 2} or above num_experts, num_experts above 16,
+    moe_normalize_expert_weights set, an expert-choice router, an activation_function other than gelu, prenorm, use_rms_norm, a rotary_emb_fraction other
+    than 1, rotary_emb_interleaved, a rotary_scaling_factor, heads that are not 64 wide, a width above 2048, an n_inner that is no multiple of 64."""
+    mtype = cfg.get("model_type")
+    if mtype != "nomic_bert":
+        raise KeyError(f"model_type={mtype} is not a NomicBERT model")
+    E, k = int(cfg.get("num_experts") or 0), int(cfg.get("moe_top_k", 1) or 0)
+    if int(cfg.get("moe_every_n_layers") or 0) <= 0 or E <= 1:
+        raise KeyError(f"moe_every_n_layers={cfg.get('moe_every_n_layers')} / num_experts={cfg.get('num_experts')} is not a mixture-of-experts NomicBERT")
+    if E > 16:
+        raise KeyError(f"num_experts={E} unsupported (at most 16)")
+    if k not in (1, 2) or k > E:
+        raise KeyError(f"moe_top_k={cfg.get('moe_top_k')} unsupported (1 or 2, at most num_experts)")
+    if cfg.get("moe_normalize_expert_weights"):
+        raise KeyError(f"moe_normalize_expert_weights={cfg['moe_normalize_expert_weights']} unsupported (the routing weights are the softmax values as they are)")
+    if cfg.get("expert_choice_router", False):
+        raise KeyError(f"expert_choice_router={cfg['expert_choice_router']} unsupported (token-choice top-k routing only)")
+    act = cfg.get("activation_function", cfg.get("hidden_act", "gelu"))
+    if act != "gelu":
+        raise KeyError(f"activation_function={act} unsupported (gelu only in the mixture-of-experts block)")
+    if cfg.get("prenorm", False):
+        raise KeyError(f"prenorm={cfg['prenorm']} unsupported (post-LN blocks only)")
+    if cfg.get("use_rms_norm", False):
+        raise KeyError(f"use_rms_norm={cfg['use_rms_norm']} unsupported (LayerNorm only)")
+    if float(cfg.get("rotary_emb_fraction", 1.0)) != 1.0:
+        raise KeyError(f"rotary_emb_fraction={cfg['rotary_emb_fraction']} unsupported (the whole head is rotated)")
+    if cfg.get("rotary_emb_interleaved", False):
+        raise KeyError(f"rotary_emb_interleaved={cfg['rotary_emb_interleaved']} unsupported (rotate_half pairs only)")
+    if cfg.get("rotary_scaling_factor") is not None:
+        raise KeyError(f"rotary_scaling_factor={cfg['rotary_scaling_factor']} unsupported (rope scaling is not served)")
+    for kb in ("qkv_proj_bias", "mlp_fc1_bias", "mlp_fc2_bias"):
+        if not cfg.get(kb, True):
+            raise KeyError(f"{kb}={cfg[kb]} unsupported (the served block's Linears have a bias)")
+    get = lambda hub, own, default=None: cfg[hub] if cfg.get(hub) is not None else cfg.get(own, default)
+    W, heads = int(get("n_embd", "hidden_size")), int(get("n_head", "num_attention_heads"))
+    F = int(get("n_inner", "intermediate_size", 4 * W))
+    theta = float(cfg.get("rotary_emb_base", 10000.0))
+    if heads < 1 or W != heads * 64:
+        raise KeyError(f"n_embd={W} / n_head={heads} unsupported (64-wide heads only)")
+    if W > 2048:
+        raise KeyError(f"n_embd={W} unsupported (at most 2048)")
+    if F % 64 or F < 64:
+        raise KeyError(f"n_inner={F} must be a multiple of 64")
+    if not theta > 0:
+        raise KeyError(f"rotary_emb_base={theta} must be positive")
+    return NomicMoeArch(vocab=int(cfg["vocab_size"]), max_pos=min(int(get("n_positions", "max_position_embeddings", 2048)), 8192), width=W,
+                        layers=int(get("n_layer", "num_hidden_layers")), heads=heads, mlp_dim=F,
+                        ln_eps=float(get("layer_norm_epsilon", "layer_norm_eps", 1e-5)), type_vocab=int(cfg.get("type_vocab_size", 1)), rope_theta=theta,
+                        experts=E, top_k=k, moe_every=int(cfg["moe_every_n_layers"]))
 
 
 @dataclass(frozen=True)
@@ -1309,7 +1400,8 @@ def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenA
     engine/rerank.py, which select their model types before they call) must not pass one through; model_type qwen3 / qwen2 gives a QwenArch
     (engine/qwen.py::QwenTower), model_type gemma3_text a GemmaArch (engine/gemma.py::GemmaTower) and model_type t5 a T5Arch (engine/t5.py::T5Tower) under
     the same rule; so do model_type bert with position_embedding_type alibi, a JinaBertArch (engine/jina_bert.py::JinaBertTower), and model_type
-    nomic_bert, a NomicBertArch (engine/nomic_bert.py::NomicBertTower).  Anything else: KeyError."""
+    nomic_bert, a NomicBertArch (engine/nomic_bert.py::NomicBertTower) — or, with both mixture-of-experts keys, a NomicMoeArch
+    (engine/nomic_moe.py::NomicMoeTower).  Anything else: KeyError."""
     mtype = cfg.get("model_type", "bert")
     if mtype == "jina_embeddings_v3":   # transformers JinaEmbeddingsV3Model: jina-embeddings-v3 with its task adapters (engine/jina_v3.py::JinaV3Tower)
         return resolve_jina_v3(cfg)
@@ -1317,6 +1409,8 @@ def bert_arch_from_hf_config(cfg: dict) -> Union[BertArch, ModernBertArch, QwenA
         raise KeyError("model_type=xlm-roberta with lora_adaptations is the original jina-embeddings-v3 repository's custom-code naming, which is not "
                        "served: bring the checkpoint in transformers' own form (model_type jina_embeddings_v3, jinaai/jina-embeddings-v3-hf)")
     if mtype == "nomic_bert":   # transformers NomicBertModel: nomic-embed-text-v1 / -v1.5, arctic-embed-m-long (engine/nomic_bert.py::NomicBertTower)
+        if int(cfg.get("moe_every_n_layers") or 0) > 0 and int(cfg.get("num_experts") or 0) > 1:
+            return nomic_moe_arch_from_hf_config(cfg)   # BOTH keys: nomic-embed-text-v2-moe (engine/nomic_moe.py::NomicMoeTower); one alone stays refused
         return nomic_bert_arch_from_hf_config(cfg)
     if mtype == "t5":   # transformers T5EncoderModel: sentence-t5, gtr-t5, flan-t5 encoders (engine/t5.py::T5Tower)
         return t5_arch_from_hf_config(cfg)

@@ -678,3 +678,47 @@ def nomic_bert_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
         out[p + "mlp.down.weight"] = f32(linears["down"] + ".weight", (W, F))
         out[p + "mlp_ln.weight"], out[p + "mlp_ln.bias"] = f32(ln2 + ".weight", (W,)), f32(ln2 + ".bias", (W,))
     return out
+
+
+def nomic_moe_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """The mixture-of-experts NomicBERT's tensors (the hub's original names, which nomic_bert_state_dict reads too; UNVERIFIED against a real
+    nomic-embed-text-v2-moe checkpoint: written from memory of the hub's modeling file) -> the fp32 tensors the tower hands to the kernels.  Per block l:
+    `layer.l.attn.qkv.weight` [3 W, W] / `.bias`, `layer.l.attn.o.weight` / `.bias`, `layer.l.attn_ln.*` (norm1), `layer.l.mlp_ln.*` (norm2), and
+
+      a DENSE block (mlp.fc1 / mlp.fc2 present):  `layer.l.mlp.fc1.weight` [F, W] / `.bias`, `layer.l.mlp.fc2.weight` [W, F] / `.bias`;
+      a ROUTED block — recognised by its tensors, `encoder.layers.l.mlp.router.layer.weight` is present, never by the layer index:
+        `layer.l.moe.router.weight` [E, W]            mlp.router.layer.weight as it is (kept in fp32 by the tower)
+        `layer.l.moe.w1` [E, F, W]                    mlp.experts.mlp.w1 [E F, W]: expert e is rows e F .., used as x @ w1_e^T
+        `layer.l.moe.w2t` [E, W, F]                   mlp.experts.mlp.w2 [E F, W]: expert e is [F, W], used as act @ w2_e — transposed per expert, so
+                                                      that it is the W^T operand every GEMM here takes
+        `layer.l.moe.bias` [W]                        mlp.experts.bias, the one shared output bias
+
+    `type0` is row 0 of the token-type table.  Ignored: pooler / MLM-head / classifier tensors, `embeddings.position_ids`, rotary `inv_freq` buffers.
+    Refused by name: a missing or mis-shaped tensor, a block with both or neither MLP form."""
+    for prefix in ("nomic_bert.", "bert."):
+        if "embeddings.word_embeddings.weight" not in sd and prefix + "embeddings.word_embeddings.weight" in sd:
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    W, F, E = arch.width, arch.mlp_dim, arch.experts
+    f32 = lambda k, shape: _need(sd, k, shape).detach().to(torch.float32)
+    out = {"word_embeddings.weight": f32("embeddings.word_embeddings.weight", (arch.vocab, W)),
+           "type0": f32("embeddings.token_type_embeddings.weight", (arch.type_vocab, W))[0].contiguous(),
+           "emb_ln.weight": f32("emb_ln.weight", (W,)), "emb_ln.bias": f32("emb_ln.bias", (W,))}
+    for l in range(arch.layers):
+        src, p = f"encoder.layers.{l}.", f"layer.{l}."
+        out[p + "attn.qkv.weight"], out[p + "attn.qkv.bias"] = f32(src + "attn.Wqkv.weight", (3 * W, W)).contiguous(), f32(src + "attn.Wqkv.bias", (3 * W,))
+        out[p + "attn.o.weight"], out[p + "attn.o.bias"] = f32(src + "attn.out_proj.weight", (W, W)), f32(src + "attn.out_proj.bias", (W,))
+        out[p + "attn_ln.weight"], out[p + "attn_ln.bias"] = f32(src + "norm1.weight", (W,)), f32(src + "norm1.bias", (W,))
+        out[p + "mlp_ln.weight"], out[p + "mlp_ln.bias"] = f32(src + "norm2.weight", (W,)), f32(src + "norm2.bias", (W,))
+        routed, dense = src + "mlp.router.layer.weight" in sd, src + "mlp.fc1.weight" in sd
+        if routed == dense:
+            raise ValueError(f"checkpoint block {l} has {'both' if routed else 'neither'} '{src}mlp.router.layer.weight' and '{src}mlp.fc1.weight': a "
+                             f"block is routed or dense")
+        if routed:
+            out[p + "moe.router.weight"] = f32(src + "mlp.router.layer.weight", (E, W)).contiguous()
+            out[p + "moe.w1"] = f32(src + "mlp.experts.mlp.w1", (E * F, W)).reshape(E, F, W).contiguous()
+            out[p + "moe.w2t"] = f32(src + "mlp.experts.mlp.w2", (E * F, W)).reshape(E, F, W).transpose(1, 2).contiguous()
+            out[p + "moe.bias"] = f32(src + "mlp.experts.bias", (W,))
+        else:
+            out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = f32(src + "mlp.fc1.weight", (F, W)), f32(src + "mlp.fc1.bias", (F,))
+            out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = f32(src + "mlp.fc2.weight", (W, F)), f32(src + "mlp.fc2.bias", (W,))
+    return out

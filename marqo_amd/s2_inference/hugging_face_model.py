@@ -158,6 +158,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             if isinstance(arch, archs.JinaV3Arch):
                 self._load_jina_v3(directory, arch, sd)
                 return
+            if isinstance(arch, archs.NomicMoeArch):
+                self._load_nomic_moe(directory, arch, sd)
+                return
             if (arch.glu or arch.rope_theta is not None) and not props.trust_remote_code:
                 # a NewModel checkpoint is custom remote code to the reference's AutoModel: refused unless trustRemoteCode is set
                 raise InvalidModelPropertiesError(f"{props.name} is a custom-code (NewModel) checkpoint: the reference loads it only with "
@@ -371,6 +374,23 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         self._refuse_fp8("NomicBERT encoders (their rotary / gated-SiLU blocks run on bf16 operands only)")
         self._check_width(arch.width)
         self._finish_packed(directory, arch, arch.max_pos, NomicBertTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="[PAD]"))
+
+    def _load_nomic_moe(self, directory: str, arch, sd) -> None:
+        """the mixture-of-experts NomicBERT (model_type "nomic_bert" with moe_every_n_layers and num_experts: nomic-embed-text-v2-moe, the hub's original
+        tensor names; custom remote code to the reference's AutoModel, so refused unless trustRemoteCode is set): host tokenisation by the `tokenizers`
+        library from the directory's tokenizer.json with the file's own post-processor, right-padded with <pad>, truncated at min(tokens, n_positions,
+        8192); the tower of engine/nomic_moe.py.  Pooling: the property, else 1_Pooling/config.json, else mean.  The search_query: / search_document:
+        prefixes are the caller's; the Matryoshka truncation of the model card is not applied.  bf16 operands only; no GPU tokeniser and no native request
+        queue for this family."""
+        from marqo_amd.engine.nomic_moe import NomicMoeTower
+        from marqo_amd.engine.tokenizers import HfJsonTokenizer
+        props = self.model_properties
+        if not props.trust_remote_code:
+            raise InvalidModelPropertiesError(f"{props.name} is a custom-code (mixture-of-experts NomicBERT) checkpoint: the reference loads it only with "
+                                              f"'trustRemoteCode': True")
+        self._refuse_fp8("mixture-of-experts NomicBERT encoders (their rotary blocks and grouped GEMM run on bf16 operands only)")
+        self._check_width(arch.width)
+        self._finish_packed(directory, arch, arch.max_pos, NomicMoeTower, sd, lambda: HfJsonTokenizer.plain(directory, pad_fallback="<pad>"))
 
     def _load_jina_v3(self, directory: str, arch, sd) -> None:
         """a Jina v3 checkpoint in transformers' own form (model_type "jina_embeddings_v3": jinaai/jina-embeddings-v3-hf; native in transformers, so
