@@ -2009,6 +2009,34 @@ size_t mq_nomic_moe_workspace_bytes(const mq_nomic_moe_cfg* cfg, int64_t rows, i
 int mq_encode_nomic_moe(const mq_nomic_moe_cfg* cfg, const mq_nomic_moe_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                         const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ColBERT rerankers: late-interaction MaxSim scoring on the BERT tower (csrc/colbert.hip; engine/rerank.py ColbertTower) ----------------------
+ *   mq_maxsim:      d_scores fp32 [n]: score[i] = sum over the Lq query rows of max over the kept tokens j of document i of q . d_j.  d_q bf16 [Lq, D],
+ *                   d_docs bf16 [rows, D] packed (document i = rows d_cu[i] .. d_cu[i + 1] - 1, d_cu int32 [n + 1], clamped to `rows`), d_keep uint8
+ *                   [rows] (0: the token never wins).  fp32 accumulation (one MFMA chain over k = 0, 32, ... per dot product), fp32 maxima and sum in
+ *                   a fixed order: a document's bits depend on Q and its own rows only.  A document without a kept token scores -inf.
+ *                   Lq 1 .. 64, D 64 | 96 | 128.
+ *   mq_colbert_project: d_out bf16 [rows, D] = y / max(||y||, eps), y = d_linear_w bf16(x) (d_x fp32 [rows, W], d_linear_w bf16 [D, W], no bias; fp32
+ *                   accumulation, norm and quotient, one rounding at the end).  W % 64 == 0, W <= 2048, D 64 | 96 | 128, eps > 0.
+ *   mq_attention_keyprefix: mq_attention(MQ_MASK_NONE) on sequences of n_rows <= 64 rows whose every row attends keys [0, n_keys) only
+ *                   (1 <= n_keys <= n_rows; n_keys == n_rows: full attention).  d_qkv bf16 [rows, 3 W], d_out bf16 [rows, W]; cu_seqlens [nseq + 1] and
+ *                   n_keys [nseq] on the device and on the host (the host copies are checked and read during the call only).  Head widths: mq_attention's.
+ *   mq_score_colbert: ONE query against nseq documents.  d_query_ids int32 [Lq] ([CLS] [Q] pieces [SEP] [MASK] ...), rows [n_keys, Lq) of the query are
+ *                   attention queries but no row's keys; d_doc_ids int32 [rows] packed by d_cu_seqlens / h_cu_seqlens (lengths 1 .. cfg->max_pos).
+ *                   Embedding and blocks as mq_encode_bert runs them (the query's blocks with mq_attention_keyprefix), mq_colbert_project (eps 1e-12)
+ *                   on both sides, keep = !d_skip[id] (d_skip uint8 [cfg->vocab], NULL: every token is kept), mq_maxsim -> d_scores fp32 [nseq].
+ *                   d_query_emb bf16 [Lq, D] / d_doc_emb bf16 [rows, D] (NULL ok): the unit rows.  bf16 operands only; cfg->pool and the projection
+ *                   head fields of cfg / w are not read.  Scratch: mq_score_colbert_workspace_bytes(cfg, D, Lq, rows, nseq). */
+int mq_maxsim(const void* d_q, const void* d_docs, const int32_t* d_cu, const uint8_t* d_keep, int64_t n, int64_t rows, int32_t Lq, int32_t D,
+              float* d_scores, void* stream);
+int mq_colbert_project(const float* d_x, const void* d_linear_w, void* d_out, int64_t rows, int32_t W, int32_t D, float eps, void* stream);
+int mq_attention_keyprefix(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens, const int32_t* d_n_keys,
+                           const int32_t* h_n_keys, int64_t nseq, int32_t W, int32_t heads, void* stream);
+size_t mq_score_colbert_workspace_bytes(const mq_bert_cfg* cfg, int32_t D, int32_t Lq, int64_t rows, int64_t nseq);
+int mq_score_colbert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const void* d_linear_w, int32_t D, const uint8_t* d_skip,
+                     const int32_t* d_query_ids, int32_t Lq, int32_t n_keys, const int32_t* d_doc_ids, const int32_t* d_cu_seqlens,
+                     const int32_t* h_cu_seqlens, int64_t nseq, float* d_scores, void* d_query_emb, void* d_doc_emb, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe", "colbert")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -606,6 +606,13 @@ _SIGNATURES = {
     "mq_moe_combine_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
     "mq_nomic_moe_workspace_bytes": (C.c_size_t, [C.POINTER(NomicMoeCfg), C.c_int64, C.c_int64]),
     "mq_encode_nomic_moe": (C.c_int, [C.POINTER(NomicMoeCfg), C.POINTER(NomicMoeWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # ColBERT rerankers: MaxSim scoring, the projection + L2 step, key-prefix attention, the tower (csrc/colbert.hip; engine/rerank.py ColbertTower)
+    "mq_maxsim": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    "mq_colbert_project": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    "mq_attention_keyprefix": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "mq_score_colbert_workspace_bytes": (C.c_size_t, [C.POINTER(BertCfg), C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
+    "mq_score_colbert": (C.c_int, [C.POINTER(BertCfg), C.POINTER(BertWeights), _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P,
+                                   _P, _P, C.c_size_t, _P]),
     "mq_tune":(C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),
@@ -637,7 +644,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-Rpass-analysis=kernel-resource-usage"]  # the remarks feed the no-scratch check below
     # units compiled without the packed fp32 VALU forms (v_pk_add / mul / fma_f32): the compiler then pairs no fp32 arithmetic of their epilogues
-    unit_flags = {"moe": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+    # (colbert: nothing to gain — its kernels' VGPR counts and bits are the same either way, checked — so the unit takes the conservative form that units
+    # added since moe take: scalar fp32 VALU only, one code-generation path less to trust in kernels whose results are compared bit for bit)
+    unit_flags = {u: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] for u in ("moe", "colbert")}
 
     def compile_one(src: str):
         obj = obj_dir / (Path(src).stem + ".o")

@@ -17,6 +17,8 @@ batch loop — is `_PairScorer.score`.  A fifth is a decoder: the Qwen3 reranker
 system prompt, the instruction and the query — the same for every document under the causal mask — are computed once).  A sixth is Gemma-2B
 (GemmaRerankerTower: BAAI/bge-reranker-v2-gemma, `GemmaForCausalLM` judged by the logit of `Yes`, or its one-logit `GemmaForSequenceClassification`
 conversion; FlagEmbedding's piecewise-tokenised input, on the host; one mq_score_gemma_pairs call per batch with `[bos] A: query` computed once).
+A seventh is late interaction (ColbertTower: colbert-ai checkpoints, `bert.*` + `linear.weight`; query and documents encoded separately, every token
+projected to a unit vector, one mq_score_colbert call per batch of documents ending in the MaxSim kernel of csrc/colbert.hip).
 `load_cross_encoder_tower` picks the class from a directory's config.json.
 """
 from __future__ import annotations
@@ -240,6 +242,8 @@ class CrossEncoderTower(_PairScorer, BertTower):
         vocab.json + merges.txt, tokenizer_config.json"""
         cfg, sd = checkpoint.load_hf_dir(directory)
         mtype = cfg.get("model_type", "bert")
+        if colbert_layout(directory, cfg, sd):      # late interaction: its own tower (below), no classifier
+            return ColbertTower._from_loaded(directory, cfg, sd, device)
         if mtype == "modernbert":       # its own tower and head (below)
             return ModernBertCrossEncoderTower._from_loaded(directory, cfg, sd, device)
         byte_bpe = False
@@ -832,11 +836,196 @@ class GemmaRerankerTower(_PrefixPairScorer, _PackedTextTower):
         return self.score_rows(shared, segs)
 
 
+# ---- ColBERT rerankers: late interaction on the BERT tower --------------------------------------------------------------------------------------------
+# The checkpoint layout (`bert.*` + `linear.weight` [dim, W], no bias), the keys of artifact.metadata, the marker tokens ([Q] = [unused0], [D] = [unused1])
+# and the punctuation skiplist are restated from memory of the colbert-ai package; neither it nor a real checkpoint has been run here (README.md).
+COLBERT_DIMS = (64, 96, 128)
+
+
+@dataclasses.dataclass(frozen=True)
+class ColbertSettings:
+    query_maxlen: int = 32
+    doc_maxlen: int = 180
+    dim: int = 128
+    mask_punctuation: bool = True
+    attend_to_mask_tokens: bool = False
+
+
+def colbert_settings(metadata: Optional[dict], linear_shape: Sequence[int], width: int, where: str = "artifact.metadata") -> ColbertSettings:
+    """the settings of a ColBERT checkpoint from its artifact.metadata (None / missing keys: the package's defaults; `dim` defaults to the rows of
+    linear.weight).  What is not served is refused with a ValueError that names the key."""
+    m = dict(metadata or {})
+    rows, cols = (int(v) for v in linear_shape)
+    if cols != width:
+        raise ValueError(f"{where}: linear.weight is [{rows}, {cols}] but the encoder is {width} wide")
+    sim = m.get("similarity", "cosine")
+    if sim != "cosine":
+        raise ValueError(f"{where}: similarity={sim!r} is not served (MaxSim over unit vectors is the 'cosine' form only)")
+    dim = int(m.get("dim", rows))
+    if dim != rows or dim not in COLBERT_DIMS:
+        raise ValueError(f"{where}: dim={dim} is not served (linear.weight has {rows} rows; the scoring kernel runs dim {' / '.join(map(str, COLBERT_DIMS))})")
+    qmax = int(m.get("query_maxlen", 32))
+    if not 4 <= qmax <= 64:
+        raise ValueError(f"{where}: query_maxlen={qmax} is not served (4 .. 64: the query is one 64-row block of the scoring kernel)")
+    dmax = int(m.get("doc_maxlen", 180))
+    if dmax < 4:
+        raise ValueError(f"{where}: doc_maxlen={dmax} must be at least 4")
+    return ColbertSettings(qmax, dmax, dim, bool(m.get("mask_punctuation", True)), bool(m.get("attend_to_mask_tokens", False)))
+
+
+def colbert_layout(directory: str, cfg: dict, keys) -> bool:
+    """is this checkpoint a colbert-ai ColBERT (`bert.*` + `linear.weight`, no `classifier.*`)?  The late-interaction layouts that are not served are
+    refused here, naming the key that tells them apart."""
+    keys = set(keys)
+    if any(k.startswith("classifier.") for k in keys):      # a cross-encoder, whatever else its directory carries
+        return False
+    if os.path.isdir(os.path.join(directory, "1_Dense")):
+        raise ValueError(f"{directory}: a PyLate-layout checkpoint (its projection lives in '1_Dense') is not served; only the colbert-ai layout "
+                         f"(linear.weight next to bert.*) is")
+    if "linear.weight" not in keys:
+        return False
+    mtype = cfg.get("model_type", "bert")
+    if mtype != "bert" or not any(k.startswith("bert.") for k in keys):
+        raise ValueError(f"{directory}: model_type={mtype!r} with a ColBERT projection (linear.weight) is not served (BERT bases only: XLM-RoBERTa and "
+                         f"ModernBERT ColBERTs are out of scope)")
+    return True
+
+
+def colbert_query_row(pieces: Sequence[int], query_maxlen: int, cls_id: int, sep_id: int, mask_id: int, q_id: int) -> Tuple[np.ndarray, int]:
+    """-> (ids int32 [query_maxlen], unpadded length): [CLS] [Q] pieces [SEP], cut to query_maxlen with [SEP] kept, filled with [MASK]"""
+    body = [int(cls_id), int(q_id)] + [int(p) for p in pieces][:query_maxlen - 3] + [int(sep_id)]
+    return np.asarray(body + [int(mask_id)] * (query_maxlen - len(body)), dtype=np.int32), len(body)
+
+
+def colbert_doc_rows(ids: Tensor, marker_id: int) -> Tensor:
+    """[n, S] rows [CLS] pieces [SEP] pad -> [n, S + 1] rows [CLS] [D] pieces [SEP] pad (memory movement only; every length grows by one)"""
+    marker = torch.full((ids.shape[0], 1), int(marker_id), dtype=ids.dtype, device=ids.device)
+    return torch.cat((ids[:, :1], marker, ids[:, 1:]), dim=1).contiguous()
+
+
+def colbert_skip_table(vocab: Dict[str, int], size: int) -> np.ndarray:
+    """uint8 [size]: 1 at the ids of the single-character `string.punctuation` pieces (the tokens a document's MaxSim never picks)"""
+    import string
+    t = np.zeros(size, dtype=np.uint8)
+    for ch in string.punctuation:
+        i = vocab.get(ch)
+        if i is not None and 0 <= i < size:
+            t[i] = 1
+    return t
+
+
+class ColbertTower(BertTower):
+    """A colbert-ai checkpoint (colbert-ir/colbertv2.0, answerdotai/answerai-colbert-small-v1): `bert.*` = the encoder, `linear.weight` [dim, W] = the
+    projection of every token to a unit vector; score(q, d) = sum over the query_maxlen query rows of the best dot product among the document's kept
+    tokens.  One query against n documents is ONE mq_score_colbert call per batch of documents (each call encodes the query again: query_maxlen rows
+    next to a batch of up to max_rows_per_call): the query's [MASK] padding rows are queries of its
+    attention but no row's keys (attend_to_mask_tokens = false: mq_attention_keyprefix), documents are ordinary packed sequences, tokenised on the GPU.
+    score() returns (maxsim, maxsim / query_maxlen): the second array, in [-1, 1], is the one the result plumbing sorts by."""
+
+    def __init__(self, arch: archs.BertArch, sd: Dict[str, Tensor], device: str, tokenizer, settings: ColbertSettings, model_max_length: int = 512):
+        if arch.glu or arch.rope_theta is not None or arch.rel_buckets or arch.pos_offset:
+            raise ValueError("ColBERT rerankers run on plain BERT encoders (model_type 'bert')")
+        gone = [t for t in ("[unused0]", "[unused1]", tokenizer.mask) if t not in tokenizer.vocab]
+        if gone:
+            raise ValueError(f"vocab.txt has no {' / '.join(gone)} token (the [Q] / [D] markers and the query's padding)")
+        lin = _need(sd, "linear.weight", (settings.dim, arch.width))
+        super().__init__(arch, {k[len("bert."):]: v for k, v in sd.items() if k.startswith("bert.")}, device, pooling="cls", precision="bf16")
+        self.settings = settings
+        self.tokenizer = tokenizer
+        self.q_id, self.d_id, self.mask_id = (int(tokenizer.vocab[t]) for t in ("[unused0]", "[unused1]", tokenizer.mask))
+        self.linear_w = self._h.bf16(lin)               # (a device pointer; the holder keeps the tensor)
+        self._skip = self._to_device(torch.from_numpy(colbert_skip_table(tokenizer.vocab, arch.vocab))) if settings.mask_punctuation else None
+        self.model_max_length = int(min(model_max_length, arch.max_pos))
+        from marqo_amd.engine.gpu_tokenizers import DeviceWordPieceTokenizer
+        self.device_tokenizer = DeviceWordPieceTokenizer(tokenizer, str(self.device))
+
+    @classmethod
+    def _from_loaded(cls, directory: str, cfg: dict, sd: Dict[str, Tensor], device: str) -> "ColbertTower":
+        meta = None
+        p = os.path.join(directory, "artifact.metadata")
+        if os.path.isfile(p):
+            try:
+                with open(p) as f:
+                    meta = json.load(f)
+            except (OSError, ValueError) as e:
+                raise ValueError(f"{p} cannot be read ({e})") from e
+        try:
+            arch = archs.bert_arch_from_hf_config(cfg)
+        except KeyError as e:
+            raise ValueError(f"{directory}: {e}") from e
+        settings = colbert_settings(meta, tuple(_need(sd, "linear.weight").shape), arch.width, p)
+        lower, max_len = _tokenizer_settings(directory)
+        try:
+            return cls(arch, sd, device, WordPieceTokenizer(directory, do_lower_case=lower), settings, model_max_length=max_len)
+        except ValueError as e:
+            raise ValueError(f"{directory}: {e}") from e
+
+    def query_row(self, query: str) -> Tuple[np.ndarray, int]:
+        """(ids int32 [query_maxlen], n_keys): the host half of score() for the query"""
+        row, n = colbert_query_row(self.tokenizer.encode(query)[1:-1], self.settings.query_maxlen, self.tokenizer.cls_id, self.tokenizer.sep_id,
+                                   self.mask_id, self.q_id)
+        return row, self.settings.query_maxlen if self.settings.attend_to_mask_tokens else n
+
+    def doc_rows(self, docs: Sequence[str], cap: int) -> Tuple[Tensor, np.ndarray]:
+        """-> (ids int32 [n, cap] on the device: [CLS] [D] pieces [SEP] pad, lengths int64 [n]), rows cut to `cap` tokens"""
+        d_ids, lens = self.device_tokenizer.encode_device(list(docs), cap - 1)
+        return colbert_doc_rows(d_ids, self.d_id), lens.numpy().astype(np.int64) + 1
+
+    def score(self, query: str, docs: Sequence[str], max_length: int = 512, return_embeddings: bool = False):
+        """-> (maxsim, maxsim / query_maxlen) fp32 [len(docs)] on the host, in the order of `docs`; documents are cut to min(doc_maxlen, max_length, the
+        tokenizer's model_max_length) tokens.  return_embeddings: also (query rows bf16 [query_maxlen, dim], [document rows bf16 [len_i, dim]]), on the
+        device (what the tests compare)."""
+        if not isinstance(query, str) or not all(isinstance(d, str) for d in docs):
+            raise TypeError("a reranker scores (str, str) pairs")
+        n, st = len(docs), self.settings
+        if n == 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        cap = int(min(st.doc_maxlen, max_length, self.model_max_length))
+        if cap < 4:
+            raise ValueError(f"max_length={max_length} must be at least 4")
+        lib, dev, Lq, D = self.lib, self.device, st.query_maxlen, st.dim
+        q_row, n_keys = self.query_row(query)
+        with request_stream(dev), torch.cuda.device(dev):
+            d_q = self._to_device(torch.from_numpy(q_row))
+            d_docs, dlen = self.doc_rows(docs, cap)
+            order = np.argsort(-dlen, kind="stable")            # longest first: a batch holds documents of similar length
+            inv = np.empty(n, dtype=np.int64)
+            inv[order] = np.arange(n)
+            sorted_len = dlen[order]
+            d_docs = d_docs.index_select(0, self._to_device(torch.from_numpy(order)))
+            scores = torch.empty(n, dtype=torch.float32, device=dev)
+            q_emb = torch.empty(Lq, D, dtype=torch.bfloat16, device=dev) if return_embeddings else None
+            d_embs = [None] * n
+            stream = self._stream()
+            with _large_call(dev, int(sorted_len.sum()) + Lq):
+                for s0, s1 in self._chunks(sorted_len):
+                    m = s1 - s0
+                    cu_np = np.zeros(m + 1, dtype=np.int32)
+                    np.cumsum(sorted_len[s0:s1], out=cu_np[1:])
+                    rows = int(cu_np[-1])
+                    cu = torch.from_numpy(cu_np)
+                    d_cu = self._to_device(cu)
+                    d_ids = torch.empty(rows, dtype=torch.int32, device=dev)
+                    L.check(lib.mq_pack_ids(d_docs[s0:s1].data_ptr(), d_docs.shape[1], d_cu.data_ptr(), m, d_ids.data_ptr(), stream), "mq_pack_ids")
+                    d_emb = torch.empty(rows, D, dtype=torch.bfloat16, device=dev) if return_embeddings else None
+                    ws = self._workspace(lib.mq_score_colbert_workspace_bytes(C.byref(self.cfg), D, Lq, rows, m))
+                    L.check(lib.mq_score_colbert(C.byref(self.cfg), C.byref(self.w), self.linear_w, D, L.ptr(self._skip), d_q.data_ptr(), Lq, n_keys,
+                                                 d_ids.data_ptr(), d_cu.data_ptr(), cu.data_ptr(), m, scores[s0:s1].data_ptr(), L.ptr(q_emb), L.ptr(d_emb),
+                                                 ws.data_ptr(), ws.numel(), stream), "mq_score_colbert")
+                    if return_embeddings:
+                        for j in range(m):
+                            d_embs[int(order[s0 + j])] = d_emb[int(cu_np[j]):int(cu_np[j + 1])]
+            out = scores.cpu().numpy()[inv]
+        res = np.ascontiguousarray(out), np.ascontiguousarray(out / np.float32(Lq))
+        return (*res, q_emb, d_embs) if return_embeddings else res
+
+
 def load_cross_encoder_tower(directory: str, device: str):
     """the cross-encoder tower of a local Hugging Face directory, by its config.json: model_type "deberta-v2" -> DebertaCrossEncoderTower.from_dir,
     "deberta" (v1) is refused here by name, "qwen3" -> QwenRerankerTower.from_dir, "gemma" -> GemmaRerankerTower.from_dir ("gemma2", "gemma3" and
     "gemma3_text" are refused there by name), everything else -> CrossEncoderTower.from_dir (which picks among BERT, XLM-RoBERTa / RoBERTa and ModernBERT
-    and refuses the rest, "qwen3" and "gemma" included when it is called directly)"""
+    and refuses the rest, "qwen3" and "gemma" included when it is called directly; a BERT directory in the colbert-ai layout — `linear.weight`, no
+    `classifier.*` — comes back from it as a ColbertTower)"""
     mtype = None
     try:
         with open(os.path.join(directory, "config.json")) as f:
