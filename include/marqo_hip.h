@@ -994,6 +994,7 @@ int mq_queue_destroy(mq_queue* q);
  *       four rows per wave from 16384 rows
  *   "xcd_band" (MQ_XCD_BAND, 1): 0 = the row-wise kernels do not follow the GEMMs' XCD banding
  *   "attn_waves" (no variable, 0): 0 = auto, 4 / 8 wave64s per attention workgroup
+ *   "w8_waves", "w8_depth" (no variable, 0): mq_gemm_small_w8: 0 = auto, 4 / 8 wave64s per workgroup; 0 = auto, 2 / 4 k-chunks of weight loads per group
  *   "gemm_addr_limit_mb" (no variable, 0): bytes / 2^20 one launch may address per operand, 0 = the 4 GiB of a 32-bit buffer offset: taller
  *       matrices go in row chunks
  * An unknown key is MQ_ERR_INVALID ("unknown key"). */
@@ -1922,6 +1923,40 @@ int mq_pool_wide(const float* d_x, const int32_t* d_cu, int64_t nseq, float* d_o
 size_t mq_llama_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows, int64_t nseq);
 int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                     int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Mistral / Llama queries from e4m3 weights: the W8A16 skinny GEMM, its quantiser and the tower entry point
+ * (csrc/gemm_small_w8.hip, csrc/llama.hip; engine/llama.py LlamaTower(weight_precision="e4m3")) ------------------------------------------------------------
+ * A single query of these towers is bound by weight bytes; e4m3 weights with bf16 activations halve them.  Additions to ABI 15: nothing above changes.
+ * Each entry point judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and
+ * allocates nothing.
+ *
+ * The weight format: d_W8 holds e4m3fn codes [N, K] row-major, K % 64 == 0; d_scale fp32 [N] holds one POWER OF TWO per output row,
+ * 2^ceil(log2(absmax_n / 448)) (1 for an all-zero row; never below 2^-100); codes = RNE(w / scale[n]): nothing saturates and no NaN code is emitted.  An
+ * e4m3 value times 2^k has 3 mantissa bits, so decode(code) * scale[n] is exactly a bf16 value.
+ *
+ *   mq_quantize_weights_pow2: d_W_bf16 [N, ldw] -> d_W8 [N, ld8], d_scale [N]; the bf16 rows are REWRITTEN in place with decode(code) * scale, so the
+ *                   bf16 copy and the e4m3 copy hold the same numbers (calls too tall for the skinny kernel run the tiled bf16 kernels on the former).
+ *   mq_gemm_small_w8_ok: 1 where mq_gemm_small_w8 takes the shape: the rows of the skinny bf16 kernels (<= "small_m" rows in one group, up to
+ *                   "small_m_grouped" in row groups of <= 80), N % 4 == 0, K % 64 == 0.
+ *   mq_gemm_small_w8: d_out [M, ldc] = epi((d_A bf16 [M, lda] @ decode(d_W8)^T) * d_scale[n]): the e4m3 fragments go global -> VGPR, are converted
+ *                   exactly to bf16 in registers and multiplied on the bf16 MFMA; the fp32 sum takes the scale once.  A row's bits do not depend on the
+ *                   other rows of the call.  flags: 0 (bf16 out), MQ_EPI_BIAS (bf16 out), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32 (fp32 residual,
+ *                   which may alias d_out); lda % 8 == 0, ldw % 16 == 0, ldc % 4 == 0.
+ *   mq_encode_llama_w8: mq_encode_llama with the four block GEMMs of every layer on mq_gemm_small_w8 wherever mq_gemm_small_w8_ok holds, and on
+ *                   mq_gemm_bf16 over w's (rewritten) bf16 weights elsewhere.  w8: host array of cfg->layers entries. */
+typedef struct mq_w8_layer {
+    const void* qkv_w8;  const float* qkv_scale;    /* [(Q + 2 KV) hd, W] codes, [(Q + 2 KV) hd] */
+    const void* out_w8;  const float* out_scale;    /* [W, Q hd], [W] */
+    const void* ug_w8;   const float* ug_scale;     /* [2 F, W], [2 F] */
+    const void* down_w8; const float* down_scale;   /* [W, F], [W] */
+} mq_w8_layer;
+
+int mq_quantize_weights_pow2(void* d_W_bf16, int64_t ldw, void* d_W8, int64_t ld8, float* d_scale, int64_t N, int64_t K, void* stream);
+int mq_gemm_small_w8_ok(int64_t M, int64_t N, int64_t K);
+int mq_gemm_small_w8(const void* d_A, int64_t lda, const void* d_W8, int64_t ldw, const float* d_scale, const float* d_bias, const void* d_residual,
+                     void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                       const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Mixture-of-experts NomicBERT (nomic-embed-text-v2-moe): router, device-side plan, grouped bf16 GEMM, and the tower
  * (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py) ---------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ mq_knob mq_gemm_small_max_rows, mq_gemm_small_group_rows;
 mq_knob mq_ln_prefetch, mq_ln_rows_per_wave, mq_ln_bf16_wide;
 mq_knob mq_xcd_band;
 mq_knob mq_attention_waves;
+mq_knob mq_w8_waves, mq_w8_depth;
 
 namespace {
 
@@ -43,6 +44,8 @@ const Knob g_knobs[] = {
     {"ln_bf16_wide", "MQ_LN_BF16_WIDE", 1, &mq_ln_bf16_wide},    // 0 = bf16 rows take the generic LayerNorm, 1 = the 16-byte form above small_m rows, 4 = that form with four rows per wave from 16384 rows
     {"xcd_band", "MQ_XCD_BAND", 1, &mq_xcd_band},                // 0 = the row-wise kernels do not follow the GEMMs' XCD banding
     {"attn_waves", nullptr, 0, &mq_attention_waves},             // 0 = auto, 4 / 8 wave64s per attention workgroup, 5 = five waves for 65..80-token sequences (else auto)
+    {"w8_waves", nullptr, 0, &mq_w8_waves},                      // the W8A16 skinny GEMM: 0 = auto, 4 / 8 wave64s per workgroup
+    {"w8_depth", nullptr, 0, &mq_w8_depth},                      // ... 0 = auto, 2 / 4 k-chunks of weight loads per group
     {"gemm_addr_limit_mb", nullptr, 0, nullptr},                 // bytes / 2^20 one launch may address per operand, 0 = the 4 GiB - 1 of a 32-bit buffer offset: taller matrices go in row chunks
 };
 

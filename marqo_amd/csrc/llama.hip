@@ -184,8 +184,11 @@ extern "C" size_t mq_llama_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows
     return plan(cfg, rows, nseq).total;
 }
 
-extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
-                               int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
+namespace {
+// the tower; w8 (nullable): the e4m3 copies of the four block weights of every layer — a GEMM whose shape the W8A16 skinny kernel takes streams those,
+// every other call runs mq_gemm_bf16 on the bf16 weight, which mq_quantize_weights_pow2 has rewritten with the same numbers (gemm_small_w8.hip)
+int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                 const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
     MQ_TRY(check_cfg(cfg));
     MQ_CHECK_ARG(w && d_out, "mq_encode_llama: null pointer");
     MQ_CHECK_ARG(w->tok_emb && w->final_norm_g && w->zeros && w->d_inv_freq && w->layers, "mq_encode_llama: null weight pointer");
@@ -193,6 +196,11 @@ extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w
         const mq_qwen_layer& b = w->layers[l];
         MQ_CHECK_ARG(b.input_norm_g && b.qkv_w && b.out_w && b.post_norm_g && b.ug_w && b.down_w, "mq_encode_llama: layer %d has null weights", l);
         MQ_CHECK_ARG(!b.qkv_b && !b.q_norm_g && !b.k_norm_g, "mq_encode_llama: layer %d carries a QKV bias or q / k norm weights (this block has neither)", l);
+        if (w8) {
+            const mq_w8_layer& q = w8[l];
+            MQ_CHECK_ARG(q.qkv_w8 && q.qkv_scale && q.out_w8 && q.out_scale && q.ug_w8 && q.ug_scale && q.down_w8 && q.down_scale,
+                         "mq_encode_llama_w8: layer %d has null e4m3 weights or scales", l);
+        }
     }
     if (nseq <= 0) return MQ_OK;
     int maxl = 0;
@@ -212,19 +220,26 @@ extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w
     const int res_flags = MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32;   // (the bias is w->zeros)
     const bool windowed = cfg->window > 0 && cfg->window < maxl;            // (a window no sequence of the call reaches cuts nothing)
 
+    // one block GEMM: out [rows, N] = epi(A [rows, K] @ W^T), from the e4m3 copy where the skinny kernel takes the call
+    auto gemm = [&](const void* A, int64_t lda, const void* Wb, const void* Wq, const float* sc, const float* bias, const void* res, void* out, int64_t N, int64_t K,
+                    int flags) {
+        if (Wq && mq_gemm_small_w8_ok(rows, N, K)) return mq_gemm_small_w8(A, lda, Wq, K, sc, bias, res, out, N, rows, N, K, flags, s);
+        return mq_gemm_bf16(A, lda, Wb, K, bias, (const float*)res, out, N, rows, N, K, flags, s);
+    };
     MQ_TRY(mq_embed_tokens_wide(d_ids, d_cu_seqlens, nseq, w->tok_emb, x, W, cfg->vocab, s));
     for (int l = 0; l < cfg->layers; ++l) {
         const mq_qwen_layer& b = w->layers[l];
+        const mq_w8_layer* q = w8 ? w8 + l : nullptr;
         MQ_TRY(mq_rmsnorm_wide(x, nullptr, b.input_norm_g, h, nullptr, rows, W, cfg->rms_eps, s));
-        MQ_TRY(mq_gemm_bf16(h, W, b.qkv_w, W, nullptr, nullptr, big, QKVW, rows, QKVW, W, 0, s));
+        MQ_TRY(gemm(h, W, b.qkv_w, q ? q->qkv_w8 : nullptr, q ? q->qkv_scale : nullptr, nullptr, nullptr, big, QKVW, W, 0));
         MQ_TRY(mq_qk_norm_rope(big, d_cu_seqlens, nseq, 0, Q, KV, hd, nullptr, nullptr, cfg->rms_eps, w->d_inv_freq, s));
         if (windowed) MQ_TRY(mq_attention_gqa_window(big, a, d_cu_seqlens, nseq, 0, maxl, Q, KV, hd, cfg->window, s));
         else MQ_TRY(mq_attention_gqa(big, a, d_cu_seqlens, nseq, 0, maxl, Q, KV, hd, MQ_MASK_CAUSAL, s));
-        MQ_TRY(mq_gemm_bf16(a, AW, b.out_w, AW, w->zeros, x, x, W, rows, W, AW, res_flags, s));
+        MQ_TRY(gemm(a, AW, b.out_w, q ? q->out_w8 : nullptr, q ? q->out_scale : nullptr, w->zeros, x, x, W, AW, res_flags));
         MQ_TRY(mq_rmsnorm_wide(x, nullptr, b.post_norm_g, h, nullptr, rows, W, cfg->rms_eps, s));
-        MQ_TRY(mq_gemm_bf16(h, W, b.ug_w, W, nullptr, nullptr, big, 2 * F, rows, 2 * F, W, 0, s));
+        MQ_TRY(gemm(h, W, b.ug_w, q ? q->ug_w8 : nullptr, q ? q->ug_scale : nullptr, nullptr, nullptr, big, 2 * F, W, 0));
         MQ_TRY(mq_glu(big, rows, F, MQ_ACT_SILU, 0, s));
-        MQ_TRY(mq_gemm_bf16(big, 2 * F, b.down_w, F, w->zeros, x, x, W, rows, W, F, res_flags, s));
+        MQ_TRY(gemm(big, 2 * F, b.down_w, q ? q->down_w8 : nullptr, q ? q->down_scale : nullptr, w->zeros, x, x, W, F, res_flags));
     }
     if (cfg->pool == MQ_POOL_LAST) {   // the final norm is per row: only the pooled rows take it
         MQ_TRY(mq_last_rows(d_cu_seqlens, last, nseq, s));
@@ -235,4 +250,19 @@ extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w
         MQ_TRY(mq_pool_wide(x, d_cu_seqlens, nseq, d_out, W, normalize, s));
     }
     return MQ_OK;
+}
+}  // namespace
+
+extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
+                               int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
+    return encode_llama(cfg, w, nullptr, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                                  const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes,
+                                  void* stream) {
+    MQ_CHECK_ARG(w8, "mq_encode_llama_w8: null e4m3 weights");
+    MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
+                 "mq_encode_llama_w8: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the e4m3 rows are walked in 64-deep chunks)");
+    return encode_llama(cfg, w, w8, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }

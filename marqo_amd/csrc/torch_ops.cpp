@@ -368,6 +368,45 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> moe_mlp(const at::Tensor& h, cons
     return {row_slot, slot_row, expert_off};
 }
 
+// ---- W8A16: Mistral / Llama queries from e4m3 weights (kernel-level entries; the tower call goes through the C ABI like every packed text tower) ----
+// W bf16 [N, K] (REWRITTEN in place with the dequantised values) -> (W8 uint8 [N, K] e4m3fn codes, scale fp32 [N], a power of two per row)
+std::tuple<at::Tensor, at::Tensor> quantize_weights_pow2(at::Tensor W) {
+    need_dev(W, at::kBFloat16, "W");
+    TORCH_CHECK(W.dim() == 2, "marqo_hip::mq_quantize_weights_pow2: W [N,K]");
+    const int64_t N = W.size(0), K = W.size(1);
+    at::Tensor W8 = at::empty({N, K}, W.options().dtype(at::kByte)), scale = at::empty({N}, W.options().dtype(at::kFloat));
+    check_rc(mq_quantize_weights_pow2(W.data_ptr(), K, W8.data_ptr(), K, (float*)scale.data_ptr(), N, K, stream_of(W)), "mq_quantize_weights_pow2");
+    return {W8, scale};
+}
+
+at::Tensor gemm_small_w8(const at::Tensor& A, const at::Tensor& W8, const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                         const c10::optional<at::Tensor>& residual, int64_t flags) {
+    need_dev(A, at::kBFloat16, "A");
+    need_dev(W8, at::kByte, "W8");
+    need_dev(scale, at::kFloat, "scale");
+    TORCH_CHECK(A.dim() == 2 && W8.dim() == 2 && A.size(1) == W8.size(1) && scale.numel() == W8.size(0), "marqo_hip::mq_gemm_small_w8: A [M,K], W8 [N,K], scale [N]");
+    const int64_t M = A.size(0), K = A.size(1), N = W8.size(0);
+    const bool f32 = (flags & MQ_EPI_OUT_F32) != 0;
+    const float* b = nullptr;
+    const void* r = nullptr;
+    if (flags & MQ_EPI_BIAS) {
+        TORCH_CHECK(bias.has_value(), "marqo_hip::mq_gemm_small_w8: MQ_EPI_BIAS without bias");
+        need_dev(*bias, at::kFloat, "bias");
+        TORCH_CHECK(bias->numel() == N, "bias must be [N]");
+        b = (const float*)bias->data_ptr();
+    }
+    if (flags & MQ_EPI_RESIDUAL) {
+        TORCH_CHECK(residual.has_value(), "marqo_hip::mq_gemm_small_w8: MQ_EPI_RESIDUAL without residual");
+        need_dev(*residual, at::kFloat, "residual");
+        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == N, "residual must be [M,N]");
+        r = residual->data_ptr();
+    }
+    at::Tensor out = at::empty({M, N}, A.options().dtype(f32 ? at::kFloat : at::kBFloat16));
+    check_rc(mq_gemm_small_w8(A.data_ptr(), K, W8.data_ptr(), K, (const float*)scale.data_ptr(), b, r, out.data_ptr(), N, M, N, K, (int)flags, stream_of(A)),
+             "mq_gemm_small_w8");
+    return out;
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -398,6 +437,8 @@ TORCH_LIBRARY(marqo_hip, m) {
           "Tensor(a!) out) -> ()");
     m.def("mq_moe_route(Tensor x, Tensor router_w, int top_k) -> (Tensor, Tensor)");
     m.def("mq_moe_mlp(Tensor h, Tensor top_e, Tensor top_w, Tensor w1, Tensor w2t, int bm, Tensor(a!) Y) -> (Tensor, Tensor, Tensor)");
+    m.def("mq_quantize_weights_pow2(Tensor(a!) W) -> (Tensor, Tensor)");
+    m.def("mq_gemm_small_w8(Tensor A, Tensor W8, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -420,4 +461,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_attention_gqa_window", &attention_gqa_window);
     m.impl("mq_moe_route", &moe_route);
     m.impl("mq_moe_mlp", &moe_mlp);
+    m.impl("mq_quantize_weights_pow2", &quantize_weights_pow2);
+    m.impl("mq_gemm_small_w8", &gemm_small_w8);
 }

@@ -2,11 +2,14 @@
 SFR-Embedding-Mistral, Linq-Embed-Mistral, Llama-2-shaped fine-tunes) -> HBM layout -> one mq_encode_llama call per batch of packed sequences
 (csrc/llama.hip; the causal sliding-window grouped-query attention kernel: csrc/attention_gqa.hip).
 
-bf16 GEMM operands, fp32 residual stream, 64- or 128-wide heads, widths up to 4096.  The block is the Qwen tower's without q / k norm and without biases,
+bf16 GEMM operands, fp32 residual stream, 64- or 128-wide heads, widths up to 4096.  weight_precision="e4m3" keeps a second, e4m3 copy of the four block
+weights (one power-of-two scale per output row) that the query path streams instead of the bf16 one (csrc/gemm_small_w8.hip: W8A16, bf16 activations);
+the bf16 copy is rewritten with the dequantised values, so every batch size embeds with the same model.  The block is the Qwen tower's without q / k norm and without biases,
 so the checkpoint-to-tensor transform (names, the fused QKV and (up | gate) weights) is engine/tower_weights.py::qwen_state_dict and the weight structs
 are the Qwen tower's."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict
 
 import torch
@@ -23,8 +26,10 @@ class LlamaTower(_PackedTextTower):
     """Mistral / Llama decoder + last-token / mean pooling (+ L2); the call loop and the input checks are _PackedTextTower's."""
     family = "llama"
 
-    def __init__(self, arch: LlamaArch, sd: Dict[str, Tensor], device: str, pooling: str = "last", precision: str = "bf16"):
+    def __init__(self, arch: LlamaArch, sd: Dict[str, Tensor], device: str, pooling: str = "last", precision: str = "bf16", weight_precision: str = "bf16"):
         super().__init__(device)
+        if weight_precision not in ("bf16", "e4m3"):
+            raise ValueError(f"weight_precision must be 'bf16' or 'e4m3', got {weight_precision!r}")
         _check_precision(precision, ("bf16",), f"the Mistral / Llama tower runs on bf16 operands only (its RMSNorm / rotary / gated-SiLU blocks have no e4m3 "
                                                f"kernels), got precision {precision!r}")
         if arch.head_dim not in (64, 128):
@@ -37,7 +42,7 @@ class LlamaTower(_PackedTextTower):
             raise ValueError(f"window must be at least 1 or None, got {arch.window}")
         if pooling not in ("last", "mean"):
             raise ValueError(f"pooling must be 'last' or 'mean', got {pooling!r}")
-        self.precision, self.arch, self.pooling = precision, arch, pooling
+        self.precision, self.arch, self.pooling, self.weight_precision = precision, arch, pooling, weight_precision
         self._fp8 = None
         h = self._h
         t = qwen_state_dict(arch, sd, tower="Mistral / Llama")
@@ -55,3 +60,32 @@ class LlamaTower(_PackedTextTower):
         self.cfg = L.LlamaCfg(width=W, layers=arch.layers, q_heads=arch.heads, kv_heads=arch.kv_heads, head_dim=arch.head_dim, mlp_dim=arch.mlp_dim,
                               vocab=arch.vocab, max_pos=arch.max_pos, pool=L.MQ_POOL_LAST if pooling == "last" else L.MQ_POOL_MEAN,
                               window=int(arch.window or 0), rms_eps=arch.rms_eps, reserved0=0)
+        if weight_precision == "e4m3":
+            self._quantize_e4m3()
+
+    def block_weight(self, layer: int, name: str) -> Tensor:
+        """the bf16 device tensor of one block matrix ('qkv', 'out', 'ug', 'down') as the kernels read it (with weight_precision 'e4m3': dequantised)"""
+        ptr = getattr(self._layers[layer], name + "_w")
+        return next(t for t in self._h.tensors if t.data_ptr() == ptr)
+
+    def _quantize_e4m3(self) -> None:
+        """the e4m3 copy of every layer's four matrices, made on the device from the uploaded bf16 weights, which are rewritten with the dequantised
+        values (mq_quantize_weights_pow2): 1.5 x the weight memory, one model on the skinny and the tiled path"""
+        a = self.arch
+        if a.width % 64 or a.mlp_dim % 64 or (a.heads * a.head_dim) % 64:
+            raise ValueError("weight_precision 'e4m3' needs width, mlp_dim and heads * head_dim to be multiples of 64")
+        aw, qkvw = a.heads * a.head_dim, (a.heads + 2 * a.kv_heads) * a.head_dim
+        shapes = (("qkv", qkvw, a.width), ("out", a.width, aw), ("ug", 2 * a.mlp_dim, a.width), ("down", a.width, a.mlp_dim))
+        self._w8_layers = (L.W8Layer * a.layers)()
+        with torch.cuda.device(self.device):
+            for l in range(a.layers):
+                for name, n, k in shapes:
+                    w8 = torch.empty(n, k, dtype=torch.uint8, device=self.device)
+                    sc = torch.empty(n, dtype=torch.float32, device=self.device)
+                    L.check(self.lib.mq_quantize_weights_pow2(getattr(self._layers[l], name + "_w"), k, w8.data_ptr(), k, sc.data_ptr(), n, k, self._stream()),
+                            "mq_quantize_weights_pow2")
+                    self._h.tensors += [w8, sc]
+                    setattr(self._w8_layers[l], name + "_w8", w8.data_ptr())
+                    setattr(self._w8_layers[l], name + "_scale", sc.data_ptr())
+            torch.cuda.current_stream(self.device).synchronize()
+        self._entry = ("mq_encode_llama_w8", (self._w8_layers,))

@@ -1075,6 +1075,7 @@ class _PackedTextTower(_TextTowerBase):
     with the interface of BertTower: encode_ids(ids, attention_mask, normalize).  A subclass is its constructor — it validates the arch and builds
     self.arch / self.cfg / self.w — and `family`, which names its two library functions."""
     family = ""        # "qwen": mq_encode_qwen, mq_qwen_workspace_bytes
+    _entry = None      # (name, arguments behind the weights) of an encode entry point other than mq_encode_<family>
 
     @property
     def out_width(self) -> int:
@@ -1094,7 +1095,7 @@ class _PackedTextTower(_TextTowerBase):
         """ids / attention_mask: int [n, S], right-padded.  Only mask == 1 tokens are run (no padded position reaches a real row in the reference, and no
         pooling reads one) -> fp32 [n, out_width] on the device."""
         ids_h, lengths = _ids_and_lengths(ids, attention_mask, self.arch.max_pos)
-        name = f"mq_encode_{self.family}"
+        name, extra = self._entry or (f"mq_encode_{self.family}", ())
         ws_bytes, encode, tail = getattr(self.lib, f"mq_{self.family}_workspace_bytes"), getattr(self.lib, name), self._tail()
         tower_l2 = 1 if normalize and tail is None else 0
         out = torch.empty(int(lengths.size), self.arch.width, dtype=torch.float32, device=self.device)
@@ -1102,7 +1103,7 @@ class _PackedTextTower(_TextTowerBase):
             for a, b in self._chunks(lengths):
                 d_packed, d_cu, cu = self._stage_host(ids_h, lengths, a, b)
                 ws = self._workspace(ws_bytes(C.byref(self.cfg), d_packed.numel(), b - a))
-                L.check(encode(C.byref(self.cfg), C.byref(self.w), d_packed.data_ptr(), d_cu.data_ptr(), cu.data_ptr(), b - a, out[a:b].data_ptr(),
+                L.check(encode(C.byref(self.cfg), C.byref(self.w), *extra, d_packed.data_ptr(), d_cu.data_ptr(), cu.data_ptr(), b - a, out[a:b].data_ptr(),
                                tower_l2, ws.data_ptr(), ws.numel(), self._stream()), name)
             if tail is not None:
                 out = tail(out, bool(normalize))

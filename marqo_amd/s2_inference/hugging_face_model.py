@@ -64,6 +64,11 @@ class HuggingFaceModelProperties:
         self.engine_precision: str = p.get("enginePrecision", p.get("engine_precision", os.environ.get("MARQO_AMD_PRECISION", "bf16")))
         if self.engine_precision not in ("bf16", "fp8"):
             raise ValueError("'enginePrecision' must be 'bf16' or 'fp8'")
+        # engine extension (Mistral / Llama checkpoints): "e4m3" keeps an e4m3 copy of the block weights, one power-of-two scale per output row, that
+        # single queries stream instead of the bf16 one (activations stay bf16; engine/llama.py); every other family refuses it at load
+        self.weight_precision: str = p.get("weightPrecision", p.get("weight_precision", "bf16"))
+        if self.weight_precision not in ("bf16", "e4m3"):
+            raise ValueError("'weightPrecision' must be 'bf16' or 'e4m3'")
         b = p.get("fp8Budget", p.get("fp8_budget"))
         if b is not None and not (isinstance(b, (int, float)) and b > 0):
             raise ValueError("'fp8Budget' must be a positive number")
@@ -134,6 +139,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 arch = archs.llama_arch_from_hf_config(cfg) if cfg.get("model_type") in ("mistral", "llama") else archs.bert_arch_from_hf_config(cfg)
             except KeyError as e:
                 raise InvalidModelPropertiesError(f"{props.name}: {e}. Only BERT-family encoders run on the marqo_amd engine.") from e
+            if props.weight_precision != "bf16" and not isinstance(arch, archs.LlamaArch):
+                raise InvalidModelPropertiesError(f"{props.name}: 'weightPrecision': {props.weight_precision!r} is available for Mistral / Llama "
+                                                  f"checkpoints only (model_type {cfg.get('model_type')!r})")
             if isinstance(arch, archs.ModernBertArch):
                 self._load_modernbert(directory, arch, sd)
                 return
@@ -187,6 +195,8 @@ class HuggingFaceModel(AbstractEmbeddingModel):
             self.weights_source = directory
         elif checkpoint.synthetic_weights_enabled() and props.name in archs.HF_BERT_ARCHS:
             arch = archs.HF_BERT_ARCHS[props.name]
+            if props.weight_precision != "bf16":
+                raise InvalidModelPropertiesError(f"{props.name}: 'weightPrecision': {props.weight_precision!r} is available for Mistral / Llama checkpoints only")
             sd = synthetic.random_bert_state_dict(arch, seed=0)
             self._tokenizer = SyntheticTokenizer("bert", arch.vocab)  # (for XLM-R archs too: ids only need to be in range)
             self.weights_source = "synthetic(seed=0)"
@@ -289,9 +299,11 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         to a text (the </s> that e5-mistral's model card appends by hand is the caller's business unless tokenizer.json adds it), the tower of
         engine/llama.py.  Pooling: the property, else 1_Pooling/config.json (last token / mean), else last token.  bf16 operands only."""
         from marqo_amd.engine.llama import LlamaTower
-        self._load_decoder(directory, arch, cfg, sd, LlamaTower, "Mistral / Llama encoders", pad_fallback="</s>")
+        wp = self.model_properties.weight_precision   # (handed on only when set: the default is the tower's own)
+        self._load_decoder(directory, arch, cfg, sd, LlamaTower, "Mistral / Llama encoders", tower_args=dict(weight_precision=wp) if wp != "bf16" else None,
+                           pad_fallback="</s>")
 
-    def _load_decoder(self, directory: str, arch, cfg: dict, sd, tower, family: str, **tokenizer_args) -> None:
+    def _load_decoder(self, directory: str, arch, cfg: dict, sd, tower, family: str, tower_args: Optional[dict] = None, **tokenizer_args) -> None:
         """what the decoder-style families share: fp8 refused, the width checked, last-token / mean pooling resolved, right-padded input truncated at
         min(tokens, max_position_embeddings, 8192); tokenizer_args: HfJsonTokenizer.plain's (the pad token to fall back to: a pad position never reaches a row)"""
         import json
@@ -312,7 +324,7 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         if pooling not in ("last", "mean"):
             raise InvalidModelPropertiesError(f"{props.name}: pooling_method {pooling!r} is not available for {family} ('last' or 'mean')")
         self._finish_packed(directory, arch, min(int(cfg.get("max_position_embeddings", 8192)), 8192), tower, sd,
-                            lambda: HfJsonTokenizer.plain(directory, **tokenizer_args), pooling=pooling)
+                            lambda: HfJsonTokenizer.plain(directory, **tokenizer_args), pooling=pooling, **(tower_args or {}))
 
     # sentence-transformers Dense module directories (relative to the checkpoint) to apply behind the pooling: set by the `sbert` loader for an
     # EmbeddingGemma or a T5 encoder pipeline, empty for `hf` (AutoModel in the reference: the bare encoder)
