@@ -26,6 +26,11 @@
 // The compiler forms the 16 biases of a tile with packed fp32 adds / multiplies / FMAs (8 of each); packed operands take no |.| modifier, so the
 // diagonal path pays 16 more v_and_b32 per tile than the uniform one — that, not the branch, is what the split saves.  As at the relative-bias kernel,
 // from 129 keys on the image (>= 96 KiB) leaves one workgroup per CU whatever the registers allow; no occupancy request was tried or measured.
+//
+// This kernel KEEPS ITS OWN COPY of the work split.  On one shared __device__ body with policies (the bias step above as the policy's score hook) it gave
+// the same bits on 20 cases and took 86 + 20 registers, 4 waves, but ran slower: 1 x 8192 on 12 heads 744.5 us against the parent's 725.5
+// [724.7 .. 726.3] (+2.6 %), 16 x 512 72.4 us against 71.6 [71.6 .. 71.7] (+1.1 %).  The tile loop had six instructions fewer and three s_waitcnt fewer;
+// two of the sixteen packed bias FMAs came apart into scalar ones.  profiles/attention_slice_core_attempt.md, DESIGN.md section 8.
 #include "attention_core.h"
 
 namespace {

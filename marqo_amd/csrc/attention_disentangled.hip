@@ -36,6 +36,9 @@
 //   disentangled_strips_kernel:         24 VGPRs + 4 AGPRs, 25 SGPRs, no VGPR / SGPR spill, no scratch, no LDS, 8 waves / SIMD by registers
 //   attention_disentangled_kernel<64>:  90 VGPRs + 32 AGPRs, 81 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS, 4 waves / SIMD by registers
 // (the LDS image decides the residency of the second: from 129 keys on one workgroup per CU, as in the siblings)
+// Pass 2 keeps its own copy of the work split: one shared __device__ body with policies was built for the five sliced kernels and not merged, because the
+// full and ALiBi kernels ran slower on it.  This kernel gave the same bits on 20 cases at 90 + 32 registers, and 32 x 512 on 12 heads took 721.2 us against
+// the parent's 722.0 [721.3 .. 722.6].  profiles/attention_slice_core_attempt.md, DESIGN.md section 8.
 #include "attention_core.h"
 
 namespace {

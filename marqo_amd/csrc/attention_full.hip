@@ -23,6 +23,12 @@
 //   attention_full_kernel<64>:  72 VGPRs + 17 AGPRs, 76 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS (dynamic: 256 B per key of the image, at
 //                               most 160 KiB), 5 waves / SIMD by registers                (the ALiBi kernel: 92 + 20, 88, 4 waves)
 // From 129 keys on the image (>= 96 KiB of the CU's 160 KiB) leaves one workgroup per CU whatever the registers allow; no occupancy request was tried.
+//
+// This kernel KEEPS ITS OWN COPY of the work split it shares with attention_alibi / _relbias / _disentangled / _window.  One shared __device__ body with
+// policies was built for the five (66 + 17 registers here, 5 waves, bit-identical on 20 cases): 1 x 8192 on 12 heads 756.3 us against the parent's 757.7
+// [757.3 .. 759.0], but 16 x 512 73.10 us against 72.90 [72.87 .. 72.95] — outside the parent's own spread on the slow side, in three runs and in
+// every ordering of the body that was tried.  Moving this body verbatim into an inlined device function is enough to change the allocation (72 -> 66)
+// and the instruction stream.  profiles/attention_slice_core_attempt.md, DESIGN.md section 8.
 #include "attention_core.h"
 
 namespace {

@@ -21,10 +21,16 @@
 //     one 64-key tile less than the bias-free kernels hold, because the 160 KiB are shared with the table.  Longer sequences stream through in pieces.
 //
 // Compiler report (gfx950, -O3, resource remarks), 4 waves per workgroup, slice 64:
-//   attention_relbias_kernel<64>:  94 VGPRs, 76 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS, 4 waves / SIMD by registers
-//   attention_relbias_kernel<128>: 130 VGPRs, 76 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS, 3 waves / SIMD by registers
-// Two registers over the 128 of a fourth wave at 128-wide heads: it matters only where the LDS image lets four workgroups share a CU (sequences of up to
-// 64 keys); from 129 keys on the image (>= 96 KiB) leaves one workgroup per CU whatever the registers allow.  No occupancy request was tried or measured.
+//   attention_relbias_kernel<64>:  94 VGPRs + 20 AGPRs, 76 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS, 4 waves / SIMD by registers
+//   attention_relbias_kernel<128>: 130 VGPRs + 34 AGPRs, 76 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS, 3 waves / SIMD by registers
+// The third wave matters only where the LDS image lets several workgroups share a CU (short sequences); from 129 keys on the image (>= 96 KiB) leaves
+// one workgroup per CU whatever the registers allow.  No occupancy request was tried or measured.
+//
+// The work split below is still this file's own copy.  One shared __device__ body with policies was built for the five sliced kernels and not merged,
+// because the full and ALiBi kernels ran slower on it; this kernel gave the same bits on 64 cases at 79 + 20 / 112 + 44 registers (4 / 3 waves), and
+// 64 x 256 on 12 heads took 62.6 us against 62.0 [62.0 .. 62.1] at 64-wide heads, 143.1 against 150.0 [149.9 .. 150.1] at 128.  A lead from that work,
+// not taken here: with the table copy IN FRONT of stage(0) instead of behind it the 64-wide shape took 53.1 us (-15 %), same bits expected, not
+// checked.  profiles/attention_slice_core_attempt.md, DESIGN.md section 8.
 #include "attention_core.h"
 
 namespace {

@@ -11,6 +11,12 @@
 //     it in pieces of 640 keys.
 //   - A 16-query block visits only the tiles that intersect ITS band, floor((16 b - hw) / 64) .. floor((16 b + 15 + hw) / 64).
 //   - A tile cut by the band's edge (or by the end of the sequence) masks per key; a tile inside the band of all 16 queries takes the unmasked path.
+//
+// Compiler report (gfx950, -O3, resource remarks), 4 waves per workgroup, slice 64:
+//   attention_window_kernel:  76 VGPRs + 17 AGPRs, 48 SGPRs, no VGPR / SGPR spill, no scratch, no static LDS, 5 waves / SIMD by registers
+// The work split is this file's own copy of the one attention_full / _alibi / _relbias / _disentangled have.  One shared __device__ body with policies was
+// built for the five and not merged, because the full and ALiBi kernels ran slower on it; this kernel gave the same bits on 32 cases at 75 + 17
+// registers, and 1 x 8192 at half_window 64 on 12 heads took 23.2 us against the parent's 23.4 [23.4 .. 23.6].  profiles/attention_slice_core_attempt.md, DESIGN.md section 8.
 #include "attention_core.h"
 
 namespace {

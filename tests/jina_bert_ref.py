@@ -151,6 +151,7 @@ def readout_cases():
     cs.append(("fixed77", [77] * 3, 3, 64 ** -0.5, 78, True))
     cs.append(("long", [700], 2, 1.0, 700, False))
     cs.append(("long", [1300], 3, 64 ** -0.5, 1300, False))
+    cs.append(("corner", [705], 2, 1.0, 705, False))
     return cs
 
 

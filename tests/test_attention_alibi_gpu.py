@@ -116,6 +116,13 @@ def test_sequences_longer_than_the_lds_holds(lib, ln, heads, scale, pieces):
     _readout(lib, "long")
 
 
+def test_one_query_in_the_last_slice_past_the_lds_image(lib):
+    """705 = 11 x 64 + 1 tokens on 2 heads: two pieces through the 640-key image, a ragged last tile of one key, and a last slice whose one query leaves
+    three of the four waves idle — they stage the second piece and keep its barriers all the same"""
+    _real(lib, "corner", [705], 2, 1.0, seed=705)
+    _readout(lib, "corner")
+
+
 @pytest.mark.parametrize("lens", J.BIAS_ONLY)
 def test_bias_only(lib, lens):
     """q = k = 0: the output is softmax(-slope |k - q|) applied to one-hot V codes, whatever the scale, bit for bit"""

@@ -126,6 +126,13 @@ def test_sequences_longer_than_the_lds_holds(lib, ln, heads, pieces):
     _check(lib, "long", "randn", SMALL, [ln], heads, seed=ln)
 
 
+def test_one_query_in_the_last_slice_past_the_lds_image(lib):
+    """577 = 512 + 64 + 1 tokens on 2 heads: two pieces through the 512-key image, a ragged last tile of one key, and a last slice whose one query leaves
+    three of the four waves idle — they fill the offsets, stage the second piece and keep its barriers all the same"""
+    for fam in ("randn", "peaked"):
+        _check(lib, "corner", fam, SMALL, [577], 2, seed=577)
+
+
 def test_position_only(lib):
     """q . k = 0 through orthogonal halves: the result is the two gathered terms alone"""
     lens, heads = [100, 65, 9], 2

@@ -86,6 +86,13 @@ def test_fixed_len_65(lib, heads):
         assert torch.equal(got.view(torch.int16), packed.view(torch.int16))
 
 
+def test_one_query_in_the_last_slice_past_the_lds_image(lib):
+    """705 = 11 x 64 + 1 tokens on 2 heads: two pieces through the 640-key image, a ragged last tile of one key, and a last slice whose one query leaves
+    three of the four waves idle — they stage the second piece and keep its barriers all the same"""
+    for fam in ("randn", "peaked", "readout"):
+        _check(lib, "corner", fam, [705], 2, seed=705)
+
+
 def _marker_keys(ln):
     keys = {0, ln - 1}
     for edge in range(64, ln, 64):

@@ -91,6 +91,15 @@ def test_sequences_longer_than_the_lds_holds(lib, hd, ln):
             _check(lib, "long", fam, [ln], heads, hd, D, scale, seed=ln)
 
 
+@pytest.mark.parametrize("hd, ln", ((64, 641), (128, 321)))
+def test_one_query_in_the_last_slice_past_the_lds_image(lib, hd, ln):
+    """one token past the 576 / 256 keys of the LDS image, on 2 heads: two pieces, a ragged last tile of one key, and a last slice whose one query leaves
+    three of the four waves idle — they stage the second piece and keep its barriers all the same"""
+    assert ln == T.LDS_KEYS[hd] + T.SLICE + 1
+    for fam in FAMS:
+        _check(lib, "corner", fam, [ln], 2, hd, 128, 1.0, seed=ln)
+
+
 @pytest.mark.parametrize("hd", (64, 128))
 def test_fixed_len_77(lib, hd):
     for fam in FAMS:

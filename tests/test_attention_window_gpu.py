@@ -77,6 +77,15 @@ def test_a_sequence_longer_than_the_lds_holds(lib, hw, fam):
     _assert_parity("long", fam, _run(lib, qkv, lens, hw), qkv, lens, hw)
 
 
+@pytest.mark.parametrize("fam", ("readout", "peaked"))
+def test_a_band_wider_than_the_lds_with_one_query_in_the_last_slice(lib, fam):
+    """1345 = 21 x 64 + 1 tokens, hw = 300: the slices in the middle reach 11 tiles (704 keys against the 640 the LDS holds: two pieces), the last tile is
+    ragged, and the last slice's one query leaves three of the four waves idle — they stage and keep the barriers all the same"""
+    lens, hw = [1345], 300
+    qkv = R.make_qkv(fam, lens, HEADS, 64, seed=1345, device="cuda")
+    _assert_parity("corner", fam, _run(lib, qkv, lens, hw), qkv, lens, hw)
+
+
 @pytest.mark.parametrize("hw", (64, 8))
 def test_fixed_length_entry(lib, hw):
     lens = [130] * 3
