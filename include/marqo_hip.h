@@ -1958,6 +1958,44 @@ int mq_gemm_small_w8(const void* d_A, int64_t lda, const void* d_W8, int64_t ldw
 int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                        const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mistral / Llama queries from 4-bit weights: the MXFP4 W4A16 skinny GEMM, its quantiser and the tower entry point
+ * (csrc/gemm_small_w4.hip, csrc/llama.hip; engine/llama.py LlamaTower(weight_precision="mxfp4")) -----------------------------------------------------------
+ * The e4m3 section's next step: OCP MX FP4, 4.25 bits per weight, bf16 activations.  Additions to ABI 15: nothing above changes.  Each entry point
+ * judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ * The weight format: e2m1 codes (sign, magnitude index 0 .. 7 onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}), K % 64 == 0, and one e8m0 byte (127 + exponent) per
+ * block of 32 consecutive k: scale = 2^ceil(log2(absmax_block / 6)) (1 for an all-zero block; the exponent is kept inside [-100, 100]);
+ * code = RNE(w / scale), a tie going to the even index (mantissa bit 0): nothing saturates.  An e2m1 value times 2^k is exactly a bf16 value.
+ * K is stored in chunks of 128 (a last half chunk is padded with zero codes): d_W4 [N, ld4] bytes, ld4 % 16 == 0, ld4 >= ceil(K / 128) * 64;
+ * d_scale [N, lds] bytes, lds % 4 == 0, lds >= ceil(K / 128) * 4, byte b of a row = block b.  The order of the codes inside a chunk (fragment-major:
+ * a lane's four MFMA operands in one 16-byte read) is private to the quantiser and the kernel and documented in csrc/gemm_small_w4.hip.
+ *
+ *   mq_quantize_weights_mxfp4: d_W_bf16 [N, ldw] -> d_W4, d_scale; the bf16 rows are REWRITTEN in place with decode(code) * scale, so the bf16 copy and
+ *                   the 4-bit copy hold the same numbers (calls too tall for the skinny kernel run the tiled bf16 kernels on the former).
+ *   mq_gemm_small_w4_ok: 1 where mq_gemm_small_w4 takes the shape: exactly mq_gemm_small_w8_ok's shapes.
+ *   mq_gemm_small_w4: d_out [M, ldc] = epi(d_A bf16 [M, lda] @ dequant(d_W4, d_scale)^T): the codes go global -> VGPR, a 32-block is one
+ *                   mfma_f32_16x16x32_bf16 k-step and its scale is folded into the decoded bf16 fragment as an exponent (a table in registers, exact
+ *                   for every code, zero and 0.5 included); the fp32 sum never sees a scale.  A row's bits do not depend on the other rows of the
+ *                   call.  flags: 0 (bf16 out), MQ_EPI_BIAS (bf16 out), MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32 (fp32 residual, which may alias
+ *                   d_out); lda % 8 == 0, ldc % 4 == 0.
+ *   mq_encode_llama_w4: mq_encode_llama with the four block GEMMs of every layer on mq_gemm_small_w4 wherever mq_gemm_small_w4_ok holds, and on
+ *                   mq_gemm_bf16 over w's (rewritten) bf16 weights elsewhere.  w4: host array of cfg->layers entries; rows are packed
+ *                   (ld4 = ceil(K / 128) * 64, lds = ceil(K / 128) * 4).
+ * "w4_waves", "w4_depth" (mq_tune, no variable, 0): 0 = auto, 4 / 8 wave64s per workgroup; 0 = auto, 1 / 2 / 4 128-deep chunks of weight loads per group. */
+typedef struct mq_w4_layer {
+    const void* qkv_w4;  const void* qkv_scale;    /* [(Q + 2 KV) hd, W] codes, [(Q + 2 KV) hd, W / 32] scales */
+    const void* out_w4;  const void* out_scale;    /* [W, Q hd] */
+    const void* ug_w4;   const void* ug_scale;     /* [2 F, W] */
+    const void* down_w4; const void* down_scale;   /* [W, F] */
+} mq_w4_layer;
+
+int mq_quantize_weights_mxfp4(void* d_W_bf16, int64_t ldw, void* d_W4, int64_t ld4, void* d_scale, int64_t lds, int64_t N, int64_t K, void* stream);
+int mq_gemm_small_w4_ok(int64_t M, int64_t N, int64_t K);
+int mq_gemm_small_w4(const void* d_A, int64_t lda, const void* d_W4, int64_t ld4, const void* d_scale, int64_t lds, const float* d_bias,
+                     const void* d_residual, void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                       const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Mixture-of-experts NomicBERT (nomic-embed-text-v2-moe): router, device-side plan, grouped bf16 GEMM, and the tower
  * (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py) ---------------------------------------------------------------------------------------------------
  * The Jina v3 base block (post-LN, biased Wqkv / out_proj, rotate-half rope over 64-wide heads, full attention) whose MLP is, layer by layer, either

@@ -18,3 +18,4 @@ extern mq_knob mq_ln_prefetch, mq_ln_rows_per_wave, mq_ln_bf16_wide;            
 extern mq_knob mq_xcd_band;                                                          // the row-wise kernels' launches (common.h, xcd_banded_block)
 extern mq_knob mq_attention_waves;                                                   // attention.hip
 extern mq_knob mq_w8_waves, mq_w8_depth;                                             // gemm_small_w8.hip
+extern mq_knob mq_w4_waves, mq_w4_depth;                                             // gemm_small_w4.hip

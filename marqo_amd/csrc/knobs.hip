@@ -16,6 +16,7 @@ mq_knob mq_ln_prefetch, mq_ln_rows_per_wave, mq_ln_bf16_wide;
 mq_knob mq_xcd_band;
 mq_knob mq_attention_waves;
 mq_knob mq_w8_waves, mq_w8_depth;
+mq_knob mq_w4_waves, mq_w4_depth;
 
 namespace {
 
@@ -46,6 +47,8 @@ const Knob g_knobs[] = {
     {"attn_waves", nullptr, 0, &mq_attention_waves},             // 0 = auto, 4 / 8 wave64s per attention workgroup, 5 = five waves for 65..80-token sequences (else auto)
     {"w8_waves", nullptr, 0, &mq_w8_waves},                      // the W8A16 skinny GEMM: 0 = auto, 4 / 8 wave64s per workgroup
     {"w8_depth", nullptr, 0, &mq_w8_depth},                      // ... 0 = auto, 2 / 4 k-chunks of weight loads per group
+    {"w4_waves", nullptr, 0, &mq_w4_waves},                      // the MXFP4 W4A16 skinny GEMM: 0 = auto, 4 / 8 wave64s per workgroup
+    {"w4_depth", nullptr, 0, &mq_w4_depth},                      // ... 0 = auto, 1 / 2 / 4 128-deep chunks of weight loads per group (capped by the row tiles)
     {"gemm_addr_limit_mb", nullptr, 0, nullptr},                 // bytes / 2^20 one launch may address per operand, 0 = the 4 GiB - 1 of a 32-bit buffer offset: taller matrices go in row chunks
 };
 

@@ -186,8 +186,9 @@ extern "C" size_t mq_llama_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows
 
 namespace {
 // the tower; w8 (nullable): the e4m3 copies of the four block weights of every layer — a GEMM whose shape the W8A16 skinny kernel takes streams those,
-// every other call runs mq_gemm_bf16 on the bf16 weight, which mq_quantize_weights_pow2 has rewritten with the same numbers (gemm_small_w8.hip)
-int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+// every other call runs mq_gemm_bf16 on the bf16 weight, which mq_quantize_weights_pow2 has rewritten with the same numbers (gemm_small_w8.hip);
+// w4 (nullable, instead of w8): the MXFP4 copies and their block scales, streamed by the W4A16 skinny kernel in the same way (gemm_small_w4.hip)
+int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                  const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
     MQ_TRY(check_cfg(cfg));
     MQ_CHECK_ARG(w && d_out, "mq_encode_llama: null pointer");
@@ -200,6 +201,11 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
             const mq_w8_layer& q = w8[l];
             MQ_CHECK_ARG(q.qkv_w8 && q.qkv_scale && q.out_w8 && q.out_scale && q.ug_w8 && q.ug_scale && q.down_w8 && q.down_scale,
                          "mq_encode_llama_w8: layer %d has null e4m3 weights or scales", l);
+        }
+        if (w4) {
+            const mq_w4_layer& q = w4[l];
+            MQ_CHECK_ARG(q.qkv_w4 && q.qkv_scale && q.out_w4 && q.out_scale && q.ug_w4 && q.ug_scale && q.down_w4 && q.down_scale,
+                         "mq_encode_llama_w4: layer %d has null MXFP4 weights or scales", l);
         }
     }
     if (nseq <= 0) return MQ_OK;
@@ -221,25 +227,31 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
     const bool windowed = cfg->window > 0 && cfg->window < maxl;            // (a window no sequence of the call reaches cuts nothing)
 
     // one block GEMM: out [rows, N] = epi(A [rows, K] @ W^T), from the e4m3 copy where the skinny kernel takes the call
-    auto gemm = [&](const void* A, int64_t lda, const void* Wb, const void* Wq, const float* sc, const float* bias, const void* res, void* out, int64_t N, int64_t K,
+    // (Wq / sc: the layer's e4m3 codes and row scales, or its MXFP4 codes and block scales in packed rows of 64 / 4 bytes per 128-deep chunk)
+    auto gemm = [&](const void* A, int64_t lda, const void* Wb, const void* Wq, const void* sc, const float* bias, const void* res, void* out, int64_t N, int64_t K,
                     int flags) {
-        if (Wq && mq_gemm_small_w8_ok(rows, N, K)) return mq_gemm_small_w8(A, lda, Wq, K, sc, bias, res, out, N, rows, N, K, flags, s);
+        if (Wq && w4 && mq_gemm_small_w4_ok(rows, N, K))
+            return mq_gemm_small_w4(A, lda, Wq, (K + 127) / 128 * 64, sc, (K + 127) / 128 * 4, bias, res, out, N, rows, N, K, flags, s);
+        if (Wq && w8 && mq_gemm_small_w8_ok(rows, N, K)) return mq_gemm_small_w8(A, lda, Wq, K, (const float*)sc, bias, res, out, N, rows, N, K, flags, s);
         return mq_gemm_bf16(A, lda, Wb, K, bias, (const float*)res, out, N, rows, N, K, flags, s);
     };
     MQ_TRY(mq_embed_tokens_wide(d_ids, d_cu_seqlens, nseq, w->tok_emb, x, W, cfg->vocab, s));
     for (int l = 0; l < cfg->layers; ++l) {
         const mq_qwen_layer& b = w->layers[l];
-        const mq_w8_layer* q = w8 ? w8 + l : nullptr;
+        // the layer's low-precision copies, by role (mq_w8_layer and mq_w4_layer name the same four pairs)
+        struct { const void *qkv, *qkv_s, *out, *out_s, *ug, *ug_s, *down, *down_s; } q = {};
+        if (w8) q = {w8[l].qkv_w8, w8[l].qkv_scale, w8[l].out_w8, w8[l].out_scale, w8[l].ug_w8, w8[l].ug_scale, w8[l].down_w8, w8[l].down_scale};
+        if (w4) q = {w4[l].qkv_w4, w4[l].qkv_scale, w4[l].out_w4, w4[l].out_scale, w4[l].ug_w4, w4[l].ug_scale, w4[l].down_w4, w4[l].down_scale};
         MQ_TRY(mq_rmsnorm_wide(x, nullptr, b.input_norm_g, h, nullptr, rows, W, cfg->rms_eps, s));
-        MQ_TRY(gemm(h, W, b.qkv_w, q ? q->qkv_w8 : nullptr, q ? q->qkv_scale : nullptr, nullptr, nullptr, big, QKVW, W, 0));
+        MQ_TRY(gemm(h, W, b.qkv_w, q.qkv, q.qkv_s, nullptr, nullptr, big, QKVW, W, 0));
         MQ_TRY(mq_qk_norm_rope(big, d_cu_seqlens, nseq, 0, Q, KV, hd, nullptr, nullptr, cfg->rms_eps, w->d_inv_freq, s));
         if (windowed) MQ_TRY(mq_attention_gqa_window(big, a, d_cu_seqlens, nseq, 0, maxl, Q, KV, hd, cfg->window, s));
         else MQ_TRY(mq_attention_gqa(big, a, d_cu_seqlens, nseq, 0, maxl, Q, KV, hd, MQ_MASK_CAUSAL, s));
-        MQ_TRY(gemm(a, AW, b.out_w, q ? q->out_w8 : nullptr, q ? q->out_scale : nullptr, w->zeros, x, x, W, AW, res_flags));
+        MQ_TRY(gemm(a, AW, b.out_w, q.out, q.out_s, w->zeros, x, x, W, AW, res_flags));
         MQ_TRY(mq_rmsnorm_wide(x, nullptr, b.post_norm_g, h, nullptr, rows, W, cfg->rms_eps, s));
-        MQ_TRY(gemm(h, W, b.ug_w, q ? q->ug_w8 : nullptr, q ? q->ug_scale : nullptr, nullptr, nullptr, big, 2 * F, W, 0));
+        MQ_TRY(gemm(h, W, b.ug_w, q.ug, q.ug_s, nullptr, nullptr, big, 2 * F, W, 0));
         MQ_TRY(mq_glu(big, rows, F, MQ_ACT_SILU, 0, s));
-        MQ_TRY(gemm(big, 2 * F, b.down_w, q ? q->down_w8 : nullptr, q ? q->down_scale : nullptr, w->zeros, x, x, W, F, res_flags));
+        MQ_TRY(gemm(big, 2 * F, b.down_w, q.down, q.down_s, w->zeros, x, x, W, F, res_flags));
     }
     if (cfg->pool == MQ_POOL_LAST) {   // the final norm is per row: only the pooled rows take it
         MQ_TRY(mq_last_rows(d_cu_seqlens, last, nseq, s));
@@ -255,7 +267,7 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
 
 extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                                int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
-    return encode_llama(cfg, w, nullptr, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, nullptr, nullptr, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
@@ -264,5 +276,14 @@ extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights
     MQ_CHECK_ARG(w8, "mq_encode_llama_w8: null e4m3 weights");
     MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
                  "mq_encode_llama_w8: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the e4m3 rows are walked in 64-deep chunks)");
-    return encode_llama(cfg, w, w8, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, w8, nullptr, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                                  const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes,
+                                  void* stream) {
+    MQ_CHECK_ARG(w4, "mq_encode_llama_w4: null MXFP4 weights");
+    MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
+                 "mq_encode_llama_w4: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the MXFP4 rows are stored in 128-deep chunks, the last one half)");
+    return encode_llama(cfg, w, nullptr, w4, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }

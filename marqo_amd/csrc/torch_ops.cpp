@@ -407,6 +407,47 @@ at::Tensor gemm_small_w8(const at::Tensor& A, const at::Tensor& W8, const at::Te
     return out;
 }
 
+// ---- MXFP4 W4A16 (csrc/gemm_small_w4.hip): packed rows of 64 code bytes and 4 scale bytes per 128-deep chunk of K ----
+// W bf16 [N, K] (REWRITTEN in place with the dequantised values) -> (W4 uint8 [N, ceil(K / 128) 64] packed e2m1 codes, scale uint8 [N, ceil(K / 128) 4] e8m0)
+std::tuple<at::Tensor, at::Tensor> quantize_weights_mxfp4(at::Tensor W) {
+    need_dev(W, at::kBFloat16, "W");
+    TORCH_CHECK(W.dim() == 2, "marqo_hip::mq_quantize_weights_mxfp4: W [N,K]");
+    const int64_t N = W.size(0), K = W.size(1), chunks = (K + 127) / 128;
+    at::Tensor W4 = at::empty({N, chunks * 64}, W.options().dtype(at::kByte)), scale = at::empty({N, chunks * 4}, W.options().dtype(at::kByte));
+    check_rc(mq_quantize_weights_mxfp4(W.data_ptr(), K, W4.data_ptr(), chunks * 64, scale.data_ptr(), chunks * 4, N, K, stream_of(W)), "mq_quantize_weights_mxfp4");
+    return {W4, scale};
+}
+
+at::Tensor gemm_small_w4(const at::Tensor& A, const at::Tensor& W4, const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                         const c10::optional<at::Tensor>& residual, int64_t flags) {
+    need_dev(A, at::kBFloat16, "A");
+    need_dev(W4, at::kByte, "W4");
+    need_dev(scale, at::kByte, "scale");
+    TORCH_CHECK(A.dim() == 2 && W4.dim() == 2 && scale.dim() == 2 && scale.size(0) == W4.size(0),
+                "marqo_hip::mq_gemm_small_w4: A [M,K], W4 [N, ceil(K/128)*64], scale [N, ceil(K/128)*4]");
+    const int64_t M = A.size(0), K = A.size(1), N = W4.size(0);
+    const bool f32 = (flags & MQ_EPI_OUT_F32) != 0;
+    const float* b = nullptr;
+    const void* r = nullptr;
+    if (flags & MQ_EPI_BIAS) {
+        TORCH_CHECK(bias.has_value(), "marqo_hip::mq_gemm_small_w4: MQ_EPI_BIAS without bias");
+        need_dev(*bias, at::kFloat, "bias");
+        TORCH_CHECK(bias->numel() == N, "bias must be [N]");
+        b = (const float*)bias->data_ptr();
+    }
+    if (flags & MQ_EPI_RESIDUAL) {
+        TORCH_CHECK(residual.has_value(), "marqo_hip::mq_gemm_small_w4: MQ_EPI_RESIDUAL without residual");
+        need_dev(*residual, at::kFloat, "residual");
+        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == N, "residual must be [M,N]");
+        r = residual->data_ptr();
+    }
+    at::Tensor out = at::empty({M, N}, A.options().dtype(f32 ? at::kFloat : at::kBFloat16));
+    // (the row strides are the tensors' widths: the entry point refuses rows shorter than K's chunks need)
+    check_rc(mq_gemm_small_w4(A.data_ptr(), K, W4.data_ptr(), W4.size(1), scale.data_ptr(), scale.size(1), b, r, out.data_ptr(), N, M, N, K, (int)flags, stream_of(A)),
+             "mq_gemm_small_w4");
+    return out;
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -439,6 +480,8 @@ TORCH_LIBRARY(marqo_hip, m) {
     m.def("mq_moe_mlp(Tensor h, Tensor top_e, Tensor top_w, Tensor w1, Tensor w2t, int bm, Tensor(a!) Y) -> (Tensor, Tensor, Tensor)");
     m.def("mq_quantize_weights_pow2(Tensor(a!) W) -> (Tensor, Tensor)");
     m.def("mq_gemm_small_w8(Tensor A, Tensor W8, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
+    m.def("mq_quantize_weights_mxfp4(Tensor(a!) W) -> (Tensor, Tensor)");
+    m.def("mq_gemm_small_w4(Tensor A, Tensor W4, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -463,4 +506,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_moe_mlp", &moe_mlp);
     m.impl("mq_quantize_weights_pow2", &quantize_weights_pow2);
     m.impl("mq_gemm_small_w8", &gemm_small_w8);
+    m.impl("mq_quantize_weights_mxfp4", &quantize_weights_mxfp4);
+    m.impl("mq_gemm_small_w4", &gemm_small_w4);
 }

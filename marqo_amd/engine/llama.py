@@ -4,7 +4,8 @@ SFR-Embedding-Mistral, Linq-Embed-Mistral, Llama-2-shaped fine-tunes) -> HBM lay
 
 bf16 GEMM operands, fp32 residual stream, 64- or 128-wide heads, widths up to 4096.  weight_precision="e4m3" keeps a second, e4m3 copy of the four block
 weights (one power-of-two scale per output row) that the query path streams instead of the bf16 one (csrc/gemm_small_w8.hip: W8A16, bf16 activations);
-the bf16 copy is rewritten with the dequantised values, so every batch size embeds with the same model.  The block is the Qwen tower's without q / k norm and without biases,
+the bf16 copy is rewritten with the dequantised values, so every batch size embeds with the same model.  weight_precision="mxfp4" does the same with
+OCP MX FP4 copies (e2m1 codes, one e8m0 scale per 32 consecutive k: 4.25 bits per weight; csrc/gemm_small_w4.hip: W4A16).  The block is the Qwen tower's without q / k norm and without biases,
 so the checkpoint-to-tensor transform (names, the fused QKV and (up | gate) weights) is engine/tower_weights.py::qwen_state_dict and the weight structs
 are the Qwen tower's."""
 from __future__ import annotations
@@ -28,8 +29,8 @@ class LlamaTower(_PackedTextTower):
 
     def __init__(self, arch: LlamaArch, sd: Dict[str, Tensor], device: str, pooling: str = "last", precision: str = "bf16", weight_precision: str = "bf16"):
         super().__init__(device)
-        if weight_precision not in ("bf16", "e4m3"):
-            raise ValueError(f"weight_precision must be 'bf16' or 'e4m3', got {weight_precision!r}")
+        if weight_precision not in ("bf16", "e4m3", "mxfp4"):
+            raise ValueError(f"weight_precision must be 'bf16' or 'e4m3' or 'mxfp4', got {weight_precision!r}")
         _check_precision(precision, ("bf16",), f"the Mistral / Llama tower runs on bf16 operands only (its RMSNorm / rotary / gated-SiLU blocks have no e4m3 "
                                                f"kernels), got precision {precision!r}")
         if arch.head_dim not in (64, 128):
@@ -62,9 +63,11 @@ class LlamaTower(_PackedTextTower):
                               window=int(arch.window or 0), rms_eps=arch.rms_eps, reserved0=0)
         if weight_precision == "e4m3":
             self._quantize_e4m3()
+        elif weight_precision == "mxfp4":
+            self._quantize_mxfp4()
 
     def block_weight(self, layer: int, name: str) -> Tensor:
-        """the bf16 device tensor of one block matrix ('qkv', 'out', 'ug', 'down') as the kernels read it (with weight_precision 'e4m3': dequantised)"""
+        """the bf16 device tensor of one block matrix ('qkv', 'out', 'ug', 'down') as the kernels read it (with weight_precision 'e4m3' / 'mxfp4': dequantised)"""
         ptr = getattr(self._layers[layer], name + "_w")
         return next(t for t in self._h.tensors if t.data_ptr() == ptr)
 
@@ -89,3 +92,27 @@ class LlamaTower(_PackedTextTower):
                     setattr(self._w8_layers[l], name + "_scale", sc.data_ptr())
             torch.cuda.current_stream(self.device).synchronize()
         self._entry = ("mq_encode_llama_w8", (self._w8_layers,))
+
+    def _quantize_mxfp4(self) -> None:
+        """the MXFP4 copy of every layer's four matrices (packed e2m1 codes, 64 bytes per 128-deep chunk of a row, and e8m0 block scales, 4 bytes per
+        chunk), made on the device from the uploaded bf16 weights, which are rewritten with the dequantised values (mq_quantize_weights_mxfp4):
+        1.27 x the weight memory, one model on the skinny and the tiled path"""
+        a = self.arch
+        if a.width % 64 or a.mlp_dim % 64 or (a.heads * a.head_dim) % 64:
+            raise ValueError("weight_precision 'mxfp4' needs width, mlp_dim and heads * head_dim to be multiples of 64")
+        aw, qkvw = a.heads * a.head_dim, (a.heads + 2 * a.kv_heads) * a.head_dim
+        shapes = (("qkv", qkvw, a.width), ("out", a.width, aw), ("ug", 2 * a.mlp_dim, a.width), ("down", a.width, a.mlp_dim))
+        self._w4_layers = (L.W4Layer * a.layers)()
+        with torch.cuda.device(self.device):
+            for l in range(a.layers):
+                for name, n, k in shapes:
+                    chunks = (k + 127) // 128
+                    w4 = torch.empty(n, chunks * 64, dtype=torch.uint8, device=self.device)
+                    sc = torch.empty(n, chunks * 4, dtype=torch.uint8, device=self.device)
+                    L.check(self.lib.mq_quantize_weights_mxfp4(getattr(self._layers[l], name + "_w"), k, w4.data_ptr(), chunks * 64, sc.data_ptr(), chunks * 4,
+                                                               n, k, self._stream()), "mq_quantize_weights_mxfp4")
+                    self._h.tensors += [w4, sc]
+                    setattr(self._w4_layers[l], name + "_w4", w4.data_ptr())
+                    setattr(self._w4_layers[l], name + "_scale", sc.data_ptr())
+            torch.cuda.current_stream(self.device).synchronize()
+        self._entry = ("mq_encode_llama_w4", (self._w4_layers,))

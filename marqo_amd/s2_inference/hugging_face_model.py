@@ -65,10 +65,11 @@ class HuggingFaceModelProperties:
         if self.engine_precision not in ("bf16", "fp8"):
             raise ValueError("'enginePrecision' must be 'bf16' or 'fp8'")
         # engine extension (Mistral / Llama checkpoints): "e4m3" keeps an e4m3 copy of the block weights, one power-of-two scale per output row, that
-        # single queries stream instead of the bf16 one (activations stay bf16; engine/llama.py); every other family refuses it at load
+        # single queries stream instead of the bf16 one (activations stay bf16; engine/llama.py); "mxfp4" keeps an OCP MX FP4 copy instead (e2m1 codes,
+        # one e8m0 scale per 32 consecutive k: 4.25 bits per weight); every other family refuses either at load
         self.weight_precision: str = p.get("weightPrecision", p.get("weight_precision", "bf16"))
-        if self.weight_precision not in ("bf16", "e4m3"):
-            raise ValueError("'weightPrecision' must be 'bf16' or 'e4m3'")
+        if self.weight_precision not in ("bf16", "e4m3", "mxfp4"):
+            raise ValueError("'weightPrecision' must be 'bf16' or 'e4m3' or 'mxfp4'")
         b = p.get("fp8Budget", p.get("fp8_budget"))
         if b is not None and not (isinstance(b, (int, float)) and b > 0):
             raise ValueError("'fp8Budget' must be a positive number")
