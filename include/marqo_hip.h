@@ -2110,6 +2110,51 @@ int mq_score_colbert(const mq_bert_cfg* cfg, const mq_bert_weights* w, const voi
                      const int32_t* h_cu_seqlens, int64_t nseq, float* d_scores, void* d_query_emb, void* d_doc_emb, void* d_workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- Gemma2 text embedders: soft-capped windowed causal grouped-query attention at 256-wide heads, the wide post-norm row kernel, the tower
+ * (csrc/attention_gqa256_softcap.hip, csrc/gemma2.hip; engine/gemma2.py) ---------------------------------------------------------------------------
+ * transformers' Gemma2Model (model_type "gemma2": BAAI/bge-multilingual-gemma2, Gemma-2-2B-shaped fine-tunes): mq_encode_gemma's block without q / k
+ * norm, with one rotary base, under a causal mask, with attention logits soft-capped at `softcap` and a causal sliding window on the layers whose
+ * mq_gemma_layer.sliding is 1.  Additions to ABI 15: nothing above changes; mq_gemma2_cfg and the entry points below are new.  Every entry point judges
+ * its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_attention_gqa256_softcap: mq_attention_gqa256_causal's layout and conventions.  Query i sees the keys j of its own sequence with
+ *                   i - window < j <= i (mq_attention_gqa_window's rule; window == 0, or a window no sequence of the call reaches: plain causal).
+ *                   Per score: s' = softcap tanh(scale q.k / softcap), then the mask, then the softmax.  0 < softcap <= 64: every capped score lies
+ *                   in [-softcap, softcap], so the softmax is taken against a fixed reference exponent (no running maximum, no rescale); uncapped
+ *                   calls belong to mq_attention_gqa256_causal.  The 128 KiB of LDS are two 64-key buffers of K + V: tile t + 1 arrives by LDS-DMA
+ *                   while tile t is scored and multiplied, one barrier per tile.
+ *   mq_rmsnorm_add_norm_wide: mq_rmsnorm_add_norm's contract for W % 64 == 0, W <= 4096.  W <= 2048: that call (the same bits); above it a kernel
+ *                   that keeps the whole row of d_o and d_x in registers.
+ *   mq_encode_gemma2: token gather (w->tok_emb holds embed_tokens * sqrtf(width), the fp32 product formed once at load) -> `layers` blocks as
+ *                   mq_encode_gemma's, on mq_rmsnorm_wide / mq_rmsnorm_add_norm_wide, mq_qk_norm_rope with NULL gains and w->d_inv_freq_global
+ *                   (q_norm_g / k_norm_g of every layer must be NULL; d_inv_freq_local is not read), mq_attention_gqa256_softcap -> final RMSNorm
+ *                   -> the last token's row (MQ_POOL_LAST) or the mean (MQ_POOL_MEAN) (+ L2).  width <= 4096 (a multiple of 64), head_dim 256,
+ *                   mlp_dim % 64 == 0, max_pos <= 8192.  d_out fp32 [nseq, width]. */
+typedef struct mq_gemma2_cfg {
+    int32_t width;        /* W, multiple of 64, <= 4096 */
+    int32_t layers;
+    int32_t q_heads;      /* Q */
+    int32_t kv_heads;     /* KV, divides Q */
+    int32_t head_dim;     /* hd: 256; Q hd need not be W */
+    int32_t mlp_dim;      /* F, multiple of 64 */
+    int32_t vocab;
+    int32_t max_pos;      /* longest sequence served (<= 8192) */
+    int32_t window;       /* of the sliding layers: config sliding_window (query i sees keys i - window < j <= i); 0: none */
+    int32_t pool;         /* MQ_POOL_LAST or MQ_POOL_MEAN */
+    float   rms_eps;
+    float   attn_scale;   /* query_pre_attn_scalar ^ -0.5 */
+    float   softcap;      /* attn_logit_softcapping, 0 < softcap <= 64 */
+    int32_t reserved0;
+} mq_gemma2_cfg;
+
+int mq_attention_gqa256_softcap(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, int64_t nseq, int32_t fixed_len, int32_t max_len,
+                                int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t window, float softcap, float scale, void* stream);
+int mq_rmsnorm_add_norm_wide(float* d_x, const void* d_o, const float* d_g_post, const float* d_g_next, void* d_h, int64_t rows, int32_t W, float eps,
+                             void* stream);
+size_t mq_gemma2_workspace_bytes(const mq_gemma2_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_gemma2(const mq_gemma2_cfg* cfg, const mq_gemma_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
+                     int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

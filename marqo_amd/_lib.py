@@ -28,12 +28,12 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "gemm_small_w8", "gemm_small_w4", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe", "colbert")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "gemm_small_w8", "gemm_small_w4", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_gqa256_softcap", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe", "colbert", "gemma2")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
 MQ_MASK_NONE, MQ_MASK_CAUSAL, MQ_MASK_CAUSAL_CLS = 0, 1, 2
-MQ_POOL_MEAN, MQ_POOL_CLS, MQ_POOL_LAST = 0, 1, 2   # (MQ_POOL_LAST: mq_encode_qwen / mq_encode_llama only)
+MQ_POOL_MEAN, MQ_POOL_CLS, MQ_POOL_LAST = 0, 1, 2   # (MQ_POOL_LAST: mq_encode_qwen / mq_encode_llama / mq_encode_gemma2 only)
 MQ_VIT_POOL_CLS, MQ_VIT_POOL_MAP, MQ_VIT_POOL_AVG, MQ_VIT_POOL_QUERY = 0, 1, 2, 3
 MQ_EPI_BIAS, MQ_EPI_GELU, MQ_EPI_QUICKGELU, MQ_EPI_RESIDUAL, MQ_EPI_OUT_F32, MQ_EPI_OUT_FP8 = 1, 2, 4, 8, 16, 32
 MQ_EPI_ROW_STATS, MQ_EPI_LN_APPLY = 64, 128
@@ -258,6 +258,13 @@ class GemmaWeights(C.Structure):
 class GemmaCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
                 ("vocab", C.c_int32), ("max_pos", C.c_int32), ("half_window", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float), ("attn_scale", C.c_float)]
+
+
+class Gemma2Cfg(C.Structure):
+    """mq_gemma2_cfg: the Gemma2 tower (csrc/gemma2.hip); its weights are GemmaWeights / GemmaLayer without q_norm_g, k_norm_g and d_inv_freq_local"""
+    _fields_ = [("width", C.c_int32), ("layers", C.c_int32), ("q_heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp_dim", C.c_int32),
+                ("vocab", C.c_int32), ("max_pos", C.c_int32), ("window", C.c_int32), ("pool", C.c_int32), ("rms_eps", C.c_float), ("attn_scale", C.c_float),
+                ("softcap", C.c_float), ("reserved0", C.c_int32)]
 
 
 class GemmaCausalLayer(C.Structure):
@@ -633,6 +640,12 @@ _SIGNATURES = {
     "mq_score_colbert_workspace_bytes": (C.c_size_t, [C.POINTER(BertCfg), C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "mq_score_colbert": (C.c_int, [C.POINTER(BertCfg), C.POINTER(BertWeights), _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P,
                                    _P, _P, C.c_size_t, _P]),
+    # Gemma2 text embedders: soft-capped windowed causal attention at 256-wide heads, the wide post-norm row kernel, the tower
+    # (csrc/attention_gqa256_softcap.hip, csrc/gemma2.hip; engine/gemma2.py)
+    "mq_attention_gqa256_softcap": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
+    "mq_rmsnorm_add_norm_wide": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
+    "mq_gemma2_workspace_bytes": (C.c_size_t, [C.POINTER(Gemma2Cfg), C.c_int64, C.c_int64]),
+    "mq_encode_gemma2": (C.c_int, [C.POINTER(Gemma2Cfg), C.POINTER(GemmaWeights), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "mq_tune":(C.c_int, [C.c_char_p, C.c_int]),
     "mq_tune_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "mq_profile_enable": (C.c_int, [C.c_int]),

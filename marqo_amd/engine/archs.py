@@ -542,6 +542,99 @@ def gemma_arch_from_hf_config(cfg: dict) -> GemmaArch:
 
 
 @dataclass(frozen=True)
+class Gemma2Arch:
+    """transformers' Gemma2Model (model_type "gemma2": BAAI/bge-multilingual-gemma2, Gemma-2-2B-shaped fine-tunes) as the engine runs it: GemmaArch's
+    block (an RMSNorm in front of and behind each sub-layer, weights applied as 1 + w, a gated tanh-GELU MLP, the token table scaled by sqrt(width))
+    without q / k norm, with one rotary base, under a causal mask, the attention logits soft-capped, softcap * tanh(scale q.k / softcap); `sliding`
+    layers see only the keys j with i - window < j <= i.  The defaults are Gemma-2-9B's."""
+    vocab: int = 256000
+    max_pos: int = 8192
+    width: int = 3584
+    layers: int = 42
+    heads: int = 16
+    kv_heads: int = 8
+    head_dim: int = 256
+    mlp_dim: int = 14336
+    rms_eps: float = 1e-6
+    sliding: Tuple[bool, ...] = ()        # per layer: True = sliding_attention, False = full_attention
+    window: int = 4096
+    rope_theta: float = 10000.0
+    query_pre_attn_scalar: float = 256.0
+    softcap: float = 50.0
+    qk_norm = False        # (the two switches tower_weights.qwen_state_dict reads)
+    qkv_bias = False
+
+    @property
+    def attn_scale(self) -> float:
+        return float(self.query_pre_attn_scalar) ** -0.5
+
+    def inv_freq(self):
+        """[head_dim / 2] inverse frequencies as transformers' default rope initialisation builds them: theta^-(2i/d)"""
+        import torch
+        d = self.head_dim
+        return 1.0 / (self.rope_theta ** (torch.arange(0, d, 2, dtype=torch.int64).to(torch.float32) / d))
+
+    def gflop_per_text(self, tokens: int) -> float:
+        T, W, F, A = tokens, self.width, self.mlp_dim, self.heads * self.head_dim
+        full = 2 * T * W * (A + 2 * self.kv_heads * self.head_dim) + 2 * T * A * W + 2 * 3 * T * W * F
+        attn = sum(4 * T * k * A - 2 * k * k * A for k in (min(T, self.window) if s else T for s in self.sliding))
+        return (self.layers * full + attn) / 1e9
+
+
+def gemma2_arch_from_hf_config(cfg: dict) -> Gemma2Arch:
+    """A local Gemma2 `config.json` (model_type "gemma2") -> Gemma2Arch.  rope_theta comes from `rope_parameters`, else the older top-level key; the
+    layer kinds from `layer_types`, else transformers' default (layer i slides when i is even).  Refused, each by the name of its key: head_dim other
+    than 256, hidden_size above 4096 or no multiple of 64 (the 27B), attn_logit_softcapping null or outside (0, 64] (the attention kernel's fixed
+    reference exponent), rope_scaling or a non-default rope_type, hidden_activation other than gelu_pytorch_tanh, attention_bias, intermediate_size
+    no multiple of 64, a sliding_window below 1.  final_logit_softcapping belongs to the language-model head, which an embedder does not run.
+    bert_arch_from_hf_config does not route here — it keeps refusing the model type for the callers that run BERT-family encoders only; the `hf` loader
+    selects it before it calls."""
+    mtype = cfg.get("model_type")
+    if mtype != "gemma2":
+        raise KeyError(f"model_type={mtype} is not a Gemma2 model")
+    act = cfg.get("hidden_activation") if cfg.get("hidden_activation") is not None else cfg.get("hidden_act", "gelu_pytorch_tanh")
+    if act != "gelu_pytorch_tanh":
+        raise KeyError(f"hidden_activation={act} unsupported (gelu_pytorch_tanh only)")
+    if cfg.get("rope_scaling"):
+        raise KeyError(f"rope_scaling={cfg.get('rope_scaling')} unsupported")
+    rp = cfg.get("rope_parameters") or {}
+    rtype = rp.get("rope_type", rp.get("type", "default"))
+    if rtype != "default" or rp.get("factor") is not None:
+        raise KeyError(f"rope_parameters.rope_type={rtype} unsupported (default, without scaling, only)")
+    if cfg.get("attention_bias", False):
+        raise KeyError("attention_bias=true unsupported (bias-free projections only)")
+    cap = cfg.get("attn_logit_softcapping")
+    if not isinstance(cap, (int, float)) or isinstance(cap, bool) or not 0 < cap <= 64:
+        raise KeyError(f"attn_logit_softcapping={cap} unsupported (a number in (0, 64]: the attention kernel takes the softmax of capped scores against "
+                       f"a fixed reference exponent)")
+    W, heads, layers = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    kv = int(cfg.get("num_key_value_heads") or heads)
+    if heads < 1 or kv < 1 or heads % kv:
+        raise KeyError(f"num_attention_heads={heads} must be a multiple of num_key_value_heads={kv}")
+    hd = int(cfg.get("head_dim") or 256)
+    if hd != 256:
+        raise KeyError(f"head_dim={hd} unsupported (256 only)")
+    if W > 4096 or W % 64:
+        raise KeyError(f"hidden_size={W} unsupported (a multiple of 64 up to 4096: the 27B size of this family is not served)")
+    F = int(cfg["intermediate_size"])
+    if F % 64:
+        raise KeyError(f"intermediate_size={F} must be a multiple of 64")
+    kinds = cfg.get("layer_types")
+    if kinds is None:
+        kinds = ["full_attention" if i % 2 else "sliding_attention" for i in range(layers)]
+    if len(kinds) != layers or any(k not in ("full_attention", "sliding_attention") for k in kinds):
+        raise KeyError(f"layer_types={kinds} must name full_attention / sliding_attention for each of the {layers} layers")
+    sw = cfg.get("sliding_window", 4096)
+    if any(k == "sliding_attention" for k in kinds) and (not isinstance(sw, int) or isinstance(sw, bool) or sw < 1):
+        raise KeyError(f"sliding_window={sw} unsupported (a positive integer)")
+    return Gemma2Arch(vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg.get("max_position_embeddings", 8192)), 8192), width=W, layers=layers, heads=heads,
+                      kv_heads=kv, head_dim=hd, mlp_dim=F, rms_eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                      sliding=tuple(k == "sliding_attention" for k in kinds), window=int(sw) if isinstance(sw, int) else 0,
+                      rope_theta=float(rp.get("rope_theta", cfg.get("rope_theta", 10000.0))),
+                      query_pre_attn_scalar=float(cfg.get("query_pre_attn_scalar", 256)), softcap=float(cap))
+
+
+@dataclass(frozen=True)
 class GemmaCausalArch:
     """transformers' GemmaForCausalLM / GemmaModel (model_type "gemma": Gemma-2B, the body of BAAI/bge-reranker-v2-gemma) as the engine runs it: pre-norm
     decoder blocks with two RMSNorms (weights applied as 1 + w), `kv_heads` K/V heads of width 256 shared by `heads` query heads, rotary positions with

@@ -518,6 +518,25 @@ def gemma_causal_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     return out
 
 
+def gemma2_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """transformers' Gemma2Model tensors (with or without a `model.` prefix; `lm_head.*` is ignored) -> the fp32 tensors the Gemma2 tower hands to the
+    kernels: qwen_state_dict's names and fusions (no q / k norm, no bias) plus the two feed-forward norms of every block, then every norm weight as
+    1 + w (Gemma2RMSNorm multiplies by 1 + weight, the kernels by their weight) and the token table times sqrtf(width) — the fp32 product
+    Gemma2Model forms per gathered row, formed once here (the same rounding)."""
+    if any(k.endswith(".bias") and ".layers." in "." + k for k in sd):
+        raise ValueError("the Gemma2 tower runs bias-free blocks; this checkpoint carries bias tensors")
+    out = qwen_state_dict(arch, sd, tower="Gemma2")
+    pre = "" if "embed_tokens.weight" in sd else "model."
+    for l in range(arch.layers):
+        for n in ("pre_feedforward_layernorm", "post_feedforward_layernorm"):
+            out[f"layers.{l}.{n}.weight"] = _need(sd, f"{pre}layers.{l}.{n}.weight", (arch.width,)).detach().to(torch.float32)
+    for k in out:
+        if k.endswith("layernorm.weight") or k == "norm.weight":
+            out[k] = 1.0 + out[k]
+    out["embed_tokens.weight"] = out["embed_tokens.weight"] * torch.tensor(float(arch.width) ** 0.5, dtype=torch.float32)
+    return out
+
+
 def t5_state_dict(arch, sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
     """transformers' T5EncoderModel / T5Model / T5ForConditionalGeneration tensors -> the fp32 tensors the tower hands to the kernels.  The encoder's keys
     are taken with or without their `encoder.` prefix; the token table is `shared.weight`, else `encoder.embed_tokens.weight` / `embed_tokens.weight`;

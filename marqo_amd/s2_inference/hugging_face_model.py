@@ -137,8 +137,16 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 raise ModelLoadError(f"{props.name}: {e}") from e
             try:
                 # (Mistral / Llama are selected here: bert_arch_from_hf_config keeps refusing them for the callers that run BERT-family encoders only)
-                arch = archs.llama_arch_from_hf_config(cfg) if cfg.get("model_type") in ("mistral", "llama") else archs.bert_arch_from_hf_config(cfg)
+                # (so is Gemma2, the same way)
+                if cfg.get("model_type") in ("mistral", "llama"):
+                    arch = archs.llama_arch_from_hf_config(cfg)
+                elif cfg.get("model_type") == "gemma2":
+                    arch = archs.gemma2_arch_from_hf_config(cfg)
+                else:
+                    arch = archs.bert_arch_from_hf_config(cfg)
             except KeyError as e:
+                if cfg.get("model_type") == "gemma2":   # (a Gemma2 config that is refused is refused for its key, not for its family)
+                    raise InvalidModelPropertiesError(f"{props.name}: {e}") from e
                 raise InvalidModelPropertiesError(f"{props.name}: {e}. Only BERT-family encoders run on the marqo_amd engine.") from e
             if props.weight_precision != "bf16" and not isinstance(arch, archs.LlamaArch):
                 raise InvalidModelPropertiesError(f"{props.name}: 'weightPrecision': {props.weight_precision!r} is available for Mistral / Llama "
@@ -154,6 +162,9 @@ class HuggingFaceModel(AbstractEmbeddingModel):
                 return
             if isinstance(arch, archs.GemmaArch):
                 self._load_gemma(directory, arch, sd)
+                return
+            if isinstance(arch, archs.Gemma2Arch):
+                self._load_gemma2(directory, arch, cfg, sd)
                 return
             if isinstance(arch, archs.T5Arch):
                 self._load_t5(directory, arch, sd)
@@ -304,13 +315,22 @@ class HuggingFaceModel(AbstractEmbeddingModel):
         self._load_decoder(directory, arch, cfg, sd, LlamaTower, "Mistral / Llama encoders", tower_args=dict(weight_precision=wp) if wp != "bf16" else None,
                            pad_fallback="</s>")
 
-    def _load_decoder(self, directory: str, arch, cfg: dict, sd, tower, family: str, tower_args: Optional[dict] = None, **tokenizer_args) -> None:
+    def _load_gemma2(self, directory: str, arch, cfg: dict, sd) -> None:
+        """a transformers Gemma2Model checkpoint (model_type "gemma2": BAAI/bge-multilingual-gemma2, Gemma-2-2B-shaped fine-tunes; AutoModel in the
+        reference), loaded as the Qwen checkpoints are: the file's own post-processor decides what surrounds a text (<bos> ... and, for the bge
+        checkpoint, <eos>), the tower of engine/gemma2.py.  Pooling: the property, else 1_Pooling/config.json (last token / mean), else last token.
+        bf16 operands only."""
+        from marqo_amd.engine.gemma2 import Gemma2Tower
+        self._load_decoder(directory, arch, cfg, sd, Gemma2Tower, "Gemma2 encoders", mlp="gated tanh-GELU", pad_fallback="<pad>")
+
+    def _load_decoder(self, directory: str, arch, cfg: dict, sd, tower, family: str, tower_args: Optional[dict] = None, mlp: str = "gated-SiLU",
+                      **tokenizer_args) -> None:
         """what the decoder-style families share: fp8 refused, the width checked, last-token / mean pooling resolved, right-padded input truncated at
         min(tokens, max_position_embeddings, 8192); tokenizer_args: HfJsonTokenizer.plain's (the pad token to fall back to: a pad position never reaches a row)"""
         import json
         from marqo_amd.engine.tokenizers import HfJsonTokenizer
         props = self.model_properties
-        self._refuse_fp8(f"{family} (their RMSNorm / rotary / gated-SiLU blocks run on bf16 operands only)")
+        self._refuse_fp8(f"{family} (their RMSNorm / rotary / {mlp} blocks run on bf16 operands only)")
         self._check_width(arch.width)
         pooling = props.pooling_method
         if pooling is None:
