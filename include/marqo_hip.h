@@ -1996,6 +1996,23 @@ int mq_gemm_small_w4(const void* d_A, int64_t lda, const void* d_W4, int64_t ld4
 int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                        const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mistral / Llama from MXFP4 weights ALONE: the tiled W4A16 GEMM and the tower entry point that needs no bf16 block matrix
+ * (csrc/gemm_w4.hip, csrc/llama.hip; engine/llama.py LlamaTower(weight_precision="mxfp4-only")) ------------------------------------------------------
+ * Additions to ABI 15: nothing above changes.  Operands, storage, epilogue flags and leading-dimension rules are mq_gemm_small_w4's; each entry point
+ * judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on `stream` and allocates nothing.
+ *
+ *   mq_gemm_w4:     d_out [M, ldc] = epi(d_A bf16 [M, lda] @ dequant(d_W4, d_scale)^T) for ANY M >= 1, N % 4 == 0, K % 64 == 0: 128 x 256 tiles, the
+ *                   codes global -> VGPR (each decoded once by the one wave that owns its 16 columns, used for all 8 row tiles), A through an LDS
+ *                   ring by LDS-DMA.  One accumulator per output, k summed in one fixed order, no split-K: a row's bits do not depend on M or on the
+ *                   rows that share its tile.  Not bit-equal to mq_gemm_small_w4 or to mq_gemm_bf16 on the dequantised copy (other k orders).
+ *   mq_encode_llama_w4_only: mq_encode_llama_w4 without bf16 block matrices: qkv_w / out_w / ug_w / down_w of every w->layers entry are NULL (a
+ *                   non-null one is refused); a block GEMM runs mq_gemm_small_w4 where mq_gemm_small_w4_ok holds (those calls give
+ *                   mq_encode_llama_w4's bits) and mq_gemm_w4 elsewhere. */
+int mq_gemm_w4(const void* d_A, int64_t lda, const void* d_W4, int64_t ld4, const void* d_scale, int64_t lds, const float* d_bias, const void* d_residual,
+               void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+int mq_encode_llama_w4_only(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                            const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Mixture-of-experts NomicBERT (nomic-embed-text-v2-moe): router, device-side plan, grouped bf16 GEMM, and the tower
  * (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py) ---------------------------------------------------------------------------------------------------
  * The Jina v3 base block (post-LN, biased Wqkv / out_proj, rotate-half rope over 64-wide heads, full attention) whose MLP is, layer by layer, either

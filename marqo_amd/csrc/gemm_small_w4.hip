@@ -40,6 +40,7 @@
 // 140 -> 3; 4 waves 56 + 4 -> 8, 67 + 8 -> 6, 84 + 12 -> 5, 102 + 16 -> 4, 121 + 20 -> 3; the same for the three epilogues.  Quantiser: 41 -> 8.
 #include "common.h"
 #include "knobs.h"
+#include "w4_decode.h"
 
 bool mq_gemm_small_ok(int64_t M, int64_t N, int64_t K, bool ln);
 bool mq_gemm_small_grouped_ok(int64_t M, int64_t N, int64_t K);
@@ -48,37 +49,7 @@ namespace {
 
 constexpr int W4_BN = 16;       // output columns per workgroup
 constexpr int W4_MAX_MT = 5;    // 16-row tiles per row group: 80 rows, as gemm_small.hip
-constexpr int W4_BK = 128;      // k per chunk: four 32-blocks, 16 B of codes per lane
-constexpr int W4_KMULT = 64;    // K % 64 == 0, as the W8 kernel
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// the scaled decode table of one block: bf16(magnitude[i] x 2^(sb - 127)), i = 0 .. 7, low bytes in {tl1, tl0}, high bytes in {th1, th0} (byte i).
-// Index 1 (0.5) has the exponent field e0 = sb - 1 and mantissa 0; index i >= 2 has e0 + (i >> 1) and mantissa bit 6 = i & 1; index 0 is 0.
-struct W4Table { uint32_t tl0, tl1, th0, th1; };
-
-__device__ __forceinline__ W4Table w4_table(uint32_t sb) {
-    const uint32_t e0 = sb - 1, h = e0 >> 1, par = e0 & 1;
-    W4Table t;
-    t.tl0 = 0xC0800000u ^ (par * 0x80808000u);               // bit 7 = the exponent field's bit 0, bit 6 = the mantissa bit
-    t.tl1 = 0xC0804000u ^ (par * 0x80808080u);
-    t.th0 = h * 0x01010100u + par * 0x01010000u;             // (e0 + (i >> 1)) >> 1; sb <= 227 keeps every byte below 0x80: the sign bit stays free
-    t.th1 = (h + 1) * 0x01010101u + par * 0x01010000u;
-    return t;
-}
-
-// eight codes (one dword of the storage above) -> eight bf16 at k offsets 0 .. 7, scale included
-__device__ __forceinline__ bf16x8 w4_decode8(uint32_t q, const W4Table& t) {
-    const uint32_t ev = q & 0x07070707u, od = (q >> 4) & 0x07070707u;     // magnitude indices of k offsets 0 .. 3 and 4 .. 7, one per byte
-    const uint32_t le = __builtin_amdgcn_perm(t.tl1, t.tl0, ev), he = __builtin_amdgcn_perm(t.th1, t.th0, ev) | ((q & 0x08080808u) << 4);
-    const uint32_t lo = __builtin_amdgcn_perm(t.tl1, t.tl0, od), ho = __builtin_amdgcn_perm(t.th1, t.th0, od) | (q & 0x80808080u);
-    u32x4 d;
-    d[0] = __builtin_amdgcn_perm(he, le, 0x05010400u);
-    d[1] = __builtin_amdgcn_perm(he, le, 0x07030602u);
-    d[2] = __builtin_amdgcn_perm(ho, lo, 0x05010400u);
-    d[3] = __builtin_amdgcn_perm(ho, lo, 0x07030602u);
-    return __builtin_bit_cast(bf16x8, d);
-}
+// (W4_BK = 128, W4_KMULT = 64, W4Table / w4_table / w4_decode8, w4_chunks: w4_decode.h, shared with the tiled kernel)
 
 template <int FLAGS, int MT, int NW, int G>
 __global__ __launch_bounds__(NW * 64) void gemm_small_w4_kernel(const bf16_t* __restrict__ A, int64_t lda, const uint8_t* __restrict__ W4, int64_t ld4,
@@ -279,8 +250,6 @@ __global__ __launch_bounds__(256) void quantize_mxfp4_kernel(bf16_t* __restrict_
         *(u32x4*)(w + k) = r;
     }
 }
-
-int64_t w4_chunks(int64_t K) { return (K + W4_BK - 1) / W4_BK; }
 
 }  // namespace
 

@@ -187,15 +187,20 @@ extern "C" size_t mq_llama_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows
 namespace {
 // the tower; w8 (nullable): the e4m3 copies of the four block weights of every layer — a GEMM whose shape the W8A16 skinny kernel takes streams those,
 // every other call runs mq_gemm_bf16 on the bf16 weight, which mq_quantize_weights_pow2 has rewritten with the same numbers (gemm_small_w8.hip);
-// w4 (nullable, instead of w8): the MXFP4 copies and their block scales, streamed by the W4A16 skinny kernel in the same way (gemm_small_w4.hip)
-int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+// w4 (nullable, instead of w8): the MXFP4 copies and their block scales, streamed by the W4A16 skinny kernel in the same way (gemm_small_w4.hip);
+// w4_only (with w4): the layers carry NO bf16 block matrices, and a call the skinny kernel does not take runs the tiled W4A16 kernel (gemm_w4.hip)
+int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const mq_w4_layer* w4, bool w4_only, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                  const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
     MQ_TRY(check_cfg(cfg));
     MQ_CHECK_ARG(w && d_out, "mq_encode_llama: null pointer");
     MQ_CHECK_ARG(w->tok_emb && w->final_norm_g && w->zeros && w->d_inv_freq && w->layers, "mq_encode_llama: null weight pointer");
     for (int l = 0; l < cfg->layers; ++l) {
         const mq_qwen_layer& b = w->layers[l];
-        MQ_CHECK_ARG(b.input_norm_g && b.qkv_w && b.out_w && b.post_norm_g && b.ug_w && b.down_w, "mq_encode_llama: layer %d has null weights", l);
+        if (w4_only) {
+            MQ_CHECK_ARG(b.input_norm_g && b.post_norm_g, "mq_encode_llama_w4_only: layer %d has null norm weights", l);
+            MQ_CHECK_ARG(!b.qkv_w && !b.out_w && !b.ug_w && !b.down_w, "mq_encode_llama_w4_only: layer %d carries a bf16 block matrix (this entry point reads the MXFP4 codes only)", l);
+        } else
+            MQ_CHECK_ARG(b.input_norm_g && b.qkv_w && b.out_w && b.post_norm_g && b.ug_w && b.down_w, "mq_encode_llama: layer %d has null weights", l);
         MQ_CHECK_ARG(!b.qkv_b && !b.q_norm_g && !b.k_norm_g, "mq_encode_llama: layer %d carries a QKV bias or q / k norm weights (this block has neither)", l);
         if (w8) {
             const mq_w8_layer& q = w8[l];
@@ -232,6 +237,7 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
                     int flags) {
         if (Wq && w4 && mq_gemm_small_w4_ok(rows, N, K))
             return mq_gemm_small_w4(A, lda, Wq, (K + 127) / 128 * 64, sc, (K + 127) / 128 * 4, bias, res, out, N, rows, N, K, flags, s);
+        if (w4_only) return mq_gemm_w4(A, lda, Wq, (K + 127) / 128 * 64, sc, (K + 127) / 128 * 4, bias, res, out, N, rows, N, K, flags, s);
         if (Wq && w8 && mq_gemm_small_w8_ok(rows, N, K)) return mq_gemm_small_w8(A, lda, Wq, K, (const float*)sc, bias, res, out, N, rows, N, K, flags, s);
         return mq_gemm_bf16(A, lda, Wb, K, bias, (const float*)res, out, N, rows, N, K, flags, s);
     };
@@ -267,7 +273,7 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
 
 extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                                int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
-    return encode_llama(cfg, w, nullptr, nullptr, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, nullptr, nullptr, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
@@ -276,7 +282,7 @@ extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights
     MQ_CHECK_ARG(w8, "mq_encode_llama_w8: null e4m3 weights");
     MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
                  "mq_encode_llama_w8: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the e4m3 rows are walked in 64-deep chunks)");
-    return encode_llama(cfg, w, w8, nullptr, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, w8, nullptr, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
@@ -285,5 +291,14 @@ extern "C" int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights
     MQ_CHECK_ARG(w4, "mq_encode_llama_w4: null MXFP4 weights");
     MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
                  "mq_encode_llama_w4: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the MXFP4 rows are stored in 128-deep chunks, the last one half)");
-    return encode_llama(cfg, w, nullptr, w4, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, nullptr, w4, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int mq_encode_llama_w4_only(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                                       const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes,
+                                       void* stream) {
+    MQ_CHECK_ARG(w4, "mq_encode_llama_w4_only: null MXFP4 weights");
+    MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
+                 "mq_encode_llama_w4_only: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the MXFP4 rows are stored in 128-deep chunks, the last one half)");
+    return encode_llama(cfg, w, nullptr, w4, true, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }

@@ -418,8 +418,10 @@ std::tuple<at::Tensor, at::Tensor> quantize_weights_mxfp4(at::Tensor W) {
     return {W4, scale};
 }
 
-at::Tensor gemm_small_w4(const at::Tensor& A, const at::Tensor& W4, const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
-                         const c10::optional<at::Tensor>& residual, int64_t flags) {
+// the skinny kernel (mq_gemm_small_w4) or the tiled one (mq_gemm_w4, csrc/gemm_w4.hip: any M): same operands, same epilogues
+template <bool TILED>
+at::Tensor gemm_w4_op(const at::Tensor& A, const at::Tensor& W4, const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                      const c10::optional<at::Tensor>& residual, int64_t flags) {
     need_dev(A, at::kBFloat16, "A");
     need_dev(W4, at::kByte, "W4");
     need_dev(scale, at::kByte, "scale");
@@ -443,8 +445,9 @@ at::Tensor gemm_small_w4(const at::Tensor& A, const at::Tensor& W4, const at::Te
     }
     at::Tensor out = at::empty({M, N}, A.options().dtype(f32 ? at::kFloat : at::kBFloat16));
     // (the row strides are the tensors' widths: the entry point refuses rows shorter than K's chunks need)
-    check_rc(mq_gemm_small_w4(A.data_ptr(), K, W4.data_ptr(), W4.size(1), scale.data_ptr(), scale.size(1), b, r, out.data_ptr(), N, M, N, K, (int)flags, stream_of(A)),
-             "mq_gemm_small_w4");
+    check_rc((TILED ? mq_gemm_w4 : mq_gemm_small_w4)(A.data_ptr(), K, W4.data_ptr(), W4.size(1), scale.data_ptr(), scale.size(1), b, r, out.data_ptr(), N, M, N, K,
+                                                      (int)flags, stream_of(A)),
+             TILED ? "mq_gemm_w4" : "mq_gemm_small_w4");
     return out;
 }
 
@@ -482,6 +485,7 @@ TORCH_LIBRARY(marqo_hip, m) {
     m.def("mq_gemm_small_w8(Tensor A, Tensor W8, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
     m.def("mq_quantize_weights_mxfp4(Tensor(a!) W) -> (Tensor, Tensor)");
     m.def("mq_gemm_small_w4(Tensor A, Tensor W4, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
+    m.def("mq_gemm_w4(Tensor A, Tensor W4, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -507,5 +511,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_quantize_weights_pow2", &quantize_weights_pow2);
     m.impl("mq_gemm_small_w8", &gemm_small_w8);
     m.impl("mq_quantize_weights_mxfp4", &quantize_weights_mxfp4);
-    m.impl("mq_gemm_small_w4", &gemm_small_w4);
+    m.impl("mq_gemm_small_w4", &gemm_w4_op<false>);
+    m.impl("mq_gemm_w4", &gemm_w4_op<true>);
 }
