@@ -2013,6 +2013,34 @@ int mq_gemm_w4(const void* d_A, int64_t lda, const void* d_W4, int64_t ld4, cons
 int mq_encode_llama_w4_only(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                             const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mistral / Llama indexing from MXFP4 codes on the MX matrix instruction: the MXFP8 activation quantiser, the W4A8 tiled GEMM and the tower entry point
+ * (csrc/gemm_w4a8.hip, csrc/llama.hip; engine/llama.py LlamaTower(weight_precision="mxfp4-a8")) --------------------------------------------------------
+ * Additions to ABI 15: nothing above changes.  The weight operand (d_W4, ld4, d_scale, lds) is mq_gemm_small_w4's, unchanged: one copy serves every
+ * kernel.  Each entry point judges its arguments before any launch (MQ_ERR_INVALID, the message names the entry point and the bad value), runs on
+ * `stream` and allocates nothing.
+ *
+ *   mq_a8_bytes:    the size of the quantised copy of M rows of K elements whose code rows are ld8 bytes apart: M ld8 bytes of e4m3fn codes, then
+ *                   ceil(M / 128) ceil(K / 128) 512 bytes of e8m0 block scales (0 for a non-positive argument).
+ *   mq_quantize_rows_mxfp8: d_A bf16 [M, lda] -> d_A8 (mq_a8_bytes(M, ld8, K) bytes): per 32 consecutive k one scale 2^ceil(log2(absmax / 448)) (1 for
+ *                   an all-zero block, exponent inside [-100, 100]) and the codes RNE(a / scale); K % 64 == 0, ld8 % 16 == 0, ld8 >= ceil(K / 128) 128;
+ *                   a half last chunk is padded with zero codes and unit scales.  The byte order inside the buffer is the GEMM's and private to the
+ *                   two (csrc/gemm_w4a8.hip states it).
+ *   mq_gemm_w4a8:   d_out [M, ldc] = epi(dequant(d_A8) @ dequant(d_W4, d_scale)^T) for ANY M >= 1, N % 4 == 0, K % 64 == 0, with d_A8 / ld8 / M / K as
+ *                   handed to mq_quantize_rows_mxfp8; mq_gemm_w4's epilogues (0; MQ_EPI_BIAS; MQ_EPI_BIAS | MQ_EPI_RESIDUAL | MQ_EPI_OUT_F32 with an
+ *                   fp32 residual that may alias d_out).  v_mfma_scale_f32_16x16x128_f8f6f4 on both operands as stored, the block scales of both
+ *                   applied by the instruction, fp32 accumulation.  One accumulator per output, k in one fixed order, no split-K: a row's bits do not
+ *                   depend on M or on the rows that share its tile.
+ *   mq_llama_w4a8_workspace_bytes: mq_llama_workspace_bytes plus the quantised copy of the widest GEMM input of `rows` rows.
+ *   mq_encode_llama_w4a8: mq_encode_llama_w4_only, except that a block GEMM the skinny kernel does not take quantises its input rows
+ *                   (mq_quantize_rows_mxfp8) and runs mq_gemm_w4a8; the calls mq_gemm_small_w4 takes give mq_encode_llama_w4_only's bits. */
+size_t mq_a8_bytes(int64_t M, int64_t ld8, int64_t K);
+int mq_quantize_rows_mxfp8(const void* d_A, int64_t lda, void* d_A8, int64_t ld8, int64_t M, int64_t K, void* stream);
+int mq_gemm_w4a8(const void* d_A8, int64_t ld8, const void* d_W4, int64_t ld4, const void* d_scale, int64_t lds, const float* d_bias, const void* d_residual,
+                 void* d_out, int64_t ldc, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+size_t mq_llama_w4a8_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows, int64_t nseq);
+int mq_encode_llama_w4a8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                         const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Mixture-of-experts NomicBERT (nomic-embed-text-v2-moe): router, device-side plan, grouped bf16 GEMM, and the tower
  * (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py) ---------------------------------------------------------------------------------------------------
  * The Jina v3 base block (post-LN, biased Wqkv / out_proj, rotate-half rope over 64-wide heads, full attention) whose MLP is, layer by layer, either

@@ -28,7 +28,7 @@ STAGE_SRC = CSRC_DIR / "py_stage.cpp"
 STAGE_PATH = LIB_DIR / "_mq_stage.so"                # CPython extension: a batch of Pillow images -> the pinned staging buffer in one call
 
 MQ_OK = 0
-NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "gemm_small_w8", "gemm_small_w4", "gemm_w4", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_gqa256_softcap", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe", "colbert", "gemma2")  # build() refuses register spills in these
+NO_SCRATCH_UNITS = ("rowops", "gemm_bf16", "gemm_wd", "gemm_fp8", "gemm_small", "gemm_small_w8", "gemm_small_w4", "gemm_w4", "gemm_w4a8", "attention", "attention_window", "attention_gqa", "attention_gqa256", "attention_gqa256_causal", "attention_gqa256_softcap", "attention_relbias", "attention_alibi", "attention_disentangled", "attention_full", "lora", "attn_proj", "panel_gemm", "embed", "convnext", "resnet", "patch_attn", "rerank", "owl_head", "temporal", "audio", "video", "moe", "colbert", "gemma2")  # build() refuses register spills in these
 ABI_VERSION = 15
 MQ_PREC_BF16, MQ_PREC_FP8 = 0, 1
 MQ_ACT_GELU, MQ_ACT_QUICKGELU, MQ_ACT_SILU, MQ_ACT_RELU = 1, 2, 3, 4
@@ -627,6 +627,13 @@ _SIGNATURES = {
     # ... from MXFP4 weights alone: the tiled W4A16 GEMM and the tower entry point without bf16 block matrices (csrc/gemm_w4.hip, csrc/llama.hip)
     "mq_gemm_w4": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P]),
     "mq_encode_llama_w4_only": (C.c_int, [C.POINTER(LlamaCfg), C.POINTER(QwenWeights), C.POINTER(W4Layer), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    # ... from MXFP4 codes on the MX matrix instruction: the MXFP8 activation quantiser, the W4A8 tiled GEMM, the tower entry point and its workspace
+    # (csrc/gemm_w4a8.hip, csrc/llama.hip)
+    "mq_a8_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "mq_quantize_rows_mxfp8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "mq_gemm_w4a8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P]),
+    "mq_llama_w4a8_workspace_bytes": (C.c_size_t, [C.POINTER(LlamaCfg), C.c_int64, C.c_int64]),
+    "mq_encode_llama_w4a8": (C.c_int, [C.POINTER(LlamaCfg), C.POINTER(QwenWeights), C.POINTER(W4Layer), _P, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     # mixture-of-experts NomicBERT: router, plan, grouped GEMM, combine and the tower (csrc/moe.hip, csrc/nomic_moe.hip; engine/nomic_moe.py)
     "mq_moe_tile_rows": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32]),
     "mq_moe_max_tiles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
@@ -682,7 +689,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     # units compiled without the packed fp32 VALU forms (v_pk_add / mul / fma_f32): the compiler then pairs no fp32 arithmetic of their epilogues
     # (colbert: nothing to gain — its kernels' VGPR counts and bits are the same either way, checked — so the unit takes the conservative form that units
     # added since moe take: scalar fp32 VALU only, one code-generation path less to trust in kernels whose results are compared bit for bit)
-    unit_flags = {u: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] for u in ("moe", "colbert", "gemm_small_w8", "gemm_small_w4", "gemm_w4")}
+    unit_flags = {u: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] for u in ("moe", "colbert", "gemm_small_w8", "gemm_small_w4", "gemm_w4", "gemm_w4a8")}
 
     def compile_one(src: str):
         obj = obj_dir / (Path(src).stem + ".o")

@@ -121,6 +121,11 @@ Plan plan(const mq_llama_cfg* c, int64_t rows, int64_t nseq) {
     p.total = ws.end();
     return p;
 }
+// the MXFP8 copy of the widest GEMM input of `rows` rows (mq_a8_bytes, csrc/gemm_w4a8.hip)
+size_t a8_scratch_bytes(const mq_llama_cfg* c, int64_t rows) {
+    const int64_t aw = (int64_t)c->q_heads * c->head_dim, kmax = std::max<int64_t>(std::max<int64_t>(c->width, c->mlp_dim), aw);
+    return align_up(mq_a8_bytes(rows, (kmax + 127) / 128 * 128, kmax), WS_ALIGN);
+}
 int check_cfg(const mq_llama_cfg* c) {
     MQ_CHECK_ARG(c, "mq_encode_llama: null cfg");
     MQ_CHECK_ARG(c->head_dim == 64 || c->head_dim == 128, "mq_encode_llama: head_dim %d unsupported (64 or 128)", c->head_dim);
@@ -188,8 +193,9 @@ namespace {
 // the tower; w8 (nullable): the e4m3 copies of the four block weights of every layer — a GEMM whose shape the W8A16 skinny kernel takes streams those,
 // every other call runs mq_gemm_bf16 on the bf16 weight, which mq_quantize_weights_pow2 has rewritten with the same numbers (gemm_small_w8.hip);
 // w4 (nullable, instead of w8): the MXFP4 copies and their block scales, streamed by the W4A16 skinny kernel in the same way (gemm_small_w4.hip);
-// w4_only (with w4): the layers carry NO bf16 block matrices, and a call the skinny kernel does not take runs the tiled W4A16 kernel (gemm_w4.hip)
-int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const mq_w4_layer* w4, bool w4_only, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+// w4_only (with w4): the layers carry NO bf16 block matrices, and a call the skinny kernel does not take runs the tiled W4A16 kernel (gemm_w4.hip);
+// a8 (with w4_only): such a call quantises its input rows to MXFP8 into scratch behind the plan's workspace and runs the W4A8 kernel (gemm_w4a8.hip)
+int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const mq_w4_layer* w4, bool w4_only, bool a8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
                  const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
     MQ_TRY(check_cfg(cfg));
     MQ_CHECK_ARG(w && d_out, "mq_encode_llama: null pointer");
@@ -218,7 +224,7 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
     int64_t rows = 0;
     MQ_TRY(packed_begin("mq_encode_llama", d_ids, d_cu_seqlens, h_cu_seqlens, nseq, cfg->max_pos, d_workspace, &maxl, &rows));
     const Plan p = plan(cfg, rows, nseq);
-    MQ_TRY(packed_workspace("mq_encode_llama", workspace_bytes, p.total));
+    MQ_TRY(packed_workspace("mq_encode_llama", workspace_bytes, p.total + (a8 ? a8_scratch_bytes(cfg, rows) : 0)));
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)d_workspace;
     float* x = (float*)(base + p.off_x);
@@ -237,6 +243,11 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
                     int flags) {
         if (Wq && w4 && mq_gemm_small_w4_ok(rows, N, K))
             return mq_gemm_small_w4(A, lda, Wq, (K + 127) / 128 * 64, sc, (K + 127) / 128 * 4, bias, res, out, N, rows, N, K, flags, s);
+        if (a8) {
+            const int64_t ld8 = (K + 127) / 128 * 128;
+            MQ_TRY(mq_quantize_rows_mxfp8(A, lda, base + p.total, ld8, rows, K, s));
+            return mq_gemm_w4a8(base + p.total, ld8, Wq, (K + 127) / 128 * 64, sc, (K + 127) / 128 * 4, bias, res, out, N, rows, N, K, flags, s);
+        }
         if (w4_only) return mq_gemm_w4(A, lda, Wq, (K + 127) / 128 * 64, sc, (K + 127) / 128 * 4, bias, res, out, N, rows, N, K, flags, s);
         if (Wq && w8 && mq_gemm_small_w8_ok(rows, N, K)) return mq_gemm_small_w8(A, lda, Wq, K, (const float*)sc, bias, res, out, N, rows, N, K, flags, s);
         return mq_gemm_bf16(A, lda, Wb, K, bias, (const float*)res, out, N, rows, N, K, flags, s);
@@ -273,7 +284,7 @@ int encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_
 
 extern "C" int mq_encode_llama(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const int32_t* d_ids, const int32_t* d_cu_seqlens, const int32_t* h_cu_seqlens,
                                int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes, void* stream) {
-    return encode_llama(cfg, w, nullptr, nullptr, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, nullptr, nullptr, false, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w8_layer* w8, const int32_t* d_ids, const int32_t* d_cu_seqlens,
@@ -282,7 +293,7 @@ extern "C" int mq_encode_llama_w8(const mq_llama_cfg* cfg, const mq_qwen_weights
     MQ_CHECK_ARG(w8, "mq_encode_llama_w8: null e4m3 weights");
     MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
                  "mq_encode_llama_w8: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the e4m3 rows are walked in 64-deep chunks)");
-    return encode_llama(cfg, w, w8, nullptr, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, w8, nullptr, false, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
@@ -291,7 +302,7 @@ extern "C" int mq_encode_llama_w4(const mq_llama_cfg* cfg, const mq_qwen_weights
     MQ_CHECK_ARG(w4, "mq_encode_llama_w4: null MXFP4 weights");
     MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
                  "mq_encode_llama_w4: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the MXFP4 rows are stored in 128-deep chunks, the last one half)");
-    return encode_llama(cfg, w, nullptr, w4, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, nullptr, w4, false, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int mq_encode_llama_w4_only(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
@@ -300,5 +311,19 @@ extern "C" int mq_encode_llama_w4_only(const mq_llama_cfg* cfg, const mq_qwen_we
     MQ_CHECK_ARG(w4, "mq_encode_llama_w4_only: null MXFP4 weights");
     MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
                  "mq_encode_llama_w4_only: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the MXFP4 rows are stored in 128-deep chunks, the last one half)");
-    return encode_llama(cfg, w, nullptr, w4, true, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+    return encode_llama(cfg, w, nullptr, w4, true, false, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t mq_llama_w4a8_workspace_bytes(const mq_llama_cfg* cfg, int64_t rows, int64_t nseq) {
+    if (!cfg || rows <= 0 || nseq <= 0) return 0;
+    return plan(cfg, rows, nseq).total + a8_scratch_bytes(cfg, rows);
+}
+
+extern "C" int mq_encode_llama_w4a8(const mq_llama_cfg* cfg, const mq_qwen_weights* w, const mq_w4_layer* w4, const int32_t* d_ids, const int32_t* d_cu_seqlens,
+                                    const int32_t* h_cu_seqlens, int64_t nseq, float* d_out, int normalize, void* d_workspace, size_t workspace_bytes,
+                                    void* stream) {
+    MQ_CHECK_ARG(w4, "mq_encode_llama_w4a8: null MXFP4 weights");
+    MQ_CHECK_ARG(cfg && cfg->width % 64 == 0 && cfg->mlp_dim % 64 == 0 && (cfg->q_heads * cfg->head_dim) % 64 == 0,
+                 "mq_encode_llama_w4a8: width, mlp_dim and q_heads * head_dim must be multiples of 64 (the MXFP4 rows are stored in 128-deep chunks, the last one half)");
+    return encode_llama(cfg, w, nullptr, w4, true, true, d_ids, d_cu_seqlens, h_cu_seqlens, nseq, d_out, normalize, d_workspace, workspace_bytes, stream);
 }

@@ -451,6 +451,50 @@ at::Tensor gemm_w4_op(const at::Tensor& A, const at::Tensor& W4, const at::Tenso
     return out;
 }
 
+// ---- MXFP4 x MXFP8 W4A8 (csrc/gemm_w4a8.hip) ----
+// A bf16 [M, K] -> the quantised copy, uint8 [M + 4 ceil(M / 128), ceil(K / 128) 128]: M rows of e4m3fn codes, then the block scales (512 bytes per
+// 128-row tile and chunk = four rows' worth per tile); its byte order is the GEMM's own
+at::Tensor quantize_rows_mxfp8(at::Tensor A) {
+    need_dev(A, at::kBFloat16, "A");
+    TORCH_CHECK(A.dim() == 2 && A.size(0) >= 1, "marqo_hip::mq_quantize_rows_mxfp8: A [M,K]");
+    const int64_t M = A.size(0), K = A.size(1), ld8 = (K + 127) / 128 * 128;
+    at::Tensor A8 = at::empty({M + 4 * ((M + 127) / 128), ld8}, A.options().dtype(at::kByte));
+    TORCH_CHECK((size_t)A8.numel() == mq_a8_bytes(M, ld8, K), "marqo_hip::mq_quantize_rows_mxfp8: buffer size");
+    check_rc(mq_quantize_rows_mxfp8(A.data_ptr(), K, A8.data_ptr(), ld8, M, K, stream_of(A)), "mq_quantize_rows_mxfp8");
+    return A8;
+}
+
+// A8: mq_quantize_rows_mxfp8's result for M rows of K elements; W4 / scale: mq_quantize_weights_mxfp4's
+at::Tensor gemm_w4a8(const at::Tensor& A8, int64_t M, int64_t K, const at::Tensor& W4, const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                     const c10::optional<at::Tensor>& residual, int64_t flags) {
+    need_dev(A8, at::kByte, "A8");
+    need_dev(W4, at::kByte, "W4");
+    need_dev(scale, at::kByte, "scale");
+    TORCH_CHECK(A8.dim() == 2 && W4.dim() == 2 && scale.dim() == 2 && scale.size(0) == W4.size(0) && M >= 1 && K >= 1 &&
+                    (size_t)A8.numel() == mq_a8_bytes(M, A8.size(1), K),
+                "marqo_hip::mq_gemm_w4a8: A8 = mq_quantize_rows_mxfp8(A [M,K]), W4 [N, ceil(K/128)*64], scale [N, ceil(K/128)*4]");
+    const int64_t N = W4.size(0);
+    const bool f32 = (flags & MQ_EPI_OUT_F32) != 0;
+    const float* b = nullptr;
+    const void* r = nullptr;
+    if (flags & MQ_EPI_BIAS) {
+        TORCH_CHECK(bias.has_value(), "marqo_hip::mq_gemm_w4a8: MQ_EPI_BIAS without bias");
+        need_dev(*bias, at::kFloat, "bias");
+        TORCH_CHECK(bias->numel() == N, "bias must be [N]");
+        b = (const float*)bias->data_ptr();
+    }
+    if (flags & MQ_EPI_RESIDUAL) {
+        TORCH_CHECK(residual.has_value(), "marqo_hip::mq_gemm_w4a8: MQ_EPI_RESIDUAL without residual");
+        need_dev(*residual, at::kFloat, "residual");
+        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == N, "residual must be [M,N]");
+        r = residual->data_ptr();
+    }
+    at::Tensor out = at::empty({M, N}, A8.options().dtype(f32 ? at::kFloat : at::kBFloat16));
+    check_rc(mq_gemm_w4a8(A8.data_ptr(), A8.size(1), W4.data_ptr(), W4.size(1), scale.data_ptr(), scale.size(1), b, r, out.data_ptr(), N, M, N, K, (int)flags, stream_of(A8)),
+             "mq_gemm_w4a8");
+    return out;
+}
+
 int64_t abi_version() { return mq_abi_version(); }
 
 }  // namespace
@@ -486,6 +530,8 @@ TORCH_LIBRARY(marqo_hip, m) {
     m.def("mq_quantize_weights_mxfp4(Tensor(a!) W) -> (Tensor, Tensor)");
     m.def("mq_gemm_small_w4(Tensor A, Tensor W4, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
     m.def("mq_gemm_w4(Tensor A, Tensor W4, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
+    m.def("mq_quantize_rows_mxfp8(Tensor A) -> Tensor");
+    m.def("mq_gemm_w4a8(Tensor A8, int M, int K, Tensor W4, Tensor scale, Tensor? bias, Tensor? residual, int flags) -> Tensor");
     m.def("abi_version() -> int", &abi_version);
 }
 
@@ -513,4 +559,6 @@ TORCH_LIBRARY_IMPL(marqo_hip, CUDA, m) {
     m.impl("mq_quantize_weights_mxfp4", &quantize_weights_mxfp4);
     m.impl("mq_gemm_small_w4", &gemm_w4_op<false>);
     m.impl("mq_gemm_w4", &gemm_w4_op<true>);
+    m.impl("mq_quantize_rows_mxfp8", &quantize_rows_mxfp8);
+    m.impl("mq_gemm_w4a8", &gemm_w4a8);
 }

@@ -7,7 +7,9 @@ weights (one power-of-two scale per output row) that the query path streams inst
 the bf16 copy is rewritten with the dequantised values, so every batch size embeds with the same model.  weight_precision="mxfp4" does the same with
 OCP MX FP4 copies (e2m1 codes, one e8m0 scale per 32 consecutive k: 4.25 bits per weight; csrc/gemm_small_w4.hip: W4A16).  weight_precision="mxfp4-only"
 keeps the MX FP4 copy ALONE: every block matrix is quantised on the device and its bf16 tensor dropped, batches too tall for the skinny kernel run the
-tiled W4A16 GEMM (csrc/gemm_w4.hip), and the block weights take 0.27 x their bf16 bytes.  The block is the Qwen tower's without q / k norm and without biases,
+tiled W4A16 GEMM (csrc/gemm_w4.hip), and the block weights take 0.27 x their bf16 bytes.  weight_precision="mxfp4-a8" loads and keeps exactly what
+"mxfp4-only" does; a batch too tall for the skinny kernel quantises each block GEMM's input rows to MX FP8 (e4m3 codes, one e8m0 scale per 32 k) and runs
+the W4A8 GEMM on the MX matrix instruction (csrc/gemm_w4a8.hip); shorter calls give "mxfp4-only"'s bits.  The block is the Qwen tower's without q / k norm and without biases,
 so the checkpoint-to-tensor transform (names, the fused QKV and (up | gate) weights) is engine/tower_weights.py::qwen_state_dict and the weight structs
 are the Qwen tower's."""
 from __future__ import annotations
@@ -31,8 +33,8 @@ class LlamaTower(_PackedTextTower):
 
     def __init__(self, arch: LlamaArch, sd: Dict[str, Tensor], device: str, pooling: str = "last", precision: str = "bf16", weight_precision: str = "bf16"):
         super().__init__(device)
-        if weight_precision not in ("bf16", "e4m3", "mxfp4", "mxfp4-only"):
-            raise ValueError(f"weight_precision must be 'bf16' or 'e4m3' or 'mxfp4' or 'mxfp4-only', got {weight_precision!r}")
+        if weight_precision not in ("bf16", "e4m3", "mxfp4", "mxfp4-only", "mxfp4-a8"):
+            raise ValueError(f"weight_precision must be 'bf16' or 'e4m3' or 'mxfp4' or 'mxfp4-only' or 'mxfp4-a8', got {weight_precision!r}")
         _check_precision(precision, ("bf16",), f"the Mistral / Llama tower runs on bf16 operands only (its RMSNorm / rotary / gated-SiLU blocks have no e4m3 "
                                                f"kernels), got precision {precision!r}")
         if arch.head_dim not in (64, 128):
@@ -51,8 +53,8 @@ class LlamaTower(_PackedTextTower):
         t = qwen_state_dict(arch, sd, tower="Mistral / Llama")
         W = arch.width
         self._layers = (L.QwenLayer * arch.layers)()
-        only = weight_precision == "mxfp4-only"
-        host = {}   # "mxfp4-only": the block matrices stay on the host until _quantize_mxfp4 takes them one at a time; the layers carry null pointers
+        only = weight_precision in ("mxfp4-only", "mxfp4-a8")
+        host = {}   # "mxfp4-only" / "mxfp4-a8": the block matrices stay on the host until _quantize_mxfp4 takes them one at a time; the layers carry null pointers
         for l in range(arch.layers):
             p = f"layers.{l}."
             a = p + "self_attn."
@@ -77,9 +79,9 @@ class LlamaTower(_PackedTextTower):
 
     def block_weight(self, layer: int, name: str) -> Tensor:
         """the bf16 device tensor of one block matrix ('qkv', 'out', 'ug', 'down') as the kernels read it (with weight_precision 'e4m3' / 'mxfp4': dequantised).
-        'mxfp4-only' holds no such tensor: the matrix is decoded on demand from the codes — mq_gemm_w4 on rows of the identity, every output one
+        'mxfp4-only' / 'mxfp4-a8' hold no such tensor: the matrix is decoded on demand from the codes — mq_gemm_w4 on rows of the identity, every output one
         product and therefore exact — into a fresh tensor (a test and debugging aid)"""
-        if self.weight_precision != "mxfp4-only":
+        if self.weight_precision not in ("mxfp4-only", "mxfp4-a8"):
             ptr = getattr(self._layers[layer], name + "_w")
             return next(t for t in self._h.tensors if t.data_ptr() == ptr)
         w4, sc, n, k = self._w4_blocks[layer, name]
@@ -153,3 +155,5 @@ class LlamaTower(_PackedTextTower):
                     setattr(self._w4_layers[l], name + "_scale", sc.data_ptr())
             torch.cuda.current_stream(self.device).synchronize()
         self._entry = ("mq_encode_llama_w4" if host is None else "mq_encode_llama_w4_only", (self._w4_layers,))
+        if self.weight_precision == "mxfp4-a8":   # the same resident tensors; the workspace also holds the MX FP8 copy of a GEMM's input rows
+            self._entry, self._workspace_query = ("mq_encode_llama_w4a8", (self._w4_layers,)), "mq_llama_w4a8_workspace_bytes"

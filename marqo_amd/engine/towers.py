@@ -1076,6 +1076,7 @@ class _PackedTextTower(_TextTowerBase):
     self.arch / self.cfg / self.w — and `family`, which names its two library functions."""
     family = ""        # "qwen": mq_encode_qwen, mq_qwen_workspace_bytes
     _entry = None      # (name, arguments behind the weights) of an encode entry point other than mq_encode_<family>
+    _workspace_query = None   # the name of a workspace query other than mq_<family>_workspace_bytes (an entry point with scratch of its own)
 
     @property
     def out_width(self) -> int:
@@ -1096,7 +1097,7 @@ class _PackedTextTower(_TextTowerBase):
         pooling reads one) -> fp32 [n, out_width] on the device."""
         ids_h, lengths = _ids_and_lengths(ids, attention_mask, self.arch.max_pos)
         name, extra = self._entry or (f"mq_encode_{self.family}", ())
-        ws_bytes, encode, tail = getattr(self.lib, f"mq_{self.family}_workspace_bytes"), getattr(self.lib, name), self._tail()
+        ws_bytes, encode, tail = getattr(self.lib, self._workspace_query or f"mq_{self.family}_workspace_bytes"), getattr(self.lib, name), self._tail()
         tower_l2 = 1 if normalize and tail is None else 0
         out = torch.empty(int(lengths.size), self.arch.width, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device), _large_call(self.device, int(lengths.sum())):

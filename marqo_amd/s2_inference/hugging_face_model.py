@@ -67,10 +67,11 @@ class HuggingFaceModelProperties:
         # engine extension (Mistral / Llama checkpoints): "e4m3" keeps an e4m3 copy of the block weights, one power-of-two scale per output row, that
         # single queries stream instead of the bf16 one (activations stay bf16; engine/llama.py); "mxfp4" keeps an OCP MX FP4 copy instead (e2m1 codes,
         # one e8m0 scale per 32 consecutive k: 4.25 bits per weight); "mxfp4-only" keeps the MX FP4 copy ALONE (no bf16 block matrix stays resident:
-        # 0.27 x the bf16 block-weight memory; batches too tall for the query kernel run the tiled W4A16 GEMM); every other family refuses these at load
+        # 0.27 x the bf16 block-weight memory; batches too tall for the query kernel run the tiled W4A16 GEMM); "mxfp4-a8" keeps what "mxfp4-only" keeps and
+        # runs those batches with MX FP8 activations on the MX matrix instruction (the W4A8 GEMM); every other family refuses these at load
         self.weight_precision: str = p.get("weightPrecision", p.get("weight_precision", "bf16"))
-        if self.weight_precision not in ("bf16", "e4m3", "mxfp4", "mxfp4-only"):
-            raise ValueError(f"'weightPrecision' must be 'bf16' or 'e4m3' or 'mxfp4' or 'mxfp4-only', got {self.weight_precision!r}")
+        if self.weight_precision not in ("bf16", "e4m3", "mxfp4", "mxfp4-only", "mxfp4-a8"):
+            raise ValueError(f"'weightPrecision' must be 'bf16' or 'e4m3' or 'mxfp4' or 'mxfp4-only' or 'mxfp4-a8', got {self.weight_precision!r}")
         b = p.get("fp8Budget", p.get("fp8_budget"))
         if b is not None and not (isinstance(b, (int, float)) and b > 0):
             raise ValueError("'fp8Budget' must be a positive number")
